@@ -2,10 +2,17 @@
 """Headline benchmark: ELBO sweeps per second at BASELINE config 3
 (N=4096 time stamps, p=3 outputs, q=2 nodes -> 8 latent GPs), fp64.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-calc] [--blocks B]]
 
 One "step" = one ELBOaux-equivalent sweep (meanfield.py:651-710) with the
-priors already factored, inputs resident in HBM.  With --gpus N > 1 the same
+priors already factored, inputs resident in HBM.  A plain run sets up, warms
+up, times exactly K steps and prints the headline; --full adds everything else
+the line used to carry (CPU baseline, full ELBOcalc, prediction, fill rates, the
+reference's golden first sweeps, the roofline of the bulk-update launches, the
+multi-GPU configs).  --dump-outputs DIR writes what the last timed call returned
+(per-sweep ELBO and its three parts) and the posterior state after it as
+DIR/<name>.npy, float64.  With --gpus N > 1 the same
 problem's latent GPs are sharded over N ranks, one per GPU
 (gpyrn_amd/sharding.py) -- strong scaling.  The ranks come either from a
 launcher that sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* (e.g.
@@ -14,7 +21,7 @@ script itself: before anything touches the GPU it starts N copies of itself as
 child processes, waits for them and relays rank 0's line.  Rank 0 prints one
 JSON line.  No torch import anywhere.
 
-The timed region is `--blocks` (default 5) blocks of exactly K steps, each
+The timed region is `--blocks` (default 1) blocks of exactly K steps, each
 bracketed by a barrier + device synchronisation and reduced with a MAX over the
 ranks; `value` is K / the median block, the spread is reported beside it.
 """
@@ -166,9 +173,13 @@ def cpu_baseline(N, p, q, kind):
            'blas': _blas_build(),
            'note': 'value: the BLAS picks its own thread count (OpenBLAS builds cap it, e.g. 64 on a 256-core box, where the '
                    'LU / Cholesky of a 4096 matrix scales badly); by_threads / best_threads: the same formulation with the BLAS held '
-                   'to 8, 16, 32 threads and its default -- divide by best_threads.value, not by value'}
+                   'to 8, 16, 32 threads (those not above the count it started with) and its default -- divide by '
+                   'best_threads.value, not by value'}
     try:
-        from threadpoolctl import threadpool_limits
+        from threadpoolctl import threadpool_info, threadpool_limits
+        # OpenBLAS sizes its buffers for the thread count it started with (OMP_NUM_THREADS and its like): a higher limit
+        # crashes it, so the BLAS is never held above that count
+        started = min([i['num_threads'] for i in threadpool_info() if i.get('user_api') == 'blas'] or [1])
         with threadpool_limits(limits=1):
             dt_1 = sweeps(1, 1, 1)
         out['one_thread'] = {'value': 1.0 / (dt_1 * G / 2), 'unit': 'sweeps/s', 'cores': 1,
@@ -178,7 +189,7 @@ def cpu_baseline(N, p, q, kind):
         # and 32 threads and at its default, each scaled by G / 2 (every latent GP costs the same in that formulation)
         by = {}
         for nt in (8, 16, 32, None):
-            if nt is not None and nt > (os.cpu_count() or 1):
+            if nt is not None and nt > started:
                 continue
             with threadpool_limits(limits=nt):
                 dt = sweeps(1, 1, 1)
@@ -518,11 +529,16 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', type=int, default=3)
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-calc', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the secondary figures: CPU baseline, full ELBOcalc, prediction, fill rates, golden first '
+                         'sweeps, roofline of the bulk-update launches, multi-GPU configs')
+    ap.add_argument('--no-cpu', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-calc', action='store_true', help='--full without the full ELBOcalc / prediction / pool legs')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the last timed call\'s outputs and the posterior state after it as DIR/<name>.npy')
     ap.add_argument('--shape', default=None,
                     help='N,p,q of an ad-hoc problem (experiments; not a BASELINE config)')
-    ap.add_argument('--blocks', type=int, default=20, help='timed blocks of --steps sweeps each')
+    ap.add_argument('--blocks', type=int, default=1, help='timed blocks of --steps sweeps each')
     ap.add_argument('--latency', action='store_true',
                     help='the small-N regime instead: nELBO evaluations/s at N = 45, 200, 497, 512, 2048 (one JSON line each)')
     ap.add_argument('--latency-reps', type=int, default=0, help='evaluations per shape (default 200, 40 at N = 2048)')
@@ -563,9 +579,9 @@ def main():
     g = gpyrn.inference(q, t, *[x for pair in zip(ys, es) for x in pair], comm=comm)
     g.set_components(nodes, weights, means, jit)
 
-    # the CPU baseline FIRST (rank 0 of a one-rank run only; ~3 min at config 3): the timed GPU blocks are then the last
-    # thing the command does, where a utilisation sampler watching the run can see them
-    cpu = cpu_baseline(N, p, q, kind) if (world == 1 and rank == 0 and not a.no_cpu) else None
+    # --full: the CPU baseline FIRST (rank 0 of a one-rank run only; ~3 min at config 3): the timed GPU blocks are then the
+    # last thing the command does, where a utilisation sampler watching the run can see them
+    cpu = cpu_baseline(N, p, q, kind) if (a.full and world == 1 and rank == 0 and not a.no_cpu) else None
 
     t0 = time.time()
     ctx = g._setup_device(nodes, weights, means, jit)     # fill + chol(K): once per ELBOcalc
@@ -579,7 +595,7 @@ def main():
     # fills + chol(K) + inverses + the reference's own trip count (discarded sweep + loop to the
     # stop rule), allocations warm.  Same control flow on every rank (the ELBO is all-reduced).
     calc = None
-    if not a.no_calc:
+    if a.full and not a.no_calc:
         times, trips = [], []
         for rep in range(2):
             for j, node in enumerate(nodes):
@@ -610,7 +626,7 @@ def main():
     # populations, emcee walkers), every rank with the whole problem on its own GPU, no
     # exchange -- aggregate full ELBOcalc evaluations per second over all ranks (weak scaling).
     pool = None
-    if world > 1 and not a.no_calc:
+    if a.full and world > 1 and not a.no_calc:
         local_dev = comm.local_rank % max(1, _hip.device_count())
         g1 = gpyrn.inference(q, t, *[x for pair in zip(ys, es) for x in pair], device=local_dev)
         n1, w1, m1, j1 = synth.build_components(covfunc, meanfunc, spec)
@@ -627,16 +643,20 @@ def main():
         pool = {'elbocalc_per_s_all_ranks': world * reps / dt_pool, 'ms_per_elbocalc': 1e3 * dt_pool / reps,
                 'scaling': 'weak', 'note': 'one independent full ELBOcalc stream per rank'}
 
-    # ---- the headline: timed blocks of forced sweeps, last (the secondary metrics above changed the hyper-parameters:
-    # back to the configuration's own)
-    nodes, weights, means, jit = synth.build_components(covfunc, meanfunc, spec)
-    g.set_components(nodes, weights, means, jit)
-    ctx = g._setup_device(nodes, weights, means, jit)
-    ctx.set_muvar(mu0, var0)
-    golden = golden_check(ctx, a, N, p, q, t, ys) if world == 1 else None
+    # ---- the headline: timed blocks of forced sweeps, last (the full ELBOcalc above changed the hyper-parameters: back to
+    # the configuration's own)
+    if calc is not None:
+        nodes, weights, means, jit = synth.build_components(covfunc, meanfunc, spec)
+        g.set_components(nodes, weights, means, jit)
+        ctx = g._setup_device(nodes, weights, means, jit)
+        ctx.set_muvar(mu0, var0)
+    golden = golden_check(ctx, a, N, p, q, t, ys) if (a.full and world == 1) else None
+    if golden is None:
+        ctx.sweep(1, commit=False)        # the sweep's code objects and buffers, state untouched (golden_check does this too)
     if a.warmup > 0:
         ctx.sweep(a.warmup, commit=True)
-    ctx.profile_enable(['update', 'update_ahead'])
+    if a.full:
+        ctx.profile_enable(['update', 'update_ahead'])
     block_s = []
     for _ in range(max(1, a.blocks)):
         ctx.barrier_max(0.0)                               # barrier + device sync
@@ -645,29 +665,27 @@ def main():
         dt_local = time.perf_counter() - t0
         block_s.append(ctx.barrier_max(dt_local))          # MAX over ranks
     dt = float(np.median(block_s))
-    prof = ctx.profile_read()
-    ctx.profile_enable([])
+    if a.full:
+        prof = ctx.profile_read()
+        ctx.profile_enable([])
+    if a.dump_outputs and rank == 0:
+        # what the timed call returned (every sweep's ELBO and its parts LogL, LogP, Ent) and the state its last sweep left
+        mu, var = ctx.get_muvar()
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in (('elbo', elbo), ('parts', parts), ('mu', mu), ('var', var)):
+            np.save(os.path.join(a.dump_outputs, name + '.npy'), np.asarray(arr, dtype=np.float64))
 
     # BASELINE's multi-GPU configs in their stated topologies (config 4: 4 GPUs, config 5: 8 GPUs) ride along with the
     # config-3 strong-scaling headline of a run that has exactly that many ranks
     extra = {}
     also = a.also_config if a.also_config is not None else {4: '4', 8: '5'}.get(world, 'none')
-    if world > 1 and also != 'none' and not a.shape:
+    if a.full and world > 1 and also != 'none' and not a.shape:
         cfg_s, _, n_s = also.partition(':')
         blk = config_in_topology(int(cfg_s), world, rank, n_override=int(n_s) if n_s else None)
         if rank == 0:
             extra['config %s on %d ranks' % (cfg_s, world)] = blk
 
     if rank == 0:
-        nodes_l, weights_l = sharding.local_gps(p, q, world, 0)
-        ms_upd, n_upd = prof['update']
-        ms_ahd, n_ahd = prof.get('update_ahead', (0.0, 0))
-        T = (N + TILE - 1) // TILE
-        split = T <= 64                                             # csrc/factor.hip: "rest" in two launches up to 64 tile steps
-        per_sweep = update_flops(T, len(nodes_l) + len(weights_l), split=split)
-        fl, fl_ahd = (x * a.steps * len(block_s) for x in per_sweep[:2])
-        uni = k512_union() if world == 1 and a.config == 3 and not a.shape else None
-        achieved = fl / (ms_upd * 1e-3) / 1e12 if ms_upd > 0 else None
         out = {
             'metric': 'ELBO iterations/sec (N=%d, P=%d, Q=%d)' % (N, p, q),
             'value': a.steps / dt,
@@ -693,53 +711,65 @@ def main():
             # the G fused Cholesky + triangular-inverse factorisations (+ q-1 X^T X products); this is
             # that flop count over the whole sweep time, O(N^2) kernels and exchanges included.
             'cholesky_gflops': sweep_flops(N, p, q) * a.steps / dt / 1e9,
-            # fused covariance fill at setup: 8 N^2 bytes written per matrix, against the HBM peak
-            # (it is fp64-VALU-bound, not HBM-bound: a division and exp/sin per element)
-            # (kernel_GBps: the launches back to back inside one event bracket -- the rate the kernels run at; GBps: every
-            # launch bracketed by its own pair of events, gaps included)
-            'fill': ({'kernel_GBps': (n_fill * 8.0 * N * N / (ms_fill_pass * 1e-3) / 1e9) if ms_fill_pass > 0 else None,
-                      'kernel_frac': (n_fill * 8.0 * N * N / (ms_fill_pass * 1e-3) / 1e9 / HBM_PEAK_GBPS) if ms_fill_pass > 0 else None,
-                      'GBps': n_fill * 8.0 * N * N / (ms_fill * 1e-3) / 1e9, 'launches': n_fill,
-                      'peak_GBps': HBM_PEAK_GBPS,
-                      'frac': n_fill * 8.0 * N * N / (ms_fill * 1e-3) / 1e9 / HBM_PEAK_GBPS}
-                     if ms_fill > 0 else None),
             'setup_s': t_setup,
-            'full_elbocalc': calc,
-            'independent_evaluations': pool,
-            # the first sweeps against the reference's recorded values for this workload (golden_check), then the ELBO the
-            # timed blocks ended on
-            'golden_check': golden,
+            # the ELBO the timed blocks ended on
             'elbo_last': float(elbo[-1]), 'info': int(info),
             # which schedule produced the line: 1 = device-side flags (the default), 0 = HIP events; fallbacks = calls of this
             # context that were re-run on events after an in-kernel wait timed out (0 in a healthy run)
             'schedule': {'flags': int(ctx.option('flags')), 'fallbacks': int(ctx.option('fallbacks'))},
-            'roofline': {
-                'kernel': 'k_tile_gemm<..., TG_BULK> (bulk trailing-update launches, K=512, v_mfma_f64_16x16x4_f64)',
-                'bound': 'mfma', 'achieved': achieved, 'peak': FP64_MFMA_PEAK_TFLOPS,
-                'unit': 'TFLOP/s',
-                'frac': (achieved / FP64_MFMA_PEAK_TFLOPS) if achieved else None,
-                'traffic': pmc_traffic() if world == 1 and a.config == 3 and not a.shape else None,
-                'pmc': pmc_mfma() if world == 1 and a.config == 3 and not a.shape else None,
-                'measured_mfma_ceiling': ctx.mfma_peak(2, 4000),
-                # the whole sweep against the same peak (every kernel, wait and O(N^2) step included)
-                'sweep_frac': sweep_flops(N, p, q) * a.steps / dt / 1e12 / FP64_MFMA_PEAK_TFLOPS,
-                # rate of ALL K = 512 launches (next-panel + look-ahead + bulk) over the time at least one of them was
-                # open, from the committed kernel trace: a launch's own rate divides by the time it is open, during which
-                # up to three other streams' kernels share the CUs with it
-                'k512_union': ({'tflops': sum(per_sweep) / (uni['k512_union_us_per_sweep'] * 1e-6) / 1e12,
-                                'union_us_per_sweep': uni['k512_union_us_per_sweep'],
-                                'bulk_ahead_tflops': (per_sweep[0] + per_sweep[1]) / (uni['bulk_ahead_union_us_per_sweep'] * 1e-6) / 1e12,
-                                'source': uni.get('source')} if uni else None),
-                'launches': n_upd, 'avg_launch_ms': (ms_upd / n_upd) if n_upd else None,
-                'flops_per_launch': (fl / n_upd) if n_upd else None,
-                # the look-ahead part of the same updates (own launches, k_tile_gemm<..., TG_AHEAD>: the tiles the
-                # next panel's update writes again; they run beside that panel's "next" launch)
-                'ahead_launches': ({'launches': n_ahd, 'avg_launch_ms': ms_ahd / n_ahd, 'flops_per_launch': fl_ahd / n_ahd,
-                                    'achieved': fl_ahd / (ms_ahd * 1e-3) / 1e12} if n_ahd else None),
-            },
         }
-        out['configs_at_n_gpus'] = extra or None
-        out['cpu_baseline'] = cpu
+        if a.full:
+            nodes_l, weights_l = sharding.local_gps(p, q, world, 0)
+            ms_upd, n_upd = prof['update']
+            ms_ahd, n_ahd = prof.get('update_ahead', (0.0, 0))
+            T = (N + TILE - 1) // TILE
+            split = T <= 64                                         # csrc/factor.hip: "rest" in two launches up to 64 tile steps
+            per_sweep = update_flops(T, len(nodes_l) + len(weights_l), split=split)
+            fl, fl_ahd = (x * a.steps * len(block_s) for x in per_sweep[:2])
+            uni = k512_union() if world == 1 and a.config == 3 and not a.shape else None
+            achieved = fl / (ms_upd * 1e-3) / 1e12 if ms_upd > 0 else None
+            out.update({
+                # fused covariance fill at setup: 8 N^2 bytes written per matrix, against the HBM peak
+                # (it is fp64-VALU-bound, not HBM-bound: a division and exp/sin per element)
+                # (kernel_GBps: the launches back to back inside one event bracket -- the rate the kernels run at; GBps: every
+                # launch bracketed by its own pair of events, gaps included)
+                'fill': ({'kernel_GBps': (n_fill * 8.0 * N * N / (ms_fill_pass * 1e-3) / 1e9) if ms_fill_pass > 0 else None,
+                          'kernel_frac': (n_fill * 8.0 * N * N / (ms_fill_pass * 1e-3) / 1e9 / HBM_PEAK_GBPS) if ms_fill_pass > 0 else None,
+                          'GBps': n_fill * 8.0 * N * N / (ms_fill * 1e-3) / 1e9, 'launches': n_fill,
+                          'peak_GBps': HBM_PEAK_GBPS,
+                          'frac': n_fill * 8.0 * N * N / (ms_fill * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+                         if ms_fill > 0 else None),
+                'full_elbocalc': calc,
+                'independent_evaluations': pool,
+                # the first sweeps against the reference's recorded values for this workload (golden_check)
+                'golden_check': golden,
+                'roofline': {
+                    'kernel': 'k_tile_gemm<..., TG_BULK> (bulk trailing-update launches, K=512, v_mfma_f64_16x16x4_f64)',
+                    'bound': 'mfma', 'achieved': achieved, 'peak': FP64_MFMA_PEAK_TFLOPS,
+                    'unit': 'TFLOP/s',
+                    'frac': (achieved / FP64_MFMA_PEAK_TFLOPS) if achieved else None,
+                    'traffic': pmc_traffic() if world == 1 and a.config == 3 and not a.shape else None,
+                    'pmc': pmc_mfma() if world == 1 and a.config == 3 and not a.shape else None,
+                    'measured_mfma_ceiling': ctx.mfma_peak(2, 4000),
+                    # the whole sweep against the same peak (every kernel, wait and O(N^2) step included)
+                    'sweep_frac': sweep_flops(N, p, q) * a.steps / dt / 1e12 / FP64_MFMA_PEAK_TFLOPS,
+                    # rate of ALL K = 512 launches (next-panel + look-ahead + bulk) over the time at least one of them was
+                    # open, from the committed kernel trace: a launch's own rate divides by the time it is open, during which
+                    # up to three other streams' kernels share the CUs with it
+                    'k512_union': ({'tflops': sum(per_sweep) / (uni['k512_union_us_per_sweep'] * 1e-6) / 1e12,
+                                    'union_us_per_sweep': uni['k512_union_us_per_sweep'],
+                                    'bulk_ahead_tflops': (per_sweep[0] + per_sweep[1]) / (uni['bulk_ahead_union_us_per_sweep'] * 1e-6) / 1e12,
+                                    'source': uni.get('source')} if uni else None),
+                    'launches': n_upd, 'avg_launch_ms': (ms_upd / n_upd) if n_upd else None,
+                    'flops_per_launch': (fl / n_upd) if n_upd else None,
+                    # the look-ahead part of the same updates (own launches, k_tile_gemm<..., TG_AHEAD>: the tiles the
+                    # next panel's update writes again; they run beside that panel's "next" launch)
+                    'ahead_launches': ({'launches': n_ahd, 'avg_launch_ms': ms_ahd / n_ahd, 'flops_per_launch': fl_ahd / n_ahd,
+                                        'achieved': fl_ahd / (ms_ahd * 1e-3) / 1e12} if n_ahd else None),
+                },
+                'configs_at_n_gpus': extra or None,
+                'cpu_baseline': cpu,
+            })
         print(json.dumps(out), flush=True)
     if comm is not None:
         ctx.barrier_max(0.0)

@@ -1,5 +1,6 @@
-"""The real-data path: loader for the reference's solar table, pinned by the
-per-column sums and end rows recorded from the file itself (tests/golden/solar.json)."""
+"""The real-data path: loader for the reference's solar table (a copy of the data file is kept as
+tests/golden/Solar_observations.txt), pinned by the per-column sums and end rows recorded from the file itself
+(tests/golden/solar.json)."""
 import json
 import os
 
@@ -9,7 +10,7 @@ import pytest
 from gpyrn_amd import datasets
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'solar.json')
-REF_FILE = '/root/reference/gpyrn/datasets/Solar_observations.txt'
+REF_FILE = os.path.join(os.path.dirname(GOLDEN), datasets.SOLAR_FILE)
 
 
 def _write_table(path, header, rows):
@@ -45,7 +46,6 @@ def test_wrong_table_is_refused(tmp_path):
         datasets.load_solar(str(p))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FILE), reason='the reference tree is not on this box')
 def test_solar_table_of_the_reference():
     with open(GOLDEN) as f:
         want = json.load(f)

@@ -142,11 +142,35 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _spawn(world, *args, timeout_s=900):
+    """`_worker(rank, world, *args)` in one fresh process per rank; the first rank to fail stops the others.  torch is
+    imported in those processes only: where the GPU tests of the same session have loaded libgprn_hip.so, importing torch
+    maps torch's own HIP and HSA runtimes beside the system ones, and the process aborts at exit."""
+    import multiprocessing
+    import time
+    ctx = multiprocessing.get_context('spawn')
+    procs = [ctx.Process(target=_worker, args=(r, world) + args) for r in range(world)]
+    for pr in procs:
+        pr.start()
+    deadline = time.time() + timeout_s
+    try:
+        while any(pr.exitcode is None for pr in procs):
+            if any(pr.exitcode not in (None, 0) for pr in procs) or time.time() > deadline:
+                break
+            time.sleep(0.1)
+    finally:
+        for pr in procs:
+            if pr.exitcode is None:
+                pr.terminate()
+            pr.join()
+    codes = [pr.exitcode for pr in procs]
+    assert codes == [0] * world, f'rank exit codes {codes}'
+
+
 @pytest.mark.parametrize('tag', ['step_p3q2', 'step_p2q3'])
 def test_two_ranks_gloo_match_unsharded(tag, tmp_path):
-    import torch.multiprocessing as mp
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), tag, str(tmp_path)), nprocs=world, join=True)
+    _spawn(world, _free_port(), tag, str(tmp_path))
     meta, d = _cases.load(tag)
     r0 = np.load(tmp_path / 'rank0.npz')
     r1 = np.load(tmp_path / 'rank1.npz')
@@ -171,7 +195,6 @@ def test_eight_ranks_gloo_config5_partition(tmp_path):
     the oracle's per-GP arithmetic, at the size the reference itself was run (cfg5shape_N1024).  Five ranks own no node,
     seven ranks own two latent GPs and one a single weight, only ranks 0 and 1 refactor a later node's K_j (quirk Q1); every rank must end
     with the reference's two sweeps."""
-    import torch.multiprocessing as mp
     tag, world = 'cfg5shape_N1024', 8
     meta, d = _cases.load(tag)
     p, q = meta['p'], meta['q']
@@ -182,7 +205,7 @@ def test_eight_ranks_gloo_config5_partition(tmp_path):
     assert [bool(sharding.helper_inverses(p, q, world, r)) for r in range(world)] == [True, True] + [False] * 6
     os.environ['OMP_NUM_THREADS'] = os.environ['OPENBLAS_NUM_THREADS'] = '1'     # (eight processes on the container's eight cores)
     try:
-        mp.spawn(_worker, args=(world, _free_port(), tag, str(tmp_path)), nprocs=world, join=True)
+        _spawn(world, _free_port(), tag, str(tmp_path))
     finally:
         os.environ.pop('OMP_NUM_THREADS', None); os.environ.pop('OPENBLAS_NUM_THREADS', None)
     res = [np.load(tmp_path / f'rank{r}.npz') for r in range(world)]
