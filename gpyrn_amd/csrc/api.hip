@@ -244,7 +244,6 @@ static void free_problem(gprn_ctx* c)
     if (c->d_fin_tickets) hipFree(c->d_fin_tickets);
     c->d_fin_terms = nullptr; c->d_fin_tickets = nullptr;
     dev_free(c->d_scal_base); c->d_scal = nullptr; dev_free(c->d_elbo_part); dev_free(c->d_out); dev_free(c->d_info);
-    c->d_ptrs = nullptr;
     c->nslot = 0; c->out_cap = 0;
     c->factored = c->have_yres = c->have_jit = c->have_muvar = false;
     c->tables_ready = false;
@@ -418,10 +417,6 @@ extern "C" int gprn_set_data(gprn_ctx* c, int N, int p, int q, const double* tim
     HIP_TRY(c, hipMemset(c->d_scal_base, 0, 2 * (size_t)(3 * c->G + q * q) * sizeof(double)));
     TRY(dev_alloc(c, &c->d_elbo_part, 2 * (size_t)GPRN_ELBO_PART_DOUBLES));
     c->d_scal = c->d_scal_base;
-    c->d_logdetB = c->d_scal;
-    c->d_trBinv = c->d_scal + c->G;
-    c->d_muKmu = c->d_scal + 2 * c->G;
-    c->d_q1 = c->d_scal + 3 * c->G;
     std::vector<double> e2(pn);
     for (size_t i = 0; i < pn; ++i) e2[i] = yerr[i] * yerr[i];
     HIP_TRY(c, hipMemcpy(c->d_time, time, N * sizeof(double), hipMemcpyHostToDevice));
@@ -851,11 +846,11 @@ int exchange_rows(gprn_ctx* c, bool weights)
     return GPRN_OK;
 }
 
-int reduce_scalars(gprn_ctx* c)
+int reduce_scalars(gprn_ctx* c, double* scal)
 {
     if (!comm_active(c)) return GPRN_OK;
     const size_t n = 3 * (size_t)c->G + (size_t)c->q * c->q;
-    return comm_allreduce(c, c->d_scal, n, false);
+    return comm_allreduce(c, scal, n, false);
 }
 
 // ------------------------------------------------------------------ tables

@@ -155,7 +155,7 @@ static inline void watch_progress(gprn_ctx* c)
 // ---- defined in api.hip
 int comm_group(gprn_ctx* c, bool begin);     // ncclGroupStart / End around several broadcasts
 int exchange_rows(gprn_ctx* c, bool weights);
-int reduce_scalars(gprn_ctx* c);
+int reduce_scalars(gprn_ctx* c, double* scal);     // all-reduce of a sweep's scalars (one copy of d_scal_base)
 int upload_table(gprn_ctx* c, double** d_tab, const std::vector<double*>& rows);
 int build_tables(gprn_ctx* c);
 int check_info(gprn_ctx* c, const int* d_info, const std::vector<int>& gps, int* first);

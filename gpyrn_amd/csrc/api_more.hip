@@ -101,6 +101,7 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
     std::vector<TileTask> tasks;
     std::vector<double> hm, hv, pad;
     const bool gather = comm_active(c);
+    const Phase pred = problem_phase(c, c->tab_pred, c->d_slotgp_all, nloc, 0, c->d_info);
     auto row_of = [&](int g) {
         if (g < c->q) return g;
         const int kk = g - c->q, j = kk / c->p, i = kk % c->p;
@@ -149,12 +150,9 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
             PHIP(hipMemcpy(d_kss + (size_t)s * ns_pad, pad.data(), ns_pad * sizeof(double), hipMemcpyHostToDevice));
         }
         PHIP(hipMemsetAsync(c->d_info, 0, 3 * (size_t)c->nslot * sizeof(int), c->stream));
-        c->d_ptrs = c->tab_pred;
-        c->slot0 = 0;
-        c->d_info_cur = c->d_info;
-        PTRY(factor_invert(c, nloc, true));
-        PTRY(vec_lower_matvec(c, BUF_X, c->d_mu, N, 1, c->d_slotgp_all, nloc, c->d_u));   // u = X mu
-        PTRY(vec_colops(c, nloc));                                                          // ct = X^T u
+        PTRY(factor_invert(c, pred, true));
+        PTRY(vec_lower_matvec(c, pred, BUF_X, c->d_mu, N, 1, c->d_u));   // u = X mu
+        PTRY(vec_colops(c, pred));                                        // ct = X^T u
         for (int bt = 0; bt < ns_pad / GPRN_TILE; ++bt)
             for (int at = 0; at < T; ++at)
                 tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE,
@@ -163,8 +161,8 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
                                          tile_modes(CM_SET, 0, 0)});
         PTRY(dev_alloc(c, &d_t, tasks.size()));
         PHIP(hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
-        PTRY(launch_tiles(c, d_t, tasks.size(), c->d_ptrs, nloc, ld, GPRN_T_UPDATE));
-        PTRY(vec_pred_rows(c, nloc, ns, ns_pad, c->d_ct, d_kss, d_mean, d_pvar));
+        PTRY(launch_tiles(c, d_t, tasks.size(), pred.ptrs, nloc, ld, GPRN_T_UPDATE));
+        PTRY(vec_pred_rows(c, pred, ns, ns_pad, c->d_ct, d_kss, d_mean, d_pvar));
     }
     if (gather) {
         // every rank ends up with every latent GP's rows: the owners' results travel as one grouped broadcast
@@ -267,8 +265,7 @@ static int sample_prior_impl(gprn_ctx* c, const KernelSpec& ks, double nugget, i
     if (!rc) rc = dev_alloc(c, &d_i, 1);
     if (!rc) rc = dev_alloc(c, &d_z, (size_t)n_samples * ld);
     if (!rc) rc = dev_alloc(c, &d_o, (size_t)n_samples * ld);
-    double** const sptrs = c->d_ptrs;
-    int* const sinfo = c->d_info_cur;
+    const Phase one = problem_phase(c, d_p, nullptr, 1, 0, d_i);
     int info0 = 0;
     hipError_t e = hipSuccess;
     if (!rc) {
@@ -280,10 +277,9 @@ static int sample_prior_impl(gprn_ctx* c, const KernelSpec& ks, double nugget, i
         if (e == hipSuccess) e = hipMemcpy2D(d_z, (size_t)ld * sizeof(double), z, (size_t)N * sizeof(double),
                                              (size_t)N * sizeof(double), n_samples, hipMemcpyHostToDevice);
         if (e == hipSuccess) rc = launch_fill(c, ks, c->d_test[0], nugget);
-        c->d_ptrs = d_p; c->d_info_cur = d_i;
-        if (e == hipSuccess && !rc) rc = factor_invert(c, 1, true);
+        if (e == hipSuccess && !rc) rc = factor_invert(c, one, true);
         for (int s = 0; s < n_samples && e == hipSuccess && !rc; ++s)     // L z: row i of lower(B) . z
-            rc = vec_lower_matvec(c, BUF_B, d_z + (size_t)s * ld, 0, 0, nullptr, 1, d_o + (size_t)s * ld);
+            rc = vec_lower_matvec(c, one, BUF_B, d_z + (size_t)s * ld, 0, 0, d_o + (size_t)s * ld);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess && !rc) rc = factor_check_waits(c);
         if (e == hipSuccess && !rc) e = hipMemcpy(&info0, d_i, sizeof(int), hipMemcpyDeviceToHost);
@@ -291,7 +287,6 @@ static int sample_prior_impl(gprn_ctx* c, const KernelSpec& ks, double nugget, i
             e = hipMemcpy2D(out, (size_t)N * sizeof(double), d_o, (size_t)ld * sizeof(double),
                             (size_t)N * sizeof(double), n_samples, hipMemcpyDeviceToHost);
     }
-    c->d_ptrs = sptrs; c->d_info_cur = sinfo;
     if (d_p) { tab_forget(c, d_p); hipFree(d_p); }
     if (d_i) hipFree(d_i);
     if (d_z) hipFree(d_z);
@@ -309,7 +304,7 @@ extern "C" int gprn_sample_prior(gprn_ctx* c, const int32_t* ops, int n_ops, con
     HIP_TRY(c, hipSetDevice(c->device));
     KernelSpec ks;
     TRY(spec_from_args(c, ks, ops, n_ops, params, n_params, nugget != 0.0));
-    TRY(ensure_tasks(c));
+    TRY(ensure_tasks(c, c->T));
     return with_event_fallback(c, "sample_prior", [&](bool) { return sample_prior_impl(c, ks, nugget, n_samples, z, out); });
 }
 
@@ -358,10 +353,7 @@ static int grad_impl(gprn_ctx* c, int gp, double* Kinv_out, double* P_out, const
     if (!rc) e = hipMemcpy(d_p, hp, sizeof(hp), hipMemcpyHostToDevice);
     // (1) K^-1 = lower(X^T X), X = L_K^-1: the X^T X task list (BUF_X -> BUF_B); then mirror it to the upper
     // triangle so that the two products below read plain full tiles
-    if (!rc && e == hipSuccess) rc = ensure_tasks(c);
-    double** const sptrs = c->d_ptrs;
-    c->d_ptrs = d_p;
-    if (!rc && e == hipSuccess) rc = lauum_lower(c, 1);
+    if (!rc && e == hipSuccess) rc = lauum_lower(c, problem_phase(c, d_p, nullptr, 1, 0, nullptr));
     if (!rc && e == hipSuccess) rc = vec_symmetrize(c, dKinv);
     // (2) C1 = -K^-1 S, all T x T tiles, K = ld
     for (int i = 0; i < T; ++i)
@@ -377,7 +369,6 @@ static int grad_impl(gprn_ctx* c, int gp, double* Kinv_out, double* P_out, const
         e = hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream);
     if (!rc && e == hipSuccess) rc = launch_tiles(c, d_t, n1, d_p, 1, ld, GPRN_T_UPDATE);
     if (!rc && e == hipSuccess) rc = launch_tiles(c, d_t + n1, tasks.size() - n1, d_p, 1, ld, GPRN_T_UPDATE);
-    c->d_ptrs = sptrs;
     if (kernel_grad) {
         // slot 1's X workspace is free: [0, ld) the mean vector, [ld, 2 ld) a = K^-1 m, then the per-row partial sums
         const KernelSpec& ks = c->kspec[gp];
@@ -518,9 +509,6 @@ extern "C" int gprn_prior_terms(gprn_ctx* c, int gp, const double* S, const doub
     int rc = dev_alloc(c, &d_t, tasks.size());
     if (!rc) rc = dev_alloc(c, &d_m, 3 * (size_t)ld + 4);
     hipError_t e = hipSuccess;
-    double** const sptrs = c->d_ptrs;
-    const int sslot0 = c->slot0;
-    const EvalMap sev = c->ev;
     if (!rc) e = hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream);
     if (!rc && e == hipSuccess) rc = launch_tiles(c, d_t, tasks.size(), tab, 1, ld, GPRN_T_UPDATE);
     if (!rc && e == hipSuccess) {
@@ -536,10 +524,10 @@ extern "C" int gprn_prior_terms(gprn_ctx* c, int gp, const double* S, const doub
         int* d_zero = nullptr;
         rc = dev_alloc(c, &d_zero, 1);
         if (!rc) e = hipMemcpyAsync(d_zero, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream);
-        c->d_ptrs = tab; c->slot0 = 0; c->ev = EvalMap{nullptr, 0, 0, 0, 0};
-        if (!rc && e == hipSuccess) rc = vec_lower_matvec(c, BUF_KLINV, d_m, 0, 0, d_zero, 1, d_m + 2 * (size_t)ld);
         // (one slot, "latent GP 0": the scalar lands at d_m[3 ld])
-        if (!rc && e == hipSuccess) rc = vec_dot_self(c, d_zero, 1, d_m + 2 * (size_t)ld, d_m + 3 * (size_t)ld);
+        const Phase one = problem_phase(c, tab, d_zero, 1, 0, nullptr);
+        if (!rc && e == hipSuccess) rc = vec_lower_matvec(c, one, BUF_KLINV, d_m, 0, 0, d_m + 2 * (size_t)ld);
+        if (!rc && e == hipSuccess) rc = vec_dot_self(c, one, d_m + 2 * (size_t)ld, d_m + 3 * (size_t)ld);
         if (!rc && e == hipSuccess) {
             std::vector<double> rows(N);
             e = hipMemcpyAsync(rows.data(), d_m + ld, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -548,7 +536,6 @@ extern "C" int gprn_prior_terms(gprn_ctx* c, int gp, const double* S, const doub
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             for (int i = 0; i < N; ++i) h[2] += rows[i];
         }
-        c->d_ptrs = sptrs; c->slot0 = sslot0; c->ev = sev;
         if (d_zero) hipFree(d_zero);
     }
     if (d_t) hipFree(d_t);
@@ -715,7 +702,7 @@ extern "C" int gprn_test_fill_rate(gprn_ctx* c, int reps, double* ms)
     return rc;
 }
 
-// run the library's own factorisation on caller matrices: temporarily a tiny "problem"
+// run the library's own factorisation on caller matrices: a phase of `batch` n x n matrices
 static int test_factor_impl(gprn_ctx* c, int n, int batch, const double* A, double* L,
                             double* Linv, bool lauum, double* lauum_out);
 
@@ -734,11 +721,6 @@ static int test_factor_impl(gprn_ctx* c, int n, int batch, const double* A, doub
     const size_t nn = (size_t)n * n;
     HIP_TRY(c, hipMemcpy(c->d_test[0], A, nn * batch * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(c->d_test[1], 0, nn * batch * sizeof(double)));
-    // borrow the context's factorisation state
-    const int sN = c->N, sld = c->ld, sT = c->T, stT = c->tasks_T;
-    double** sptrs = c->d_ptrs;
-    int* sinfo = c->d_info_cur;
-    c->N = n; c->ld = n; c->T = n / GPRN_TILE;
     double** d_p = nullptr;
     int* d_i = nullptr;
     int rc = dev_alloc(c, &d_p, (size_t)batch * GPRN_NBUF);
@@ -754,13 +736,12 @@ static int test_factor_impl(gprn_ctx* c, int n, int batch, const double* A, doub
         e = hipMemcpy(d_p, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice);
         if (e == hipSuccess) tab_note(c, d_p, hp.data(), hp.size());
         if (e == hipSuccess) e = hipMemset(d_i, 0, batch * sizeof(int));
-        c->d_ptrs = d_p; c->d_info_cur = d_i;
-        c->tasks_T = -1;                       // force a task rebuild for this n
-        if (e == hipSuccess) rc = lauum ? GPRN_OK : factor_invert(c, batch);
+        const Phase ph{d_p, nullptr, batch, 0, d_i, EvalMap{nullptr, 0, 0, 0, 0}, n, n, n / GPRN_TILE};
+        if (e == hipSuccess) rc = lauum ? GPRN_OK : factor_invert(c, ph);
         if (lauum && e == hipSuccess) {
             // X := A (lower), out -> BUF_B
             e = hipMemcpy(c->d_test[1], A, nn * sizeof(double), hipMemcpyHostToDevice);
-            if (e == hipSuccess) rc = lauum_lower(c, 1);
+            if (e == hipSuccess) rc = lauum_lower(c, ph);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess && !rc) rc = factor_check_waits(c);
@@ -778,9 +759,6 @@ static int test_factor_impl(gprn_ctx* c, int n, int batch, const double* A, doub
     }
     if (d_p) { tab_forget(c, d_p); hipFree(d_p); }
     if (d_i) hipFree(d_i);
-    c->N = sN; c->ld = sld; c->T = sT; c->d_ptrs = sptrs; c->d_info_cur = sinfo;
-    c->tasks_T = -1;                           // the problem's own lists are rebuilt on demand
-    (void)stT;
     if (rc) return rc;
     HIP_TRY(c, e);
     return info0;

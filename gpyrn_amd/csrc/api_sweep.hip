@@ -96,7 +96,7 @@ static int factor_priors_small(gprn_ctx* c, bool sync = true)
 static int factor_priors_single(gprn_ctx* c)
 {
     TRY(build_tables(c));
-    TRY(ensure_tasks(c));
+    TRY(ensure_tasks(c, c->T));
     c->small_tabs_ready = false;
     c->small_sweep_ready = false;
     c->info_gp = -1;
@@ -134,16 +134,10 @@ static int factor_priors_single(gprn_ctx* c)
         HIP_TRY(c, hipMemcpyAsync(c->wsB[s], c->K[g], nn * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(c, hipMemsetAsync(c->d_info, 0, 3 * (size_t)c->nslot * sizeof(int), c->stream));
-    c->d_ptrs = c->tab_setup;
-    c->slot0 = 0;
-    c->d_info_cur = c->d_info;
-    TRY(factor_invert(c, nb, true));
-    TRY(vec_logdet(c, BUF_B, c->d_slotgp_setup, nb, c->d_logdetK));
-    if (n_inv > 0) {
-        c->d_ptrs = c->tab_kinv1;
-        TRY(lauum_lower(c, n_inv));
-        c->d_ptrs = c->tab_setup;
-    }
+    const Phase setup = problem_phase(c, c->tab_setup, c->d_slotgp_setup, nb, 0, c->d_info);
+    TRY(factor_invert(c, setup, true));
+    TRY(vec_logdet(c, setup, BUF_B, c->d_logdetK));
+    if (n_inv > 0) TRY(lauum_lower(c, problem_phase(c, c->tab_kinv1, nullptr, n_inv, 0, nullptr)));
     int first_info = 0;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);          // (the one wait of the call; the null stream's copy below does not
     TRY(check_info(c, c->d_info, gps, &first_info));      // wait for the library's non-blocking streams by itself)
@@ -157,7 +151,7 @@ static int factor_priors_impl(gprn_ctx* c)
     if (small_applies(c) && c->world == 1) return factor_priors_small(c);
     if (!comm_active(c) && c->world == 1) return factor_priors_single(c);
     TRY(build_tables(c));
-    TRY(ensure_tasks(c));
+    TRY(ensure_tasks(c, c->T));
     c->small_tabs_ready = false;               // (tab_setup gets this path's rows; Kinv[j] may be allocated below)
     c->small_sweep_ready = false;
     c->setup1_ready = false;
@@ -204,11 +198,10 @@ static int factor_priors_impl(gprn_ctx* c)
         TRY(upload_table(c, c->tab_setup, rows));
         HIP_TRY(c, hipMemcpy(c->d_slotgp_setup, gps.data(), nb * sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemsetAsync(c->d_info, 0, 3 * (size_t)c->nslot * sizeof(int), c->stream));
-        c->d_ptrs = c->tab_setup;
-        c->d_info_cur = c->d_info;
-        TRY(factor_invert(c, nb, true));
+        const Phase setup = problem_phase(c, c->tab_setup, c->d_slotgp_setup, nb, 0, c->d_info);
+        TRY(factor_invert(c, setup, true));
         // log det K: non-owned helper entries are dropped below, before the all-reduce
-        TRY(vec_logdet(c, BUF_B, c->d_slotgp_setup, nb, c->d_logdetK));
+        TRY(vec_logdet(c, setup, BUF_B, c->d_logdetK));
         HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);      // (the verdicts are read through the null stream, which does not wait
         TRY(check_info(c, c->d_info, gps, &first_info));  // for the library's non-blocking streams by itself)
         // K_j^-1 = X^T X for the nodes that need it (one at a time: output goes to Kinv[j])
@@ -221,7 +214,7 @@ static int factor_priors_impl(gprn_ctx* c)
             one[BUF_X] = rows[s * GPRN_NBUF + BUF_X];
             HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
             TRY(upload_table(c, c->tab_setup, one));
-            TRY(lauum_lower(c, 1));
+            TRY(lauum_lower(c, problem_phase(c, c->tab_setup, nullptr, 1, 0, nullptr)));
             HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
             TRY(upload_table(c, c->tab_setup, rows));
         }
@@ -249,7 +242,13 @@ static int factor_priors_impl(gprn_ctx* c)
 // workspaces -- measured 108.4 against 111.3 sweeps/s at config 3 and is gone: DESIGN.md 5d)
 static int overlap_mask(const gprn_ctx* c) { return c->overlap_opt >= 0 ? c->overlap_opt : 31; }
 
-static int mu_k_mu(gprn_ctx* c, bool weights, hipStream_t stream = nullptr, double* out = nullptr);
+// the node (weights = false) or weight half-sweep of this rank
+static Phase sweep_phase(const gprn_ctx* c, bool weights)
+{
+    return problem_phase(c, weights ? c->tab_weight : c->tab_node, weights ? c->d_slotgp_weight : c->d_slotgp_node,
+                         (int)(weights ? c->loc_weights : c->loc_nodes).size(), weights ? (int)c->loc_nodes.size() : 0,
+                         c->d_info + (weights ? 2 : 1) * (size_t)c->nslot);
+}
 
 // One sweep of the small path (smalln.hip): node half-sweep, weight half-sweep, tail -- three launches, no host step
 // between them.  (mu_in, var_in) is the state the sweep starts from, (mu_out, var_out) receives the new one.
@@ -257,24 +256,21 @@ static int small_sweep(gprn_ctx* c, const double* mu_in, const double* var_in, d
                        double* out4, double* scal, const SmallLoop* loop)
 {
     c->d_scal = scal;
-    c->d_logdetB = scal; c->d_trBinv = scal + c->G; c->d_muKmu = scal + 2 * (size_t)c->G; c->d_q1 = scal + 3 * (size_t)c->G;
     const int* done = loop ? loop->ctl : nullptr;
     TRY(ensure_small_sweep_tabs(c));
-    c->d_ptrs = c->tab_node; c->slot0 = 0; c->d_info_cur = c->d_info + (size_t)c->nslot;
-    TRY(small_phase(c, false, c->d_slotgp_node, (int)c->loc_nodes.size(), mu_in, var_in, mu_out, var_out, done));
-    c->d_ptrs = c->tab_weight; c->slot0 = (int)c->loc_nodes.size(); c->d_info_cur = c->d_info + 2 * (size_t)c->nslot;
-    TRY(small_phase(c, true, c->d_slotgp_weight, (int)c->loc_weights.size(), mu_in, var_in, mu_out, var_out, done));
+    TRY(small_phase(c, sweep_phase(c, false), false, scal, mu_in, var_in, mu_out, var_out, done));
+    TRY(small_phase(c, sweep_phase(c, true), true, scal, mu_in, var_in, mu_out, var_out, done));
     return small_tail(c, out4, scal, mu_out, var_out, loop);
 }
 
-// One half-sweep's factorisation with its head and tail, against c->d_ptrs / slot0 / d_info_cur (set by the caller): d, s,
-// right-hand side -> B = I + D^1/2 K D^1/2 = L L^T, X = L^-1 -> u = X z, column sums over X -> the new rows of the state,
-// tr B^-1, log det B.  `ns` slots whose latent GPs are d_slot_gp[slot] (and, for a batch of evaluations, whose evaluation
-// is c->ev.slot_eval[slot]: midn.hip).
-int phase_core(gprn_ctx* c, bool weights, const int* slotgp, int ns)
+// One half-sweep's factorisation with its head and tail: d, s, right-hand side -> B = I + D^1/2 K D^1/2 = L L^T,
+// X = L^-1 -> u = X z, column sums over X -> the new rows of the state, tr B^-1 and log det B into the sweep's scalars
+// `scal`.  The phase's slots hold latent GPs ph.slot_gp[slot] (and, for a batch of evaluations, evaluations
+// ph.ev.slot_eval[slot]: midn.hip).
+int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::function<int()>& chain_started)
 {
-    const size_t o = (size_t)c->slot0 * c->ld;
-    TRY(vec_prep(c, weights, slotgp, ns));
+    const size_t o = (size_t)ph.slot0 * ph.ld;
+    TRY(vec_prep(c, ph, weights));
     // B = I + D^1/2 K D^1/2: built by factor_invert -- only the tiles its first outer panel's tile steps touch; the
     // others are formed from K inside that panel's K = 512 update (overlap bit 1).
     // The reductions over the rows of X = L^-1 (u = X z, column norms, X^T u: 8 N^2 bytes per matrix) run outer
@@ -282,53 +278,68 @@ int phase_core(gprn_ctx* c, bool weights, const int* slotgp, int ns)
     // behind the factorisation only the last panel's rows, the reduction over the partial sums and the new state
     // are left.  Same kernels, same partial sums, same order of every addition: bit-identical results.
     const int overlap = overlap_mask(c);
-    c->rows_done = 0;
-    c->build_pending = ns;
-    c->ft_s_phase = (overlap & 1) ? c->d_s + o : nullptr;
+    FactorHooks h;
+    h.build_B = true;
+    h.ft_s = (overlap & 1) ? c->d_s + o : nullptr;
     if (overlap & 2) {
-        c->rows_final = [c, o, slotgp, ns](int r0, int r1, hipStream_t st) -> int {
-            TRY(vec_lower_matvec(c, BUF_X, c->d_z + o, c->ld, 0, slotgp, ns, c->d_u + o, st, r0 * GPRN_TILE,
-                                 (r1 - r0) * GPRN_TILE));
-            return vec_colops_partial(c, ns, st, r0, r1 - r0);
+        h.rows_final = [c, &ph, o](int r0, int r1, hipStream_t st) -> int {
+            TRY(vec_lower_matvec(c, ph, BUF_X, c->d_z + o, ph.ld, 0, c->d_u + o, st, r0 * GPRN_TILE, (r1 - r0) * GPRN_TILE));
+            return vec_colops_partial(c, ph, st, r0, r1 - r0);
         };
     }
-    const int rc_f = factor_invert(c, ns);
-    c->ft_s_phase = nullptr; c->build_pending = 0;
-    const int rd = c->rows_done;
-    c->rows_final = nullptr; c->rows_done = 0;
+    h.chain_started.swap(chain_started);
+    const int rc_f = factor_invert(c, ph, false, &h);
+    chain_started.swap(h.chain_started);
     TRY(rc_f);
-    TRY(vec_lower_matvec(c, BUF_X, c->d_z + o, c->ld, 0, slotgp, ns, c->d_u + o, nullptr, rd * GPRN_TILE, -1));
-    TRY(vec_colops_partial(c, ns, nullptr, rd, -1));
-    if (overlap & 8) TRY(vec_reduce_finalize(c, slotgp, ns, true));     // column sums, new state, tr B^-1, log det B
+    TRY(vec_lower_matvec(c, ph, BUF_X, c->d_z + o, ph.ld, 0, c->d_u + o, nullptr, h.rows_done * GPRN_TILE, -1));
+    TRY(vec_colops_partial(c, ph, nullptr, h.rows_done, -1));
+    if (overlap & 8) TRY(vec_reduce_finalize(c, ph, scal, true));     // column sums, new state, tr B^-1, log det B
     else {
-        TRY(vec_colops_reduce(c, ns));
-        TRY(vec_logdet(c, BUF_B, slotgp, ns, c->d_logdetB));
-        TRY(vec_finalize(c, slotgp, ns, false));
+        TRY(vec_colops_reduce(c, ph));
+        TRY(vec_logdet(c, ph, BUF_B, scal));
+        TRY(vec_finalize(c, ph, scal, false));
     }
     return GPRN_OK;
 }
 
-static int run_phase(gprn_ctx* c, bool weights)
+// mu^T K^-1 mu of the phase's latent GPs into out (the sweep's muKmu)
+static int mu_k_mu(gprn_ctx* c, bool weights, double* out, hipStream_t stream = nullptr)
 {
+    const Phase ph = sweep_phase(c, weights);
+    if (!ph.nslots) return GPRN_OK;
+    // a = L_K^-1 m_g with m_g = state row g (nodes: mu_f[g]; weights: the raw-reshape row, quirk Q2)
+    double* a = c->d_u + (size_t)ph.slot0 * ph.ld;
+    TRY(vec_lower_matvec(c, ph, BUF_KLINV, c->d_mu, c->N, 1, a, stream));
+    return vec_dot_self(c, ph, a, out, stream);
+}
+
+// What the node phase leaves for the bulk stream beside the weight phase (quirk Q1's traces, the node term)
+struct NodeSide {
+    std::function<int()> work;
+    bool q1 = false;                 // the work records ev_q1: join it before the ELBO assembly
+    bool term_done = false;          // ... and computes the node term mu_f^T K_f^-1 mu_f
+};
+
+// One half-sweep of the sweep whose scalars are `scal`.  handed: work for the bulk stream behind this phase's first
+// diagonal block (run here when no factorisation takes it); nodes (node phase): what it leaves for the weight phase.
+static int run_phase(gprn_ctx* c, bool weights, double* scal, std::function<int()>& handed, NodeSide* nodes)
+{
+    const Phase ph = sweep_phase(c, weights);
     const std::vector<int>& gps = weights ? c->loc_weights : c->loc_nodes;
-    const int ns = (int)gps.size();
-    const int* slotgp = weights ? c->d_slotgp_weight : c->d_slotgp_node;
-    c->d_ptrs = weights ? c->tab_weight : c->tab_node;
-    c->slot0 = weights ? (int)c->loc_nodes.size() : 0;
-    c->d_info_cur = c->d_info + (weights ? 2 : 1) * (size_t)c->nslot;
-    const size_t o = (size_t)c->slot0 * c->ld;
+    const int ns = ph.nslots;
+    const size_t o = (size_t)ph.slot0 * ph.ld;
     if (ns) {
-        TRY(phase_core(c, weights, slotgp, ns));
+        TRY(phase_core(c, ph, weights, scal, handed));
         const int overlap = overlap_mask(c);
         if (c->keep_sigma) {
             const size_t nn = (size_t)c->ld * c->ld;
-            TRY(lauum_lower(c, ns));
+            TRY(lauum_lower(c, ph));
             for (int s = 0; s < ns; ++s) {
                 if (!c->Sig[gps[s]]) {
                     TRY(dev_alloc(c, &c->Sig[gps[s]], nn));
                     HIP_TRY(c, hipMemsetAsync(c->Sig[gps[s]], 0, nn * sizeof(double), c->stream));   // padding stays zero
                 }
-                TRY(vec_sigma(c, c->wsB[c->slot0 + s], c->d_s + o + (size_t)s * c->ld, c->Sig[gps[s]]));
+                TRY(vec_sigma(c, c->wsB[ph.slot0 + s], c->d_s + o + (size_t)s * c->ld, c->Sig[gps[s]]));
             }
         }
         if (!weights && c->q > 1) {
@@ -337,58 +348,37 @@ static int run_phase(gprn_ctx* c, bool weights)
             // the second stream and is joined before the ELBO assembly.  It is handed to the weight
             // phase's factorisation, which enqueues it behind its first diagonal block (a launch of
             // 528 long-running workgroups just before would keep that block waiting for a free CU).
-            const int n_inv = (gps.back() == c->q - 1) ? ns - 1 : ns;
+            Phase inv = ph;
+            inv.nslots = (gps.back() == c->q - 1) ? ns - 1 : ns;
             const std::vector<int> node_gps = gps;
-            double** const node_tab = c->d_ptrs;
             const std::vector<double*> node_B(c->wsB.begin(), c->wsB.begin() + ns);
-            double* const q1_out = c->d_q1;
             HIP_TRY(c, hipEventRecord(c->ev_nodes, c->stream));
             const bool early_term = (overlap & 4) && !c->loc_weights.empty();
-            c->node_term_done = early_term;
-            c->chain_started = [c, early_term, n_inv, ns, node_gps, node_tab, node_B, q1_out]() -> int {
-                double** const cur = c->d_ptrs;
-                const int cur_slot0 = c->slot0;
+            nodes->term_done = early_term;
+            nodes->q1 = true;
+            nodes->work = [c, scal, early_term, inv, node_gps, node_B]() -> int {
                 HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_nodes, 0));
                 // mu_f^T K_f^-1 mu_f needs the node phase's result only: HBM-bound work beside the MFMA-bound weight phase
-                int rc = early_term ? mu_k_mu(c, false, c->stream2) : GPRN_OK;
-                c->d_ptrs = node_tab;
-                if (!rc && n_inv && !c->keep_sigma) rc = lauum_lower(c, n_inv, c->stream2);
-                for (int s = 0; s < ns && !rc; ++s) {
+                if (early_term) TRY(mu_k_mu(c, false, scal + 2 * (size_t)c->G, c->stream2));
+                if (inv.nslots && !c->keep_sigma) TRY(lauum_lower(c, inv, c->stream2));
+                for (size_t s = 0; s < node_gps.size(); ++s) {
                     const int k = node_gps[s];
-                    for (int j = k + 1; j < c->q && !rc; ++j)
-                        rc = vec_q1(c, c->Kinv[j], node_B[s], c->d_s + (size_t)s * c->ld, c->d_u,
-                                    q1_out + (size_t)j * c->q + k, c->stream2);
+                    for (int j = k + 1; j < c->q; ++j)
+                        TRY(vec_q1(c, c->Kinv[j], node_B[s], c->d_s + s * c->ld, c->d_u,
+                                   scal + 3 * (size_t)c->G + (size_t)j * c->q + k, c->stream2));
                 }
-                c->d_ptrs = cur;
-                c->slot0 = cur_slot0;
-                if (rc) return rc;
                 HIP_TRY(c, hipEventRecord(c->ev_q1, c->stream2));
                 return GPRN_OK;
             };
-            c->q1_pending = true;
         }
     }
-    if (weights && c->chain_started) {
-        // no factorisation took it along (no weight GP on this rank): now
+    if (handed) {
+        // no factorisation took it along (no GP of this phase on this rank): now
         std::function<int()> f;
-        f.swap(c->chain_started);
+        f.swap(handed);
         TRY(f());
     }
     return exchange_rows(c, weights);
-}
-
-static int mu_k_mu(gprn_ctx* c, bool weights, hipStream_t stream, double* out)
-{
-    const std::vector<int>& gps = weights ? c->loc_weights : c->loc_nodes;
-    const int ns = (int)gps.size();
-    if (!ns) return GPRN_OK;
-    const int* slotgp = weights ? c->d_slotgp_weight : c->d_slotgp_node;
-    c->d_ptrs = weights ? c->tab_weight : c->tab_node;
-    // a = L_K^-1 m_g with m_g = state row g (nodes: mu_f[g]; weights: the raw-reshape row, quirk Q2)
-    c->slot0 = weights ? (int)c->loc_nodes.size() : 0;
-    double* a = c->d_u + (size_t)c->slot0 * c->ld;
-    TRY(vec_lower_matvec(c, BUF_KLINV, c->d_mu, c->N, 1, slotgp, ns, a, stream));
-    return vec_dot_self(c, slotgp, ns, a, out ? out : c->d_muKmu, stream);
 }
 
 static int sweep_impl(gprn_ctx* c, int n_sweeps, int commit, double* elbo_out, double* parts_out, bool retry);
@@ -438,8 +428,7 @@ static int sweep_impl(gprn_ctx* c, int n_sweeps, int commit, double* elbo_out, d
     const int overlap = overlap_mask(c);
     const size_t nscal = 3 * (size_t)c->G + (size_t)c->q * c->q;
     // (the node phase's factorisation must be one that joins the bulk stream at its end: an outer panel with a "rest")
-    c->chain_started = nullptr;
-    TRY(ensure_tasks(c));
+    TRY(ensure_tasks(c, c->T));
     const int node_set = (int)c->loc_nodes.size() * c->T <= GPRN_LAT_MAX ? 1 : 0;
     const bool node_joins = !c->outers[node_set].empty() && c->outers[node_set][0].nrest > 0;
     const bool may_defer = (overlap & 16) && !comm_active(c) && factor_use_flags(c) == 1 &&
@@ -449,15 +438,14 @@ static int sweep_impl(gprn_ctx* c, int n_sweeps, int commit, double* elbo_out, d
         HIP_TRY(c, hipMemsetAsync(c->d_scal_base, 0, 2 * nscal * sizeof(double), c->stream));
         scal_cleared = true;
     }
+    std::function<int()> deferred;                 // the end of the sweep before, handed to this sweep's node phase
     for (int it = 0; it < n_sweeps; ++it) {
         double* const scal = c->d_scal_base + (size_t)(it & 1) * nscal;
         double* const part = c->d_elbo_part + (size_t)(it & 1) * GPRN_ELBO_PART_DOUBLES;
         c->d_scal = scal;
-        c->d_logdetB = scal; c->d_trBinv = scal + c->G; c->d_muKmu = scal + 2 * (size_t)c->G; c->d_q1 = scal + 3 * (size_t)c->G;
         // (every entry a sweep reads it has written itself, with '=': the two copies are cleared once per call, above; on a
         // sharded context the all-reduce leaves the other ranks' entries behind, so there it is cleared every sweep)
         if (comm_active(c) || !scal_cleared) HIP_TRY(c, hipMemsetAsync(scal, 0, nscal * sizeof(double), c->stream));
-        c->node_term_done = false;
         if (small) {
             // three launches: the two half-sweeps read the state the sweep starts from and write the other copy
             TRY(small_sweep(c, c->d_mu, c->d_var, c->d_mu_alt, c->d_var_alt, c->d_out + 4 * (size_t)it, scal, nullptr));
@@ -470,30 +458,27 @@ static int sweep_impl(gprn_ctx* c, int n_sweeps, int commit, double* elbo_out, d
             // watchdog's budget bounds a STALL (a rank that died) and not the legitimate length of the call
             HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
         }
-        TRY(run_phase(c, false));
-        TRY(run_phase(c, true));
+        NodeSide nodes;
+        TRY(run_phase(c, false, scal, deferred, &nodes));
+        TRY(run_phase(c, true, scal, nodes.work, nullptr));
         const bool defer = may_defer && it + 1 < n_sweeps;
-        if (c->q1_pending && !defer) {          // the Q1 traces (and the node term) computed behind the weight phase
+        if (nodes.q1 && !defer) {               // the Q1 traces (and the node term) computed behind the weight phase
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_q1, 0));
         }
-        c->q1_pending = false;
-        const bool node_term = !c->node_term_done;
+        const bool node_term = !nodes.term_done;
         double* const out4 = c->d_out + 4 * (size_t)it;
+        double* const muKmu = scal + 2 * (size_t)c->G;
         if (defer) {
-            c->chain_started = [c, scal, part, out4, node_term]() -> int {
-                double** const cur = c->d_ptrs;
-                const int cur_slot0 = c->slot0;
-                int rc = node_term ? mu_k_mu(c, false, c->stream2, scal + 2 * (size_t)c->G) : GPRN_OK;
-                if (!rc) rc = mu_k_mu(c, true, c->stream2, scal + 2 * (size_t)c->G);
-                if (!rc) rc = vec_elbo(c, out4, scal, part, c->stream2);
-                c->d_ptrs = cur; c->slot0 = cur_slot0;
-                return rc;
+            deferred = [c, scal, part, out4, muKmu, node_term]() -> int {
+                if (node_term) TRY(mu_k_mu(c, false, muKmu, c->stream2));
+                TRY(mu_k_mu(c, true, muKmu, c->stream2));
+                return vec_elbo(c, out4, scal, part, c->stream2);
             };
             continue;
         }
-        if (node_term) TRY(mu_k_mu(c, false));
-        TRY(mu_k_mu(c, true));
-        TRY(reduce_scalars(c));
+        if (node_term) TRY(mu_k_mu(c, false, muKmu));
+        TRY(mu_k_mu(c, true, muKmu));
+        TRY(reduce_scalars(c, scal));
         TRY(vec_elbo(c, out4, scal, part));
     }
     if (!commit) {

@@ -101,10 +101,9 @@ unsigned long long* step_stamp_ptr(gprn_ctx* c, int k, int which)
     return c->d_step_stamps + (((size_t)ph * c->step_stamps_T + k) * 3 + which) * 3;
 }
 
-int launch_diag(gprn_ctx* c, double** d_ptrs, int nbatch, int ld, int kblk, int* d_info, hipStream_t stream,
-                Signal sig, Await aw)
+int launch_diag(gprn_ctx* c, const Phase& ph, int kblk, bool acc, hipStream_t stream, Signal sig, Await aw)
 {
-    if (!stream) stream = c->stream;
+    const int nbatch = ph.nslots;
     prof_begin(c, GPRN_T_DIAG, stream);
     PtrArgs pa;
     // Little work in total (batch x tiles <= GPRN_LAT_MAX, the latency set's problems): most CUs are idle, and with all
@@ -113,17 +112,16 @@ int launch_diag(gprn_ctx* c, double** d_ptrs, int nbatch, int ld, int kblk, int*
     // Config 2 (N = 2048, one matrix per phase): 686 -> 741 sweeps/s.  On a loaded device it waits for such a CU as long
     // as the neighbours would have cost (config 3 with the pad in the node phase: 109.8 vs 110.1), hence the limit.
     size_t dyn = 0;
-    if (nbatch * c->T <= GPRN_LAT_MAX)
-        dyn = std::min<size_t>((size_t)113 * 1024, lds_limit(c->device) - (c->acc_now ? DIAG_LDS_DOUBLES_ACC : DIAG_LDS_DOUBLES) * sizeof(double));
+    if (nbatch * ph.T <= GPRN_LAT_MAX)
+        dyn = std::min<size_t>((size_t)113 * 1024, lds_limit(c->device) - (acc ? DIAG_LDS_DOUBLES_ACC : DIAG_LDS_DOUBLES) * sizeof(double));
     pa.stamps = step_stamp_ptr(c, kblk, 0);
-    // rows of data in this tile: all 128 but in the last tile of a ragged matrix (ld is the context's: the diagnostic entry
-    // points factor whole tiles)
-    const int rows_here = ld == c->ld ? std::min(GPRN_TILE, c->N - kblk * GPRN_TILE) : GPRN_TILE;
+    // rows of data in this tile: all 128 but in the last tile of a ragged matrix
+    const int rows_here = std::min(GPRN_TILE, ph.N - kblk * GPRN_TILE);
     const int nph = std::max(1, (rows_here + 15) / 16);
-#define GO_D(ARGS, ACC) hipLaunchKernelGGL((k_diag_block<ARGS, ACC>), dim3(nbatch), dim3(256), dyn, stream, (double* const*)d_ptrs, pa, ld, kblk, \
-                           d_info, sig.slot, sig.value, aw.flag, aw.value, aw.timed_out, nph)
-    if (tab_rows(c, d_ptrs, nbatch, &pa)) { if (c->acc_now) GO_D(true, true); else GO_D(true, false); }
-    else { if (c->acc_now) GO_D(false, true); else GO_D(false, false); }
+#define GO_D(ARGS, ACC) hipLaunchKernelGGL((k_diag_block<ARGS, ACC>), dim3(nbatch), dim3(256), dyn, stream, (double* const*)ph.ptrs, pa, \
+                           ph.ld, kblk, ph.info, sig.slot, sig.value, aw.flag, aw.value, aw.timed_out, nph)
+    if (tab_rows(c, ph.ptrs, nbatch, &pa)) { if (acc) GO_D(true, true); else GO_D(true, false); }
+    else { if (acc) GO_D(false, true); else GO_D(false, false); }
 #undef GO_D
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
@@ -151,9 +149,9 @@ static inline int64_t toff(int ti, int tj, int ld) {
 // can run while the rest streams on a second HIP stream.
 // Two sets of lists: [0] outer panels of GPRN_OUTER tiles (throughput), [1] of GPRN_OUTER_SMALL for problems with little
 // work in total (batch x tiles <= GPRN_LAT_MAX: fewer joins of the bulk stream on the chain).
-int ensure_tasks(gprn_ctx* c)
+int ensure_tasks(gprn_ctx* c, int T)
 {
-    const int T = c->T, ld = c->ld;
+    const int ld = T * GPRN_TILE;
     if (c->tasks_T == T && c->d_tasks) return GPRN_OK;
     std::vector<TileTask>& v = c->h_tasks;
     v.clear();
@@ -380,33 +378,30 @@ int factor_use_flags(gprn_ctx* c)
 //                 per outer panel the "first" part of its K = 512 update;
 //   next    (s4): per outer panel the "next" part (T <= 64; on the bulk stream beyond: a "rest" launch there runs 11 ms);
 //   bulk    (s2): per outer panel "rest" in two launches (look-ahead part, then the others), and the phase's row
-//                 reductions over X as its rows become final (run_phase's rows_final hook).
+//                 reductions over X as its rows become final (FactorHooks::rows_final).
 // Order of read-modify-writes on a tile is kept by flags (use_flags: 32-bit words in device memory -- the chain's small
 // kernels raise and poll them in-kernel, larger launches are bracketed by one-thread kernels or stream memory operations)
 // or, the same launch sequence, by HIP events (serialising tools, no stream memory operations, or after a time-out).
 // Flags only grow: a call waits for its own epoch.
-static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
+static int factor_invert_launches(gprn_ctx* c, const Phase& ph, FactorHooks& h, bool acc, int set)
 {
     int rc;
+    const int nbatch = ph.nslots, T = ph.T;
     hipStream_t s0 = c->stream, s1 = c->stream3, s2 = c->stream2;
     auto shape_upd = [&](size_t n) { return n * (size_t)nbatch > GPRN_FEW_TASKS ? TS_128x128 : TS_64x64; };
-    auto tiles = [&](size_t first, size_t n, hipStream_t st, int shape, int fam = GPRN_T_PANEL,
-                     Signal sig = Signal{nullptr, 0, nullptr, 0, nullptr}, Await aw = Await{nullptr, 0, nullptr}, int tag = TG_INNER) {
-        return launch_tiles(c, c->d_tasks + first, n, c->d_ptrs, nbatch, c->ld, fam, st, shape, sig, aw, tag);
-    };
     const int use_flags = factor_use_flags(c);
     auto side_stamp = [&](int k, int i) {          // GPRN_STEP_STAMPS=2: the clock on stream3 at this point of step k
         if (c->side_stamps) hipLaunchKernelGGL(k_stamp, dim3(1), dim3(64), 0, s1, c->side_stamps + (size_t)k * 8 + i);
     };
     enum { F_DIAG = 0, F_MINIL, F_INNER, F_PANEL, F_NEXT, F_REST, F_FIRST, F_XW, F_RESTA, F_TAIL, F_KINDS };
     static_assert(F_KINDS == GPRN_FLAG_KINDS, "factor_check_waits decodes the flag table by GPRN_FLAG_KINDS");
-    if (use_flags && c->sig_T < c->T) {
+    if (use_flags && c->sig_T < T) {
         if (c->d_sig) hipFree(c->d_sig);
         c->d_sig = nullptr;
         // [T][F_KINDS] pairs {counter, flag}, then: sticky time-out word, budget of one wait, which flag timed out
-        HIP_TRY(c, hipMalloc(&c->d_sig, ((size_t)c->T * F_KINDS * 2 + 4) * sizeof(unsigned)));
-        HIP_TRY(c, hipMemset(c->d_sig, 0, ((size_t)c->T * F_KINDS * 2 + 4) * sizeof(unsigned)));
-        c->sig_T = c->T;
+        HIP_TRY(c, hipMalloc(&c->d_sig, ((size_t)T * F_KINDS * 2 + 4) * sizeof(unsigned)));
+        HIP_TRY(c, hipMemset(c->d_sig, 0, ((size_t)T * F_KINDS * 2 + 4) * sizeof(unsigned)));
+        c->sig_T = T;
         c->epoch = 0;
         c->sig_budget_ms = -1;
     }
@@ -417,6 +412,13 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
         c->sig_budget_ms = c->wait_budget_ms;
     }
     const unsigned epoch = ++c->epoch;
+    // ft_s: the first outer panel's update forms B's tiles from K; start_flag: raised by the launch's first workgroup
+    auto tiles = [&](size_t first, size_t n, hipStream_t st, int shape, int fam = GPRN_T_PANEL,
+                     Signal sig = Signal{nullptr, 0, nullptr, 0, nullptr}, Await aw = Await{nullptr, 0, nullptr}, int tag = TG_INNER,
+                     const double* ft_s = nullptr, unsigned* start_flag = nullptr) {
+        return launch_tiles(c, c->d_tasks + first, n, ph.ptrs, nbatch, ph.ld, fam, st, shape, sig, aw, tag,
+                            TileSide{acc, ft_s, ph.N, start_flag, epoch});
+    };
     hipEvent_t events[F_KINDS] = {c->ev_diag, c->ev_minil, c->ev_inner, c->ev_panel, c->ev_next, c->ev_rest, c->ev_first,
                                   nullptr, c->ev_resta, c->ev_tail};
     auto slot = [&](int idx, int kind) { return c->d_sig + ((size_t)idx * F_KINDS + kind) * 2; };
@@ -467,7 +469,7 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
     bool tail_on_s2 = false;                       // rows_final ran on the bulk stream: joined at the end
     // "rest" as two launches with "next" on a stream of its own, beside the previous panel's whole "rest": +2.1 % sweeps/s
     // at N = 4096 and 8192; at N = 16384, where a "rest" launch runs for 11 ms, -0.7 %: up to 64 tile steps
-    const bool sr = c->stream4 && c->T <= 64;
+    const bool sr = c->stream4 && T <= 64;
     hipStream_t sn = sr ? c->stream4 : s2;
     // The chain's two products per tile step, L_{k+1,k} and the update of B_{k+1,k+1}, have kernels of their own that cut
     // a 128 x 128 tile into 16 x 16 pieces (k_chain_l / k_chain_u: 3-5 us for one matrix, where the tile kernel needs 12).
@@ -508,28 +510,25 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
     // less per step on stream3 (config 2 737 -> 751 sweeps/s, config 3 +0.5 %; with six matrices, whose panel launches
     // are hundreds of workgroups that would all poll: -1 %, and beyond may_poll not safe)
     auto folds_sync = [&](int k) {
-        if (k < 0 || k >= c->T) return false;
+        if (k < 0 || k >= T) return false;
         const gprn_ctx::StepRange& sk = c->steps[set][k];
         return use_flags && nbatch <= 2 && sk.npanel_l > 0 && sk.npanel > 1 && may_poll(2 * (sk.npanel - 1) * (size_t)nbatch);
     };
 
-    // B is still to be built (run_phase): only what the first outer panel's tile steps touch; its K = 512 update forms
+    // B is still to be built (phase_core): only what the first outer panel's tile steps touch; its K = 512 update forms
     // the other tiles from K on the way in (bit 5 of their tasks; tile_mma ft_K) -- 16 N^2 bytes of HBM traffic per
     // matrix and three quarters of k_build_B's time at the head of the phase less
     bool ft_fused = false;
-    if (c->build_pending) {
-        const int pend = c->build_pending;
-        c->build_pending = 0;
+    if (h.build_B) {
         const gprn_ctx::OuterRange& o0 = c->outers[set][0];
         const int outer = o0.k1 - o0.k0;
         // (the 64 x 64 tile kernel only: every launch of the first panel's update must use that shape)
-        ft_fused = c->ft_s_phase && pend == nbatch && c->T > outer &&
-                   shape_upd(o0.nfirst) == TS_64x64 && shape_upd(o0.nnext) == TS_64x64;
-        if ((rc = vec_build_B(c, pend, s0, ft_fused ? 1 : 0, outer))) return rc;
+        ft_fused = h.ft_s && T > outer && shape_upd(o0.nfirst) == TS_64x64 && shape_upd(o0.nnext) == TS_64x64;
+        if ((rc = vec_build_B(c, ph, s0, ft_fused ? 1 : 0, outer))) return rc;
     }
-    if (!use_flags && c->chain_started) {          // event schedule: nothing to gate the caller's side work on
+    if (!use_flags && h.chain_started) {           // event schedule: nothing to gate the caller's side work on
         std::function<int()> f;
-        f.swap(c->chain_started);
+        f.swap(h.chain_started);
         if ((rc = f())) return rc;
     }
 
@@ -551,12 +550,11 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
             if (rest_J >= 0) HIP_TRY(c, await(s1, rest_J, sr ? F_RESTA : F_REST));
             if (next_J >= 0) { HIP_TRY(c, await(s1, next_J, F_NEXT)); next_J = -1; }
         }
-        // the first panel's update forms the tiles of B it touches from K (run_phase built only the others)
-        struct FtScope { gprn_ctx* c; ~FtScope() { c->ft_s_now = nullptr; } } ft_scope{c};
-        c->ft_s_now = (o.k0 == 0 && ft_fused) ? c->ft_s_phase : nullptr;
-        if (o.k1 < c->T) side_stamp(o.k1, 6);          // (stamps of the NEXT panel's first step: behind the waits, behind "first")
-        if ((rc = tiles(o.first0, o.nfirst, s1, shape_upd(o.nfirst), GPRN_T_PANEL, nosig, noaw, TG_NEXT))) return rc;
-        if (o.k1 < c->T) side_stamp(o.k1, 7);
+        // the first panel's update forms the tiles of B it touches from K (vec_build_B built only the others)
+        const double* const ft_s = (o.k0 == 0 && ft_fused) ? h.ft_s : nullptr;
+        if (o.k1 < T) side_stamp(o.k1, 6);             // (stamps of the NEXT panel's first step: behind the waits, behind "first")
+        if ((rc = tiles(o.first0, o.nfirst, s1, shape_upd(o.nfirst), GPRN_T_PANEL, nosig, noaw, TG_NEXT, ft_s))) return rc;
+        if (o.k1 < T) side_stamp(o.k1, 7);
         // F_FIRST: by the first workgroup of the next launch on stream3 when that is a panel launch with the
         // synchronisation folded in, else a stream write
         if (use_flags && folds_sync(o.k1)) pending_up = slot(J, F_FIRST) + 1;
@@ -570,7 +568,7 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
             HIP_TRY(c, await(sn, J, F_PANEL));
             if (sr && rest_J >= 0) HIP_TRY(c, await(sn, rest_J, F_RESTA));
         }
-        if ((rc = tiles(o.next0, o.nnext, sn, shape_upd(o.nnext), GPRN_T_PANEL, nosig, noaw, TG_NEXT))) return rc;
+        if ((rc = tiles(o.next0, o.nnext, sn, shape_upd(o.nnext), GPRN_T_PANEL, nosig, noaw, TG_NEXT, ft_s))) return rc;
         // (a stream write, not the launch's own end-of-kernel signal: with a fence and an atomic at the end of each of its
         // several hundred workgroups 116.6 vs 117.6 sweeps/s at config 3 with two matrices, 113.4 with six)
         HIP_TRY(c, raise(sn, J, F_NEXT));
@@ -580,24 +578,22 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
             // 8-wave 128 x 128 form (109.0 vs 105.9 sweeps/s at config 3)
             if (sr) {
                 HIP_TRY(c, await(s2, J, F_PANEL));
-                if ((rc = tiles(o.rest0, o.nrestA, s2, TS_64x64, GPRN_T_UPDATE_AHEAD, nosig, noaw, TG_AHEAD))) return rc;
-                // F_RESTA: by the first workgroup of the "bulk" launch behind it (gprn_ctx::start_flag_now) when there is one
+                if ((rc = tiles(o.rest0, o.nrestA, s2, TS_64x64, GPRN_T_UPDATE_AHEAD, nosig, noaw, TG_AHEAD, ft_s))) return rc;
+                // F_RESTA: by the first workgroup of the "bulk" launch behind it (TileSide::start_flag) when there is one
                 const bool resta_by_bulk = use_flags && o.nrest > o.nrestA;
-                if (resta_by_bulk) { c->start_flag_now = slot(J, F_RESTA) + 1; c->start_value_now = epoch; }
-                else HIP_TRY(c, raise(s2, J, F_RESTA));
-                rc = tiles(o.rest0 + o.nrestA, o.nrest - o.nrestA, s2, TS_64x64, GPRN_T_UPDATE, nosig, noaw, TG_BULK);
-                c->start_flag_now = nullptr;
-                if (rc) return rc;
-            } else if ((rc = tiles(o.rest0, o.nrest, s2, TS_64x64, GPRN_T_UPDATE, nosig, noaw, TG_BULK))) return rc;
+                if (!resta_by_bulk) HIP_TRY(c, raise(s2, J, F_RESTA));
+                if ((rc = tiles(o.rest0 + o.nrestA, o.nrest - o.nrestA, s2, TS_64x64, GPRN_T_UPDATE, nosig, noaw, TG_BULK, ft_s,
+                                resta_by_bulk ? slot(J, F_RESTA) + 1 : nullptr))) return rc;
+            } else if ((rc = tiles(o.rest0, o.nrest, s2, TS_64x64, GPRN_T_UPDATE, nosig, noaw, TG_BULK, ft_s))) return rc;
             HIP_TRY(c, raise(s2, J, F_REST));
             rest_J = J;
         }
         // rows [k0, k1) of X are final once stream3 is through with the panel: their share of the phase's O(N^2)
-        // reductions goes behind the panel's bulk update on the bulk stream (run_phase, api_sweep.hip)
-        if (c->rows_final) {
+        // reductions goes behind the panel's bulk update on the bulk stream (phase_core, api_sweep.hip)
+        if (h.rows_final) {
             if (!(o.nrest && sr) && sn != s2) HIP_TRY(c, await(s2, J, F_PANEL));
-            if ((rc = c->rows_final(o.k0, o.k1, s2))) return rc;
-            c->rows_done = o.k1;
+            if ((rc = h.rows_final(o.k0, o.k1, s2))) return rc;
+            h.rows_done = o.k1;
             tail_on_s2 = true;
         }
         return GPRN_OK;
@@ -609,15 +605,15 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
             const gprn_ctx::StepRange& s = c->steps[set][k];
             if (pending_outer >= 0 && s.npanel_l == 0 && (rc = do_outer(pending_outer))) return rc;
             // ---- the chain
-            if ((rc = launch_diag(c, c->d_ptrs, nbatch, c->ld, k, c->d_info_cur, s0, in_kernel(k, F_DIAG), noaw))) return rc;
+            if ((rc = launch_diag(c, ph, k, acc, s0, in_kernel(k, F_DIAG), noaw))) return rc;
             if (!use_flags) HIP_TRY(c, raise(s0, k, F_DIAG));
-            if (use_flags && k == 0 && c->chain_started) {
+            if (use_flags && k == 0 && h.chain_started) {
                 // work handed over by the caller for the bulk stream (run_phase: the previous phase's X^T X
                 // product, 528 long-running workgroups) goes behind the FIRST diagonal block: launched before
                 // it, it holds every CU and the block waits for one to drain (211 us instead of 50 measured)
                 HIP_TRY(c, await(s2, 0, F_DIAG));
                 std::function<int()> f;
-                f.swap(c->chain_started);
+                f.swap(h.chain_started);
                 if ((rc = f())) return rc;
             }
             if (s.npanel_l == 0) {
@@ -645,22 +641,20 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
                 // the same two products as tasks of the tile kernel: the step's first panel task and first update task
                 // (ensure_tasks), a few hundred 64-row workgroups at its K = 128 rate
                 if ((rc = tiles(s.panel0, 1, s0, TS_64x128_BTRI, GPRN_T_PANEL, nosig, noaw, TG_PANEL))) return rc;
-                if (use_flags) { c->start_flag_now = slot(k, F_MINIL) + 1; c->start_value_now = epoch; }
-                else HIP_TRY(c, raise(s0, k, F_MINIL));
-                rc = tiles(s.upd0, 1, s0, TS_64x64, GPRN_T_PANEL, nosig, noaw, TG_INNER);
-                c->start_flag_now = nullptr;
-                if (rc) return rc;
+                if (!use_flags) HIP_TRY(c, raise(s0, k, F_MINIL));
+                if ((rc = tiles(s.upd0, 1, s0, TS_64x64, GPRN_T_PANEL, nosig, noaw, TG_INNER, nullptr,
+                                use_flags ? slot(k, F_MINIL) + 1 : nullptr))) return rc;
             } else {
             // (a prior matrix: the tile by substitution, the panel kernel's ACC form on the step's first task)
-            if (c->acc_now) rc = launch_panel(c, c->d_tasks + s.panel0, 1, 0, c->d_ptrs, nbatch, c->ld, s0, nosig,
-                                              spin ? in_kernel_wait(k - 1, F_INNER) : noaw);
-            else rc = launch_tile_rows(c, k, c->d_ptrs, nbatch, c->ld, 0, GPRN_T_PANEL, s0, nosig,
+            if (acc) rc = launch_panel(c, c->d_tasks + s.panel0, 1, 0, ph.ptrs, nbatch, ph.ld, true, s0, nosig,
+                                       spin ? in_kernel_wait(k - 1, F_INNER) : noaw);
+            else rc = launch_tile_rows(c, k, ph.ptrs, nbatch, ph.ld, 0, GPRN_T_PANEL, s0, nosig,
                                        spin ? in_kernel_wait(k - 1, F_INNER) : noaw);
             if (rc) return rc;
             if (!use_flags) HIP_TRY(c, raise(s0, k, F_MINIL));
             // (flag schedule: L_{k+1,k}'s flag goes up at the START of the update launch behind it on the chain stream
             // instead of at the end of its own -- 1.7 us less between the two at every tile step)
-            if ((rc = launch_tile_rows(c, k, c->d_ptrs, nbatch, c->ld, 1, GPRN_T_PANEL, s0, nosig, noaw,
+            if ((rc = launch_tile_rows(c, k, ph.ptrs, nbatch, ph.ld, 1, GPRN_T_PANEL, s0, nosig, noaw,
                                        use_flags ? slot(k, F_MINIL) + 1 : (unsigned*)nullptr, epoch))) return rc;
             }
             // The outer update of the previous panel is ENQUEUED here, behind the chain's three launches of this panel's
@@ -685,8 +679,8 @@ static int factor_invert_launches(gprn_ctx* c, int nbatch, int set)
                     pending_up = nullptr;
                     aw_d = in_kernel_wait(k, F_DIAG);
                 }
-                if ((rc = launch_panel(c, c->d_tasks + s.panel0 + 1, s.npanel_l - 1, s.npanel - s.npanel_l, c->d_ptrs,
-                                       nbatch, c->ld, s1, x_part_then(k), aw_d, up, epoch, up2))) return rc;
+                if ((rc = launch_panel(c, c->d_tasks + s.panel0 + 1, s.npanel_l - 1, s.npanel - s.npanel_l, ph.ptrs,
+                                       nbatch, ph.ld, acc, s1, x_part_then(k), aw_d, up, epoch, up2))) return rc;
             } else {
                 if ((rc = tiles(s.panel0 + 1, s.npanel_l - 1, s1, TS_64x128_BTRI, GPRN_T_PANEL, nosig, noaw, TG_PANEL))) return rc;
                 if ((rc = tiles(s.panel0 + s.npanel_l, s.npanel - s.npanel_l, s1, TS_128x64_ATRI, GPRN_T_PANEL, nosig, noaw, TG_PANEL))) return rc;
@@ -763,7 +757,7 @@ int factor_check_waits(gprn_ctx* c)
                 fprintf(stderr, "[gprn] chain of factorisation %d (batch %d), us: step | diag: ->start run | L: ->launch wait run | U: ->launch run | step total\n",
                         c->step_stamps_n - back, c->step_stamps_batch[ph]);
                 unsigned long long prev_end = p[0];
-                for (int k = 0; k < c->T; ++k) {
+                for (int k = 0; k < T; ++k) {
                     const unsigned long long* d = p + (size_t)k * 9;
                     const unsigned long long* l = d + 3;
                     const unsigned long long* u = d + 6;
@@ -811,38 +805,39 @@ int factor_check_waits(gprn_ctx* c)
 }
 
 
-int factor_invert(gprn_ctx* c, int nbatch, bool prior)
+int factor_invert(gprn_ctx* c, const Phase& ph, bool prior, FactorHooks* hooks)
 {
-    int rc = ensure_tasks(c);
+    const int nbatch = ph.nslots, T = ph.T;
+    int rc = ensure_tasks(c, T);
     if (rc) return rc;
-    struct AccScope { gprn_ctx* c; ~AccScope() { c->acc_now = false; } } acc_scope{c};
-    c->acc_now = c->acc_opt < 0 ? prior : c->acc_opt != 0;
+    const bool acc = c->acc_opt < 0 ? prior : c->acc_opt != 0;
+    FactorHooks none;
     static int step_stamps_env = -1;               // GPRN_STEP_STAMPS=1/2 (probes): in-kernel clock stamps of the chain / of stream3 too
     if (step_stamps_env < 0) { const char* e = getenv("GPRN_STEP_STAMPS"); step_stamps_env = e ? atoi(e) : 0; }
     c->side_stamps = nullptr;
     if (step_stamps_env) {
-        if (c->step_stamps_T < c->T) {
+        if (c->step_stamps_T < T) {
             if (c->d_step_stamps) hipFree(c->d_step_stamps);
             if (c->d_side_stamps) hipFree(c->d_side_stamps);
             c->d_side_stamps = nullptr;
-            HIP_TRY(c, hipMalloc(&c->d_side_stamps, (size_t)c->T * 8 * sizeof(unsigned long long)));
-            HIP_TRY(c, hipMalloc(&c->d_step_stamps, (size_t)8 * c->T * 9 * sizeof(unsigned long long)));
-            c->step_stamps_T = c->T;
+            HIP_TRY(c, hipMalloc(&c->d_side_stamps, (size_t)T * 8 * sizeof(unsigned long long)));
+            HIP_TRY(c, hipMalloc(&c->d_step_stamps, (size_t)8 * T * 9 * sizeof(unsigned long long)));
+            c->step_stamps_T = T;
             c->step_stamps_n = 0;
         }
         c->step_stamps_n += 1;
-        const int ph = (c->step_stamps_n - 1) & 7;
-        c->step_stamps_batch[ph] = nbatch;
-        HIP_TRY(c, hipMemsetAsync(c->d_step_stamps + (size_t)ph * c->step_stamps_T * 9, 0, (size_t)c->step_stamps_T * 9 * sizeof(unsigned long long), c->stream));
+        const int at = (c->step_stamps_n - 1) & 7;
+        c->step_stamps_batch[at] = nbatch;
+        HIP_TRY(c, hipMemsetAsync(c->d_step_stamps + (size_t)at * c->step_stamps_T * 9, 0, (size_t)c->step_stamps_T * 9 * sizeof(unsigned long long), c->stream));
         if (step_stamps_env >= 2 && nbatch <= 2) {       // (the node phase: the one the chain bounds)
             HIP_TRY(c, hipMemsetAsync(c->d_side_stamps, 0, (size_t)c->step_stamps_T * 8 * sizeof(unsigned long long), c->stream));
             c->side_stamps = c->d_side_stamps;
-            c->side_stamps_ph = ph;
+            c->side_stamps_ph = at;
         }
     }
     // latency set of task lists for problems with little work in total (measured: +11 % at N = 2048 x 1 matrix,
     // -3 % at N = 4096 x 2)
-    rc = factor_invert_launches(c, nbatch, nbatch * c->T <= GPRN_LAT_MAX ? 1 : 0);
+    rc = factor_invert_launches(c, ph, hooks ? *hooks : none, acc, nbatch * T <= GPRN_LAT_MAX ? 1 : 0);
     if (rc && c->d_sig && c->use_flags == 1) {
         // The enqueue broke off half-way: stream waits already queued on the device's shared streams would
         // wait for flags nobody will raise (they have no time-out).  Put every flag of this call up so that
@@ -860,10 +855,10 @@ int factor_invert(gprn_ctx* c, int nbatch, bool prior)
 }
 
 // BUF_B of every slot = lower(X^T X), X in BUF_X (L in BUF_B is overwritten)
-int lauum_lower(gprn_ctx* c, int nbatch, hipStream_t stream)
+int lauum_lower(gprn_ctx* c, const Phase& ph, hipStream_t stream)
 {
-    int rc = ensure_tasks(c);
+    int rc = ensure_tasks(c, ph.T);
     if (rc) return rc;
-    return launch_tiles(c, c->d_tasks + c->lauum0, c->nlauum, c->d_ptrs, nbatch, c->ld,
+    return launch_tiles(c, c->d_tasks + c->lauum0, c->nlauum, ph.ptrs, ph.nslots, ph.ld,
                         GPRN_T_LAUUM, stream);
 }

@@ -60,7 +60,7 @@ void k_tile_gemm(const TileTask* __restrict__ tasks, double* const* __restrict__
                  const double* ft_s, int ft_n,
                  unsigned* start_flag, unsigned start_value)
 {
-    // (gprn_ctx::start_flag_now: the flag of the launch before this one on the stream -- in memory once a workgroup of
+    // (TileSide::start_flag: the flag of the launch before this one on the stream -- in memory once a workgroup of
     // this launch runs -- instead of a stream write, a 4.5 us kernel of its own, between the two)
     if (start_flag && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
         __hip_atomic_store(start_flag, start_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -179,14 +179,15 @@ void k_tile_panel(const TileTask* __restrict__ tasks, int n_l, double* const* __
 }
 
 int launch_panel(gprn_ctx* c, const TileTask* d_tasks, size_t n_l, size_t n_x, double** d_ptrs, int nbatch, int ld,
-                 hipStream_t stream, Signal sig, Await aw, unsigned* raise_at_start, unsigned raise_value, unsigned* raise_at_start2)
+                 bool acc, hipStream_t stream, Signal sig, Await aw, unsigned* raise_at_start, unsigned raise_value,
+                 unsigned* raise_at_start2)
 {
     if (n_l + n_x == 0 || nbatch == 0) return launch_tiles(c, d_tasks, 0, d_ptrs, nbatch, ld, GPRN_T_PANEL, stream, TS_128x64, sig);
     prof_begin(c, GPRN_T_PANEL, stream);
 #define GO_P(ACC) hipLaunchKernelGGL(k_tile_panel<ACC>, dim3((unsigned)(2 * (n_l + n_x)), (unsigned)nbatch), dim3(256), 0, stream, d_tasks, (int)n_l, \
                        (double* const*)d_ptrs, ld, sig.slot, sig.value, sig.then_wait, sig.then_value, \
                        aw.timed_out ? aw.timed_out : sig.timed_out, aw.flag, aw.value, raise_at_start, raise_value, raise_at_start2)
-    if (c->acc_now) GO_P(true); else GO_P(false);
+    if (acc) GO_P(true); else GO_P(false);
 #undef GO_P
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
@@ -380,7 +381,7 @@ size_t lds_limit(int device)
 
 template <int BM, int BN, int TRI, int TAG>
 static bool launch_one(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double* const* tab, int nbatch, int ld,
-                       size_t dyn, hipStream_t stream, const Signal& sig, const Await& aw)
+                       size_t dyn, hipStream_t stream, const Signal& sig, const Await& aw, const TileSide& side)
 {
     constexpr size_t static_lds = 2 * 16 * (BM + BN + 32) * sizeof(double);
     if (dyn && static_lds + dyn > lds_limit(c->device)) {
@@ -394,12 +395,12 @@ static bool launch_one(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, doub
     hipLaunchKernelGGL((k_tile_gemm<BM, BN, NW, TRI, TAG>), dim3((unsigned)ntasks * per_task, (unsigned)nbatch),
                        dim3(64 * NW), dyn, stream, d_tasks, tab, ld, sig.slot, sig.value, sig.then_wait,
                        sig.then_value, aw.flag, aw.value, aw.timed_out ? aw.timed_out : sig.timed_out, GPRN_XCD_CHUNK_LOG2,
-                       c->ft_s_now, c->N, c->start_flag_now, c->start_value_now);
+                       side.ft_s, side.N, side.start_flag, side.start_value);
     return true;
 }
 
 int launch_tiles(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double** d_ptrs,
-                 int nbatch, int ld, int fam, hipStream_t stream, int shape, Signal sig, Await aw, int tag)
+                 int nbatch, int ld, int fam, hipStream_t stream, int shape, Signal sig, Await aw, int tag, const TileSide& side)
 {
     if (!stream) stream = c->stream;
     if (ntasks == 0 || nbatch == 0) {
@@ -414,8 +415,8 @@ int launch_tiles(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double** d
         return GPRN_OK;
     }
     // (ACC: the L part of a panel never runs as a product -- k_tile_panel<true>, same grid, same flags)
-    if (c->acc_now && shape == TS_64x128_BTRI && tag == TG_PANEL)
-        return launch_panel(c, d_tasks, ntasks, 0, d_ptrs, nbatch, ld, stream, sig, aw, c->start_flag_now, c->start_value_now);
+    if (side.acc && shape == TS_64x128_BTRI && tag == TG_PANEL)
+        return launch_panel(c, d_tasks, ntasks, 0, d_ptrs, nbatch, ld, true, stream, sig, aw, side.start_flag, side.start_value);
     prof_begin(c, fam, stream);
     // Bulk launches on the look-ahead stream (the K = 512 trailing updates, the X^T X product) ask for 16 KiB of unused
     // dynamic LDS on top of their image: two 64 x 64 workgroups per CU instead of three (one 128 x 128 instead of two).
@@ -428,7 +429,7 @@ int launch_tiles(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double** d
     const bool padded_fam = fam == GPRN_T_UPDATE || fam == GPRN_T_UPDATE_AHEAD || fam == GPRN_T_LAUUM;
     const size_t dyn = (stream == c->stream2 && padded_fam) ? (size_t)kb * 1024 : 0;
     double* const* tab = (double* const*)d_ptrs;
-#define GO(BM, BN, TRI, TAG) fits = launch_one<BM, BN, TRI, TAG>(c, d_tasks, ntasks, tab, nbatch, ld, dyn, stream, sig, aw)
+#define GO(BM, BN, TRI, TAG) fits = launch_one<BM, BN, TRI, TAG>(c, d_tasks, ntasks, tab, nbatch, ld, dyn, stream, sig, aw, side)
     bool known = true, fits = true;
     switch (shape * 8 + tag) {
     // panel products (K = 128 against the triangular X_kk)

@@ -116,12 +116,6 @@ struct gprn_ctx {
     hipEvent_t ev_diag = nullptr, ev_minil = nullptr, ev_inner = nullptr, ev_first = nullptr;
     // head / tail of a phase beside its factorisation (run_phase, api_sweep.hip; factor_invert_split, factor.hip)
     hipEvent_t ev_tail = nullptr;
-    bool node_term_done = false;     // the node phase's mu^T K^-1 mu went to the bulk stream beside the weight phase (run_phase)
-    // run_phase: called (by schedules that know) once tile rows [r0, r1) of X are final in `stream` order -- the O(N^2)
-    // reductions over X's rows (X z, column norms, X^T u) then run beside the rest of the factorisation instead of
-    // behind it; rows_done: first tile row the caller still has to do itself
-    std::function<int(int r0, int r1, hipStream_t stream)> rows_final;
-    int rows_done = 0;
     hipStream_t prof_stream = nullptr;
     std::string err;
     int info_gp = -1;
@@ -155,13 +149,10 @@ struct gprn_ctx {
     std::vector<double*> Kinv;       // q   K_j^-1 lower, only for nodes j>=1 that feed quirk Q1
     std::vector<double*> Sig;        // G   explicit Sigma of the last sweep (keep_sigma only)
     bool keep_sigma = false;
-    bool q1_pending = false;
     double* d_logdetK = nullptr;     // G
     // ---- workspaces: nslot pairs (B, X), nslot = max local GPs of a phase
     int nslot = 0;                   // local nodes + local weights: every local GP has its own (B, X)
-    int slot0 = 0;                   // first slot of the running phase (0 nodes, #local nodes weights)
     std::vector<double*> wsB, wsX;
-    double** d_ptrs = nullptr;       // the table the launchers use right now (one of the three below)
     // host copies of the live pointer tables (device address -> rows): the chain's kernels take the few pointers
     // they need as kernel arguments instead of fetching them from the table (one memory round trip less on the
     // critical path of every tile step); tab_note / tab_forget / tab_rows, factor.hip
@@ -175,16 +166,14 @@ struct gprn_ctx {
     double* d_part = nullptr;        // partial column sums scratch [nslot][T][2][ld]
     double* d_fin_terms = nullptr;   // k_reduce_finalize: per-element terms of tr B^-1 and log det B [nslot][2][ld]
     unsigned* d_fin_tickets = nullptr;   // ... and its per-slot ticket counters (zero between launches)
-    // per-GP scalars of the running sweep, one allocation (all-reduced as one message):
+    // per-GP scalars of a sweep, one allocation per copy (all-reduced as one message):
     // logdetB[G], trBinv[G], muKmu[G], Q1 traces [q*q]
-    double* d_scal = nullptr;        // (two copies: a sweep's ELBO assembly may run beside the next sweep, sweep_impl)
-    double* d_scal_base = nullptr;
+    double* d_scal_base = nullptr;   // two copies: a sweep's ELBO assembly may run beside the next sweep (sweep_impl)
+    double* d_scal = nullptr;        // the copy the last sweep wrote (gprn_get_scalars)
     double* d_elbo_part = nullptr;   // scratch of the ELBO assembly, two copies
-    double *d_logdetB = nullptr, *d_trBinv = nullptr, *d_muKmu = nullptr, *d_q1 = nullptr;
     double* d_out = nullptr;         // per sweep: elbo, logl, logp, ent
     int out_cap = 0;
     int* d_info = nullptr;           // [3][nslot] first failing pivot per slot: setup, node phase, weight phase
-    int* d_info_cur = nullptr;       // the row factor_invert writes to
     // prediction scratch (gprn_predict): K* and (X K*^T)^T per local GP, [ns_pad x ld] each
     std::vector<double*> predKs, predWT;
     // host-evaluated matrices staged for the next gprn_predict (gprn_predict_upload): K + 1.25e-12 I (N x N), K* (ns x N), k** (ns)
@@ -205,10 +194,8 @@ struct gprn_ctx {
     // memory (stream memory operations + in-kernel waits), 0 = HIP events, -1 = not decided yet.  Decided per
     // context from the device and the environment; latched to 0 after an in-kernel wait timed out.
     int use_flags = -1;
-    // Panel steps by substitution instead of products with explicit inverses (diag_tile.h ACC): acc_now is what the running
-    // factor_invert uses; option "accurate_factor": -1 every factorisation of a PRIOR matrix (set-up, prediction, prior draws),
-    // 0 never, 1 always (the sweeps' B too: diagnostics)
-    bool acc_now = false;
+    // Panel steps by substitution instead of products with explicit inverses (diag_tile.h ACC), option "accurate_factor":
+    // -1 every factorisation of a PRIOR matrix (set-up, prediction, prior draws), 0 never, 1 always (the sweeps' B too: diagnostics)
     int acc_opt = -1;
     int fenced_finalize = 0;         // gprn_set_option "fenced_finalize" (tests): k_reduce_finalize's release / acquire form
     int wait_budget_ms = 2000;       // wall-clock budget of one in-kernel wait (gprn_set_option "wait_budget_ms")
@@ -218,13 +205,9 @@ struct gprn_ctx {
     // LDS pads of the tile launches (gemm_tile.hip launch_tiles), KiB; -1: the environment's / the default
     int pad_kb_opt = -1, pad_small_kb_opt = -1;
     int sig_budget_ms = -1;          // budget the device word holds
-    // enqueued by the next factor_invert behind its first diagonal block (factor.hip)
-    std::function<int()> chain_started;
     // GPRN_STEP_STAMPS=1 (probes): per tile step and chain kernel (diag, L, U) the 100 MHz clock at its start, after its
     // wait and at its end -- the launch schedule's chain as it really ran (a kernel trace slows the chain's small
     // kernels by 15 %); [phase slot][T][3 kernels][3 stamps], printed by factor_check_waits
-    unsigned* start_flag_now = nullptr;            // launch_tiles: a flag word the next tile launch sets to start_value_now when its
-    unsigned start_value_now = 0;                  // first workgroup runs (the flag of the launch BEFORE it on its stream)
     unsigned long long* d_step_stamps = nullptr;
     int step_stamps_T = 0, step_stamps_n = 0;
     int step_stamps_batch[8] = {0};
@@ -242,13 +225,7 @@ struct gprn_ctx {
     struct OuterRange { int k0, k1; size_t first0, nfirst, next0, nnext, rest0, nrest, nrestA; };
     std::vector<OuterRange> outers[2];
     size_t lauum0 = 0, nlauum = 0;
-    int tasks_T = 0;
-    // run_phase -> factor_invert_split: s = sqrt(d) of the phase's slots when B's tiles beyond the first outer panel are
-    // still to be formed -- by the first panel's K = 512 update, on the way in (tile_mma ft_K); ft_s_now: what launch_tiles
-    // passes to the kernel right now (set around that update's launches only)
-    int build_pending = 0;           // run_phase: B of this many slots is still to be built by the next factor_invert
-    const double* ft_s_phase = nullptr;
-    const double* ft_s_now = nullptr;
+    int tasks_T = 0;                 // T the lists were built for
     int overlap_opt = -1;            // gprn_set_option "overlap" (api_sweep.hip overlap_mask); -1: the default
     // ---- small-N path (smalln.hip): problems of one or two tiles run a half-sweep as ONE launch, one workgroup per latent GP
     int small_opt = -1;              // gprn_set_option "small_path": 0 never, else wherever it applies (small_applies)
@@ -267,12 +244,28 @@ struct gprn_ctx {
     bool setup1_ready = false;       // tab_setup / d_slotgp_setup / tab_kinv1 hold the unsharded launch-path set-up's rows (factor_priors_single)
     double** tab_kinv1 = nullptr;    // [q - 1][GPRN_NBUF]: BUF_B = K_j^-1, BUF_X = chol(K_j)^-1, nodes j >= 1 (one X^T X launch)
     // ---- many evaluations side by side above one tile (midn.hip): a worker context holds the matrices and states of a
-    // chunk of evaluations; its kernels find an evaluation's arrays through `ev`
-    EvalMap ev = {nullptr, 0, 0, 0, 0};
+    // chunk of evaluations; its kernels find an evaluation's arrays through the EvalMap of each Phase
     void* mid_batch = nullptr;       // MidBatch (midn.hip): the worker context and its slabs, owned by the PARENT context
     int batch_mem_mb = -1;           // gprn_set_option "batch_mem_mb": device memory one chunk of evaluations may take; -1: a share of what is free
     int last_batch_chunk = 0;        // read-only option "batch_chunk": evaluations per chunk in the last gprn_elbocalc_batch call
 };
+
+// The matrices a call works on -- a half-sweep, a set-up, a prediction, a diagnostic -- passed by const reference to
+// everything that launches against them
+struct Phase {
+    double** ptrs;             // device pointer table, GPRN_NBUF rows per slot
+    const int* slot_gp;        // slot -> latent GP (device), or null where no launch reads it
+    int nslots;
+    int slot0;                 // first slot of the per-slot vectors (d, s, pred, z, u, colsq, colt, partial sums)
+    int* info;                 // pivot-verdict row the factorisation writes to
+    EvalMap ev;                // all null / zero for one problem
+    int N, ld, T;              // geometry of the matrices (ld = 128 T)
+};
+// ... over the context's own problem
+static inline Phase problem_phase(const gprn_ctx* c, double** ptrs, const int* slot_gp, int nslots, int slot0, int* info)
+{
+    return Phase{ptrs, slot_gp, nslots, slot0, info, EvalMap{nullptr, 0, 0, 0, 0}, c->N, c->ld, c->T};
+}
 
 struct DeviceLock {                                // no-op for a null context (the entry point rejects it next)
     std::unique_lock<std::recursive_mutex> l;
@@ -315,17 +308,26 @@ struct Signal {
 // start until *flag >= value; a wait that times out (about a second) sets *timed_out and goes on.
 struct Await { const unsigned* flag; unsigned value; unsigned* timed_out; };
 size_t lds_limit(int device);         // LDS bytes one workgroup may ask for, static + dynamic (gemm_tile.hip)
+// What a tile launch of a factorisation takes beside its tasks (factor_invert_launches)
+struct TileSide {
+    bool acc = false;                  // panel steps by substitution: the L part of a panel runs on k_tile_panel<true>
+    const double* ft_s = nullptr;      // s of the slots whose first-touch B tiles the launch forms from K (tile_mma ft_K), or null
+    int N = 0;                         // ... and the matrices' N
+    unsigned* start_flag = nullptr;    // a flag word the launch sets to start_value when its first workgroup runs (the flag
+    unsigned start_value = 0;          // of the launch BEFORE it on its stream), or null
+};
 int launch_tiles(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double** d_ptrs,
                  int nbatch, int ld, int fam, hipStream_t stream = nullptr, int shape = TS_128x128,
                  Signal sig = Signal{nullptr, 0, nullptr, 0, nullptr}, Await aw = Await{nullptr, 0, nullptr},
-                 int tag = TG_MISC);
+                 int tag = TG_MISC, const TileSide& side = TileSide{});
 // < 1/2 (P - Kinv + a a^T), dK/dtheta_l > for every parameter of a kernel program by central differences of the
 // program, on the device (fill.hip); out: n_params doubles of device memory, part: N doubles of scratch
 int launch_grad_fd(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const double* P, const double* a,
                    double* part, double* out);
-// the L part (n_l tasks) and the X part (n_x tasks) of a tile step's panel in one launch (gemm_tile.hip)
+// the L part (n_l tasks) and the X part (n_x tasks) of a tile step's panel in one launch (gemm_tile.hip); acc: the L part
+// by substitution
 int launch_panel(gprn_ctx* c, const TileTask* d_tasks, size_t n_l, size_t n_x, double** d_ptrs, int nbatch, int ld,
-                 hipStream_t stream, Signal sig, Await aw = Await{nullptr, 0, nullptr},
+                 bool acc, hipStream_t stream, Signal sig, Await aw = Await{nullptr, 0, nullptr},
                  unsigned* raise_at_start = nullptr, unsigned raise_value = 0, unsigned* raise_at_start2 = nullptr);
 // BUF_B and BUF_X of up to GPRN_ARG_SLOTS matrices as a kernel argument
 #define GPRN_ARG_SLOTS 16
@@ -341,9 +343,8 @@ unsigned long long* step_stamp_ptr(gprn_ctx* c, int k, int which);   // GPRN_STE
 // update of B_{k+1,k+1}
 int launch_tile_rows(gprn_ctx* c, int k, double** d_ptrs, int nbatch, int ld, int mode, int fam,
                      hipStream_t stream, Signal sig, Await aw, unsigned* raise_at_start = nullptr, unsigned raise_value = 0);
-int launch_diag(gprn_ctx* c, double** d_ptrs, int nbatch, int ld, int kblk, int* d_info,
-                hipStream_t stream = nullptr, Signal sig = Signal{nullptr, 0, nullptr, 0, nullptr},
-                Await aw = Await{nullptr, 0, nullptr});
+// diagonal block kblk of every slot of the phase (factor.hip); acc: the ACC form of diag_tile
+int launch_diag(gprn_ctx* c, const Phase& ph, int kblk, bool acc, hipStream_t stream, Signal sig, Await aw);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ size_t ev_of(const EvalMap& e, int slot) { return e.slot_eval ? (size_t)e.slot_eval[slot] : 0; }
@@ -406,20 +407,36 @@ __device__ __forceinline__ void signal_done(unsigned* slot, unsigned value, cons
     }
 }
 #endif
-// factor B (slot buffers BUF_B) into L and X = L^-1 (BUF_X) for nbatch slots; prior: the matrices are prior covariances
+// What a half-sweep hands its factorisation beside the matrices (phase_core, api_sweep.hip)
+struct FactorHooks {
+    // B is still to be built: only the tiles the first outer panel's tile steps touch; with ft_s (s = sqrt(d) of the
+    // phase's slots) the others are formed from K by that panel's K = 512 update, on the way in (tile_mma ft_K)
+    bool build_B = false;
+    const double* ft_s = nullptr;
+    // called once tile rows [r0, r1) of X are final in `stream` order -- the O(N^2) reductions over X's rows (X z, column
+    // norms, X^T u) then run beside the rest of the factorisation instead of behind it; rows_done (out): first tile row
+    // the caller still has to do itself
+    std::function<int(int r0, int r1, hipStream_t stream)> rows_final;
+    int rows_done = 0;
+    // work for the bulk stream, run (and cleared) by the factorisation: behind its first diagonal block on the flag schedule,
+    // before its first launch on events; left set when no factorisation took it -- the caller runs it then
+    std::function<int()> chain_started;
+};
+// factor B (slot buffers BUF_B) into L and X = L^-1 (BUF_X) for the phase's slots; prior: the matrices are prior covariances
 // (cond ~ 1e8 under the reference's nugget): panel steps by substitution (gprn_ctx::acc_opt)
-int factor_invert(gprn_ctx* c, int nbatch, bool prior = false);
-int lauum_lower(gprn_ctx* c, int nbatch, hipStream_t stream = nullptr);   // BUF_B = lower(X^T X), X in BUF_X
-int ensure_tasks(gprn_ctx* c);
+int factor_invert(gprn_ctx* c, const Phase& ph, bool prior = false, FactorHooks* hooks = nullptr);
+int lauum_lower(gprn_ctx* c, const Phase& ph, hipStream_t stream = nullptr);   // BUF_B = lower(X^T X), X in BUF_X
+int ensure_tasks(gprn_ctx* c, int T);  // the task lists for T tiles (ld = 128 T), rebuilt when T changes
 // internal status: an in-kernel dependency wait gave up; the entry points of api.hip re-run the call on events
 #define GPRN_E_WAIT_TIMEOUT (-100)
 int factor_check_waits(gprn_ctx* c);   // GPRN_E_WAIT_TIMEOUT if an in-kernel dependency wait timed out since the last check
 int factor_use_flags(gprn_ctx* c);
 // smalln.hip
 bool small_applies(const gprn_ctx* c);
-// one half-sweep against c->d_ptrs / slot0: reads the state (mu_in, var_in), writes this phase's rows of (mu_out, var_out);
-// the weight phase takes the node rows from the new state.  done: device word that makes the launch a no-op when set, or null
-int small_phase(gprn_ctx* c, bool weights, const int* d_slot_gp, int nslots, const double* mu_in, const double* var_in,
+// one half-sweep of the phase: reads the state (mu_in, var_in), writes this phase's rows of (mu_out, var_out) and its entries
+// of the sweep's scalars `scal`; the weight phase takes the node rows from the new state.  done: device word that makes the
+// launch a no-op when set, or null
+int small_phase(gprn_ctx* c, const Phase& ph, bool weights, double* scal, const double* mu_in, const double* var_in,
                 double* mu_out, double* var_out, const int* done = nullptr);
 // the loop of ELBOcalc on the device (gprn_elbocalc): control words, the batch's ELBO values, the loop's last three values
 struct SmallLoop { int* ctl; double *hist, *last3; int sweep, hist_at, max_iter; };
@@ -439,8 +456,9 @@ int mid_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_kpa
                        double* mu_out, double* var_out);
 void mid_batch_free(gprn_ctx* c);
 size_t batch_budget_bytes(gprn_ctx* c);        // device memory a chunk of evaluations may take (option "batch_mem_mb")
-// api_sweep.hip: one half-sweep's factorisation with its head and tail against c->d_ptrs / slot0 / d_info_cur (run_phase, midn.hip)
-int phase_core(gprn_ctx* c, bool weights, const int* d_slot_gp, int ns);
+// api_sweep.hip: one half-sweep's factorisation with its head and tail (run_phase, midn.hip); scal: the sweep's scalars;
+// chain_started: see FactorHooks (left set when the factorisation did not take it)
+int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::function<int()>& chain_started);
 
 // meanfield.py:640-643: np.std / np.mean of the last three values, operation by operation (one rounding each)
 static inline bool elbo_stop_rule(double e0, double e1, double e2)

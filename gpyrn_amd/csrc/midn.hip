@@ -11,7 +11,7 @@
 // A WORKER context (a gprn_ctx of its own on the parent's device and streams) holds a chunk of evaluations: per
 // evaluation and latent GP the prior matrix K, chol(K)^-1, the sweep's workspaces B and X, K_j^-1 for nodes j >= 1
 // (quirk Q1), and per evaluation the state, y - mean, the variances, the per-GP scalars -- the kernels of vecops.hip find
-// an evaluation's copy through gprn_ctx::ev (slot -> evaluation, strides).  The parent's own state and factors are not
+// an evaluation's copy through the EvalMap of the phase (slot -> evaluation, strides: mid_ev).  The parent's own state and factors are not
 // touched.  Per sweep: node phase (phase_core, api_sweep.hip), the Q1 products, weight phase, the prior terms, the ELBO of
 // every evaluation still running, ONE read-back (4 doubles per evaluation + the pivot verdicts); the stop rule of
 // meanfield.py:640-643 is applied per evaluation on the host, and an evaluation that has stopped leaves the tables of the
@@ -158,9 +158,6 @@ static int mid_ensure(gprn_ctx* c, int want, int* cap_out)
     HIP_TRY(c, hipMemcpy(w->d_yraw, c->d_yraw, pn * sizeof(double), hipMemcpyDeviceToDevice));
     HIP_TRY(c, hipMemset(w->d_scal_base, 0, (size_t)cap * nscal * sizeof(double)));
     HIP_TRY(c, hipMemset(w->d_info, 0, 3 * nslot * sizeof(int)));
-    w->d_scal = w->d_scal_base;
-    w->d_logdetB = w->d_scal; w->d_trBinv = w->d_scal + G; w->d_muKmu = w->d_scal + 2 * (size_t)G; w->d_q1 = w->d_scal + 3 * (size_t)G;
-    w->ev = EvalMap{nullptr, d, pn, nscal, (size_t)G};
     w->have_yres = w->have_jit = w->have_muvar = true;
     // ---- the slabs
     MB_TRY(mb_alloc(c, &m->K, (size_t)cap * G * nn));
@@ -259,65 +256,61 @@ static int mid_upload_active(gprn_ctx* c, MidBatch* m, const std::vector<int>& a
     return GPRN_OK;
 }
 
-static int mid_phase(gprn_ctx* w, MidBatch* m, bool weights, int nA)
+// strides between two evaluations' copies of the per-problem arrays; slot_eval: slot -> evaluation of the phase
+static EvalMap mid_ev(const MidBatch* m, const int* slot_eval)
 {
-    const int per = weights ? m->q * m->p : m->q, ns = per * nA;
-    w->d_ptrs = m->d_ptr_block + (weights ? m->o_weight : m->o_node);
-    w->ev.slot_eval = m->d_int_block + (weights ? m->i_ev_weight : m->i_ev_node);
-    w->slot0 = weights ? nA * m->q : 0;
-    w->d_info_cur = w->d_info + (weights ? 2 : 1) * (size_t)w->nslot;
-    return phase_core(w, weights, m->d_int_block + (weights ? m->i_gp_weight : m->i_gp_node), ns);
+    return EvalMap{slot_eval, (size_t)(m->p + 1) * m->q * m->N, (size_t)m->p * m->N, 3 * (size_t)m->G + (size_t)m->q * m->q,
+                   (size_t)m->G};
+}
+
+// the node or weight phase of the evaluations in the active tables (node-major slots, mid_upload_active)
+static Phase mid_phase(const gprn_ctx* w, const MidBatch* m, bool weights, int nA)
+{
+    const int per = weights ? m->q * m->p : m->q;
+    return Phase{m->d_ptr_block + (weights ? m->o_weight : m->o_node), m->d_int_block + (weights ? m->i_gp_weight : m->i_gp_node),
+                 per * nA, weights ? nA * m->q : 0, w->d_info + (weights ? 2 : 1) * (size_t)w->nslot,
+                 mid_ev(m, m->d_int_block + (weights ? m->i_ev_weight : m->i_ev_node)), w->N, w->ld, w->T};
 }
 
 // m^T K^-1 m = |L_K^-1 m|^2 per latent GP of the phase, m the state row as it lies in memory (quirk Q2)
 static int mid_prior_term(gprn_ctx* w, MidBatch* m, bool weights, int nA, hipStream_t st)
 {
-    const int per = weights ? m->q * m->p : m->q, ns = per * nA;
-    const int* slotgp = m->d_int_block + (weights ? m->i_gp_weight : m->i_gp_node);
-    w->d_ptrs = m->d_ptr_block + (weights ? m->o_weight : m->o_node);
-    w->ev.slot_eval = m->d_int_block + (weights ? m->i_ev_weight : m->i_ev_node);
-    w->slot0 = weights ? nA * m->q : 0;
-    double* a = w->d_u + (size_t)w->slot0 * w->ld;
-    MB_TRY(vec_lower_matvec(w, BUF_KLINV, w->d_mu, w->N, 1, slotgp, ns, a, st));
-    return vec_dot_self(w, slotgp, ns, a, w->d_muKmu, st);
+    const Phase ph = mid_phase(w, m, weights, nA);
+    double* a = w->d_u + (size_t)ph.slot0 * ph.ld;
+    MB_TRY(vec_lower_matvec(w, ph, BUF_KLINV, w->d_mu, w->N, 1, a, st));
+    return vec_dot_self(w, ph, a, w->d_scal_base + 2 * (size_t)m->G, st);
 }
 
 // One sweep (meanfield.py:651-710) of the evaluations in the active tables; out4 of each lands at out4 + 4 * evaluation.
 // The pivot verdicts of its phases are only raised (rows 1, 2 of d_info: the caller clears them).
 static int mid_sweep(gprn_ctx* w, MidBatch* m, int nA, double* out4)
 {
-    w->chain_started = nullptr;                          // (nothing left over from a sweep that broke off)
-    MB_TRY(mid_phase(w, m, false, nA));
+    double* const scal = w->d_scal_base;
+    std::function<int()> side;
+    MB_TRY(phase_core(w, mid_phase(w, m, false, nA), false, scal, side));
     // What reads the node phase's results and nothing of the weight phase's runs BESIDE that phase on the bulk stream, handed to
     // its factorisation (behind the first diagonal block, as run_phase does it for one evaluation) and joined before the
     // ELBO assembly: the nodes' prior term m^T K^-1 m, and quirk Q1 (:1039-1041) -- lower(B_k^-1) = lower(X^T X) of every
     // node but the last into its B buffer (L is not needed any more: log det B is taken), then <K_j^-1, Sigma_k> for j > k.
     HIP_TRY(w, hipEventRecord(w->ev_nodes, w->stream));
-    w->chain_started = [w, m, nA]() -> int {
-        double** const cur = w->d_ptrs;
-        const int cur_slot0 = w->slot0;
-        const int* const cur_ev = w->ev.slot_eval;
+    side = [w, m, nA, scal]() -> int {
         HIP_TRY(w, hipStreamWaitEvent(w->stream2, w->ev_nodes, 0));
-        int rc = mid_prior_term(w, m, false, nA, w->stream2);
-        if (!rc && m->q > 1) {
-            w->d_ptrs = m->d_ptr_block + m->o_node;
-            rc = lauum_lower(w, (m->q - 1) * nA, w->stream2);
-            if (!rc) rc = vec_q1_evals(w, m->d_int_block + m->i_ev_node, m->Kinv, nA, m->q1_scratch, w->stream2);
+        MB_TRY(mid_prior_term(w, m, false, nA, w->stream2));
+        if (m->q > 1) {
+            const Phase nodes = mid_phase(w, m, false, nA);
+            Phase inv = nodes;
+            inv.nslots = (m->q - 1) * nA;
+            MB_TRY(lauum_lower(w, inv, w->stream2));
+            MB_TRY(vec_q1_evals(w, nodes, m->Kinv, nA, m->q1_scratch, scal + 3 * (size_t)m->G, w->stream2));
         }
-        w->d_ptrs = cur; w->slot0 = cur_slot0; w->ev.slot_eval = cur_ev;
-        if (rc) return rc;
         HIP_TRY(w, hipEventRecord(w->ev_q1, w->stream2));
         return GPRN_OK;
     };
-    MB_TRY(mid_phase(w, m, true, nA));
-    if (w->chain_started) {                              // (no factorisation took it along)
-        std::function<int()> f;
-        f.swap(w->chain_started);
-        MB_TRY(f());
-    }
+    MB_TRY(phase_core(w, mid_phase(w, m, true, nA), true, scal, side));
+    if (side) MB_TRY(side());                            // (no factorisation took it along)
     HIP_TRY(w, hipStreamWaitEvent(w->stream, w->ev_q1, 0));
     MB_TRY(mid_prior_term(w, m, true, nA, w->stream));
-    return vec_elbo_evals(w, m->d_int_block + m->i_evals, nA, out4, w->d_scal_base, w->d_elbo_part);
+    return vec_elbo_evals(w, mid_ev(m, nullptr), m->d_int_block + m->i_evals, nA, out4, scal, w->d_elbo_part);
 }
 
 struct MidIo {
@@ -370,18 +363,18 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const MidIo& io)
     HIP_TRY(c, hipMemcpyAsync(w->d_var, v0_h, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
     // ---- set-up (meanfield.py:619-622): every evaluation's G covariance matrices in one launch, chol(K) and its inverse for
     // all of them in one factorisation, log det K, and K_j^-1 = X^T X for the nodes quirk Q1 needs
-    w->ev.slot_eval = m->d_int_block + m->i_ev_setup;
     MB_TRY(launch_fill_batch(w, m->programs, (double* const*)(m->d_ptr_block + m->o_kptr), B * G,
                              (double* const*)(m->d_ptr_block + m->o_kptr2)));
     HIP_TRY(c, hipMemsetAsync(w->d_info, 0, 3 * (size_t)w->nslot * sizeof(int), st));
-    w->d_ptrs = m->d_ptr_block + m->o_setup;
-    w->slot0 = 0;
-    w->d_info_cur = w->d_info;
-    MB_TRY(factor_invert(w, B * G, true));
-    MB_TRY(vec_logdet(w, BUF_B, m->d_int_block + m->i_gp_setup, B * G, w->d_logdetK));
+    const Phase setup{m->d_ptr_block + m->o_setup, m->d_int_block + m->i_gp_setup, B * G, 0, w->d_info,
+                      mid_ev(m, m->d_int_block + m->i_ev_setup), w->N, w->ld, w->T};
+    MB_TRY(factor_invert(w, setup, true));
+    MB_TRY(vec_logdet(w, setup, BUF_B, w->d_logdetK));
     if (q > 1) {
-        w->d_ptrs = m->d_ptr_block + m->o_kinv;
-        MB_TRY(lauum_lower(w, B * (q - 1)));
+        Phase kinv = setup;
+        kinv.ptrs = m->d_ptr_block + m->o_kinv;
+        kinv.nslots = B * (q - 1);
+        MB_TRY(lauum_lower(w, kinv));
     }
     // ---- the loop of meanfield.py:626-649, per evaluation.  Quirk Q7: the first ELBOaux call (update discarded, ELBO kept
     // as elboArray[0]) and the loop's first trip are the same computation on the same input -- it runs once and its value

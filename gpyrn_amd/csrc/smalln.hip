@@ -590,18 +590,18 @@ bool small_applies(const gprn_ctx* c)
     return c->small_opt != 0 && c->T >= 1 && c->T <= max_T && !c->comm && !c->shm && !c->keep_sigma && c->world == 1;
 }
 
-int small_phase(gprn_ctx* c, bool weights, const int* d_slot_gp, int nslots, const double* mu_in, const double* var_in,
+int small_phase(gprn_ctx* c, const Phase& ph, bool weights, double* scal, const double* mu_in, const double* var_in,
                 double* mu_out, double* var_out, const int* done)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_DIAG);
-    const size_t o = (size_t)c->slot0 * c->ld;
-    SmallPhaseArgs a{(double* const*)c->d_ptrs, d_slot_gp, c->N, c->ld, c->p, c->q, c->d_yres, c->d_variance,
+    const size_t o = (size_t)ph.slot0 * ph.ld;
+    SmallPhaseArgs a{(double* const*)ph.ptrs, ph.slot_gp, ph.N, ph.ld, c->p, c->q, c->d_yres, c->d_variance,
                      mu_in, var_in, mu_out, var_out, done,
                      c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, c->d_u + o, c->d_cs + o, c->d_ct + o,
-                     c->d_trBinv, c->d_logdetB, c->d_info_cur, weights ? nullptr : c->d_small_stamps};
-#define GO(W, TT) hipLaunchKernelGGL((k_small_phase<W, TT>), dim3(nslots), dim3(256), 0, c->stream, a)
-    if (c->T == 1) { if (weights) GO(true, 1); else GO(false, 1); }
+                     scal + c->G, scal, ph.info, weights ? nullptr : c->d_small_stamps};
+#define GO(W, TT) hipLaunchKernelGGL((k_small_phase<W, TT>), dim3(ph.nslots), dim3(256), 0, c->stream, a)
+    if (ph.T == 1) { if (weights) GO(true, 1); else GO(false, 1); }
     else { if (weights) GO(true, 2); else GO(false, 2); }
 #undef GO
     prof_end(c);

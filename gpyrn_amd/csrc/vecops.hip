@@ -512,122 +512,122 @@ __global__ void k_elbo_final(int N, int p, int q, const double* __restrict__ par
 // ------------------------------------------------------------------ launchers
 #define LAUNCH_END(c) do { prof_end(c); HIP_TRY(c, hipGetLastError()); return GPRN_OK; } while (0)
 
-int vec_prep(gprn_ctx* c, bool weights, const int* d_slot_gp, int nslots)
+int vec_prep(gprn_ctx* c, const Phase& ph, bool weights)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
-    const size_t o = (size_t)c->slot0 * c->ld;
-    dim3 grid((c->ld + 255) / 256, nslots);
+    const size_t o = (size_t)ph.slot0 * ph.ld;
+    dim3 grid((ph.ld + 255) / 256, ph.nslots);
     if (weights)
-        hipLaunchKernelGGL(k_prep_weights, grid, dim3(256), 0, c->stream, d_slot_gp, c->N, c->ld,
+        hipLaunchKernelGGL(k_prep_weights, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
                            c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance,
-                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, c->ev);
+                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev);
     else
-        hipLaunchKernelGGL(k_prep_nodes, grid, dim3(256), 0, c->stream, d_slot_gp, c->N, c->ld,
+        hipLaunchKernelGGL(k_prep_nodes, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
                            c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance,
-                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, c->ev);
+                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev);
     LAUNCH_END(c);
 }
 
-int vec_build_B(gprn_ctx* c, int nslots, hipStream_t stream, int part, int outer)
+int vec_build_B(gprn_ctx* c, const Phase& ph, hipStream_t stream, int part, int outer)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_BUILD_B, stream);
-    const int T = c->T;
+    const int T = ph.T;
     int ntiles = T * (T + 1) / 2;                              // parts 0 and 2 (part 2's few part-1 tiles exit at once)
     if (part == 1) {
         ntiles = 0;
         for (int tj = 0; tj < outer && tj < T; ++tj) ntiles += T - tj;
         for (int tj = outer; tj < 2 * outer && tj < T; ++tj) ntiles += tj + 1 < T ? 2 : 1;
     }
-    hipLaunchKernelGGL(k_build_B, dim3(ntiles, nslots), dim3(256), 0, stream,
-                       (double* const*)c->d_ptrs, c->N, c->ld, c->d_s + (size_t)c->slot0 * c->ld, part, outer, T);
+    hipLaunchKernelGGL(k_build_B, dim3(ntiles, ph.nslots), dim3(256), 0, stream,
+                       (double* const*)ph.ptrs, ph.N, ph.ld, c->d_s + (size_t)ph.slot0 * ph.ld, part, outer, T);
     LAUNCH_END(c);
 }
 
-int vec_logdet(gprn_ctx* c, int buf, const int* d_slot_gp, int nslots, double* out)
+int vec_logdet(gprn_ctx* c, const Phase& ph, int buf, double* out)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
-    hipLaunchKernelGGL(k_logdet, dim3(nslots), dim3(256), 0, c->stream,
-                       (double* const*)c->d_ptrs, buf, c->N, c->ld, d_slot_gp, out, c->ev,
-                       out == c->d_logdetK ? c->ev.G : c->ev.scal);
+    hipLaunchKernelGGL(k_logdet, dim3(ph.nslots), dim3(256), 0, c->stream,
+                       (double* const*)ph.ptrs, buf, ph.N, ph.ld, ph.slot_gp, out, ph.ev,
+                       out == c->d_logdetK ? ph.ev.G : ph.ev.scal);
     LAUNCH_END(c);
 }
 
-int vec_lower_matvec(gprn_ctx* c, int buf, const double* vin, size_t vstride, int vin_by_gp,
-                     const int* d_slot_gp, int nslots, double* out, hipStream_t stream, int row0, int nrows)
+int vec_lower_matvec(gprn_ctx* c, const Phase& ph, int buf, const double* vin, size_t vstride, int vin_by_gp,
+                     double* out, hipStream_t stream, int row0, int nrows)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     if (!stream) stream = c->stream;
-    if (nrows < 0) nrows = c->ld - row0;
+    if (nrows < 0) nrows = ph.ld - row0;
     if (nrows <= 0) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC, stream);
-    hipLaunchKernelGGL(k_lower_matvec, dim3((nrows + 3) / 4, nslots), dim3(256), 0, stream,
-                       (double* const*)c->d_ptrs, buf, c->N, c->ld, vin, vstride, vin_by_gp,
-                       d_slot_gp, out, row0, c->ev);
+    hipLaunchKernelGGL(k_lower_matvec, dim3((nrows + 3) / 4, ph.nslots), dim3(256), 0, stream,
+                       (double* const*)ph.ptrs, buf, ph.N, ph.ld, vin, vstride, vin_by_gp,
+                       ph.slot_gp, out, row0, ph.ev);
     LAUNCH_END(c);
 }
 
 // partial column sums of tile rows [ch0, ch0 + nch) (nch < 0: to the last); columns right of tile row ch0 + nch - 1
 // hold nothing of these rows
-int vec_colops_partial(gprn_ctx* c, int nslots, hipStream_t stream, int ch0, int nch)
+int vec_colops_partial(gprn_ctx* c, const Phase& ph, hipStream_t stream, int ch0, int nch)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     if (!stream) stream = c->stream;
-    if (nch < 0) nch = c->T - ch0;
+    if (nch < 0) nch = ph.T - ch0;
     if (nch <= 0) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC, stream);
-    const size_t o = (size_t)c->slot0 * c->ld, po = (size_t)c->slot0 * c->T * 2 * c->ld;
-    const int ncol64 = std::min(c->ld / 64, 2 * (ch0 + nch));
-    hipLaunchKernelGGL(k_colops_partial, dim3(ncol64, nch, nslots), dim3(256), 0, stream,
-                       (double* const*)c->d_ptrs, c->ld, c->T, c->d_u + o, c->d_part + po, ch0);
+    const size_t o = (size_t)ph.slot0 * ph.ld, po = (size_t)ph.slot0 * ph.T * 2 * ph.ld;
+    const int ncol64 = std::min(ph.ld / 64, 2 * (ch0 + nch));
+    hipLaunchKernelGGL(k_colops_partial, dim3(ncol64, nch, ph.nslots), dim3(256), 0, stream,
+                       (double* const*)ph.ptrs, ph.ld, ph.T, c->d_u + o, c->d_part + po, ch0);
     LAUNCH_END(c);
 }
 
-int vec_colops_reduce(gprn_ctx* c, int nslots)
+int vec_colops_reduce(gprn_ctx* c, const Phase& ph)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
-    const size_t o = (size_t)c->slot0 * c->ld, po = (size_t)c->slot0 * c->T * 2 * c->ld;
-    hipLaunchKernelGGL(k_colops_reduce, dim3((c->ld + 255) / 256, nslots), dim3(256), 0,
-                       c->stream, c->ld, c->T, c->d_part + po, c->d_cs + o, c->d_ct + o);
+    const size_t o = (size_t)ph.slot0 * ph.ld, po = (size_t)ph.slot0 * ph.T * 2 * ph.ld;
+    hipLaunchKernelGGL(k_colops_reduce, dim3((ph.ld + 255) / 256, ph.nslots), dim3(256), 0,
+                       c->stream, ph.ld, ph.T, c->d_part + po, c->d_cs + o, c->d_ct + o);
     LAUNCH_END(c);
 }
 
-int vec_colops(gprn_ctx* c, int nslots)
+int vec_colops(gprn_ctx* c, const Phase& ph)
 {
-    int rc = vec_colops_partial(c, nslots, nullptr, 0, -1);
-    return rc ? rc : vec_colops_reduce(c, nslots);
+    int rc = vec_colops_partial(c, ph, nullptr, 0, -1);
+    return rc ? rc : vec_colops_reduce(c, ph);
 }
 
-int vec_finalize(gprn_ctx* c, const int* d_slot_gp, int nslots, bool with_logdet)
+int vec_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_logdet)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
-    const size_t o = (size_t)c->slot0 * c->ld;
-    hipLaunchKernelGGL(k_finalize, dim3(nslots), dim3(256), 0, c->stream, d_slot_gp, c->N, c->ld,
+    const size_t o = (size_t)ph.slot0 * ph.ld;
+    hipLaunchKernelGGL(k_finalize, dim3(ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
                        c->p, c->q, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, c->d_var,
-                       c->d_trBinv, with_logdet ? (double* const*)c->d_ptrs : (double* const*)nullptr, c->d_logdetB, c->ev);
+                       scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, ph.ev);
     LAUNCH_END(c);
 }
 
 // vec_colops_reduce + vec_finalize (with log det B) in one launch
-int vec_reduce_finalize(gprn_ctx* c, const int* d_slot_gp, int nslots, bool with_logdet)
+int vec_reduce_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_logdet)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     if (!c->d_fin_terms) {
         HIP_TRY(c, hipMalloc(&c->d_fin_terms, (size_t)c->nslot * 2 * c->ld * sizeof(double)));
         HIP_TRY(c, hipMalloc(&c->d_fin_tickets, (size_t)c->nslot * sizeof(unsigned)));
         HIP_TRY(c, hipMemset(c->d_fin_tickets, 0, (size_t)c->nslot * sizeof(unsigned)));
     }
     prof_begin(c, GPRN_T_VEC);
-    const size_t o = (size_t)c->slot0 * c->ld, po = (size_t)c->slot0 * c->T * 2 * c->ld;
-#define GO_RF(F) hipLaunchKernelGGL(k_reduce_finalize<F>, dim3((c->ld + 255) / 256, nslots), dim3(256), 0, c->stream, d_slot_gp, c->N, c->ld, c->T, \
-                       c->p, c->q, c->d_part + po, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, c->d_var, \
-                       c->d_trBinv, with_logdet ? (double* const*)c->d_ptrs : (double* const*)nullptr, c->d_logdetB, \
-                       c->d_fin_terms + (size_t)c->slot0 * 2 * c->ld, c->d_fin_tickets + c->slot0, c->ev)
+    const size_t o = (size_t)ph.slot0 * ph.ld, po = (size_t)ph.slot0 * ph.T * 2 * ph.ld;
+#define GO_RF(F) hipLaunchKernelGGL(k_reduce_finalize<F>, dim3((ph.ld + 255) / 256, ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, \
+                       ph.ld, ph.T, c->p, c->q, c->d_part + po, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, \
+                       c->d_var, scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, \
+                       c->d_fin_terms + (size_t)ph.slot0 * 2 * ph.ld, c->d_fin_tickets + ph.slot0, ph.ev)
     if (c->fenced_finalize) GO_RF(true); else GO_RF(false);
 #undef GO_RF
     LAUNCH_END(c);
@@ -643,13 +643,13 @@ int vec_q1(gprn_ctx* c, const double* Kinv_j, const double* Binv_k, const double
     LAUNCH_END(c);
 }
 
-int vec_dot_self(gprn_ctx* c, const int* d_slot_gp, int nslots, const double* a, double* out, hipStream_t stream)
+int vec_dot_self(gprn_ctx* c, const Phase& ph, const double* a, double* out, hipStream_t stream)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
-    hipLaunchKernelGGL(k_dot_self, dim3(nslots), dim3(256), 0, stream, d_slot_gp, c->N, c->ld,
-                       a, out, c->ev);
+    hipLaunchKernelGGL(k_dot_self, dim3(ph.nslots), dim3(256), 0, stream, ph.slot_gp, ph.N, ph.ld,
+                       a, out, ph.ev);
     LAUNCH_END(c);
 }
 
@@ -658,25 +658,27 @@ int vec_elbo(gprn_ctx* c, double* out4, const double* scal, double* part, hipStr
 {
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
+    const EvalMap one{nullptr, 0, 0, 0, 0};
     hipLaunchKernelGGL(k_loglike_partial, dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q,
-                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, (const int*)nullptr, c->ev);
+                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, (const int*)nullptr, one);
     hipLaunchKernelGGL(k_elbo_final, dim3(1), dim3(64), 0, stream, c->N, c->p, c->q, part,
                        c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4,
-                       (const int*)nullptr, c->ev);
+                       (const int*)nullptr, one);
     LAUNCH_END(c);
 }
 
 // the same for the n evaluations listed in d_evals (midn.hip): evaluation b reads its own state, variance and per-GP scalars
-// (strides c->ev) and writes out4 + 4 b; part: n x 3 * ELBO_BLOCKS doubles of scratch
-int vec_elbo_evals(gprn_ctx* c, const int* d_evals, int n, double* out4, const double* scal, double* part, hipStream_t stream)
+// (strides ev) and writes out4 + 4 b; part: n x 3 * ELBO_BLOCKS doubles of scratch
+int vec_elbo_evals(gprn_ctx* c, const EvalMap& ev, const int* d_evals, int n, double* out4, const double* scal, double* part,
+                   hipStream_t stream)
 {
     if (!n) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
     hipLaunchKernelGGL(k_loglike_partial, dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
-                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, c->ev);
+                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, ev);
     hipLaunchKernelGGL(k_elbo_final, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part,
-                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, c->ev);
+                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, ev);
     LAUNCH_END(c);
 }
 
@@ -722,16 +724,17 @@ void k_q1_sum_evals(const double* __restrict__ rowsum, const int* __restrict__ s
     if (threadIdx.x == 0) q1[(size_t)slot_eval[k * n_eval + a] * scal_stride + (size_t)j * q + k] = acc;
 }
 
-int vec_q1_evals(gprn_ctx* c, const int* d_slot_eval, const double* Kinv_slab, int n_eval, double* scratch, hipStream_t stream)
+int vec_q1_evals(gprn_ctx* c, const Phase& ph, const double* Kinv_slab, int n_eval, double* scratch, double* q1, hipStream_t stream)
 {
     const int npair = c->q * (c->q - 1) / 2;
     if (!n_eval || !npair) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
-    hipLaunchKernelGGL(k_q1_rows_evals, dim3((c->N + 3) / 4, npair * n_eval), dim3(256), 0, stream, (double* const*)c->d_ptrs,
-                       d_slot_eval, Kinv_slab, (size_t)c->ld * c->ld, c->q, n_eval, c->N, c->ld, c->d_s, scratch);
-    hipLaunchKernelGGL(k_q1_sum_evals, dim3(npair * n_eval), dim3(256), 0, stream, (const double*)scratch, d_slot_eval, c->q,
-                       n_eval, c->N, c->ld, c->d_q1, c->ev.scal);
+    hipLaunchKernelGGL(k_q1_rows_evals, dim3((ph.N + 3) / 4, npair * n_eval), dim3(256), 0, stream, (double* const*)ph.ptrs,
+                       ph.ev.slot_eval, Kinv_slab, (size_t)ph.ld * ph.ld, c->q, n_eval, ph.N, ph.ld, c->d_s + (size_t)ph.slot0 * ph.ld,
+                       scratch);
+    hipLaunchKernelGGL(k_q1_sum_evals, dim3(npair * n_eval), dim3(256), 0, stream, (const double*)scratch, ph.ev.slot_eval, c->q,
+                       n_eval, ph.N, ph.ld, q1, ph.ev.scal);
     LAUNCH_END(c);
 }
 
@@ -892,12 +895,12 @@ void k_pred_rows(double* const* __restrict__ ptrs, int ns, int N, int ld, int ns
     }
 }
 
-int vec_pred_rows(gprn_ctx* c, int nslots, int ns, int ns_pad, const double* sol, const double* kss,
+int vec_pred_rows(gprn_ctx* c, const Phase& ph, int ns, int ns_pad, const double* sol, const double* kss,
                   double* mean, double* var)
 {
-    if (!nslots) return GPRN_OK;
+    if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
-    hipLaunchKernelGGL(k_pred_rows, dim3((ns + 3) / 4, nslots), dim3(256), 0, c->stream,
-                       (double* const*)c->d_ptrs, ns, c->N, c->ld, ns_pad, sol, kss, mean, var);
+    hipLaunchKernelGGL(k_pred_rows, dim3((ns + 3) / 4, ph.nslots), dim3(256), 0, c->stream,
+                       (double* const*)ph.ptrs, ns, ph.N, ph.ld, ns_pad, sol, kss, mean, var);
     LAUNCH_END(c);
 }
