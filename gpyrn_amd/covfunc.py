@@ -85,21 +85,9 @@ class covFunction:
     # -- derivatives in the hyper-parameters (not in the reference: SURVEY.md 8f-3) ----------
     def _dk_dpars(self, r):
         """``[dK/dpars[0], dK/dpars[1], ...]`` on the array of time differences `r`.  The base version
-        differentiates ``self(r)`` numerically (central differences, relative step 1e-6), which serves
-        every kernel, user subclasses included; built-ins with a closed form override it."""
-        out = []
-        keep = self.pars.copy()
-        try:
-            for i, v in enumerate(keep):
-                h = 1e-6 * max(1.0, abs(v))
-                self.pars = keep.copy(); self.pars[i] = v + h
-                up = np.asarray(self(r), dtype=float)
-                self.pars = keep.copy(); self.pars[i] = v - h
-                dn = np.asarray(self(r), dtype=float)
-                out.append((up - dn) / (2 * h))
-        finally:
-            self.pars = keep
-        return out
+        differentiates ``self(r)`` numerically (``_richardson``), which serves every kernel, user subclasses
+        included; built-ins with a closed form override it."""
+        return _richardson(self, lambda: np.asarray(self(r), dtype=float))
 
     # -- algebra -------------------------------------------------------------
     def __add__(self, other):
@@ -124,6 +112,29 @@ class covFunction:
             return None
         pars = np.asarray(self._device_pars(), dtype=float).ravel()
         return [(OP_PUSH, type(self)._device_id, 0)], pars
+
+
+def _richardson(kernel, evaluate):
+    """d evaluate() / d kernel.pars[i] for every i: Richardson's extrapolation (4 D(h/2) - D(h)) / 3 of central
+    differences D(s) = (f(v + s) - f(v - s)) / 2s, h = 1e-6 max(1, |v|) -- the rule of the device's gprn_grad_kernel
+    (csrc/fill.hip, launch_grad_fd), so that the two stay comparable.  Its truncation error is O((h w)^4), w the rate at
+    which the parameter moves the kernel's phase or exponent: a plain central difference is O((h w)^2), ~1e-6 relative
+    for a period of 0.3 over a span of 60."""
+    out = []
+    keep = kernel.pars.copy()
+    try:
+        for i, v in enumerate(keep):
+            h = 1e-6 * max(1.0, abs(v))
+            d = []
+            for s in (h, 0.5 * h):
+                kernel.pars = keep.copy(); kernel.pars[i] = v + s
+                up = evaluate()
+                kernel.pars = keep.copy(); kernel.pars[i] = v - s
+                d.append((up - evaluate()) / (2 * s))
+            out.append((4 * d[1] - d[0]) / 3)
+    finally:
+        kernel.pars = keep
+    return out
 
 
 def _is_builtin(cls):

@@ -62,9 +62,12 @@ __device__ __forceinline__ double exp_neg(double x)
 // a / b correctly rounded (but for a sliver of near-halfway cases) from rb = RN(1 / b): one residual, one correction -- two
 // FMAs where the IEEE division sequence is ~10 quarter-rate instructions.  The reference divides (NumPy: x / ell**2), and on
 // a prior matrix with cond(K) ~ 1e9 the last bits of K's entries are worth 1e-8 on m^T K^-1 m (profiles/r06_fill_rounding.txt).
+// Where a * rb is not finite -- rb = inf because b is below ~5.6e-309 (ell^2 subnormal), or the quotient overflows -- the
+// correction would make NaN of what NumPy's division makes -0, +-inf or a number: that rare case divides.
 __device__ __forceinline__ double div_rn(double a, double b, double rb)
 {
     const double q = a * rb;
+    if (!isfinite(q)) return a / b;
     return fma(fma(-q, b, a), rb, q);
 }
 
@@ -72,9 +75,11 @@ __device__ __forceinline__ double div_rn(double a, double b, double rb)
 // argument is the ROUNDED product / quotient, several hundred periods out, so its rounding error (|x| 1.1e-16 absolute) is part
 // of the reference's value: sinpi_sq of the exact fraction |r| / P is closer to the mathematical kernel but differs from
 // NumPy's by tens to hundreds of ulp of K (mean 34, max 589 at |x| ~ 110), which the Cholesky of an ill-conditioned prior
-// amplifies.  Reduction by pi in three words (Cody-Waite: the first two have 33 bits, n pi_A and n pi_B are exact for
-// n < 2^19 -- |x| < 1.6e6, i.e. 5e5 periods), then sin on [0, pi/4] by its Taylor polynomial of degree 19 (next term 8e-20)
-// and, beyond pi/4, 1 - sin^2(pi/2 - g).
+// amplifies.  Reduction by pi in three words (Cody-Waite, each step one FMA: the first, x - n pi_A, is exact while its result
+// fits 53 bits above pi_A's last bit 2^-31, i.e. for |x| up to ~1e16; n pi_C then carries the reduction's error below an
+// ulp of g), then sin on [0, pi/4] by its Taylor polynomial of degree 19 (next term 8e-20) and, beyond pi/4,
+// 1 - sin^2(pi/2 - g).  Measured on gfx950 (tests/test_fill_gpu.py, the R5 cases of tests/golden/fill_highprec): within
+// a few ulp of the exact sin^2 of the rounded argument for |x| up to 1e12, the largest argument the tests pin.
 __device__ __forceinline__ double sin_sq_rad(double x)
 {
     const double n = rint(x * 0.318309886183790671538);
@@ -99,8 +104,13 @@ __device__ __forceinline__ double sin_sq_rad(double x)
     return hi ? 1.0 - s2 : s2;
 }
 
+// The element formulas below round as they are written -- as NumPy does, which has no fused multiply-add: a contraction the
+// compiler chose per call site made K differ from K^T, the full-matrix fill from the symmetric one and a kernel's own
+// instantiation from the generic program in the last bit (Matern52, HarmonicPeriodic: tests/test_fill_gpu.py).  The
+// hand-written exp_neg, div_rn and sin_sq_rad above spell their FMAs out.
 __device__ __forceinline__ void harmonic_terms(double Nh, double P, double t, double& s, double& u)
 {
+#pragma clang fp contract(off)
     // covfunc.py:599-605 with its precedence: sin(phase)/2*sin(half)
     const double phase = (Nh + 0.5) * 2 * PI_D * t / P;
     const double half = PI_D * t / P;
@@ -111,6 +121,7 @@ __device__ __forceinline__ void harmonic_terms(double Nh, double P, double t, do
 __device__ __forceinline__ double eval_kernel(int kid, const double* __restrict__ q,
                                               double ti, double tj, bool diag, const double* __restrict__ aux = nullptr)
 {
+#pragma clang fp contract(off)
     const double r = ti - tj;
     switch (kid) {
     case GPRN_K_CONSTANT: return q[0] * q[0];
@@ -127,8 +138,7 @@ __device__ __forceinline__ double eval_kernel(int kid, const double* __restrict_
         const double x = GPRN_FILL_FAST ? div_rn(-0.5 * (r * r), l2, aux ? aux[0] : 1.0 / l2) : -0.5 * (r * r) / l2;
         return q[0] * q[0] * (GPRN_FILL_FAST ? exp_neg(x) : exp(x));
     }
-    // (sin(pi |r| / P) through the fraction of |r| / P, not through sin on an argument of several hundred periods, whose
-    // reduction is a multi-word product)
+    // (sin^2 of the reference's rounded argument pi |r| / P, reduced by pi in three words: sin_sq_rad)
     case GPRN_K_PERIODIC: {           // theta**2 * exp(-2 * sin(pi * |r| / P)**2 / ell**2)
         const double l2 = q[2] * q[2];
         double x;
@@ -239,6 +249,7 @@ __device__ __forceinline__ double eval_kernel(int kid, const double* __restrict_
 
 __device__ __forceinline__ double eval_program(const FillProgram& pg, double ti, double tj, bool diag)
 {
+#pragma clang fp contract(off)
     double st[8];
     int sp = 0;
     for (int o = 0; o < pg.n_ops; ++o) {
@@ -393,12 +404,16 @@ static void make_program(const KernelSpec& ks, double nugget_val, FillProgram& p
 }
 
 // ---- gradient of the ELBO in the hyper-parameters of ANY kernel program: per parameter l
-//   < 1/2 (P - Kinv + a a^T), (K(theta + h e_l) - K(theta - h e_l)) / 2h >,
-// the central difference of the program itself (relative step 1e-6, as covFunction._dk_dpars does on the host for
-// kernels without a closed form), evaluated and contracted on the fly: one wave per row, rows summed in a fixed order.
-// Nothing N x N is written or leaves the GPU.  The nugget is a constant of the parameters and drops out.
+//   < 1/2 (P - Kinv + a a^T), dK/dtheta_l >,
+// dK/dtheta_l by Richardson's extrapolation of two central differences of the program itself, steps h and h/2 with
+// h = 1e-6 max(1, |theta_l|) -- as covFunction._dk_dpars does on the host for kernels without a closed form:
+//   (4 D(h/2) - D(h)) / 3,   D(s) = (K(theta + s e_l) - K(theta - s e_l)) / 2s,
+// whose truncation error is O((h w)^4), w the rate at which theta_l moves the kernel's phase or exponent (a plain central
+// difference, O((h w)^2), was ~1e-6 relative at P = 0.3 over a span of 60), evaluated and contracted on the fly: one wave
+// per row, rows summed in a fixed order.  Nothing N x N is written or leaves the GPU.  The nugget is a constant of the
+// parameters and drops out.  part[m] = (accumulate ? part[m] : 0) + coef * sum_n G[m][n] (K+ - K-)[m][n].
 __global__ __launch_bounds__(256)
-void k_grad_fd_rows(FillProgram pp, FillProgram pm, double inv2h, const double* __restrict__ t,
+void k_grad_fd_rows(FillProgram pp, FillProgram pm, double coef, int accumulate, const double* __restrict__ t,
                     const double* __restrict__ Kinv, const double* __restrict__ P, const double* __restrict__ a,
                     int N, int ld, double* __restrict__ part /* N */)
 {
@@ -413,7 +428,7 @@ void k_grad_fd_rows(FillProgram pp, FillProgram pm, double inv2h, const double* 
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (lane == 0) part[m] = acc * inv2h;
+    if (lane == 0) part[m] = (accumulate ? part[m] : 0.0) + acc * coef;
 }
 
 __global__ __launch_bounds__(256)
@@ -441,10 +456,15 @@ int launch_grad_fd(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const 
         make_program(ks, 0.0, pp);
         make_program(ks, 0.0, pm);
         const double v = ks.params[l], h = 1e-6 * fmax(1.0, fabs(v));
-        pp.par[l] = v + h;
-        pm.par[l] = v - h;
-        hipLaunchKernelGGL(k_grad_fd_rows, dim3((c->N + 3) / 4), dim3(256), 0, c->stream, pp, pm, 1.0 / (2 * h), c->d_time,
-                           Kinv, P, a, c->N, c->ld, part);
+        // -D(h) / 3, then + 4 D(h/2) / 3 (the same steps and weights as covfunc._richardson)
+        for (int k = 0; k < 2; ++k) {
+            const double s = k ? 0.5 * h : h;
+            pp.par[l] = v + s;
+            pm.par[l] = v - s;
+            const double coef = (k ? 4.0 : -1.0) / (3.0 * (2 * s));
+            hipLaunchKernelGGL(k_grad_fd_rows, dim3((c->N + 3) / 4), dim3(256), 0, c->stream, pp, pm, coef, k, c->d_time,
+                               Kinv, P, a, c->N, c->ld, part);
+        }
         hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(256), 0, c->stream, (const double*)part, c->N, out + l);
     }
     prof_end(c);

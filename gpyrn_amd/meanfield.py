@@ -933,8 +933,8 @@ class inference:
           (S, m) the reference pairs with that kernel -- quirks included: node j meets the cumulative
           ``Sigma_f0 + ... + Sigma_fj`` (Q1), weight (j, i) the raw-reshape row of ``mu_w`` (Q2).  The
           N^3 work (K^-1, K^-1 S K^-1) runs on the GPU (``gprn_grad_matrices``); ``dK/dtheta`` comes from
-          ``covFunction._dk_dpars`` (closed forms for SquaredExponential, Periodic, QuasiPeriodic; central
-          differences of ``kernel(r)`` otherwise, user kernels included).
+          ``covFunction._dk_dpars`` (closed forms for SquaredExponential, Periodic, QuasiPeriodic; Richardson-extrapolated
+          central differences of ``kernel(r)`` otherwise, user kernels included).
         * jitters enter through the expected log likelihood (meanfield.py:895-990), in closed form.
         * mean-function parameters: at a fixed variational state, zero -- the reference's likelihood term reads
           the RAW data (quirk Q3), so the reported ELBO does not see them.  They act through the residual
@@ -1037,16 +1037,8 @@ class inference:
             Kinv, P = matrices(gp)
             a = Kinv @ m
             G = 0.5 * (P - Kinv + np.outer(a, a)) / q        # ELBO = (...) / q, meanfield.py:709
-            if isinstance(kernel, _TWO_ARGUMENT):
-                keep = kernel.pars.copy()
-                dks = []
-                for i, v in enumerate(keep):                  # kernel(t_i, t_j): differences only
-                    h = 1e-6 * max(1.0, abs(v))
-                    kernel.pars = keep.copy(); kernel.pars[i] = v + h
-                    up = kernel(t[:, None], t[None, :])
-                    kernel.pars = keep.copy(); kernel.pars[i] = v - h
-                    dks.append((up - kernel(t[:, None], t[None, :])) / (2 * h))
-                kernel.pars = keep
+            if isinstance(kernel, _TWO_ARGUMENT):             # kernel(t_i, t_j): differences only
+                dks = covfunc._richardson(kernel, lambda: np.asarray(kernel(t[:, None], t[None, :]), dtype=float))
             else:
                 dks = kernel._dk_dpars(r)
             grads += [float(np.sum(G * dk)) for dk in dks]

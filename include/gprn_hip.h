@@ -172,8 +172,12 @@ int gprn_grad_matrices(gprn_ctx* ctx, int gp, double* Kinv_out, double* P_out);
 /* the contraction as well on the device: grad_out[l] = < 1/2 (K^-1 S K^-1 + a a^T - K^-1), dK/dtheta_l >, l < n_params,
  * a = K^-1 m (m: N values, the mean the reference pairs with that kernel; the 1/q of meanfield.py:709 is left to the
  * caller).  dK/dtheta in closed form for a single SquaredExponential, Periodic or QuasiPeriodic (the formulas of
- * covFunction._dk_dpars), by central differences of the kernel program (relative step 1e-6) for every other kernel
- * gprn_set_kernel accepted.  GPRN_E_UNSUPPORTED for a latent GP whose matrix was uploaded (gprn_upload_K). */
+ * covFunction._dk_dpars), by Richardson's extrapolation of central differences of the kernel program (steps h and h/2,
+ * h = 1e-6 max(1, |theta|), as covfunc._richardson) for every other kernel gprn_set_kernel accepted.  Accuracy, pinned by
+ * tests/test_fill_gpu.py against a long-double reference dK/dtheta: closed forms within 1e-12 sum |G| |dK/dtheta|,
+ * differences within 1e-7 sum |G| |dK/dtheta| + 8 2^-53 sum |G| |K| / h (G = 1/2 (K^-1 S K^-1 + a a^T - K^-1); the second
+ * term is the rounding of K that any difference of step h carries), periods down to 0.3 over a span of 60 and length
+ * scales down to a third of the sampling included.  GPRN_E_UNSUPPORTED for a latent GP whose matrix was uploaded (gprn_upload_K). */
 int gprn_grad_kernel(gprn_ctx* ctx, int gp, const double* m, double* grad_out);
 
 /* ---- the terms of the ELBO on their own: what the reference's private step methods return (meanfield.py:895-990 and
