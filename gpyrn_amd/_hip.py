@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GPRN_HIP_LIB') or os.path.join(_HERE, 'libgprn_hip.so')
 
 GPRN_E_ARG, GPRN_E_HIP, GPRN_E_NODEV, GPRN_E_COMM, GPRN_E_NOMEM, GPRN_E_UNSUPPORTED = -1, -2, -3, -4, -5, -6
+COV_JOINT = 1
 M_K, M_KLINV, M_SIGMA, M_BX, M_BL = 0, 1, 2, 3, 4
 T_NAMES = ('fill', 'build_B', 'diag', 'panel', 'update', 'lauum', 'vec', 'update_ahead')
 TILE = 128
@@ -52,6 +53,9 @@ SIGNATURES = {
     'gprn_sweep': (c_int, [c_void_p, c_int, c_int, _dp, _dp]),
     'gprn_predict': (c_int, [c_void_p, c_int, _dp, _dp, _dp]),
     'gprn_predict_upload': (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp]),
+    'gprn_predict_cov': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp]),
+    'gprn_predict_draws': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp]),
+    'gprn_predict_upload_kss': (c_int, [c_void_p, c_int, c_int, _dp]),
     'gprn_get_scalars': (c_int, [c_void_p, _dp]),
     'gprn_keep_sigma': (c_int, [c_void_p, c_int]),
     'gprn_get_matrix': (c_int, [c_void_p, c_int, c_int, _dp]),
@@ -265,6 +269,42 @@ class Context:
         kss = _f64(np.ravel(kss), (Kstar.shape[0],))
         self._check(self._lib.gprn_predict_upload(self._h, int(gp), Kstar.shape[0], _ptr(K_tiny), _ptr(Kstar),
                                                   _ptr(kss)), 'predict_upload')
+
+    def predict_upload_kss(self, gp, Kss):
+        """Host-evaluated K** (n*, n*) of latent GP `gp` for the next predict_cov() / predict_draws()."""
+        Kss = _f64(np.atleast_2d(Kss))
+        if Kss.shape[0] != Kss.shape[1]:
+            raise ValueError('Kss must be square')
+        self._check(self._lib.gprn_predict_upload_kss(self._h, int(gp), Kss.shape[0], _ptr(Kss)), 'predict_upload_kss')
+
+    def predict_cov(self, tstar, joint=False, latent=True, outputs=True):
+        """Latent means (G, n*), latent covariances (G, n*, n*) or None, and the per-output covariance -- (p, n*, n*), or
+        (p n*, p n*) with `joint` -- or None (gprn_predict_cov; the jitters last set)."""
+        ts = _f64(np.ravel(tstar))
+        ns = ts.size
+        mean = np.zeros((self.G, ns))
+        lat = np.empty((self.G, ns, ns)) if latent else None
+        out = (np.empty((self.p * ns, self.p * ns)) if joint else np.empty((self.p, ns, ns))) if outputs else None
+        self._check(self._lib.gprn_predict_cov(self._h, ns, _ptr(ts), COV_JOINT if joint else 0, _ptr(mean),
+                                               _ptr(lat) if latent else None, _ptr(out) if outputs else None),
+                    'predict_cov')
+        return mean, lat, out
+
+    def predict_draws(self, tstar, z, outputs=True):
+        """Joint posterior draws from standard normals z (G, n, n*): (latent draws (G, n, n*), sum_j w o f per output
+        (p, n, n*) or None, the nugget of every latent GP (G), info)."""
+        ts = _f64(np.ravel(tstar))
+        ns = ts.size
+        z = _f64(z)
+        if z.ndim != 3 or z.shape[0] != self.G or z.shape[2] != ns:
+            raise ValueError(f'z must be (G, n, n*) = ({self.G}, n, {ns})')
+        nd = z.shape[1]
+        lat = np.empty((self.G, nd, ns))
+        out = np.empty((self.p, nd, ns)) if outputs else None
+        nug = np.zeros(self.G)
+        info = self._check(self._lib.gprn_predict_draws(self._h, ns, _ptr(ts), nd, _ptr(z), _ptr(lat),
+                                                        _ptr(out) if outputs else None, _ptr(nug)), 'predict_draws')
+        return lat, out, nug, info
 
     def get_scalars(self):
         """Per-GP scalars of the last sweep: dict of log det B (G), tr B^-1 (G), m^T K^-1 m (G), Q1 traces (q, q)."""

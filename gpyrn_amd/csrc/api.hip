@@ -512,6 +512,7 @@ extern "C" int gprn_set_jitters(gprn_ctx* c, const double* jit)
         for (int n = 0; n < c->N; ++n)
             v[(size_t)i * c->N + n] = jit[i] * jit[i] + c->h_yerr2[(size_t)i * c->N + n];
     HIP_TRY(c, hipMemcpy(c->d_variance, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->h_jit.assign(jit, jit + c->p);
     c->have_jit = true;
     return GPRN_OK;
 }

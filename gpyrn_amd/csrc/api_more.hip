@@ -1,4 +1,5 @@
-// C ABI of libgprn_hip.so (include/gprn_hip.h): prediction (meanfield.py:1289-1400), kernel matrices and prior draws (:413-434,
+// C ABI of libgprn_hip.so (include/gprn_hip.h): prediction (meanfield.py:1289-1400) with full predictive covariances and joint
+// posterior draws, kernel matrices and prior draws (:413-434,
 // 517-539), the gradient's pieces, the ELBO's terms on their own (:895-1093), diagnostics.
 #include "api_internal.h"
 
@@ -8,7 +9,12 @@
 // (meanfield.py:1289-1381): cov = K + 1.25e-12 I + diag(var), sol = cov^-1 mu,
 // mean* = K* sol, var*_i = k(t*_i,t*_i) + 1.25e-12 - |L^-1 K*_i|^2.  Here: fused fills,
 // the blocked factor+inverse (X = L^-1), sol = X^T X mu, W^T = K* X^T by the tile kernel.
-static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out);
+// after (may be empty): more work on the device state of the call once the latent means are formed -- gprn_predict_cov /
+// gprn_predict_draws, below.  gps: slot -> latent GP; mean: (slots, ns_pad); WT: per slot W^T = K* X^T (ns_pad x ld).
+struct PredState { const std::vector<int>& gps; int ns, ns_pad; const double* d_ts; const double* d_mean; };
+typedef std::function<int(const PredState&)> PredAfter;
+static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out,
+                        const PredAfter& after = PredAfter());
 
 // Host-evaluated matrices of latent GP `gp` for the next gprn_predict call with the same `ns`: what a user-defined
 // covFunction subclass -- whose K reached the device through gprn_upload_K -- needs in place of the fused fills.
@@ -61,7 +67,7 @@ extern "C" int gprn_predict(gprn_ctx* c, int ns, const double* tstar, double* me
     return rc;
 }
 
-static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out)
+static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out, const PredAfter& after)
 {
     TRY(build_tables(c));
     std::vector<int> gps = c->loc_nodes;
@@ -163,6 +169,7 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
         PHIP(hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
         PTRY(launch_tiles(c, d_t, tasks.size(), pred.ptrs, nloc, ld, GPRN_T_UPDATE));
         PTRY(vec_pred_rows(c, pred, ns, ns_pad, c->d_ct, d_kss, d_mean, d_pvar));
+        if (after) PTRY(after(PredState{gps, ns, ns_pad, d_ts, d_mean}));
     }
     if (gather) {
         // every rank ends up with every latent GP's rows: the owners' results travel as one grouped broadcast
@@ -204,6 +211,450 @@ done:
     hipStreamSynchronize(c->stream);
     dev_free(d_ts); dev_free(d_kss); dev_free(d_mean); dev_free(d_pvar); dev_free(d_t); dev_free(d_all);
     return rc;
+}
+
+// ------------------------------------------------------------------ predictive covariances and joint draws
+// The reference's _gp.GP.prediction (_gp.py:125-137) forms the whole conditional covariance of a latent GP g,
+//     C_g = K**_g - K*_g (K_g + 1.25e-12 I + diag v_g)^-1 K*_g^T        (no nugget in K_g / K** for the two-argument kernels)
+// and keeps its diagonal; inference._Prediction (meanfield.py:1346-1373) combines those diagonals.  Here the matrices stay:
+// predict_impl leaves W^T = K* X^T (X = L^-1, ns_pad x ld per latent GP); K** is filled at t* (launch_fill_times, identity
+// padding), C = K** - W W^T runs on the tile kernel (lower tiles, K = ld; TG_COV: C's pitch is ns_pad), and the upper
+// triangle is mirrored from the lower one, so that every returned matrix is exactly symmetric.
+// Per output i, under the mean-field independence of the latent GPs (f_j = node j, w_ij = weight (j, i)):
+//     Cov(y_i(t), y_i(t')) = sum_j [ w_ij(t) w_ij(t') C_fj + C_wij (C_fj + f_j(t) f_j(t')) ] + q jitter_i^2 delta(t, t')
+//     Cov(y_i(t), y_k(t')) = sum_j w_ij(t) w_kj(t') C_fj(t, t')                              (i != k)
+// (bars dropped: the w and f there are the predictive means).  The diagonal is _Prediction's predictivesVar, with its
+// quirk of adding jitter_i^2 once per node (meanfield.py:1372-1373) -- kept.
+// Draws: C_g + nu_g I = L_g L_g^T by the blocked factorisation, nu_g = 1.25e-12 x 100^k up to 1.25e-6 (the ladder of
+// inference._sample_from_gp), latent draw = mean + L z, output draw sum_j w_ij o f_j (mean functions and noise: host).
+
+#define GPRN_COV_BLK 32
+// the lower 32 x 32 blocks of an n x n grid, block L -> (bi, bj), bi >= bj
+__device__ __forceinline__ void lower_block(int L, int& bi, int& bj)
+{
+    bi = (int)((sqrt(8.0 * L + 1.0) - 1.0) * 0.5);
+    while ((bi + 1) * (bi + 2) / 2 <= L) ++bi;
+    while (bi * (bi + 1) / 2 > L) --bi;
+    bj = L - bi * (bi + 1) / 2;
+}
+
+// upper triangle := lower triangle, every matrix of the table (pitch n_pad, all n_pad rows); block (bi, bj) of the
+// lower triangle goes through LDS to (bj, bi).  grid (lower blocks, matrices)
+__global__ __launch_bounds__(256)
+void k_mirror_lower(double* const* __restrict__ Ms, int n_pad)
+{
+    __shared__ double tile[GPRN_COV_BLK][GPRN_COV_BLK + 1];
+    double* const M = Ms[blockIdx.y];
+    int bi, bj;
+    lower_block(blockIdx.x, bi, bj);
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int r = ty; r < GPRN_COV_BLK; r += 8)
+        tile[r][tx] = M[(size_t)(bi * GPRN_COV_BLK + r) * n_pad + bj * GPRN_COV_BLK + tx];
+    __syncthreads();
+    for (int r = ty; r < GPRN_COV_BLK; r += 8) {
+        const int row = bj * GPRN_COV_BLK + r, col = bi * GPRN_COV_BLK + tx;
+        if (col > row) M[(size_t)row * n_pad + col] = tile[tx][r];
+    }
+}
+
+// dst = src + nu I on the first n diagonal entries (everything else, padding included, copied as it is): the matrix a rung
+// of the ladder factors.  grid (n_pad rows, matrices); src[b], dst[b], nu[b] per matrix
+__global__ __launch_bounds__(256)
+void k_shift_copy(const double* const* __restrict__ src, double* const* __restrict__ dst, const double* __restrict__ nu,
+                  int n, int n_pad)
+{
+    const int row = blockIdx.x, b = blockIdx.y;
+    const double* s = src[b] + (size_t)row * n_pad;
+    double* d = dst[b] + (size_t)row * n_pad;
+    for (int col = 2 * threadIdx.x; col < n_pad; col += 512) {
+        double2 v = *(const double2*)(s + col);
+        if (col == row && row < n) v.x += nu[b];
+        if (col + 1 == row && row < n) v.y += nu[b];
+        *(double2*)(d + col) = v;
+    }
+}
+
+// zeros above the diagonal of every 128 x 128 diagonal tile of L (the factorisation leaves the input there; the product
+// L Z reads those tiles whole).  grid (tiles, matrices)
+__global__ __launch_bounds__(256)
+void k_zero_diag_upper(double* const* __restrict__ Ls, int n_pad)
+{
+    double* const L = Ls[blockIdx.y] + (size_t)blockIdx.x * GPRN_TILE * n_pad + (size_t)blockIdx.x * GPRN_TILE;
+    for (int idx = threadIdx.x; idx < GPRN_TILE * GPRN_TILE; idx += 256) {
+        const int r = idx / GPRN_TILE, col = idx % GPRN_TILE;
+        if (col > r) L[(size_t)r * n_pad + col] = 0.0;
+    }
+}
+
+// Per-output covariance from the latent covariances Cs[g] (symmetric, pitch ns_pad, g = latent GP index) and the predictive
+// means mean[g][t] (pitch ns_pad).  joint = 0: out (p, ns, ns), output i = blockIdx.y; joint = 1: out (M, M), M = p ns, row
+// R = i ns + t.  Each workgroup takes one lower 32 x 32 block of an output matrix, writes it and its mirror image (LDS
+// transpose): exactly symmetric, and only the lower half of the latent matrices is read.  Memory-bound: per lower element
+// 2q (diagonal blocks i = k) or q (cross blocks) doubles are read and two are written.
+__global__ __launch_bounds__(256)
+void k_output_cov(const double* const* __restrict__ Cs, const double* __restrict__ mean, const double* __restrict__ jit2,
+                  int q, int p, int ns, int ns_pad, int joint, double* __restrict__ out)
+{
+    __shared__ double tile[GPRN_COV_BLK][GPRN_COV_BLK + 1];
+    const int M = joint ? p * ns : ns;
+    double* const O = out + (joint ? 0 : (size_t)blockIdx.y * ns * ns);
+    int bi, bj;
+    lower_block(blockIdx.x, bi, bj);
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int S = bj * GPRN_COV_BLK + tx;
+    const int k = joint ? (S < M ? S / ns : 0) : blockIdx.y, u = joint ? S - k * ns : S;
+    for (int r = ty; r < GPRN_COV_BLK; r += 8) {
+        const int R = bi * GPRN_COV_BLK + r;
+        double v = 0.0;
+        if (R < M && S < M && R >= S) {
+            const int i = joint ? R / ns : blockIdx.y, t = joint ? R - i * ns : R;
+            for (int j = 0; j < q; ++j) {
+                const int gi = q + j * p + i, gk = q + j * p + k;
+                const double cf = Cs[j][(size_t)t * ns_pad + u];
+                const double a = mean[(size_t)gi * ns_pad + t] * mean[(size_t)gk * ns_pad + u];
+                if (i == k) {
+                    // (meanfield.py:1372-1373, term by term: w w C_f + C_w (C_f + f f) + jitter^2, once per node)
+                    double term = a * cf + Cs[gi][(size_t)t * ns_pad + u] *
+                                               (cf + mean[(size_t)j * ns_pad + t] * mean[(size_t)j * ns_pad + u]);
+                    if (t == u) term += jit2[i];
+                    v += term;
+                } else
+                    v += a * cf;
+            }
+            O[(size_t)R * M + S] = v;
+        }
+        tile[r][tx] = v;
+    }
+    __syncthreads();
+    for (int r = ty; r < GPRN_COV_BLK; r += 8) {
+        const int row = bj * GPRN_COV_BLK + r, col = bi * GPRN_COV_BLK + tx;
+        if (row < M && col < M && col > row) O[(size_t)row * M + col] = tile[tx][r];
+    }
+}
+
+// Draw combination: lat[g][d][t] = mean[g][t] + LZ[g][d][t], out[i][d][t] = sum_j lat[w_ij][d][t] lat[f_j][d][t] (out may be
+// null).  LZ: per latent GP, rows d of pitch ns_pad.  grid ((ns + 255) / 256, draws)
+__global__ __launch_bounds__(256)
+void k_draw_combine(const double* const* __restrict__ LZ, const double* __restrict__ mean, int q, int p, int ns, int ns_pad,
+                    int nd, double* __restrict__ lat, double* __restrict__ out)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
+    if (t >= ns) return;
+    const int G = q * (p + 1);
+    auto val = [&](int g) { return mean[(size_t)g * ns_pad + t] + LZ[g][(size_t)d * ns_pad + t]; };
+    for (int g = 0; g < G; ++g) lat[((size_t)g * nd + d) * ns + t] = val(g);
+    if (!out) return;
+    for (int i = 0; i < p; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < q; ++j) s += val(q + j * p + i) * val(j);
+        out[((size_t)i * nd + d) * ns + t] = s;
+    }
+}
+
+// What one call of gprn_predict_cov / gprn_predict_draws asks for
+struct CovRequest {
+    int flags = 0;
+    double* latent_cov = nullptr;     // (G, ns, ns)
+    double* out_cov = nullptr;        // (p, ns, ns) or (p ns, p ns)
+    int n_draws = 0;                  // > 0: draws instead of covariances
+    const double* z = nullptr;        // (G, n_draws, ns)
+    double* latent_draws = nullptr;   // (G, n_draws, ns)
+    double* out_draws = nullptr;      // (p, n_draws, ns)
+    double* nugget_out = nullptr;     // (G)
+    int info = 0;                     // > 0: the pivot at which C_{info_gp} + 1.25e-6 I failed
+    int info_gp = -1;
+};
+
+static int device_table(gprn_ctx* c, double*** d_tab, const std::vector<double*>& rows)
+{
+    TRY(dev_alloc(c, d_tab, rows.size()));
+    HIP_TRY(c, hipMemcpy(*d_tab, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice));
+    return GPRN_OK;
+}
+
+// runs behind predict_impl's means (PredAfter): every latent GP is local (one rank), slot s = latent GP s
+static int cov_after(gprn_ctx* c, const PredState& st, CovRequest& rq)
+{
+    const int G = c->G, ns = st.ns, ns_pad = st.ns_pad, Ts = ns_pad / GPRN_TILE, ld = c->ld;
+    const size_t nn = (size_t)ns_pad * ns_pad;
+    const int nd = rq.n_draws, nd_pad = ((std::max(nd, 1) + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+    const bool draws = nd > 0;
+    // device memory of the call: C (G ns_pad^2); draws: the factor's B and X (2 G ns_pad^2), Z and L Z (2 G nd_pad ns_pad)
+    double *d_C = nullptr, *d_F = nullptr, *d_X = nullptr, *d_Z = nullptr, *d_LZ = nullptr, *d_out = nullptr, *d_lat = nullptr;
+    double *d_jit2 = nullptr, *d_nu = nullptr;
+    double **t_pred = nullptr, **t_C = nullptr, **t_fac = nullptr, **t_src = nullptr, **t_dst = nullptr, **t_L = nullptr,
+           **t_mm = nullptr, **t_LZ = nullptr;
+    int* d_inf = nullptr;
+    TileTask* d_t = nullptr;
+    int rc = GPRN_OK;
+    std::vector<double*> rows;
+    std::vector<TileTask> tasks;
+    auto fail_mem = [&](int r) {
+        if (r == GPRN_E_NOMEM)
+            c->err = "predict_cov: out of device memory for " + std::to_string(G) + " covariance matrices of " +
+                     std::to_string(ns) + " x " + std::to_string(ns) + (draws ? " and their factors" : "") + " (" + c->err + ")";
+        return r;
+    };
+#define CTRY(expr) do { rc = (expr); if (rc) goto done; } while (0)
+#define CHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e_); rc = GPRN_E_HIP; goto done; } } while (0)
+    CTRY(fail_mem(dev_alloc(c, &d_C, (size_t)G * nn)));
+    if (draws) {
+        CTRY(fail_mem(dev_alloc(c, &d_F, (size_t)G * nn)));
+        CTRY(fail_mem(dev_alloc(c, &d_X, (size_t)G * nn)));
+        CHIP(hipMemsetAsync(d_X, 0, (size_t)G * nn * sizeof(double), c->stream));
+        CTRY(fail_mem(dev_alloc(c, &d_Z, (size_t)G * nd_pad * ns_pad)));
+        CTRY(fail_mem(dev_alloc(c, &d_LZ, (size_t)G * nd_pad * ns_pad)));
+        CTRY(fail_mem(dev_alloc(c, &d_lat, (size_t)G * nd * ns)));
+        if (rq.out_draws) CTRY(fail_mem(dev_alloc(c, &d_out, (size_t)c->p * nd * ns)));
+    } else if (rq.out_cov) {
+        const size_t M = (rq.flags & GPRN_COV_JOINT) ? (size_t)c->p * ns : (size_t)ns;
+        CTRY(fail_mem(dev_alloc(c, &d_out, (rq.flags & GPRN_COV_JOINT) ? M * M : (size_t)c->p * M * M)));
+    }
+    // ---- K** at t* into C (identity padding); the caller's matrix for a host-evaluated kernel
+    for (int g = 0; g < G; ++g) {
+        double* Cg = d_C + (size_t)g * nn;
+        const KernelSpec& ks = c->kspec[g];
+        if (!ks.uploaded) { CTRY(launch_fill_times(c, ks, Cg, 1.25e-12, nullptr, st.d_ts, ns, ns_pad)); continue; }
+        const gprn_ctx::PredStage& ps = c->pred_stage[g];
+        std::vector<double> pad(nn, 0.0);
+        for (int m = 0; m < ns_pad; ++m) {
+            if (m < ns) memcpy(&pad[(size_t)m * ns_pad], &ps.Kss[(size_t)m * ns], ns * sizeof(double));
+            else pad[(size_t)m * ns_pad + m] = 1.0;
+        }
+        CHIP(hipMemcpyAsync(Cg, pad.data(), nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        CHIP(hipStreamSynchronize(c->stream));
+    }
+    // ---- C -= W W^T: lower tiles (bt, at), K = ld (W^T's columns beyond N are zero), diagonal tiles lower blocks only
+    rows.assign((size_t)G * GPRN_NBUF, nullptr);
+    for (int g = 0; g < G; ++g) {
+        rows[(size_t)g * GPRN_NBUF + BUF_B] = d_C + (size_t)g * nn;
+        rows[(size_t)g * GPRN_NBUF + BUF_KLINV] = c->predWT[g];
+    }
+    CTRY(device_table(c, &t_pred, rows));
+    for (int bt = 0; bt < Ts; ++bt)
+        for (int at = 0; at <= bt; ++at)
+            tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ns_pad + (int64_t)at * GPRN_TILE, (int64_t)bt * GPRN_TILE * ld,
+                                     (int64_t)at * GPRN_TILE * ld, ld, BUF_B, BUF_KLINV, BUF_KLINV,
+                                     tile_modes(CM_SUB, 0, 0, bt == at)});
+    CTRY(dev_alloc(c, &d_t, tasks.size()));
+    CHIP(hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
+    {
+        TileSide side;
+        side.ldc = ns_pad;
+        CTRY(launch_tiles(c, d_t, tasks.size(), t_pred, G, ld, GPRN_T_UPDATE, c->stream, TS_64x64,
+                          Signal{nullptr, 0, nullptr, 0, nullptr}, Await{nullptr, 0, nullptr}, TG_COV, side));
+    }
+    rows.assign(G, nullptr);
+    for (int g = 0; g < G; ++g) rows[g] = d_C + (size_t)g * nn;
+    CTRY(device_table(c, &t_C, rows));
+    {
+        const int nb = ns_pad / GPRN_COV_BLK;
+        hipLaunchKernelGGL(k_mirror_lower, dim3(nb * (nb + 1) / 2, G), dim3(256), 0, c->stream, t_C, ns_pad);
+        CHIP(hipGetLastError());
+    }
+    if (!draws) {
+        if (rq.latent_cov)
+            for (int g = 0; g < G; ++g)
+                CHIP(hipMemcpy2DAsync(rq.latent_cov + (size_t)g * ns * ns, (size_t)ns * sizeof(double), d_C + (size_t)g * nn,
+                                      (size_t)ns_pad * sizeof(double), (size_t)ns * sizeof(double), ns,
+                                      hipMemcpyDeviceToHost, c->stream));
+        if (rq.out_cov) {
+            const bool joint = rq.flags & GPRN_COV_JOINT;
+            const int M = joint ? c->p * ns : ns, nb = (M + GPRN_COV_BLK - 1) / GPRN_COV_BLK;
+            std::vector<double> j2(c->p);
+            for (int i = 0; i < c->p; ++i) j2[i] = c->h_jit[i] * c->h_jit[i];
+            CTRY(dev_alloc(c, &d_jit2, c->p));
+            CHIP(hipMemcpyAsync(d_jit2, j2.data(), c->p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            prof_begin(c, GPRN_T_VEC);
+            hipLaunchKernelGGL(k_output_cov, dim3(nb * (nb + 1) / 2, joint ? 1 : c->p), dim3(256), 0, c->stream,
+                               (const double* const*)t_C, st.d_mean, (const double*)d_jit2, c->q, c->p, ns, ns_pad, joint ? 1 : 0, d_out);
+            prof_end(c);
+            CHIP(hipGetLastError());
+            CHIP(hipMemcpyAsync(rq.out_cov, d_out, (joint ? (size_t)M * M : (size_t)c->p * M * M) * sizeof(double),
+                                hipMemcpyDeviceToHost, c->stream));
+        }
+        CHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
+        goto done;
+    }
+    {
+        // ---- the ladder: factor C_g + nu_g I for every latent GP still pending in ONE phase of geometry (ns, ns_pad, Ts)
+        // (its task lists replace the context's: every other factorisation rebuilds them for its own T)
+        CHIP(hipStreamSynchronize(c->stream)); CHIP(hipStreamSynchronize(c->stream2));
+        CHIP(hipStreamSynchronize(c->stream3)); if (c->stream4) CHIP(hipStreamSynchronize(c->stream4));
+        std::vector<int> pending(G);
+        std::vector<double> nu(G, 1.25e-12);
+        for (int g = 0; g < G; ++g) pending[g] = g;
+        CTRY(dev_alloc(c, &t_fac, (size_t)G * GPRN_NBUF));
+        CTRY(dev_alloc(c, &t_src, G)); CTRY(dev_alloc(c, &t_dst, G));
+        CTRY(dev_alloc(c, &d_nu, G)); CTRY(dev_alloc(c, &d_inf, G));
+        while (!pending.empty()) {
+            const int np = (int)pending.size();
+            std::vector<double*> fr((size_t)np * GPRN_NBUF, nullptr), src(np), dst(np);
+            std::vector<double> nup(np);
+            for (int b = 0; b < np; ++b) {
+                const int g = pending[b];
+                fr[(size_t)b * GPRN_NBUF + BUF_B] = dst[b] = d_F + (size_t)g * nn;
+                fr[(size_t)b * GPRN_NBUF + BUF_X] = d_X + (size_t)g * nn;
+                src[b] = d_C + (size_t)g * nn;
+                nup[b] = nu[g];
+            }
+            CHIP(hipMemcpy(t_fac, fr.data(), fr.size() * sizeof(double*), hipMemcpyHostToDevice));
+            tab_note(c, t_fac, fr.data(), fr.size());
+            CHIP(hipMemcpy(t_src, src.data(), np * sizeof(double*), hipMemcpyHostToDevice));
+            CHIP(hipMemcpy(t_dst, dst.data(), np * sizeof(double*), hipMemcpyHostToDevice));
+            CHIP(hipMemcpy(d_nu, nup.data(), np * sizeof(double), hipMemcpyHostToDevice));
+            CHIP(hipMemset(d_inf, 0, np * sizeof(int)));
+            hipLaunchKernelGGL(k_shift_copy, dim3(ns_pad, np), dim3(256), 0, c->stream, (const double* const*)t_src, t_dst,
+                               (const double*)d_nu, ns, ns_pad);
+            CHIP(hipGetLastError());
+            const Phase ph{t_fac, nullptr, np, 0, d_inf, EvalMap{nullptr, 0, 0, 0, 0}, ns, ns_pad, Ts};
+            CTRY(factor_invert(c, ph, true));
+            CHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
+            CTRY(factor_check_waits(c));
+            std::vector<int> inf(np);
+            CHIP(hipMemcpy(inf.data(), d_inf, np * sizeof(int), hipMemcpyDeviceToHost));
+            tab_forget(c, t_fac);
+            std::vector<int> again;
+            for (int b = 0; b < np; ++b) {
+                const int g = pending[b];
+                if (inf[b] <= 0) continue;
+                if (nu[g] >= 1.25e-6 * 0.5) {            // the last rung failed
+                    if (!rq.info) { rq.info = inf[b]; rq.info_gp = g; }
+                    continue;
+                }
+                nu[g] *= 100.0;
+                again.push_back(g);
+            }
+            if (rq.info) break;
+            pending.swap(again);
+        }
+        if (rq.nugget_out) memcpy(rq.nugget_out, nu.data(), G * sizeof(double));
+        if (rq.info) goto done;
+    }
+    {
+        // ---- L Z for every draw: out tile (dt, nt) = Z[dt, 0:nt+1] L[nt, 0:nt+1]^T, K = (nt + 1) 128 (L is zero beyond)
+        rows.assign(G, nullptr);
+        for (int g = 0; g < G; ++g) rows[g] = d_F + (size_t)g * nn;
+        CTRY(device_table(c, &t_L, rows));
+        hipLaunchKernelGGL(k_zero_diag_upper, dim3(Ts, G), dim3(256), 0, c->stream, t_L, ns_pad);
+        CHIP(hipGetLastError());
+        CHIP(hipMemsetAsync(d_Z, 0, (size_t)G * nd_pad * ns_pad * sizeof(double), c->stream));
+        for (int g = 0; g < G; ++g)
+            CHIP(hipMemcpy2DAsync(d_Z + (size_t)g * nd_pad * ns_pad, (size_t)ns_pad * sizeof(double), rq.z + (size_t)g * nd * ns,
+                                  (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), nd, hipMemcpyHostToDevice, c->stream));
+        rows.assign((size_t)G * GPRN_NBUF, nullptr);
+        for (int g = 0; g < G; ++g) {
+            rows[(size_t)g * GPRN_NBUF + BUF_B] = d_F + (size_t)g * nn;
+            rows[(size_t)g * GPRN_NBUF + BUF_K] = d_Z + (size_t)g * nd_pad * ns_pad;
+            rows[(size_t)g * GPRN_NBUF + BUF_KLINV] = d_LZ + (size_t)g * nd_pad * ns_pad;
+        }
+        CTRY(device_table(c, &t_mm, rows));
+        tasks.clear();
+        for (int dt = 0; dt < nd_pad / GPRN_TILE; ++dt)
+            for (int nt = 0; nt < Ts; ++nt)
+                tasks.push_back(TileTask{(int64_t)dt * GPRN_TILE * ns_pad + (int64_t)nt * GPRN_TILE, (int64_t)dt * GPRN_TILE * ns_pad,
+                                         (int64_t)nt * GPRN_TILE * ns_pad, (nt + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_B,
+                                         tile_modes(CM_SET, 0, 0)});
+        dev_free(d_t);
+        CTRY(dev_alloc(c, &d_t, tasks.size()));
+        CHIP(hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
+        CTRY(launch_tiles(c, d_t, tasks.size(), t_mm, G, ns_pad, GPRN_T_UPDATE, c->stream,
+                          tasks.size() * (size_t)G > GPRN_FEW_TASKS ? TS_128x128 : TS_64x64));
+        rows.assign(G, nullptr);
+        for (int g = 0; g < G; ++g) rows[g] = d_LZ + (size_t)g * nd_pad * ns_pad;
+        CTRY(device_table(c, &t_LZ, rows));
+        prof_begin(c, GPRN_T_VEC);
+        hipLaunchKernelGGL(k_draw_combine, dim3((ns + 255) / 256, nd), dim3(256), 0, c->stream, (const double* const*)t_LZ,
+                           st.d_mean, c->q, c->p, ns, ns_pad, nd, d_lat, d_out);
+        prof_end(c);
+        CHIP(hipGetLastError());
+        CHIP(hipMemcpyAsync(rq.latent_draws, d_lat, (size_t)G * nd * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (rq.out_draws)
+            CHIP(hipMemcpyAsync(rq.out_draws, d_out, (size_t)c->p * nd * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        CHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
+    }
+done:
+#undef CTRY
+#undef CHIP
+    hipStreamSynchronize(c->stream);
+    if (t_fac) tab_forget(c, t_fac);
+    dev_free(d_C); dev_free(d_F); dev_free(d_X); dev_free(d_Z); dev_free(d_LZ); dev_free(d_out); dev_free(d_lat);
+    dev_free(d_jit2); dev_free(d_nu); dev_free(d_inf); dev_free(d_t);
+    dev_free(t_pred); dev_free(t_C); dev_free(t_fac); dev_free(t_src); dev_free(t_dst); dev_free(t_L); dev_free(t_mm);
+    dev_free(t_LZ);
+    return rc;
+}
+
+// the checks and the call shared by the two entry points
+static int cov_entry(gprn_ctx* c, const char* what, int ns, const double* tstar, double* mean_out, CovRequest& rq)
+{
+    if (!c || !c->N) return bad(c, "predict_cov: call set_data first");
+    if (c->world > 1) {
+        c->err = std::string(what) + ": full predictive covariances are not available on a sharded context (world > 1); "
+                 "use gprn_predict for the per-time variances";
+        return GPRN_E_UNSUPPORTED;
+    }
+    if (c->owner.empty()) return bad(c, "predict_cov: call set_owners first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int pre = GPRN_OK;
+    if (ns <= 0 || !tstar) pre = bad(c, "predict_cov: bad argument");
+    else if (!c->have_muvar) pre = bad(c, "predict_cov: set_muvar (or a sweep) first");
+    else if (rq.out_cov && (int)c->h_jit.size() != c->p) pre = bad(c, "predict_cov: set_jitters first");
+    else
+        for (int g = 0; g < c->G && !pre; ++g) {
+            if (!c->kspec[g].set) pre = bad(c, "predict_cov: a latent GP has no kernel");
+            else if (c->kspec[g].uploaded) {
+                auto it = c->pred_stage.find(g);
+                if (it == c->pred_stage.end() || it->second.ns != ns || it->second.kss_ns != ns)
+                    pre = bad(c, "predict_cov: a host-evaluated kernel needs gprn_predict_upload (K, K*, k**) and "
+                                 "gprn_predict_upload_kss (K**) for this ns first");
+            }
+        }
+    if (pre) { c->pred_stage.clear(); return pre; }
+    std::vector<double> var((size_t)c->G * ns);
+    std::vector<double> mean_tmp(mean_out ? 0 : (size_t)c->G * ns);
+    double* mean = mean_out ? mean_out : mean_tmp.data();
+    const int rc = with_event_fallback(c, what, [&](bool) {
+        rq.info = 0; rq.info_gp = -1;
+        return predict_impl(c, ns, tstar, mean, var.data(), [&](const PredState& st) { return cov_after(c, st, rq); });
+    });
+    c->pred_stage.clear();
+    if (rc) return rc;
+    if (rq.info) { c->info_gp = rq.info_gp; return rq.info; }
+    return GPRN_OK;
+}
+
+extern "C" int gprn_predict_cov(gprn_ctx* c, int ns, const double* tstar, int flags, double* mean_out,
+                                double* latent_cov_out, double* out_cov)
+{
+    DeviceLock lock_(c);
+    if (c && (flags & ~GPRN_COV_JOINT)) return bad(c, "predict_cov: unknown flags");
+    if (c && !mean_out) return bad(c, "predict_cov: bad argument");
+    CovRequest rq;
+    rq.flags = flags; rq.latent_cov = latent_cov_out; rq.out_cov = out_cov;
+    return cov_entry(c, "predict_cov", ns, tstar, mean_out, rq);
+}
+
+extern "C" int gprn_predict_draws(gprn_ctx* c, int ns, const double* tstar, int n_draws, const double* z,
+                                  double* latent_out, double* out, double* nugget_out)
+{
+    DeviceLock lock_(c);
+    if (c && (n_draws <= 0 || !z || !latent_out || !nugget_out)) return bad(c, "predict_draws: bad argument");
+    CovRequest rq;
+    rq.n_draws = n_draws; rq.z = z; rq.latent_draws = latent_out; rq.out_draws = out; rq.nugget_out = nugget_out;
+    return cov_entry(c, "predict_draws", ns, tstar, nullptr, rq);
+}
+
+extern "C" int gprn_predict_upload_kss(gprn_ctx* c, int gp, int ns, const double* Kss)
+{
+    DeviceLock lock_(c);
+    if (!c || !c->N || gp < 0 || gp >= c->G || ns <= 0 || !Kss) return bad(c, "predict_upload_kss: bad argument");
+    if (c->owner.empty()) return bad(c, "predict_upload_kss: call set_owners first");
+    if (c->owner[gp] != c->rank) return GPRN_OK;
+    gprn_ctx::PredStage& st = c->pred_stage[gp];
+    st.kss_ns = ns;
+    st.Kss.assign(Kss, Kss + (size_t)ns * ns);
+    return GPRN_OK;
 }
 
 // ------------------------------------------------------------------ kernel matrices, prior samples

@@ -569,6 +569,7 @@ static int elbocalc_small(gprn_ctx* c, const ElboIo& io, int max_iter, std::vect
             for (int n = 0; n < c->N; ++n)
                 v[(size_t)i * c->N + n] = io.jitters[i] * io.jitters[i] + c->h_yerr2[(size_t)i * c->N + n];
         HIP_TRY(c, hipMemcpyAsync(c->d_variance, v, pn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        c->h_jit.assign(io.jitters, io.jitters + c->p);
         c->have_jit = true;
     }
     if (io.mu && io.var) {

@@ -474,30 +474,38 @@ int launch_grad_fd(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const 
 
 int launch_fill(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val, const double* diag_add)
 {
+    return launch_fill_times(c, ks, K, nugget_val, diag_add, c->d_time, c->N, c->ld);
+}
+
+// the same over any time vector t (N entries, device) into a matrix of pitch ld (a multiple of 128; identity padding):
+// K** at the prediction times (gprn_predict_cov) -- the element code and its bits are those of the data's own fill
+int launch_fill_times(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val, const double* diag_add,
+                      const double* t, int N, int ld)
+{
     FillProgram pg;
     make_program(ks, nugget_val, pg);
     prof_begin(c, GPRN_T_FILL);
     static int use_sym = -1;                       // GPRN_FILL_SYM=0: always the full-matrix kernel
     if (use_sym < 0) { const char* e = getenv("GPRN_FILL_SYM"); use_sym = e ? atoi(e) : 1; }
     if (use_sym && program_is_even(pg)) {          // ld is a multiple of 128
-        const int nb = c->ld / 64;
+        const int nb = ld / 64;
         dim3 tri(nb * (nb + 1) / 2);
         switch (program_kid(pg)) {
-#define X(id) case id: hipLaunchKernelGGL(k_fill_sym<id>, tri, dim3(256), 0, c->stream, pg, c->d_time, K, c->N, c->ld, diag_add); break;
+#define X(id) case id: hipLaunchKernelGGL(k_fill_sym<id>, tri, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add); break;
         GPRN_FOR_EACH_KID(X)
 #undef X
-        default: hipLaunchKernelGGL(k_fill_sym<-1>, tri, dim3(256), 0, c->stream, pg, c->d_time, K, c->N, c->ld, diag_add);
+        default: hipLaunchKernelGGL(k_fill_sym<-1>, tri, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add);
         }
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         return GPRN_OK;
     }
-    dim3 grid((c->ld + 255) / 256, (c->ld + 7) / 8);
+    dim3 grid((ld + 255) / 256, (ld + 7) / 8);
     switch (program_kid(pg)) {
-#define X(id) case id: hipLaunchKernelGGL(k_fill<id>, grid, dim3(256), 0, c->stream, pg, c->d_time, K, c->N, c->ld, diag_add); break;
+#define X(id) case id: hipLaunchKernelGGL(k_fill<id>, grid, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add); break;
     GPRN_FOR_EACH_KID(X)
 #undef X
-    default: hipLaunchKernelGGL(k_fill<-1>, grid, dim3(256), 0, c->stream, pg, c->d_time, K, c->N, c->ld, diag_add);
+    default: hipLaunchKernelGGL(k_fill<-1>, grid, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add);
     }
     prof_end(c);
     HIP_TRY(c, hipGetLastError());

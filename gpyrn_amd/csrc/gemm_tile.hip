@@ -51,14 +51,15 @@
 // block are skipped -- 28 of 64 block products.
 // TAG only names the launch family in profiles (rocprofv3 reports one row per instantiation):
 // TG_PANEL panel products, TG_INNER in-panel K=128 updates, TG_NEXT next-panel K=512 updates,
-// TG_BULK bulk K=512 updates, TG_AHEAD their look-ahead part, TG_MISC the rest.
+// TG_BULK bulk K=512 updates, TG_AHEAD their look-ahead part, TG_MISC the rest, TG_COV the lower tiles of a predictive
+// covariance K** - W W^T (its C with a pitch of its own, ldc_arg; every other family ignores that argument).
 template <int BM, int BN, int NW, int TRI, int TAG>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2)
 void k_tile_gemm(const TileTask* __restrict__ tasks, double* const* __restrict__ ptrs, int ld,
                  unsigned* sig_slot, unsigned sig_value, const unsigned* then_wait, unsigned then_value,
                  const unsigned* wait_flag, unsigned wait_value, unsigned* wait_timed_out, int xcd_map,
                  const double* ft_s, int ft_n,
-                 unsigned* start_flag, unsigned start_value)
+                 unsigned* start_flag, unsigned start_value, int ldc_arg)
 {
     // (TileSide::start_flag: the flag of the launch before this one on the stream -- in memory once a workgroup of
     // this launch runs -- instead of a stream write, a 4.5 us kernel of its own, between the two)
@@ -94,13 +95,16 @@ void k_tile_gemm(const TileTask* __restrict__ tasks, double* const* __restrict__
     const int b_mode = (t.modes >> 3) & 1;
     const double* A = pick(t.a_buf) + t.a_off + (a_mode ? (size_t)sr * BM : (size_t)sr * BM * ld);
     const double* B = pick(t.b_buf) + t.b_off + (b_mode ? (size_t)sc * BN : (size_t)sc * BN * ld);
-    gptr_t C = (gptr_t)(pick(t.c_buf) + t.c_off) + (size_t)sr * BM * ld + sc * BN;
+    // (TG_COV: C has a pitch of its own, ldc_arg; every other family folds this to ld)
+    const int ldc_own = TAG == TG_COV ? ldc_arg : 0;
+    gptr_t C = (gptr_t)(pick(t.c_buf) + t.c_off) + (size_t)sr * BM * (ldc_own ? ldc_own : ld) + sc * BN;
 
     // A symmetric update of a DIAGONAL tile (modes bit 4, ensure_tasks): only its lower triangle is ever read (the
     // diagonal-block kernel, the chain's update), so the 64 x 64 quarter above the diagonal is not computed at all and
     // the two quarters on it skip their upper 16 x 16 blocks -- 40 of 64 block products instead of 64 (the exact
     // triangle would be 36).  Round 2 measured 13 % more MFMAs in the bulk launches than the algorithm needs.
-    constexpr bool CAN_LOWER = BM == 64 && BN == 64 && TRI == 0 && (TAG == TG_INNER || TAG == TG_NEXT || TAG == TG_BULK || TAG == TG_AHEAD);
+    constexpr bool CAN_LOWER = BM == 64 && BN == 64 && TRI == 0 &&
+                               (TAG == TG_INNER || TAG == TG_NEXT || TAG == TG_BULK || TAG == TG_AHEAD || TAG == TG_COV);
     const bool lower = CAN_LOWER && ((t.modes >> 4) & 1);
     // First touch (modes bit 5, the first outer panel's K = 512 update when the caller hands over s = sqrt(d)): the tile
     // of B = I + D^1/2 K D^1/2 is formed from K on the way in instead of being read -- k_build_B then writes only what the
@@ -122,13 +126,13 @@ void k_tile_gemm(const TileTask* __restrict__ tasks, double* const* __restrict__
     if (lower && sr < sc) { /* nothing of this quarter is ever read */ }
     else if (CAN_LOWER && lower && sr == sc)
         tile_mma<BM, BN, WM, WN, TRI, CAN_LOWER, true>(lds, A, B, C, ld, a_mode, b_mode, c_mode, t.klen,
-                                                       (sr * BM) >> 4, (sc * BN) >> 4, ft_K, ft_sv, ft_row, ft_col, ft_n);
+                                                       (sr * BM) >> 4, (sc * BN) >> 4, ft_K, ft_sv, ft_row, ft_col, ft_n, ldc_own);
     else if (CAN_SYM128 && ((t.modes >> 4) & 1))
         tile_mma<BM, BN, WM, WN, TRI, false, false, CAN_SYM128>(lds, A, B, C, ld, a_mode, b_mode, c_mode, t.klen,
                                                                 (sr * BM) >> 4, (sc * BN) >> 4);
     else
         tile_mma<BM, BN, WM, WN, TRI, false, true>(lds, A, B, C, ld, a_mode, b_mode, c_mode, t.klen,
-                                                   (sr * BM) >> 4, (sc * BN) >> 4, ft_K, ft_sv, ft_row, ft_col, ft_n);
+                                                   (sr * BM) >> 4, (sc * BN) >> 4, ft_K, ft_sv, ft_row, ft_col, ft_n, ldc_own);
     signal_done(sig_slot, sig_value, then_wait, then_value, wait_timed_out);
 }
 
@@ -395,7 +399,7 @@ static bool launch_one(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, doub
     hipLaunchKernelGGL((k_tile_gemm<BM, BN, NW, TRI, TAG>), dim3((unsigned)ntasks * per_task, (unsigned)nbatch),
                        dim3(64 * NW), dyn, stream, d_tasks, tab, ld, sig.slot, sig.value, sig.then_wait,
                        sig.then_value, aw.flag, aw.value, aw.timed_out ? aw.timed_out : sig.timed_out, GPRN_XCD_CHUNK_LOG2,
-                       side.ft_s, side.N, side.start_flag, side.start_value);
+                       side.ft_s, side.N, side.start_flag, side.start_value, side.ldc);
     return true;
 }
 
@@ -452,6 +456,8 @@ int launch_tiles(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double** d
     case TS_64x64 * 8 + TG_MISC: GO(64, 64, 0, TG_MISC); break;
     case TS_64x128 * 8 + TG_MISC: GO(64, 128, 0, TG_MISC); break;
     case TS_128x64 * 8 + TG_MISC: GO(128, 64, 0, TG_MISC); break;
+    // lower tiles of a predictive covariance, C (pitch side.ldc) -= W W^T (gprn_predict_cov)
+    case TS_64x64 * 8 + TG_COV: GO(64, 64, 0, TG_COV); break;
     default: known = false;
     }
 #undef GO

@@ -128,6 +128,7 @@ struct gprn_ctx {
     double *d_time = nullptr, *d_yraw = nullptr, *d_yerr2 = nullptr;
     double *d_yres = nullptr, *d_variance = nullptr;
     std::vector<double> h_yerr2;
+    std::vector<double> h_jit;                       // the jitters last set (p): gprn_predict_cov's per-output term
     double *d_mu = nullptr, *d_var = nullptr;        // (p+1, q, N) each, reference layout
     double *d_mu_save = nullptr, *d_var_save = nullptr;
     bool have_yres = false, have_jit = false, have_muvar = false, factored = false;
@@ -177,7 +178,8 @@ struct gprn_ctx {
     // prediction scratch (gprn_predict): K* and (X K*^T)^T per local GP, [ns_pad x ld] each
     std::vector<double*> predKs, predWT;
     // host-evaluated matrices staged for the next gprn_predict (gprn_predict_upload): K + 1.25e-12 I (N x N), K* (ns x N), k** (ns)
-    struct PredStage { int ns = 0; std::vector<double> K, Kstar, kss; };
+    // ... and, for gprn_predict_cov / gprn_predict_draws, the full K** (ns x ns; gprn_predict_upload_kss)
+    struct PredStage { int ns = 0; std::vector<double> K, Kstar, kss; int kss_ns = 0; std::vector<double> Kss; };
     std::map<int, PredStage> pred_stage;
     size_t pred_cap = 0;
     double **tab_pred = nullptr;
@@ -279,6 +281,9 @@ void prof_end(gprn_ctx* c);
 
 int launch_fill(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val = 1e-6,
                 const double* diag_add = nullptr);
+// ... over a time vector of the caller's (N entries, device) into a matrix of pitch ld = 128 k (K** at prediction times)
+int launch_fill_times(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val, const double* diag_add,
+                      const double* t, int N, int ld);
 // many small matrices in one launch (fill.hip; gprn_elbocalc_batch)
 size_t fill_program_bytes();
 bool fill_program_with(const KernelSpec& ks, const double* params, void* dst);
@@ -291,8 +296,9 @@ enum { TS_128x128 = 0, TS_64x64 = 1, TS_64x128 = 2, TS_128x64 = 3,
        TS_64x128_BTRI = 4, TS_128x64_ATRI = 5 };   // panel products with the triangular X_kk (gemm_tile.hip TRI)
 // launch family of a tile launch: a template tag of k_tile_gemm, so that a kernel trace reports every
 // family under its own kernel name (panel products, in-panel K=128 updates, next-panel K=512 updates,
-// bulk K=512 updates, everything else)
-enum { TG_PANEL = 0, TG_INNER = 1, TG_NEXT = 2, TG_BULK = 3, TG_MISC = 4, TG_AHEAD = 5 };
+// bulk K=512 updates, everything else; TG_COV: the lower tiles of a predictive covariance C -= W W^T, whose C has a pitch of
+// its own -- TileSide::ldc -- beside the operands' ld: gprn_predict_cov, api_more.hip)
+enum { TG_PANEL = 0, TG_INNER = 1, TG_NEXT = 2, TG_BULK = 3, TG_MISC = 4, TG_AHEAD = 5, TG_COV = 6 };
 // Completion signal of a launch, raised from the device: slot[0] counts the workgroups that have
 // finished, the last one resets it and stores `value` to slot[1] (system scope).  Another stream
 // picks it up with hipStreamWaitValue32 about 2 us later (profiles/probes/streamvalue.hip) -- no event
@@ -315,6 +321,7 @@ struct TileSide {
     int N = 0;                         // ... and the matrices' N
     unsigned* start_flag = nullptr;    // a flag word the launch sets to start_value when its first workgroup runs (the flag
     unsigned start_value = 0;          // of the launch BEFORE it on its stream), or null
+    int ldc = 0;                       // TG_COV launches: pitch of the C tiles (the operands keep the launch's ld)
 };
 int launch_tiles(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double** d_ptrs,
                  int nbatch, int ld, int fam, hipStream_t stream = nullptr, int shape = TS_128x128,

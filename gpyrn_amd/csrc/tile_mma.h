@@ -48,6 +48,7 @@ __device__ __forceinline__ void lane_geometry(int tid, int mode, int ld, unsigne
 // formed from K (same offsets as C) and s = sqrt(d): delta + (s_row s_col) K, zero outside the n x n problem -- what
 // k_build_B would have written there (same expression, same rounding).  ft_row / ft_col: the part's first row / column
 // inside the matrix.
+// ldc_own: C's pitch when it differs from the operands' (TG_COV launches), 0: ld.
 // DEEP_OK: the caller's register budget allows the second set of staging registers (the 64 x 64 form: 110 registers per lane)
 // SYM: the part lies on the diagonal of a symmetric update of a diagonal tile, B_jj -= L[j,.] L[j,.]^T (task bit 4).  Its
 // 16 x 16 blocks ON the diagonal hold the matrix' diagonal entries, which are ~1 in B = I + D^1/2 K D^1/2 where the update
@@ -61,8 +62,10 @@ template <int BM, int BN, int WM, int WN, int TRI, bool LOWER = false, bool DEEP
 __device__ __forceinline__ void tile_mma(double* lds, const double* A, const double* B, gptr_t C, int ld,
                                          int a_mode, int b_mode, int c_mode, int klen, int mb16_0, int nb16_0,
                                          const double* ft_K = nullptr,
-                                         const double* ft_s = nullptr, int ft_row = 0, int ft_col = 0, int ft_n = 0)
+                                         const double* ft_s = nullptr, int ft_row = 0, int ft_col = 0, int ft_n = 0,
+                                         int ldc_own = 0)
 {
+    const int ldc = ldc_own ? ldc_own : ld;                     // pitch of C (the operands': ld)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // in an SGPR: conditions on it are scalar branches
@@ -108,7 +111,7 @@ __device__ __forceinline__ void tile_mma(double* lds, const double* A, const dou
 
     const bool neg = c_mode != CM_SET;                       // acc holds -(result)
     auto on_diag = [&](int i, int j) { return SYM && nb16 + j == mb16 + i; };   // (wave-uniform)
-    gptr_t Cw = C + (size_t)(row0 + fk) * ld + wc * TN + fr;
+    gptr_t Cw = C + (size_t)(row0 + fk) * ldc + wc * TN + fr;
     auto crow = [&](int i) { return (size_t)(i * 16); };       // rows of block i past Cw
     auto arow_bytes = [&](int i) { return i * 128; };          // same, LDS bytes
     v4d acc[MI][NI];
@@ -186,7 +189,7 @@ __device__ __forceinline__ void tile_mma(double* lds, const double* A, const dou
                 if (on_diag(i, j)) { acc[i][j] = v4d{0.0, 0.0, 0.0, 0.0}; continue; }   // (SYM: read in the epilogue)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    acc[i][j][r] = -Cw[(crow(i) + 4 * r) * ld + j * 16];
+                    acc[i][j][r] = -Cw[(crow(i) + 4 * r) * ldc + j * 16];
             }
     } else {
 #pragma unroll
@@ -320,15 +323,15 @@ __device__ __forceinline__ void tile_mma(double* lds, const double* A, const dou
                     }
                 } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) cin[r] = Cw[(crow(i) + 4 * r) * ld + j * 16];
+                    for (int r = 0; r < 4; ++r) cin[r] = Cw[(crow(i) + 4 * r) * ldc + j * 16];
                 }
 #pragma unroll
-                for (int r = 0; r < 4; ++r) Cw[(crow(i) + 4 * r) * ld + j * 16] = cin[r] - acc[i][j][r];
+                for (int r = 0; r < 4; ++r) Cw[(crow(i) + 4 * r) * ldc + j * 16] = cin[r] - acc[i][j][r];
                 continue;
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                Cw[(crow(i) + 4 * r) * ld + j * 16] = neg ? -acc[i][j][r] : acc[i][j][r];
+                Cw[(crow(i) + 4 * r) * ldc + j * 16] = neg ? -acc[i][j][r] : acc[i][j][r];
             }
         }
 }

@@ -742,6 +742,96 @@ class inference:
             return predictives, predictivesVar, np.array([nPred, wPred], dtype=object)
         return predictives, predictivesVar
 
+    def _stage_posterior(self, nodes, weights, means, jitters, tstar):
+        """What predict_cov / sample_posterior hand the device before their call: the kernels (as _Prediction does), the
+        host-evaluated matrices of user-defined kernels -- K + 1.25e-12 I, K*, k** and the whole K** -- the state and the
+        jitters.  Returns the context."""
+        if self._mu is None and self._var is None:
+            mu, var = self._initMuVar(nodes, weights, jitters)
+        else:
+            mu, var = self._mu, self._var
+        specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
+        ctx = self._backend()                  # (a sharded context refuses the call itself: GPRN_E_UNSUPPORTED)
+        key = tuple(self._spec_key(sp) for sp in specs)
+        if key != self._prior_key:
+            for gp, sp in enumerate(specs):
+                self._send_spec(ctx, gp, sp)
+            self._prior_key = None             # the priors must be refactored before the next sweep
+        data_t = np.asarray(self.time, dtype=float)
+        for gp, (sp, kernel) in enumerate(zip(specs, chain(nodes, weights))):
+            if sp[0] != 'host':
+                continue
+            ctx.predict_upload(gp, self._tinyNuggetKMatrix(kernel, data_t),
+                               self._predictKMatrix(kernel, tstar), self._kss_diagonal(kernel, tstar))
+            ctx.predict_upload_kss(gp, self._tinyNuggetKMatrix(kernel, tstar))
+        ctx.set_muvar(np.asarray(mu, dtype=float), np.asarray(var, dtype=float))
+        ctx.set_jitters(np.asarray(jitters, dtype=float))
+        return ctx
+
+    def predict_cov(self, tstar=None, joint=False, separate=False):
+        """
+        Full predictive covariance of the GPRN at `tstar` (default: the data times), from the state _Prediction uses.
+        Not in the reference: its _gp.GP.prediction forms every latent GP's conditional covariance
+        C_g = K** - K* (K + 1.25e-12 I + diag v)^-1 K*^T (_gp.py:125-137) and keeps only the diagonal.  Here the
+        matrices stay, on the GPU (gprn_predict_cov), and are combined per output under the mean-field independence of
+        the latent GPs:
+
+            Cov(y_i(t), y_i(t')) = sum_j [w_ij w_ij' C_fj + C_wij (C_fj + f_j f_j')] + q jitter_i^2 delta(t, t')
+            Cov(y_i(t), y_k(t')) = sum_j w_ij w_kj' C_fj(t, t')                    (i != k, `joint` only)
+
+        whose diagonal is _Prediction's variance, quirk included (jitter_i^2 added once per node).
+
+        Returns (mean (N*, p), cov): cov (p, N*, N*), or (p N*, p N*) with `joint` (row i N* + t); with `separate` also
+        the node covariances (q, N*, N*) and the weight covariances (q p, N*, N*), weight (j, i) at j p + i.
+        """
+        nodes, weights, means, jitters = self._get_components()
+        tstar = self.time if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
+        ctx = self._stage_posterior(nodes, weights, means, jitters, tstar)
+        gmean, lat, cov = ctx.predict_cov(tstar, joint=joint, latent=separate)
+        q, p = self.q, self.p
+        nPred, wP = gmean[:q], gmean[q:].reshape(q, p, tstar.size)
+        meanVal = np.array(np.array_split(self._mean(means, tstar), p))
+        predictives = np.zeros((tstar.size, p))
+        for i in range(p):                     # (as _Prediction)
+            predictives[:, i] += meanVal[i]
+            for j in range(q):
+                predictives[:, i] += nPred[j] * wP[j, i]
+        if separate:
+            return predictives, cov, lat[:q], lat[q:]
+        return predictives, cov
+
+    def sample_posterior(self, tstar=None, n=1, noise=False, separate=False, rng=None):
+        """
+        `n` joint draws of the GPRN's predictive distribution at `tstar` (default: the data times).  Not in the
+        reference.  Every latent GP is drawn from N(mean_g, C_g) (predict_cov's C_g) as mean_g + L_g z, with
+        C_g + nu_g I = L_g L_g^T factored on the GPU (gprn_predict_draws); nu_g starts at 1.25e-12 and grows by factors
+        of 100, to 1.25e-6 at most, while fp64 finds the matrix not positive definite (the ladder of _sample_from_gp; the
+        values used are left in ``self.last_nuggets``).  Output i is mean function_i + sum_j w_ij o f_j, and with `noise`
+        also N(0, q jitter_i^2) per time (q: _Prediction's jitter counted once per node).  The first two moments of the
+        draws are _Prediction's mean and variance.  The standard normals come from ``np.random.default_rng(rng)``.
+
+        Returns draws (n, N*, p); with `separate` also the node draws (q, n, N*) and weight draws (q p, n, N*).
+        """
+        nodes, weights, means, jitters = self._get_components()
+        tstar = self.time if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
+        gen = np.random.default_rng(rng)
+        ctx = self._stage_posterior(nodes, weights, means, jitters, tstar)
+        q, p, ns = self.q, self.p, tstar.size
+        z = gen.standard_normal((q * (p + 1), int(n), ns))
+        lat, out, nug, info = ctx.predict_draws(tstar, z)
+        self.last_nuggets = nug
+        if info:
+            raise np.linalg.LinAlgError(f'predictive covariance of latent GP {ctx.last_info_gp} is not positive definite '
+                                        f'even with a 1.25e-6 nugget (pivot {info})')
+        meanVal = np.array(np.array_split(self._mean(means, tstar), p))
+        draws = np.transpose(out, (1, 2, 0)) + meanVal.T[None]
+        if noise:
+            sd = np.sqrt(q) * np.abs(np.asarray(jitters, dtype=float))
+            draws = draws + gen.standard_normal(draws.shape) * sd
+        if separate:
+            return draws, lat[:q], lat[q:]
+        return draws
+
     def predict(self, tstar=None, nn=1000):
         """
         GPRN prediction at `tstar`, or on `nn` points spanning the data padded by

@@ -147,6 +147,34 @@ int gprn_predict(gprn_ctx* ctx, int ns, const double* tstar, double* mean_out, d
  * every rank (the owners' results travel as one grouped broadcast). */
 int gprn_predict_upload(gprn_ctx* ctx, int gp, int ns, const double* K_tiny, const double* Kstar, const double* kss);
 
+/* ---- full predictive covariances and joint posterior draws (not in the reference, which forms the
+ * conditional covariance of every latent GP in _gp.GP.prediction, _gp.py:125-137, and keeps only its diagonal; the
+ * combination below extends inference._Prediction, meanfield.py:1346-1373, from variances to covariances).
+ * For latent GP g (index as above) with predictive times t* (ns) and the variational state last set:
+ *   C_g = K**_g - K*_g (K_g + 1.25e-12 I + diag v_g)^-1 K*_g^T,   K**_g = _gp.GP._kernel_matrix(kernel, t*) (_gp.py:40-50:
+ *   + 1.25e-12 I for one-argument kernels, no nugget for Polynomial / (Quasi)HarmonicPeriodic; no nugget in K_g for those).
+ * Per output i, the latent GPs independent (mean field; f_j node j, w_ij weight (j, i); f, w their predictive means):
+ *   Cov(y_i(t), y_i(t')) = sum_j [ w_ij(t) w_ij(t') C_fj + C_wij (C_fj + f_j(t) f_j(t')) ] + q jitter_i^2 delta(t, t')
+ *   Cov(y_i(t), y_k(t')) = sum_j w_ij(t) w_kj(t') C_fj(t, t')      (i != k)
+ * whose diagonal is _Prediction's predictivesVar -- including its quirk of adding jitter_i^2 once per NODE (q times).
+ * predict_cov: mean_out (G, ns) as gprn_predict; latent_cov_out (G, ns, ns) or NULL; out_cov or NULL: (p, ns, ns), or
+ * with GPRN_COV_JOINT the (p ns, p ns) matrix, row i ns + t, cross-output blocks included.  Jitters: gprn_set_jitters.
+ * Every returned matrix is exactly symmetric.  Memory: G ns_pad^2 doubles (ns_pad = 128 ceil(ns / 128)) + the output.
+ * predict_draws: C_g + nu_g I = L_g L_g^T, nu_g = 1.25e-12, x 100 while fp64 finds it not positive definite, 1.25e-6 at
+ * most (the ladder of inference._sample_from_gp); latent_out[g][d] = mean_g + L_g z[g][d]; out[i][d] (or NULL) =
+ * sum_j latent_out[w_ij][d] o latent_out[f_j][d] -- without the mean functions and the noise, which live on the host;
+ * nugget_out[g] = nu_g.  z, latent_out: (G, n_draws, ns); out: (p, n_draws, ns).  Returns info > 0 (gprn_last_info_gp
+ * names the latent GP) when C_g + 1.25e-6 I is not positive definite.  Memory: 3 G ns_pad^2 + 2 G ns_pad n_draws_pad doubles.
+ * predict_upload_kss: the full K** (ns, ns) of a latent GP whose kernel is a user-defined covFunction subclass, for the next
+ * predict_cov / predict_draws call with this ns, beside gprn_predict_upload (K, K*, k**).
+ * Sharded contexts (world > 1): GPRN_E_UNSUPPORTED.  Device memory that cannot be had: GPRN_E_NOMEM. */
+#define GPRN_COV_JOINT 1
+int gprn_predict_cov(gprn_ctx* ctx, int ns, const double* tstar, int flags, double* mean_out,
+                     double* latent_cov_out, double* out_cov);
+int gprn_predict_draws(gprn_ctx* ctx, int ns, const double* tstar, int n_draws, const double* z,
+                       double* latent_out, double* out, double* nugget_out);
+int gprn_predict_upload_kss(gprn_ctx* ctx, int gp, int ns, const double* Kss);
+
 /* ---- kernel matrices and prior draws outside the ELBO loop ----
  * eval_kernel: K = expr(t_i, t_j) + nugget I at the data times through the fused fill kernel: replaces
  * inference._KMatrix (meanfield.py:413-434; nugget 1e-6) and _tinyNuggetKMatrix (:436-452; 1.25e-12) when
