@@ -39,6 +39,7 @@ SIGNATURES = {
     'gprn_last_error': (c_char_p, [c_void_p]),
     'gprn_last_info_gp': (c_int, [c_void_p]),
     'gprn_set_data': (c_int, [c_void_p, c_int, c_int, c_int, _dp, _dp, _dp]),
+    'gprn_set_mask': (c_int, [c_void_p, c_void_p]),
     'gprn_comm_unique_id': (c_int, [POINTER(c_char)]),
     'gprn_comm_init': (c_int, [c_void_p, c_int, c_int, POINTER(c_char)]),
     'gprn_set_owners': (c_int, [c_void_p, POINTER(c_int)]),
@@ -181,6 +182,16 @@ class Context:
         self._check(self._lib.gprn_set_data(self._h, N, p, int(q), _ptr(time), _ptr(y), _ptr(yerr)),
                     'set_data')
         self.N, self.p, self.q, self.G = N, p, int(q), int(q) * (p + 1)
+
+    def set_mask(self, mask):
+        """(p, N) truthy = observed, or None to clear (gprn_set_mask)."""
+        if mask is None:
+            self._check(self._lib.gprn_set_mask(self._h, None), 'set_mask')
+            return
+        m = np.ascontiguousarray(np.asarray(mask, dtype=bool), dtype=np.uint8)
+        if m.shape != (self.p, self.N):
+            raise ValueError(f'expected shape {(self.p, self.N)}, got {m.shape}')
+        self._check(self._lib.gprn_set_mask(self._h, m.ctypes.data_as(c_void_p)), 'set_mask')
 
     def comm_init(self, world, rank, unique_id):
         buf = ctypes.create_string_buffer(bytes(unique_id), 128) if unique_id else None

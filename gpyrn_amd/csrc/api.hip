@@ -236,6 +236,9 @@ static void free_problem(gprn_ctx* c)
     c->predKs.clear(); c->predWT.clear(); c->pred_cap = 0;
     tab_forget(c, nullptr);
     dev_free(c->tab_pred); dev_free(c->d_slotgp_all);
+    mask_free(c);
+    dev_free(c->d_mask); dev_free(c->d_mask_U); dev_free(c->d_mask_nU);
+    c->h_mask.clear(); c->mask_U.clear(); c->mask_upad = 0;
     dev_free(c->tab_node); dev_free(c->tab_weight); dev_free(c->tab_setup);
     dev_free(c->d_slotgp_node); dev_free(c->d_slotgp_weight); dev_free(c->d_slotgp_setup);
     dev_free(c->d_d); dev_free(c->d_s); dev_free(c->d_pred); dev_free(c->d_z); dev_free(c->d_u);
@@ -866,7 +869,8 @@ int upload_table(gprn_ctx* c, double** d_tab, const std::vector<double*>& rows)
 
 int build_tables(gprn_ctx* c)
 {
-    if (c->tables_ready) return GPRN_OK;
+    if (c->tables_ready) return mask_prepare(c);     // (a data mask set since: its buffers, as part of the set-up)
+    mask_invalidate(c);
     // (the second set of node workspaces and its table are rebuilt on demand: sweep_impl)
     c->loc_nodes.clear(); c->loc_weights.clear();
     for (int g = 0; g < c->q; ++g) if (c->owner[g] == c->rank) c->loc_nodes.push_back(g);
@@ -928,7 +932,7 @@ int build_tables(gprn_ctx* c)
     c->small_tabs_ready = false;
     c->small_sweep_ready = false;
     c->setup1_ready = false;
-    return GPRN_OK;
+    return mask_prepare(c);
 }
 
 int check_info(gprn_ctx* c, const int* d_info, const std::vector<int>& gps, int* first)
@@ -946,6 +950,7 @@ extern "C" int gprn_keep_sigma(gprn_ctx* c, int on)
 {
     DeviceLock lock_(c);
     if (!c) return GPRN_E_ARG;
+    if (on && c->d_mask) { c->err = "keep_sigma: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     c->keep_sigma = on != 0;
     return GPRN_OK;
 }

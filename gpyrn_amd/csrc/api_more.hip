@@ -859,6 +859,7 @@ extern "C" int gprn_grad_matrices(gprn_ctx* c, int gp, double* Kinv_out, double*
 {
     DeviceLock lock_(c);
     if (!c || !c->N || gp < 0 || gp >= c->G || !Kinv_out || !P_out) return bad(c, "grad_matrices: bad argument");
+    if (c->d_mask) { c->err = "grad_matrices: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     return grad_impl(c, gp, Kinv_out, P_out, nullptr, nullptr);
 }
 
@@ -872,6 +873,7 @@ extern "C" int gprn_grad_kernel(gprn_ctx* c, int gp, const double* m, double* gr
 {
     DeviceLock lock_(c);
     if (!c || !c->N || gp < 0 || gp >= c->G || !m || !grad_out) return bad(c, "grad_kernel: bad argument");
+    if (c->d_mask) { c->err = "grad_kernel: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     const KernelSpec& ks = c->kspec[gp];
     if (!ks.set || ks.uploaded || ks.n_ops < 1) {
         c->err = "grad_kernel: the kernel of this latent GP has no device program (uploaded matrix)";

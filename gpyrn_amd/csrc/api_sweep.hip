@@ -258,8 +258,11 @@ static int small_sweep(gprn_ctx* c, const double* mu_in, const double* var_in, d
     c->d_scal = scal;
     const int* done = loop ? loop->ctl : nullptr;
     TRY(ensure_small_sweep_tabs(c));
+    // (under a data mask the points of zero precision of each phase get their state from mask.hip right behind it)
     TRY(small_phase(c, sweep_phase(c, false), false, scal, mu_in, var_in, mu_out, var_out, done));
+    TRY(mask_rows(c, sweep_phase(c, false), false, mu_out, var_out, done));
     TRY(small_phase(c, sweep_phase(c, true), true, scal, mu_in, var_in, mu_out, var_out, done));
+    TRY(mask_rows(c, sweep_phase(c, true), true, mu_out, var_out, done));
     return small_tail(c, out4, scal, mu_out, var_out, loop);
 }
 
@@ -299,7 +302,7 @@ int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::fu
         TRY(vec_logdet(c, ph, BUF_B, scal));
         TRY(vec_finalize(c, ph, scal, false));
     }
-    return GPRN_OK;
+    return mask_rows(c, ph, weights, c->d_mu, c->d_var, nullptr);                                  // under a data mask: mu, var where d = 0 (mask.hip)
 }
 
 // mu^T K^-1 mu of the phase's latent GPs into out (the sweep's muKmu)
@@ -765,6 +768,7 @@ extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel
     if (!c || !c->N || n_eval < 1 || !kernel_params || !y_resid || !jitters || !mu || !var || max_iter < 0 || !elbo ||
         !iterations || !converged || !info || (!mu_out != !var_out))
         return bad(c, "elbocalc_batch: bad argument");
+    if (c->d_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "elbocalc_batch: call set_owners first");
     if (comm_active(c) || c->world != 1) { c->err = "elbocalc_batch: one rank only (a pool of ranks splits the list itself)"; return GPRN_E_UNSUPPORTED; }

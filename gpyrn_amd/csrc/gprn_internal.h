@@ -229,6 +229,26 @@ struct gprn_ctx {
     size_t lauum0 = 0, nlauum = 0;
     int tasks_T = 0;                 // T the lists were built for
     int overlap_opt = -1;            // gprn_set_option "overlap" (api_sweep.hip overlap_mask); -1: the default
+    // ---- data mask (gprn_set_mask, mask.hip): output i unobserved at t_n has zero precision there.  Per latent GP the set U
+    // of its points with d_n = 0 (weight (j, i): the masked entries of output i; node: the times with every output masked,
+    // q = 1 only) gets its mean and variance from mask_rows behind the phase's finalize.
+    uint8_t* d_mask = nullptr;           // (p, N), 1 = observed; null: everything observed (every kernel as without a mask)
+    std::vector<uint8_t> h_mask;
+    std::vector<std::vector<int>> mask_U;  // G: the unobserved points of each latent GP
+    int mask_upad = 0;                   // max |U| over the latent GPs, rounded up to 128 (0: no latent GP has one)
+    int* d_mask_U = nullptr;             // [G][mask_upad] U of each latent GP, by GP
+    int* d_mask_nU = nullptr;            // [G] |U|
+    // per phase (0 nodes, 1 weights), only over its latent GPs with a U ("entries"):
+    std::vector<double*> mask_WT, mask_C;  // per entry (upad x ld): rows K[U_u, :] diag(s), then (X diag(s) K[:, U])^T
+    double **tab_mask[2] = {nullptr, nullptr};    // [entry][GPRN_NBUF]: BUF_X = the slot's X, BUF_K = WT, BUF_KLINV = C
+    int *d_mask_slot[2] = {nullptr, nullptr};     // [entry]: the phase slot (its per-slot vectors and pointer-table row)
+    int *d_mask_gp[2] = {nullptr, nullptr};       // [entry]: the latent GP
+    int mask_n[2] = {0, 0};                       // entries
+    TileTask *d_mask_tasks[2] = {nullptr, nullptr};                 // the tile tasks of C = WT X^T
+    size_t mask_ntasks[2] = {0, 0};
+    int mask_upad_ph[2] = {0, 0};        // max |U| over the entries, rounded up to 128
+    bool mask_ready = false;             // the buffers, tables and task lists above match the problem and the slots
+
     // ---- small-N path (smalln.hip): problems of one or two tiles run a half-sweep as ONE launch, one workgroup per latent GP
     int small_opt = -1;              // gprn_set_option "small_path": 0 never, else wherever it applies (small_applies)
     double** d_kinv_tab = nullptr;   // [q] device pointers K_j^-1 (quirk Q1), for k_small_tail
@@ -466,6 +486,12 @@ size_t batch_budget_bytes(gprn_ctx* c);        // device memory a chunk of evalu
 // api_sweep.hip: one half-sweep's factorisation with its head and tail (run_phase, midn.hip); scal: the sweep's scalars;
 // chain_started: see FactorHooks (left set when the factorisation did not take it)
 int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::function<int()>& chain_started);
+// mask.hip: the rows U of the phase's latent GPs under a data mask (no-op without one), behind the phase's finalize; the
+// state (mu, var) they go to; done: the small path's stop word (nothing to do once it is set), or null
+int mask_rows(gprn_ctx* c, const Phase& ph, bool weights, double* mu, double* var, const int* done);
+int mask_prepare(gprn_ctx* c);       // buffers, tables and task lists for the current slots (build_tables: the set-up)
+void mask_free(gprn_ctx* c);
+void mask_invalidate(gprn_ctx* c);   // the slots changed (build_tables rebuilds them)
 
 // meanfield.py:640-643: np.std / np.mean of the last three values, operation by operation (one rounding each)
 static inline bool elbo_stop_rule(double e0, double e1, double e2)

@@ -176,10 +176,14 @@ struct SmallPhaseArgs {
     double *trBinv, *logdetB;   // per latent GP
     int* info;
     unsigned long long* stamps; // GPRN_SMALL_STAMPS (probes): 100 MHz clock of workgroup 0 at the stages of the kernel, or null
+    const uint8_t* mask;        // the data mask (p, N), 1 = observed (the MASKED instantiations only; gprn_set_mask)
 };
 
 // One half-sweep.  WEIGHTS: the weight phase (new mu_f, old mu_w) or the node phase; T: tiles per matrix edge.
-template <bool WEIGHTS, int T>
+// MASKED: k_prep_*'s selection inside the workgroup -- a masked entry is left out of d and the right-hand side, a point
+// with d = 0 gets s = z = 0 (row and column of B the identity) and a placeholder state that mask.hip's rows overwrite
+// behind this launch (small_sweep).
+template <bool WEIGHTS, int T, bool MASKED = false>
 __device__ __forceinline__ void small_phase_body(const SmallPhaseArgs& a)
 {
     // (one tile: the diagonal-block kernel's 46.6 KB only -- with the vectors 59 KB, two workgroups per CU when many
@@ -203,7 +207,8 @@ __device__ __forceinline__ void small_phase_body(const SmallPhaseArgs& a)
         double dv = 1.0, pv = 0.0;
         if (WEIGHTS) {
             const int kk = gp - q, j = kk / p, i = kk % p;
-            if (n < N) {
+            if (MASKED && n < N && !a.mask[(size_t)i * N + n]) dv = 0.0;
+            else if (n < N) {
                 const double vi = a.variance[(size_t)i * N + n];
                 const double mfj = a.mu_out[(size_t)j * N + n];
                 dv = (mfj * mfj + a.var_out[(size_t)j * N + n]) / vi;
@@ -218,6 +223,7 @@ __device__ __forceinline__ void small_phase_body(const SmallPhaseArgs& a)
             if (n < N) {
                 dv = 0.0;
                 for (int i = 0; i < p; ++i) {
+                    if (MASKED && !a.mask[(size_t)i * N + n]) continue;
                     const double vi = a.variance[(size_t)i * N + n];
                     const size_t wrow = (size_t)(1 + i) * q;
                     const double mwj = a.mu_in[(wrow + j) * N + n];
@@ -231,8 +237,9 @@ __device__ __forceinline__ void small_phase_body(const SmallPhaseArgs& a)
             }
         }
         const double sv = sqrt(dv);
-        sD[n] = dv; sS[n] = sv; sZ[n] = pv / sv;
-        a.d[vo + n] = dv; a.s[vo + n] = sv; a.pred[vo + n] = pv; a.z[vo + n] = pv / sv;
+        const double zv = (MASKED && dv == 0.0) ? 0.0 : pv / sv;
+        sD[n] = dv; sS[n] = sv; sZ[n] = zv;
+        a.d[vo + n] = dv; a.s[vo + n] = sv; a.pred[vo + n] = pv; a.z[vo + n] = zv;
     }
     __syncthreads();
     SM_STAMP(1);
@@ -315,6 +322,7 @@ __device__ __forceinline__ void small_phase_body(const SmallPhaseArgs& a)
         if (tid < N) {
             a.mu_out[row * N + tid] = (sZ[tid] - my_ct) / sS[tid];
             a.var_out[row * N + tid] = (1.0 - my_cs) / sD[tid];
+            if (MASKED && sD[tid] == 0.0) { a.mu_out[row * N + tid] = 0.0; a.var_out[row * N + tid] = 0.0; }
             tr = my_cs;
             ld_acc = log(Bm[(size_t)tid * ld + tid]);
         }
@@ -348,10 +356,12 @@ struct SmallTailArgs {
     int sweep, hist_at, max_iter;
     const int* info;            // the pivot verdicts of this evaluation (set-up, node phase, weight phase), n_info words
     int n_info;
+    const uint8_t* mask;        // the data mask (p, N) (the MASKED instantiations only)
 };
 
 // log-likelihood terms of k_loglike_partial for block 0 (with N <= 256 the other 31 blocks of that kernel are empty
 // and contribute exact zeros); result valid in thread 0
+template <bool MASKED>
 __device__ __forceinline__ void small_loglike(const SmallTailArgs& a, double* sh4, double& t1, double& t2, double& t3)
 {
     const double TWO_PI = 6.283185307179586;
@@ -359,6 +369,7 @@ __device__ __forceinline__ void small_loglike(const SmallTailArgs& a, double* sh
     const int n = threadIdx.x;
     if (n < a.N) {
         for (int i = 0; i < a.p; ++i) {
+            if (MASKED && !a.mask[(size_t)i * a.N + n]) continue;   // (k_loglike_partial<true>)
             const double vi = a.variance[(size_t)i * a.N + n];
             const size_t wrow = (size_t)(1 + i) * a.q;
             t1 += log(TWO_PI * vi);
@@ -379,7 +390,7 @@ __device__ __forceinline__ void small_loglike(const SmallTailArgs& a, double* sh
     t3 = sm_block_sum(t3, sh4);
 }
 
-template <int T>
+template <int T, bool MASKED = false>
 __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
 {
     __shared__ __attribute__((aligned(16))) double lds[SMALL_MMA_DOUBLES];
@@ -451,7 +462,7 @@ __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
     if (!last) return;                              // (uniform)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     double t1, t2, t3;
-    small_loglike(a, sh4, t1, t2, t3);
+    small_loglike<MASKED>(a, sh4, t1, t2, t3);
     if (tid == 0) {
         atomicExch(a.ticket, 0u);
         const double TWO_PI = 6.283185307179586;
@@ -556,6 +567,10 @@ __device__ __forceinline__ void small_prior_body(const SmallPriorArgs& a)
 template <bool WEIGHTS, int T>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_small_phase(SmallPhaseArgs a) { small_phase_body<WEIGHTS, T>(a); }
+// ... under a data mask (gprn_set_mask): its own kernels, so that the unmasked ones keep their code and registers
+template <bool WEIGHTS, int T>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void k_small_phase_m(SmallPhaseArgs a) { small_phase_body<WEIGHTS, T, true>(a); }
 // (one tile, many evaluations: up to two workgroups per CU -- 222 registers per lane fit twice)
 template <bool WEIGHTS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
@@ -564,6 +579,9 @@ void k_small_phase_b(const SmallPhaseArgs* __restrict__ lanes) { small_phase_bod
 template <int T>
 __global__ __launch_bounds__(256)
 void k_small_tail(SmallTailArgs a) { small_tail_body<T>(a); }
+template <int T>
+__global__ __launch_bounds__(256)
+void k_small_tail_m(SmallTailArgs a) { small_tail_body<T, true>(a); }
 template <int T>
 __global__ __launch_bounds__(256)
 void k_small_tail_b(const SmallTailArgs* __restrict__ lanes, int sweep, int hist_at, int max_iter)
@@ -599,10 +617,15 @@ int small_phase(gprn_ctx* c, const Phase& ph, bool weights, double* scal, const 
     SmallPhaseArgs a{(double* const*)ph.ptrs, ph.slot_gp, ph.N, ph.ld, c->p, c->q, c->d_yres, c->d_variance,
                      mu_in, var_in, mu_out, var_out, done,
                      c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, c->d_u + o, c->d_cs + o, c->d_ct + o,
-                     scal + c->G, scal, ph.info, weights ? nullptr : c->d_small_stamps};
-#define GO(W, TT) hipLaunchKernelGGL((k_small_phase<W, TT>), dim3(ph.nslots), dim3(256), 0, c->stream, a)
-    if (ph.T == 1) { if (weights) GO(true, 1); else GO(false, 1); }
-    else { if (weights) GO(true, 2); else GO(false, 2); }
+                     scal + c->G, scal, ph.info, weights ? nullptr : c->d_small_stamps, c->d_mask};
+#define GO(K, W, TT) hipLaunchKernelGGL((K<W, TT>), dim3(ph.nslots), dim3(256), 0, c->stream, a)
+    if (c->d_mask) {
+        if (ph.T == 1) { if (weights) GO(k_small_phase_m, true, 1); else GO(k_small_phase_m, false, 1); }
+        else { if (weights) GO(k_small_phase_m, true, 2); else GO(k_small_phase_m, false, 2); }
+    } else {
+        if (ph.T == 1) { if (weights) GO(k_small_phase, true, 1); else GO(k_small_phase, false, 1); }
+        else { if (weights) GO(k_small_phase, true, 2); else GO(k_small_phase, false, 2); }
+    }
 #undef GO
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
@@ -619,9 +642,14 @@ int small_tail(gprn_ctx* c, double* out4, double* scal, const double* mu, const 
                     (double* const*)c->d_kinv_tab, c->d_u, c->d_logdetK, scal, out4, c->d_small_ticket,
                     loop ? loop->ctl : nullptr, loop ? loop->hist : nullptr, loop ? loop->last3 : nullptr,
                     loop ? loop->sweep : 0, loop ? loop->hist_at : 0, loop ? loop->max_iter : 0,
-                    c->d_info, 3 * c->nslot};
-    if (c->T == 1) hipLaunchKernelGGL(k_small_tail<1>, dim3(nn + nw), dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_small_tail<2>, dim3(nn + nw), dim3(256), 0, c->stream, a);
+                    c->d_info, 3 * c->nslot, c->d_mask};
+    if (c->d_mask) {
+        if (c->T == 1) hipLaunchKernelGGL(k_small_tail_m<1>, dim3(nn + nw), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(k_small_tail_m<2>, dim3(nn + nw), dim3(256), 0, c->stream, a);
+    } else {
+        if (c->T == 1) hipLaunchKernelGGL(k_small_tail<1>, dim3(nn + nw), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(k_small_tail<2>, dim3(nn + nw), dim3(256), 0, c->stream, a);
+    }
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

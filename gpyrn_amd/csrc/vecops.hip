@@ -40,12 +40,16 @@ __device__ __forceinline__ double block_sum(double v, double* sh /* >= 4 doubles
     return r;
 }
 
+// MASKED (gprn_set_mask): an output that was not observed at t_n has zero precision there.  Its terms are SELECTED away
+// (never multiplied by a 0 / 1 weight: whatever the caller left in a masked y or yerr stays out of the arithmetic), and a
+// latent GP with d_n = 0 gets s_n = z_n = 0: row and column n of B are the identity (mask.hip finishes those rows).
+template <bool MASKED>
 __global__ __launch_bounds__(256)
 void k_prep_nodes(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
                   const double* __restrict__ mu, const double* __restrict__ var,
                   const double* __restrict__ yres, const double* __restrict__ variance,
                   double* __restrict__ d, double* __restrict__ s, double* __restrict__ pred,
-                  double* __restrict__ z, EvalMap ev)
+                  double* __restrict__ z, EvalMap ev, const uint8_t* __restrict__ mask)
 {
     const int slot = blockIdx.y, j = slot_gp[slot];
     const int n = blockIdx.x * 256 + threadIdx.x;
@@ -56,6 +60,7 @@ void k_prep_nodes(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
     if (n < N) {
         dsum = 0.0;
         for (int i = 0; i < p; ++i) {
+            if (MASKED && !mask[(size_t)i * N + n]) continue;
             const double vi = variance[(size_t)i * N + n];
             const size_t wrow = (size_t)(1 + i) * q;
             const double mwj = mu[(wrow + j) * N + n];
@@ -72,14 +77,16 @@ void k_prep_nodes(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
     s[o] = sqrt(dsum);
     pred[o] = psum;
     z[o] = psum / sqrt(dsum);           // q = D^-1/2 pred: Sigma pred = D^-1/2 (q - X^T X q)
+    if (MASKED && dsum == 0.0) z[o] = 0.0;   // (every output masked at t_n: q = 1 only)
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256)
 void k_prep_weights(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
                     const double* __restrict__ mu, const double* __restrict__ var,
                     const double* __restrict__ yres, const double* __restrict__ variance,
                     double* __restrict__ d, double* __restrict__ s, double* __restrict__ pred,
-                    double* __restrict__ z, EvalMap ev)
+                    double* __restrict__ z, EvalMap ev, const uint8_t* __restrict__ mask)
 {
     const int slot = blockIdx.y, kk = slot_gp[slot] - q;
     const int j = kk / p, i = kk % p;
@@ -88,6 +95,11 @@ void k_prep_weights(const int* __restrict__ slot_gp, int N, int ld, int p, int q
     const size_t eb = ev_of(ev, slot);
     mu += eb * ev.state; var += eb * ev.state; yres += eb * ev.yv; variance += eb * ev.yv;
     double dv = 1.0, pv = 0.0;
+    if (MASKED && n < N && !mask[(size_t)i * N + n]) {
+        const size_t o = (size_t)slot * ld + n;
+        d[o] = 0.0; s[o] = 0.0; pred[o] = 0.0; z[o] = 0.0;
+        return;
+    }
     if (n < N) {
         const double vi = variance[(size_t)i * N + n];
         const double mfj = mu[(size_t)j * N + n];
@@ -271,6 +283,7 @@ void k_colops_reduce(int ld, int T, const double* __restrict__ part,
 // new mu = Sigma pred = (q - X^T X q)/s  (q = pred/s: no product with K needed),
 // new var = (1 - diag B^-1)/d into the state rows of the GP;
 // trBinv[gp] = sum diag B^-1
+template <bool MASKED>
 __global__ __launch_bounds__(256)
 void k_finalize(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
                 const double* __restrict__ d, const double* __restrict__ s,
@@ -294,6 +307,7 @@ void k_finalize(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
         tr += binv;
         mu[row * N + n] = (z[o] - ct[o]) / s[o];
         var[row * N + n] = (1.0 - binv) / d[o];
+        if (MASKED && d[o] == 0.0) { mu[row * N + n] = 0.0; var[row * N + n] = 0.0; }   // (mask.hip writes these)
         if (Lm) ld_acc += log(Lm[(size_t)n * ld + n]);
     }
     tr = block_sum(tr, sh);
@@ -326,7 +340,7 @@ void k_finalize(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
 // the 192 matrices of a batch's weight phase against 9.  tests/test_parity_gpu.py::
 // test_reduce_finalize_relaxed_handover_keeps_the_bits runs both forms 200 times over more workgroups per slot than an
 // XCD holds and compares tr B^-1 and log det B bit for bit.
-template <bool FENCED>
+template <bool FENCED, bool MASKED>
 __global__ __launch_bounds__(256)
 void k_reduce_finalize(const int* __restrict__ slot_gp, int N, int ld, int T, int p, int q,
                        const double* __restrict__ part, const double* __restrict__ d, const double* __restrict__ s,
@@ -358,6 +372,7 @@ void k_reduce_finalize(const int* __restrict__ slot_gp, int N, int ld, int T, in
         if (n < N) {
             mu[row * N + n] = (z[o] - b) / s[o];
             var[row * N + n] = (1.0 - a) / d[o];
+            if (MASKED && d[o] == 0.0) { mu[row * N + n] = 0.0; var[row * N + n] = 0.0; }   // (mask.hip writes these)
             // (the terms go to the last workgroup of this launch, possibly on another XCD: agent-scope stores -- written
             // through -- and loads, no fence.  A __threadfence() here is an L2 write-back per workgroup, on an L2 full of
             // the factorisation's freshly written tiles: 84 us for the 192 matrices of a batch's weight phase)
@@ -435,11 +450,14 @@ void k_dot_self(const int* __restrict__ slot_gp, int N, int ld, const double* __
 
 // Expected log-likelihood (meanfield.py:895-990; y_raw is the RAW data, quirk Q3): partial sums
 // of its three terms over a slice of the time stamps per block (fixed slices -> deterministic).
+// MASKED: the three terms over the observed (i, n) only, log(2 pi v) included.
 #define ELBO_BLOCKS 32
+template <bool MASKED>
 __global__ __launch_bounds__(256)
 void k_loglike_partial(int N, int p, int q, const double* __restrict__ mu, const double* __restrict__ var,
                        const double* __restrict__ yraw, const double* __restrict__ variance,
-                       double* __restrict__ part /* [ELBO_BLOCKS][3] */, const int* __restrict__ evals, EvalMap ev)
+                       double* __restrict__ part /* [ELBO_BLOCKS][3] */, const int* __restrict__ evals, EvalMap ev,
+                       const uint8_t* __restrict__ mask)
 {
     __shared__ double sh[4];
     const double TWO_PI = 6.283185307179586;
@@ -450,6 +468,7 @@ void k_loglike_partial(int N, int p, int q, const double* __restrict__ mu, const
     double t1 = 0.0, t2 = 0.0, t3 = 0.0;
     for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += 256 * ELBO_BLOCKS) {
         for (int i = 0; i < p; ++i) {
+            if (MASKED && !mask[(size_t)i * N + n]) continue;
             const double vi = variance[(size_t)i * N + n];
             const size_t wrow = (size_t)(1 + i) * q;
             t1 += log(TWO_PI * vi);
@@ -518,14 +537,12 @@ int vec_prep(gprn_ctx* c, const Phase& ph, bool weights)
     prof_begin(c, GPRN_T_VEC);
     const size_t o = (size_t)ph.slot0 * ph.ld;
     dim3 grid((ph.ld + 255) / 256, ph.nslots);
-    if (weights)
-        hipLaunchKernelGGL(k_prep_weights, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
-                           c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance,
-                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev);
-    else
-        hipLaunchKernelGGL(k_prep_nodes, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
-                           c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance,
-                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev);
+#define GO_PREP(KER, M) hipLaunchKernelGGL(KER<M>, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld, \
+                           c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance, \
+                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev, (const uint8_t*)c->d_mask)
+    if (weights) { if (c->d_mask) GO_PREP(k_prep_weights, true); else GO_PREP(k_prep_weights, false); }
+    else         { if (c->d_mask) GO_PREP(k_prep_nodes, true);   else GO_PREP(k_prep_nodes, false); }
+#undef GO_PREP
     LAUNCH_END(c);
 }
 
@@ -607,9 +624,11 @@ int vec_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_logdet)
     if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
     const size_t o = (size_t)ph.slot0 * ph.ld;
-    hipLaunchKernelGGL(k_finalize, dim3(ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
-                       c->p, c->q, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, c->d_var,
-                       scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, ph.ev);
+#define GO_FIN(M) hipLaunchKernelGGL(k_finalize<M>, dim3(ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld, \
+                       c->p, c->q, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, c->d_var, \
+                       scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, ph.ev)
+    if (c->d_mask) GO_FIN(true); else GO_FIN(false);
+#undef GO_FIN
     LAUNCH_END(c);
 }
 
@@ -624,11 +643,12 @@ int vec_reduce_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_lo
     }
     prof_begin(c, GPRN_T_VEC);
     const size_t o = (size_t)ph.slot0 * ph.ld, po = (size_t)ph.slot0 * ph.T * 2 * ph.ld;
-#define GO_RF(F) hipLaunchKernelGGL(k_reduce_finalize<F>, dim3((ph.ld + 255) / 256, ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, \
+#define GO_RF(F, M) hipLaunchKernelGGL((k_reduce_finalize<F, M>), dim3((ph.ld + 255) / 256, ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, \
                        ph.ld, ph.T, c->p, c->q, c->d_part + po, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, \
                        c->d_var, scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, \
                        c->d_fin_terms + (size_t)ph.slot0 * 2 * ph.ld, c->d_fin_tickets + ph.slot0, ph.ev)
-    if (c->fenced_finalize) GO_RF(true); else GO_RF(false);
+    if (c->d_mask) { if (c->fenced_finalize) GO_RF(true, true); else GO_RF(false, true); }
+    else           { if (c->fenced_finalize) GO_RF(true, false); else GO_RF(false, false); }
 #undef GO_RF
     LAUNCH_END(c);
 }
@@ -659,8 +679,14 @@ int vec_elbo(gprn_ctx* c, double* out4, const double* scal, double* part, hipStr
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
     const EvalMap one{nullptr, 0, 0, 0, 0};
-    hipLaunchKernelGGL(k_loglike_partial, dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q,
-                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, (const int*)nullptr, one);
+    if (c->d_mask)
+        hipLaunchKernelGGL(k_loglike_partial<true>, dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q,
+                           c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, (const int*)nullptr, one,
+                           (const uint8_t*)c->d_mask);
+    else
+        hipLaunchKernelGGL(k_loglike_partial<false>, dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q,
+                           c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, (const int*)nullptr, one,
+                           (const uint8_t*)nullptr);
     hipLaunchKernelGGL(k_elbo_final, dim3(1), dim3(64), 0, stream, c->N, c->p, c->q, part,
                        c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4,
                        (const int*)nullptr, one);
@@ -675,8 +701,8 @@ int vec_elbo_evals(gprn_ctx* c, const EvalMap& ev, const int* d_evals, int n, do
     if (!n) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
-    hipLaunchKernelGGL(k_loglike_partial, dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
-                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, ev);
+    hipLaunchKernelGGL(k_loglike_partial<false>, dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
+                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)nullptr);
     hipLaunchKernelGGL(k_elbo_final, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part,
                        c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, ev);
     LAUNCH_END(c);

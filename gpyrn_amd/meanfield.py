@@ -54,9 +54,16 @@ class inference:
             GPU ordinal (default: LOCAL_RANK when sharded, else 0)
         comm: ``sharding.Comm``, keyword only
             Shard the q + q*p latent GPs over the ranks of one node
+        mask: array-like (p, N) or None, keyword only
+            Truthy where output i was observed at time n (not in the reference, whose outputs are observed at every
+            time).  A masked entry has zero precision: it is left out of the updates and of the expected
+            log-likelihood, and its y / yerr may hold anything (NaN, inf): they are replaced by 0 / 1 here and never
+            reach arithmetic.  ``_initMuVar`` reads a masked y as 0.  Every latent GP still lives on all N times;
+            ``predict`` at a masked time is the imputation.  ``inference.from_series`` builds a mask from series on
+            different time grids.
     """
 
-    def __init__(self, q: int, time: Array, *args, device=None, comm=None):
+    def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -73,6 +80,11 @@ class inference:
         self.tt = np.tile(time, self.p)                 # "extended" time
         self.y = np.concatenate([args[::2]])            # (p, N)
         self.yerr = np.concatenate([args[1::2]])
+        self.mask = None if mask is None else self._check_mask(mask, comm)
+        if self.mask is not None:
+            # (masked entries never reach arithmetic: the device selects them away, and these values fill them)
+            self.y = np.where(self.mask, self.y, 0.0)
+            self.yerr = np.where(self.mask, self.yerr, 1.0)
         self.yerr2 = self.yerr**2
 
         self._components_set = False
@@ -87,6 +99,54 @@ class inference:
         self._ctx = None
         self._prior_key = None
         self.last_info = 0
+
+    def _check_mask(self, mask, comm):
+        """The (p, N) bool mask, validated before anything touches a device."""
+        m = np.asarray(mask)
+        if m.shape != (self.p, self.N):
+            raise ValueError(f'mask must have shape (p, N) = {(self.p, self.N)}, got {m.shape}')
+        m = m.astype(bool)
+        empty = np.flatnonzero(~m.any(axis=1))
+        if empty.size:
+            raise ValueError(f'mask: output(s) {empty.tolist()} have no observed entry')
+        if self.q >= 2:
+            gaps = np.flatnonzero(~m.any(axis=0))
+            if gaps.size:
+                raise ValueError(f'mask: with q >= 2 every time needs at least one observed output; no output is '
+                                 f'observed at time index(es) {gaps[:10].tolist()}: drop those times from the data '
+                                 f'(predict still reaches them)')
+        if comm is not None:
+            raise NotImplementedError('mask: a sharded inference object does not support a data mask')
+        return m
+
+    @classmethod
+    def from_series(cls, q, series, **kwargs):
+        """
+        An inference object from p series on their own time grids: ``series`` = [(t1, y1, e1), (t2, y2, e2), ...].
+        The time vector is the sorted union of the grids (a time that several series share appears once), and the
+        mask marks which output was observed at which time.  Keyword arguments go to the constructor.
+        """
+        series = [tuple(np.asarray(a, dtype=float).ravel() for a in s) for s in series]
+        if not series:
+            raise ValueError('from_series: no series given')
+        for t, y, e in series:
+            if not (t.size == y.size == e.size):
+                raise ValueError('from_series: t, y and yerr of a series must have the same length')
+            if np.unique(t).size != t.size:
+                raise ValueError('from_series: a series has a repeated time')
+        time = np.unique(np.concatenate([s[0] for s in series]))
+        p, N = len(series), time.size
+        y, e = np.zeros((p, N)), np.ones((p, N))
+        mask = np.zeros((p, N), dtype=bool)
+        for i, (t, yi, ei) in enumerate(series):
+            idx = np.searchsorted(time, t)
+            y[i, idx], e[i, idx], mask[i, idx] = yi, ei, True
+        args = [a for i in range(p) for a in (y[i], e[i])]
+        return cls(q, time, *args, mask=mask, **kwargs)
+
+    def _refuse_masked(self, what):
+        if self.mask is not None:
+            raise NotImplementedError(f'{what} is not supported under a data mask')
 
     # ------------------------------------------------------------ components
     def set_components(self, nodes, weights, means, jitters):
@@ -295,6 +355,8 @@ class inference:
                 ctx.comm_init(comm.world, comm.rank, comm.unique_id())
                 comm.done()
             ctx.set_data(np.asarray(self.time, dtype=float), self.y, self.yerr, self.q)
+            if self.mask is not None and not self.mask.all():     # (an all-True mask is no mask: the same kernels run)
+                ctx.set_mask(self.mask)
             if comm is not None and comm.world > 1:
                 ctx.set_owners(sharding.owners(self.p, self.q, comm.world))
             self._ctx = ctx
@@ -509,6 +571,7 @@ class inference:
         device and ignored).  Returns ELBO, new_mu, new_var, sigmaF (q,N,N),
         sigmaW (q,p,N,N).
         """
+        self._refuse_masked('ELBOaux')
         ctx = self._backend()
         Kf = np.asarray(Kf, dtype=float).reshape(self.q, self.N, self.N)
         Kw = np.asarray(Kw, dtype=float).reshape(self.qp, self.N, self.N)
@@ -541,6 +604,7 @@ class inference:
         Bonilla 2013): ``(sigma_f (q, N, N), mu_f (q, N), sigma_w (q, p, N, N), mu_w (p, q, N))`` from the prior
         matrices, ``y - mean``, the squared jitters and the current state split as ``_u_to_fhatW`` splits it.  One device
         sweep with the explicit covariances kept (as ``ELBOaux``); ``Lf`` / ``Lw`` are recomputed there."""
+        self._refuse_masked('_updateSigMu')
         q, p, N = self.q, self.p, self.N
         mu = np.concatenate((np.reshape(muF, (1, q, N)), np.reshape(muW, (p, q, N))))
         var = np.concatenate((np.reshape(varF, (1, q, N)), np.reshape(varW, (p, q, N))))
@@ -552,6 +616,7 @@ class inference:
         covariances ``+ q (p + 1) N (1 + log 2 pi) / 2``.  The Choleskys run on the device (the covariances go in as the
         latent GPs' matrices, the set-up's factorisation returns ``log det``); a covariance that is not positive definite
         gives NaN, as jax's cholesky does."""
+        self._refuse_masked('_entropy')
         q, p, N = self.q, self.p, self.N
         sigma_f = np.asarray(sigma_f, dtype=float).reshape(q, N, N)
         sigma_w = np.asarray(sigma_w, dtype=float).reshape(q, p, N, N)
@@ -573,6 +638,7 @@ class inference:
         (:1025, 1039: quirk Q1), weight (j, i) with the raw reshape ``mu_w.reshape(q, p, N)[j, i]`` (:1021: quirk Q2),
         ``- N q (p + 1) log(2 pi) / 2``.  The matrices are factored on the device (``Lf`` / ``Lw`` are recomputed there) and
         every term comes from the resident factor (``gprn_prior_terms``: tr(K^-1 S) as one triangular product, N^3)."""
+        self._refuse_masked('_expectedLogPrior')
         q, p, N = self.q, self.p, self.N
         Kf = np.asarray(Kf, dtype=float).reshape(q, N, N)
         Kw = np.asarray(Kw, dtype=float).reshape(q * p, N, N)
@@ -604,6 +670,7 @@ class inference:
         enters: the residual is taken against the raw data ``self.y`` (:940, quirk Q3), and of the covariances only the
         diagonals (:956-957).  Computed by the kernel of the device's own ELBO assembly from the state
         ``(mu_f, mu_w)`` / ``(diag Sigma_f, diag Sigma_w)`` and the jitters."""
+        self._refuse_masked('_expectedLogLike')
         q, p, N = self.q, self.p, self.N
         sigma_f = np.asarray(sigma_f, dtype=float).reshape(q, N, N)
         sigma_w = np.asarray(sigma_w, dtype=float).reshape(q, p, N, N)
@@ -652,6 +719,7 @@ class inference:
         # from the previous evaluation) jumps by 1e-3 relative whenever the trip count changes, which a line search
         # cannot work with
         if kwargs.get('jac') is True:
+            self._refuse_masked('optimize(jac=True)')
             sweeps = int(kwargs.pop('sweeps', 40))
             nodes, weights, means, jitters = self._get_components()
             start = (self._mu, self._var) if self._mu is not None else self._initMuVar(nodes, weights, jitters)
@@ -883,7 +951,7 @@ class inference:
     def _batchable(self):
         """Whether ``_nELBO_batch_device`` applies to this object at its current components -- a property of the problem,
         the same on every rank of a pool (so that all of them take the same branch, collectives included)."""
-        if self._comm is not None or self.N > self.batch_max_N:
+        if self._comm is not None or self.N > self.batch_max_N or self.mask is not None:
             return False
         nodes, weights, _, _ = self._get_components()
         return all(self._kernel_spec(k)[0] == 'device' for k in chain(nodes, weights))
@@ -928,8 +996,8 @@ class inference:
 
     def _nELBO_batch_device(self, sets, max_iter):
         """``nELBO_batch`` through ``gprn_elbocalc_batch``, or None where that does not apply (larger problems, sharded
-        objects, user-defined kernels, kernel expressions that change shape from one vector to the next)."""
-        if self._comm is not None or self.N > self.batch_max_N:
+        objects, user-defined kernels, kernel expressions that change shape from one vector to the next, a data mask)."""
+        if self._comm is not None or self.N > self.batch_max_N or self.mask is not None:
             return None
         ctx = self._backend()
         max_iter = 10000 if max_iter is None else int(max_iter)
@@ -1046,6 +1114,7 @@ class inference:
 
         Returns ``(ELBO, gradient)``.  Unsharded problems only.
         """
+        self._refuse_masked('grad_ELBO')
         assert self._components_set, _NOT_SET
         if self._mu is None:
             self.ELBOcalc()
@@ -1149,6 +1218,7 @@ class inference:
         ``nELBO(parameters)`` (warm-started ELBOcalc, as the reference's objective), then ``grad_ELBO``.  With
         ``sweeps`` (and a start state ``(mu, var)``): the ELBO after exactly that many forced sweeps from ``start``
         plus the one ``grad_ELBO`` adds -- a deterministic, smooth function of the parameters."""
+        self._refuse_masked('nELBO_and_grad')
         if sweeps is None:
             self.nELBO(parameters, max_iter=max_iter)
             elbo, grad = self.grad_ELBO()

@@ -89,6 +89,18 @@ int gprn_last_info_gp(const gprn_ctx* ctx);
 int gprn_set_data(gprn_ctx* ctx, int N, int p, int q,
                   const double* time, const double* y, const double* yerr);
 
+/* ---- outputs with missing observations (new; lifts the dense (p, N) requirement of meanfield.py:106-134).
+ * mask is (p, N) row-major, non-zero = observed; NULL clears it.  Call after set_data and before the set-up.
+ * A masked entry has zero precision: it is left out of the node precision d_j (:765), the weight precision d (:838, 850),
+ * the right-hand sides (:759-791, 838-864) and every term of the expected log-likelihood (:895-990, log(2 pi v) included);
+ * the prior, the entropy and the constants are unchanged, and every latent GP still lives on all N times.  Masked
+ * entries of y / yerr are never read into arithmetic (the kernels select; NaN and inf are fine there).
+ * GPRN_E_ARG: an output with no observed entry, or q >= 2 with a time at which every output is masked (drop that time;
+ * predict still reaches it).  Both paths (one-tile kernels and launch schedule) have a masked form;
+ * gprn_keep_sigma(1), gprn_grad_matrices, gprn_grad_kernel, gprn_elbocalc_batch and contexts with a communicator
+ * return GPRN_E_UNSUPPORTED. */
+int gprn_set_mask(gprn_ctx* ctx, const uint8_t* mask);
+
 /* ---- multi-GPU sharding (new): one context per rank/GPU.
  * comm_init before set_data; set_owners after set_data and before set_kernel:
  * latent GP g is factored and updated by rank owner[g] (q + q*p entries).
