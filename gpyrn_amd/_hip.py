@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('GPRN_HIP_LIB') or os.path.join(_HERE, 'libgprn_hip.so
 
 GPRN_E_ARG, GPRN_E_HIP, GPRN_E_NODEV, GPRN_E_COMM, GPRN_E_NOMEM, GPRN_E_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 COV_JOINT = 1
+ORDER_REFERENCE, ORDER_SEQUENTIAL = 0, 1
 M_K, M_KLINV, M_SIGMA, M_BX, M_BL = 0, 1, 2, 3, 4
 T_NAMES = ('fill', 'build_B', 'diag', 'panel', 'update', 'lauum', 'vec', 'update_ahead')
 TILE = 128
@@ -40,6 +41,7 @@ SIGNATURES = {
     'gprn_last_info_gp': (c_int, [c_void_p]),
     'gprn_set_data': (c_int, [c_void_p, c_int, c_int, c_int, _dp, _dp, _dp]),
     'gprn_set_mask': (c_int, [c_void_p, c_void_p]),
+    'gprn_set_sweep_order': (c_int, [c_void_p, c_int]),
     'gprn_comm_unique_id': (c_int, [POINTER(c_char)]),
     'gprn_comm_init': (c_int, [c_void_p, c_int, c_int, POINTER(c_char)]),
     'gprn_set_owners': (c_int, [c_void_p, POINTER(c_int)]),
@@ -192,6 +194,11 @@ class Context:
         if m.shape != (self.p, self.N):
             raise ValueError(f'expected shape {(self.p, self.N)}, got {m.shape}')
         self._check(self._lib.gprn_set_mask(self._h, m.ctypes.data_as(c_void_p)), 'set_mask')
+
+    def set_sweep_order(self, order):
+        """ORDER_REFERENCE (0: the reference's Jacobi ordering) or ORDER_SEQUENTIAL (1) for every following sweep
+        (gprn_set_sweep_order)."""
+        self._check(self._lib.gprn_set_sweep_order(self._h, int(order)), 'set_sweep_order')
 
     def comm_init(self, world, rank, unique_id):
         buf = ctypes.create_string_buffer(bytes(unique_id), 128) if unique_id else None

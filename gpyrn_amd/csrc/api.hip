@@ -216,6 +216,7 @@ static void free_problem(gprn_ctx* c)
     dev_free(c->d_variance); dev_free(c->d_mu); dev_free(c->d_var);
     dev_free(c->d_mu_save); dev_free(c->d_var_save);
     dev_free(c->d_mu_alt); dev_free(c->d_var_alt);
+    dev_free(c->d_mu_old); c->mu_old_cap = 0;
     if (c->d_loop_ctl) { hipFree(c->d_loop_ctl); c->d_loop_ctl = nullptr; }
     small_batch_free(c);
     mid_batch_free(c);
@@ -757,6 +758,10 @@ extern "C" int gprn_comm_init(gprn_ctx* c, int world, int rank, const char* id12
     DeviceLock lock_(c);
     if (!c || world < 1 || rank < 0 || rank >= world) return bad(c, "comm_init: bad argument");
     if (c->N) return bad(c, "comm_init: call before set_data");
+    if (c->sweep_order != GPRN_ORDER_REFERENCE && (world > 1 || getenv("GPRN_FORCE_RCCL"))) {
+        c->err = "comm_init: a communicator is not supported under the sequential sweep order (gprn_set_sweep_order)";
+        return GPRN_E_UNSUPPORTED;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     comm_teardown(c);
     c->world = world; c->rank = rank;

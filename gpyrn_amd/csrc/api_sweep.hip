@@ -260,8 +260,10 @@ static int small_sweep(gprn_ctx* c, const double* mu_in, const double* var_in, d
     TRY(ensure_small_sweep_tabs(c));
     // (under a data mask the points of zero precision of each phase get their state from mask.hip right behind it)
     TRY(small_phase(c, sweep_phase(c, false), false, scal, mu_in, var_in, mu_out, var_out, done));
+    TRY(order_small(c, sweep_phase(c, false), false, mu_in, var_in, mu_out, var_out, done));   // (sequential order only)
     TRY(mask_rows(c, sweep_phase(c, false), false, mu_out, var_out, done));
     TRY(small_phase(c, sweep_phase(c, true), true, scal, mu_in, var_in, mu_out, var_out, done));
+    TRY(order_small(c, sweep_phase(c, true), true, mu_in, var_in, mu_out, var_out, done));
     TRY(mask_rows(c, sweep_phase(c, true), true, mu_out, var_out, done));
     return small_tail(c, out4, scal, mu_out, var_out, loop);
 }
@@ -273,6 +275,7 @@ static int small_sweep(gprn_ctx* c, const double* mu_in, const double* var_in, d
 int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::function<int()>& chain_started)
 {
     const size_t o = (size_t)ph.slot0 * ph.ld;
+    TRY(order_snapshot(c, ph));                      // (sequential order: the means this phase starts from)
     TRY(vec_prep(c, ph, weights));
     // B = I + D^1/2 K D^1/2: built by factor_invert -- only the tiles its first outer panel's tile steps touch; the
     // others are formed from K inside that panel's K = 512 update (overlap bit 1).
@@ -302,6 +305,10 @@ int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::fu
         TRY(vec_logdet(c, ph, BUF_B, scal));
         TRY(vec_finalize(c, ph, scal, false));
     }
+    // sequential order: the means of the groups 1 .. q - 1 again, each from the new means of the groups before it -- on this
+    // stream, so whatever is ordered behind the phase (the node term beside the weight phase, the deferred end of a sweep:
+    // overlap bits 4 and 16) reads refreshed means
+    TRY(order_refresh(c, ph, weights));
     return mask_rows(c, ph, weights, c->d_mu, c->d_var, nullptr);                                  // under a data mask: mu, var where d = 0 (mask.hip)
 }
 

@@ -270,6 +270,11 @@ struct gprn_ctx {
     void* mid_batch = nullptr;       // MidBatch (midn.hip): the worker context and its slabs, owned by the PARENT context
     int batch_mem_mb = -1;           // gprn_set_option "batch_mem_mb": device memory one chunk of evaluations may take; -1: a share of what is free
     int last_batch_chunk = 0;        // read-only option "batch_chunk": evaluations per chunk in the last gprn_elbocalc_batch call
+    // ---- sweep order (gprn_set_sweep_order, order.hip)
+    int sweep_order = 0;             // GPRN_ORDER_REFERENCE (Jacobi, quirk Q6) or GPRN_ORDER_SEQUENTIAL
+    double* d_mu_old = nullptr;      // sequential order on the launch path: the means a phase started from (order_snapshot)
+    size_t mu_old_cap = 0;
+    int n_states = 1;                // copies of the state behind d_mu (a batch's worker context: its evaluations)
 };
 
 // The matrices a call works on -- a half-sweep, a set-up, a prediction, a diagnostic -- passed by const reference to
@@ -492,6 +497,15 @@ int mask_rows(gprn_ctx* c, const Phase& ph, bool weights, double* mu, double* va
 int mask_prepare(gprn_ctx* c);       // buffers, tables and task lists for the current slots (build_tables: the set-up)
 void mask_free(gprn_ctx* c);
 void mask_invalidate(gprn_ctx* c);   // the slots changed (build_tables rebuilds them)
+
+// order.hip: the sequential sweep order (no-ops under the reference's order and for q = 1).  order_snapshot before a
+// phase's head, order_refresh behind its finalize (launch path: phase_core); order_small behind a half-sweep launch of the
+// one-tile path, order_small_batch the same for n_eval evaluations (lanes: the half-sweep's SmallPhaseArgs per evaluation)
+int order_snapshot(gprn_ctx* c, const Phase& ph);
+int order_refresh(gprn_ctx* c, const Phase& ph, bool weights);
+int order_small(gprn_ctx* c, const Phase& ph, bool weights, const double* mu_in, const double* var_in,
+                double* mu_out, double* var_out, const int* done);
+int order_small_batch(gprn_ctx* c, const void* lanes, bool weights, int n_eval);
 
 // meanfield.py:640-643: np.std / np.mean of the last three values, operation by operation (one rounding each)
 static inline bool elbo_stop_rule(double e0, double e1, double e2)

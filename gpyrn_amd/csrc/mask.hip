@@ -187,6 +187,10 @@ extern "C" int gprn_set_mask(gprn_ctx* c, const uint8_t* mask)
         c->err = "set_mask: a data mask is not supported on a context with a communicator";
         return GPRN_E_UNSUPPORTED;
     }
+    if (mask && c->sweep_order != GPRN_ORDER_REFERENCE) {
+        c->err = "set_mask: a data mask is not supported under the sequential sweep order (gprn_set_sweep_order)";
+        return GPRN_E_UNSUPPORTED;
+    }
     if (mask && c->keep_sigma) { c->err = "set_mask: not supported with gprn_keep_sigma(1)"; return GPRN_E_UNSUPPORTED; }
     std::vector<std::vector<int>> U(G);
     if (mask) {

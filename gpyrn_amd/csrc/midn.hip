@@ -127,11 +127,11 @@ static int mid_ensure(gprn_ctx* c, int want, int* cap_out)
         // (free_problem's fields, sized for cap evaluations; everything a phase's launchers read from the context)
         void* old[] = {w->d_time, w->d_yraw, w->d_mu, w->d_var, w->d_yres, w->d_variance, w->d_logdetK, w->d_scal_base, w->d_elbo_part,
                        w->d_out, w->d_d, w->d_s, w->d_pred, w->d_z, w->d_u, w->d_cs, w->d_ct, w->d_part, w->d_info, w->d_fin_terms,
-                       w->d_fin_tickets};
+                       w->d_fin_tickets, w->d_mu_old};
         for (void* ptr : old) if (ptr) hipFree(ptr);
         w->d_time = w->d_yraw = w->d_mu = w->d_var = w->d_yres = w->d_variance = w->d_logdetK = w->d_scal_base = nullptr;
         w->d_elbo_part = w->d_out = w->d_d = w->d_s = w->d_pred = w->d_z = w->d_u = w->d_cs = w->d_ct = w->d_part = nullptr;
-        w->d_info = nullptr; w->d_fin_terms = nullptr; w->d_fin_tickets = nullptr;
+        w->d_info = nullptr; w->d_fin_terms = nullptr; w->d_fin_tickets = nullptr; w->d_mu_old = nullptr; w->mu_old_cap = 0;
     }
     w->N = N; w->p = p; w->q = q; w->G = G; w->ld = ld; w->T = T;
     w->h_yerr2 = c->h_yerr2;
@@ -139,6 +139,7 @@ static int mid_ensure(gprn_ctx* c, int want, int* cap_out)
     w->owner.assign(G, 0);
     w->nslot = (int)nslot;
     w->out_cap = cap;
+    w->n_states = cap;
     MB_TRY(mb_alloc(c, &w->d_time, (size_t)N));
     MB_TRY(mb_alloc(c, &w->d_yraw, pn));
     MB_TRY(mb_alloc(c, &w->d_mu, (size_t)cap * d));
@@ -494,6 +495,7 @@ int mid_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_kpa
     w->overlap_opt = c->overlap_opt;
     w->acc_opt = c->acc_opt;
     w->fenced_finalize = c->fenced_finalize;
+    w->sweep_order = c->sweep_order;
     w->pad_kb_opt = c->pad_kb_opt; w->pad_small_kb_opt = c->pad_small_kb_opt;
     w->prof.on = false;
     const size_t d = (size_t)(c->p + 1) * c->q * c->N, pn = (size_t)c->p * c->N;

@@ -61,9 +61,19 @@ class inference:
             reach arithmetic.  ``_initMuVar`` reads a masked y as 0.  Every latent GP still lives on all N times;
             ``predict`` at a masked time is the imputation.  ``inference.from_series`` builds a mask from series on
             different time grids.
+        sweep_order: 'reference' (default) or 'sequential', keyword only
+            The order of a sweep's mean updates (not in the reference).  'reference' is the reference's own: every node
+            mean from the OLD means of the other nodes, every weight mean from the OLD weight means of the other nodes of
+            its output -- an iteration that diverges at q >= 3.  'sequential' updates the node means in turn, node j from
+            the NEW means of the nodes before it, then the weight means in turn over the node index: a proper coordinate
+            ascent.  With q = 1 the two are the same computation.  Everything
+            that sweeps follows it (``ELBOcalc``, ``nELBO``, ``optimize``, ``mcmc``, ``nELBO_batch``, ``grad_ELBO``, ...)
+            except ``ELBOaux`` and ``_updateSigMu``, which restate reference functions.  Not with ``mask`` or ``comm``.
     """
 
-    def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None):
+    _SWEEP_ORDERS = {'reference': _hip.ORDER_REFERENCE, 'sequential': _hip.ORDER_SEQUENTIAL}
+
+    def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference'):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -97,6 +107,7 @@ class inference:
         self._device = device
         self._comm = comm
         self._ctx = None
+        self._sweep_order = self._check_sweep_order(sweep_order)
         self._prior_key = None
         self.last_info = 0
 
@@ -118,6 +129,28 @@ class inference:
         if comm is not None:
             raise NotImplementedError('mask: a sharded inference object does not support a data mask')
         return m
+
+    def _check_sweep_order(self, order):
+        """'reference' or 'sequential', validated before anything touches a device."""
+        if not isinstance(order, str) or order not in self._SWEEP_ORDERS:
+            raise ValueError(f"sweep_order must be 'reference' or 'sequential', got {order!r}")
+        if order != 'reference':
+            if self.mask is not None:
+                raise NotImplementedError('sweep_order: the sequential order is not supported under a data mask')
+            if self._comm is not None:
+                raise NotImplementedError('sweep_order: the sequential order is not supported on a sharded inference object')
+        return order
+
+    @property
+    def sweep_order(self):
+        """ 'reference' or 'sequential': the order of a sweep's mean updates """
+        return self._sweep_order
+
+    @sweep_order.setter
+    def sweep_order(self, order):
+        self._sweep_order = self._check_sweep_order(order)
+        if self._ctx is not None:
+            self._ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
 
     @classmethod
     def from_series(cls, q, series, **kwargs):
@@ -355,6 +388,8 @@ class inference:
                 ctx.comm_init(comm.world, comm.rank, comm.unique_id())
                 comm.done()
             ctx.set_data(np.asarray(self.time, dtype=float), self.y, self.yerr, self.q)
+            if self._sweep_order != 'reference':
+                ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
             if self.mask is not None and not self.mask.all():     # (an all-True mask is no mask: the same kernels run)
                 ctx.set_mask(self.mask)
             if comm is not None and comm.world > 1:
@@ -583,6 +618,7 @@ class inference:
         ctx.set_jitters(np.sqrt(np.asarray(jitt2, dtype=float)))
         ctx.set_muvar(np.asarray(mu, dtype=float), np.asarray(var, dtype=float))
         ctx.keep_sigma(True)
+        ctx.set_sweep_order(_hip.ORDER_REFERENCE)          # (a restatement of the reference's function: its order, always)
         try:
             e, _, info = ctx.sweep(1, commit=True)
             sigmaF = np.array([ctx.get_matrix(_hip.M_SIGMA, j) for j in range(self.q)])
@@ -590,6 +626,7 @@ class inference:
                                for k in range(self.qp)]).reshape(self.q, self.p, self.N, self.N)
         finally:
             ctx.keep_sigma(False)
+            ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
         self.last_info = self.last_info or info
         new_mu, new_var = ctx.get_muvar()
         return np.float64(e[0]), new_mu, new_var, sigmaF, sigmaW

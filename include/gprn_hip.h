@@ -277,6 +277,21 @@ int gprn_elbocalc(gprn_ctx* ctx, int do_setup, const double* y_resid, const doub
                   const double* var, int max_iter, double* history, int cap, int* n_history, int* iterations,
                   int* converged, double* mu_out, double* var_out);
 
+/* ---- the order of a sweep's mean updates (new).
+ * GPRN_ORDER_REFERENCE (default): the reference's Jacobi ordering, quirk Q6 -- every node mean from the OLD means of the other
+ * nodes, every weight mean from the OLD weight means of the other nodes of its output (meanfield.py:765-792, 838-864).  At
+ * q >= 3 that iteration diverges.
+ * GPRN_ORDER_SEQUENTIAL: a proper coordinate ascent.  Per sweep the node means in turn, j = 0 .. q - 1, node j reading the
+ * NEW means of the nodes k < j and the sweep's starting means of the nodes k > j; then the weight means in turn over the
+ * node index j, per output, in the same way.  Inside a half-sweep the precisions -- and with them the factors, variances,
+ * tr B^-1, log det B and the Q1 traces -- read none of the means the order is about and are computed as before, all latent
+ * GPs of the phase side by side; node 0 and the weights of node 0 are updated by the reference order's own formula; with
+ * q = 1 the two orders are the same computation (same launches, same bits).
+ * Governs gprn_sweep, gprn_elbocalc and gprn_elbocalc_batch; factors and state are kept.  GPRN_E_ARG for another value;
+ * GPRN_E_UNSUPPORTED when the sequential order meets a communicator or a data mask, whichever is set second. */
+enum { GPRN_ORDER_REFERENCE = 0, GPRN_ORDER_SEQUENTIAL = 1 };
+int gprn_set_sweep_order(gprn_ctx* ctx, int order);
+
 /* (On a sharded context every local finding of gprn_elbocalc -- arguments, call order, a failing setter -- is agreed between
  * the ranks before its first collective: either every rank goes on or every rank returns.) */
 
