@@ -210,7 +210,31 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     return GPRN_OK;
 }
 
-static void free_problem(gprn_ctx* c)
+void free_slot_arrays(gprn_ctx* c)
+{
+    dev_free(c->d_d); dev_free(c->d_s); dev_free(c->d_pred); dev_free(c->d_z); dev_free(c->d_u);
+    dev_free(c->d_cs); dev_free(c->d_ct); dev_free(c->d_part); dev_free(c->d_fin_terms); dev_free(c->d_fin_tickets);
+    dev_free(c->d_info);
+    c->nslot = 0;
+}
+
+int alloc_slot_arrays(gprn_ctx* c, int nslot)
+{
+    const size_t vec = (size_t)nslot * c->ld;
+    TRY(dev_alloc(c, &c->d_d, vec)); TRY(dev_alloc(c, &c->d_s, vec)); TRY(dev_alloc(c, &c->d_pred, vec));
+    TRY(dev_alloc(c, &c->d_z, vec)); TRY(dev_alloc(c, &c->d_u, vec)); TRY(dev_alloc(c, &c->d_cs, vec));
+    TRY(dev_alloc(c, &c->d_ct, vec));
+    TRY(dev_alloc(c, &c->d_part, vec * c->T * 2));
+    TRY(dev_alloc(c, &c->d_fin_terms, vec * 2));         // (vec_reduce_finalize, vecops.hip: tickets zero between launches)
+    TRY(dev_alloc(c, &c->d_fin_tickets, (size_t)nslot));
+    TRY(dev_alloc(c, &c->d_info, 3 * (size_t)nslot));
+    HIP_TRY(c, hipMemset(c->d_fin_tickets, 0, (size_t)nslot * sizeof(unsigned)));
+    HIP_TRY(c, hipMemset(c->d_info, 0, 3 * (size_t)nslot * sizeof(int)));
+    c->nslot = nslot;
+    return GPRN_OK;
+}
+
+void free_problem(gprn_ctx* c)
 {
     dev_free(c->d_time); dev_free(c->d_yraw); dev_free(c->d_yerr2); dev_free(c->d_yres);
     dev_free(c->d_variance); dev_free(c->d_mu); dev_free(c->d_var);
@@ -242,13 +266,9 @@ static void free_problem(gprn_ctx* c)
     c->h_mask.clear(); c->mask_U.clear(); c->mask_upad = 0;
     dev_free(c->tab_node); dev_free(c->tab_weight); dev_free(c->tab_setup);
     dev_free(c->d_slotgp_node); dev_free(c->d_slotgp_weight); dev_free(c->d_slotgp_setup);
-    dev_free(c->d_d); dev_free(c->d_s); dev_free(c->d_pred); dev_free(c->d_z); dev_free(c->d_u);
-    dev_free(c->d_cs); dev_free(c->d_ct); dev_free(c->d_part);
-    if (c->d_fin_terms) hipFree(c->d_fin_terms);
-    if (c->d_fin_tickets) hipFree(c->d_fin_tickets);
-    c->d_fin_terms = nullptr; c->d_fin_tickets = nullptr;
-    dev_free(c->d_scal_base); c->d_scal = nullptr; dev_free(c->d_elbo_part); dev_free(c->d_out); dev_free(c->d_info);
-    c->nslot = 0; c->out_cap = 0;
+    free_slot_arrays(c);
+    dev_free(c->d_scal_base); c->d_scal = nullptr; dev_free(c->d_elbo_part); dev_free(c->d_out);
+    c->out_cap = 0;
     c->factored = c->have_yres = c->have_jit = c->have_muvar = false;
     c->tables_ready = false;
     c->small_tabs_ready = c->small_sweep_ready = c->setup1_ready = false;
@@ -893,23 +913,13 @@ int build_tables(gprn_ctx* c)
         tab_forget(c, c->tab_node); tab_forget(c, c->tab_weight); tab_forget(c, c->tab_setup);
         dev_free(c->tab_node); dev_free(c->tab_weight); dev_free(c->tab_setup);
         dev_free(c->d_slotgp_node); dev_free(c->d_slotgp_weight); dev_free(c->d_slotgp_setup);
-        dev_free(c->d_d); dev_free(c->d_s); dev_free(c->d_pred); dev_free(c->d_z); dev_free(c->d_u);
-        dev_free(c->d_cs); dev_free(c->d_ct); dev_free(c->d_part); dev_free(c->d_info);
-        if (c->d_fin_terms) hipFree(c->d_fin_terms);
-        if (c->d_fin_tickets) hipFree(c->d_fin_tickets);
-        c->d_fin_terms = nullptr; c->d_fin_tickets = nullptr;
-        const size_t tab = (size_t)want * GPRN_NBUF, vec = (size_t)want * c->ld;
+        free_slot_arrays(c);
+        const size_t tab = (size_t)want * GPRN_NBUF;
         TRY(dev_alloc(c, &c->tab_node, tab)); TRY(dev_alloc(c, &c->tab_weight, tab));
         TRY(dev_alloc(c, &c->tab_setup, tab));
         TRY(dev_alloc(c, &c->d_slotgp_node, want)); TRY(dev_alloc(c, &c->d_slotgp_weight, want));
         TRY(dev_alloc(c, &c->d_slotgp_setup, want));
-        TRY(dev_alloc(c, &c->d_d, vec)); TRY(dev_alloc(c, &c->d_s, vec)); TRY(dev_alloc(c, &c->d_pred, vec));
-        TRY(dev_alloc(c, &c->d_z, vec)); TRY(dev_alloc(c, &c->d_u, vec)); TRY(dev_alloc(c, &c->d_cs, vec));
-        TRY(dev_alloc(c, &c->d_ct, vec));
-        TRY(dev_alloc(c, &c->d_part, (size_t)want * c->T * 2 * c->ld));
-        TRY(dev_alloc(c, &c->d_info, 3 * (size_t)want));
-        HIP_TRY(c, hipMemset(c->d_info, 0, 3 * (size_t)want * sizeof(int)));
-        c->nslot = want;
+        TRY(alloc_slot_arrays(c, want));
     }
     for (int g : c->loc_nodes) TRY(ensure_gp_storage(c, g));
     for (int g : c->loc_weights) TRY(ensure_gp_storage(c, g));

@@ -22,8 +22,9 @@ static int dev_alloc(gprn_ctx* c, T** p, size_t count)
     if (count == 0) count = 1;
     hipError_t e = hipMalloc((void**)p, count * sizeof(T));
     if (e != hipSuccess) {
+        (void)hipGetLastError();          // (not sticky: a batch call allocates again, in halves -- gprn_elbocalc_batch)
         c->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? GPRN_E_NOMEM : GPRN_E_HIP;
+        return GPRN_E_NOMEM;
     }
     return GPRN_OK;
 }
@@ -37,6 +38,8 @@ static inline int bad(gprn_ctx* c, const char* msg) { if (c) c->err = msg; retur
 // Runs `body` (an entry point that factorises); when one of its in-kernel dependency waits gave up
 // (GPRN_E_WAIT_TIMEOUT: a serialising tool, a starved device, ...), the context is latched to the event
 // schedule and the body runs once more -- `body` must restore what it changed before it starts over.
+// ran_on: the context the body's launches went through when that is not c itself (a batch's worker, midn.hip: same device,
+// same streams) -- it is latched beside c, and its factor_check_waits knows which flag the wait was for.
 // On a sharded context the verdict is shared first (one max-reduce of the "timed out" word per call): the body
 // issues collectives, so either every rank runs it again or none does -- a rank re-running on its own would issue
 // its broadcasts and its all-reduce a second time while the others have moved on.
@@ -88,8 +91,9 @@ static inline int agree_to_start(gprn_ctx* c, int local_rc, const char* what)
 }
 
 template <class F>
-static int with_event_fallback(gprn_ctx* c, const char* what, F&& body, bool collective = false)
+static int with_event_fallback(gprn_ctx* c, const char* what, F&& body, bool collective = false, gprn_ctx* ran_on = nullptr)
 {
+    gprn_ctx* const r = ran_on ? ran_on : c;
     int rc = body(false);
     bool again = rc == GPRN_E_WAIT_TIMEOUT;
     if (collective) {
@@ -97,14 +101,14 @@ static int with_event_fallback(gprn_ctx* c, const char* what, F&& body, bool col
         if (ra) return ra;
     }
     if (!again) return rc;
-    hipStreamSynchronize(c->stream); hipStreamSynchronize(c->stream2); hipStreamSynchronize(c->stream3);
-    if (c->stream4) hipStreamSynchronize(c->stream4);
-    c->use_flags = 0;
+    hipStreamSynchronize(r->stream); hipStreamSynchronize(r->stream2); hipStreamSynchronize(r->stream3);
+    if (r->stream4) hipStreamSynchronize(r->stream4);
+    c->use_flags = 0; r->use_flags = 0;
     c->fallbacks += 1;
     if (rc == GPRN_E_WAIT_TIMEOUT)
         fprintf(stderr, "[gprn] %s: a device-side dependency wait timed out after %d ms%s; re-running the call with "
                         "HIP events (device-side waits are now off for this context)\n", what, c->wait_budget_ms,
-                c->last_timeout.c_str());
+                r->last_timeout.c_str());
     else
         fprintf(stderr, "[gprn] %s: a device-side dependency wait timed out on another rank; re-running the call with "
                         "HIP events on this rank too (device-side waits are now off for this context)\n", what);
@@ -158,6 +162,11 @@ int exchange_rows(gprn_ctx* c, bool weights);
 int reduce_scalars(gprn_ctx* c, double* scal);     // all-reduce of a sweep's scalars (one copy of d_scal_base)
 int upload_table(gprn_ctx* c, double** d_tab, const std::vector<double*>& rows);
 int build_tables(gprn_ctx* c);
+void free_problem(gprn_ctx* c);                   // every device and pinned array of the context's problem
+// the per-slot arrays (d, s, pred, z, u, colsq, colt, partial column sums, finalising terms and tickets, pivot verdicts):
+// freed, and allocated for c->nslot = nslot slots of the context's ld and T
+void free_slot_arrays(gprn_ctx* c);
+int alloc_slot_arrays(gprn_ctx* c, int nslot);
 int check_info(gprn_ctx* c, const int* d_info, const std::vector<int>& gps, int* first);
 int ensure_gp_storage(gprn_ctx* c, int g);
 // ---- defined in api_more.hip (diagnostics): a scratch "problem" of `batch` ld x ld matrices

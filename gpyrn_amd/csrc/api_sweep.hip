@@ -614,7 +614,7 @@ static int elbocalc_small(gprn_ctx* c, const ElboIo& io, int max_iter, std::vect
         int nb = 0;
         // (the stop rule cannot fire before trip 4, and a warm-started evaluation -- nELBO's case -- usually stops there: the
         // first batch ends at trip 4, so that no sweep is enqueued past the usual verdict; 4.7 us per no-op launch otherwise)
-        const int nb_max = s0 <= 1 ? 4 : K;
+        const int nb_max = s0 <= 1 ? ELBO_LEAD : K;
         for (; nb < nb_max && s <= max_iter; ++nb, ++s) {
             // sweep 0 (discarded) and trip 1 both start from A; from then on the copies alternate
             const bool from_a = s <= 1 || (s & 1);
@@ -711,7 +711,6 @@ extern "C" int gprn_elbocalc(gprn_ctx* c, int do_setup, const double* y_resid, c
             if (rc < 0) return rc;
             info = rc;
         }
-        double e = 0.0;
         // Quirk Q7: the first ELBOaux call's update is discarded and its ELBO kept as elboArray[0] (:627-628); the loop's
         // first trip then repeats that very call (same state in, :636) -- elboArray[1] == elboArray[0] by construction.
         // The sweep is deterministic (no atomics in any reduction), so it runs ONCE, committed, and its ELBO is entered
@@ -719,29 +718,25 @@ extern "C" int gprn_elbocalc(gprn_ctx* c, int do_setup, const double* y_resid, c
         // The stop rule cannot fire before trip 4 (:640), so trips 1 .. min(4, max_iter) go out as ONE call of sweep_impl: one
         // host synchronisation instead of four, and each sweep's ELBO assembly runs beside the next sweep's node phase
         // (overlap bit 16: same bits).  A warm-started evaluation -- nELBO's case -- usually stops right there.
-        const int first_commit = max_iter >= 1 ? 1 : 0;
-        const int nfirst = std::max(1, std::min(max_iter, 4));
-        double efirst[4] = {0.0, 0.0, 0.0, 0.0};
-        rc = with_event_fallback(c, "sweep", [&](bool retry) { return sweep_impl(c, nfirst, first_commit, efirst, nullptr, retry); }, true);
-        if (rc < 0) return rc;
-        if (!info) info = rc;
-        e = efirst[0];
-        hist.push_back(e);
-        if (first_commit) {
-            for (int k = 0; k < nfirst; ++k) hist.push_back(efirst[k]);
-            iter = nfirst;
-            const size_t n = hist.size();
-            if (iter > 3 && elbo_stop_rule(hist[n - 3], hist[n - 2], hist[n - 1])) conv = 1;
-        }
-        while (!conv && iter < max_iter) {
-            rc = with_event_fallback(c, "sweep", [&](bool retry) { return sweep_impl(c, 1, 1, &e, nullptr, retry); }, true);
+        // (a NaN is carried to max_iter, as the reference does: the rule is false for it)
+        ElboLoop loop;
+        auto enter = [&](double e) {                   // into the history and the loop's record; true: another trip
+            if (hist.empty()) hist.push_back(e);       // elboArray[0]
+            const bool go_on = loop.enter(e, max_iter);
+            if (loop.iters) hist.push_back(e);         // elboArray[trip]
+            return go_on;
+        };
+        double e[ELBO_LEAD] = {0.0, 0.0, 0.0, 0.0};
+        int n = elbo_lead(max_iter);                   // sweeps of the next call of sweep_impl: later trips go one by one
+        bool go_on = false;
+        do {
+            rc = with_event_fallback(c, "sweep", [&](bool retry) { return sweep_impl(c, n, max_iter >= 1, e, nullptr, retry); }, true);
             if (rc < 0) return rc;
             if (!info) info = rc;
-            hist.push_back(e);
-            iter += 1;
-            const size_t n = hist.size();
-            if (iter > 3 && elbo_stop_rule(hist[n - 3], hist[n - 2], hist[n - 1])) { conv = 1; break; }
-        }
+            for (int k = 0; k < n; ++k) go_on = enter(e[k]);
+            n = 1;
+        } while (go_on);
+        iter = loop.iters; conv = loop.converged;
         if (mu_out && (rc = gprn_get_muvar(c, mu_out, var_out))) return rc;
     }
     *n_history = (int)hist.size();
@@ -781,29 +776,78 @@ extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel
     if (comm_active(c) || c->world != 1) { c->err = "elbocalc_batch: one rank only (a pool of ranks splits the list itself)"; return GPRN_E_UNSUPPORTED; }
     TRY(build_tables(c));
     const bool small = c->T == 1 && small_applies(c);
-    const size_t d = (size_t)(c->p + 1) * c->q * c->N, pn = (size_t)c->p * c->N;
-    int chunk = small ? small_batch_chunk(c) : n_eval;             // (midn.hip sizes its own chunks: it knows what a matrix costs)
-    if (small) c->last_batch_chunk = std::min(chunk, n_eval);
-    for (int e0 = 0; e0 < n_eval;) {
-        const int ne = std::min(chunk, n_eval - e0);
-        const double* kp = kernel_params + (size_t)e0 * n_kernel_params;
-        double* mo = mu_out ? mu_out + (size_t)e0 * d : nullptr;
-        double* vo = var_out ? var_out + (size_t)e0 * d : nullptr;
-        auto run = small ? small_batch_elbocalc : mid_batch_elbocalc;
-        const int rc = run(c, ne, kp, n_kernel_params, y_resid + (size_t)e0 * pn, jitters + (size_t)e0 * c->p, mu + (size_t)e0 * d,
-                           var + (size_t)e0 * d, max_iter, elbo + e0, iterations + e0, converged + e0, info + e0, mo, vo);
-        if (rc == GPRN_E_NOMEM && small && ne > 1) {
-            // the budget is an estimate: the device has less in one piece than it reports free -- the same chunk in halves
-            // (nothing of it has run: the buffers are allocated before anything is enqueued)
-            small_batch_free(c);
-            chunk = std::max(1, ne / 2);
-            c->last_batch_chunk = chunk;
-            c->err.clear();
-            continue;
-        }
-        if (rc) return rc;
-        e0 += ne;
-    }
+    // (a one-tile problem with the small path switched off -- option "small_path" = 0, or gprn_keep_sigma on: there is no
+    // batched form for it, as include/gprn_hip.h promises; inference.nELBO_batch then evaluates one by one -- ADVICE r5)
+    if (!small && c->T < 2) { c->err = "elbocalc_batch: one-tile problems run side by side on the small path only"; return GPRN_E_UNSUPPORTED; }
+    TRY(batch_validate(c, n_kernel_params));
+    const auto reserve = small ? small_batch_reserve : mid_batch_reserve;
+    const auto run = small ? small_batch_run : mid_batch_run;
+    // the budget is an estimate: when the device has less in one piece than it reports free, the list runs in smaller chunks
+    // (nothing has run yet: the buffers are allocated before anything is enqueued)
+    int cap = 0, want = n_eval, rc;
+    while ((rc = reserve(c, want, &cap)) == GPRN_E_NOMEM && cap > 1) want = cap / 2;
+    if (rc) return rc;
+    if (want != n_eval) c->err.clear();
+    c->last_batch_chunk = std::min(cap, n_eval);
+    const BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info,
+                     mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N};
+    for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(run(c, io.slice(e0, std::min(cap, n_eval - e0))));
     return GPRN_OK;
 }
 
+
+int batch_validate(gprn_ctx* c, int n_kpar)
+{
+    int kp_total = 0;
+    for (int g = 0; g < c->G; ++g) {
+        if (!c->kspec[g].set || c->kspec[g].uploaded) { c->err = "elbocalc_batch: every latent GP needs a device kernel program"; return GPRN_E_UNSUPPORTED; }
+        kp_total += c->kspec[g].n_params;
+    }
+    if (kp_total != n_kpar) { c->err = "elbocalc_batch: kernel_params has the wrong length per evaluation"; return GPRN_E_ARG; }
+    return GPRN_OK;
+}
+
+size_t batch_stage_bytes(const gprn_ctx* c, int cap)
+{
+    return (size_t)cap * c->G * fill_program_bytes() + 2 * (size_t)cap * ((size_t)c->p * c->N + (size_t)(c->p + 1) * c->q * c->N) * sizeof(double);
+}
+
+int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchDst& dst, hipStream_t stream, LapTimer& t, double* us_host)
+{
+    const int B = io.n, G = c->G, p = c->p, N = c->N;
+    const size_t pb = fill_program_bytes();
+    double* const yres_h = (double*)(pin + (size_t)cap * G * pb);
+    double* const var_h = yres_h + (size_t)cap * io.yv;
+    double* const mu_h = var_h + (size_t)cap * io.yv;
+    double* const v_h = mu_h + (size_t)cap * io.state;
+    for (int b = 0; b < B; ++b) {
+        const double* kp = io.kparams + (size_t)b * io.n_kpar;
+        for (int g = 0; g < G; ++g) {
+            if (!fill_program_with(c->kspec[g], kp, pin + ((size_t)b * G + g) * pb)) {
+                c->err = "elbocalc_batch: a kernel that is not an even function of t_i - t_j"; return GPRN_E_UNSUPPORTED;
+            }
+            kp += c->kspec[g].n_params;
+        }
+        for (int i = 0; i < p; ++i) {
+            const double j2 = io.jitters[(size_t)b * p + i] * io.jitters[(size_t)b * p + i];
+            for (int n = 0; n < N; ++n) var_h[b * io.yv + (size_t)i * N + n] = j2 + c->h_yerr2[(size_t)i * N + n];
+        }
+    }
+    memcpy(yres_h, io.y_resid, B * io.yv * sizeof(double));
+    memcpy(mu_h, io.mu, B * io.state * sizeof(double));
+    memcpy(v_h, io.var, B * io.state * sizeof(double));
+    *us_host = t.lap();
+    HIP_TRY(c, hipMemcpyAsync(dst.programs, pin, (size_t)B * G * pb, hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.yres, yres_h, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.variance, var_h, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.mu, mu_h, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.var, v_h, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
+    return GPRN_OK;
+}
+
+bool batch_timers_on()
+{
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("GPRN_BATCH_TIMERS"); on = e ? atoi(e) : 0; }
+    return on != 0;
+}

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <chrono>
 #include <functional>
 #include <string>
 #include <map>
@@ -475,17 +477,45 @@ struct SmallLoop { int* ctl; double *hist, *last3; int sweep, hist_at, max_iter;
 // mu^T K^-1 mu, Q1 traces, ELBO assembly of the sweep whose new state is (mu, var); loop: the stop rule too, or null
 int small_tail(gprn_ctx* c, double* out4, double* scal, const double* mu, const double* var, const SmallLoop* loop = nullptr);
 int small_prior(gprn_ctx* c, double** d_tab, const int* d_job_gp, double** d_kinv_out, int njobs, int* d_info);
-// n_eval independent evaluations of the ELBOcalc loop side by side (gprn_elbocalc_batch); GPRN_E_UNSUPPORTED where it does not apply
-int small_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_kpar, const double* y_resid, const double* jitters,
-                         const double* mu, const double* var, int max_iter, double* elbo, int* iters, int* conv, int* info,
-                         double* mu_out, double* var_out);
+// One call of gprn_elbocalc_batch -- its pointers and counts -- or a run of its evaluations (slice)
+struct BatchIo {
+    int n; const double* kparams; int n_kpar; const double *y_resid, *jitters, *mu, *var; int max_iter;
+    double* elbo; int *iters, *conv, *info; double *mu_out, *var_out;     // (mu_out, var_out: both or neither)
+    int p; size_t state, yv;               // per evaluation: jitters, doubles of mu / var, doubles of y_resid
+    BatchIo slice(int e0, int ne) const    // evaluations [e0, e0 + ne)
+    {
+        return BatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, y_resid + e0 * yv, jitters + (size_t)e0 * p, mu + e0 * state,
+                       var + e0 * state, max_iter, elbo + e0, iters + e0, conv + e0, info + e0,
+                       mu_out ? mu_out + e0 * state : nullptr, var_out ? var_out + e0 * state : nullptr, p, state, yv};
+    }
+};
+// What both drivers of gprn_elbocalc_batch ask of the caller's kernels and kernel_params (api_sweep.hip)
+int batch_validate(gprn_ctx* c, int n_kpar);
+// GPRN_BATCH_TIMERS=1 (probes): where the host's time of a chunk goes -- staging, enqueue, waits, read-back -- on stderr
+bool batch_timers_on();
+struct LapTimer {
+    typedef std::chrono::steady_clock clock;
+    clock::time_point begin = clock::now(), mark = begin;
+    static double us(clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
+    double lap() { const auto now = clock::now(); const double t = us(mark, now); mark = now; return t; }   // since the last lap
+    double total() const { return us(begin, clock::now()); }
+};
+// The inputs of io's evaluations through a pinned buffer laid out for `cap` of them -- programs | y - mean | variance | mu |
+// var -- and from there to the driver's device buffers, five copies enqueued on `stream`; the host's part is a lap of the
+// driver's timer: *us_host
+struct BatchDst { void* programs; double *yres, *variance, *mu, *var; };
+int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchDst& dst, hipStream_t stream, LapTimer& t,
+                double* us_host);
+size_t batch_stage_bytes(const gprn_ctx* c, int cap);        // ... and the pinned buffer's size
+// The two drivers of gprn_elbocalc_batch (one tile: smalln.hip, one launch per half-sweep of ALL evaluations; above:
+// midn.hip, the launch schedule with batch = evaluations x latent GPs).  reserve: room for up to `want` evaluations, never
+// more than the memory budget pays for; *cap: what there is room for -- on GPRN_E_NOMEM what was tried (the caller halves).
+// run: io.n <= cap evaluations from staging to results.
+int small_batch_reserve(gprn_ctx* c, int want, int* cap);
+int small_batch_run(gprn_ctx* c, const BatchIo& io);
 void small_batch_free(gprn_ctx* c);
-// evaluations one chunk of gprn_elbocalc_batch may hold on the small path (memory budget), >= 1
-int small_batch_chunk(gprn_ctx* c);
-// midn.hip: the same for problems of more than one tile, through the launch schedule with batch = evaluations x latent GPs
-int mid_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_kpar, const double* y_resid, const double* jitters,
-                       const double* mu, const double* var, int max_iter, double* elbo, int* iters, int* conv, int* info,
-                       double* mu_out, double* var_out);
+int mid_batch_reserve(gprn_ctx* c, int want, int* cap);
+int mid_batch_run(gprn_ctx* c, const BatchIo& io);
 void mid_batch_free(gprn_ctx* c);
 size_t batch_budget_bytes(gprn_ctx* c);        // device memory a chunk of evaluations may take (option "batch_mem_mb")
 // api_sweep.hip: one half-sweep's factorisation with its head and tail (run_phase, midn.hip); scal: the sweep's scalars;
@@ -520,3 +550,26 @@ static inline bool elbo_stop_rule(double e0, double e1, double e2)
     const double crit = __builtin_fabs(ratio);
     return crit < 1e-3 && crit != 0.0;
 }
+
+// The first trips of the loop that go out without a host round trip between them: the stop rule cannot fire before trip 4
+// (:640), and a warm-started evaluation -- nELBO's case -- usually stops right there
+#define ELBO_LEAD 4
+static inline int elbo_lead(int max_iter) { return std::max(1, std::min(ELBO_LEAD, max_iter)); }
+
+// The host's record of one loop of meanfield.py:626-649: trips made, the last three values, the verdict.  Quirk Q7: the first
+// ELBOaux call (update discarded, ELBO kept as elboArray[0]) and the loop's first trip are the same computation on the same
+// input -- it runs once, and enter() takes its value twice (max_iter = 0: that sweep alone; no trip counts).
+struct ElboLoop {
+    int iters = 0, converged = 0;
+    double last3[3] = {0.0, 0.0, 0.0};
+    bool enter(double e, int max_iter)             // the ELBO of the next sweep; true: the loop goes on
+    {
+        if (iters == 0) {
+            last3[1] = e; last3[2] = e;
+            if (max_iter == 0) return false;
+        } else { last3[0] = last3[1]; last3[1] = last3[2]; last3[2] = e; }
+        iters += 1;
+        if (iters > 3 && elbo_stop_rule(last3[0], last3[1], last3[2])) { converged = 1; return false; }
+        return iters < max_iter;
+    }
+};

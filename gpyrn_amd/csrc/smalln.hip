@@ -14,7 +14,7 @@
 // Every reduction follows the order of the kernels it replaces (vecops.hip: k_lower_matvec, k_colops_partial / _reduce,
 // k_reduce_finalize, k_dot_self, k_q1_rows / k_sum_to, k_loglike_partial / k_elbo_final), so the two paths agree to
 // rounding of the compiler's contraction choices (tests/test_parity_gpu.py::test_small_path_matches_launch_schedule).
-#include "gprn_internal.h"
+#include "api_internal.h"
 #include "tile_mma.h"
 #include "diag_tile.h"
 #include "vecops.h"
@@ -31,7 +31,9 @@
 
 // LDS: the diagonal-block kernel's buffers and the tile contraction's stages are used in turn
 #define SMALL_MMA_DOUBLES (2 * 16 * (128 + 128 + 32))
-#define SMALL_LDS_DOUBLES (SMALL_MMA_DOUBLES > DIAG_LDS_DOUBLES ? SMALL_MMA_DOUBLES : DIAG_LDS_DOUBLES)
+// (the ACC forms of a prior matrix included: diag_tile<true>'s extra line, trsm_rows16's scratch of four waves)
+#define SMALL_MAX2(a, b) ((a) > (b) ? (a) : (b))
+#define SMALL_LDS_DOUBLES SMALL_MAX2(SMALL_MAX2(SMALL_MMA_DOUBLES, DIAG_LDS_DOUBLES_ACC), 4 * TRSM_SCRATCH)
 
 // B = L L^T, X = L^-1 for T in {1, 2} tiles by one workgroup; tiles at Bm / Xm (leading dimension ld)
 // N: rows that hold data -- the 16-column phases of a diagonal tile beyond them are identity padding and are not run
@@ -40,6 +42,9 @@
 template <int T, bool ACC = false>
 __device__ __forceinline__ void small_factor(double* lds, double* Bm, double* Xm, int ld, int* info, int slot, int N)
 {
+    // (ACC: `lds` is small_prior_body's buffer of SMALL_LDS_DOUBLES)
+    static_assert(!ACC || (SMALL_LDS_DOUBLES >= DIAG_LDS_DOUBLES_ACC && SMALL_LDS_DOUBLES >= 4 * TRSM_SCRATCH),
+                  "the ACC forms need diag_tile<true>'s extra line and trsm_rows16's scratch of four waves");
     diag_tile<ACC>(lds, (gptr_t)Bm, (gptr_t)Xm, ld, info, slot, 0, T == 1 ? (N + 15) / 16 : NSB);
     if (T == 1) return;
     sm_publish();
@@ -590,12 +595,12 @@ struct SmallBatchMem {
     unsigned* ticket = nullptr;
     double** ptrs = nullptr;          // pointer tables: [cap] x (3 tables of G x 4, kinv_tab q, kinv_out G, K pointers G)
     double** kptr_dense = nullptr;    // [cap][G]: where the fill puts evaluation b's matrix g
-    void* programs = nullptr;         // [cap][G] fill programs
+    char* programs = nullptr;         // [cap][G] fill programs
     SmallPhaseArgs* phase_args = nullptr;   // [2 parity][2 phase][cap]
     SmallTailArgs* tail_args = nullptr;     // [2 parity][cap]
     SmallPriorArgs* prior_args = nullptr;   // [cap]
     char *pin_in = nullptr, *pin_out = nullptr;
-    size_t pin_in_bytes = 0, pin_out_bytes = 0;
+    double us_reserve = 0.0;          // GPRN_BATCH_TIMERS: what making room took, reported with the next chunk
 };
 #define SB_K 8                         // sweeps per batch of launches (one synchronisation each)
 
@@ -612,18 +617,9 @@ void small_batch_free(gprn_ctx* c)
     c->small_batch = nullptr;
 }
 
-template <typename TT>
-static int sb_alloc(gprn_ctx* c, TT** ptr, size_t count)
-{
-    *ptr = nullptr;
-    if (hipMalloc((void**)ptr, std::max<size_t>(count, 1) * sizeof(TT)) != hipSuccess) { c->err = "hipMalloc (evaluation batch)"; return GPRN_E_NOMEM; }
-    return GPRN_OK;
-}
-#define SB_TRY(x) do { int r_ = (x); if (r_) return r_; } while (0)
-
 // evaluations one chunk may hold: what the memory budget pays for (4 G + q matrices of ld^2 doubles each and small change
 // per evaluation), 16 at least -- an emcee run with thousands of walkers is split, not refused
-int small_batch_chunk(gprn_ctx* c)
+static int small_batch_chunk(gprn_ctx* c)
 {
     const size_t nn = (size_t)c->ld * c->ld, d = (size_t)(c->p + 1) * c->q * c->N;
     const size_t per = ((4 * (size_t)c->G + c->q) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256) * sizeof(double) +
@@ -643,24 +639,24 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     m->G = G; m->q = q; m->p = p; m->N = N; m->ld = ld;
     const size_t nn = (size_t)ld * ld, d = (size_t)(p + 1) * q * N, pn = (size_t)p * N, nscal = 3 * (size_t)G + (size_t)q * q;
     const size_t nmat = 4 * (size_t)G + q, nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
-    SB_TRY(sb_alloc(c, &m->mats, (size_t)cap * nmat * nn));
-    SB_TRY(sb_alloc(c, &m->vecs, (size_t)cap * 7 * G * ld));
-    SB_TRY(sb_alloc(c, &m->state, 4 * (size_t)cap * d));
-    SB_TRY(sb_alloc(c, &m->yv, 2 * (size_t)cap * pn));
-    SB_TRY(sb_alloc(c, &m->scal, (size_t)cap * nscal));
-    SB_TRY(sb_alloc(c, &m->logdetK, (size_t)cap * G));
-    SB_TRY(sb_alloc(c, &m->out4, (size_t)cap * 4));
-    SB_TRY(sb_alloc(c, &m->hist, (size_t)cap * (SB_K + 4)));
-    SB_TRY(sb_alloc(c, &m->ctl, (size_t)cap * 4));
-    SB_TRY(sb_alloc(c, &m->info, (size_t)cap * 3 * G));
-    SB_TRY(sb_alloc(c, &m->gp_ids, (size_t)G));
-    SB_TRY(sb_alloc(c, &m->ticket, (size_t)cap));
-    SB_TRY(sb_alloc(c, &m->ptrs, (size_t)cap * nptr));
-    SB_TRY(sb_alloc(c, &m->kptr_dense, (size_t)cap * G));
-    if (hipMalloc(&m->programs, (size_t)cap * G * fill_program_bytes()) != hipSuccess) { c->err = "hipMalloc (fill programs)"; return GPRN_E_NOMEM; }
-    SB_TRY(sb_alloc(c, &m->phase_args, 4 * (size_t)cap));
-    SB_TRY(sb_alloc(c, &m->tail_args, 2 * (size_t)cap));
-    SB_TRY(sb_alloc(c, &m->prior_args, (size_t)cap));
+    TRY(dev_alloc(c, &m->mats, (size_t)cap * nmat * nn));
+    TRY(dev_alloc(c, &m->vecs, (size_t)cap * 7 * G * ld));
+    TRY(dev_alloc(c, &m->state, 4 * (size_t)cap * d));
+    TRY(dev_alloc(c, &m->yv, 2 * (size_t)cap * pn));
+    TRY(dev_alloc(c, &m->scal, (size_t)cap * nscal));
+    TRY(dev_alloc(c, &m->logdetK, (size_t)cap * G));
+    TRY(dev_alloc(c, &m->out4, (size_t)cap * 4));
+    TRY(dev_alloc(c, &m->hist, (size_t)cap * (SB_K + 4)));
+    TRY(dev_alloc(c, &m->ctl, (size_t)cap * 4));
+    TRY(dev_alloc(c, &m->info, (size_t)cap * 3 * G));
+    TRY(dev_alloc(c, &m->gp_ids, (size_t)G));
+    TRY(dev_alloc(c, &m->ticket, (size_t)cap));
+    TRY(dev_alloc(c, &m->ptrs, (size_t)cap * nptr));
+    TRY(dev_alloc(c, &m->kptr_dense, (size_t)cap * G));
+    TRY(dev_alloc(c, &m->programs, (size_t)cap * G * fill_program_bytes()));
+    TRY(dev_alloc(c, &m->phase_args, 4 * (size_t)cap));
+    TRY(dev_alloc(c, &m->tail_args, 2 * (size_t)cap));
+    TRY(dev_alloc(c, &m->prior_args, (size_t)cap));
     HIP_TRY(c, hipMemset(m->ticket, 0, (size_t)cap * sizeof(unsigned)));
     HIP_TRY(c, hipMemset(m->info, 0, (size_t)cap * 3 * G * sizeof(int)));      // (the kernels write the entries they use)
     HIP_TRY(c, hipMemset(m->scal, 0, (size_t)cap * nscal * sizeof(double)));
@@ -733,71 +729,40 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     HIP_TRY(c, hipMemcpy(m->tail_args, ta.data(), ta.size() * sizeof(SmallTailArgs), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(m->prior_args, pr.data(), pr.size() * sizeof(SmallPriorArgs), hipMemcpyHostToDevice));
     // pinned staging: in = programs | y - mean | variance | mu | var;  out = ctl | hist | info | the four state copies
-    m->pin_in_bytes = (size_t)cap * G * fill_program_bytes() + (2 * (size_t)cap * pn + 2 * (size_t)cap * d) * sizeof(double);
-    m->pin_out_bytes = (size_t)cap * (4 * sizeof(int) + (SB_K + 4) * sizeof(double) + 3 * G * sizeof(int)) + 4 * (size_t)cap * d * sizeof(double) + 64;
-    HIP_TRY(c, hipHostMalloc((void**)&m->pin_in, m->pin_in_bytes, hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc((void**)&m->pin_out, m->pin_out_bytes, hipHostMallocDefault));
+    const size_t pin_out_bytes = (size_t)cap * (4 * sizeof(int) + (SB_K + 4) * sizeof(double) + 3 * G * sizeof(int)) + 4 * (size_t)cap * d * sizeof(double) + 64;
+    HIP_TRY(c, hipHostMalloc((void**)&m->pin_in, batch_stage_bytes(c, cap), hipHostMallocDefault));
+    HIP_TRY(c, hipHostMalloc((void**)&m->pin_out, pin_out_bytes, hipHostMallocDefault));
     m->cap = cap;
     return GPRN_OK;
 }
 
-int small_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_kpar, const double* y_resid, const double* jitters,
-                         const double* mu, const double* var, int max_iter, double* elbo, int* iters, int* conv, int* info,
-                         double* mu_out, double* var_out)
+int small_batch_reserve(gprn_ctx* c, int want, int* cap)
 {
-    if (c->T != 1 || !small_applies(c)) { c->err = "elbocalc_batch: one-tile problems on one rank only"; return GPRN_E_UNSUPPORTED; }
-    const int G = c->G, p = c->p, N = c->N, B = n_eval;
-    int kp_total = 0;
-    for (int g = 0; g < G; ++g) {
-        if (!c->kspec[g].set || c->kspec[g].uploaded) { c->err = "elbocalc_batch: every latent GP needs a device kernel program"; return GPRN_E_UNSUPPORTED; }
-        kp_total += c->kspec[g].n_params;
-    }
-    if (kp_total != n_kpar) { c->err = "elbocalc_batch: kernel_params has the wrong length per evaluation"; return GPRN_E_ARG; }
-    // GPRN_BATCH_TIMERS=1 (probes): where the host's time of a call goes -- staging, enqueue, waits, read-back -- on stderr
-    static int timers_env = -1;
-    if (timers_env < 0) { const char* e = getenv("GPRN_BATCH_TIMERS"); timers_env = e ? atoi(e) : 0; }
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
-    double us_stage = 0.0, us_enqueue = 0.0, us_wait = 0.0, us_host = 0.0;
-    SB_TRY(small_batch_ensure(c, B));
+    LapTimer t;
+    *cap = want = std::min(want, small_batch_chunk(c));
+    const int rc = small_batch_ensure(c, want);
+    if (rc) small_batch_free(c);                               // (what of it was allocated goes back before the caller tries less)
+    else ((SmallBatchMem*)c->small_batch)->us_reserve = t.lap();
+    return rc;
+}
+
+int small_batch_run(gprn_ctx* c, const BatchIo& io)
+{
     SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
-    const int cap = m->cap;
-    const double us_ensure = since(t_begin);
-    auto t_mark = std::chrono::steady_clock::now();
-    const size_t d = (size_t)(p + 1) * c->q * N, pn = (size_t)p * N, pb = fill_program_bytes();
-    // ---- inputs through the pinned buffer
-    char* const pg_h = m->pin_in;
-    double* const yres_h = (double*)(pg_h + (size_t)cap * G * pb);
-    double* const var_h = yres_h + (size_t)cap * pn;
-    double* const mu0_h = var_h + (size_t)cap * pn;
-    double* const v0_h = mu0_h + (size_t)cap * d;
-    for (int b = 0; b < B; ++b) {
-        const double* kp = kparams + (size_t)b * n_kpar;
-        for (int g = 0; g < G; ++g) {
-            if (!fill_program_with(c->kspec[g], kp, pg_h + ((size_t)b * G + g) * pb)) {
-                c->err = "elbocalc_batch: a kernel that is not an even function of t_i - t_j"; return GPRN_E_UNSUPPORTED;
-            }
-            kp += c->kspec[g].n_params;
-        }
-        memcpy(yres_h + (size_t)b * pn, y_resid + (size_t)b * pn, pn * sizeof(double));
-        for (int i = 0; i < p; ++i) {
-            const double j2 = jitters[(size_t)b * p + i] * jitters[(size_t)b * p + i];
-            for (int n = 0; n < N; ++n) var_h[(size_t)b * pn + (size_t)i * N + n] = j2 + c->h_yerr2[(size_t)i * N + n];
-        }
-        memcpy(mu0_h + (size_t)b * d, mu + (size_t)b * d, d * sizeof(double));
-        memcpy(v0_h + (size_t)b * d, var + (size_t)b * d, d * sizeof(double));
-    }
+    const int G = c->G, B = io.n, cap = m->cap, max_iter = io.max_iter;
+    const size_t d = io.state;
+    double* const elbo = io.elbo; int* const iters = io.iters; int* const conv = io.conv; int* const info = io.info;
+    LapTimer t;
+    double us_stage = 0.0, us_enqueue = 0.0, us_wait = 0.0, us_host = 0.0;
+    const double us_ensure = m->us_reserve;
+    m->us_reserve = 0.0;
     hipStream_t st = c->stream;
-    us_stage = since(t_mark); t_mark = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipMemcpyAsync(m->programs, pg_h, (size_t)B * G * pb, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(m->yv, yres_h, (size_t)B * pn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(m->yv + (size_t)cap * pn, var_h, (size_t)B * pn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(m->state, mu0_h, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(m->state + (size_t)cap * d, v0_h, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
+    TRY(batch_stage(c, io, m->pin_in, cap, BatchDst{m->programs, m->yv, m->yv + (size_t)cap * io.yv, m->state, m->state + (size_t)cap * d},
+                    st, t, &us_stage));
     HIP_TRY(c, hipMemsetAsync(m->ctl, 0, (size_t)B * 4 * sizeof(int), st));
     HIP_TRY(c, hipMemsetAsync(m->info, 0, (size_t)B * 3 * G * sizeof(int), st));    // (the kernels only raise them)
     // ---- set-up: every evaluation's G covariance matrices in one launch, their factors in another
-    SB_TRY(launch_fill_batch(c, m->programs, (double* const*)m->kptr_dense, B * G));
+    TRY(launch_fill_batch(c, m->programs, (double* const*)m->kptr_dense, B * G));
     prof_begin(c, GPRN_T_DIAG);
     if (c->acc_opt != 0) hipLaunchKernelGGL((k_small_prior_b<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallPriorArgs*)m->prior_args);
     else hipLaunchKernelGGL((k_small_prior_b<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallPriorArgs*)m->prior_args);
@@ -819,17 +784,17 @@ int small_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_k
     while (!all_done && s <= max_iter) {
         const int s0 = s;
         int nb = 0;
-        const int nb_max = s0 <= 1 ? 4 : SB_K;                 // (no verdict before trip 4, and most warm starts stop there)
+        const int nb_max = s0 <= 1 ? ELBO_LEAD : SB_K;         // (no verdict before trip 4, and most warm starts stop there)
         for (; nb < nb_max && s <= max_iter; ++nb, ++s) {
             const int par = (s <= 1 || (s & 1)) ? 0 : 1;          // sweep 0 and trip 1 start from copy A, then they alternate
             prof_begin(c, GPRN_T_DIAG);
             hipLaunchKernelGGL((k_small_phase_b<false>), dim3(q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 0) * cap));
             prof_end(c);
-            SB_TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 0) * cap, false, B));   // (sequential order only)
+            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 0) * cap, false, B));   // (sequential order only)
             prof_begin(c, GPRN_T_DIAG);
             hipLaunchKernelGGL((k_small_phase_b<true>), dim3(G - q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 1) * cap));
             prof_end(c);
-            SB_TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B));
+            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B));
             prof_begin(c, GPRN_T_VEC);
             hipLaunchKernelGGL(k_small_tail_b<1>, dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
             prof_end(c);
@@ -838,9 +803,9 @@ int small_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_k
         HIP_TRY(c, hipMemcpyAsync(ctl_h, m->ctl, (size_t)B * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipMemcpyAsync(hist_h, m->hist, (size_t)B * (SB_K + 4) * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipMemcpyAsync(info_h, m->info, (size_t)B * 3 * G * sizeof(int), hipMemcpyDeviceToHost, st));
-        us_enqueue += since(t_mark); t_mark = std::chrono::steady_clock::now();
+        us_enqueue += t.lap();
         HIP_TRY(c, hipStreamSynchronize(st));
-        us_wait += since(t_mark); t_mark = std::chrono::steady_clock::now();
+        us_wait += t.lap();
         all_done = true;
         for (int b = 0; b < B; ++b) {
             if (was_done[b]) continue;
@@ -855,22 +820,22 @@ int small_batch_elbocalc(gprn_ctx* c, int n_eval, const double* kparams, int n_k
             if (cb[0]) was_done[b] = 1;
             else all_done = false;
         }
-        us_host += since(t_mark); t_mark = std::chrono::steady_clock::now();
+        us_host += t.lap();
     }
-    if (mu_out && var_out) {
+    if (io.mu_out && io.var_out) {
         for (int k = 0; k < 4; ++k)                            // (B evaluations of each copy, not the buffers' capacity)
             HIP_TRY(c, hipMemcpyAsync(st_h + (size_t)k * cap * d, m->state + (size_t)k * cap * d, (size_t)B * d * sizeof(double),
                                       hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         for (int b = 0; b < B; ++b) {
             const bool in_b = iters[b] >= 1 && (iters[b] & 1);     // odd trips wrote copy B
-            memcpy(mu_out + (size_t)b * d, st_h + ((in_b ? 2 : 0) * (size_t)cap + b) * d, d * sizeof(double));
-            memcpy(var_out + (size_t)b * d, st_h + ((in_b ? 3 : 1) * (size_t)cap + b) * d, d * sizeof(double));
+            memcpy(io.mu_out + (size_t)b * d, st_h + ((in_b ? 2 : 0) * (size_t)cap + b) * d, d * sizeof(double));
+            memcpy(io.var_out + (size_t)b * d, st_h + ((in_b ? 3 : 1) * (size_t)cap + b) * d, d * sizeof(double));
         }
     }
-    if (timers_env)
+    if (batch_timers_on())
         fprintf(stderr, "[gprn] elbocalc_batch (one tile), %d evaluations, us: buffers %.0f | staging %.0f | enqueue %.0f | waiting for the device "
                         "%.0f | verdicts %.0f | states back %.0f | total %.0f (%d launches of sweeps)\n", B, us_ensure, us_stage, us_enqueue,
-                us_wait, us_host, since(t_mark), since(t_begin), s - (max_iter >= 1 ? 1 : 0));
+                us_wait, us_host, t.lap(), us_ensure + t.total(), s - (max_iter >= 1 ? 1 : 0));
     return GPRN_OK;
 }

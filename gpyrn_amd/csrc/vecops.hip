@@ -636,11 +636,6 @@ int vec_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_logdet)
 int vec_reduce_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_logdet)
 {
     if (!ph.nslots) return GPRN_OK;
-    if (!c->d_fin_terms) {
-        HIP_TRY(c, hipMalloc(&c->d_fin_terms, (size_t)c->nslot * 2 * c->ld * sizeof(double)));
-        HIP_TRY(c, hipMalloc(&c->d_fin_tickets, (size_t)c->nslot * sizeof(unsigned)));
-        HIP_TRY(c, hipMemset(c->d_fin_tickets, 0, (size_t)c->nslot * sizeof(unsigned)));
-    }
     prof_begin(c, GPRN_T_VEC);
     const size_t o = (size_t)ph.slot0 * ph.ld, po = (size_t)ph.slot0 * ph.T * 2 * ph.ld;
 #define GO_RF(F, M) hipLaunchKernelGGL((k_reduce_finalize<F, M>), dim3((ph.ld + 255) / 256, ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, \
