@@ -822,13 +822,13 @@ extern "C" int gprn_comm_barrier_max(gprn_ctx* c, double* value)
     if (!c || !value) return GPRN_E_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     if (comm_active(c)) {
+        CallScratch scr(c);
         double* d = nullptr;
-        TRY(dev_alloc(c, &d, 1));
+        TRY(scr.alloc(&d, 1));
         HIP_TRY(c, hipMemcpyAsync(d, value, sizeof(double), hipMemcpyHostToDevice, c->stream));
         TRY(comm_allreduce(c, d, 1, true));
         HIP_TRY(c, hipMemcpyAsync(value, d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
-        hipFree(d);
     } else {
         HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     }
@@ -844,16 +844,14 @@ extern "C" int gprn_comm_allreduce_sum(gprn_ctx* c, double* buf, int n)
     if (!c || !buf || n < 0) return bad(c, "comm_allreduce_sum: bad argument");
     if (!comm_active(c) || n == 0) return GPRN_OK;
     HIP_TRY(c, hipSetDevice(c->device));
+    CallScratch scr(c);
     double* d = nullptr;
-    TRY(dev_alloc(c, &d, (size_t)n));
-    int rc = GPRN_OK;
-    if (hipMemcpyAsync(d, buf, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = GPRN_E_HIP;
-    if (rc == GPRN_OK) rc = comm_allreduce(c, d, (size_t)n, false);
-    if (rc == GPRN_OK && hipMemcpyAsync(buf, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = GPRN_E_HIP;
-    if (rc == GPRN_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = GPRN_E_HIP;
-    hipFree(d);
-    if (rc == GPRN_E_HIP) c->err = "comm_allreduce_sum: copy failed";
-    return rc;
+    TRY(scr.alloc(&d, (size_t)n));
+    HIP_TRY(c, hipMemcpyAsync(d, buf, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    TRY(comm_allreduce(c, d, (size_t)n, false));
+    HIP_TRY(c, hipMemcpyAsync(buf, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GPRN_OK;
 }
 
 // rows of the (p+1, q, N) state owned by other ranks arrive from their owners

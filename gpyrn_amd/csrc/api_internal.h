@@ -35,6 +35,74 @@ static void dev_free(T*& p) { if (p) hipFree(p); p = nullptr; }
 
 static inline int bad(gprn_ctx* c, const char* msg) { if (c) c->err = msg; return GPRN_E_ARG; }
 
+// The device temporaries of ONE call (nothing is kept across calls; what the context owns -- workspaces, prediction
+// buffers, d_test, slot arrays, masks, batch slabs -- stays with the context).  Whatever it hands out lives until it goes out of
+// scope, on every return path: the destructor waits for c->stream, forgets the tables it noted and frees everything.
+// (tab_host, which tab_rows reads, is keyed by a table's device address: a table freed while still noted would hand its old
+// rows to whichever table hipMalloc puts at that address next.)  Declare it AFTER the host buffers that copies queued on
+// c->stream write into: locals go in reverse order, so its wait then comes before they do.
+struct CallScratch {
+    gprn_ctx* const c;
+    std::vector<void*> mem;
+    std::vector<double**> noted;
+    std::vector<std::vector<TileTask>> staged;      // host side of the task lists until the copies behind them are done
+    explicit CallScratch(gprn_ctx* c_) : c(c_) {}
+    CallScratch(const CallScratch&) = delete;
+    CallScratch& operator=(const CallScratch&) = delete;
+    ~CallScratch()
+    {
+        hipStreamSynchronize(c->stream);
+        for (double** t : noted) tab_forget(c, t);
+        for (void* p : mem) hipFree(p);
+    }
+    template <typename T>
+    int alloc(T** p, size_t count)
+    {
+        TRY(dev_alloc(c, p, count));
+        mem.push_back(*p);
+        return GPRN_OK;
+    }
+    // a device pointer table of `rows`, there when the call returns; note: tab_rows may pass its rows as kernel arguments
+    int table(double*** d_tab, const std::vector<double*>& rows, bool note = false)
+    {
+        TRY(alloc(d_tab, rows.size()));
+        return fill(*d_tab, rows, note);
+    }
+    // `rows` into a table it allocated (again, for a table that changes within the call: tab_note replaces the rows it knew)
+    int fill(double** d_tab, const std::vector<double*>& rows, bool note = false)
+    {
+        HIP_TRY(c, hipMemcpy(d_tab, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice));
+        if (note) {
+            tab_note(c, d_tab, rows.data(), rows.size());
+            if (std::find(noted.begin(), noted.end(), d_tab) == noted.end()) noted.push_back(d_tab);
+        }
+        return GPRN_OK;
+    }
+    // a task list, copied behind the work already on c->stream (no host wait)
+    int tasks(TileTask** d_t, const std::vector<TileTask>& t)
+    {
+        TRY(alloc(d_t, t.size()));
+        staged.push_back(t);
+        HIP_TRY(c, hipMemcpyAsync(*d_t, staged.back().data(), t.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
+        return GPRN_OK;
+    }
+};
+
+// the two events of a rate diagnostic
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+    int create(gprn_ctx* c)
+    {
+        HIP_TRY(c, hipEventCreate(&a));
+        HIP_TRY(c, hipEventCreate(&b));
+        return GPRN_OK;
+    }
+};
+
 // Runs `body` (an entry point that factorises); when one of its in-kernel dependency waits gave up
 // (GPRN_E_WAIT_TIMEOUT: a serialising tool, a starved device, ...), the context is latched to the event
 // schedule and the body runs once more -- `body` must restore what it changed before it starts over.

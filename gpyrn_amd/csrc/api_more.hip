@@ -33,6 +33,13 @@ extern "C" int gprn_predict_upload(gprn_ctx* c, int gp, int ns, const double* K_
     return GPRN_OK;
 }
 
+// are the host matrices of latent GP g staged for this ns (gprn_predict_upload; with_kss: gprn_predict_upload_kss as well)?
+static bool pred_staged(const gprn_ctx* c, int g, int ns, bool with_kss)
+{
+    const auto it = c->pred_stage.find(g);
+    return it != c->pred_stage.end() && it->second.ns == ns && (!with_kss || it->second.kss_ns == ns);
+}
+
 __global__ void k_add_to_diagonal(double* __restrict__ A, int ld, const double* __restrict__ v, int N)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -53,11 +60,8 @@ extern "C" int gprn_predict(gprn_ctx* c, int ns, const double* tstar, double* me
         for (int g = 0; g < c->G && !pre; ++g) {
             if (c->owner[g] != c->rank) continue;
             if (!c->kspec[g].set) pre = bad(c, "predict: a latent GP has no kernel");
-            else if (c->kspec[g].uploaded) {
-                auto it = c->pred_stage.find(g);
-                if (it == c->pred_stage.end() || it->second.ns != ns)
-                    pre = bad(c, "predict: a host-evaluated kernel needs gprn_predict_upload (K, K*, k**) for this ns first");
-            }
+            else if (c->kspec[g].uploaded && !pred_staged(c, g, ns, false))
+                pre = bad(c, "predict: a host-evaluated kernel needs gprn_predict_upload (K, K*, k**) for this ns first");
         }
     if ((pre = agree_to_start(c, pre, "predict"))) { c->pred_stage.clear(); return pre; }
     // (everything it factors is refilled from the kernel specs, the staged matrices and the variational state)
@@ -73,14 +77,6 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
     std::vector<int> gps = c->loc_nodes;
     gps.insert(gps.end(), c->loc_weights.begin(), c->loc_weights.end());
     const int nloc = (int)gps.size();
-    for (int g : gps) {
-        if (!c->kspec[g].set) return bad(c, "predict: a latent GP has no kernel");
-        if (c->kspec[g].uploaded) {
-            auto it = c->pred_stage.find(g);
-            if (it == c->pred_stage.end() || it->second.ns != ns)
-                return bad(c, "predict: a host-evaluated kernel needs gprn_predict_upload (K, K*, k**) for this ns first");
-        }
-    }
     const int ld = c->ld, N = c->N, T = c->T;
     const int ns_pad = ((ns + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
     const size_t need = (size_t)ns_pad * ld;
@@ -99,13 +95,13 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
         TRY(dev_alloc(c, &c->tab_pred, (size_t)c->nslot * GPRN_NBUF));
         TRY(dev_alloc(c, &c->d_slotgp_all, c->nslot));
     }
-    double *d_ts = nullptr, *d_kss = nullptr, *d_mean = nullptr, *d_pvar = nullptr, *d_all = nullptr;
-    TileTask* d_t = nullptr;
-    int rc = GPRN_OK, first = 0;
     std::vector<double*> rows((size_t)c->nslot * GPRN_NBUF, nullptr);
     std::vector<int> staterow(nloc);
     std::vector<TileTask> tasks;
     std::vector<double> hm, hv, pad;
+    CallScratch scr(c);                               // (after hm / hv: it drains the copies into them before they go)
+    double *d_ts = nullptr, *d_kss = nullptr, *d_mean = nullptr, *d_pvar = nullptr, *d_all = nullptr;
+    TileTask* d_t = nullptr;
     const bool gather = comm_active(c);
     const Phase pred = problem_phase(c, c->tab_pred, c->d_slotgp_all, nloc, 0, c->d_info);
     auto row_of = [&](int g) {
@@ -113,14 +109,12 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
         const int kk = g - c->q, j = kk / c->p, i = kk % c->p;
         return (1 + i) * c->q + j;
     };
-#define PTRY(expr) do { rc = (expr); if (rc) goto done; } while (0)
-#define PHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e_); rc = GPRN_E_HIP; goto done; } } while (0)
     if (nloc) {
-        PTRY(dev_alloc(c, &d_ts, ns));
-        PTRY(dev_alloc(c, &d_kss, (size_t)nloc * ns_pad));
-        PTRY(dev_alloc(c, &d_mean, (size_t)nloc * ns_pad));
-        PTRY(dev_alloc(c, &d_pvar, (size_t)nloc * ns_pad));
-        PHIP(hipMemcpy(d_ts, tstar, ns * sizeof(double), hipMemcpyHostToDevice));
+        TRY(scr.alloc(&d_ts, ns));
+        TRY(scr.alloc(&d_kss, (size_t)nloc * ns_pad));
+        TRY(scr.alloc(&d_mean, (size_t)nloc * ns_pad));
+        TRY(scr.alloc(&d_pvar, (size_t)nloc * ns_pad));
+        HIP_TRY(c, hipMemcpy(d_ts, tstar, ns * sizeof(double), hipMemcpyHostToDevice));
         for (int s = 0; s < nloc; ++s) {
             rows[(size_t)s * GPRN_NBUF + BUF_B] = c->wsB[s];
             rows[(size_t)s * GPRN_NBUF + BUF_X] = c->wsX[s];
@@ -128,13 +122,13 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
             rows[(size_t)s * GPRN_NBUF + BUF_KLINV] = c->predWT[s];
             staterow[s] = row_of(gps[s]);
         }
-        PTRY(upload_table(c, c->tab_pred, rows));
-        PHIP(hipMemcpy(c->d_slotgp_all, staterow.data(), nloc * sizeof(int), hipMemcpyHostToDevice));
+        TRY(upload_table(c, c->tab_pred, rows));
+        HIP_TRY(c, hipMemcpy(c->d_slotgp_all, staterow.data(), nloc * sizeof(int), hipMemcpyHostToDevice));
         for (int s = 0; s < nloc; ++s) {
             const KernelSpec& ks = c->kspec[gps[s]];
             if (!ks.uploaded) {
-                PTRY(launch_fill(c, ks, c->wsB[s], 1.25e-12, c->d_var + (size_t)staterow[s] * N));
-                PTRY(launch_fill_rect(c, ks, 1.25e-12, d_ts, ns, ns_pad, c->predKs[s], d_kss + (size_t)s * ns_pad));
+                TRY(launch_fill(c, ks, c->wsB[s], 1.25e-12, c->d_var + (size_t)staterow[s] * N));
+                TRY(launch_fill_rect(c, ks, 1.25e-12, d_ts, ns, ns_pad, c->predKs[s], d_kss + (size_t)s * ns_pad));
                 continue;
             }
             // the caller's matrices: K (identity padding) + diag(var), K* (zero padding), k**
@@ -144,73 +138,68 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
                 if (m < N) memcpy(&pad[(size_t)m * ld], &st.K[(size_t)m * N], N * sizeof(double));
                 else pad[(size_t)m * ld + m] = 1.0;
             }
-            PHIP(hipMemcpy(c->wsB[s], pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(c->wsB[s], pad.data(), pad.size() * sizeof(double), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(k_add_to_diagonal, dim3((N + 255) / 256), dim3(256), 0, c->stream, c->wsB[s], ld,
                                c->d_var + (size_t)staterow[s] * N, N);
-            PHIP(hipGetLastError());
+            HIP_TRY(c, hipGetLastError());
             pad.assign(need, 0.0);
             for (int m = 0; m < ns; ++m) memcpy(&pad[(size_t)m * ld], &st.Kstar[(size_t)m * N], N * sizeof(double));
-            PHIP(hipMemcpy(c->predKs[s], pad.data(), need * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(c->predKs[s], pad.data(), need * sizeof(double), hipMemcpyHostToDevice));
             pad.assign(ns_pad, 0.0);
             memcpy(pad.data(), st.kss.data(), ns * sizeof(double));
-            PHIP(hipMemcpy(d_kss + (size_t)s * ns_pad, pad.data(), ns_pad * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_kss + (size_t)s * ns_pad, pad.data(), ns_pad * sizeof(double), hipMemcpyHostToDevice));
         }
-        PHIP(hipMemsetAsync(c->d_info, 0, 3 * (size_t)c->nslot * sizeof(int), c->stream));
-        PTRY(factor_invert(c, pred, true));
-        PTRY(vec_lower_matvec(c, pred, BUF_X, c->d_mu, N, 1, c->d_u));   // u = X mu
-        PTRY(vec_colops(c, pred));                                        // ct = X^T u
+        HIP_TRY(c, hipMemsetAsync(c->d_info, 0, 3 * (size_t)c->nslot * sizeof(int), c->stream));
+        TRY(factor_invert(c, pred, true));
+        TRY(vec_lower_matvec(c, pred, BUF_X, c->d_mu, N, 1, c->d_u));   // u = X mu
+        TRY(vec_colops(c, pred));                                        // ct = X^T u
         for (int bt = 0; bt < ns_pad / GPRN_TILE; ++bt)
             for (int at = 0; at < T; ++at)
                 tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE,
                                          (int64_t)bt * GPRN_TILE * ld, (int64_t)at * GPRN_TILE * ld,
                                          (at + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_X,
                                          tile_modes(CM_SET, 0, 0)});
-        PTRY(dev_alloc(c, &d_t, tasks.size()));
-        PHIP(hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
-        PTRY(launch_tiles(c, d_t, tasks.size(), pred.ptrs, nloc, ld, GPRN_T_UPDATE));
-        PTRY(vec_pred_rows(c, pred, ns, ns_pad, c->d_ct, d_kss, d_mean, d_pvar));
-        if (after) PTRY(after(PredState{gps, ns, ns_pad, d_ts, d_mean}));
+        TRY(scr.tasks(&d_t, tasks));
+        TRY(launch_tiles(c, d_t, tasks.size(), pred.ptrs, nloc, ld, GPRN_T_UPDATE));
+        TRY(vec_pred_rows(c, pred, ns, ns_pad, c->d_ct, d_kss, d_mean, d_pvar));
+        if (after) TRY(after(PredState{gps, ns, ns_pad, d_ts, d_mean}));
     }
     if (gather) {
         // every rank ends up with every latent GP's rows: the owners' results travel as one grouped broadcast
         // (2 G messages of ns doubles); ranks that own nothing take part all the same
-        PTRY(dev_alloc(c, &d_all, 2 * (size_t)c->G * ns));
+        TRY(scr.alloc(&d_all, 2 * (size_t)c->G * ns));
         for (int s = 0; s < nloc; ++s) {
-            PHIP(hipMemcpyAsync(d_all + (size_t)gps[s] * ns, d_mean + (size_t)s * ns_pad, ns * sizeof(double),
-                                hipMemcpyDeviceToDevice, c->stream));
-            PHIP(hipMemcpyAsync(d_all + ((size_t)c->G + gps[s]) * ns, d_pvar + (size_t)s * ns_pad, ns * sizeof(double),
-                                hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_all + (size_t)gps[s] * ns, d_mean + (size_t)s * ns_pad, ns * sizeof(double),
+                                      hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_all + ((size_t)c->G + gps[s]) * ns, d_pvar + (size_t)s * ns_pad, ns * sizeof(double),
+                                      hipMemcpyDeviceToDevice, c->stream));
         }
-        if ((rc = comm_group(c, true))) goto done;
+        TRY(comm_group(c, true));
+        int rc = GPRN_OK;
         for (int g = 0; g < c->G && !rc; ++g) {
             rc = comm_broadcast(c, d_all + (size_t)g * ns, ns, c->owner[g]);
             if (!rc) rc = comm_broadcast(c, d_all + ((size_t)c->G + g) * ns, ns, c->owner[g]);
         }
         { const int rg = comm_group(c, false); if (!rc) rc = rg; }
-        if (rc) goto done;
-        PHIP(hipMemcpyAsync(mean_out, d_all, (size_t)c->G * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PHIP(hipMemcpyAsync(var_out, d_all + (size_t)c->G * ns, (size_t)c->G * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
+        TRY(rc);
+        HIP_TRY(c, hipMemcpyAsync(mean_out, d_all, (size_t)c->G * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(var_out, d_all + (size_t)c->G * ns, (size_t)c->G * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     } else if (nloc) {
         hm.resize((size_t)nloc * ns_pad); hv.resize((size_t)nloc * ns_pad);
-        PHIP(hipMemcpyAsync(hm.data(), d_mean, hm.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PHIP(hipMemcpyAsync(hv.data(), d_pvar, hv.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
+        HIP_TRY(c, hipMemcpyAsync(hm.data(), d_mean, hm.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(hv.data(), d_pvar, hv.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
         for (int s = 0; s < nloc; ++s) {
             memcpy(mean_out + (size_t)gps[s] * ns, &hm[(size_t)s * ns_pad], ns * sizeof(double));
             memcpy(var_out + (size_t)gps[s] * ns, &hv[(size_t)s * ns_pad], ns * sizeof(double));
         }
     }
     c->info_gp = -1;
-    rc = factor_check_waits(c);
-    if (!rc && nloc) rc = check_info(c, c->d_info, gps, &first);
-    if (!rc) rc = first;
-done:
-#undef PTRY
-#undef PHIP
-    hipStreamSynchronize(c->stream);
-    dev_free(d_ts); dev_free(d_kss); dev_free(d_mean); dev_free(d_pvar); dev_free(d_t); dev_free(d_all);
-    return rc;
+    TRY(factor_check_waits(c));
+    int first = 0;
+    if (nloc) TRY(check_info(c, c->d_info, gps, &first));
+    return first;
 }
 
 // ------------------------------------------------------------------ predictive covariances and joint draws
@@ -365,224 +354,234 @@ struct CovRequest {
     int info_gp = -1;
 };
 
-static int device_table(gprn_ctx* c, double*** d_tab, const std::vector<double*>& rows)
-{
-    TRY(dev_alloc(c, d_tab, rows.size()));
-    HIP_TRY(c, hipMemcpy(*d_tab, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice));
-    return GPRN_OK;
-}
+// Geometry and device memory of one call, shared by the parts of cov_after (each runs behind predict_impl's means, PredAfter:
+// every latent GP is local -- one rank -- and slot s = latent GP s): C (G ns_pad^2); draws: the factor's B and X
+// (2 G ns_pad^2), Z and L Z (2 G nd_pad ns_pad)
+struct CovWork {
+    int G, ns, ns_pad, Ts, ld, nd, nd_pad;
+    size_t nn;
+    double *C = nullptr, *F = nullptr, *X = nullptr, *Z = nullptr, *LZ = nullptr, *out = nullptr, *lat = nullptr;
+    double** t_C = nullptr;                           // the matrices of C as a table
+};
 
-// runs behind predict_impl's means (PredAfter): every latent GP is local (one rank), slot s = latent GP s
-static int cov_after(gprn_ctx* c, const PredState& st, CovRequest& rq)
+// C = K** - W W^T, symmetric
+static int cov_conditional(gprn_ctx* c, CallScratch& scr, const PredState& st, CovWork& w)
 {
-    const int G = c->G, ns = st.ns, ns_pad = st.ns_pad, Ts = ns_pad / GPRN_TILE, ld = c->ld;
-    const size_t nn = (size_t)ns_pad * ns_pad;
-    const int nd = rq.n_draws, nd_pad = ((std::max(nd, 1) + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
-    const bool draws = nd > 0;
-    // device memory of the call: C (G ns_pad^2); draws: the factor's B and X (2 G ns_pad^2), Z and L Z (2 G nd_pad ns_pad)
-    double *d_C = nullptr, *d_F = nullptr, *d_X = nullptr, *d_Z = nullptr, *d_LZ = nullptr, *d_out = nullptr, *d_lat = nullptr;
-    double *d_jit2 = nullptr, *d_nu = nullptr;
-    double **t_pred = nullptr, **t_C = nullptr, **t_fac = nullptr, **t_src = nullptr, **t_dst = nullptr, **t_L = nullptr,
-           **t_mm = nullptr, **t_LZ = nullptr;
-    int* d_inf = nullptr;
-    TileTask* d_t = nullptr;
-    int rc = GPRN_OK;
-    std::vector<double*> rows;
-    std::vector<TileTask> tasks;
-    auto fail_mem = [&](int r) {
-        if (r == GPRN_E_NOMEM)
-            c->err = "predict_cov: out of device memory for " + std::to_string(G) + " covariance matrices of " +
-                     std::to_string(ns) + " x " + std::to_string(ns) + (draws ? " and their factors" : "") + " (" + c->err + ")";
-        return r;
-    };
-#define CTRY(expr) do { rc = (expr); if (rc) goto done; } while (0)
-#define CHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e_); rc = GPRN_E_HIP; goto done; } } while (0)
-    CTRY(fail_mem(dev_alloc(c, &d_C, (size_t)G * nn)));
-    if (draws) {
-        CTRY(fail_mem(dev_alloc(c, &d_F, (size_t)G * nn)));
-        CTRY(fail_mem(dev_alloc(c, &d_X, (size_t)G * nn)));
-        CHIP(hipMemsetAsync(d_X, 0, (size_t)G * nn * sizeof(double), c->stream));
-        CTRY(fail_mem(dev_alloc(c, &d_Z, (size_t)G * nd_pad * ns_pad)));
-        CTRY(fail_mem(dev_alloc(c, &d_LZ, (size_t)G * nd_pad * ns_pad)));
-        CTRY(fail_mem(dev_alloc(c, &d_lat, (size_t)G * nd * ns)));
-        if (rq.out_draws) CTRY(fail_mem(dev_alloc(c, &d_out, (size_t)c->p * nd * ns)));
-    } else if (rq.out_cov) {
-        const size_t M = (rq.flags & GPRN_COV_JOINT) ? (size_t)c->p * ns : (size_t)ns;
-        CTRY(fail_mem(dev_alloc(c, &d_out, (rq.flags & GPRN_COV_JOINT) ? M * M : (size_t)c->p * M * M)));
-    }
+    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad, ld = w.ld;
+    const size_t nn = w.nn;
     // ---- K** at t* into C (identity padding); the caller's matrix for a host-evaluated kernel
     for (int g = 0; g < G; ++g) {
-        double* Cg = d_C + (size_t)g * nn;
+        double* Cg = w.C + (size_t)g * nn;
         const KernelSpec& ks = c->kspec[g];
-        if (!ks.uploaded) { CTRY(launch_fill_times(c, ks, Cg, 1.25e-12, nullptr, st.d_ts, ns, ns_pad)); continue; }
+        if (!ks.uploaded) { TRY(launch_fill_times(c, ks, Cg, 1.25e-12, nullptr, st.d_ts, ns, ns_pad)); continue; }
         const gprn_ctx::PredStage& ps = c->pred_stage[g];
         std::vector<double> pad(nn, 0.0);
         for (int m = 0; m < ns_pad; ++m) {
             if (m < ns) memcpy(&pad[(size_t)m * ns_pad], &ps.Kss[(size_t)m * ns], ns * sizeof(double));
             else pad[(size_t)m * ns_pad + m] = 1.0;
         }
-        CHIP(hipMemcpyAsync(Cg, pad.data(), nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        CHIP(hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(Cg, pad.data(), nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     // ---- C -= W W^T: lower tiles (bt, at), K = ld (W^T's columns beyond N are zero), diagonal tiles lower blocks only
-    rows.assign((size_t)G * GPRN_NBUF, nullptr);
+    std::vector<double*> rows((size_t)G * GPRN_NBUF, nullptr);
     for (int g = 0; g < G; ++g) {
-        rows[(size_t)g * GPRN_NBUF + BUF_B] = d_C + (size_t)g * nn;
+        rows[(size_t)g * GPRN_NBUF + BUF_B] = w.C + (size_t)g * nn;
         rows[(size_t)g * GPRN_NBUF + BUF_KLINV] = c->predWT[g];
     }
-    CTRY(device_table(c, &t_pred, rows));
-    for (int bt = 0; bt < Ts; ++bt)
+    double** t_pred = nullptr;
+    TRY(scr.table(&t_pred, rows));
+    std::vector<TileTask> tasks;
+    for (int bt = 0; bt < w.Ts; ++bt)
         for (int at = 0; at <= bt; ++at)
             tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ns_pad + (int64_t)at * GPRN_TILE, (int64_t)bt * GPRN_TILE * ld,
                                      (int64_t)at * GPRN_TILE * ld, ld, BUF_B, BUF_KLINV, BUF_KLINV,
                                      tile_modes(CM_SUB, 0, 0, bt == at)});
-    CTRY(dev_alloc(c, &d_t, tasks.size()));
-    CHIP(hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
-    {
-        TileSide side;
-        side.ldc = ns_pad;
-        CTRY(launch_tiles(c, d_t, tasks.size(), t_pred, G, ld, GPRN_T_UPDATE, c->stream, TS_64x64,
-                          Signal{nullptr, 0, nullptr, 0, nullptr}, Await{nullptr, 0, nullptr}, TG_COV, side));
-    }
+    TileTask* d_t = nullptr;
+    TRY(scr.tasks(&d_t, tasks));
+    TileSide side;
+    side.ldc = ns_pad;
+    TRY(launch_tiles(c, d_t, tasks.size(), t_pred, G, ld, GPRN_T_UPDATE, c->stream, TS_64x64,
+                     Signal{nullptr, 0, nullptr, 0, nullptr}, Await{nullptr, 0, nullptr}, TG_COV, side));
     rows.assign(G, nullptr);
-    for (int g = 0; g < G; ++g) rows[g] = d_C + (size_t)g * nn;
-    CTRY(device_table(c, &t_C, rows));
-    {
-        const int nb = ns_pad / GPRN_COV_BLK;
-        hipLaunchKernelGGL(k_mirror_lower, dim3(nb * (nb + 1) / 2, G), dim3(256), 0, c->stream, t_C, ns_pad);
-        CHIP(hipGetLastError());
-    }
-    if (!draws) {
-        if (rq.latent_cov)
-            for (int g = 0; g < G; ++g)
-                CHIP(hipMemcpy2DAsync(rq.latent_cov + (size_t)g * ns * ns, (size_t)ns * sizeof(double), d_C + (size_t)g * nn,
-                                      (size_t)ns_pad * sizeof(double), (size_t)ns * sizeof(double), ns,
-                                      hipMemcpyDeviceToHost, c->stream));
-        if (rq.out_cov) {
-            const bool joint = rq.flags & GPRN_COV_JOINT;
-            const int M = joint ? c->p * ns : ns, nb = (M + GPRN_COV_BLK - 1) / GPRN_COV_BLK;
-            std::vector<double> j2(c->p);
-            for (int i = 0; i < c->p; ++i) j2[i] = c->h_jit[i] * c->h_jit[i];
-            CTRY(dev_alloc(c, &d_jit2, c->p));
-            CHIP(hipMemcpyAsync(d_jit2, j2.data(), c->p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            prof_begin(c, GPRN_T_VEC);
-            hipLaunchKernelGGL(k_output_cov, dim3(nb * (nb + 1) / 2, joint ? 1 : c->p), dim3(256), 0, c->stream,
-                               (const double* const*)t_C, st.d_mean, (const double*)d_jit2, c->q, c->p, ns, ns_pad, joint ? 1 : 0, d_out);
-            prof_end(c);
-            CHIP(hipGetLastError());
-            CHIP(hipMemcpyAsync(rq.out_cov, d_out, (joint ? (size_t)M * M : (size_t)c->p * M * M) * sizeof(double),
-                                hipMemcpyDeviceToHost, c->stream));
-        }
-        CHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
-        goto done;
-    }
-    {
-        // ---- the ladder: factor C_g + nu_g I for every latent GP still pending in ONE phase of geometry (ns, ns_pad, Ts)
-        // (its task lists replace the context's: every other factorisation rebuilds them for its own T)
-        CHIP(hipStreamSynchronize(c->stream)); CHIP(hipStreamSynchronize(c->stream2));
-        CHIP(hipStreamSynchronize(c->stream3)); if (c->stream4) CHIP(hipStreamSynchronize(c->stream4));
-        std::vector<int> pending(G);
-        std::vector<double> nu(G, 1.25e-12);
-        for (int g = 0; g < G; ++g) pending[g] = g;
-        CTRY(dev_alloc(c, &t_fac, (size_t)G * GPRN_NBUF));
-        CTRY(dev_alloc(c, &t_src, G)); CTRY(dev_alloc(c, &t_dst, G));
-        CTRY(dev_alloc(c, &d_nu, G)); CTRY(dev_alloc(c, &d_inf, G));
-        while (!pending.empty()) {
-            const int np = (int)pending.size();
-            std::vector<double*> fr((size_t)np * GPRN_NBUF, nullptr), src(np), dst(np);
-            std::vector<double> nup(np);
-            for (int b = 0; b < np; ++b) {
-                const int g = pending[b];
-                fr[(size_t)b * GPRN_NBUF + BUF_B] = dst[b] = d_F + (size_t)g * nn;
-                fr[(size_t)b * GPRN_NBUF + BUF_X] = d_X + (size_t)g * nn;
-                src[b] = d_C + (size_t)g * nn;
-                nup[b] = nu[g];
-            }
-            CHIP(hipMemcpy(t_fac, fr.data(), fr.size() * sizeof(double*), hipMemcpyHostToDevice));
-            tab_note(c, t_fac, fr.data(), fr.size());
-            CHIP(hipMemcpy(t_src, src.data(), np * sizeof(double*), hipMemcpyHostToDevice));
-            CHIP(hipMemcpy(t_dst, dst.data(), np * sizeof(double*), hipMemcpyHostToDevice));
-            CHIP(hipMemcpy(d_nu, nup.data(), np * sizeof(double), hipMemcpyHostToDevice));
-            CHIP(hipMemset(d_inf, 0, np * sizeof(int)));
-            hipLaunchKernelGGL(k_shift_copy, dim3(ns_pad, np), dim3(256), 0, c->stream, (const double* const*)t_src, t_dst,
-                               (const double*)d_nu, ns, ns_pad);
-            CHIP(hipGetLastError());
-            const Phase ph{t_fac, nullptr, np, 0, d_inf, EvalMap{nullptr, 0, 0, 0, 0}, ns, ns_pad, Ts};
-            CTRY(factor_invert(c, ph, true));
-            CHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
-            CTRY(factor_check_waits(c));
-            std::vector<int> inf(np);
-            CHIP(hipMemcpy(inf.data(), d_inf, np * sizeof(int), hipMemcpyDeviceToHost));
-            tab_forget(c, t_fac);
-            std::vector<int> again;
-            for (int b = 0; b < np; ++b) {
-                const int g = pending[b];
-                if (inf[b] <= 0) continue;
-                if (nu[g] >= 1.25e-6 * 0.5) {            // the last rung failed
-                    if (!rq.info) { rq.info = inf[b]; rq.info_gp = g; }
-                    continue;
-                }
-                nu[g] *= 100.0;
-                again.push_back(g);
-            }
-            if (rq.info) break;
-            pending.swap(again);
-        }
-        if (rq.nugget_out) memcpy(rq.nugget_out, nu.data(), G * sizeof(double));
-        if (rq.info) goto done;
-    }
-    {
-        // ---- L Z for every draw: out tile (dt, nt) = Z[dt, 0:nt+1] L[nt, 0:nt+1]^T, K = (nt + 1) 128 (L is zero beyond)
-        rows.assign(G, nullptr);
-        for (int g = 0; g < G; ++g) rows[g] = d_F + (size_t)g * nn;
-        CTRY(device_table(c, &t_L, rows));
-        hipLaunchKernelGGL(k_zero_diag_upper, dim3(Ts, G), dim3(256), 0, c->stream, t_L, ns_pad);
-        CHIP(hipGetLastError());
-        CHIP(hipMemsetAsync(d_Z, 0, (size_t)G * nd_pad * ns_pad * sizeof(double), c->stream));
+    for (int g = 0; g < G; ++g) rows[g] = w.C + (size_t)g * nn;
+    TRY(scr.table(&w.t_C, rows));
+    const int nb = ns_pad / GPRN_COV_BLK;
+    hipLaunchKernelGGL(k_mirror_lower, dim3(nb * (nb + 1) / 2, G), dim3(256), 0, c->stream, w.t_C, ns_pad);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
+// the covariances asked for, to the host
+static int cov_outputs(gprn_ctx* c, CallScratch& scr, const PredState& st, const CovWork& w, const CovRequest& rq)
+{
+    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad;
+    if (rq.latent_cov)
         for (int g = 0; g < G; ++g)
-            CHIP(hipMemcpy2DAsync(d_Z + (size_t)g * nd_pad * ns_pad, (size_t)ns_pad * sizeof(double), rq.z + (size_t)g * nd * ns,
-                                  (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), nd, hipMemcpyHostToDevice, c->stream));
-        rows.assign((size_t)G * GPRN_NBUF, nullptr);
-        for (int g = 0; g < G; ++g) {
-            rows[(size_t)g * GPRN_NBUF + BUF_B] = d_F + (size_t)g * nn;
-            rows[(size_t)g * GPRN_NBUF + BUF_K] = d_Z + (size_t)g * nd_pad * ns_pad;
-            rows[(size_t)g * GPRN_NBUF + BUF_KLINV] = d_LZ + (size_t)g * nd_pad * ns_pad;
-        }
-        CTRY(device_table(c, &t_mm, rows));
-        tasks.clear();
-        for (int dt = 0; dt < nd_pad / GPRN_TILE; ++dt)
-            for (int nt = 0; nt < Ts; ++nt)
-                tasks.push_back(TileTask{(int64_t)dt * GPRN_TILE * ns_pad + (int64_t)nt * GPRN_TILE, (int64_t)dt * GPRN_TILE * ns_pad,
-                                         (int64_t)nt * GPRN_TILE * ns_pad, (nt + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_B,
-                                         tile_modes(CM_SET, 0, 0)});
-        dev_free(d_t);
-        CTRY(dev_alloc(c, &d_t, tasks.size()));
-        CHIP(hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream));
-        CTRY(launch_tiles(c, d_t, tasks.size(), t_mm, G, ns_pad, GPRN_T_UPDATE, c->stream,
-                          tasks.size() * (size_t)G > GPRN_FEW_TASKS ? TS_128x128 : TS_64x64));
-        rows.assign(G, nullptr);
-        for (int g = 0; g < G; ++g) rows[g] = d_LZ + (size_t)g * nd_pad * ns_pad;
-        CTRY(device_table(c, &t_LZ, rows));
+            HIP_TRY(c, hipMemcpy2DAsync(rq.latent_cov + (size_t)g * ns * ns, (size_t)ns * sizeof(double), w.C + (size_t)g * w.nn,
+                                        (size_t)ns_pad * sizeof(double), (size_t)ns * sizeof(double), ns,
+                                        hipMemcpyDeviceToHost, c->stream));
+    if (rq.out_cov) {
+        const bool joint = rq.flags & GPRN_COV_JOINT;
+        const int M = joint ? c->p * ns : ns, nb = (M + GPRN_COV_BLK - 1) / GPRN_COV_BLK;
+        std::vector<double> j2(c->p);
+        for (int i = 0; i < c->p; ++i) j2[i] = c->h_jit[i] * c->h_jit[i];
+        double* d_jit2 = nullptr;
+        TRY(scr.alloc(&d_jit2, c->p));
+        HIP_TRY(c, hipMemcpyAsync(d_jit2, j2.data(), c->p * sizeof(double), hipMemcpyHostToDevice, c->stream));
         prof_begin(c, GPRN_T_VEC);
-        hipLaunchKernelGGL(k_draw_combine, dim3((ns + 255) / 256, nd), dim3(256), 0, c->stream, (const double* const*)t_LZ,
-                           st.d_mean, c->q, c->p, ns, ns_pad, nd, d_lat, d_out);
+        hipLaunchKernelGGL(k_output_cov, dim3(nb * (nb + 1) / 2, joint ? 1 : c->p), dim3(256), 0, c->stream,
+                           (const double* const*)w.t_C, st.d_mean, (const double*)d_jit2, c->q, c->p, ns, ns_pad, joint ? 1 : 0, w.out);
         prof_end(c);
-        CHIP(hipGetLastError());
-        CHIP(hipMemcpyAsync(rq.latent_draws, d_lat, (size_t)G * nd * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (rq.out_draws)
-            CHIP(hipMemcpyAsync(rq.out_draws, d_out, (size_t)c->p * nd * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        CHIP(hipStreamSynchronize(c->stream)); watch_progress(c);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(rq.out_cov, w.out, (joint ? (size_t)M * M : (size_t)c->p * M * M) * sizeof(double),
+                                  hipMemcpyDeviceToHost, c->stream));
     }
-done:
-#undef CTRY
-#undef CHIP
-    hipStreamSynchronize(c->stream);
-    if (t_fac) tab_forget(c, t_fac);
-    dev_free(d_C); dev_free(d_F); dev_free(d_X); dev_free(d_Z); dev_free(d_LZ); dev_free(d_out); dev_free(d_lat);
-    dev_free(d_jit2); dev_free(d_nu); dev_free(d_inf); dev_free(d_t);
-    dev_free(t_pred); dev_free(t_C); dev_free(t_fac); dev_free(t_src); dev_free(t_dst); dev_free(t_L); dev_free(t_mm);
-    dev_free(t_LZ);
-    return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
+    return GPRN_OK;
+}
+
+// ---- the ladder: factor C_g + nu_g I for every latent GP still pending in ONE phase of geometry (ns, ns_pad, Ts)
+// (its task lists replace the context's: every other factorisation rebuilds them for its own T).  L_g is left in F;
+// rq.info > 0: the last rung failed for rq.info_gp
+static int cov_ladder(gprn_ctx* c, CallScratch& scr, const CovWork& w, CovRequest& rq)
+{
+    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad;
+    const size_t nn = w.nn;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream2));
+    HIP_TRY(c, hipStreamSynchronize(c->stream3)); if (c->stream4) HIP_TRY(c, hipStreamSynchronize(c->stream4));
+    std::vector<int> pending(G);
+    std::vector<double> nu(G, 1.25e-12);
+    for (int g = 0; g < G; ++g) pending[g] = g;
+    double **t_fac = nullptr, **t_src = nullptr, **t_dst = nullptr, *d_nu = nullptr;
+    int* d_inf = nullptr;
+    TRY(scr.alloc(&t_fac, (size_t)G * GPRN_NBUF));
+    TRY(scr.alloc(&t_src, G)); TRY(scr.alloc(&t_dst, G));
+    TRY(scr.alloc(&d_nu, G)); TRY(scr.alloc(&d_inf, G));
+    while (!pending.empty() && !rq.info) {
+        const int np = (int)pending.size();
+        std::vector<double*> fr((size_t)np * GPRN_NBUF, nullptr), src(np), dst(np);
+        std::vector<double> nup(np);
+        for (int b = 0; b < np; ++b) {
+            const int g = pending[b];
+            fr[(size_t)b * GPRN_NBUF + BUF_B] = dst[b] = w.F + (size_t)g * nn;
+            fr[(size_t)b * GPRN_NBUF + BUF_X] = w.X + (size_t)g * nn;
+            src[b] = w.C + (size_t)g * nn;
+            nup[b] = nu[g];
+        }
+        TRY(scr.fill(t_fac, fr, true));               // (noted afresh with this rung's rows)
+        TRY(scr.fill(t_src, src));
+        TRY(scr.fill(t_dst, dst));
+        HIP_TRY(c, hipMemcpy(d_nu, nup.data(), np * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemset(d_inf, 0, np * sizeof(int)));
+        hipLaunchKernelGGL(k_shift_copy, dim3(ns_pad, np), dim3(256), 0, c->stream, (const double* const*)t_src, t_dst,
+                           (const double*)d_nu, ns, ns_pad);
+        HIP_TRY(c, hipGetLastError());
+        const Phase ph{t_fac, nullptr, np, 0, d_inf, EvalMap{nullptr, 0, 0, 0, 0}, ns, ns_pad, w.Ts};
+        TRY(factor_invert(c, ph, true));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
+        TRY(factor_check_waits(c));
+        std::vector<int> inf(np);
+        HIP_TRY(c, hipMemcpy(inf.data(), d_inf, np * sizeof(int), hipMemcpyDeviceToHost));
+        std::vector<int> again;
+        for (int b = 0; b < np; ++b) {
+            const int g = pending[b];
+            if (inf[b] <= 0) continue;
+            if (nu[g] >= 1.25e-6 * 0.5) {            // the last rung failed
+                if (!rq.info) { rq.info = inf[b]; rq.info_gp = g; }
+                continue;
+            }
+            nu[g] *= 100.0;
+            again.push_back(g);
+        }
+        pending.swap(again);
+    }
+    if (rq.nugget_out) memcpy(rq.nugget_out, nu.data(), G * sizeof(double));
+    return GPRN_OK;
+}
+
+// ---- L Z for every draw: out tile (dt, nt) = Z[dt, 0:nt+1] L[nt, 0:nt+1]^T, K = (nt + 1) 128 (L is zero beyond); then the
+// draws of the latent GPs and of the outputs, to the host
+static int cov_draw(gprn_ctx* c, CallScratch& scr, const PredState& st, const CovWork& w, const CovRequest& rq)
+{
+    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad, nd = w.nd, nd_pad = w.nd_pad;
+    const size_t nn = w.nn;
+    std::vector<double*> rows(G, nullptr);
+    for (int g = 0; g < G; ++g) rows[g] = w.F + (size_t)g * nn;
+    double **t_L = nullptr, **t_mm = nullptr, **t_LZ = nullptr;
+    TRY(scr.table(&t_L, rows));
+    hipLaunchKernelGGL(k_zero_diag_upper, dim3(w.Ts, G), dim3(256), 0, c->stream, t_L, ns_pad);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemsetAsync(w.Z, 0, (size_t)G * nd_pad * ns_pad * sizeof(double), c->stream));
+    for (int g = 0; g < G; ++g)
+        HIP_TRY(c, hipMemcpy2DAsync(w.Z + (size_t)g * nd_pad * ns_pad, (size_t)ns_pad * sizeof(double), rq.z + (size_t)g * nd * ns,
+                                    (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), nd, hipMemcpyHostToDevice, c->stream));
+    rows.assign((size_t)G * GPRN_NBUF, nullptr);
+    for (int g = 0; g < G; ++g) {
+        rows[(size_t)g * GPRN_NBUF + BUF_B] = w.F + (size_t)g * nn;
+        rows[(size_t)g * GPRN_NBUF + BUF_K] = w.Z + (size_t)g * nd_pad * ns_pad;
+        rows[(size_t)g * GPRN_NBUF + BUF_KLINV] = w.LZ + (size_t)g * nd_pad * ns_pad;
+    }
+    TRY(scr.table(&t_mm, rows));
+    std::vector<TileTask> tasks;
+    for (int dt = 0; dt < nd_pad / GPRN_TILE; ++dt)
+        for (int nt = 0; nt < w.Ts; ++nt)
+            tasks.push_back(TileTask{(int64_t)dt * GPRN_TILE * ns_pad + (int64_t)nt * GPRN_TILE, (int64_t)dt * GPRN_TILE * ns_pad,
+                                     (int64_t)nt * GPRN_TILE * ns_pad, (nt + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_B,
+                                     tile_modes(CM_SET, 0, 0)});
+    TileTask* d_t = nullptr;
+    TRY(scr.tasks(&d_t, tasks));
+    TRY(launch_tiles(c, d_t, tasks.size(), t_mm, G, ns_pad, GPRN_T_UPDATE, c->stream,
+                     tasks.size() * (size_t)G > GPRN_FEW_TASKS ? TS_128x128 : TS_64x64));
+    rows.assign(G, nullptr);
+    for (int g = 0; g < G; ++g) rows[g] = w.LZ + (size_t)g * nd_pad * ns_pad;
+    TRY(scr.table(&t_LZ, rows));
+    prof_begin(c, GPRN_T_VEC);
+    hipLaunchKernelGGL(k_draw_combine, dim3((ns + 255) / 256, nd), dim3(256), 0, c->stream, (const double* const*)t_LZ,
+                       st.d_mean, c->q, c->p, ns, ns_pad, nd, w.lat, w.out);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(rq.latent_draws, w.lat, (size_t)G * nd * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (rq.out_draws)
+        HIP_TRY(c, hipMemcpyAsync(rq.out_draws, w.out, (size_t)c->p * nd * ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
+    return GPRN_OK;
+}
+
+static int cov_after(gprn_ctx* c, const PredState& st, CovRequest& rq)
+{
+    CovWork w;
+    w.G = c->G; w.ns = st.ns; w.ns_pad = st.ns_pad; w.Ts = st.ns_pad / GPRN_TILE; w.ld = c->ld;
+    w.nn = (size_t)st.ns_pad * st.ns_pad;
+    w.nd = rq.n_draws; w.nd_pad = ((std::max(w.nd, 1) + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+    const int G = w.G, ns = w.ns, nd = w.nd;
+    const bool draws = nd > 0;
+    CallScratch scr(c);
+    auto big = [&](double** p, size_t count) {
+        const int r = scr.alloc(p, count);
+        if (r == GPRN_E_NOMEM)
+            c->err = "predict_cov: out of device memory for " + std::to_string(G) + " covariance matrices of " +
+                     std::to_string(ns) + " x " + std::to_string(ns) + (draws ? " and their factors" : "") + " (" + c->err + ")";
+        return r;
+    };
+    TRY(big(&w.C, (size_t)G * w.nn));
+    if (draws) {
+        TRY(big(&w.F, (size_t)G * w.nn));
+        TRY(big(&w.X, (size_t)G * w.nn));
+        HIP_TRY(c, hipMemsetAsync(w.X, 0, (size_t)G * w.nn * sizeof(double), c->stream));
+        TRY(big(&w.Z, (size_t)G * w.nd_pad * w.ns_pad));
+        TRY(big(&w.LZ, (size_t)G * w.nd_pad * w.ns_pad));
+        TRY(big(&w.lat, (size_t)G * nd * ns));
+        if (rq.out_draws) TRY(big(&w.out, (size_t)c->p * nd * ns));
+    } else if (rq.out_cov) {
+        const size_t M = (rq.flags & GPRN_COV_JOINT) ? (size_t)c->p * ns : (size_t)ns;
+        TRY(big(&w.out, (rq.flags & GPRN_COV_JOINT) ? M * M : (size_t)c->p * M * M));
+    }
+    TRY(cov_conditional(c, scr, st, w));
+    if (!draws) return cov_outputs(c, scr, st, w, rq);
+    TRY(cov_ladder(c, scr, w, rq));
+    if (rq.info) return GPRN_OK;
+    return cov_draw(c, scr, st, w, rq);
 }
 
 // the checks and the call shared by the two entry points
@@ -603,12 +602,9 @@ static int cov_entry(gprn_ctx* c, const char* what, int ns, const double* tstar,
     else
         for (int g = 0; g < c->G && !pre; ++g) {
             if (!c->kspec[g].set) pre = bad(c, "predict_cov: a latent GP has no kernel");
-            else if (c->kspec[g].uploaded) {
-                auto it = c->pred_stage.find(g);
-                if (it == c->pred_stage.end() || it->second.ns != ns || it->second.kss_ns != ns)
-                    pre = bad(c, "predict_cov: a host-evaluated kernel needs gprn_predict_upload (K, K*, k**) and "
-                                 "gprn_predict_upload_kss (K**) for this ns first");
-            }
+            else if (c->kspec[g].uploaded && !pred_staged(c, g, ns, true))
+                pre = bad(c, "predict_cov: a host-evaluated kernel needs gprn_predict_upload (K, K*, k**) and "
+                             "gprn_predict_upload_kss (K**) for this ns first");
         }
     if (pre) { c->pred_stage.clear(); return pre; }
     std::vector<double> var((size_t)c->G * ns);
@@ -710,40 +706,28 @@ static int sample_prior_impl(gprn_ctx* c, const KernelSpec& ks, double nugget, i
 {
     const int ld = c->ld, N = c->N;
     TRY(test_setup(c, ld, 2, 1));
+    CallScratch scr(c);
     double **d_p = nullptr, *d_z = nullptr, *d_o = nullptr;
     int* d_i = nullptr;
-    int rc = dev_alloc(c, &d_p, GPRN_NBUF);
-    if (!rc) rc = dev_alloc(c, &d_i, 1);
-    if (!rc) rc = dev_alloc(c, &d_z, (size_t)n_samples * ld);
-    if (!rc) rc = dev_alloc(c, &d_o, (size_t)n_samples * ld);
+    TRY(scr.table(&d_p, {c->d_test[0], c->d_test[1], nullptr, nullptr}, true));
+    TRY(scr.alloc(&d_i, 1));
+    TRY(scr.alloc(&d_z, (size_t)n_samples * ld));
+    TRY(scr.alloc(&d_o, (size_t)n_samples * ld));
     const Phase one = problem_phase(c, d_p, nullptr, 1, 0, d_i);
+    HIP_TRY(c, hipMemset(d_i, 0, sizeof(int)));
+    HIP_TRY(c, hipMemset(d_z, 0, (size_t)n_samples * ld * sizeof(double)));
+    HIP_TRY(c, hipMemcpy2D(d_z, (size_t)ld * sizeof(double), z, (size_t)N * sizeof(double), (size_t)N * sizeof(double), n_samples,
+                           hipMemcpyHostToDevice));
+    TRY(launch_fill(c, ks, c->d_test[0], nugget));
+    TRY(factor_invert(c, one, true));
+    for (int s = 0; s < n_samples; ++s)                               // L z: row i of lower(B) . z
+        TRY(vec_lower_matvec(c, one, BUF_B, d_z + (size_t)s * ld, 0, 0, d_o + (size_t)s * ld));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    TRY(factor_check_waits(c));
     int info0 = 0;
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        double* hp[GPRN_NBUF] = {c->d_test[0], c->d_test[1], nullptr, nullptr};
-        e = hipMemcpy(d_p, hp, sizeof(hp), hipMemcpyHostToDevice);
-        if (e == hipSuccess) tab_note(c, d_p, hp, GPRN_NBUF);
-        if (e == hipSuccess) e = hipMemset(d_i, 0, sizeof(int));
-        if (e == hipSuccess) e = hipMemset(d_z, 0, (size_t)n_samples * ld * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy2D(d_z, (size_t)ld * sizeof(double), z, (size_t)N * sizeof(double),
-                                             (size_t)N * sizeof(double), n_samples, hipMemcpyHostToDevice);
-        if (e == hipSuccess) rc = launch_fill(c, ks, c->d_test[0], nugget);
-        if (e == hipSuccess && !rc) rc = factor_invert(c, one, true);
-        for (int s = 0; s < n_samples && e == hipSuccess && !rc; ++s)     // L z: row i of lower(B) . z
-            rc = vec_lower_matvec(c, one, BUF_B, d_z + (size_t)s * ld, 0, 0, d_o + (size_t)s * ld);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess && !rc) rc = factor_check_waits(c);
-        if (e == hipSuccess && !rc) e = hipMemcpy(&info0, d_i, sizeof(int), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && !rc)
-            e = hipMemcpy2D(out, (size_t)N * sizeof(double), d_o, (size_t)ld * sizeof(double),
-                            (size_t)N * sizeof(double), n_samples, hipMemcpyDeviceToHost);
-    }
-    if (d_p) { tab_forget(c, d_p); hipFree(d_p); }
-    if (d_i) hipFree(d_i);
-    if (d_z) hipFree(d_z);
-    if (d_o) hipFree(d_o);
-    if (rc) return rc;
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpy(&info0, d_i, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy2D(out, (size_t)N * sizeof(double), d_o, (size_t)ld * sizeof(double), (size_t)N * sizeof(double), n_samples,
+                           hipMemcpyDeviceToHost));
     return info0;
 }
 
@@ -793,19 +777,18 @@ static int grad_impl(gprn_ctx* c, int gp, double* Kinv_out, double* P_out, const
     HIP_TRY(c, hipMemsetAsync(dS, 0, nn * sizeof(double), c->stream));
     for (int k = 0; k < nsum; ++k)
         TRY(vec_axpy_matrix(c, c->Sig[gp < c->q ? k : gp], dS, N));
+    double gh[GPRN_MAX_KPARAMS] = {0};
+    CallScratch scr(c);
     TileTask* d_t = nullptr;
     double** d_p = nullptr;
     std::vector<TileTask> tasks;
     auto toff = [&](int ti, int tj) { return ((int64_t)ti * GPRN_TILE) * ld + (int64_t)tj * GPRN_TILE; };
     // buffer slots of these launches: 0 = K^-1 (BUF_B), 1 = L_K^-1 (BUF_X, for the X^T X list), 2 = S then P, 3 = C1
-    double* hp[GPRN_NBUF] = {dKinv, c->KLinv[gp], dS, dC1};
-    int rc = dev_alloc(c, &d_p, GPRN_NBUF);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpy(d_p, hp, sizeof(hp), hipMemcpyHostToDevice);
+    TRY(scr.table(&d_p, {dKinv, c->KLinv[gp], dS, dC1}));
     // (1) K^-1 = lower(X^T X), X = L_K^-1: the X^T X task list (BUF_X -> BUF_B); then mirror it to the upper
     // triangle so that the two products below read plain full tiles
-    if (!rc && e == hipSuccess) rc = lauum_lower(c, problem_phase(c, d_p, nullptr, 1, 0, nullptr));
-    if (!rc && e == hipSuccess) rc = vec_symmetrize(c, dKinv);
+    TRY(lauum_lower(c, problem_phase(c, d_p, nullptr, 1, 0, nullptr)));
+    TRY(vec_symmetrize(c, dKinv));
     // (2) C1 = -K^-1 S, all T x T tiles, K = ld
     for (int i = 0; i < T; ++i)
         for (int j = 0; j < T; ++j)
@@ -815,43 +798,31 @@ static int grad_impl(gprn_ctx* c, int gp, double* Kinv_out, double* P_out, const
     for (int i = 0; i < T; ++i)
         for (int j = 0; j < T; ++j)
             tasks.push_back(TileTask{toff(i, j), toff(i, 0), toff(0, j), ld, 2, 3, 0, tile_modes(CM_SETNEG, 0, 1)});
-    if (!rc && e == hipSuccess) rc = dev_alloc(c, &d_t, tasks.size());
-    if (!rc && e == hipSuccess)
-        e = hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream);
-    if (!rc && e == hipSuccess) rc = launch_tiles(c, d_t, n1, d_p, 1, ld, GPRN_T_UPDATE);
-    if (!rc && e == hipSuccess) rc = launch_tiles(c, d_t + n1, tasks.size() - n1, d_p, 1, ld, GPRN_T_UPDATE);
+    TRY(scr.tasks(&d_t, tasks));
+    TRY(launch_tiles(c, d_t, n1, d_p, 1, ld, GPRN_T_UPDATE));
+    TRY(launch_tiles(c, d_t + n1, tasks.size() - n1, d_p, 1, ld, GPRN_T_UPDATE));
     if (kernel_grad) {
         // slot 1's X workspace is free: [0, ld) the mean vector, [ld, 2 ld) a = K^-1 m, then the per-row partial sums
         const KernelSpec& ks = c->kspec[gp];
         double* const w = c->wsX[1];
-        double gh[GPRN_MAX_KPARAMS] = {0};
         const int np_out = closed_form ? 4 : ks.n_params;
-        if (!rc && e == hipSuccess) e = hipMemcpyAsync(w, m, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (!rc && e == hipSuccess) {
-            if (closed_form)
-                rc = vec_grad_contract(c, ks.ops[1], ks.params, dKinv, dS, w, w + ld, w + 2 * (size_t)ld, w + 6 * (size_t)ld);
-            else {
-                rc = vec_symv(c, dKinv, w, w + ld);
-                if (!rc) rc = launch_grad_fd(c, ks, dKinv, dS, w + ld, w + 2 * (size_t)ld, w + 6 * (size_t)ld);
-            }
+        HIP_TRY(c, hipMemcpyAsync(w, m, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (closed_form)
+            TRY(vec_grad_contract(c, ks.ops[1], ks.params, dKinv, dS, w, w + ld, w + 2 * (size_t)ld, w + 6 * (size_t)ld));
+        else {
+            TRY(vec_symv(c, dKinv, w, w + ld));
+            TRY(launch_grad_fd(c, ks, dKinv, dS, w + ld, w + 2 * (size_t)ld, w + 6 * (size_t)ld));
         }
-        if (!rc && e == hipSuccess)
-            e = hipMemcpyAsync(gh, w + 6 * (size_t)ld, (size_t)np_out * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        HIP_TRY(c, hipMemcpyAsync(gh, w + 6 * (size_t)ld, (size_t)np_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (int l = 0; l < ks.n_params && l < np_out; ++l) kernel_grad[l] = gh[l];
     } else {
-        if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (!rc && e == hipSuccess)
-            e = hipMemcpy2D(Kinv_out, (size_t)N * sizeof(double), dKinv, (size_t)ld * sizeof(double),
-                            (size_t)N * sizeof(double), N, hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess)
-            e = hipMemcpy2D(P_out, (size_t)N * sizeof(double), dS, (size_t)ld * sizeof(double),
-                            (size_t)N * sizeof(double), N, hipMemcpyDeviceToHost);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy2D(Kinv_out, (size_t)N * sizeof(double), dKinv, (size_t)ld * sizeof(double),
+                               (size_t)N * sizeof(double), N, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy2D(P_out, (size_t)N * sizeof(double), dS, (size_t)ld * sizeof(double),
+                               (size_t)N * sizeof(double), N, hipMemcpyDeviceToHost));
     }
-    if (d_t) hipFree(d_t);
-    if (d_p) { tab_forget(c, d_p); hipFree(d_p); }
-    if (rc) return rc;
-    HIP_TRY(c, e);
     return GPRN_OK;
 }
 
@@ -957,44 +928,32 @@ extern "C" int gprn_prior_terms(gprn_ctx* c, int gp, const double* S, const doub
         for (int tj = 0; tj < T; ++tj)
             tasks.push_back(TileTask{toff(ti, tj), toff(ti, 0), toff(0, tj), (ti + 1) * GPRN_TILE, BUF_X, BUF_KLINV, BUF_B,
                                      tile_modes(CM_SET, 0, 1)});
+    double h[3] = {0.0, 0.0, 0.0};
+    std::vector<double> rows(N);
+    CallScratch scr(c);
     TileTask* d_t = nullptr;
     double* d_m = nullptr;
-    int rc = dev_alloc(c, &d_t, tasks.size());
-    if (!rc) rc = dev_alloc(c, &d_m, 3 * (size_t)ld + 4);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, c->stream);
-    if (!rc && e == hipSuccess) rc = launch_tiles(c, d_t, tasks.size(), tab, 1, ld, GPRN_T_UPDATE);
-    if (!rc && e == hipSuccess) {
-        hipLaunchKernelGGL(k_rowdot_lower, dim3((N + 3) / 4), dim3(256), 0, c->stream, (const double*)c->KLinv[gp], (const double*)dW,
-                           N, ld, d_m + ld);
-        e = hipGetLastError();
-    }
+    int* d_zero = nullptr;
+    TRY(scr.tasks(&d_t, tasks));
+    TRY(scr.alloc(&d_m, 3 * (size_t)ld + 4));
+    TRY(launch_tiles(c, d_t, tasks.size(), tab, 1, ld, GPRN_T_UPDATE));
+    hipLaunchKernelGGL(k_rowdot_lower, dim3((N + 3) / 4), dim3(256), 0, c->stream, (const double*)c->KLinv[gp], (const double*)dW,
+                       N, ld, d_m + ld);
+    HIP_TRY(c, hipGetLastError());
     // tr(K^-1 S): the rows' sums in a fixed order; m^T K^-1 m: a = L^-1 m (one wave per row), then a . a
-    double h[3] = {0.0, 0.0, 0.0};
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(d_m, m, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (!rc && e == hipSuccess) {
-        static const int zero = 0;
-        int* d_zero = nullptr;
-        rc = dev_alloc(c, &d_zero, 1);
-        if (!rc) e = hipMemcpyAsync(d_zero, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream);
-        // (one slot, "latent GP 0": the scalar lands at d_m[3 ld])
-        const Phase one = problem_phase(c, tab, d_zero, 1, 0, nullptr);
-        if (!rc && e == hipSuccess) rc = vec_lower_matvec(c, one, BUF_KLINV, d_m, 0, 0, d_m + 2 * (size_t)ld);
-        if (!rc && e == hipSuccess) rc = vec_dot_self(c, one, d_m + 2 * (size_t)ld, d_m + 3 * (size_t)ld);
-        if (!rc && e == hipSuccess) {
-            std::vector<double> rows(N);
-            e = hipMemcpyAsync(rows.data(), d_m + ld, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&h[1], d_m + 3 * (size_t)ld, sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&h[0], c->d_logdetK + gp, sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            for (int i = 0; i < N; ++i) h[2] += rows[i];
-        }
-        if (d_zero) hipFree(d_zero);
-    }
-    if (d_t) hipFree(d_t);
-    if (d_m) hipFree(d_m);
-    if (rc) return rc;
-    if (e != hipSuccess) { c->err = std::string("prior_terms: ") + hipGetErrorString(e); return GPRN_E_HIP; }
+    HIP_TRY(c, hipMemcpyAsync(d_m, m, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    static const int zero = 0;
+    TRY(scr.alloc(&d_zero, 1));
+    HIP_TRY(c, hipMemcpyAsync(d_zero, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // (one slot, "latent GP 0": the scalar lands at d_m[3 ld])
+    const Phase one = problem_phase(c, tab, d_zero, 1, 0, nullptr);
+    TRY(vec_lower_matvec(c, one, BUF_KLINV, d_m, 0, 0, d_m + 2 * (size_t)ld));
+    TRY(vec_dot_self(c, one, d_m + 2 * (size_t)ld, d_m + 3 * (size_t)ld));
+    HIP_TRY(c, hipMemcpyAsync(rows.data(), d_m + ld, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&h[1], d_m + 3 * (size_t)ld, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&h[0], c->d_logdetK + gp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < N; ++i) h[2] += rows[i];
     out3[0] = h[0]; out3[1] = h[1]; out3[2] = h[2];
     return GPRN_OK;
 }
@@ -1053,20 +1012,15 @@ extern "C" int gprn_test_gemm(gprn_ctx* c, int M, int N, int K, int a_mode, int 
             t.modes = tile_modes(c_mode & 3, a_mode, b_mode);
             tasks.push_back(t);
         }
+    CallScratch scr(c);
     TileTask* d_t = nullptr;
     double** d_p = nullptr;
-    TRY(dev_alloc(c, &d_t, tasks.size()));
-    TRY(dev_alloc(c, &d_p, GPRN_NBUF));
-    double* hp[GPRN_NBUF] = {c->d_test[0], c->d_test[1], c->d_test[2], nullptr};
+    TRY(scr.alloc(&d_t, tasks.size()));
     HIP_TRY(c, hipMemcpy(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_p, hp, sizeof(hp), hipMemcpyHostToDevice));
-    int rc = launch_tiles(c, d_t, tasks.size(), d_p, 1, ld, GPRN_T_UPDATE, nullptr, (c_mode >> 4) & 3);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (!rc && e == hipSuccess)
-        e = hipMemcpy(hc.data(), c->d_test[2], nn * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(d_t); tab_forget(c, d_p); hipFree(d_p);
-    if (rc) return rc;
-    HIP_TRY(c, e);
+    TRY(scr.table(&d_p, {c->d_test[0], c->d_test[1], c->d_test[2], nullptr}));
+    TRY(launch_tiles(c, d_t, tasks.size(), d_p, 1, ld, GPRN_T_UPDATE, nullptr, (c_mode >> 4) & 3));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(hc.data(), c->d_test[2], nn * sizeof(double), hipMemcpyDeviceToHost));
     for (int m = 0; m < M; ++m)
         for (int n = 0; n < N; ++n) C[(size_t)m * N + n] = hc[(size_t)m * ld + n];
     return GPRN_OK;
@@ -1093,34 +1047,26 @@ extern "C" int gprn_test_gemm_rate(gprn_ctx* c, int M, int N, int K, int how, in
         for (int tj = 0; tj < N / GPRN_TILE; ++tj)
             tasks.push_back(TileTask{(int64_t)ti * GPRN_TILE * ld + (int64_t)tj * GPRN_TILE, (int64_t)ti * GPRN_TILE * ld,
                                      (int64_t)tj * GPRN_TILE * ld, K, 2, 0, 1, tile_modes(CM_SUB, 0, 0)});
+    CallScratch scr(c);
+    EventPair ev;
     TileTask* d_t = nullptr;
     double** d_p = nullptr;
-    TRY(dev_alloc(c, &d_t, tasks.size()));
-    TRY(dev_alloc(c, &d_p, GPRN_NBUF));
-    double* hp[GPRN_NBUF] = {c->d_test[0], c->d_test[1], c->d_test[2], nullptr};
+    TRY(scr.alloc(&d_t, tasks.size()));
     HIP_TRY(c, hipMemcpy(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_p, hp, sizeof(hp), hipMemcpyHostToDevice));
+    TRY(scr.table(&d_p, {c->d_test[0], c->d_test[1], c->d_test[2], nullptr}));
+    TRY(ev.create(c));
     int rc = GPRN_OK;
-    float t = 0.f;
-    {
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0); hipEventCreate(&e1);
-        float total = 0.f;
-        for (int r = 0; r < reps + 1 && !rc; ++r) {
-            hipEventRecord(e0, c->stream);
-            rc = launch_tiles(c, d_t, tasks.size(), d_p, 1, ld, GPRN_T_UPDATE, nullptr, how == 0 ? TS_64x64 : TS_128x128);
-            hipEventRecord(e1, c->stream);
-            hipEventSynchronize(e1);
-            float tt = 0.f;
-            hipEventElapsedTime(&tt, e0, e1);
-            if (r) total += tt;
-        }
-        t = total / reps;
-        hipEventDestroy(e0); hipEventDestroy(e1);
+    float total = 0.f;
+    for (int r = 0; r < reps + 1 && !rc; ++r) {
+        hipEventRecord(ev.a, c->stream);
+        rc = launch_tiles(c, d_t, tasks.size(), d_p, 1, ld, GPRN_T_UPDATE, nullptr, how == 0 ? TS_64x64 : TS_128x128);
+        hipEventRecord(ev.b, c->stream);
+        hipEventSynchronize(ev.b);
+        float tt = 0.f;
+        hipEventElapsedTime(&tt, ev.a, ev.b);
+        if (r) total += tt;
     }
-    hipStreamSynchronize(c->stream);
-    hipFree(d_t); tab_forget(c, d_p); hipFree(d_p);
-    *ms = t;
+    *ms = total / reps;
     return rc;
 }
 
@@ -1138,19 +1084,17 @@ extern "C" int gprn_test_fill_rate(gprn_ctx* c, int reps, double* ms)
     gps.insert(gps.end(), c->loc_weights.begin(), c->loc_weights.end());
     for (int g : gps)
         if (!c->kspec[g].set || c->kspec[g].uploaded) return bad(c, "test_fill_rate: every local latent GP needs a device kernel");
-    hipEvent_t e0, e1;
-    HIP_TRY(c, hipEventCreate(&e0));
-    HIP_TRY(c, hipEventCreate(&e1));
+    EventPair ev;
+    TRY(ev.create(c));
     int rc = GPRN_OK;
     for (int g : gps) if (!rc) rc = launch_fill(c, c->kspec[g], c->K[g]);          // warm
-    hipEventRecord(e0, c->stream);
+    hipEventRecord(ev.a, c->stream);
     for (int r = 0; r < reps && !rc; ++r)
         for (int g : gps) if (!rc) rc = launch_fill(c, c->kspec[g], c->K[g]);
-    hipEventRecord(e1, c->stream);
-    hipEventSynchronize(e1);
+    hipEventRecord(ev.b, c->stream);
+    hipEventSynchronize(ev.b);
     float t = 0.f;
-    hipEventElapsedTime(&t, e0, e1);
-    hipEventDestroy(e0); hipEventDestroy(e1);
+    hipEventElapsedTime(&t, ev.a, ev.b);
     *ms = t / reps;
     return rc;
 }
@@ -1174,46 +1118,37 @@ static int test_factor_impl(gprn_ctx* c, int n, int batch, const double* A, doub
     const size_t nn = (size_t)n * n;
     HIP_TRY(c, hipMemcpy(c->d_test[0], A, nn * batch * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(c->d_test[1], 0, nn * batch * sizeof(double)));
-    double** d_p = nullptr;
-    int* d_i = nullptr;
-    int rc = dev_alloc(c, &d_p, (size_t)batch * GPRN_NBUF);
-    if (!rc) rc = dev_alloc(c, &d_i, batch);
     std::vector<double*> hp((size_t)batch * GPRN_NBUF, nullptr);
     for (int b = 0; b < batch; ++b) {
         hp[(size_t)b * GPRN_NBUF + BUF_B] = c->d_test[0] + b * nn;
         hp[(size_t)b * GPRN_NBUF + BUF_X] = c->d_test[1] + b * nn;
     }
-    hipError_t e = hipSuccess;
-    int info0 = 0;
-    if (!rc) {
-        e = hipMemcpy(d_p, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice);
-        if (e == hipSuccess) tab_note(c, d_p, hp.data(), hp.size());
-        if (e == hipSuccess) e = hipMemset(d_i, 0, batch * sizeof(int));
-        const Phase ph{d_p, nullptr, batch, 0, d_i, EvalMap{nullptr, 0, 0, 0, 0}, n, n, n / GPRN_TILE};
-        if (e == hipSuccess) rc = lauum ? GPRN_OK : factor_invert(c, ph);
-        if (lauum && e == hipSuccess) {
-            // X := A (lower), out -> BUF_B
-            e = hipMemcpy(c->d_test[1], A, nn * sizeof(double), hipMemcpyHostToDevice);
-            if (e == hipSuccess) rc = lauum_lower(c, ph);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess && !rc) rc = factor_check_waits(c);
-        if (e == hipSuccess && !rc) {
-            if (lauum) e = hipMemcpy(lauum_out, c->d_test[0], nn * sizeof(double), hipMemcpyDeviceToHost);
-            else {
-                e = hipMemcpy(L, c->d_test[0], nn * batch * sizeof(double), hipMemcpyDeviceToHost);
-                if (e == hipSuccess) e = hipMemcpy(Linv, c->d_test[1], nn * batch * sizeof(double), hipMemcpyDeviceToHost);
-                if (e == hipSuccess) e = hipMemcpy(&info0, d_i, sizeof(int), hipMemcpyDeviceToHost);
-                for (int b = 0; b < batch; ++b)           // the upper triangle still holds A
-                    for (int m = 0; m < n; ++m)
-                        for (int k2 = m + 1; k2 < n; ++k2) L[b * nn + (size_t)m * n + k2] = 0.0;
-            }
-        }
+    CallScratch scr(c);
+    double** d_p = nullptr;
+    int* d_i = nullptr;
+    TRY(scr.table(&d_p, hp, true));
+    TRY(scr.alloc(&d_i, batch));
+    HIP_TRY(c, hipMemset(d_i, 0, batch * sizeof(int)));
+    const Phase ph{d_p, nullptr, batch, 0, d_i, EvalMap{nullptr, 0, 0, 0, 0}, n, n, n / GPRN_TILE};
+    if (lauum) {
+        // X := A (lower), out -> BUF_B
+        HIP_TRY(c, hipMemcpy(c->d_test[1], A, nn * sizeof(double), hipMemcpyHostToDevice));
+        TRY(lauum_lower(c, ph));
+    } else
+        TRY(factor_invert(c, ph));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    TRY(factor_check_waits(c));
+    if (lauum) {
+        HIP_TRY(c, hipMemcpy(lauum_out, c->d_test[0], nn * sizeof(double), hipMemcpyDeviceToHost));
+        return GPRN_OK;
     }
-    if (d_p) { tab_forget(c, d_p); hipFree(d_p); }
-    if (d_i) hipFree(d_i);
-    if (rc) return rc;
-    HIP_TRY(c, e);
+    int info0 = 0;
+    HIP_TRY(c, hipMemcpy(L, c->d_test[0], nn * batch * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(Linv, c->d_test[1], nn * batch * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&info0, d_i, sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < batch; ++b)           // the upper triangle still holds A
+        for (int m = 0; m < n; ++m)
+            for (int k2 = m + 1; k2 < n; ++k2) L[b * nn + (size_t)m * n + k2] = 0.0;
     return info0;
 }
 
