@@ -81,6 +81,8 @@ SIGNATURES = {
     'gprn_prior_terms': (c_int, [c_void_p, c_int, _dp, _dp, _dp]),
     'gprn_grad_matrices': (c_int, [c_void_p, c_int, _dp, _dp]),
     'gprn_grad_kernel': (c_int, [c_void_p, c_int, _dp, _dp]),
+    'gprn_grad_elbo': (c_int, [c_void_p, _dp, c_int]),
+    'gprn_grad_matrix': (c_int, [c_void_p, c_int, _dp]),
     'gprn_eval_kernel': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, c_double, _dp]),
     'gprn_sample_prior': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, c_double, c_int, _dp, _dp]),
 }
@@ -385,6 +387,21 @@ class Context:
             return None
         self._check(rc, 'grad_kernel')
         return out[:n_params]
+
+    def grad_elbo(self, n_params):
+        """d/dtheta of the expected log prior of the last committed sweep for every kernel parameter of every latent GP
+        with a device program, one call (gprn_grad_elbo: the B-form, no keep_sigma); `n_params`: their number.  NOT
+        divided by q."""
+        out = np.zeros(max(1, int(n_params)))
+        self._check(self._lib.gprn_grad_elbo(self._h, _ptr(out), int(n_params)), 'grad_elbo')
+        return out[:int(n_params)]
+
+    def grad_matrix(self, gp):
+        """G = 1/2 (a a^T + M) of latent GP `gp` after a committed sweep, (N, N) symmetric: what meets dK/dtheta
+        (gprn_grad_matrix; for kernels the caller differentiates)."""
+        out = np.empty((self.N, self.N))
+        self._check(self._lib.gprn_grad_matrix(self._h, int(gp), _ptr(out)), 'grad_matrix')
+        return out
 
     def keep_sigma(self, on=True):
         self._check(self._lib.gprn_keep_sigma(self._h, int(bool(on))), 'keep_sigma')

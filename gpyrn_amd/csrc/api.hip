@@ -414,6 +414,7 @@ extern "C" int gprn_set_data(gprn_ctx* c, int N, int p, int q, const double* tim
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     free_problem(c);
+    c->grad_ready = false;
     c->N = N; c->p = p; c->q = q; c->G = q + q * p;
     c->ld = ((N + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
     c->T = c->ld / GPRN_TILE;
@@ -479,7 +480,7 @@ extern "C" int gprn_set_kernel(gprn_ctx* c, int gp, const int32_t* ops, int n_op
     ks.n_ops = n_ops; ks.n_params = n_params; ks.nugget = add_nugget ? 1 : 0;
     memcpy(ks.ops, ops, 3 * n_ops * sizeof(int32_t));
     if (n_params) memcpy(ks.params, params, n_params * sizeof(double));
-    c->factored = false;
+    c->factored = false; c->grad_ready = false;
     return GPRN_OK;
 }
 
@@ -499,7 +500,7 @@ extern "C" int gprn_upload_K(gprn_ctx* c, int gp, const double* Kh)
     HIP_TRY(c, hipSetDevice(c->device));
     KernelSpec& ks = c->kspec[gp];
     ks.set = true; ks.uploaded = true;
-    c->factored = false;
+    c->factored = false; c->grad_ready = false;
     if (c->owner.empty()) return bad(c, "upload_K: call set_owners first");
     if (c->owner[gp] != c->rank) return GPRN_OK;                    // not needed on this rank
     TRY(ensure_gp_storage(c, gp));
@@ -545,6 +546,7 @@ extern "C" int gprn_set_muvar(gprn_ctx* c, const double* mu, const double* var)
 {
     DeviceLock lock_(c);
     if (!c || !c->N || !mu || !var) return bad(c, "set_muvar: bad argument");
+    c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     const size_t dn = (size_t)(c->p + 1) * c->q * c->N * sizeof(double);
@@ -894,6 +896,7 @@ int build_tables(gprn_ctx* c)
 {
     if (c->tables_ready) return mask_prepare(c);     // (a data mask set since: its buffers, as part of the set-up)
     mask_invalidate(c);
+    c->grad_ready = false;
     // (the second set of node workspaces and its table are rebuilt on demand: sweep_impl)
     c->loc_nodes.clear(); c->loc_weights.clear();
     for (int g = 0; g < c->q; ++g) if (c->owner[g] == c->rank) c->loc_nodes.push_back(g);

@@ -74,6 +74,7 @@ extern "C" int gprn_predict(gprn_ctx* c, int ns, const double* tstar, double* me
 static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out, const PredAfter& after)
 {
     TRY(build_tables(c));
+    c->grad_ready = false;                           // (the sweep's workspaces hold the prediction's factors from here on)
     std::vector<int> gps = c->loc_nodes;
     gps.insert(gps.end(), c->loc_weights.begin(), c->loc_weights.end());
     const int nloc = (int)gps.size();
@@ -763,6 +764,7 @@ static int grad_impl(gprn_ctx* c, int gp, double* Kinv_out, double* P_out, const
     for (int k = 0; k < nsum; ++k)
         if (!c->Sig[gp < c->q ? k : gp]) return bad(c, "grad_matrices: no Sigma yet (run a sweep with keep_sigma on)");
     if (c->nslot < 2) return bad(c, "grad_matrices: needs two workspace slots");
+    c->grad_ready = false;                           // (the sweep's workspaces are scratch here)
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     HIP_TRY(c, hipStreamSynchronize(c->stream2));
@@ -904,6 +906,7 @@ extern "C" int gprn_prior_terms(gprn_ctx* c, int gp, const double* S, const doub
     if (!c || !c->N || gp < 0 || gp >= c->G || !S || !m || !out3) return bad(c, "prior_terms: bad argument");
     if (c->world != 1) return bad(c, "prior_terms: not available on a sharded context");
     if (!c->factored) return bad(c, "prior_terms: needs factor_priors first");
+    c->grad_ready = false;                           // (the latent GP's workspaces are scratch here)
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(build_tables(c));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);

@@ -13,6 +13,7 @@ extern "C" int gprn_factor_priors(gprn_ctx* c)
     if (!c || !c->N) return bad(c, "factor_priors: call set_data first");
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "factor_priors: call set_owners first");
+    c->grad_ready = false;
     int pre = GPRN_OK;
     for (int g = 0; g < c->G && !pre; ++g)
         if (!c->kspec[g].set) pre = bad(c, "factor_priors: a latent GP has no kernel");
@@ -410,6 +411,7 @@ extern "C" int gprn_sweep(gprn_ctx* c, int n_sweeps, int commit, double* elbo_ou
 
 static int sweep_impl(gprn_ctx* c, int n_sweeps, int commit, double* elbo_out, double* parts_out, bool retry)
 {
+    c->grad_ready = false;                           // set again below: by a committed call whose pivots all passed
     if (n_sweeps > c->out_cap) {
         dev_free(c->d_out);
         TRY(dev_alloc(c, &c->d_out, 4 * (size_t)n_sweeps));
@@ -517,11 +519,13 @@ static int sweep_impl(gprn_ctx* c, int n_sweeps, int commit, double* elbo_out, d
                 if (v > 0 && first == 0) { first = v; c->info_gp = gps[sl]; }
             }
         }
+        c->grad_ready = commit && first == 0;
         return first;
     }
     TRY(factor_check_waits(c));
     TRY(check_info(c, c->d_info + (size_t)c->nslot, c->loc_nodes, &first));
     TRY(check_info(c, c->d_info + 2 * (size_t)c->nslot, c->loc_weights, &first));
+    c->grad_ready = commit && first == 0;
     return first;
 }
 
@@ -680,6 +684,7 @@ extern "C" int gprn_elbocalc(gprn_ctx* c, int do_setup, const double* y_resid, c
     DeviceLock lock_(c);
     if (!c) return GPRN_E_ARG;
     WatchScope watch_(c, "gprn_elbocalc");
+    c->grad_ready = false;
     // On a sharded context every LOCAL finding -- arguments, call order, a setter that fails -- goes into `pre`, and the
     // ranks agree on it before the first collective of the call (the set-up's own): a rank that returned here on its own
     // would leave the others in gprn_factor_priors' all-reduce.
@@ -745,6 +750,7 @@ extern "C" int gprn_elbocalc(gprn_ctx* c, int do_setup, const double* y_resid, c
     // (a history longer than the caller's array keeps its LAST values: the first is elboArray[0] of a loop that ran to max_iter)
     const int n = (int)hist.size(), keep = std::min(n, cap);
     for (int i = 0; i < keep; ++i) history[i] = hist[(size_t)(n - keep) + i];
+    c->grad_ready = info == 0 && iter >= 1;         // (max_iter = 0 commits nothing)
     return info;
 }
 
@@ -771,6 +777,7 @@ extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel
         !iterations || !converged || !info || (!mu_out != !var_out))
         return bad(c, "elbocalc_batch: bad argument");
     if (c->d_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
+    c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "elbocalc_batch: call set_owners first");
     if (comm_active(c) || c->world != 1) { c->err = "elbocalc_batch: one rank only (a pool of ranks splits the list itself)"; return GPRN_E_UNSUPPORTED; }

@@ -134,6 +134,10 @@ struct gprn_ctx {
     double *d_mu = nullptr, *d_var = nullptr;        // (p+1, q, N) each, reference layout
     double *d_mu_save = nullptr, *d_var_save = nullptr;
     bool have_yres = false, have_jit = false, have_muvar = false, factored = false;
+    // the workspaces (X = chol(B)^-1 in wsX, s in d_s) and the state are those of one committed sweep: what gprn_grad_elbo /
+    // gprn_grad_matrix read (grad.hip).  Set by a committed gprn_sweep and by gprn_elbocalc, cleared by everything that
+    // rewrites wsB / wsX / d_s or the state
+    bool grad_ready = false;
 
     // ---- sharding
     int world = 1, rank = 0;

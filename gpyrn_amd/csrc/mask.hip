@@ -216,6 +216,7 @@ extern "C" int gprn_set_mask(gprn_ctx* c, const uint8_t* mask)
     dev_free(c->d_mask); dev_free(c->d_mask_U); dev_free(c->d_mask_nU);
     c->h_mask.clear(); c->mask_U.clear(); c->mask_upad = 0;
     c->factored = false;                 // the set-up runs on the path the sweeps will take (small_applies)
+    c->grad_ready = false;
     c->small_tabs_ready = false; c->small_sweep_ready = false; c->setup1_ready = false;
     if (!mask) return GPRN_OK;
     size_t umax = 0;

@@ -13,6 +13,7 @@
 //   k_loglike_partial / k_elbo_final  expected log-likelihood (:895-990) + assembly (:709)
 #include "gprn_internal.h"
 #include "vecops.h"
+#include "grad_elem.h"
 
 #include <math.h>
 
@@ -806,24 +807,7 @@ void k_grad_rows(int kid, double q0, double q1, double q2, double q3, const doub
     for (int n = lane; n < N; n += 64) {
         const double G = 0.5 * (P[(size_t)m * ld + n] - Kinv[(size_t)m * ld + n] + am * a[n]);
         const double r = tm - t[n];
-        if (kid == GPRN_K_SE) {
-            const double K = q0 * q0 * exp(-0.5 * (r * r) / (q1 * q1));
-            g0 += G * (2 * K / q0);
-            g1 += G * (K * (r * r) / (q1 * q1 * q1));
-        } else if (kid == GPRN_K_PERIODIC) {
-            const double x = 3.141592653589793 * fabs(r) / q1, sx = sin(x);
-            const double K = q0 * q0 * exp(-2 * (sx * sx) / (q2 * q2));
-            g0 += G * (2 * K / q0);
-            g1 += G * (K * 2 * x * sin(2 * x) / (q1 * (q2 * q2)));
-            g2 += G * (K * 4 * (sx * sx) / (q2 * q2 * q2));
-        } else {                                   // GPRN_K_QP
-            const double x = 3.141592653589793 * fabs(r) / q2, sx = sin(x);
-            const double K = q0 * q0 * exp(-2 * (sx * sx) / (q3 * q3) - (r * r) / (2 * (q1 * q1)));
-            g0 += G * (2 * K / q0);
-            g1 += G * (K * (r * r) / (q1 * q1 * q1));
-            g2 += G * (K * 2 * x * sin(2 * x) / (q2 * (q3 * q3)));
-            g3 += G * (K * 4 * (sx * sx) / (q3 * q3 * q3));
-        }
+        GRAD_CLOSED_ELEM(kid, q0, q1, q2, q3, r, G, g0, g1, g2, g3);
     }
     g0 = wave_sum(g0); g1 = wave_sum(g1); g2 = wave_sum(g2); g3 = wave_sum(g3);
     if (lane == 0) { part[4 * m] = g0; part[4 * m + 1] = g1; part[4 * m + 2] = g2; part[4 * m + 3] = g3; }

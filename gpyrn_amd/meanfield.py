@@ -745,6 +745,8 @@ class inference:
         -- ``optimize()`` itself minimises ``nELBO``, the warm-started ELBOcalc under the reference's 1e-3 stop rule,
         which jumps whenever the trip count changes.  The result says so: ``res.objective`` names what ``res.fun`` is,
         and ``res.fun_reference`` is ``nELBO(res.x)``, the reference's objective at the point found.
+        ``fused=True`` (with ``jac=True``): the gradient through ``grad_ELBO(fused=True)`` -- one device call per
+        evaluation, and the only gradient there is under a data mask (``from_series``).
         """
         from scipy.optimize import minimize
         self._select_vars(vars)
@@ -755,13 +757,20 @@ class inference:
         # state this call starts at -- the reference's own objective (ELBOcalc under its 1e-3 stop rule, warm-started
         # from the previous evaluation) jumps by 1e-3 relative whenever the trip count changes, which a line search
         # cannot work with
+        fused = bool(kwargs.pop('fused', False))
+        if fused and kwargs.get('jac') is not True:
+            raise ValueError('optimize(fused=True) chooses the form of the gradient: it needs jac=True')
         if kwargs.get('jac') is True:
-            self._refuse_masked('optimize(jac=True)')
+            if fused:
+                if self._comm is not None:
+                    raise NotImplementedError('optimize(jac=True, fused=True) is not available on a sharded inference object')
+            else:
+                self._refuse_masked('optimize(jac=True)')
             sweeps = int(kwargs.pop('sweeps', 40))
             nodes, weights, means, jitters = self._get_components()
             start = (self._mu, self._var) if self._mu is not None else self._initMuVar(nodes, weights, jitters)
             start = (np.array(start[0], dtype=float), np.array(start[1], dtype=float))
-            fun = lambda x: self.nELBO_and_grad(x, sweeps=sweeps, start=start)
+            fun = lambda x: self.nELBO_and_grad(x, sweeps=sweeps, start=start, fused=fused)
         else:
             fun = self.nELBO
         smooth = kwargs.get('jac') is True
@@ -1113,7 +1122,7 @@ class inference:
         return [float(-e) for e in elbo]
 
     # ------------------------------------------------------------ gradients
-    def grad_ELBO(self, mean_sweeps=8, mean_start=None, total=False):
+    def grad_ELBO(self, mean_sweeps=8, mean_start=None, total=False, fused=False):
         """
         Gradient of the ELBO with respect to ALL parameters (the order of ``get_parameters(
         include_frozen=True)``: nodes, weights, means, jitters) at the current variational state.
@@ -1149,9 +1158,23 @@ class inference:
         mean-function parameters: central differences of the ELBO after ``mean_sweeps`` forced sweeps (two set-ups and
         runs per kernel parameter: this is for small problems and few parameters).
 
+        ``fused=True``: the same gradient in the B-form, one device call for all kernel parameters
+        (``gprn_grad_elbo``).  With ``B = I + S K S`` and ``X = chol(B)^-1`` as the sweep leaves it,
+        ``K^-1 Sigma K^-1 - K^-1 = -S B^-1 S``, so the matrix that meets ``dK/dtheta`` is ``1/2 (a a^T - S B^-1 S)`` (plus
+        the Q1 cross terms of the nodes j >= 1): the committed sweep runs WITHOUT the explicit covariances, on whichever
+        path the problem takes, and nothing is divided by ``s`` -- which is why this form is also the gradient under a
+        data mask (the default form raises ``NotImplementedError`` there).  Latent GPs with user-defined kernels get
+        their matrix from ``gprn_grad_matrix`` and are contracted on the host.  The entries of the two forms agree to
+        the accuracy of the explicit one (the B-form is the better conditioned: DESIGN.md 9 f-3).  Where the sweep meets
+        a non-positive pivot (``last_info != 0``) this form returns ``(-inf, zeros)`` and keeps the stored state.
+
         Returns ``(ELBO, gradient)``.  Unsharded problems only.
         """
-        self._refuse_masked('grad_ELBO')
+        if fused:
+            if self._comm is not None:
+                raise NotImplementedError('grad_ELBO(fused=True) is not available on a sharded inference object')
+        else:
+            self._refuse_masked('grad_ELBO')
         assert self._components_set, _NOT_SET
         if self._mu is None:
             self.ELBOcalc()
@@ -1159,14 +1182,24 @@ class inference:
         ctx = self._setup_device(nodes, weights, means, jitters)
         mu_in, var_in = np.array(self._mu, dtype=float), np.array(self._var, dtype=float)
         ctx.set_muvar(mu_in, var_in)
-        ctx.keep_sigma(True)
-        try:
+        if fused:
             elbo, _, info = ctx.sweep(1, commit=True)
+            if info:
+                # a non-positive pivot: no factors to take the gradient from.  As in the default form the ELBO is not
+                # finite there and nELBO_and_grad hands a line search (inf, 0) to back off from; the state is kept
+                self.last_info = info
+                return -np.inf, np.zeros(len(self.get_parameters(include_frozen=True)))
             mu, var = ctx.get_muvar()
-            grads = self._grad_from_state(nodes, weights, means, jitters, mu, var, ctx.grad_matrices,
-                                          device=ctx.grad_kernel)
-        finally:
-            ctx.keep_sigma(False)
+            grads = self._grad_from_state(nodes, weights, means, jitters, mu, var, None, fused=ctx)
+        else:
+            ctx.keep_sigma(True)
+            try:
+                elbo, _, info = ctx.sweep(1, commit=True)
+                mu, var = ctx.get_muvar()
+                grads = self._grad_from_state(nodes, weights, means, jitters, mu, var, ctx.grad_matrices,
+                                              device=ctx.grad_kernel)
+            finally:
+                ctx.keep_sigma(False)
         self._mu, self._var = mu, var
         self.last_info = info
         grads = np.array(grads)
@@ -1209,17 +1242,38 @@ class inference:
             self._setup_device(nodes, weights, means, jitters).set_muvar(*restore)
         return out
 
-    def _grad_from_state(self, nodes, weights, means, jitters, mu, var, matrices, device=None):
+    def _grad_from_state(self, nodes, weights, means, jitters, mu, var, matrices, device=None, fused=None):
         """The O(N^2) and O(pqN) part of grad_ELBO: `matrices(gp)` returns ``(K^-1, K^-1 S K^-1)`` of latent GP
         `gp` (the GPU's ``gprn_grad_matrices``; a NumPy stand-in in the CPU tests).  `device(gp, m, n)`, when
         given, is tried first: the whole contraction on the GPU (``gprn_grad_kernel``: closed-form or
-        central-difference dK/dtheta of the kernel's device program), None for kernels without one."""
+        central-difference dK/dtheta of the kernel's device program), None for kernels without one.
+        `fused`: the device context after a committed sweep -- the B-form instead: every kernel with a device program in
+        ONE call (``gprn_grad_elbo``), the others through ``gprn_grad_matrix`` (G itself) and the host contraction
+        below; `matrices` and `device` are not used then."""
         t = np.asarray(self.time, dtype=float)
-        r = t[:, None] - t[None, :]
+        # (N x N on the host: formed only for a kernel that is contracted here -- 134 MB and 16 ms at N = 4096)
+        r = None
         q, p, N = self.q, self.p, self.N
         m_scr = mu[1:].reshape(q, p, N)                      # quirk Q2 (meanfield.py:1021)
         grads = []
+        on_dev = None
+        if fused is not None:
+            counts = [k.pars.size if isinstance(k, covfunc.covFunction) and k._device_program() is not None else 0
+                      for k in chain(nodes, weights)]
+            on_dev = list(fused.grad_elbo(int(sum(counts))))
         for gp, kernel in enumerate(chain(nodes, weights)):
+            if fused is not None:
+                if counts[gp]:
+                    grads += [float(on_dev.pop(0)) / q for _ in range(counts[gp])]
+                    continue
+                G = fused.grad_matrix(gp) / q
+                if isinstance(kernel, _TWO_ARGUMENT):
+                    dks = covfunc._richardson(kernel, lambda: np.asarray(kernel(t[:, None], t[None, :]), dtype=float))
+                else:
+                    r = t[:, None] - t[None, :] if r is None else r
+                    dks = kernel._dk_dpars(r)
+                grads += [float(np.sum(G * dk)) for dk in dks]
+                continue
             if gp < q:
                 m = mu[0, gp]
             else:
@@ -1236,6 +1290,7 @@ class inference:
             if isinstance(kernel, _TWO_ARGUMENT):             # kernel(t_i, t_j): differences only
                 dks = covfunc._richardson(kernel, lambda: np.asarray(kernel(t[:, None], t[None, :]), dtype=float))
             else:
+                r = t[:, None] - t[None, :] if r is None else r
                 dks = kernel._dk_dpars(r)
             grads += [float(np.sum(G * dk)) for dk in dks]
         grads += [0.0] * sum(0 if m_ is None else int(m_._parsize) for m_ in means)
@@ -1247,18 +1302,25 @@ class inference:
             for j in range(q):
                 A[i] += var[0, j] * mu[1 + i, j]**2 + var[1 + i, j] * mu[0, j]**2 + var[0, j] * var[1 + i, j]
         dv = -0.5 * (1.0 / variance - ((self.y - fit)**2 + A) / variance**2)
+        if self.mask is not None:                            # observed entries only (whatever a masked y / yerr holds)
+            dv = np.where(self.mask, dv, 0.0)
         grads += [float(np.sum(dv[i]) * 2 * jitters[i]) / q for i in range(p)]
         return grads
 
-    def nELBO_and_grad(self, parameters, max_iter=None, sweeps=None, start=None):
+    def nELBO_and_grad(self, parameters, max_iter=None, sweeps=None, start=None, fused=False):
         """``(-ELBO, -dELBO/dparameters)`` over the FREE parameters, for gradient-based optimisers.  Default:
         ``nELBO(parameters)`` (warm-started ELBOcalc, as the reference's objective), then ``grad_ELBO``.  With
         ``sweeps`` (and a start state ``(mu, var)``): the ELBO after exactly that many forced sweeps from ``start``
-        plus the one ``grad_ELBO`` adds -- a deterministic, smooth function of the parameters."""
-        self._refuse_masked('nELBO_and_grad')
+        plus the one ``grad_ELBO`` adds -- a deterministic, smooth function of the parameters.  ``fused``: as in
+        ``grad_ELBO`` (one device call for the kernel parameters; allowed under a data mask)."""
+        if fused:
+            if self._comm is not None:
+                raise NotImplementedError('nELBO_and_grad(fused=True) is not available on a sharded inference object')
+        else:
+            self._refuse_masked('nELBO_and_grad')
         if sweeps is None:
             self.nELBO(parameters, max_iter=max_iter)
-            elbo, grad = self.grad_ELBO()
+            elbo, grad = self.grad_ELBO(fused=fused)
             return -elbo, -grad[~self.frozen_mask]
         assert self._components_set, _NOT_SET
         self.set_parameters(np.array(parameters, dtype=float))
@@ -1270,7 +1332,7 @@ class inference:
         _, _, info = ctx.sweep(int(sweeps), commit=True)
         self.last_info = info
         self._mu, self._var = ctx.get_muvar()
-        elbo, grad = self.grad_ELBO(mean_sweeps=int(sweeps) + 1, mean_start=start, total=True)
+        elbo, grad = self.grad_ELBO(mean_sweeps=int(sweeps) + 1, mean_start=start, total=True, fused=fused)
         if not np.isfinite(elbo):
             return np.inf, np.zeros(int((~self.frozen_mask).sum()))
         return -elbo, -grad[~self.frozen_mask]

@@ -98,7 +98,7 @@ int gprn_set_data(gprn_ctx* ctx, int N, int p, int q,
  * GPRN_E_ARG: an output with no observed entry, or q >= 2 with a time at which every output is masked (drop that time;
  * predict still reaches it).  Both paths (one-tile kernels and launch schedule) have a masked form;
  * gprn_keep_sigma(1), gprn_grad_matrices, gprn_grad_kernel, gprn_elbocalc_batch and contexts with a communicator
- * return GPRN_E_UNSUPPORTED. */
+ * return GPRN_E_UNSUPPORTED.  The masked gradient is gprn_grad_elbo / gprn_grad_matrix (the B-form needs no division by s). */
 int gprn_set_mask(gprn_ctx* ctx, const uint8_t* mask);
 
 /* ---- multi-GPU sharding (new): one context per rank/GPU.
@@ -219,6 +219,28 @@ int gprn_grad_matrices(gprn_ctx* ctx, int gp, double* Kinv_out, double* P_out);
  * term is the rounding of K that any difference of step h carries), periods down to 0.3 over a span of 60 and length
  * scales down to a third of the sampling included.  GPRN_E_UNSUPPORTED for a latent GP whose matrix was uploaded (gprn_upload_K). */
 int gprn_grad_kernel(gprn_ctx* ctx, int gp, const double* m, double* grad_out);
+/* ---- the same gradient for EVERY latent GP in one call, in the B-form: no gprn_keep_sigma, no K^-1, no
+ * explicit Sigma, one host synchronisation.  With B = I + S K S, S = diag(s), and X = chol(B)^-1 as the last sweep left it,
+ *   K^-1 Sigma K^-1 - K^-1 = - S B^-1 S      (exact; valid where s_n = 0, i.e. under gprn_set_mask)
+ * so d/dtheta of the expected log prior (meanfield.py:992-1067) is < G_gp, dK_gp/dtheta > with G_gp = 1/2 (a a^T + M_gp),
+ * a = K_gp^-1 m_gp, m_gp = the state row of latent GP gp as it lies in memory (quirk Q2),
+ *   weight:  M = - S B^-1 S;    node j:  M = - S B^-1 S + sum_{k<j} K_j^-1 Sigma_fk K_j^-1   (quirk Q1),
+ * the nugget not differentiated.  dK/dtheta by gprn_grad_kernel's rules (closed forms for a single SE / Periodic /
+ * QuasiPeriodic, Richardson-extrapolated central differences of the kernel program with h = 1e-6 max(1, |theta|) otherwise).
+ * gprn_grad_elbo: d/dtheta of the expected log prior of the LAST COMMITTED sweep for every kernel parameter of every latent
+ * GP: grad_out = concatenation over gp = 0 .. G-1 of n_params[gp] values (the layout of gprn_elbocalc_batch's kernel_params; a
+ * latent GP whose K was uploaded contributes no entry), NOT divided by q.  n_out: the length of grad_out (GPRN_E_ARG if it
+ * is not the number of those parameters).  Sums in a fixed order: two calls return the same bits.
+ * gprn_grad_matrix: G_gp itself, (N, N) symmetric, for the caller to contract with its own dK/dtheta (user-defined kernels).
+ * Both need a committed sweep right before them -- gprn_sweep(commit = 1) or gprn_elbocalc (max_iter >= 1) with every pivot
+ * positive; GPRN_E_ARG "needs a committed sweep" after anything that rewrites the sweep's workspaces or the state
+ * (gprn_sweep(commit = 0), gprn_set_muvar, gprn_factor_priors, gprn_set_kernel, gprn_upload_K, gprn_set_mask, gprn_prior_terms,
+ * gprn_grad_matrices, gprn_grad_kernel, gprn_elbocalc_batch, the prediction entry points, a failed pivot).  They read X and
+ * write lower(B^-1) into the B workspaces (GPRN_M_BL then reads B^-1 for every latent GP); the state, gprn_get_scalars and
+ * the next sweep's results are bit-identical with and without them.  Data masks and both sweep orders are supported;
+ * sharded contexts: GPRN_E_UNSUPPORTED.  GPRN_E_NOMEM when the scratch of the cross terms (q >= 2) cannot be had. */
+int gprn_grad_elbo(gprn_ctx* ctx, double* grad_out, int n_out);
+int gprn_grad_matrix(gprn_ctx* ctx, int gp, double* G_out);
 
 /* ---- the terms of the ELBO on their own: what the reference's private step methods return (meanfield.py:895-990 and
  * 992-1067; ELBOaux :651-710 calls them in turn, and scripts written against the reference may too).
