@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GPRN_HIP_LIB') or os.path.join(_HERE, 'libgprn_hip.so')
 
 GPRN_E_ARG, GPRN_E_HIP, GPRN_E_NODEV, GPRN_E_COMM, GPRN_E_NOMEM, GPRN_E_UNSUPPORTED = -1, -2, -3, -4, -5, -6
+GPRN_BATCH_FORCED = 1          # gprn_elbocalc_batch_grad: no stop rule, max_iter committed sweeps per evaluation
 COV_JOINT = 1
 ORDER_REFERENCE, ORDER_SEQUENTIAL = 0, 1
 M_K, M_KLINV, M_SIGMA, M_BX, M_BL = 0, 1, 2, 3, 4
@@ -75,6 +76,8 @@ SIGNATURES = {
     'gprn_set_option': (c_int, [c_void_p, c_char_p, c_int, POINTER(c_int)]),
     'gprn_elbocalc_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, _dp, POINTER(c_int), POINTER(c_int),
                             POINTER(c_int), _dp, _dp]),
+    'gprn_elbocalc_batch_grad': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, _dp, POINTER(c_int),
+                                 POINTER(c_int), POINTER(c_int), _dp, _dp, _dp]),
     'gprn_elbocalc': (c_int, [c_void_p, c_int, _dp, _dp, _dp, _dp, c_int, _dp, c_int, POINTER(c_int), POINTER(c_int),
                       POINTER(c_int), _dp, _dp]),
     'gprn_expected_loglike': (c_int, [c_void_p, _dp]),
@@ -438,10 +441,14 @@ class Context:
         return (hist[:min(n.value, cap)].copy(), it.value, bool(conv.value), info,
                 mu_out.reshape(shape), var_out.reshape(shape))
 
-    def elbocalc_batch(self, kernel_params, y_resid, jitters, mu, var, max_iter, want_state=False):
+    def elbocalc_batch(self, kernel_params, y_resid, jitters, mu, var, max_iter, want_state=False, want_grad=False,
+                       forced=False):
         """B independent ELBOcalc loops side by side (gprn_elbocalc_batch): kernel_params (B, n_kpar), y_resid (B, p, N),
         jitters (B, p), mu / var (B, d).  Returns (elbo[B], iterations[B], converged[B], info[B]) and, with want_state,
-        the final states (B, p+1, q, N) twice -- or None where the library has no batched form for this problem."""
+        the final states (B, p+1, q, N) twice -- or None where the library has no batched form for this problem.
+        want_grad (gprn_elbocalc_batch_grad): the tuple ends with grads (B, n_kpar), row b what grad_elbo returns after
+        evaluation b's loop alone (NOT divided by q; zeros where info > 0).  forced (GPRN_BATCH_FORCED): no stop rule,
+        exactly max_iter committed sweeps per evaluation."""
         kp = _f64(np.atleast_2d(kernel_params))
         B = kp.shape[0]
         d = (self.p + 1) * self.q * self.N
@@ -453,9 +460,16 @@ class Context:
         mo = np.empty((B, d)) if want_state else None
         vo = np.empty((B, d)) if want_state else None
         ip = lambda a: a.ctypes.data_as(POINTER(c_int))
-        rc = self._lib.gprn_elbocalc_batch(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
-                                           int(max_iter), _ptr(elbo), ip(it), ip(cv), ip(info),
-                                           _ptr(mo) if want_state else None, _ptr(vo) if want_state else None)
+        grads = np.zeros((B, kp.shape[1])) if want_grad else None
+        if want_grad or forced:
+            rc = self._lib.gprn_elbocalc_batch_grad(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
+                                                    int(max_iter), GPRN_BATCH_FORCED if forced else 0, _ptr(elbo), ip(it),
+                                                    ip(cv), ip(info), _ptr(mo) if want_state else None,
+                                                    _ptr(vo) if want_state else None, _ptr(grads) if want_grad else None)
+        else:
+            rc = self._lib.gprn_elbocalc_batch(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
+                                               int(max_iter), _ptr(elbo), ip(it), ip(cv), ip(info),
+                                               _ptr(mo) if want_state else None, _ptr(vo) if want_state else None)
         if rc == GPRN_E_UNSUPPORTED:
             return None
         self._check(rc, 'elbocalc_batch')
@@ -463,6 +477,8 @@ class Context:
         if want_state:
             shape = (B, self.p + 1, self.q, self.N)
             out += (mo.reshape(shape), vo.reshape(shape))
+        if want_grad:
+            out += (grads,)
         return out
 
     def option(self, name, value=-1):

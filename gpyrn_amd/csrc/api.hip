@@ -244,6 +244,7 @@ void free_problem(gprn_ctx* c)
     if (c->d_loop_ctl) { hipFree(c->d_loop_ctl); c->d_loop_ctl = nullptr; }
     small_batch_free(c);
     mid_batch_free(c);
+    if (c->grad_scratch) { hipFree(c->grad_scratch); c->grad_scratch = nullptr; c->grad_scratch_bytes = 0; }
     if (c->h_pin_in) { hipHostFree(c->h_pin_in); c->h_pin_in = nullptr; c->pin_in_cap = 0; }
     if (c->h_pin_out) { hipHostFree(c->h_pin_out); c->h_pin_out = nullptr; c->pin_out_cap = 0; }
     dev_free(c->d_loop_hist);

@@ -767,15 +767,16 @@ size_t batch_budget_bytes(gprn_ctx* c)
 // B independent evaluations of the loop above, side by side on the device: see include/gprn_hip.h.  One-tile problems run a
 // half-sweep of ALL evaluations as one launch (smalln.hip); larger ones go through the launch schedule with
 // batch = evaluations x latent GPs (midn.hip).  Either way a list longer than the memory budget holds runs chunk by chunk.
-extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
-                                   const double* y_resid, const double* jitters, const double* mu, const double* var,
-                                   int max_iter, double* elbo, int* iterations, int* converged, int* info,
-                                   double* mu_out, double* var_out)
+extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                        const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                        int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
+                                        double* mu_out, double* var_out, double* grad_out)
 {
     DeviceLock lock_(c);
     if (!c || !c->N || n_eval < 1 || !kernel_params || !y_resid || !jitters || !mu || !var || max_iter < 0 || !elbo ||
-        !iterations || !converged || !info || (!mu_out != !var_out))
+        !iterations || !converged || !info || (!mu_out != !var_out) || (flags & ~GPRN_BATCH_FORCED))
         return bad(c, "elbocalc_batch: bad argument");
+    if (grad_out && max_iter < 1) return bad(c, "elbocalc_batch_grad: a gradient needs a committed sweep (max_iter >= 1)");
     if (c->d_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -797,9 +798,19 @@ extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel
     if (want != n_eval) c->err.clear();
     c->last_batch_chunk = std::min(cap, n_eval);
     const BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info,
-                     mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N};
+                     mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N, flags, grad_out};
+    // (with grad_out each chunk ends with the gradient pass of its evaluations, before the next chunk overwrites the slabs)
     for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(run(c, io.slice(e0, std::min(cap, n_eval - e0))));
     return GPRN_OK;
+}
+
+extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                   const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                   int max_iter, double* elbo, int* iterations, int* converged, int* info,
+                                   double* mu_out, double* var_out)
+{
+    return gprn_elbocalc_batch_grad(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, 0, elbo,
+                                    iterations, converged, info, mu_out, var_out, nullptr);
 }
 
 

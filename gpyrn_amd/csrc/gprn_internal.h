@@ -275,6 +275,10 @@ struct gprn_ctx {
     // chunk of evaluations; its kernels find an evaluation's arrays through the EvalMap of each Phase
     void* mid_batch = nullptr;       // MidBatch (midn.hip): the worker context and its slabs, owned by the PARENT context
     int batch_mem_mb = -1;           // gprn_set_option "batch_mem_mb": device memory one chunk of evaluations may take; -1: a share of what is free
+    // scratch of the batched gradient pass (grad.hip grad_batch_pass), on the context its launches go through: one piece that
+    // only grows and stays until the problem is freed
+    void* grad_scratch = nullptr;
+    size_t grad_scratch_bytes = 0;
     int last_batch_chunk = 0;        // read-only option "batch_chunk": evaluations per chunk in the last gprn_elbocalc_batch call
     // ---- sweep order (gprn_set_sweep_order, order.hip)
     int sweep_order = 0;             // GPRN_ORDER_REFERENCE (Jacobi, quirk Q6) or GPRN_ORDER_SEQUENTIAL
@@ -486,13 +490,36 @@ struct BatchIo {
     int n; const double* kparams; int n_kpar; const double *y_resid, *jitters, *mu, *var; int max_iter;
     double* elbo; int *iters, *conv, *info; double *mu_out, *var_out;     // (mu_out, var_out: both or neither)
     int p; size_t state, yv;               // per evaluation: jitters, doubles of mu / var, doubles of y_resid
+    int flags;                             // GPRN_BATCH_FORCED: no stop rule, max_iter committed trips each
+    double* grad_out;                      // [n][n_kpar]: the gradient of each evaluation's last committed sweep, or null
     BatchIo slice(int e0, int ne) const    // evaluations [e0, e0 + ne)
     {
         return BatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, y_resid + e0 * yv, jitters + (size_t)e0 * p, mu + e0 * state,
                        var + e0 * state, max_iter, elbo + e0, iters + e0, conv + e0, info + e0,
-                       mu_out ? mu_out + e0 * state : nullptr, var_out ? var_out + e0 * state : nullptr, p, state, yv};
+                       mu_out ? mu_out + e0 * state : nullptr, var_out ? var_out + e0 * state : nullptr, p, state, yv,
+                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr};
     }
 };
+// grad.hip: the steps of gprn_grad_elbo over the evaluations of a batch's chunk whose loops have ended, slots = evaluations x
+// latent GPs (gprn_elbocalc_batch_grad).  The drivers say where each evaluation's matrices, s = sqrt(d) and state lie; the
+// launches do not grow with n.  Evaluation e's state is state + state_idx[e] * state_stride (the reference's layout).
+struct GradBatchIn {
+    int N, ld, T, q, G;
+    const double* t;                       // the observation times (device)
+    int n = 0;                             // evaluations
+    std::vector<double*> rows;             // [n][G][GPRN_NBUF]: BUF_B (overwritten: lower(B^-1)), BUF_X, BUF_K, BUF_KLINV
+    std::vector<double*> kinv;             // [n][q - 1]: lower(K_j^-1), j >= 1
+    std::vector<double*> s;                // [n][G]: sqrt(d) of the last committed sweep (ld each)
+    const double* state = nullptr;
+    size_t state_stride = 0;
+    std::vector<int> state_idx;            // [n]
+    std::vector<const double*> kparams;    // [n] (host): the evaluation's kernel parameters
+    std::vector<double*> out;              // [n] (host): its row of grad_out
+};
+// w: the context the launches go through (its stream, its task lists, its grad_scratch); budget: bytes the pass's scratch may
+// take -- beyond it (or when the device refuses) the evaluations go in groups; GPRN_E_NOMEM when one evaluation's scratch does
+// not fit.  The scratch is an allocation class of its own: the drivers give it what the chunk's slabs left of the budget
+int grad_batch_pass(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const GradBatchIn& in, size_t budget);
 // What both drivers of gprn_elbocalc_batch ask of the caller's kernels and kernel_params (api_sweep.hip)
 int batch_validate(gprn_ctx* c, int n_kpar);
 // GPRN_BATCH_TIMERS=1 (probes): where the host's time of a chunk goes -- staging, enqueue, waits, read-back -- on stderr
@@ -566,14 +593,15 @@ static inline int elbo_lead(int max_iter) { return std::max(1, std::min(ELBO_LEA
 struct ElboLoop {
     int iters = 0, converged = 0;
     double last3[3] = {0.0, 0.0, 0.0};
-    bool enter(double e, int max_iter)             // the ELBO of the next sweep; true: the loop goes on
+    // the ELBO of the next sweep; true: the loop goes on.  forced (GPRN_BATCH_FORCED): the stop rule is not applied
+    bool enter(double e, int max_iter, bool forced = false)
     {
         if (iters == 0) {
             last3[1] = e; last3[2] = e;
             if (max_iter == 0) return false;
         } else { last3[0] = last3[1]; last3[1] = last3[2]; last3[2] = e; }
         iters += 1;
-        if (iters > 3 && elbo_stop_rule(last3[0], last3[1], last3[2])) { converged = 1; return false; }
+        if (!forced && iters > 3 && elbo_stop_rule(last3[0], last3[1], last3[2])) { converged = 1; return false; }
         return iters < max_iter;
     }
 };

@@ -17,6 +17,9 @@
 //   k_grad_contract_b<FD>    < G, dK/dtheta_l > for all parameters of all latent GPs: 64 x 64 lower blocks, grid.y = latent GP
 //   k_grad_final             the blocks' partial sums in a fixed order (no floating-point atomics: two calls, same bits)
 //   k_grad_matrix_full       G itself, symmetric, for kernels the caller differentiates (gprn_grad_matrix)
+//
+// grad_batch_pass runs the same steps over the evaluations of a batch's chunk (gprn_elbocalc_batch_grad): slots = evaluations
+// x latent GPs in every launch's batch dimension, so the number of launches does not depend on the number of evaluations.
 #include "api_internal.h"
 #include "fill_eval.h"
 #include "grad_elem.h"
@@ -52,11 +55,16 @@ __device__ __forceinline__ double grad_block_sum(double v, double* sh /* 4 */)
 // For node j = j0 + blockIdx.z: tab[z][2] <- sum_{k<j} Sigma_fk, Sigma_fk = S_k^-1 (I - B_k^-1) S_k^-1 (k_sigma's expression; node
 // precisions are strictly positive whenever q >= 2), and tab[z][0] <- K_j^-1 mirrored to a full matrix from tab[z][1] (lower);
 // both ld x ld with zero padding.  node_tab: the node phase's pointer table (BUF_B = lower(B_k^-1)); s: the node slots' sqrt(d).
+// BATCH (gprn_elbocalc_batch_grad): z = evaluation e * (q - 1) + (j - 1); node_tab holds G rows per evaluation (slot = e G + gp)
+// and s_tab that slot's sqrt(d).
+template <bool BATCH>
 __global__ __launch_bounds__(256)
 void k_grad_cross_prep(double* const* __restrict__ tab, double* const* __restrict__ node_tab, const double* __restrict__ s,
-                       int j0, int N, int ld)
+                       int j0, int N, int ld, double* const* __restrict__ s_tab = nullptr, int q = 0, int G = 0)
 {
-    const int n = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y, z = blockIdx.z, j = j0 + z;
+    const int n = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y, z = blockIdx.z;
+    const int j = BATCH ? 1 + z % (q - 1) : j0 + z;
+    const size_t slot0 = BATCH ? (size_t)(z / (q - 1)) * G : 0;      // the evaluation's node 0
     if (n >= ld) return;
     double* const Kf = tab[(size_t)z * GPRN_NBUF + 0];
     const double* const Kl = tab[(size_t)z * GPRN_NBUF + 1];
@@ -65,8 +73,8 @@ void k_grad_cross_prep(double* const* __restrict__ tab, double* const* __restric
     if (m < N && n < N) {
         const int hi = m > n ? m : n, lo = m > n ? n : m;
         for (int k = 0; k < j; ++k) {
-            const double* Binv = node_tab[(size_t)k * GPRN_NBUF + BUF_B];
-            const double* sk = s + (size_t)k * ld;
+            const double* Binv = node_tab[(slot0 + k) * GPRN_NBUF + BUF_B];
+            const double* sk = BATCH ? s_tab[slot0 + k] : s + (size_t)k * ld;
             sum += ((m == n ? 1.0 : 0.0) - Binv[(size_t)hi * ld + lo]) / (sk[m] * sk[n]);
         }
         kv = Kl[(size_t)hi * ld + lo];
@@ -113,19 +121,21 @@ void k_lower_tmatvec_reduce(const double* __restrict__ part, int N, int ld, int 
 
 // r[g][i] = m_g[i] - sum_c K_g[i][c] a_g[c] (i < N; zero in the padding), m_g = row g of the state: the residual of a = K^-1 m
 // against the prior matrix itself (full, symmetric, nugget included: what the set-up factored).  One wave per row,
-// grid ((N + 3) / 4, G)
+// grid ((N + 3) / 4, G).  BATCH: g is a slot of a batch -- row slot_gp[g] of the state of the slot's evaluation (ev)
+template <bool BATCH>
 __global__ __launch_bounds__(256)
 void k_grad_residual(double* const* __restrict__ Ks, const double* __restrict__ mu, const double* __restrict__ a, int N, int ld,
-                     double* __restrict__ r)
+                     double* __restrict__ r, const int* __restrict__ slot_gp = nullptr, EvalMap ev = EvalMap{nullptr, 0, 0, 0, 0})
 {
     const int g = blockIdx.y, i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= N) return;
     const double* Kr = Ks[g] + (size_t)i * ld;
     const double* ag = a + (size_t)g * ld;
+    const double* mg = BATCH ? mu + ev_of(ev, g) * ev.state + (size_t)slot_gp[g] * N : mu + (size_t)g * N;
     double acc = 0.0;
     for (int c = lane; c < N; c += 64) acc += Kr[c] * ag[c];
     acc = grad_wave_sum(acc);
-    if (lane == 0) r[(size_t)g * ld + i] = mu[(size_t)g * N + i] - acc;
+    if (lane == 0) r[(size_t)g * ld + i] = mg[i] - acc;
 }
 
 // part[(g * pmax + l) * nblk + blk] = sum over the elements (m, n), n <= m, of the 64 x 64 lower block blk of
@@ -293,6 +303,16 @@ struct GradWork {
     std::vector<double*> cross;             // per node: the cross term (null for node 0 and for nodes not asked for)
 };
 
+// the kernel's part of a slot: the program at `params`, which derivative applies (gprn_grad_kernel's rules), where its sums go
+static void grad_slot_kernel(const KernelSpec& ks, const double* params, int out_off, GradSlot* s)
+{
+    fill_program_with(ks, params, &s->pg);
+    const int kid = (ks.n_ops == 1 && ks.ops[0] == GPRN_OP_PUSH && ks.ops[2] == 0) ? ks.ops[1] : -1;
+    const bool closed = kid == GPRN_K_SE || kid == GPRN_K_PERIODIC || kid == GPRN_K_QP;
+    s->mode = closed ? 0 : 1;
+    s->kid = kid; s->n_params = ks.n_params; s->out_off = out_off;
+}
+
 static int grad_checks(gprn_ctx* c, const char* what)
 {
     if (c->world > 1 || c->comm || c->shm) {
@@ -344,8 +364,8 @@ static int grad_prelude(gprn_ctx* c, CallScratch& scr, int only_gp, GradWork& w)
         double** d_p = nullptr;
         TRY(scr.table(&d_p, rows));
         prof_begin(c, GPRN_T_VEC);
-        hipLaunchKernelGGL(k_grad_cross_prep, dim3((ld + 255) / 256, ld, nj), dim3(256), 0, c->stream, (double* const*)d_p,
-                           (double* const*)c->tab_node, (const double*)c->d_s, j0, N, ld);
+        hipLaunchKernelGGL(k_grad_cross_prep<false>, dim3((ld + 255) / 256, ld, nj), dim3(256), 0, c->stream, (double* const*)d_p,
+                           (double* const*)c->tab_node, (const double*)c->d_s, j0, N, ld, (double* const*)nullptr, 0, 0);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         std::vector<TileTask> tasks;
@@ -385,8 +405,9 @@ static int grad_prelude(gprn_ctx* c, CallScratch& scr, int only_gp, GradWork& w)
             TRY(vec_lower_matvec(c, weights, BUF_KLINV, c->d_mu, N, 1, w.u + (size_t)q * ld));
         } else {
             prof_begin(c, GPRN_T_VEC);
-            hipLaunchKernelGGL(k_grad_residual, dim3((N + 3) / 4, G), dim3(256), 0, c->stream, (double* const*)d_k,
-                               (const double*)c->d_mu, (const double*)w.a, N, ld, resid);
+            hipLaunchKernelGGL(k_grad_residual<false>, dim3((N + 3) / 4, G), dim3(256), 0, c->stream, (double* const*)d_k,
+                               (const double*)c->d_mu, (const double*)w.a, N, ld, resid, (const int*)nullptr,
+                               EvalMap{nullptr, 0, 0, 0, 0});
             prof_end(c);
             HIP_TRY(c, hipGetLastError());
             TRY(vec_lower_matvec(c, nodes, BUF_KLINV, resid, ld, 0, w.u));
@@ -434,13 +455,9 @@ extern "C" int gprn_grad_elbo(gprn_ctx* c, double* grad_out, int n_out)
         s.Binv = c->wsB[g]; s.s = c->d_s + (size_t)g * ld; s.a = w.a + (size_t)g * ld;
         s.cross = g < q ? w.cross[g] : nullptr;
         if (ks.uploaded) continue;
-        fill_program_with(ks, ks.params, &s.pg);
-        const int kid = (ks.n_ops == 1 && ks.ops[0] == GPRN_OP_PUSH && ks.ops[2] == 0) ? ks.ops[1] : -1;
-        const bool closed = kid == GPRN_K_SE || kid == GPRN_K_PERIODIC || kid == GPRN_K_QP;
-        s.mode = closed ? 0 : 1;
-        s.kid = kid; s.n_params = ks.n_params; s.out_off = off;
+        grad_slot_kernel(ks, ks.params, off, &s);
         off += ks.n_params;
-        if (closed) pmax = std::max(pmax, 4);          // (k_grad_contract_b's closed forms write four sums)
+        if (s.mode == 0) pmax = std::max(pmax, 4);     // (k_grad_contract_b's closed forms write four sums)
     }
     const int nb = ld / 64, nblk = nb * (nb + 1) / 2;
     GradSlot* d_slots = nullptr;
@@ -492,5 +509,193 @@ extern "C" int gprn_grad_matrix(gprn_ctx* c, int gp, double* G_out)
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     HIP_TRY(c, hipMemcpy2D(G_out, (size_t)N * sizeof(double), d_G, (size_t)ld * sizeof(double), (size_t)N * sizeof(double), N,
                            hipMemcpyDeviceToHost));
+    return GPRN_OK;
+}
+
+// ------------------------------------------------------------------ many evaluations (gprn_elbocalc_batch_grad)
+// what the kernels of one latent GP ask of the contraction's partial sums: total parameters, widest row of `part`
+static void grad_batch_counts(const std::vector<KernelSpec>& kspec, int* total, int* pmax)
+{
+    *total = 0; *pmax = 1;
+    GradSlot probe;
+    for (const KernelSpec& ks : kspec) {
+        grad_slot_kernel(ks, ks.params, 0, &probe);
+        *total += ks.n_params;
+        *pmax = std::max(*pmax, probe.mode == 0 ? std::max(4, ks.n_params) : ks.n_params);
+    }
+}
+
+// device bytes of the pass's scratch per evaluation: a, u, the residual, the column partial sums, the blocks' partial sums,
+// three ld x ld matrices per node j >= 1, the slots and the tables
+static size_t grad_batch_bytes(const GradBatchIn& in, int total, int pmax)
+{
+    const size_t ld = in.ld, nn = ld * ld, G = in.G, nb = ld / 64, nblk = nb * (nb + 1) / 2;
+    return (G * ld * (3 + (size_t)in.T) + G * pmax * nblk + total + 3 * (size_t)(in.q - 1) * nn) * sizeof(double) +
+           G * (sizeof(GradSlot) + (GPRN_NBUF + 3) * sizeof(double*) + 2 * sizeof(int)) + (size_t)(in.q - 1) * GPRN_NBUF * sizeof(double*) +
+           256 * 11;                                         // (each piece is rounded up to 256 bytes; the task list is per group)
+}
+
+// evaluations [e0, e0 + ne) of the pass; the scratch grows before the first launch (GPRN_E_NOMEM: nothing has run)
+static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const GradBatchIn& in, int e0, int ne, int total,
+                            int pmax)
+{
+    const int N = in.N, ld = in.ld, T = in.T, q = in.q, G = in.G;
+    const size_t nn = (size_t)ld * ld, nslots = (size_t)ne * G, nj = (size_t)ne * (q - 1);
+    const int nb = ld / 64, nblk = nb * (nb + 1) / 2;
+    hipStream_t st = w->stream;
+    std::vector<double> h((size_t)ne * total);
+    // grad_prelude's pair of task lists for the cross terms: C1 = -K_j^-1 S in full, then the lower tiles of P = -C1 K_j^-1
+    std::vector<TileTask> tasks;
+    size_t n1 = 0;
+    if (nj) {
+        auto toff = [&](int ti, int tj) { return ((int64_t)ti * GPRN_TILE) * ld + (int64_t)tj * GPRN_TILE; };
+        for (int i = 0; i < T; ++i)
+            for (int j = 0; j < T; ++j)
+                tasks.push_back(TileTask{toff(i, j), toff(i, 0), toff(0, j), ld, 3, 0, 2, tile_modes(CM_SETNEG, 0, 1)});
+        n1 = tasks.size();
+        for (int i = 0; i < T; ++i)
+            for (int j = 0; j <= i; ++j)
+                tasks.push_back(TileTask{toff(i, j), toff(i, 0), toff(0, j), ld, 2, 3, 0, tile_modes(CM_SETNEG, 0, 1)});
+    }
+    // tables, one block: rows [nslots][GPRN_NBUF] | chol(K)^-1 [nslots] | K [nslots] | s [nslots] | cross rows [nj][GPRN_NBUF];
+    // slot -> latent GP [nslots] | slot -> index of its evaluation's state [nslots]
+    const size_t o_kl = nslots * GPRN_NBUF, o_k = o_kl + nslots, o_s = o_k + nslots, o_cp = o_s + nslots, n_ptr = o_cp + nj * GPRN_NBUF;
+    // ONE piece of device memory, kept with the context from call to call (gprn_ctx::grad_scratch: an allocation and its
+    // release cost more than the pass's launches at small N) and carved up here; it only grows, before anything is enqueued
+    size_t need = 0;
+    auto carve = [&need](size_t bytes) { const size_t at = need; need += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t at_u = carve(nslots * ld * sizeof(double)), at_a = carve(nslots * ld * sizeof(double)),
+                 at_resid = carve(nslots * ld * sizeof(double)), at_tpart = carve(nslots * T * ld * sizeof(double)),
+                 at_part = carve(nslots * pmax * nblk * sizeof(double)), at_out = carve((size_t)ne * total * sizeof(double)),
+                 at_cross = carve(3 * nj * nn * sizeof(double)), at_ptr = carve(n_ptr * sizeof(double*)),
+                 at_int = carve(2 * nslots * sizeof(int)), at_slots = carve(nslots * sizeof(GradSlot)),
+                 at_tasks = carve(tasks.size() * sizeof(TileTask));
+    if (w->grad_scratch_bytes < need) {
+        HIP_TRY(w, hipStreamSynchronize(st));
+        if (w->grad_scratch) hipFree(w->grad_scratch);
+        w->grad_scratch = nullptr; w->grad_scratch_bytes = 0;
+        char* fresh = nullptr;
+        TRY(dev_alloc(w, &fresh, need));
+        w->grad_scratch = fresh; w->grad_scratch_bytes = need;
+    }
+    char* const base = (char*)w->grad_scratch;
+    double* const u = (double*)(base + at_u); double* const a = (double*)(base + at_a);
+    double* const resid = (double*)(base + at_resid); double* const tpart = (double*)(base + at_tpart);
+    double* const part = (double*)(base + at_part); double* const d_out = (double*)(base + at_out);
+    double* const cross = (double*)(base + at_cross);
+    double** const d_ptr = (double**)(base + at_ptr);
+    int* const d_int = (int*)(base + at_int);
+    GradSlot* const d_slots = (GradSlot*)(base + at_slots);
+    TileTask* const d_t = (TileTask*)(base + at_tasks);
+    TRY(ensure_tasks(w, T));
+    std::vector<double*> hp(n_ptr, nullptr);
+    std::vector<int> hi(2 * nslots);
+    std::vector<GradSlot> slots(nslots);
+    for (int e = 0; e < ne; ++e) {
+        const int ev = e0 + e;
+        const double* kp = in.kparams[ev];
+        int off = 0;
+        for (int g = 0; g < G; ++g) {
+            const size_t sl = (size_t)e * G + g;
+            double* const* row = in.rows.data() + ((size_t)ev * G + g) * GPRN_NBUF;
+            for (int b = 0; b < GPRN_NBUF; ++b) hp[sl * GPRN_NBUF + b] = row[b];
+            hp[o_kl + sl] = row[BUF_KLINV];
+            hp[o_k + sl] = row[BUF_K];
+            hp[o_s + sl] = in.s[(size_t)ev * G + g];
+            hi[sl] = g;
+            hi[nslots + sl] = in.state_idx[ev];
+            double* cr = nullptr;
+            if (g >= 1 && g < q) {
+                const size_t z = (size_t)e * (q - 1) + (g - 1);
+                double** cp = hp.data() + o_cp + z * GPRN_NBUF;
+                cp[0] = cross + (3 * z) * nn; cp[1] = in.kinv[(size_t)ev * (q - 1) + (g - 1)];
+                cp[2] = cross + (3 * z + 1) * nn; cp[3] = cross + (3 * z + 2) * nn;
+                cr = cp[2];
+            }
+            GradSlot& s = slots[sl];
+            memset(&s, 0, sizeof(s));
+            grad_slot_kernel(kspec[g], kp + off, e * total + off, &s);
+            s.Binv = row[BUF_B]; s.s = in.s[(size_t)ev * G + g]; s.a = a + sl * ld; s.cross = cr;
+            off += kspec[g].n_params;
+        }
+    }
+    // (the host side of these copies lives to the end of the function, which waits for the stream on every path)
+    struct WaitOnExit { hipStream_t s; ~WaitOnExit() { hipStreamSynchronize(s); } } wait_{st};
+    HIP_TRY(w, hipMemcpyAsync(d_ptr, hp.data(), n_ptr * sizeof(double*), hipMemcpyHostToDevice, st));
+    HIP_TRY(w, hipMemcpyAsync(d_int, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(w, hipMemcpyAsync(d_slots, slots.data(), nslots * sizeof(GradSlot), hipMemcpyHostToDevice, st));
+    if (nj) HIP_TRY(w, hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, st));
+    const Phase ph{d_ptr, d_int, (int)nslots, 0, nullptr, EvalMap{d_int + nslots, in.state_stride, 0, 0, 0}, N, ld, T};
+    // (1) lower(B^-1) = lower(X^T X) of every slot into its B workspace
+    TRY(lauum_lower(w, ph));
+    // (2) the cross terms of every (evaluation, node j >= 1): grad_prelude's pair of task lists, batch = nj
+    if (nj) {
+        prof_begin(w, GPRN_T_VEC);
+        hipLaunchKernelGGL(k_grad_cross_prep<true>, dim3((ld + 255) / 256, ld, (unsigned)nj), dim3(256), 0, st,
+                           (double* const*)(d_ptr + o_cp), (double* const*)d_ptr, (const double*)nullptr, 0, N, ld,
+                           (double* const*)(d_ptr + o_s), q, G);
+        prof_end(w);
+        HIP_TRY(w, hipGetLastError());
+        TRY(launch_tiles(w, d_t, n1, d_ptr + o_cp, (int)nj, ld, GPRN_T_UPDATE));
+        TRY(launch_tiles(w, d_t + n1, tasks.size() - n1, d_ptr + o_cp, (int)nj, ld, GPRN_T_UPDATE));
+    }
+    // (3) a = L_K^-T L_K^-1 m and one refinement step, per slot
+    HIP_TRY(w, hipMemsetAsync(resid, 0, nslots * ld * sizeof(double), st));
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 0) TRY(vec_lower_matvec(w, ph, BUF_KLINV, in.state, N, 1, u));
+        else {
+            prof_begin(w, GPRN_T_VEC);
+            hipLaunchKernelGGL(k_grad_residual<true>, dim3((N + 3) / 4, (unsigned)nslots), dim3(256), 0, st,
+                               (double* const*)(d_ptr + o_k), in.state, (const double*)a, N, ld, resid, (const int*)d_int, ph.ev);
+            prof_end(w);
+            HIP_TRY(w, hipGetLastError());
+            TRY(vec_lower_matvec(w, ph, BUF_KLINV, resid, ld, 0, u));
+        }
+        prof_begin(w, GPRN_T_VEC);
+        hipLaunchKernelGGL(k_lower_tmatvec_partial, dim3(ld / 64, T, (unsigned)nslots), dim3(256), 0, st,
+                           (double* const*)(d_ptr + o_kl), (const double*)u, N, ld, T, tpart);
+        hipLaunchKernelGGL(k_lower_tmatvec_reduce, dim3((ld + 255) / 256, (unsigned)nslots), dim3(256), 0, st, (const double*)tpart,
+                           N, ld, T, pass, a);
+        prof_end(w);
+        HIP_TRY(w, hipGetLastError());
+    }
+    // (4) the contraction and its fixed-order sums, grid y = slot
+    bool any_closed = false, any_fd = false;
+    for (int g = 0; g < G; ++g) { any_closed = any_closed || slots[g].mode == 0; any_fd = any_fd || slots[g].mode == 1; }
+    prof_begin(w, GPRN_T_VEC);
+    if (any_closed)
+        hipLaunchKernelGGL(k_grad_contract_b<false>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+                           N, ld, nblk, pmax, part);
+    if (any_fd)
+        hipLaunchKernelGGL(k_grad_contract_b<true>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+                           N, ld, nblk, pmax, part);
+    hipLaunchKernelGGL(k_grad_final, dim3(pmax, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, (const double*)part,
+                       nblk, pmax, d_out);
+    prof_end(w);
+    HIP_TRY(w, hipGetLastError());
+    HIP_TRY(w, hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(w, hipStreamSynchronize(st));
+    for (int e = 0; e < ne; ++e) memcpy(in.out[e0 + e], h.data() + (size_t)e * total, (size_t)total * sizeof(double));
+    return GPRN_OK;
+}
+
+int grad_batch_pass(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const GradBatchIn& in, size_t budget)
+{
+    if (!in.n) return GPRN_OK;
+    int total = 0, pmax = 1;
+    grad_batch_counts(kspec, &total, &pmax);
+    if (!total) return GPRN_OK;
+    const size_t per = grad_batch_bytes(in, total, pmax);
+    // (a launch's grid y or z is the number of slots of the group: far below its 65 535 limit)
+    int group = (int)std::max<size_t>(1, std::min<size_t>(budget / per, (size_t)32768 / in.G));
+    for (int e0 = 0; e0 < in.n;) {
+        const int ne = std::min(group, in.n - e0);
+        const int rc = grad_batch_group(w, kspec, in, e0, ne, total, pmax);
+        if (rc == GPRN_E_NOMEM && ne > 1) { group = (ne + 1) / 2; w->err.clear(); continue; }   // (nothing of the group has run)
+        if (rc == GPRN_E_NOMEM)
+            w->err = "elbocalc_batch_grad: out of device memory for the gradient pass of one evaluation (" + w->err + ")";
+        if (rc) return rc;
+        e0 += ne;
+    }
     return GPRN_OK;
 }

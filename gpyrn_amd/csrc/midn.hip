@@ -17,6 +17,12 @@
 // meanfield.py:640-643 is applied per evaluation on the host, and an evaluation that has stopped leaves the tables of the
 // next sweep (its slots are compacted away: the launches shrink with the number of evaluations still running).
 // Lists longer than the memory budget (option "batch_mem_mb") run chunk by chunk.
+//
+// With gradients asked for (gprn_elbocalc_batch_grad) a chunk ends with grad.hip's batched pass over its evaluations: X, the
+// state and the prior's factors of an evaluation stay where its last sweep left them, but the per-slot vectors are indexed by
+// the slot of the ACTIVE tables, which later sweeps of the others reuse -- so s = sqrt(d) of every running evaluation is kept
+// per (evaluation, latent GP) behind each group of sweeps (k_mid_keep_s: reads only, the values' bits do not change).  The pass's
+// scratch is an allocation of its own (gprn_ctx::grad_scratch of the worker) that takes what the slabs left of the budget.
 #include "api_internal.h"
 
 #include <math.h>
@@ -30,6 +36,17 @@
 #include <vector>
 
 
+// keep[(evaluation, latent GP)] <- s of the phase's slots.  grid (slots of the phase)
+__global__ __launch_bounds__(256)
+void k_mid_keep_s(const double* __restrict__ s, const int* __restrict__ slot_gp, const int* __restrict__ slot_eval, int G, int ld,
+                  double* __restrict__ keep)
+{
+    const int slot = blockIdx.x;
+    const double* src = s + (size_t)slot * ld;
+    double* dst = keep + ((size_t)slot_eval[slot] * G + slot_gp[slot]) * ld;
+    for (int n = threadIdx.x; n < ld; n += 256) dst[n] = src[n];
+}
+
 struct MidBatch {
     gprn_ctx* w = nullptr;            // the worker context
     int cap = 0;                      // evaluations the slabs hold
@@ -37,6 +54,7 @@ struct MidBatch {
     double *K = nullptr, *KL = nullptr, *Bw = nullptr, *Xw = nullptr;   // [cap][G][ld * ld]
     double *Kinv = nullptr;           // [cap][q - 1][ld * ld]: K_j^-1 (lower), j = 1 .. q - 1
     double *q1_scratch = nullptr;     // [cap q (q - 1) / 2][ld]
+    double *keep_s = nullptr;         // [cap][G][ld]: s of each evaluation's last sweep, there from the first call that asks for gradients
     char* programs = nullptr;         // [cap][G] fill programs
     // device tables, one allocation: pointers first, then ints
     double** d_ptr_block = nullptr;   // kptr [cap G] | kptr2 [cap G] | tab_setup [cap G][4] | tab_kinv [cap (q-1)][4] | tab_node [cap q][4] | tab_weight [cap qp][4]
@@ -50,9 +68,9 @@ struct MidBatch {
 
 static void mid_free_slabs(MidBatch* m)
 {
-    void* dev[] = {m->K, m->KL, m->Bw, m->Xw, m->Kinv, m->q1_scratch, m->programs, m->d_ptr_block, m->d_int_block};
+    void* dev[] = {m->K, m->KL, m->Bw, m->Xw, m->Kinv, m->q1_scratch, m->keep_s, m->programs, m->d_ptr_block, m->d_int_block};
     for (void* ptr : dev) if (ptr) hipFree(ptr);
-    m->K = m->KL = m->Bw = m->Xw = m->Kinv = m->q1_scratch = nullptr;
+    m->K = m->KL = m->Bw = m->Xw = m->Kinv = m->q1_scratch = m->keep_s = nullptr;
     m->programs = nullptr; m->d_ptr_block = nullptr; m->d_int_block = nullptr;
     if (m->pin_in) hipHostFree(m->pin_in);
     if (m->pin_out) hipHostFree(m->pin_out);
@@ -313,6 +331,11 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
     std::vector<int> act(B);
     for (int b = 0; b < B; ++b) { act[b] = b; io.elbo[b] = 0.0; io.iters[b] = 0; io.conv[b] = 0; io.info[b] = 0; }
     std::vector<ElboLoop> loops(B);
+    const bool forced = (io.flags & GPRN_BATCH_FORCED) != 0;
+    // gradients: s of every (evaluation, latent GP) as its last sweep left it (G ld doubles per evaluation beside the slabs)
+    if (io.grad_out && !m->keep_s) TRY(dev_alloc(c, &m->keep_s, (size_t)m->cap * G * m->ld));
+    double* const keep_s = io.grad_out ? m->keep_s : nullptr;
+    int trips = 0;                                       // (forced: every running evaluation has made this many)
     double* const out_h = (double*)m->pin_out;
     int* const info_h = (int*)(out_h + (size_t)ELBO_LEAD * m->cap * 4);
     bool tables_stale = true, first = true;
@@ -324,9 +347,21 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
         // the rule, the next sweep's first launches), and the device goes from one sweep into the next.  A warm-started
         // evaluation -- nELBO's case -- usually stops right there.  Later trips go one by one: each may be an
         // evaluation's last, and its state must stay what that trip left.
-        const int lead = first ? elbo_lead(io.max_iter) : 1;
+        // (forced: nothing but a failed pivot ends a loop early, so every group goes out ahead)
+        const int lead = first ? elbo_lead(io.max_iter) : (forced ? std::max(1, std::min(ELBO_LEAD, io.max_iter - trips)) : 1);
         HIP_TRY(w, hipMemsetAsync(w->d_info + (size_t)w->nslot, 0, 2 * (size_t)w->nslot * sizeof(int), st));
         for (int sw = 0; sw < lead; ++sw) TRY(mid_sweep(w, m, nA, w->d_out + (size_t)sw * m->cap * 4));
+        trips += lead;
+        if (keep_s) {
+            prof_begin(w, GPRN_T_VEC);
+            for (int wt = 0; wt < 2; ++wt) {
+                const Phase ph = mid_phase(w, m, wt != 0, nA);
+                hipLaunchKernelGGL(k_mid_keep_s, dim3(ph.nslots), dim3(256), 0, st, (const double*)(w->d_s + (size_t)ph.slot0 * ph.ld),
+                                   ph.slot_gp, ph.ev.slot_eval, G, ph.ld, keep_s);
+            }
+            prof_end(w);
+            HIP_TRY(w, hipGetLastError());
+        }
         HIP_TRY(c, hipMemcpyAsync(out_h, w->d_out, (size_t)lead * m->cap * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipMemcpyAsync(info_h, w->d_info, 3 * (size_t)w->nslot * sizeof(int), hipMemcpyDeviceToHost, st));
         us_enqueue += t.lap();
@@ -358,7 +393,7 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
                     go_on = false;
                     break;
                 }
-                go_on = loop.enter(e, io.max_iter);
+                go_on = loop.enter(e, io.max_iter, forced);
                 io.elbo[b] = e; io.iters[b] = loop.iters; io.conv[b] = loop.converged;
             }
             if (go_on) next.push_back(b);
@@ -380,10 +415,39 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
             memcpy(io.var_out, io.var, (size_t)B * d * sizeof(double));
         }
     }
+    const double us_states = t.lap();
+    if (io.grad_out) {
+        // ---- the gradient of every evaluation's last committed sweep (grad.hip), over the full chunk in the set-up's order;
+        // an evaluation whose pivot failed gets a row of zeros
+        const size_t nn = (size_t)m->ld * m->ld;
+        GradBatchIn in;
+        in.N = N; in.ld = m->ld; in.T = w->T; in.q = q; in.G = G; in.t = w->d_time;
+        in.state = w->d_mu; in.state_stride = d;
+        for (int b = 0; b < B; ++b) {
+            double* const row = io.grad_out + (size_t)b * io.n_kpar;
+            if (io.info[b] > 0) { for (int k = 0; k < io.n_kpar; ++k) row[k] = 0.0; continue; }
+            for (int g = 0; g < G; ++g) {
+                const size_t s = (size_t)b * G + g;
+                double* r4[GPRN_NBUF];
+                r4[BUF_B] = m->Bw + s * nn; r4[BUF_X] = m->Xw + s * nn; r4[BUF_K] = m->K + s * nn; r4[BUF_KLINV] = m->KL + s * nn;
+                in.rows.insert(in.rows.end(), r4, r4 + GPRN_NBUF);
+                in.s.push_back(keep_s + s * m->ld);
+            }
+            for (int j = 1; j < q; ++j) in.kinv.push_back(m->Kinv + ((size_t)b * (q - 1) + (j - 1)) * nn);
+            in.state_idx.push_back(b);
+            in.kparams.push_back(io.kparams + (size_t)b * io.n_kpar);
+            in.out.push_back(row);
+            in.n += 1;
+        }
+        // (its scratch gets what the slabs left of the budget; one evaluation's worth at the least)
+        const size_t budget = batch_budget_bytes(c), slabs = (size_t)m->cap * mid_bytes_per_eval(c);
+        TRY(grad_batch_pass(w, c->kspec, in, budget > slabs ? budget - slabs : 0));
+    }
+    const double us_grad = t.lap();
     if (batch_timers_on())
         fprintf(stderr, "[gprn] elbocalc_batch (N = %d, T = %d), %d evaluations, us: staging %.0f | set-up enqueued %.0f | %d sweeps: enqueue %.0f, "
-                        "waiting for the device %.0f, verdicts %.0f | states back %.0f | total %.0f\n", N, w->T, B, us_stage, us_setup, n_sweeps,
-                us_enqueue, us_wait, us_host, t.lap(), t.total());
+                        "waiting for the device %.0f, verdicts %.0f | states back %.0f | gradient pass %.0f | total %.0f\n", N, w->T, B, us_stage, us_setup, n_sweeps,
+                us_enqueue, us_wait, us_host, us_states, us_grad, t.total());
     return GPRN_OK;
 }
 

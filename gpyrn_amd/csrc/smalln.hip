@@ -296,7 +296,8 @@ __device__ __forceinline__ void small_loglike(const SmallTailArgs& a, double* sh
     t3 = sm_block_sum(t3, sh4);
 }
 
-template <int T, bool MASKED = false>
+// FORCED (GPRN_BATCH_FORCED): the stop rule is not applied -- max_iter committed trips, converged = 0
+template <int T, bool MASKED = false, bool FORCED = false>
 __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
 {
     __shared__ __attribute__((aligned(16))) double lds[SMALL_MMA_DOUBLES];
@@ -412,7 +413,7 @@ __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
                 a.last3[0] = e0; a.last3[1] = e1; a.last3[2] = e2;
                 a.ctl[1] = a.sweep;
                 bool stop = false;
-                if (a.sweep > 3) {
+                if (!FORCED && a.sweep > 3) {
                     const double mean = __ddiv_rn(__dadd_rn(__dadd_rn(e0, e1), e2), 3.0);
                     const double d0 = __dsub_rn(e0, mean), d1 = __dsub_rn(e1, mean), d2 = __dsub_rn(e2, mean);
                     const double var3 = __ddiv_rn(__dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2)), 3.0);
@@ -488,13 +489,13 @@ void k_small_tail(SmallTailArgs a) { small_tail_body<T>(a); }
 template <int T>
 __global__ __launch_bounds__(256)
 void k_small_tail_m(SmallTailArgs a) { small_tail_body<T, true>(a); }
-template <int T>
+template <int T, bool FORCED = false>
 __global__ __launch_bounds__(256)
 void k_small_tail_b(const SmallTailArgs* __restrict__ lanes, int sweep, int hist_at, int max_iter)
 {
     SmallTailArgs a = lanes[blockIdx.y];
     a.sweep = sweep; a.hist_at = hist_at; a.max_iter = max_iter;
-    small_tail_body<T>(a);
+    small_tail_body<T, false, FORCED>(a);
 }
 
 template <int T, bool ACC>
@@ -619,11 +620,16 @@ void small_batch_free(gprn_ctx* c)
 
 // evaluations one chunk may hold: what the memory budget pays for (4 G + q matrices of ld^2 doubles each and small change
 // per evaluation), 16 at least -- an emcee run with thousands of walkers is split, not refused
-static int small_batch_chunk(gprn_ctx* c)
+static size_t small_bytes_per_eval(const gprn_ctx* c)
 {
     const size_t nn = (size_t)c->ld * c->ld, d = (size_t)(c->p + 1) * c->q * c->N;
-    const size_t per = ((4 * (size_t)c->G + c->q) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256) * sizeof(double) +
-                       (size_t)c->G * fill_program_bytes() * 2;
+    return ((4 * (size_t)c->G + c->q) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256) * sizeof(double) +
+           (size_t)c->G * fill_program_bytes() * 2;
+}
+
+static int small_batch_chunk(gprn_ctx* c)
+{
+    const size_t per = small_bytes_per_eval(c);
     return (int)std::max<size_t>(16, std::min<size_t>(batch_budget_bytes(c) / per, 32768));   // (grid y = evaluations)
 }
 
@@ -796,7 +802,10 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
             prof_end(c);
             TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B));
             prof_begin(c, GPRN_T_VEC);
-            hipLaunchKernelGGL(k_small_tail_b<1>, dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
+            if (io.flags & GPRN_BATCH_FORCED)
+                hipLaunchKernelGGL((k_small_tail_b<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
+            else
+                hipLaunchKernelGGL((k_small_tail_b<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
             prof_end(c);
         }
         HIP_TRY(c, hipGetLastError());
@@ -833,9 +842,41 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
             memcpy(io.var_out + (size_t)b * d, st_h + ((in_b ? 3 : 1) * (size_t)cap + b) * d, d * sizeof(double));
         }
     }
+    const double us_states = t.lap();
+    if (io.grad_out) {
+        // ---- the gradient of every evaluation's last committed sweep: grad.hip's batched pass over the B x G one-tile slots
+        // (T = 1).  A stopped evaluation's launches were no-ops: X, s and both copies of its state are its last trip's; that
+        // trip wrote copy B when odd.  An evaluation whose pivot failed gets a row of zeros.
+        const size_t nn = (size_t)c->ld * c->ld, nmat = 4 * (size_t)G + q;
+        GradBatchIn in;
+        in.N = c->N; in.ld = c->ld; in.T = 1; in.q = q; in.G = G; in.t = c->d_time;
+        in.state = m->state; in.state_stride = d;
+        for (int b = 0; b < B; ++b) {
+            double* const row = io.grad_out + (size_t)b * io.n_kpar;
+            if (info[b] > 0) { for (int k = 0; k < io.n_kpar; ++k) row[k] = 0.0; continue; }
+            double* const mb = m->mats + (size_t)b * nmat * nn;
+            for (int g = 0; g < G; ++g) {
+                double* r4[GPRN_NBUF];
+                r4[BUF_B] = mb + (2 * (size_t)G + g) * nn; r4[BUF_X] = mb + (3 * (size_t)G + g) * nn;
+                r4[BUF_K] = mb + (size_t)g * nn; r4[BUF_KLINV] = mb + ((size_t)G + g) * nn;
+                in.rows.insert(in.rows.end(), r4, r4 + GPRN_NBUF);
+                in.s.push_back(m->vecs + (size_t)b * 7 * G * c->ld + ((size_t)G + g) * c->ld);
+            }
+            for (int j = 1; j < q; ++j) in.kinv.push_back(mb + (4 * (size_t)G + j) * nn);
+            const bool in_b = iters[b] >= 1 && (iters[b] & 1);
+            in.state_idx.push_back((in_b ? 2 * cap : 0) + b);
+            in.kparams.push_back(io.kparams + (size_t)b * io.n_kpar);
+            in.out.push_back(row);
+            in.n += 1;
+        }
+        // (its scratch gets what the buffers left of the budget; one evaluation's worth at the least)
+        const size_t budget = batch_budget_bytes(c), held = (size_t)cap * small_bytes_per_eval(c);
+        TRY(grad_batch_pass(c, c->kspec, in, budget > held ? budget - held : 0));
+    }
+    const double us_grad = t.lap();
     if (batch_timers_on())
         fprintf(stderr, "[gprn] elbocalc_batch (one tile), %d evaluations, us: buffers %.0f | staging %.0f | enqueue %.0f | waiting for the device "
-                        "%.0f | verdicts %.0f | states back %.0f | total %.0f (%d launches of sweeps)\n", B, us_ensure, us_stage, us_enqueue,
-                us_wait, us_host, t.lap(), us_ensure + t.total(), s - (max_iter >= 1 ? 1 : 0));
+                        "%.0f | verdicts %.0f | states back %.0f | gradient pass %.0f | total %.0f (%d launches of sweeps)\n", B, us_ensure, us_stage,
+                us_enqueue, us_wait, us_host, us_states, us_grad, us_ensure + t.total(), s - (max_iter >= 1 ? 1 : 0));
     return GPRN_OK;
 }

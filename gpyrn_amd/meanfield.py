@@ -1043,13 +1043,42 @@ class inference:
     def _nELBO_batch_device(self, sets, max_iter):
         """``nELBO_batch`` through ``gprn_elbocalc_batch``, or None where that does not apply (larger problems, sharded
         objects, user-defined kernels, kernel expressions that change shape from one vector to the next, a data mask)."""
+        max_iter = 10000 if max_iter is None else int(max_iter)
+        start = time_module.time()
+        staged = self._batch_stage(sets)
+        if staged is None:
+            return None
+        ctx, kp, yr, jt, m0, v0 = staged
+        res = ctx.elbocalc_batch(kp, yr, jt, m0, v0, max_iter, want_state=True)
+        if res is None:
+            return None
+        elbo = self._batch_keep(res)[0]
+        took = 1e3 * (time_module.time() - start)
+        print(f'{len(sets)} ELBO evaluations side by side (took {took:5.2f} ms)' + 20 * ' ', end='\r', flush=True)
+        return [float(-e) for e in elbo]
+
+    def _batch_keep(self, res):
+        """What a side-by-side call leaves with the object: ``last_info``, and as the warm start of whatever comes next the
+        state of the last evaluation whose loop converged (meanfield.py:644-646).  Returns ``res``."""
+        info, conv, mu_f, var_f = res[3], res[2], res[4], res[5]
+        self.last_info = int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
+        done = np.flatnonzero(conv)
+        self._batch_last_done = int(done[-1]) if done.size else -1
+        if done.size:
+            self._mu, self._var = mu_f[done[-1]], var_f[done[-1]]
+        return res
+
+    def _batch_stage(self, sets, start=None):
+        """The B problems of a side-by-side call laid out for ``Context.elbocalc_batch``: ``(ctx, kernel_params (B, n_kpar),
+        y_resid (B, p N), jitters (B, p), mu (B, d), var (B, d))``, every evaluation starting from ``start`` = ``(mu, var)``,
+        else the stored state, else ``_initMuVar`` of its own parameters -- or None where the side-by-side form does not
+        apply.  The kernel programs go to the device; the object's parameters end at the last vector."""
         if self._comm is not None or self.N > self.batch_max_N or self.mask is not None:
             return None
         ctx = self._backend()
-        max_iter = 10000 if max_iter is None else int(max_iter)
         y_raw = np.concatenate(self.y)
-        start = time_module.time()
         B = len(sets)
+        state = (self._mu, self._var) if start is None else (np.asarray(start[0], dtype=float), np.asarray(start[1], dtype=float))
         # (set_parameters takes full-length vectors too, meanfield.py:223-259: the fast layout below wants them all alike)
         n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
         if any(x.ndim != 1 or x.size not in (n_free, n_all) for x in sets):
@@ -1071,7 +1100,7 @@ class inference:
         n_k = sum(k.pars.size for k in kernels)
         plain_kernels = all(sp[2].size == k.pars.size and np.array_equal(sp[2], k.pars) for sp, k in zip(specs, kernels))
         plain_means = all(m_ is None or type(m_) is meanfunc.Constant for m_ in means)
-        if plain_kernels and plain_means and self._mu is not None:
+        if plain_kernels and plain_means and state[0] is not None:
             # every program's parameters ARE its kernel's, the means are constants and the start is the stored state:
             # the B problems are slices of the B full parameter vectors (nodes, weights, means, jitters: meanfield.py:193-202)
             full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
@@ -1086,8 +1115,8 @@ class inference:
                     yr[:, i * self.N:(i + 1) * self.N] -= full[:, col:col + 1]
                     col += 1
             jt = full[:, n_k + n_m:]
-            m0 = np.tile(np.ravel(self._mu), (B, 1))
-            v0 = np.tile(np.ravel(self._var), (B, 1))
+            m0 = np.tile(np.ravel(state[0]), (B, 1))
+            v0 = np.tile(np.ravel(state[1]), (B, 1))
             self.set_parameters(sets[-1])
         else:
             kp, yr, jt, m0, v0 = [], [], [], [], []
@@ -1101,25 +1130,13 @@ class inference:
                 kp.append(np.concatenate([sp[2] for sp in specs]))
                 yr.append(y_raw - self._mean(means))
                 jt.append(np.asarray(jitters, dtype=float))
-                if self._mu is not None:
-                    mu, var = self._mu, self._var
+                if state[0] is not None:
+                    mu, var = state
                 else:
                     mu, var = self._initMuVar(nodes, weights, jitters)
                 m0.append(np.ravel(mu))
                 v0.append(np.ravel(var))
-        res = ctx.elbocalc_batch(np.array(kp), np.array(yr), np.array(jt), np.array(m0), np.array(v0), max_iter,
-                                 want_state=True)
-        if res is None:
-            return None
-        elbo, iters, conv, info, mu_f, var_f = res
-        self.last_info = int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
-        done = np.flatnonzero(conv)
-        self._batch_last_done = int(done[-1]) if done.size else -1
-        if done.size:                                      # the warm start of whatever comes next (meanfield.py:644-646)
-            self._mu, self._var = mu_f[done[-1]], var_f[done[-1]]
-        took = 1e3 * (time_module.time() - start)
-        print(f'{len(sets)} ELBO evaluations side by side (took {took:5.2f} ms)' + 20 * ' ', end='\r', flush=True)
-        return [float(-e) for e in elbo]
+        return ctx, np.array(kp), np.array(yr), np.array(jt), np.array(m0), np.array(v0)
 
     # ------------------------------------------------------------ gradients
     def grad_ELBO(self, mean_sweeps=8, mean_start=None, total=False, fused=False):
@@ -1336,6 +1353,117 @@ class inference:
         if not np.isfinite(elbo):
             return np.inf, np.zeros(int((~self.frozen_mask).sum()))
         return -elbo, -grad[~self.frozen_mask]
+
+    def _jitter_grads_batch(self, jitters, mu, var):
+        """``_grad_from_state``'s jitter entries for B states at once: ``jitters (B, p)``, ``mu`` / ``var (B, p + 1, q, N)``
+        -> ``(B, p)``, d ELBO / d jitter_i at fixed state (LogL = -1/2 sum [log(2 pi v) + ((Y - fit)^2 + A) / v],
+        v = jitter^2 + yerr^2; divided by q as the ELBO is, meanfield.py:709)."""
+        jitters = np.asarray(jitters, dtype=float)
+        mu, var = np.asarray(mu, dtype=float), np.asarray(var, dtype=float)
+        variance = jitters[:, :, None]**2 + self.yerr2[None]
+        fit = np.einsum('biqn,bqn->bin', mu[:, 1:], mu[:, 0])
+        mf2, vf = mu[:, :1]**2, var[:, :1]
+        A = np.sum(vf * mu[:, 1:]**2 + var[:, 1:] * mf2 + vf * var[:, 1:], axis=2)
+        dv = -0.5 * (1.0 / variance - ((self.y[None] - fit)**2 + A) / variance**2)
+        if self.mask is not None:
+            dv = np.where(self.mask[None], dv, 0.0)
+        return np.sum(dv, axis=2) * 2 * jitters / self.q
+
+    def nELBO_and_grad_batch(self, parameter_sets, max_iter=None, sweeps=None, start=None):
+        """
+        ``(values, grads)`` for several free-parameter vectors: ``values`` a list of ``-ELBO``, ``grads`` an array
+        ``(B, n_free)`` of ``-dELBO/d(free parameters)`` -- the objective and gradient a multi-start gradient optimiser or a
+        gradient-based ensemble sampler asks for, all vectors SIDE BY SIDE on the GPU (``gprn_elbocalc_batch_grad``).  Not
+        in the reference, whose optimiser is derivative-free (meanfield.py:1149-1150).
+
+        The gradient is the fixed-state one of ``grad_ELBO(mean_sweeps=0, fused=True)``, and value and gradient belong to the
+        SAME sweep, the last one of that vector's loop (no further sweep is run for the gradient):
+
+        * kernel hyper-parameters: the B-form on the device, ``1/(2q) < a a^T - S B^-1 S (+ the Q1 cross terms), dK/dtheta >``
+          at the state and factors that sweep left (quirks Q1, Q2 as in ``grad_ELBO``);
+        * jitters: closed form from each vector's returned state (``_grad_from_state``'s formula, vectorised);
+        * mean-function parameters: zero.  At a fixed variational state the reported ELBO does not see them -- the
+          reference's likelihood term reads the RAW data (quirk Q3) -- and because the update maximises a bound on the
+          mean-subtracted data while the ELBO is evaluated on the raw data, the state the sweeps converge to is not
+          stationary for it: the envelope theorem does not make their effect through the state vanish.  What
+          ``grad_ELBO(mean_sweeps > 0)`` adds by differences is not computed here.
+
+        ``sweeps=n`` (n >= 1): every vector runs exactly ``n`` forced sweeps -- no stop rule: a deterministic, smooth
+        function of the parameters -- from ``start`` = ``(mu, var)``, else the stored state, else ``_initMuVar``.  Without
+        ``sweeps``: the warm-started loop under the stop rule (``max_iter`` >= 1 trips at most), every vector from the state
+        the object holds, as ``nELBO_batch``; the object then keeps the state of the last vector whose loop converged
+        (``start`` without ``sweeps`` is a ``ValueError``).
+        A vector whose factorisation meets a non-positive pivot returns ``(inf, zeros)``.
+
+        Where the side-by-side form does not apply (user-defined kernels, N above ``batch_max_N``, a data mask, kernel
+        expressions that change shape between vectors) the vectors are evaluated one by one with the same meaning: the
+        loop, then ``gprn_grad_elbo`` on what it left.  Unsharded objects only.
+        """
+        if self._comm is not None:
+            raise NotImplementedError('nELBO_and_grad_batch is not available on a sharded inference object')
+        assert self._components_set, _NOT_SET
+        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
+        for x in sets:
+            if x.ndim != 1:                                    # (before anything of the object changes)
+                raise ValueError('nELBO_and_grad_batch: one-dimensional parameter vectors expected')
+            if x.size not in (n_free, n_all):
+                self.set_parameters(x)                         # (raises the reference's ValueError, meanfield.py:223-259)
+        forced = sweeps is not None
+        if start is not None and not forced:
+            raise ValueError('nELBO_and_grad_batch: `start` goes with `sweeps`; the loop under the stop rule starts from '
+                             'the state the object holds')
+        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
+        if trips < 1:
+            raise ValueError('nELBO_and_grad_batch: a gradient needs at least one sweep')
+        free = ~self.frozen_mask
+        if not sets:
+            return [], np.zeros((0, n_free))
+        entry = (self._mu, self._var) if start is None else start
+        staged = self._batch_stage(sets, start=start)
+        res = None
+        if staged is not None:
+            ctx, kp, yr, jt, m0, v0 = staged
+            n_k = sum(k.pars.size for k in chain(self.nodes, self.weights))
+            if kp.shape[1] == n_k:                             # (every program's parameters are its kernel's own)
+                res = ctx.elbocalc_batch(kp, yr, jt, m0, v0, trips, want_state=True, want_grad=True, forced=forced)
+        if res is not None:
+            elbo, _, _, info, mu_f, var_f, g_k = self._batch_keep(res)
+            n_m = n_all - n_k - self.p
+            grads = np.concatenate((g_k / self.q, np.zeros((len(sets), n_m)), self._jitter_grads_batch(jt, mu_f, var_f)), axis=1)
+            bad = (info > 0) | ~np.isfinite(elbo)
+            grads[bad] = 0.0
+            values = [float('inf') if b else float(-e) for e, b in zip(elbo, bad)]
+            return values, -grads[:, free]
+        # one by one, each vector from the same state
+        values, grads = [], np.zeros((len(sets), n_free))
+        keep = None
+        for b, x in enumerate(sets):
+            self.set_parameters(x)
+            nodes, weights, means, jitters = self._get_components()
+            mu0, var0 = entry if entry[0] is not None else self._initMuVar(nodes, weights, jitters)
+            ctx = self._setup_device(nodes, weights, means, jitters)
+            ctx.set_muvar(np.asarray(mu0, dtype=float), np.asarray(var0, dtype=float))
+            if forced:
+                e, _, info = ctx.sweep(trips, commit=True)
+                e, conv = e[-1], False
+                mu, var = ctx.get_muvar()
+            else:
+                hist, _, conv, info, mu, var = ctx.elbocalc(trips)
+                e = hist[-1]
+            info = info or self.last_info
+            self.last_info = info
+            if info or not np.isfinite(e):
+                values.append(float('inf'))
+                continue
+            g = np.array(self._grad_from_state(nodes, weights, means, jitters, mu, var, None, fused=ctx))
+            values.append(float(-e))
+            grads[b] = -g[free]
+            if conv:
+                keep = (mu, var)
+        if keep is not None:
+            self._mu, self._var = keep
+        return values, grads
 
     def mcmc(self, priors, p0=None, vars=None, niter=500, **kwargs):
         """

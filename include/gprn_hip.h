@@ -337,6 +337,34 @@ int gprn_elbocalc_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, 
                         int max_iter, double* elbo, int* iterations, int* converged, int* info,
                         double* mu_out, double* var_out);
 
+/* gprn_elbocalc_batch with, per evaluation, the gradient of gprn_grad_elbo at the end of its loop -- what a multi-start
+ * optimiser or a gradient-based ensemble sampler asks for vector by vector (nELBO at meanfield.py:1095-1111 followed by the
+ * derivative of the expected log prior, :992-1067).  gprn_elbocalc_batch IS this call with flags = 0 and grad_out = NULL.
+ *   grad_out [n_eval][n_kernel_params], or NULL: row b is what gprn_grad_elbo returns right after gprn_elbocalc has run
+ *       evaluation b's loop alone -- d/dtheta of the expected log prior at the state and factors of that evaluation's LAST
+ *       COMMITTED sweep, every kernel parameter of every latent GP in kernel_params' layout, NOT divided by q, quirks Q1 and
+ *       Q2 as in gprn_grad_elbo, dK/dtheta by gprn_grad_kernel's rules (closed forms for a single SE, Periodic or
+ *       QuasiPeriodic kernel, Richardson-extrapolated central differences of the kernel program otherwise).  Every sum runs
+ *       in a fixed order: two calls return the same bits.  Both sweep orders (gprn_set_sweep_order).
+ *   flags: GPRN_BATCH_FORCED -- the stop rule of :640-643 is NOT applied: every evaluation makes exactly max_iter committed
+ *       trips (converged = 0, iterations = max_iter), the smooth objective of a gradient optimiser; a non-positive pivot still
+ *       ends that evaluation at once.  Other bits: GPRN_E_ARG.
+ * An evaluation with info > 0 gets a NaN ELBO and a row of zeros; the others are untouched.  grad_out with max_iter < 1:
+ * GPRN_E_ARG (no sweep was committed).  Refusals: gprn_elbocalc_batch's (a data mask, a communicator, uploaded kernels, a
+ * kernel that is not even in t_i - t_j, a one-tile problem with the small path off).
+ * elbo, iterations, converged, info and the states are bit-identical to the same call without grad_out: the gradient pass runs
+ * per chunk behind the chunk's loop (csrc/grad.hip, slots = evaluations x latent GPs: its launches do not grow with the number
+ * of evaluations), in scratch of its own outside the chunk's slabs -- a, u, the residual, the partial sums and three ld x ld
+ * matrices per node j >= 1 (quirk Q1); it overwrites the chunk's B workspaces with lower(B^-1).  Where that scratch exceeds
+ * the budget ("batch_mem_mb") or the device refuses it, the chunk's evaluations go in groups; GPRN_E_NOMEM only when one
+ * evaluation's scratch does not fit.  The context's own state and factors are not touched; its gprn_grad_elbo needs a
+ * committed sweep of its own afterwards. */
+#define GPRN_BATCH_FORCED 1
+int gprn_elbocalc_batch_grad(gprn_ctx* ctx, int n_eval, const double* kernel_params, int n_kernel_params,
+                             const double* y_resid, const double* jitters, const double* mu, const double* var,
+                             int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
+                             double* mu_out, double* var_out, double* grad_out);
+
 /* ---- per-context switches (tests, experiments; nothing in the reference corresponds) ----
  * name: "flags" (1: the factorisation's cross-stream dependencies travel through device-side flags and
  * in-kernel waits, 0: HIP events -- chosen automatically per context, and latched to 0 after an in-kernel
