@@ -73,6 +73,9 @@ SIGNATURES = {
     'gprn_test_gemm_rate': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, _dp]),
     'gprn_test_fill_rate': (c_int, [c_void_p, c_int, _dp]),
     'gprn_test_mfma_peak': (c_int, [c_void_p, c_int, c_int, _dp]),
+    'gprn_test_tile_launch': (c_int, [c_void_p, c_int, c_int, _dp, c_int, POINTER(c_int64), c_int, c_int, c_int, _dp, c_int,
+                              c_int]),
+    'gprn_test_tile_step': (c_int, [c_void_p, c_int, _dp, c_int, c_int, c_int, c_int, POINTER(c_int64)]),
     'gprn_set_option': (c_int, [c_void_p, c_char_p, c_int, POINTER(c_int)]),
     'gprn_elbocalc_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, _dp, POINTER(c_int), POINTER(c_int),
                             POINTER(c_int), _dp, _dp]),
@@ -546,4 +549,30 @@ class Context:
         X = _f64(X)
         out = np.empty_like(X)
         self._check(self._lib.gprn_test_lauum(self._h, X.shape[0], _ptr(X), _ptr(out)), 'test_lauum')
+        return out
+
+    def test_tile_launch(self, bufs, tasks, shape, tag, ldc=0, ft_s=None, ft_n=0, acc=False):
+        """One launch of the tile kernel (gprn_test_tile_launch).  bufs: (nbatch, 4, ld, ld); tasks: rows of (c_off, a_off,
+        b_off, klen, c_buf, a_buf, b_buf, modes).  Returns every buffer as the launch left it."""
+        out = _f64(bufs).copy()
+        nbatch, nbuf, ld, ld2 = out.shape
+        if nbuf != 4 or ld != ld2:
+            raise ValueError(f'expected (nbatch, 4, ld, ld), got {out.shape}')
+        t = np.ascontiguousarray(tasks, dtype=np.int64).reshape(-1, 8)
+        s = None if ft_s is None else _f64(ft_s, (nbatch, ld))
+        self._check(self._lib.gprn_test_tile_launch(self._h, ld, nbatch, _ptr(out), len(t),
+                                                    t.ctypes.data_as(POINTER(c_int64)), int(shape), int(tag), int(ldc),
+                                                    None if s is None else _ptr(s), int(ft_n), int(bool(acc))),
+                    'test_tile_launch')
+        return out
+
+    def test_tile_step(self, bufs, which, table=True, tasks=(), n_l=0):
+        """One launch of k_chain_l / k_chain_u / k_tile_panel at step 0 of 256 x 256 matrices (gprn_test_tile_step).  bufs:
+        (nbatch, 2, 256, 256), B and X; tasks: the panel's list, its first n_l the L part."""
+        out = _f64(bufs).copy()
+        if out.shape[1:] != (2, 2 * TILE, 2 * TILE):
+            raise ValueError(f'expected (nbatch, 2, 256, 256), got {out.shape}')
+        t = np.ascontiguousarray(tasks, dtype=np.int64).reshape(-1, 8)
+        self._check(self._lib.gprn_test_tile_step(self._h, out.shape[0], _ptr(out), int(which), int(bool(table)), int(n_l),
+                                                  len(t) - int(n_l), t.ctypes.data_as(POINTER(c_int64))), 'test_tile_step')
         return out

@@ -415,6 +415,27 @@ int gprn_test_factor_invert(gprn_ctx* ctx, int n, int batch, const double* A,
 int gprn_test_mfma_peak(gprn_ctx* ctx, int wg_per_cu, int iters, double* tflops);
 /* out = lower(X^T X) for lower-triangular X */
 int gprn_test_lauum(gprn_ctx* ctx, int n, const double* X, double* out);
+/* ---- launch-level diagnostics (csrc/api_test.hip, tests/test_tiles_gpu.py): ONE launch on the caller's data.
+ * gprn_test_tile_launch: one call of the tile launcher.  bufs: [nbatch][4][ld * ld], the four buffers (B, X, K, KLinv
+ * slots) of every matrix, row-major, read in and written back IN FULL.  tasks: ntasks x 8 integers -- c_off, a_off,
+ * b_off, klen, c_buf, a_buf, b_buf, modes (bits 0-1 c_mode, 2 a_mode, 3 b_mode, 4 symmetric update of a diagonal tile,
+ * 5 first touch), offsets in doubles from the start of a buffer.  shape: workgroup shape (0 128x128, 1 64x64, 2 64x128,
+ * 3 128x64, 4 64x128 with a triangular B, 5 128x64 with a triangular A); tag: launch family (0 panel, 1 inner, 2 next,
+ * 3 bulk, 4 misc, 5 ahead, 6 cov); ldc: 0, or the pitch of the C tiles of a cov launch; ft_s ([nbatch][ld], may be NULL)
+ * and ft_n: s = sqrt(d) and the problem size of the first-touch tiles; acc: the panel's L part by substitution.
+ * No signals, no waits.  Checked on the host before anything is launched -- ld a multiple of 128, klen a positive
+ * multiple of 16, buffer indices below 4, every operand and C tile inside its buffer, C tiles pairwise disjoint and
+ * apart from every operand but a panel task's own, a known shape/tag pair, bit 5 only with ft_s and c_mode 1 --
+ * anything else is GPRN_E_ARG with a text, and nothing runs. */
+int gprn_test_tile_launch(gprn_ctx* ctx, int ld, int nbatch, double* bufs, int ntasks, const int64_t* tasks,
+                          int shape, int tag, int ldc, const double* ft_s, int ft_n, int acc);
+/* one launch of the tile step's other kernels at step 0 of nbatch 256 x 256 matrices; bufs: [nbatch][2][256 * 256], B
+ * and X, returned in full.  which 0: L_10 = B_10 X_00^T in place (k_chain_l); 1: B_11 -= L_10 L_10^T, lower 16 x 16
+ * blocks (k_chain_u); 2 / 3: the panel launch (k_tile_panel) on `tasks` (as above, buffers 0 and 1), the first n_l by
+ * product / by substitution with a triangular B, the other n_x with a triangular A.  table != 0: the launch may take
+ * its pointers as kernel arguments (up to 16 matrices); 0: it reads them from the device table.  Same checks. */
+int gprn_test_tile_step(gprn_ctx* ctx, int nbatch, double* bufs, int which, int table, int n_l, int n_x,
+                        const int64_t* tasks);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,19 @@ def test_lauum(ctx):
     np.testing.assert_allclose(np.tril(out), np.tril(X.T @ X), rtol=0, atol=1e-11)
 
 
+@pytest.mark.parametrize('n', [128, 256, 640, 1152])
+def test_lauum_sizes(ctx, n):
+    # one tile, an even count, an odd count, more tiles than an outer panel (the K = 512 lists run); integer data: every
+    # partial sum is representable, so the lower triangle is X^T X exactly, in any summation order
+    rng = np.random.RandomState(90 + n)
+    X = np.tril(rng.randint(-3, 4, size=(n, n))).astype(float)
+    out = ctx.test_lauum(X)
+    assert np.array_equal(np.tril(out), np.tril(X.T @ X))
+    X = np.tril(rng.standard_normal((n, n)))
+    out = ctx.test_lauum(X)
+    np.testing.assert_allclose(np.tril(out), np.tril(X.T @ X), rtol=0, atol=1e-11)
+
+
 def _check_factor_by_probes(A, L, X, rng, tol):
     """O(n^2) checks of a factor + inverse: L L^T v = A v and X (L v) = v for random v."""
     n = A.shape[0]
