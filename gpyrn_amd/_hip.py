@@ -81,6 +81,8 @@ SIGNATURES = {
                             POINTER(c_int), _dp, _dp]),
     'gprn_elbocalc_batch_grad': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, _dp, POINTER(c_int),
                                  POINTER(c_int), POINTER(c_int), _dp, _dp, _dp]),
+    'gprn_predict_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
+    'gprn_test_predict_fill': (c_int, [c_void_p, c_int, c_int, _dp, c_int, _dp, c_int, c_int, c_int, _dp, _dp, _dp, _dp]),
     'gprn_elbocalc': (c_int, [c_void_p, c_int, _dp, _dp, _dp, _dp, c_int, _dp, c_int, POINTER(c_int), POINTER(c_int),
                       POINTER(c_int), _dp, _dp]),
     'gprn_expected_loglike': (c_int, [c_void_p, _dp]),
@@ -483,6 +485,60 @@ class Context:
         if want_grad:
             out += (grads,)
         return out
+
+    def predict_batch(self, kernel_params, mu, var, tstar, jitters=None, latent=True, outputs=True):
+        """gprn_predict for B parameter vectors side by side (gprn_predict_batch): kernel_params (B, n_kpar), mu / var (B, d)
+        -- each evaluation's own state -- jitters (B, p) (needed with `outputs`), tstar (n*).  Returns (lat_mean, lat_var,
+        out_mean, out_var, info): the latent rows (B, G, n*) -- row b what predict() returns for vector b and state b alone --
+        or None without `latent`; the per-output combination of _Prediction without the mean functions, (B, p, n*), or None
+        without `outputs`; info (B,), LAPACK-style per evaluation.  None where the library has no side-by-side form for
+        this problem (a communicator, a host-evaluated kernel, a kernel that is not even in t_i - t_j)."""
+        if not (latent or outputs):
+            raise ValueError('predict_batch: ask for the latent pair, the output pair or both')
+        kp = _f64(kernel_params)
+        if kp.ndim != 2 or kp.shape[0] < 1:
+            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        B = kp.shape[0]
+        d = (self.p + 1) * self.q * self.N
+        m0, v0 = _f64(mu), _f64(var)
+        if m0.size != B * d or v0.size != B * d:
+            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
+        ts = _f64(np.ravel(tstar))
+        if ts.size < 1:
+            raise ValueError('tstar is empty')
+        jt = None
+        if outputs:
+            if jitters is None:
+                raise ValueError('predict_batch: the output pair needs the jitters')
+            jt = _f64(jitters)
+            if jt.size != B * self.p:
+                raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
+        ns = ts.size
+        lm = np.empty((B, self.G, ns)) if latent else None
+        lv = np.empty((B, self.G, ns)) if latent else None
+        om = np.empty((B, self.p, ns)) if outputs else None
+        ov = np.empty((B, self.p, ns)) if outputs else None
+        info = np.zeros(B, dtype=np.int32)
+        opt = lambda a: None if a is None else _ptr(a)
+        rc = self._lib.gprn_predict_batch(self._h, B, _ptr(kp), kp.shape[1], _ptr(m0), _ptr(v0), opt(jt), ns, _ptr(ts),
+                                          opt(lm), opt(lv), opt(om), opt(ov), info.ctypes.data_as(POINTER(c_int)))
+        if rc == GPRN_E_UNSUPPORTED:
+            return None
+        self._check(rc, 'predict_batch')
+        return lm, lv, om, ov, info.astype(int)
+
+    def test_predict_fill(self, kernel_params, var, eval_index, gp, tstar, batched):
+        """K + 1.25e-12 I + diag(v) (N, N), K* (n*, N) and k** (n*) of slot (eval_index, gp) as gprn_predict_batch fills them
+        (`batched`) or as gprn_predict does for that vector alone (gprn_test_predict_fill)."""
+        kp = _f64(np.atleast_2d(kernel_params))
+        B = kp.shape[0]
+        v0 = _f64(np.reshape(var, (B, (self.p + 1) * self.q * self.N)))
+        ts = _f64(np.ravel(tstar))
+        K, Ks, kss = np.empty((self.N, self.N)), np.empty((ts.size, self.N)), np.empty(ts.size)
+        self._check(self._lib.gprn_test_predict_fill(self._h, int(bool(batched)), B, _ptr(kp), kp.shape[1], _ptr(v0),
+                                                     int(eval_index), int(gp), ts.size, _ptr(ts), _ptr(K), _ptr(Ks), _ptr(kss)),
+                    'test_predict_fill')
+        return K, Ks, kss
 
     def option(self, name, value=-1):
         """Read (value < 0) or set a per-context switch of the library; returns the previous value."""

@@ -71,6 +71,35 @@ extern "C" int gprn_predict(gprn_ctx* c, int ns, const double* tstar, double* me
     return rc;
 }
 
+// gprn_predict for n_eval parameter vectors and states side by side (include/gprn_hip.h): the worker context and slabs of
+// gprn_elbocalc_batch at every T (midn.hip mid_predict_chunk); nothing of the caller's context is written.
+extern "C" int gprn_predict_batch(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                  const double* mu, const double* var, const double* jitters, int ns, const double* tstar,
+                                  double* lat_mean, double* lat_var, double* out_mean, double* out_var, int* info)
+{
+    DeviceLock lock_(c);
+    WatchScope watch_(c, "gprn_predict_batch");
+    if (!c || !c->N || n_eval < 1 || !kernel_params || !mu || !var || ns <= 0 || !tstar || !info || (!lat_mean != !lat_var) ||
+        (!out_mean != !out_var))
+        return bad(c, "predict_batch: bad argument");
+    if (!lat_mean && !out_mean) return bad(c, "predict_batch: neither the latent nor the output pair was asked for");
+    if (out_mean && !jitters) return bad(c, "predict_batch: the output pair needs the jitters");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->owner.empty()) return bad(c, "predict_batch: call set_owners first");
+    if (comm_active(c) || c->world != 1) { c->err = "predict_batch: one rank only"; return GPRN_E_UNSUPPORTED; }
+    TRY(batch_validate(c, n_kernel_params));
+    // (the budget is an estimate, as for gprn_elbocalc_batch_grad: nothing has run when an allocation is refused)
+    int cap = 0, want = n_eval, rc;
+    while ((rc = mid_batch_reserve(c, want, &cap)) == GPRN_E_NOMEM && cap > 1) want = cap / 2;
+    if (rc) return rc;
+    if (want != n_eval) c->err.clear();
+    c->last_batch_chunk = std::min(cap, n_eval);
+    const PredBatchIo io{n_eval, kernel_params, n_kernel_params, mu, var, jitters, ns, tstar, lat_mean, lat_var, out_mean, out_var,
+                         info, c->p, c->G, (size_t)(c->p + 1) * c->q * c->N};
+    for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(mid_predict_run(c, io.slice(e0, std::min(cap, n_eval - e0))));
+    return GPRN_OK;
+}
+
 static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out, const PredAfter& after)
 {
     TRY(build_tables(c));

@@ -841,7 +841,7 @@ int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchD
     for (int b = 0; b < B; ++b) {
         const double* kp = io.kparams + (size_t)b * io.n_kpar;
         for (int g = 0; g < G; ++g) {
-            if (!fill_program_with(c->kspec[g], kp, pin + ((size_t)b * G + g) * pb)) {
+            if (!fill_program_with(c->kspec[g], kp, pin + ((size_t)b * G + g) * pb, 1e-6)) {
                 c->err = "elbocalc_batch: a kernel that is not an even function of t_i - t_j"; return GPRN_E_UNSUPPORTED;
             }
             kp += c->kspec[g].n_params;

@@ -231,3 +231,52 @@ extern "C" int gprn_test_tile_step(gprn_ctx* c, int nbatch, double* bufs, int wh
     HIP_TRY(c, hipMemcpy(bufs, d_bufs, total * sizeof(double), hipMemcpyDeviceToHost));
     return GPRN_OK;
 }
+
+// The two fills of prediction for one slot (include/gprn_hip.h): batched, slot (eval, gp) of the launches gprn_predict_batch
+// makes, read back before the factorisation overwrites it; or the fills of gprn_predict with vector `eval` substituted.
+extern "C" int gprn_test_predict_fill(gprn_ctx* c, int batched, int n_eval, const double* kernel_params, int n_kernel_params,
+                                      const double* var, int eval, int gp, int ns, const double* tstar,
+                                      double* K_out, double* Ks_out, double* kss_out)
+{
+    DeviceLock lock_(c);
+    if (!c || !c->N || n_eval < 1 || !kernel_params || !var || eval < 0 || eval >= n_eval || gp < 0 || gp >= c->G || ns < 1 ||
+        ns > c->ld || !tstar || !K_out || !Ks_out || !kss_out)
+        return bad(c, "test_predict_fill: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (comm_active(c) || c->world != 1) { c->err = "test_predict_fill: one rank only"; return GPRN_E_UNSUPPORTED; }
+    TRY(batch_validate(c, n_kernel_params));
+    const size_t d = (size_t)(c->p + 1) * c->q * c->N;
+    if (batched) {
+        int cap = 0;
+        TRY(mid_batch_reserve(c, n_eval, &cap));
+        if (cap < n_eval) return bad(c, "test_predict_fill: the evaluations do not fit one chunk");
+        std::vector<int> info(n_eval);
+        // (the state's means are not read by the fills: the variances stand in)
+        const PredBatchIo io{n_eval, kernel_params, n_kernel_params, var, var, nullptr, ns, tstar, nullptr, nullptr, nullptr, nullptr,
+                             info.data(), c->p, c->G, d};
+        return mid_predict_fill_test(c, io, eval, gp, K_out, Ks_out, kss_out);
+    }
+    const int N = c->N, ld = c->ld, ns_pad = ((ns + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+    KernelSpec ks = c->kspec[gp];
+    const double* kp = kernel_params + (size_t)eval * n_kernel_params;
+    for (int g = 0; g < gp; ++g) kp += c->kspec[g].n_params;
+    for (int i = 0; i < ks.n_params; ++i) ks.params[i] = kp[i];
+    const int kk = gp - c->q, srow = gp < c->q ? gp : (1 + kk % c->p) * c->q + kk / c->p;
+    CallScratch scr(c);
+    double *d_K = nullptr, *d_Ks = nullptr, *d_kss = nullptr, *d_ts = nullptr, *d_v = nullptr;
+    TRY(scr.alloc(&d_K, (size_t)ld * ld));
+    TRY(scr.alloc(&d_Ks, (size_t)ns_pad * ld));
+    TRY(scr.alloc(&d_kss, ns_pad));
+    TRY(scr.alloc(&d_ts, ns));
+    TRY(scr.alloc(&d_v, N));
+    HIP_TRY(c, hipMemcpy(d_ts, tstar, ns * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_v, var + (size_t)eval * d + (size_t)srow * N, N * sizeof(double), hipMemcpyHostToDevice));
+    TRY(launch_fill(c, ks, d_K, 1.25e-12, d_v));
+    TRY(launch_fill_rect(c, ks, 1.25e-12, d_ts, ns, ns_pad, d_Ks, d_kss));
+    const size_t row = sizeof(double);
+    HIP_TRY(c, hipMemcpy2DAsync(K_out, N * row, d_K, ld * row, N * row, N, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpy2DAsync(Ks_out, N * row, d_Ks, ld * row, N * row, ns, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(kss_out, d_kss, ns * row, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GPRN_OK;
+}

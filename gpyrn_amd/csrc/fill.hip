@@ -270,10 +270,12 @@ int launch_fill_times(gprn_ctx* c, const KernelSpec& ks, double* K, double nugge
 // matrix filled here has the bits of one filled by launch_fill; everything else goes through the postfix program.
 // (The first version read the program from global memory inside the element loop: 1.04 ms for 256 matrices of 512^2,
 // 0.5 TB/s -- profiles/r05_batch512_first_kernel_stats.txt.)  K2: a second copy of every matrix (the set-up factors a
-// copy of K in place), or null.
-template <int KID>
+// copy of K in place), or null.  DIAG (gprn_predict_batch): matrix b also gets diags[b][m] on its diagonal, m < N, behind the
+// nugget -- the bits of launch_fill with diag_add; the instantiation without it is the kernel the ELBO batches always had.
+template <int KID, bool DIAG>
 __device__ __forceinline__ void fill_sym_batch_block(const FillProgram& pg, const double* __restrict__ t, double* __restrict__ K,
-                                                     double* __restrict__ K2, int N, int ld, double (*tile)[65])
+                                                     double* __restrict__ K2, int N, int ld, double (*tile)[65],
+                                                     const double* __restrict__ diag)
 {
     constexpr int TR = 64;
     double par[4] = {0.0, 0.0, 0.0, 0.0}, aux[3] = {0.0, 0.0, 0.0};
@@ -306,6 +308,7 @@ __device__ __forceinline__ void fill_sym_batch_block(const FillProgram& pg, cons
         if (m == n || m == n + 1) {
             double d = (m == n) ? v0 : v1;
             if (nugget) d += nugget_val;
+            if constexpr (DIAG) { if (m < N) d += diag[m]; }
             if (m == n) v0 = d; else v1 = d;
         }
         if (m >= N || n >= N) v0 = (m == n) ? 1.0 : 0.0;
@@ -326,9 +329,10 @@ __device__ __forceinline__ void fill_sym_batch_block(const FillProgram& pg, cons
     }
 }
 
+template <bool DIAG>
 __global__ __launch_bounds__(256)
 void k_fill_sym_batch(const FillProgram* __restrict__ pgs, const double* __restrict__ t, double* const* __restrict__ Ks,
-                      double* const* __restrict__ K2s, int N, int ld)
+                      double* const* __restrict__ K2s, int N, int ld, const double* const* __restrict__ diags)
 {
     __shared__ double tile[64][65];
     __shared__ FillProgram spg;
@@ -341,37 +345,48 @@ void k_fill_sym_batch(const FillProgram* __restrict__ pgs, const double* __restr
     double* const K = Ks[blockIdx.y];
     double* const K2 = K2s ? K2s[blockIdx.y] : nullptr;
     // (uniform per workgroup: a scalar branch)
+    const double* diag = nullptr;
+    if constexpr (DIAG) diag = diags[blockIdx.y];
     const int kid = (spg.n_ops == 1 && spg.ops[0] == GPRN_OP_PUSH && spg.ops[2] == 0) ? spg.ops[1] : -1;
     switch (kid) {
-    case GPRN_K_SE: fill_sym_batch_block<GPRN_K_SE>(spg, t, K, K2, N, ld, tile); break;
-    case GPRN_K_PERIODIC: fill_sym_batch_block<GPRN_K_PERIODIC>(spg, t, K, K2, N, ld, tile); break;
-    case GPRN_K_QP: fill_sym_batch_block<GPRN_K_QP>(spg, t, K, K2, N, ld, tile); break;
-    default: fill_sym_batch_block<-1>(spg, t, K, K2, N, ld, tile);
+    case GPRN_K_SE: fill_sym_batch_block<GPRN_K_SE, DIAG>(spg, t, K, K2, N, ld, tile, diag); break;
+    case GPRN_K_PERIODIC: fill_sym_batch_block<GPRN_K_PERIODIC, DIAG>(spg, t, K, K2, N, ld, tile, diag); break;
+    case GPRN_K_QP: fill_sym_batch_block<GPRN_K_QP, DIAG>(spg, t, K, K2, N, ld, tile, diag); break;
+    default: fill_sym_batch_block<-1, DIAG>(spg, t, K, K2, N, ld, tile, diag);
     }
 }
 
 size_t fill_program_bytes() { return sizeof(FillProgram); }
 
-// the program of `ks` (1e-6 nugget for one-argument kernels: meanfield.py:433) with other parameter values, written to dst;
-// false when the program is not an even function of t_i - t_j (Polynomial: the symmetric fill does not apply)
-bool fill_program_with(const KernelSpec& ks, const double* params, void* dst)
+// the program of `ks` with other parameter values, written to dst; nugget_val: what one-argument kernels get on the diagonal
+// (quirk Q9 as in make_program: two-argument kernels get none) -- 1e-6 for the priors (meanfield.py:433), 1.25e-12 for
+// prediction (_gp.py:47); false when the program is not an even function of t_i - t_j (Polynomial: the symmetric fill does
+// not apply)
+bool fill_program_with(const KernelSpec& ks, const double* params, void* dst, double nugget_val)
 {
     KernelSpec k2 = ks;
     for (int i = 0; i < ks.n_params; ++i) k2.params[i] = params[i];
     FillProgram pg;
-    make_program(k2, 1e-6, pg);
+    make_program(k2, nugget_val, pg);
     memcpy(dst, &pg, sizeof(pg));
     return program_is_even(pg);
 }
 
-// n_matrices matrices of the context's N (ld = 128 T) from d_programs[i] into d_Ks[i]
-int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, double* const* d_K2s)
+// n_matrices matrices of the context's N (ld = 128 T) from d_programs[i] into d_Ks[i]; d_diags: per matrix the N values its
+// diagonal gets on top (device pointers, device table), or null
+int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, double* const* d_K2s,
+                      const double* const* d_diags)
 {
     if (n_matrices <= 0) return GPRN_OK;
     prof_begin(c, GPRN_T_FILL);
     const int nb = c->ld / 64;
-    hipLaunchKernelGGL(k_fill_sym_batch, dim3(nb * (nb + 1) / 2, n_matrices), dim3(256), 0, c->stream,
-                       (const FillProgram*)d_programs, c->d_time, d_Ks, d_K2s, c->N, c->ld);
+    const dim3 grid(nb * (nb + 1) / 2, n_matrices);
+    if (d_diags)
+        hipLaunchKernelGGL(k_fill_sym_batch<true>, grid, dim3(256), 0, c->stream,
+                           (const FillProgram*)d_programs, c->d_time, d_Ks, d_K2s, c->N, c->ld, d_diags);
+    else
+        hipLaunchKernelGGL(k_fill_sym_batch<false>, grid, dim3(256), 0, c->stream,
+                           (const FillProgram*)d_programs, c->d_time, d_Ks, d_K2s, c->N, c->ld, d_diags);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
@@ -419,6 +434,90 @@ int launch_fill_rect(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const
 #undef X
     default: hipLaunchKernelGGL(k_fill_rect<-1>, grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss);
     }
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
+// ---- K* and k** of many matrices in one launch (gprn_predict_batch, midn.hip): matrix b of the launch has its own program
+// (device memory) and destinations Ks[b] (rows of pitch ld) and kss + b * kss_stride; the prediction times are the same for
+// all.  One workgroup = 32 rows x 256 columns of one matrix, a thread one column of them: a row goes out as 2 KiB
+// contiguous, as in k_fill_rect.  The program comes into LDS once per workgroup; SE, Periodic and QP take their parameters and
+// host-computed reciprocals into registers and run their own instruction stream, everything else goes through the postfix
+// program (fill_eval.h: the element code of k_fill_rect, so a matrix filled here has launch_fill_rect's bits).  Rows
+// [ns, ns_pad) and columns [N, ld) are zeros.
+#define GPRN_RECT_ROWS 32
+template <int KID>
+__device__ __forceinline__ void fill_rect_batch_rows(const FillProgram& pg, const double* __restrict__ ts, int ns, int ns_pad,
+                                                     const double* __restrict__ t, int N, int ld, double* __restrict__ Ks,
+                                                     double* __restrict__ kss)
+{
+    double par[4] = {0.0, 0.0, 0.0, 0.0}, aux[3] = {0.0, 0.0, 0.0};
+    if (KID >= 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) par[i] = pg.par[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) aux[i] = pg.aux[i];
+    }
+    const int nugget = pg.nugget;
+    const double nugget_val = pg.nugget_val;
+    auto eval = [&](double ti, double tj, bool diag) {
+        if constexpr (KID >= 0) return eval_kernel(KID, par, ti, tj, diag, aux);
+        else return eval_program(pg, ti, tj, diag);
+    };
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int i0 = blockIdx.y * GPRN_RECT_ROWS;
+    if (n >= ld) return;
+    const double tn = (n < N) ? t[n] : 0.0;
+#pragma unroll 1
+    for (int r = 0; r < GPRN_RECT_ROWS; ++r) {
+        const int i = i0 + r;
+        if (i >= ns_pad) break;
+        double v = 0.0;
+        if (i < ns && n < N) v = eval(ts[i], tn, false);
+        Ks[(size_t)i * ld + n] = v;
+        if (n == 0 && i < ns) {
+            double d = eval(ts[i], ts[i], true);
+            if (nugget) d += nugget_val;
+            kss[i] = d;
+        }
+    }
+}
+
+// grid (ceil(ld / 256), ceil(ns_pad / 32), matrices)
+__global__ __launch_bounds__(256)
+void k_fill_rect_batch(const FillProgram* __restrict__ pgs, const double* __restrict__ ts, int ns, int ns_pad,
+                       const double* __restrict__ t, int N, int ld, double* const* __restrict__ Kss,
+                       double* __restrict__ kss, size_t kss_stride)
+{
+    __shared__ FillProgram spg;
+    {
+        const int* src = reinterpret_cast<const int*>(pgs + blockIdx.z);
+        int* dst = reinterpret_cast<int*>(&spg);
+        for (int i = threadIdx.x; i < (int)(sizeof(FillProgram) / sizeof(int)); i += 256) dst[i] = src[i];
+    }
+    __syncthreads();
+    double* const Ks = Kss[blockIdx.z];
+    double* const kd = kss + (size_t)blockIdx.z * kss_stride;
+    // (uniform per workgroup: a scalar branch)
+    const int kid = (spg.n_ops == 1 && spg.ops[0] == GPRN_OP_PUSH && spg.ops[2] == 0) ? spg.ops[1] : -1;
+    switch (kid) {
+    case GPRN_K_SE: fill_rect_batch_rows<GPRN_K_SE>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
+    case GPRN_K_PERIODIC: fill_rect_batch_rows<GPRN_K_PERIODIC>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
+    case GPRN_K_QP: fill_rect_batch_rows<GPRN_K_QP>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
+    default: fill_rect_batch_rows<-1>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd);
+    }
+}
+
+// ns <= ns_pad <= ld rows (ns_pad a multiple of 128) of n_matrices matrices: K* into d_Ks[i], k** into kss + i * kss_stride
+int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* d_tstar,
+                           int ns, int ns_pad, double* kss, size_t kss_stride)
+{
+    if (n_matrices <= 0) return GPRN_OK;
+    prof_begin(c, GPRN_T_FILL);
+    hipLaunchKernelGGL(k_fill_rect_batch, dim3((c->ld + 255) / 256, (ns_pad + GPRN_RECT_ROWS - 1) / GPRN_RECT_ROWS, n_matrices),
+                       dim3(256), 0, c->stream, (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time,
+                       c->N, c->ld, d_Ks, kss, kss_stride);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

@@ -321,9 +321,13 @@ int launch_fill_times(gprn_ctx* c, const KernelSpec& ks, double* K, double nugge
                       const double* t, int N, int ld);
 // many small matrices in one launch (fill.hip; gprn_elbocalc_batch)
 size_t fill_program_bytes();
-bool fill_program_with(const KernelSpec& ks, const double* params, void* dst);
+bool fill_program_with(const KernelSpec& ks, const double* params, void* dst, double nugget_val);
 int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices,
-                      double* const* d_K2s = nullptr);      // d_K2s: a second copy of every matrix, or null
+                      double* const* d_K2s = nullptr,       // d_K2s: a second copy of every matrix, or null
+                      const double* const* d_diags = nullptr);   // per matrix: N values added to its diagonal, or null
+// K* (ns rows, zero-padded to ns_pad <= ld) and k** of many matrices at the same prediction times in one launch
+int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* d_tstar,
+                           int ns, int ns_pad, double* kss, size_t kss_stride);
 int launch_fill_rect(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
                      int ns, int ns_pad, double* Ks, double* kss);
 // workgroup output shape of a tile launch (csrc/gemm_tile.hip)
@@ -548,6 +552,25 @@ void small_batch_free(gprn_ctx* c);
 int mid_batch_reserve(gprn_ctx* c, int want, int* cap);
 int mid_batch_run(gprn_ctx* c, const BatchIo& io);
 void mid_batch_free(gprn_ctx* c);
+// One call of gprn_predict_batch -- its pointers and counts -- or a run of its evaluations (slice)
+struct PredBatchIo {
+    int n; const double* kparams; int n_kpar; const double *mu, *var, *jitters; int ns; const double* tstar;
+    double *lat_mean, *lat_var, *out_mean, *out_var;     // (each pair: both or neither)
+    int* info;
+    int p, G; size_t state;                               // per evaluation: jitters, latent GPs, doubles of mu / var
+    PredBatchIo slice(int e0, int ne) const               // evaluations [e0, e0 + ne)
+    {
+        const size_t lat = (size_t)e0 * G * ns, out = (size_t)e0 * p * ns;
+        return PredBatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, mu + e0 * state, var + e0 * state,
+                           jitters ? jitters + (size_t)e0 * p : nullptr, ns, tstar,
+                           lat_mean ? lat_mean + lat : nullptr, lat_var ? lat_var + lat : nullptr,
+                           out_mean ? out_mean + out : nullptr, out_var ? out_var + out : nullptr, info + e0, p, G, state};
+    }
+};
+// midn.hip: io.n <= cap evaluations of gprn_predict_batch through the worker and slabs mid_batch_reserve made (at every T)
+int mid_predict_run(gprn_ctx* c, const PredBatchIo& io);
+// ... and its two fills alone for slot (eval, gp), read back before anything is factored (gprn_test_predict_fill)
+int mid_predict_fill_test(gprn_ctx* c, const PredBatchIo& io, int eval, int gp, double* K_out, double* Ks_out, double* kss_out);
 size_t batch_budget_bytes(gprn_ctx* c);        // device memory a chunk of evaluations may take (option "batch_mem_mb")
 // api_sweep.hip: one half-sweep's factorisation with its head and tail (run_phase, midn.hip); scal: the sweep's scalars;
 // chain_started: see FactorHooks (left set when the factorisation did not take it)

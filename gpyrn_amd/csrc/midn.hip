@@ -23,6 +23,10 @@
 // the slot of the ACTIVE tables, which later sweeps of the others reuse -- so s = sqrt(d) of every running evaluation is kept
 // per (evaluation, latent GP) behind each group of sweeps (k_mid_keep_s: reads only, the values' bits do not change).  The pass's
 // scratch is an allocation of its own (gprn_ctx::grad_scratch of the worker) that takes what the slabs left of the budget.
+//
+// PREDICTION for many parameter vectors (gprn_predict_batch: mid_predict_chunk, at the end of this file) walks gprn_predict's
+// steps over the same slot table, in the same slabs, at every T >= 1: B holds K + 1.25e-12 I + diag v and then its factor, X
+// its inverse, K and KL a block of K* and of (X K*^T)^T.
 #include "api_internal.h"
 
 #include <math.h>
@@ -57,13 +61,13 @@ struct MidBatch {
     double *keep_s = nullptr;         // [cap][G][ld]: s of each evaluation's last sweep, there from the first call that asks for gradients
     char* programs = nullptr;         // [cap][G] fill programs
     // device tables, one allocation: pointers first, then ints
-    double** d_ptr_block = nullptr;   // kptr [cap G] | kptr2 [cap G] | tab_setup [cap G][4] | tab_kinv [cap (q-1)][4] | tab_node [cap q][4] | tab_weight [cap qp][4]
-    int* d_int_block = nullptr;       // gp_setup [cap G] | ev_setup [cap G] | gp_node, ev_node [cap q] | gp_weight, ev_weight [cap qp] | evals [cap]
+    double** d_ptr_block = nullptr;   // kptr [cap G] | kptr2 [cap G] | tab_setup [cap G][4] | tab_kinv [cap (q-1)][4] | tab_pred [cap G][4] | diag_pred [cap G] | tab_node [cap q][4] | tab_weight [cap qp][4]
+    int* d_int_block = nullptr;       // gp_setup [cap G] | ev_setup [cap G] | row_pred [cap G] | gp_node, ev_node [cap q] | gp_weight, ev_weight [cap qp] | evals [cap]
     size_t n_ptr = 0, n_int = 0;
     char *pin_in = nullptr, *pin_out = nullptr, *pin_tab = nullptr;
     // offsets into the blocks
-    size_t o_kptr = 0, o_kptr2 = 0, o_setup = 0, o_kinv = 0, o_node = 0, o_weight = 0;
-    size_t i_gp_setup = 0, i_ev_setup = 0, i_gp_node = 0, i_ev_node = 0, i_gp_weight = 0, i_ev_weight = 0, i_evals = 0;
+    size_t o_kptr = 0, o_kptr2 = 0, o_setup = 0, o_kinv = 0, o_pred = 0, o_diag = 0, o_node = 0, o_weight = 0;
+    size_t i_gp_setup = 0, i_ev_setup = 0, i_row_pred = 0, i_gp_node = 0, i_ev_node = 0, i_gp_weight = 0, i_ev_weight = 0, i_evals = 0;
 };
 
 static void mid_free_slabs(MidBatch* m)
@@ -163,11 +167,14 @@ int mid_batch_reserve(gprn_ctx* c, int want, int* cap_out)
     m->o_kptr2 = m->o_kptr + nslot;
     m->o_setup = m->o_kptr2 + nslot;
     m->o_kinv = m->o_setup + nslot * GPRN_NBUF;
-    m->o_node = m->o_kinv + (size_t)cap * (q - 1) * GPRN_NBUF;
+    m->o_pred = m->o_kinv + (size_t)cap * (q - 1) * GPRN_NBUF;
+    m->o_diag = m->o_pred + nslot * GPRN_NBUF;
+    m->o_node = m->o_diag + nslot;
     m->o_weight = m->o_node + (size_t)cap * q * GPRN_NBUF;
     m->n_ptr = m->o_weight + (size_t)cap * qp * GPRN_NBUF;
     m->i_gp_setup = 0; m->i_ev_setup = nslot;
-    m->i_gp_node = 2 * nslot; m->i_ev_node = m->i_gp_node + (size_t)cap * q;
+    m->i_row_pred = 2 * nslot;
+    m->i_gp_node = 3 * nslot; m->i_ev_node = m->i_gp_node + (size_t)cap * q;
     m->i_gp_weight = m->i_ev_node + (size_t)cap * q; m->i_ev_weight = m->i_gp_weight + (size_t)cap * qp;
     m->i_evals = m->i_ev_weight + (size_t)cap * qp;
     m->n_int = m->i_evals + cap;
@@ -190,6 +197,13 @@ int mid_batch_reserve(gprn_ctx* c, int want, int* cap_out)
                 row[BUF_B] = m->Bw + s * nn; row[BUF_X] = m->KL + s * nn; row[BUF_K] = m->K + s * nn; row[BUF_KLINV] = m->KL + s * nn;
                 hi[m->i_gp_setup + s] = g;
                 hi[m->i_ev_setup + s] = b;
+                // prediction (mid_predict_chunk): the sweep's workspaces and the prior's slabs, the row of latent GP g in the
+                // state's layout (p + 1, q, N) and that row of the evaluation's variances for the fill's diagonal
+                double** pr = hp + m->o_pred + s * GPRN_NBUF;
+                pr[BUF_B] = m->Bw + s * nn; pr[BUF_X] = m->Xw + s * nn; pr[BUF_K] = m->K + s * nn; pr[BUF_KLINV] = m->KL + s * nn;
+                const int kk = g - q, srow = g < q ? g : (1 + kk % p) * q + kk / p;
+                hi[m->i_row_pred + s] = srow;
+                hp[m->o_diag + s] = w->d_var + (size_t)b * d + (size_t)srow * N;
             }
         for (int b = 0; b < cap; ++b)
             for (int j = 1; j < q; ++j) {                      // lower(K_j^-1) = lower(X^T X), X = chol(K_j)^-1
@@ -451,11 +465,9 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
     return GPRN_OK;
 }
 
-int mid_batch_run(gprn_ctx* c, const BatchIo& io)
+// the worker follows the parent's switches
+static void mid_follow(const gprn_ctx* c, gprn_ctx* w)
 {
-    MidBatch* m = (MidBatch*)c->mid_batch;
-    gprn_ctx* w = m->w;
-    // the worker follows the parent's switches
     w->use_flags = c->use_flags;
     w->wait_budget_ms = c->wait_budget_ms;
     w->overlap_opt = c->overlap_opt;
@@ -464,9 +476,150 @@ int mid_batch_run(gprn_ctx* c, const BatchIo& io)
     w->sweep_order = c->sweep_order;
     w->pad_kb_opt = c->pad_kb_opt; w->pad_small_kb_opt = c->pad_small_kb_opt;
     w->prof.on = false;
+}
+
+int mid_batch_run(gprn_ctx* c, const BatchIo& io)
+{
+    MidBatch* m = (MidBatch*)c->mid_batch;
+    gprn_ctx* w = m->w;
+    mid_follow(c, w);
     // (an in-kernel dependency wait that gave up: both contexts go to the event schedule and the chunk runs again from the
     // caller's inputs)
     const int rc = with_event_fallback(c, "elbocalc_batch", [&](bool) { return mid_chunk(c, m, io); }, false, w);
     if (rc < 0 && !w->err.empty()) c->err = w->err;
     return rc;
+}
+
+// ------------------------------------------------------------------ prediction for many parameter vectors (gprn_predict_batch)
+// The inputs of a chunk through the pinned staging buffer -- programs (1.25e-12 on the diagonal, _gp.py:47) | mu | var |
+// jitters -- to the worker: the programs, the states, and the jitters into the head of its d_variance.
+static int mid_predict_stage(gprn_ctx* c, MidBatch* m, const PredBatchIo& io)
+{
+    gprn_ctx* w = m->w;
+    const int B = io.n, G = m->G;
+    const size_t pb = fill_program_bytes(), d = io.state;
+    char* const pin = m->pin_in;                           // (batch_stage_bytes: cap G programs and 2 cap (p N + d) doubles)
+    double* const mu_h = (double*)(pin + (size_t)m->cap * G * pb);
+    double* const var_h = mu_h + (size_t)B * d;
+    double* const jit_h = var_h + (size_t)B * d;
+    for (int b = 0; b < B; ++b) {
+        const double* kp = io.kparams + (size_t)b * io.n_kpar;
+        for (int g = 0; g < G; ++g) {
+            if (!fill_program_with(c->kspec[g], kp, pin + ((size_t)b * G + g) * pb, 1.25e-12)) {
+                c->err = "predict_batch: a kernel that is not an even function of t_i - t_j"; return GPRN_E_UNSUPPORTED;
+            }
+            kp += c->kspec[g].n_params;
+        }
+    }
+    memcpy(mu_h, io.mu, (size_t)B * d * sizeof(double));
+    memcpy(var_h, io.var, (size_t)B * d * sizeof(double));
+    if (io.jitters) memcpy(jit_h, io.jitters, (size_t)B * io.p * sizeof(double));
+    hipStream_t st = w->stream;
+    HIP_TRY(c, hipMemcpyAsync(m->programs, pin, (size_t)B * G * pb, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(w->d_mu, mu_h, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(w->d_var, var_h, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
+    if (io.jitters) HIP_TRY(c, hipMemcpyAsync(w->d_variance, jit_h, (size_t)B * io.p * sizeof(double), hipMemcpyHostToDevice, st));
+    return GPRN_OK;
+}
+
+// slots = evaluations x latent GPs in the set-up's order (slot = evaluation * G + latent GP); slot_gp: the state's row
+static Phase mid_predict_phase(const gprn_ctx* w, const MidBatch* m, int B)
+{
+    return Phase{m->d_ptr_block + m->o_pred, m->d_int_block + m->i_row_pred, B * m->G, 0, w->d_info,
+                 mid_ev(m, m->d_int_block + m->i_ev_setup), w->N, w->ld, w->T};
+}
+
+// One chunk of evaluations (n <= cap): gprn_predict's steps (api_more.hip predict_impl) with batch = evaluations x latent
+// GPs.  Launches per chunk: one symmetric fill, one factorisation, X mu and X^T (X mu) (three launches); per block of at most
+// ld prediction times one rectangular fill, one tile product, one row kernel and, for the out_* pair, the combination.  The
+// per-slot vectors of the worker carry the block's rows at pitch ld: k** in d, the latent means in pred, the latent
+// variances in s, the outputs in z and cs.  Restartable (everything it reads is the caller's).
+static int mid_predict_chunk(gprn_ctx* c, MidBatch* m, const PredBatchIo& io)
+{
+    gprn_ctx* w = m->w;
+    const int B = io.n, G = m->G, p = m->p, N = m->N, ld = m->ld, T = w->T, ns = io.ns, nslots = B * G;
+    hipStream_t st = w->stream;
+    TRY(mid_predict_stage(c, m, io));
+    const Phase pred = mid_predict_phase(w, m, B);
+    TRY(launch_fill_batch(w, m->programs, (double* const*)(m->d_ptr_block + m->o_kptr2), nslots, nullptr,
+                          (const double* const*)(m->d_ptr_block + m->o_diag)));
+    HIP_TRY(c, hipMemsetAsync(w->d_info, 0, 3 * (size_t)w->nslot * sizeof(int), st));
+    TRY(factor_invert(w, pred, true));
+    TRY(vec_lower_matvec(w, pred, BUF_X, w->d_mu, N, 1, w->d_u));      // u = X mu (the state's row of the slot's evaluation)
+    TRY(vec_colops(w, pred));                                           // ct = X^T u
+    int* const info_h = (int*)((double*)m->pin_out + (size_t)ELBO_LEAD * m->cap * 4);
+    HIP_TRY(c, hipMemcpyAsync(info_h, w->d_info, (size_t)nslots * sizeof(int), hipMemcpyDeviceToHost, st));
+    // W^T = K* X^T, one block of 128 rows of K* after the other: a ragged last block of t* runs a prefix of the list
+    std::vector<TileTask> tasks;
+    for (int bt = 0; bt < T; ++bt)
+        for (int at = 0; at < T; ++at)
+            tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE, (int64_t)bt * GPRN_TILE * ld,
+                                     (int64_t)at * GPRN_TILE * ld, (at + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_X,
+                                     tile_modes(CM_SET, 0, 0)});
+    CallScratch scr(w);
+    double* d_ts = nullptr;
+    TileTask* d_t = nullptr;
+    TRY(scr.alloc(&d_ts, ns));
+    HIP_TRY(c, hipMemcpyAsync(d_ts, io.tstar, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, st));
+    TRY(scr.tasks(&d_t, tasks));
+    double *const kss = w->d_d, *const lmean = w->d_pred, *const lvar = w->d_s, *const omean = w->d_z, *const ovar = w->d_cs;
+    const size_t row = sizeof(double);
+    for (int t0 = 0; t0 < ns; t0 += ld) {
+        const int nsb = std::min(ld, ns - t0), nsb_pad = ((nsb + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+        TRY(launch_fill_rect_batch(w, m->programs, (double* const*)(m->d_ptr_block + m->o_kptr), nslots, d_ts + t0, nsb, nsb_pad,
+                                   kss, ld));
+        TRY(launch_tiles(w, d_t, (size_t)(nsb_pad / GPRN_TILE) * T, pred.ptrs, nslots, ld, GPRN_T_UPDATE));
+        TRY(vec_pred_rows(w, pred, nsb, ld, w->d_ct, kss, lmean, lvar));
+        if (io.lat_mean) {
+            HIP_TRY(c, hipMemcpy2DAsync(io.lat_mean + t0, ns * row, lmean, ld * row, nsb * row, nslots, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpy2DAsync(io.lat_var + t0, ns * row, lvar, ld * row, nsb * row, nslots, hipMemcpyDeviceToHost, st));
+        }
+        if (io.out_mean) {
+            TRY(vec_predict_outputs(w, B, nsb, ld, lmean, lvar, w->d_variance, omean, ovar));
+            HIP_TRY(c, hipMemcpy2DAsync(io.out_mean + t0, ns * row, omean, ld * row, nsb * row, (size_t)B * p, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpy2DAsync(io.out_var + t0, ns * row, ovar, ld * row, nsb * row, (size_t)B * p, hipMemcpyDeviceToHost, st));
+        }
+        // (the next block rewrites the rows these copies read, and the caller's arrays are pageable)
+        HIP_TRY(c, hipStreamSynchronize(st));
+    }
+    TRY(factor_check_waits(w));
+    // pivot verdicts: per slot on the device, the first failing latent GP's per evaluation here
+    for (int b = 0; b < B; ++b) {
+        io.info[b] = 0;
+        for (int g = 0; g < G && !io.info[b]; ++g) io.info[b] = std::max(0, info_h[(size_t)b * G + g]);
+    }
+    return GPRN_OK;
+}
+
+int mid_predict_run(gprn_ctx* c, const PredBatchIo& io)
+{
+    MidBatch* m = (MidBatch*)c->mid_batch;
+    gprn_ctx* w = m->w;
+    mid_follow(c, w);
+    const int rc = with_event_fallback(c, "predict_batch", [&](bool) { return mid_predict_chunk(c, m, io); }, false, w);
+    if (rc < 0 && !w->err.empty()) c->err = w->err;
+    return rc;
+}
+
+int mid_predict_fill_test(gprn_ctx* c, const PredBatchIo& io, int eval, int gp, double* K_out, double* Ks_out, double* kss_out)
+{
+    MidBatch* m = (MidBatch*)c->mid_batch;
+    gprn_ctx* w = m->w;
+    const int N = m->N, ld = m->ld, ns = io.ns, nslots = io.n * m->G;
+    const int ns_pad = ((ns + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+    const size_t s = (size_t)eval * m->G + gp, nn = (size_t)ld * ld;
+    TRY(mid_predict_stage(c, m, io));
+    CallScratch scr(w);
+    double* d_ts = nullptr;
+    TRY(scr.alloc(&d_ts, ns));
+    HIP_TRY(c, hipMemcpyAsync(d_ts, io.tstar, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, w->stream));
+    TRY(launch_fill_batch(w, m->programs, (double* const*)(m->d_ptr_block + m->o_kptr2), nslots, nullptr,
+                          (const double* const*)(m->d_ptr_block + m->o_diag)));
+    TRY(launch_fill_rect_batch(w, m->programs, (double* const*)(m->d_ptr_block + m->o_kptr), nslots, d_ts, ns, ns_pad, w->d_d, ld));
+    const size_t row = sizeof(double);
+    HIP_TRY(c, hipMemcpy2DAsync(K_out, N * row, m->Bw + s * nn, ld * row, N * row, N, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(c, hipMemcpy2DAsync(Ks_out, N * row, m->K + s * nn, ld * row, N * row, ns, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(c, hipMemcpyAsync(kss_out, w->d_d + s * ld, ns * row, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(c, hipStreamSynchronize(w->stream));
+    return GPRN_OK;
 }

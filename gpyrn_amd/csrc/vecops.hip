@@ -909,3 +909,38 @@ int vec_pred_rows(gprn_ctx* c, const Phase& ph, int ns, int ns_pad, const double
                        (double* const*)ph.ptrs, ns, ph.N, ph.ld, ns_pad, sol, kss, mean, var);
     LAUNCH_END(c);
 }
+
+// ---- many parameter vectors side by side (gprn_predict_batch): outputs from latent rows, meanfield.py:1346-1373 --
+//   mean_i = sum_j f_j w_ji,   var_i = sum_j [w_ji^2 v_fj + v_wji (v_fj + f_j^2) + jitter_i^2]
+// (the jitter once per node j, as the reference has it), rounded operation by operation as NumPy does.  One thread per
+// (evaluation, output, t*), consecutive threads at consecutive t*: 4 q coalesced reads, two writes.  grid (ns / 256, p, n_eval)
+__global__ __launch_bounds__(256)
+void k_predict_outputs_b(int q, int p, int ns, size_t pitch, const double* __restrict__ lat_mean,
+                         const double* __restrict__ lat_var, const double* __restrict__ jit,
+                         double* __restrict__ out_mean, double* __restrict__ out_var)
+{
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y, b = blockIdx.z;
+    if (t >= ns) return;
+    const size_t slot0 = (size_t)b * q * (p + 1);
+    const double jt = jit[(size_t)b * p + i], j2 = jt * jt;
+    double m = 0.0, v = 0.0;
+    for (int j = 0; j < q; ++j) {
+        const size_t f_at = (slot0 + j) * pitch + t, w_at = (slot0 + q + (size_t)j * p + i) * pitch + t;
+        const double f = lat_mean[f_at], vf = lat_var[f_at], w = lat_mean[w_at], vw = lat_var[w_at];
+        m += f * w;
+        v += w * w * vf + vw * (vf + f * f) + j2;
+    }
+    out_mean[((size_t)b * p + i) * pitch + t] = m;
+    out_var[((size_t)b * p + i) * pitch + t] = v;
+}
+
+int vec_predict_outputs(gprn_ctx* c, int n_eval, int ns, size_t pitch, const double* lat_mean, const double* lat_var,
+                        const double* jit, double* out_mean, double* out_var)
+{
+    if (n_eval <= 0 || ns <= 0) return GPRN_OK;
+    prof_begin(c, GPRN_T_VEC);
+    hipLaunchKernelGGL(k_predict_outputs_b, dim3((ns + 255) / 256, c->p, n_eval), dim3(256), 0, c->stream, c->q, c->p, ns, pitch,
+                       lat_mean, lat_var, jit, out_mean, out_var);
+    LAUNCH_END(c);
+}

@@ -1138,6 +1138,140 @@ class inference:
                 v0.append(np.ravel(var))
         return ctx, np.array(kp), np.array(yr), np.array(jt), np.array(m0), np.array(v0)
 
+    # ------------------------------------------------ prediction for many vectors
+    def _predict_stage(self, sets, tstar):
+        """The B problems of a side-by-side prediction laid out for ``Context.predict_batch``: ``(ctx, kernel_params (B,
+        n_kpar), jitters (B, p), mean functions at tstar (B, p, n*))`` -- or None where the side-by-side form does not
+        apply (a sharded object, N > ``batch_max_N``, a kernel without a device program, expressions that change shape from
+        one vector to the next).  A data mask is no obstacle: prediction reads only the state.  The kernel programs go to
+        the device; the object's parameters end at the last vector."""
+        if self._comm is not None or self.N > self.batch_max_N:
+            return None
+        n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
+        if any(x.ndim != 1 or x.size not in (n_free, n_all) for x in sets):
+            return None                                        # (the one-by-one form raises the reference's ValueError)
+        ctx = self._backend()
+        kp, jt, mv = [], [], []
+        shape_ref = None
+        for x in sets:
+            self.set_parameters(x)
+            nodes, weights, means, jitters = self._get_components()
+            specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
+            if any(sp[0] != 'device' for sp in specs):
+                return None
+            shape = tuple((sp[1], sp[3]) for sp in specs)
+            if shape_ref is None:
+                shape_ref = shape
+                for gp, sp in enumerate(specs):                # the programs the library substitutes the parameters into
+                    self._send_spec(ctx, gp, sp)
+                self._prior_key = None                         # (the object's own factors are stale now)
+            elif shape != shape_ref:
+                return None
+            kp.append(np.concatenate([sp[2] for sp in specs]))
+            jt.append(np.asarray(jitters, dtype=float))
+            mv.append(np.array(np.array_split(self._mean(means, tstar), self.p)))
+        return ctx, np.array(kp), np.array(jt), np.array(mv)
+
+    def _final_states(self, sets, max_iter):
+        """Each vector's ``ELBOcalc`` loop as ``nELBO_batch`` runs it -- side by side from the state the object holds where
+        ``_batchable()`` holds, else one after the other, each warm-started by its predecessor -- and the state each loop
+        ended in: ``(mu (B, p+1, q, N), var)``.  The object keeps what ``nELBO_batch`` would keep."""
+        if len(sets) > 1 and self._batchable():
+            staged = self._batch_stage(sets)
+            if staged is not None:
+                ctx, kp, yr, jt, m0, v0 = staged
+                res = ctx.elbocalc_batch(kp, yr, jt, m0, v0, 10000 if max_iter is None else int(max_iter), want_state=True)
+                if res is not None:
+                    self._batch_keep(res)
+                    return res[4], res[5]
+        mus, vars_ = [], []
+        for x in sets:
+            self.set_parameters(x)
+            _, mu, var, _ = self.ELBOcalc(self.nodes, self.weights, self.means, self.jitters, max_iter=max_iter,
+                                          mu='previous', var='previous')
+            mus.append(mu)
+            vars_.append(var)
+        return np.array(mus), np.array(vars_)
+
+    def predict_batch(self, parameter_sets, tstar=None, states=None, max_iter=None, separate=False):
+        """
+        ``_Prediction`` for several free-parameter vectors -- the step that follows an ``mcmc`` run, whose posterior
+        predictive averages the prediction over the hyper-parameter vectors the chain kept (the reference calls
+        ``_Prediction`` once per vector, meanfield.py:1289-1381).  Not in the reference.
+
+        ``states = (mu (B, ...), var (B, ...))`` predicts vector b from state b.  ``states=None`` first runs each vector's
+        ``ELBOcalc`` loop exactly as ``nELBO_batch`` does (same shared warm start, same state and parameters kept by the
+        object afterwards; side by side where that applies, else one by one) and predicts from each loop's final state.
+
+        Where every kernel has a device program the B predictions run SIDE BY SIDE on the GPU (``gprn_predict_batch``):
+        every latent GP of every vector is filled, factored and solved in the same launches, the times ``tstar`` going in
+        blocks, and the per-output combination is formed on the device too.  A data mask is no obstacle.  Otherwise --
+        user-defined kernels, expressions that change shape between vectors, a sharded object, N > ``batch_max_N`` -- one
+        ``_Prediction`` per vector, same return value.  Mean functions are evaluated per vector on the host.
+
+        Returns (mean (B, N*, p), variance (B, N*, p)) and, with `separate`, the latent means (B, G, N*): nodes first,
+        then weight (j, i) at q + j p + i.
+        """
+        assert self._components_set, _NOT_SET
+        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        B = len(sets)
+        if B < 1:
+            raise ValueError('predict_batch: no parameter vector')
+        tstar = np.asarray(self.time, dtype=float) if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
+        if tstar.ndim != 1 or tstar.size < 1:
+            raise ValueError('predict_batch: tstar must be a non-empty vector of times')
+        d = (self.p + 1) * self.q * self.N
+        if states is None:
+            states = self._final_states(sets, max_iter)
+        try:
+            mu_b, var_b = (np.asarray(a, dtype=float) for a in states)
+        except (TypeError, ValueError) as exc:
+            raise ValueError('predict_batch: states must be the pair (mu, var)') from exc
+        if mu_b.size != B * d or var_b.size != B * d or mu_b.shape[0] != B or var_b.shape[0] != B:
+            raise ValueError(f'predict_batch: states must be two arrays of {B} states of {d} values, got {mu_b.shape} and '
+                             f'{var_b.shape}')
+        mu_b, var_b = mu_b.reshape(B, d), var_b.reshape(B, d)
+        staged = self._predict_stage(sets, tstar)
+        res = None
+        if staged is not None:
+            ctx, kp, jt, meanvals = staged
+            res = ctx.predict_batch(kp, mu_b, var_b, tstar, jitters=jt, latent=separate, outputs=True)
+        if res is not None:
+            lat_mean, _, out_mean, out_var, info = res
+            self.last_info = int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
+            mean = np.transpose(out_mean + meanvals, (0, 2, 1))
+            var = np.transpose(out_var, (0, 2, 1))
+            return (mean, var, lat_mean) if separate else (mean, var)
+        # one by one
+        shape = (self.p + 1, self.q, self.N)
+        means_, vars_, lats = [], [], []
+        for b, x in enumerate(sets):
+            self.set_parameters(x)
+            m_, v_, parts = self._Prediction(tstar=tstar, mu=mu_b[b].reshape(shape), var=var_b[b].reshape(shape), separate=True)
+            means_.append(m_)
+            vars_.append(v_)
+            lats.append(np.concatenate([np.asarray(parts[0], dtype=float), np.asarray(parts[1], dtype=float)]))
+        mean, var = np.array(means_), np.array(vars_)
+        return (mean, var, np.array(lats)) if separate else (mean, var)
+
+    def posterior_predictive(self, parameter_sets, tstar=None, weights=None, **kw):
+        """
+        The first two moments of the mixture of ``predict_batch``'s predictions over `parameter_sets` -- the posterior
+        predictive of a chain: ``mean = sum_b w_b mean_b``, ``var = sum_b w_b (var_b + mean_b^2) - mean^2``.  `weights`
+        (B,): default uniform, normalised to sum 1.  Further keywords go to ``predict_batch`` (``states``, ``max_iter``).
+        Returns (mean (N*, p), variance (N*, p)).
+        """
+        kw.pop('separate', None)
+        mean_b, var_b = self.predict_batch(parameter_sets, tstar=tstar, **kw)
+        B = mean_b.shape[0]
+        w = np.full(B, 1.0 / B) if weights is None else np.asarray(weights, dtype=float)
+        if w.shape != (B,) or np.any(w < 0) or not np.sum(w) > 0:
+            raise ValueError(f'posterior_predictive: weights must be {B} non-negative numbers with a positive sum')
+        w = (w / np.sum(w))[:, None, None]
+        mean = np.sum(w * mean_b, axis=0)
+        var = np.sum(w * (var_b + mean_b * mean_b), axis=0) - mean * mean
+        return mean, var
+
     # ------------------------------------------------------------ gradients
     def grad_ELBO(self, mean_sweeps=8, mean_start=None, total=False, fused=False):
         """

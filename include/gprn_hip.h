@@ -365,6 +365,31 @@ int gprn_elbocalc_batch_grad(gprn_ctx* ctx, int n_eval, const double* kernel_par
                              int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
                              double* mu_out, double* var_out, double* grad_out);
 
+/* gprn_predict for n_eval parameter vectors side by side -- the posterior predictive of a chain: the reference's
+ * inference._Prediction (meanfield.py:1289-1381) over _gp.GP.prediction (_gp.py:107-138), once per hyper-parameter vector
+ * that inference.mcmc kept.
+ *   kernel_params [n_eval][n_kernel_params]: as for gprn_elbocalc_batch;
+ *   mu, var [n_eval][(p + 1) q N]: each evaluation's variational state;
+ *   jitters [n_eval][p]: read for the out_* pair only (may be NULL without it);
+ *   tstar [ns]: the prediction times, the same for every evaluation.
+ * lat_mean, lat_var [n_eval][G][ns] (or both NULL): row b is what gprn_predict returns at tstar after every latent GP's
+ * kernel parameters were set to vector b and gprn_set_muvar(mu_b, var_b) was called.
+ * out_mean, out_var [n_eval][p][ns] (or both NULL): the combination inference._Prediction forms from those rows, per output
+ * i: sum_j f_j w_ji, and sum_j [w_ji^2 v_fj + v_wji (v_fj + f_j^2) + jitter_i^2] -- the jitter once per NODE, as the
+ * reference has it; the mean functions are the caller's to add.  With only this pair the read-back is 2 n_eval p ns doubles.
+ * At least one pair must be given.  info [n_eval]: LAPACK-style, the first failing latent GP's pivot verdict of each
+ * evaluation; its rows then hold whatever gprn_predict leaves there (NaN), the other evaluations are untouched.
+ * One code path for every N (csrc/midn.hip): the worker context and slabs of gprn_elbocalc_batch hold, per (evaluation,
+ * latent GP), K + 1.25e-12 I + diag v and its factor, X = L^-1, a block of K* and of (X K*^T)^T; t* goes in blocks of at
+ * most ld = 128 ceil(N / 128) rows, the factorisation runs once per chunk of evaluations.  Chunks and halving on
+ * GPRN_E_NOMEM as gprn_elbocalc_batch_grad ("batch_mem_mb"; "batch_chunk" reports this call's chunk too).
+ * The context's own state, factors and validity flags are not touched: a gprn_sweep right after the call returns the bits
+ * it would have returned before it.  A data mask is no obstacle (prediction reads only the state).  GPRN_E_UNSUPPORTED: a
+ * communicator, a latent GP without a device program, a program that is not even in t_i - t_j. */
+int gprn_predict_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, int n_kernel_params,
+                       const double* mu, const double* var, const double* jitters, int ns, const double* tstar,
+                       double* lat_mean, double* lat_var, double* out_mean, double* out_var, int* info);
+
 /* ---- per-context switches (tests, experiments; nothing in the reference corresponds) ----
  * name: "flags" (1: the factorisation's cross-stream dependencies travel through device-side flags and
  * in-kernel waits, 0: HIP events -- chosen automatically per context, and latched to 0 after an in-kernel
@@ -436,6 +461,14 @@ int gprn_test_tile_launch(gprn_ctx* ctx, int ld, int nbatch, double* bufs, int n
  * its pointers as kernel arguments (up to 16 matrices); 0: it reads them from the device table.  Same checks. */
 int gprn_test_tile_step(gprn_ctx* ctx, int nbatch, double* bufs, int which, int table, int n_l, int n_x,
                         const int64_t* tasks);
+/* The two fills of prediction for ONE slot, for tests/test_predict_batch_gpu.py: K + nugget + diag(v) of latent GP `gp` at
+ * the data times (K_out, N x N) and K*, k** at tstar (Ks_out ns x N, kss_out ns; ns <= 128 ceil(N / 128)), for evaluation
+ * `eval` of n_eval parameter vectors and states (layouts of gprn_predict_batch).  batched != 0: through the batched fills of
+ * gprn_predict_batch over all n_eval x G slots, reading slot (eval, gp) back BEFORE anything is factored; 0: through the
+ * fills gprn_predict uses (one launch per matrix) with vector `eval` substituted into the latent GP's program. */
+int gprn_test_predict_fill(gprn_ctx* ctx, int batched, int n_eval, const double* kernel_params, int n_kernel_params,
+                           const double* var, int eval, int gp, int ns, const double* tstar,
+                           double* K_out, double* Ks_out, double* kss_out);
 
 #ifdef __cplusplus
 }
