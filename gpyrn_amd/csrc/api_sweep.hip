@@ -777,7 +777,8 @@ extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* k
         !iterations || !converged || !info || (!mu_out != !var_out) || (flags & ~GPRN_BATCH_FORCED))
         return bad(c, "elbocalc_batch: bad argument");
     if (grad_out && max_iter < 1) return bad(c, "elbocalc_batch_grad: a gradient needs a committed sweep (max_iter >= 1)");
-    if (c->d_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
+    // (side by side every evaluation starts from one shared state: under a mask that is the caller's choice, option "batch_mask")
+    if (c->d_mask && !c->batch_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "elbocalc_batch: call set_owners first");

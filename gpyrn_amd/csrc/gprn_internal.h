@@ -100,6 +100,27 @@ struct EvalMap {
     size_t G;                  // log det K: G
 };
 
+// The rows U of many evaluations side by side (mask.hip's _b kernels; gprn_elbocalc_batch under option "batch_mask"): one
+// lane per (evaluation, latent GP of the phase with a non-empty U).  The mask, and with it every U, is the data's: the same
+// for all evaluations.
+struct MaskLane {
+    const double *K, *s, *ct;  // the latent GP's prior matrix of this evaluation, its s = sqrt(d) and ct = X^T X z (ld each)
+    double *WT, *C;            // upad x ld each: K[U, :] diag(s), then WT X^T
+    double *mu, *var;          // the evaluation's state copy the half-sweep writes, (p + 1, q, N)
+    const int* done;           // the evaluation's stop word (one tile: its workgroups are no-ops once it is set), or null
+    int gp;
+};
+struct MaskBatch {
+    const MaskLane* lanes = nullptr;   // [n] (device)
+    double** tab = nullptr;            // [n][GPRN_NBUF]: BUF_X = the slot's X, BUF_K = WT, BUF_KLINV = C
+    int n = 0;                         // lanes of the next launch
+    int upad = 0;                      // max |U| over the phase's entries, rounded up to 128
+    const TileTask* tasks = nullptr;   // C = WT X^T (mask_prepare's list of the phase)
+    size_t ntasks = 0;
+    const int *U = nullptr, *nU = nullptr;   // gprn_ctx::d_mask_U, d_mask_nU
+    int upad_all = 0;
+};
+
 struct DeviceStreams {         // one per device and process, see gprn_create
     hipStream_t s[4] = {nullptr, nullptr, nullptr, nullptr};
     int device = 0, refs = 0;
@@ -254,6 +275,8 @@ struct gprn_ctx {
     size_t mask_ntasks[2] = {0, 0};
     int mask_upad_ph[2] = {0, 0};        // max |U| over the entries, rounded up to 128
     bool mask_ready = false;             // the buffers, tables and task lists above match the problem and the slots
+    int batch_mask = 0;                  // gprn_set_option "batch_mask": gprn_elbocalc_batch* run under a data mask (default: refused)
+    MaskBatch mask_batch[2];             // a batch's worker context (midn.hip): the lanes of its node / weight phase
 
     // ---- small-N path (smalln.hip): problems of one or two tiles run a half-sweep as ONE launch, one workgroup per latent GP
     int small_opt = -1;              // gprn_set_option "small_path": 0 never, else wherever it applies (small_applies)
@@ -578,6 +601,8 @@ int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::fu
 // mask.hip: the rows U of the phase's latent GPs under a data mask (no-op without one), behind the phase's finalize; the
 // state (mu, var) they go to; done: the small path's stop word (nothing to do once it is set), or null
 int mask_rows(gprn_ctx* c, const Phase& ph, bool weights, double* mu, double* var, const int* done);
+// ... of the lanes of a batch (a Phase with an EvalMap gets here from mask_rows: the context's mask_batch)
+int mask_rows_lanes(gprn_ctx* c, const MaskBatch& mb, int N, int ld);
 int mask_prepare(gprn_ctx* c);       // buffers, tables and task lists for the current slots (build_tables: the set-up)
 void mask_free(gprn_ctx* c);
 void mask_invalidate(gprn_ctx* c);   // the slots changed (build_tables rebuilds them)

@@ -77,6 +77,78 @@ void k_mask_rows(double* const* __restrict__ ptrs, double* const* __restrict__ m
     }
 }
 
+// ---- the same two kernels for many evaluations side by side: lane = (evaluation, latent GP with a U), everything an
+// evaluation owns found through its MaskLane; a lane whose evaluation has stopped does nothing (its state stays its last trip's)
+// grid (ld / 256, upad, lanes)
+__global__ __launch_bounds__(256)
+void k_mask_gather_b(const MaskLane* __restrict__ lanes, const int* __restrict__ U, const int* __restrict__ nU, int upad_all,
+                     int N, int ld)
+{
+    const MaskLane a = lanes[blockIdx.z];
+    if (a.done && *a.done) return;
+    const int u = blockIdx.y, m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= ld) return;
+    double v = 0.0;
+    if (u < nU[a.gp] && m < N) {
+        const int n = U[(size_t)a.gp * upad_all + u];
+        v = a.K[(size_t)n * ld + m] * a.s[m];
+    }
+    a.WT[(size_t)u * ld + m] = v;
+}
+
+// grid (upad / 4, lanes)
+__global__ __launch_bounds__(256)
+void k_mask_rows_b(const MaskLane* __restrict__ lanes, const int* __restrict__ U, const int* __restrict__ nU, int upad_all,
+                   int N, int ld, int p, int q)
+{
+    const MaskLane a = lanes[blockIdx.y];
+    if (a.done && *a.done) return;
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int gp = a.gp;
+    if (u >= nU[gp]) return;
+    const int n = U[(size_t)gp * upad_all + u];
+    const double* WT = a.WT + (size_t)u * ld;
+    const double* C = a.C + (size_t)u * ld;
+    double sa = 0.0, sb = 0.0;
+    for (int m = lane; m < N; m += 64) {
+        sa += WT[m] * a.ct[m];
+        sb += C[m] * C[m];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sa += __shfl_down(sa, o, 64);
+        sb += __shfl_down(sb, o, 64);
+    }
+    if (lane == 0) {
+        size_t row;
+        if (gp < q) row = gp;
+        else { const int kk = gp - q, j = kk / p, i = kk % p; row = (size_t)(1 + i) * q + j; }
+        const double Knn = a.K[(size_t)n * ld + n];
+        a.mu[row * N + n] = sa;
+        a.var[row * N + n] = Knn - sb;
+    }
+}
+
+// gather, C = WT X^T, rows -- over mb.n lanes (the callers keep mb.n within a grid's 65 535)
+int mask_rows_lanes(gprn_ctx* c, const MaskBatch& mb, int N, int ld)
+{
+    if (!mb.n) return GPRN_OK;
+    if (!mb.lanes || !mb.tab || !mb.tasks || mb.n > 65535)
+        return bad(c, "elbocalc_batch: the data mask's lanes are not set up");
+    prof_begin(c, GPRN_T_VEC);
+    hipLaunchKernelGGL(k_mask_gather_b, dim3(ld / 256 + (ld % 256 ? 1 : 0), mb.upad, mb.n), dim3(256), 0, c->stream,
+                       mb.lanes, mb.U, mb.nU, mb.upad_all, N, ld);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    TRY(launch_tiles(c, mb.tasks, mb.ntasks, mb.tab, mb.n, ld, GPRN_T_UPDATE));
+    prof_begin(c, GPRN_T_VEC);
+    hipLaunchKernelGGL(k_mask_rows_b, dim3(mb.upad / 4, mb.n), dim3(256), 0, c->stream,
+                       mb.lanes, mb.U, mb.nU, mb.upad_all, N, ld, c->p, c->q);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
 void mask_invalidate(gprn_ctx* c)
 {
     c->mask_ready = false;
@@ -154,6 +226,7 @@ int mask_prepare(gprn_ctx* c)
 int mask_rows(gprn_ctx* c, const Phase& ph, bool weights, double* mu, double* var, const int* done)
 {
     if (!c->d_mask || !ph.nslots) return GPRN_OK;
+    if (ph.ev.slot_eval) return mask_rows_lanes(c, c->mask_batch[weights ? 1 : 0], ph.N, ph.ld);   // (a batch's worker: midn.hip)
     if (!c->mask_ready) return bad(c, "sweep: the data mask's buffers are not set up (gprn_factor_priors after gprn_set_mask)");
     const int w = weights ? 1 : 0, upad = c->mask_upad_ph[w], ne = c->mask_n[w];
     if (!ne) return GPRN_OK;
@@ -213,6 +286,9 @@ extern "C" int gprn_set_mask(gprn_ctx* c, const uint8_t* mask)
                     if (!mask[(size_t)i * N + n]) U[q + j * p + i].push_back(n);
     }
     mask_free(c);
+    // (the batches' cached argument blocks, lanes and slabs are the old mask's: gprn_elbocalc_batch under "batch_mask")
+    small_batch_free(c);
+    mid_batch_free(c);
     dev_free(c->d_mask); dev_free(c->d_mask_U); dev_free(c->d_mask_nU);
     c->h_mask.clear(); c->mask_U.clear(); c->mask_upad = 0;
     c->factored = false;                 // the set-up runs on the path the sweeps will take (small_applies)

@@ -68,14 +68,35 @@ struct MidBatch {
     // offsets into the blocks
     size_t o_kptr = 0, o_kptr2 = 0, o_setup = 0, o_kinv = 0, o_pred = 0, o_diag = 0, o_node = 0, o_weight = 0;
     size_t i_gp_setup = 0, i_ev_setup = 0, i_row_pred = 0, i_gp_node = 0, i_ev_node = 0, i_gp_weight = 0, i_ev_weight = 0, i_evals = 0;
+    // under a data mask (option "batch_mask"): per phase the latent GPs with a non-empty U ("entries", the same for every
+    // evaluation); WT and C per (evaluation, entry); the lanes of mask.hip's batched rows over the ACTIVE evaluations and the tile
+    // product's pointer rows (tab_mask, the tail of d_ptr_block), rebuilt with the node-major tables (mid_upload_active)
+    const uint8_t* mask = nullptr;    // the parent's mask the slabs were sized for (null: none)
+    std::vector<int> mask_gps[2];
+    int mask_upad = 0;
+    double* mask_wc = nullptr;        // [cap][entries of both phases][2][mask_upad * ld]
+    MaskLane* d_mask_lanes = nullptr; // [cap entries node | cap entries weight]
+    size_t o_mask[2] = {0, 0};        // [lane][GPRN_NBUF] of each phase in d_ptr_block
 };
+
+// the latent GPs of a phase with a non-empty U under the parent's mask, when batches run under it
+static std::vector<int> mid_mask_entries(const gprn_ctx* c, bool weights)
+{
+    std::vector<int> e;
+    if (c->d_mask && c->batch_mask)
+        for (int g = weights ? c->q : 0; g < (weights ? c->G : c->q); ++g)
+            if (!c->mask_U[g].empty()) e.push_back(g);
+    return e;
+}
 
 static void mid_free_slabs(MidBatch* m)
 {
-    void* dev[] = {m->K, m->KL, m->Bw, m->Xw, m->Kinv, m->q1_scratch, m->keep_s, m->programs, m->d_ptr_block, m->d_int_block};
+    void* dev[] = {m->K, m->KL, m->Bw, m->Xw, m->Kinv, m->q1_scratch, m->keep_s, m->programs, m->d_ptr_block, m->d_int_block,
+                   m->mask_wc, m->d_mask_lanes};
     for (void* ptr : dev) if (ptr) hipFree(ptr);
     m->K = m->KL = m->Bw = m->Xw = m->Kinv = m->q1_scratch = m->keep_s = nullptr;
     m->programs = nullptr; m->d_ptr_block = nullptr; m->d_int_block = nullptr;
+    m->mask_wc = nullptr; m->d_mask_lanes = nullptr;
     if (m->pin_in) hipHostFree(m->pin_in);
     if (m->pin_out) hipHostFree(m->pin_out);
     if (m->pin_tab) hipHostFree(m->pin_tab);
@@ -101,7 +122,10 @@ static size_t mid_bytes_per_eval(const gprn_ctx* c)
     size_t dbl = (4 * G + (size_t)(c->q - 1)) * nn             // K, KL, B, X, K_j^-1
                + G * ld * (7 + 2 * (size_t)c->T + 2)           // per-slot vectors, partial column sums, finalising terms
                + (size_t)c->q * (c->q - 1) / 2 * ld + 2 * d + 2 * (size_t)c->p * c->N + 64;
-    return dbl * sizeof(double);
+    // (under a data mask: WT and C of every latent GP with a U, mask_upad x ld each, its lane and pointer row)
+    const size_t ne = mid_mask_entries(c, false).size() + mid_mask_entries(c, true).size();
+    dbl += ne * (2 * (size_t)c->mask_upad * ld + GPRN_NBUF);
+    return dbl * sizeof(double) + ne * sizeof(MaskLane);
 }
 
 // The worker context and the slabs for `want` evaluations (never more than the budget allows; at least one).
@@ -112,13 +136,18 @@ int mid_batch_reserve(gprn_ctx* c, int want, int* cap_out)
     // (a launch's grid y is the number of slots of a phase: cap x G stays far below its 65 535 limit)
     const int fit = (int)std::max<size_t>(1, std::min<size_t>(batch_budget_bytes(c) / per, (size_t)32768 / c->G));
     want = std::min(want, fit);
-    const bool same = m && m->N == c->N && m->p == c->p && m->q == c->q && m->ld == c->ld;
+    const uint8_t* const mask = c->batch_mask ? c->d_mask : nullptr;
+    const bool same = m && m->N == c->N && m->p == c->p && m->q == c->q && m->ld == c->ld && m->mask == mask;
     if (same && m->cap >= want && m->cap <= fit) { *cap_out = m->cap; return GPRN_OK; }
     if (m && !same) { mid_batch_free(c); m = nullptr; }
     if (!m) { m = new MidBatch(); c->mid_batch = m; }
     mid_free_slabs(m);
     const int N = c->N, p = c->p, q = c->q, G = c->G, ld = c->ld, T = c->T;
     m->N = N; m->p = p; m->q = q; m->G = G; m->ld = ld;
+    m->mask = mask;
+    m->mask_gps[0] = mid_mask_entries(c, false); m->mask_gps[1] = mid_mask_entries(c, true);
+    m->mask_upad = c->mask_upad;
+    const size_t ne0 = m->mask_gps[0].size(), ne_all = ne0 + m->mask_gps[1].size();
     // ---- the worker: the parent's problem, `cap` evaluations' worth of state and per-slot vectors
     if (!m->w) {
         const int rc = gprn_create(&m->w, c->device);
@@ -161,6 +190,10 @@ int mid_batch_reserve(gprn_ctx* c, int want, int* cap_out)
         TRY(dev_alloc(c, &m->q1_scratch, (size_t)cap * (q * (q - 1) / 2) * ld));
     }
     TRY(dev_alloc(c, &m->programs, (size_t)cap * G * fill_program_bytes()));
+    if (ne_all) {
+        TRY(dev_alloc(c, &m->mask_wc, (size_t)cap * ne_all * 2 * m->mask_upad * ld));
+        TRY(dev_alloc(c, &m->d_mask_lanes, (size_t)cap * ne_all));
+    }
     // ---- tables
     const size_t qp = (size_t)q * p;
     m->o_kptr = 0;
@@ -171,7 +204,9 @@ int mid_batch_reserve(gprn_ctx* c, int want, int* cap_out)
     m->o_diag = m->o_pred + nslot * GPRN_NBUF;
     m->o_node = m->o_diag + nslot;
     m->o_weight = m->o_node + (size_t)cap * q * GPRN_NBUF;
-    m->n_ptr = m->o_weight + (size_t)cap * qp * GPRN_NBUF;
+    m->o_mask[0] = m->o_weight + (size_t)cap * qp * GPRN_NBUF;
+    m->o_mask[1] = m->o_mask[0] + (size_t)cap * ne0 * GPRN_NBUF;
+    m->n_ptr = m->o_mask[0] + (size_t)cap * ne_all * GPRN_NBUF;
     m->i_gp_setup = 0; m->i_ev_setup = nslot;
     m->i_row_pred = 2 * nslot;
     m->i_gp_node = 3 * nslot; m->i_ev_node = m->i_gp_node + (size_t)cap * q;
@@ -181,7 +216,9 @@ int mid_batch_reserve(gprn_ctx* c, int want, int* cap_out)
     TRY(dev_alloc(c, &m->d_ptr_block, m->n_ptr));
     TRY(dev_alloc(c, &m->d_int_block, m->n_int));
     const size_t pin_out_bytes = (size_t)ELBO_LEAD * cap * 4 * sizeof(double) + 3 * nslot * sizeof(int) + 2 * (size_t)cap * d * sizeof(double) + 64;
-    HIP_TRY(c, hipHostMalloc((void**)&m->pin_tab, m->n_ptr * sizeof(double*) + m->n_int * sizeof(int), hipHostMallocDefault));
+    // (pointers | ints, padded to 8 bytes | the mask's lanes)
+    HIP_TRY(c, hipHostMalloc((void**)&m->pin_tab, m->n_ptr * sizeof(double*) + (m->n_int + 2) * sizeof(int) +
+                                                  (size_t)cap * ne_all * sizeof(MaskLane), hipHostMallocDefault));
     HIP_TRY(c, hipHostMalloc((void**)&m->pin_in, batch_stage_bytes(c, cap), hipHostMallocDefault));
     HIP_TRY(c, hipHostMalloc((void**)&m->pin_out, pin_out_bytes, hipHostMallocDefault));
     // the tables of the set-up never change: slot = evaluation * G + latent GP
@@ -247,6 +284,32 @@ static int mid_upload_active(gprn_ctx* c, MidBatch* m, const std::vector<int>& a
             hi[m->i_ev_weight + s] = act[a];
         }
     for (int a = 0; a < nA; ++a) hi[m->i_evals + a] = act[a];
+    // under a data mask: the lanes of the rows U -- the ACTIVE slots whose latent GP has one -- and their pointer rows, with
+    // the tables above (the rows ride in the same copy: the tail of the pointer block)
+    const size_t ne0 = m->mask_gps[0].size(), ne_all = ne0 + m->mask_gps[1].size();
+    if (ne_all) {
+        MaskLane* hl = (MaskLane*)(m->pin_tab + m->n_ptr * sizeof(double*) + ((m->n_int + 1) / 2) * 2 * sizeof(int));
+        const size_t d = (size_t)(p + 1) * q * m->N, wc = (size_t)m->mask_upad * m->ld;
+        for (int wt = 0; wt < 2; ++wt) {
+            const size_t ne = m->mask_gps[wt].size(), first = wt ? (size_t)m->cap * ne0 : 0;
+            for (size_t e = 0; e < ne; ++e)
+                for (int a = 0; a < nA; ++a) {
+                    const int g = m->mask_gps[wt][e], b = act[a];
+                    // (node-major slots: the per-slot vectors of the weight phase lie behind the q nA node slots)
+                    const size_t slot = wt ? (size_t)q * nA + (size_t)(g - q) * nA + a : (size_t)g * nA + a;
+                    const size_t sb = (size_t)b * G + g, ln = e * nA + a;
+                    double* const wtp = m->mask_wc + (((size_t)b * ne_all + (wt ? ne0 : 0) + e) * 2) * wc;
+                    hl[first + ln] = MaskLane{m->K + sb * nn, w->d_s + slot * m->ld, w->d_ct + slot * m->ld, wtp, wtp + wc,
+                                              w->d_mu + (size_t)b * d, w->d_var + (size_t)b * d, nullptr, g};
+                    double** const r = hp + m->o_mask[wt] + ln * GPRN_NBUF;
+                    r[BUF_B] = m->Bw + sb * nn; r[BUF_X] = m->Xw + sb * nn; r[BUF_K] = wtp; r[BUF_KLINV] = wtp + wc;
+                }
+            w->mask_batch[wt].lanes = m->d_mask_lanes + first;
+            w->mask_batch[wt].tab = m->d_ptr_block + m->o_mask[wt];
+            w->mask_batch[wt].n = (int)ne * nA;
+        }
+        HIP_TRY(c, hipMemcpyAsync(m->d_mask_lanes, hl, (size_t)m->cap * ne_all * sizeof(MaskLane), hipMemcpyHostToDevice, w->stream));
+    }
     // (two pieces each: the node and weight tables lie side by side in both blocks)
     HIP_TRY(c, hipMemcpyAsync(m->d_ptr_block + m->o_node, hp + m->o_node, (m->n_ptr - m->o_node) * sizeof(double*),
                               hipMemcpyHostToDevice, w->stream));
@@ -478,11 +541,32 @@ static void mid_follow(const gprn_ctx* c, gprn_ctx* w)
     w->prof.on = false;
 }
 
+// The worker BORROWS the parent's data mask for the length of a run (the mask is the data's: one for all evaluations) and
+// hands it back before anything could free it: free_problem(w) / gprn_destroy(w) never see the parent's device arrays.
+// With it phase_core takes the masked vec_prep / finalize instantiations and ends in mask_rows over the batch's lanes.
+struct MidMaskLoan {
+    gprn_ctx* w;
+    MidMaskLoan(gprn_ctx* c, gprn_ctx* w_, const MidBatch* m) : w(w_)
+    {
+        w->d_mask = const_cast<uint8_t*>(m->mask);
+        for (int wt = 0; wt < 2; ++wt) {
+            MaskBatch& mb = w->mask_batch[wt];
+            mb = MaskBatch{};
+            if (!m->mask || m->mask_gps[wt].empty()) continue;
+            mb.upad = c->mask_upad_ph[wt]; mb.tasks = c->d_mask_tasks[wt]; mb.ntasks = c->mask_ntasks[wt];
+            mb.U = c->d_mask_U; mb.nU = c->d_mask_nU; mb.upad_all = c->mask_upad;
+        }
+    }
+    ~MidMaskLoan() { w->d_mask = nullptr; w->mask_batch[0] = w->mask_batch[1] = MaskBatch{}; }
+};
+
 int mid_batch_run(gprn_ctx* c, const BatchIo& io)
 {
     MidBatch* m = (MidBatch*)c->mid_batch;
     gprn_ctx* w = m->w;
     mid_follow(c, w);
+    if (m->mask && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
+    const MidMaskLoan loan(c, w, m);
     // (an in-kernel dependency wait that gave up: both contexts go to the event schedule and the chunk runs again from the
     // caller's inputs)
     const int rc = with_event_fallback(c, "elbocalc_batch", [&](bool) { return mid_chunk(c, m, io); }, false, w);

@@ -482,6 +482,11 @@ void k_small_phase_m(SmallPhaseArgs a) { small_phase_body<WEIGHTS, T, true>(a); 
 template <bool WEIGHTS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
 void k_small_phase_b(const SmallPhaseArgs* __restrict__ lanes) { small_phase_body<WEIGHTS, 1>(lanes[blockIdx.y]); }
+// ... under a data mask (option "batch_mask"): kernels of their own, so that the unmasked ones keep their code and registers;
+// the selection costs no register (206 / 208 VGPRs + 104 AGPRs, as k_small_phase_b: DESIGN.md 7)
+template <bool WEIGHTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
+void k_small_phase_bm(const SmallPhaseArgs* __restrict__ lanes) { small_phase_body<WEIGHTS, 1, true>(lanes[blockIdx.y]); }
 
 template <int T>
 __global__ __launch_bounds__(256)
@@ -496,6 +501,14 @@ void k_small_tail_b(const SmallTailArgs* __restrict__ lanes, int sweep, int hist
     SmallTailArgs a = lanes[blockIdx.y];
     a.sweep = sweep; a.hist_at = hist_at; a.max_iter = max_iter;
     small_tail_body<T, false, FORCED>(a);
+}
+template <int T, bool FORCED = false>
+__global__ __launch_bounds__(256)
+void k_small_tail_bm(const SmallTailArgs* __restrict__ lanes, int sweep, int hist_at, int max_iter)
+{
+    SmallTailArgs a = lanes[blockIdx.y];
+    a.sweep = sweep; a.hist_at = hist_at; a.max_iter = max_iter;
+    small_tail_body<T, true, FORCED>(a);
 }
 
 template <int T, bool ACC>
@@ -600,6 +613,14 @@ struct SmallBatchMem {
     SmallPhaseArgs* phase_args = nullptr;   // [2 parity][2 phase][cap]
     SmallTailArgs* tail_args = nullptr;     // [2 parity][cap]
     SmallPriorArgs* prior_args = nullptr;   // [cap]
+    // under a data mask (option "batch_mask"): per phase the latent GPs with a non-empty U ("entries", the same for every
+    // evaluation), per (evaluation, entry) WT and C of 128 x ld each, the lanes of mask.hip's batched rows -- one set per
+    // parity, because mu_out / var_out alternate -- and the tile product's pointer rows
+    const uint8_t* mask = nullptr;    // the mask the argument blocks were made for (null: none)
+    int mask_ne[2] = {0, 0};
+    double* mask_wc = nullptr;        // [cap][ne node + ne weight][2][128 * ld]
+    MaskLane* mask_lanes = nullptr;   // [2 parity][cap ne node | cap ne weight], evaluation-major
+    double** mask_tab = nullptr;      // [cap ne node | cap ne weight][GPRN_NBUF]
     char *pin_in = nullptr, *pin_out = nullptr;
     double us_reserve = 0.0;          // GPRN_BATCH_TIMERS: what making room took, reported with the next chunk
 };
@@ -610,7 +631,8 @@ void small_batch_free(gprn_ctx* c)
     SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
     if (!m) return;
     void* dev[] = {m->mats, m->vecs, m->state, m->yv, m->scal, m->logdetK, m->out4, m->hist, m->ctl, m->info, m->gp_ids,
-                   m->ticket, m->ptrs, m->kptr_dense, m->programs, m->phase_args, m->tail_args, m->prior_args};
+                   m->ticket, m->ptrs, m->kptr_dense, m->programs, m->phase_args, m->tail_args, m->prior_args, m->mask_wc,
+                   m->mask_lanes, m->mask_tab};
     for (void* ptr : dev) if (ptr) hipFree(ptr);
     if (m->pin_in) hipHostFree(m->pin_in);
     if (m->pin_out) hipHostFree(m->pin_out);
@@ -620,29 +642,46 @@ void small_batch_free(gprn_ctx* c)
 
 // evaluations one chunk may hold: what the memory budget pays for (4 G + q matrices of ld^2 doubles each and small change
 // per evaluation), 16 at least -- an emcee run with thousands of walkers is split, not refused
+// the latent GPs of a phase with a non-empty U under the context's mask (one rank: slot = latent GP, nodes first)
+static std::vector<int> small_mask_entries(const gprn_ctx* c, bool weights)
+{
+    std::vector<int> e;
+    if (c->d_mask)
+        for (int g = weights ? c->q : 0; g < (weights ? c->G : c->q); ++g)
+            if (!c->mask_U[g].empty()) e.push_back(g);
+    return e;
+}
+
 static size_t small_bytes_per_eval(const gprn_ctx* c)
 {
     const size_t nn = (size_t)c->ld * c->ld, d = (size_t)(c->p + 1) * c->q * c->N;
-    return ((4 * (size_t)c->G + c->q) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256) * sizeof(double) +
-           (size_t)c->G * fill_program_bytes() * 2;
+    const size_t ne = small_mask_entries(c, false).size() + small_mask_entries(c, true).size();   // (WT and C per entry)
+    return ((4 * (size_t)c->G + c->q) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256 +
+            ne * 2 * GPRN_TILE * c->ld) * sizeof(double) + (size_t)c->G * fill_program_bytes() * 2 + ne * 2 * sizeof(MaskLane);
 }
 
 static int small_batch_chunk(gprn_ctx* c)
 {
     const size_t per = small_bytes_per_eval(c);
-    return (int)std::max<size_t>(16, std::min<size_t>(batch_budget_bytes(c) / per, 32768));   // (grid y = evaluations)
+    // (grid y = evaluations; under a mask the rows' launches have evaluations x entries of a phase in grid y / z: below 65 535)
+    const size_t ne = std::max<size_t>(1, std::max(small_mask_entries(c, false).size(), small_mask_entries(c, true).size()));
+    return (int)std::max<size_t>(16, std::min<size_t>(batch_budget_bytes(c) / per, std::min<size_t>(32768, 65535 / ne)));
 }
 
 static int small_batch_ensure(gprn_ctx* c, int n_eval)
 {
     SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
     const int G = c->G, q = c->q, p = c->p, N = c->N, ld = c->ld;
-    if (m && m->cap >= n_eval && m->G == G && m->q == q && m->p == p && m->N == N && m->ld == ld) return GPRN_OK;
+    if (m && m->cap >= n_eval && m->G == G && m->q == q && m->p == p && m->N == N && m->ld == ld && m->mask == c->d_mask) return GPRN_OK;
     small_batch_free(c);
     m = new SmallBatchMem();
     c->small_batch = m;
     const int cap = std::max(n_eval, 16);
     m->G = G; m->q = q; m->p = p; m->N = N; m->ld = ld;
+    m->mask = c->d_mask;
+    const std::vector<int> ent[2] = {small_mask_entries(c, false), small_mask_entries(c, true)};
+    const size_t ne0 = ent[0].size(), ne_all = ne0 + ent[1].size(), wc = (size_t)GPRN_TILE * ld;
+    m->mask_ne[0] = (int)ne0; m->mask_ne[1] = (int)ent[1].size();
     const size_t nn = (size_t)ld * ld, d = (size_t)(p + 1) * q * N, pn = (size_t)p * N, nscal = 3 * (size_t)G + (size_t)q * q;
     const size_t nmat = 4 * (size_t)G + q, nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
     TRY(dev_alloc(c, &m->mats, (size_t)cap * nmat * nn));
@@ -663,6 +702,11 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     TRY(dev_alloc(c, &m->phase_args, 4 * (size_t)cap));
     TRY(dev_alloc(c, &m->tail_args, 2 * (size_t)cap));
     TRY(dev_alloc(c, &m->prior_args, (size_t)cap));
+    if (ne_all) {
+        TRY(dev_alloc(c, &m->mask_wc, (size_t)cap * ne_all * 2 * wc));
+        TRY(dev_alloc(c, &m->mask_lanes, 2 * (size_t)cap * ne_all));
+        TRY(dev_alloc(c, &m->mask_tab, (size_t)cap * ne_all * GPRN_NBUF));
+    }
     HIP_TRY(c, hipMemset(m->ticket, 0, (size_t)cap * sizeof(unsigned)));
     HIP_TRY(c, hipMemset(m->info, 0, (size_t)cap * 3 * G * sizeof(int)));      // (the kernels write the entries they use)
     HIP_TRY(c, hipMemset(m->scal, 0, (size_t)cap * nscal * sizeof(double)));
@@ -674,6 +718,8 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     std::vector<SmallPhaseArgs> pa(4 * (size_t)cap);
     std::vector<SmallTailArgs> ta(2 * (size_t)cap);
     std::vector<SmallPriorArgs> pr((size_t)cap);
+    std::vector<MaskLane> ml(2 * (size_t)cap * ne_all);
+    std::vector<double*> mt((size_t)cap * ne_all * GPRN_NBUF, nullptr);
     for (int b = 0; b < cap; ++b) {
         double* const mb = m->mats + (size_t)b * nmat * nn;
         auto Kp = [&](int g) { return mb + (size_t)g * nn; };
@@ -714,13 +760,23 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
                     (double* const*)(ph ? d_weight : d_node), m->gp_ids + s0, N, ld, p, q, yres, variance,
                     mu_in, var_in, mu_out, var_out, ctl,
                     vec(0, s0), vec(1, s0), vec(2, s0), vec(3, s0), vec(4, s0), vec(5, s0), vec(6, s0),
-                    scal + G, scal, info + (size_t)(1 + ph) * G, nullptr};
+                    scal + G, scal, info + (size_t)(1 + ph) * G, nullptr, c->d_mask};
+                // the lanes of the rows behind this half-sweep: evaluation-major, so that B evaluations are a prefix
+                const size_t ne = ent[ph].size(), first = ph ? (size_t)cap * ne0 : 0;
+                for (size_t e = 0; e < ne; ++e) {
+                    const int g = ent[ph][e];
+                    double* const wt = m->mask_wc + (((size_t)b * ne_all + (ph ? ne0 : 0) + e) * 2) * wc;
+                    ml[(size_t)par * cap * ne_all + first + (size_t)b * ne + e] =
+                        MaskLane{Kp(g), vec(1, g), vec(6, g), wt, wt + wc, mu_out, var_out, ctl, g};
+                    double** const r = mt.data() + (first + (size_t)b * ne + e) * GPRN_NBUF;
+                    r[BUF_B] = Bp(g); r[BUF_X] = Xp(g); r[BUF_K] = wt; r[BUF_KLINV] = wt + wc;
+                }
             }
             ta[(size_t)par * cap + b] = SmallTailArgs{
                 (double* const*)d_node, (double* const*)d_weight, m->gp_ids, m->gp_ids + q, q, G - q, N, ld, p, q, G,
                 mu_out, var_out, c->d_yraw, variance, vec(1, 0), (double* const*)d_kinv_tab, vec(4, 0), m->logdetK + (size_t)b * G,
                 scal, m->out4 + (size_t)b * 4, m->ticket + b, ctl, m->hist + (size_t)b * (SB_K + 4),
-                m->hist + (size_t)b * (SB_K + 4) + SB_K, 0, 0, 0, info, 3 * G};
+                m->hist + (size_t)b * (SB_K + 4) + SB_K, 0, 0, 0, info, 3 * G, c->d_mask};
         }
         pr[b] = SmallPriorArgs{(double* const*)d_setup, m->gp_ids, (double* const*)d_kinv_out, N, ld, m->logdetK + (size_t)b * G, info};
     }
@@ -734,6 +790,10 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     HIP_TRY(c, hipMemcpy(m->phase_args, pa.data(), pa.size() * sizeof(SmallPhaseArgs), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(m->tail_args, ta.data(), ta.size() * sizeof(SmallTailArgs), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(m->prior_args, pr.data(), pr.size() * sizeof(SmallPriorArgs), hipMemcpyHostToDevice));
+    if (ne_all) {
+        HIP_TRY(c, hipMemcpy(m->mask_lanes, ml.data(), ml.size() * sizeof(MaskLane), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(m->mask_tab, mt.data(), mt.size() * sizeof(double*), hipMemcpyHostToDevice));
+    }
     // pinned staging: in = programs | y - mean | variance | mu | var;  out = ctl | hist | info | the four state copies
     const size_t pin_out_bytes = (size_t)cap * (4 * sizeof(int) + (SB_K + 4) * sizeof(double) + 3 * G * sizeof(int)) + 4 * (size_t)cap * d * sizeof(double) + 64;
     HIP_TRY(c, hipHostMalloc((void**)&m->pin_in, batch_stage_bytes(c, cap), hipHostMallocDefault));
@@ -787,6 +847,19 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     int s = max_iter >= 1 ? 1 : 0;
     bool all_done = false;
     const int q = c->q;
+    // under a data mask: the masked kernels, and behind each half-sweep the rows U of its entries for all B evaluations
+    const bool masked = m->mask != nullptr;
+    if (masked && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
+    const size_t ne_all = (size_t)m->mask_ne[0] + m->mask_ne[1];
+    auto rows_u = [&](int par, int ph) -> int {
+        if (!m->mask_ne[ph]) return GPRN_OK;
+        const size_t first = ph ? (size_t)cap * m->mask_ne[0] : 0;
+        MaskBatch mb;
+        mb.lanes = m->mask_lanes + (size_t)par * cap * ne_all + first; mb.tab = m->mask_tab + first * GPRN_NBUF;
+        mb.n = B * m->mask_ne[ph]; mb.upad = c->mask_upad_ph[ph]; mb.tasks = c->d_mask_tasks[ph]; mb.ntasks = c->mask_ntasks[ph];
+        mb.U = c->d_mask_U; mb.nU = c->d_mask_nU; mb.upad_all = c->mask_upad;
+        return mask_rows_lanes(c, mb, c->N, c->ld);
+    };
     while (!all_done && s <= max_iter) {
         const int s0 = s;
         int nb = 0;
@@ -794,15 +867,25 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
         for (; nb < nb_max && s <= max_iter; ++nb, ++s) {
             const int par = (s <= 1 || (s & 1)) ? 0 : 1;          // sweep 0 and trip 1 start from copy A, then they alternate
             prof_begin(c, GPRN_T_DIAG);
+            if (masked) hipLaunchKernelGGL((k_small_phase_bm<false>), dim3(q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 0) * cap));
+            else
             hipLaunchKernelGGL((k_small_phase_b<false>), dim3(q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 0) * cap));
             prof_end(c);
             TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 0) * cap, false, B));   // (sequential order only)
+            if (masked) TRY(rows_u(par, 0));
             prof_begin(c, GPRN_T_DIAG);
+            if (masked) hipLaunchKernelGGL((k_small_phase_bm<true>), dim3(G - q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 1) * cap));
+            else
             hipLaunchKernelGGL((k_small_phase_b<true>), dim3(G - q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 1) * cap));
             prof_end(c);
             TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B));
+            if (masked) TRY(rows_u(par, 1));
             prof_begin(c, GPRN_T_VEC);
-            if (io.flags & GPRN_BATCH_FORCED)
+            if (masked && (io.flags & GPRN_BATCH_FORCED))
+                hipLaunchKernelGGL((k_small_tail_bm<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
+            else if (masked)
+                hipLaunchKernelGGL((k_small_tail_bm<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
+            else if (io.flags & GPRN_BATCH_FORCED)
                 hipLaunchKernelGGL((k_small_tail_b<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
             else
                 hipLaunchKernelGGL((k_small_tail_b<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);

@@ -697,6 +697,10 @@ int vec_elbo_evals(gprn_ctx* c, const EvalMap& ev, const int* d_evals, int n, do
     if (!n) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
+    if (c->d_mask)                                   // (the mask is the data's: one for all evaluations)
+        hipLaunchKernelGGL(k_loglike_partial<true>, dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
+                           c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)c->d_mask);
+    else
     hipLaunchKernelGGL(k_loglike_partial<false>, dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
                        c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)nullptr);
     hipLaunchKernelGGL(k_elbo_final, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part,

@@ -69,11 +69,18 @@ class inference:
             ascent.  With q = 1 the two are the same computation.  Everything
             that sweeps follows it (``ELBOcalc``, ``nELBO``, ``optimize``, ``mcmc``, ``nELBO_batch``, ``grad_ELBO``, ...)
             except ``ELBOaux`` and ``_updateSigMu``, which restate reference functions.  Not with ``mask`` or ``comm``.
+        batch_under_mask: bool (default False), keyword only
+            Whether the side-by-side forms (``nELBO_batch``, ``mcmc(batch=True)``, ``nELBO_and_grad_batch`` and the states
+            behind ``predict_batch`` / ``posterior_predictive``) also run under a data mask.  Off, a masked object
+            evaluates one vector after the other, each from its predecessor's state; on, all of them start from one
+            shared state, which moves rule-stopped values within the stop rule's 1e-3.  An attribute that may be set
+            later, as ``batch_max_N``.  Without a mask it changes nothing.
     """
 
     _SWEEP_ORDERS = {'reference': _hip.ORDER_REFERENCE, 'sequential': _hip.ORDER_SEQUENTIAL}
 
-    def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference'):
+    def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference',
+                 batch_under_mask=False):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -96,6 +103,7 @@ class inference:
             self.y = np.where(self.mask, self.y, 0.0)
             self.yerr = np.where(self.mask, self.yerr, 1.0)
         self.yerr2 = self.yerr**2
+        self.batch_under_mask = bool(batch_under_mask)
 
         self._components_set = False
         self._frozen_mask = np.array([])
@@ -997,10 +1005,14 @@ class inference:
     def _batchable(self):
         """Whether ``_nELBO_batch_device`` applies to this object at its current components -- a property of the problem,
         the same on every rank of a pool (so that all of them take the same branch, collectives included)."""
-        if self._comm is not None or self.N > self.batch_max_N or self.mask is not None:
+        if self._comm is not None or self.N > self.batch_max_N or self._mask_bars_batch():
             return False
         nodes, weights, _, _ = self._get_components()
         return all(self._kernel_spec(k)[0] == 'device' for k in chain(nodes, weights))
+
+    def _mask_bars_batch(self):
+        """A data mask keeps the side-by-side forms away unless ``batch_under_mask`` is set."""
+        return self.mask is not None and not self.batch_under_mask
 
     def _nELBO_batch_pool(self, sets, max_iter, pool):
         """``nELBO_batch`` over the GPUs of a node: rank r evaluates ``sets[r::world]`` SIDE BY SIDE on its own GPU, all
@@ -1042,7 +1054,8 @@ class inference:
 
     def _nELBO_batch_device(self, sets, max_iter):
         """``nELBO_batch`` through ``gprn_elbocalc_batch``, or None where that does not apply (larger problems, sharded
-        objects, user-defined kernels, kernel expressions that change shape from one vector to the next, a data mask)."""
+        objects, user-defined kernels, kernel expressions that change shape from one vector to the next, a data mask without
+        ``batch_under_mask``)."""
         max_iter = 10000 if max_iter is None else int(max_iter)
         start = time_module.time()
         staged = self._batch_stage(sets)
@@ -1073,9 +1086,10 @@ class inference:
         y_resid (B, p N), jitters (B, p), mu (B, d), var (B, d))``, every evaluation starting from ``start`` = ``(mu, var)``,
         else the stored state, else ``_initMuVar`` of its own parameters -- or None where the side-by-side form does not
         apply.  The kernel programs go to the device; the object's parameters end at the last vector."""
-        if self._comm is not None or self.N > self.batch_max_N or self.mask is not None:
+        if self._comm is not None or self.N > self.batch_max_N or self._mask_bars_batch():
             return None
         ctx = self._backend()
+        ctx.option('batch_mask', 1 if self.batch_under_mask else 0)   # (every call: the attribute may have changed)
         y_raw = np.concatenate(self.y)
         B = len(sets)
         state = (self._mu, self._var) if start is None else (np.asarray(start[0], dtype=float), np.asarray(start[1], dtype=float))
@@ -1529,8 +1543,8 @@ class inference:
         (``start`` without ``sweeps`` is a ``ValueError``).
         A vector whose factorisation meets a non-positive pivot returns ``(inf, zeros)``.
 
-        Where the side-by-side form does not apply (user-defined kernels, N above ``batch_max_N``, a data mask, kernel
-        expressions that change shape between vectors) the vectors are evaluated one by one with the same meaning: the
+        Where the side-by-side form does not apply (user-defined kernels, N above ``batch_max_N``, a data mask without
+        ``batch_under_mask``, kernel expressions that change shape between vectors) the vectors are evaluated one by one with the same meaning: the
         loop, then ``gprn_grad_elbo`` on what it left.  Unsharded objects only.
         """
         if self._comm is not None:

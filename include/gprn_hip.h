@@ -97,8 +97,9 @@ int gprn_set_data(gprn_ctx* ctx, int N, int p, int q,
  * entries of y / yerr are never read into arithmetic (the kernels select; NaN and inf are fine there).
  * GPRN_E_ARG: an output with no observed entry, or q >= 2 with a time at which every output is masked (drop that time;
  * predict still reaches it).  Both paths (one-tile kernels and launch schedule) have a masked form;
- * gprn_keep_sigma(1), gprn_grad_matrices, gprn_grad_kernel, gprn_elbocalc_batch and contexts with a communicator
- * return GPRN_E_UNSUPPORTED.  The masked gradient is gprn_grad_elbo / gprn_grad_matrix (the B-form needs no division by s). */
+ * gprn_keep_sigma(1), gprn_grad_matrices, gprn_grad_kernel, gprn_elbocalc_batch (unless option "batch_mask" is 1) and
+ * contexts with a communicator return GPRN_E_UNSUPPORTED.  Setting or clearing a mask frees the buffers of
+ * gprn_elbocalc_batch (their argument blocks carry the mask).  The masked gradient is gprn_grad_elbo / gprn_grad_matrix (the B-form needs no division by s). */
 int gprn_set_mask(gprn_ctx* ctx, const uint8_t* mask);
 
 /* ---- multi-GPU sharding (new): one context per rank/GPU.
@@ -329,7 +330,13 @@ int gprn_set_sweep_order(gprn_ctx* ctx, int order);
  * otherwise (the caller evaluates one by one).  One-tile problems (N <= 128) run a half-sweep of ALL evaluations as one
  * launch (csrc/smalln.hip); larger ones go through the launch schedule of the large problems with its batch dimension =
  * evaluations x latent GPs of the phase, an evaluation that has stopped leaving the next sweep's launches (csrc/midn.hip).
- * Lists longer than the memory budget (option "batch_mem_mb") run chunk by chunk.  The context's own state and factors
+ * Lists longer than the memory budget (option "batch_mem_mb") run chunk by chunk.
+ * Under a data mask (gprn_set_mask): GPRN_E_UNSUPPORTED, unless option "batch_mask" is 1.  Then row b of every output is what
+ * gprn_elbocalc returns on this context under this mask for vector b from (mu_b, var_b) -- the mask is the data's, one for all
+ * evaluations; masked entries of y_resid and of the variances are selected away, never multiplied (NaN / inf there reach no
+ * arithmetic); behind each half-sweep the rows U of every (evaluation, latent GP with unobserved points) are formed by
+ * csrc/mask.hip's three steps with an evaluation dimension.  Forced batches, chunks, halving and gprn_elbocalc_batch_grad's
+ * gradient (the B-form divides by no s) work as without a mask.  The context's own state and factors
  * are not touched.  An evaluation whose factorisation fails returns info > 0 and a NaN ELBO at once (the reference's loop
  * would carry the NaN to max_iter: iterations reports max_iter). */
 int gprn_elbocalc_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, int n_kernel_params,
@@ -350,7 +357,7 @@ int gprn_elbocalc_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, 
  *       trips (converged = 0, iterations = max_iter), the smooth objective of a gradient optimiser; a non-positive pivot still
  *       ends that evaluation at once.  Other bits: GPRN_E_ARG.
  * An evaluation with info > 0 gets a NaN ELBO and a row of zeros; the others are untouched.  grad_out with max_iter < 1:
- * GPRN_E_ARG (no sweep was committed).  Refusals: gprn_elbocalc_batch's (a data mask, a communicator, uploaded kernels, a
+ * GPRN_E_ARG (no sweep was committed).  Refusals: gprn_elbocalc_batch's (a data mask without option "batch_mask", a communicator, uploaded kernels, a
  * kernel that is not even in t_i - t_j, a one-tile problem with the small path off).
  * elbo, iterations, converged, info and the states are bit-identical to the same call without grad_out: the gradient pass runs
  * per chunk behind the chunk's loop (csrc/grad.hip, slots = evaluations x latent GPs: its launches do not grow with the number
@@ -406,7 +413,10 @@ int gprn_predict_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, i
  * of two tiles too; 0: the launch schedule at every size; same results to rounding); "batch_mem_mb" (device memory, MiB, that
  * one chunk of gprn_elbocalc_batch's evaluations may take: longer lists run chunk by chunk; default: half of what is free, 48 GiB
  * at most; when the device cannot give that much in one piece the chunk is halved until it can); "batch_chunk" (read-only:
- * evaluations per chunk in the last gprn_elbocalc_batch call); "comm_budget_s" (sharded contexts: seconds an entry point may stay inside its collective section -- a rank that
+ * evaluations per chunk in the last gprn_elbocalc_batch call); "batch_mask" (0, the default: gprn_elbocalc_batch and
+ * gprn_elbocalc_batch_grad refuse a context with a data mask; 1: they run under it -- side by side every evaluation starts from
+ * one shared state, which moves rule-stopped values within the stop rule's 1e-3 against one evaluation after the other);
+ * "comm_budget_s" (sharded contexts: seconds an entry point may stay inside its collective section -- a rank that
  * died leaves the others there -- before the library's watchdog names the entry point, the collective and the rank on
  * stderr and ends the process with status 86; default 600, or GPRN_COMM_BUDGET_S); "accurate_factor" (the panel steps of
  * a blocked factorisation as triangular SOLVES -- what LAPACK's potrf does -- instead of products with the explicit inverse
