@@ -35,6 +35,20 @@ static void dev_free(T*& p) { if (p) hipFree(p); p = nullptr; }
 
 static inline int bad(gprn_ctx* c, const char* msg) { if (c) c->err = msg; return GPRN_E_ARG; }
 
+// Owns device and pinned allocations: everything it hands out is freed in release() and in its destructor, on every path
+// (CallScratch for one call; SmallBatchMem, MidBatch between side-by-side calls).  A failed alloc / pin leaves a null pointer.
+struct DeviceOwner {
+    std::vector<void*> dev, pinned;
+    DeviceOwner() = default;
+    DeviceOwner(const DeviceOwner&) = delete; DeviceOwner& operator=(const DeviceOwner&) = delete;
+    ~DeviceOwner() { release(); }
+    template <typename T>
+    int alloc(gprn_ctx* c, T** p, size_t count) { TRY(dev_alloc(c, p, count)); dev.push_back(*p); return GPRN_OK; }
+    template <typename T>
+    int pin(gprn_ctx* c, T** p, size_t bytes) { *p = nullptr; HIP_TRY(c, hipHostMalloc((void**)p, bytes, hipHostMallocDefault)); pinned.push_back(*p); return GPRN_OK; }
+    void release() { for (void* p : dev) hipFree(p); for (void* p : pinned) hipHostFree(p); dev.clear(); pinned.clear(); }
+};
+
 // The device temporaries of ONE call (nothing is kept across calls; what the context owns -- workspaces, prediction
 // buffers, d_test, slot arrays, masks, batch slabs -- stays with the context).  Whatever it hands out lives until it goes out of
 // scope, on every return path: the destructor waits for c->stream, forgets the tables it noted and frees everything.
@@ -43,7 +57,7 @@ static inline int bad(gprn_ctx* c, const char* msg) { if (c) c->err = msg; retur
 // c->stream write into: locals go in reverse order, so its wait then comes before they do.
 struct CallScratch {
     gprn_ctx* const c;
-    std::vector<void*> mem;
+    DeviceOwner mem;
     std::vector<double**> noted;
     std::vector<std::vector<TileTask>> staged;      // host side of the task lists until the copies behind them are done
     explicit CallScratch(gprn_ctx* c_) : c(c_) {}
@@ -53,15 +67,9 @@ struct CallScratch {
     {
         hipStreamSynchronize(c->stream);
         for (double** t : noted) tab_forget(c, t);
-        for (void* p : mem) hipFree(p);
-    }
+    }                                               // (mem frees behind this)
     template <typename T>
-    int alloc(T** p, size_t count)
-    {
-        TRY(dev_alloc(c, p, count));
-        mem.push_back(*p);
-        return GPRN_OK;
-    }
+    int alloc(T** p, size_t count) { return mem.alloc(c, p, count); }
     // a device pointer table of `rows`, there when the call returns; note: tab_rows may pass its rows as kernel arguments
     int table(double*** d_tab, const std::vector<double*>& rows, bool note = false)
     {

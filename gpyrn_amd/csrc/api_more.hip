@@ -88,12 +88,8 @@ extern "C" int gprn_predict_batch(gprn_ctx* c, int n_eval, const double* kernel_
     if (c->owner.empty()) return bad(c, "predict_batch: call set_owners first");
     if (comm_active(c) || c->world != 1) { c->err = "predict_batch: one rank only"; return GPRN_E_UNSUPPORTED; }
     TRY(batch_validate(c, n_kernel_params));
-    // (the budget is an estimate, as for gprn_elbocalc_batch_grad: nothing has run when an allocation is refused)
-    int cap = 0, want = n_eval, rc;
-    while ((rc = mid_batch_reserve(c, want, &cap)) == GPRN_E_NOMEM && cap > 1) want = cap / 2;
-    if (rc) return rc;
-    if (want != n_eval) c->err.clear();
-    c->last_batch_chunk = std::min(cap, n_eval);
+    int cap = 0;
+    TRY(batch_reserve(c, mid_batch_reserve, n_eval, &cap));
     const PredBatchIo io{n_eval, kernel_params, n_kernel_params, mu, var, jitters, ns, tstar, lat_mean, lat_var, out_mean, out_var,
                          info, c->p, c->G, (size_t)(c->p + 1) * c->q * c->N};
     for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(mid_predict_run(c, io.slice(e0, std::min(cap, n_eval - e0))));

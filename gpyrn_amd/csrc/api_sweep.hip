@@ -789,15 +789,9 @@ extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* k
     // batched form for it, as include/gprn_hip.h promises; inference.nELBO_batch then evaluates one by one -- ADVICE r5)
     if (!small && c->T < 2) { c->err = "elbocalc_batch: one-tile problems run side by side on the small path only"; return GPRN_E_UNSUPPORTED; }
     TRY(batch_validate(c, n_kernel_params));
-    const auto reserve = small ? small_batch_reserve : mid_batch_reserve;
     const auto run = small ? small_batch_run : mid_batch_run;
-    // the budget is an estimate: when the device has less in one piece than it reports free, the list runs in smaller chunks
-    // (nothing has run yet: the buffers are allocated before anything is enqueued)
-    int cap = 0, want = n_eval, rc;
-    while ((rc = reserve(c, want, &cap)) == GPRN_E_NOMEM && cap > 1) want = cap / 2;
-    if (rc) return rc;
-    if (want != n_eval) c->err.clear();
-    c->last_batch_chunk = std::min(cap, n_eval);
+    int cap = 0;
+    TRY(batch_reserve(c, small ? small_batch_reserve : mid_batch_reserve, n_eval, &cap));
     const BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info,
                      mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N, flags, grad_out};
     // (with grad_out each chunk ends with the gradient pass of its evaluations, before the next chunk overwrites the slabs)
@@ -826,41 +820,50 @@ int batch_validate(gprn_ctx* c, int n_kpar)
     return GPRN_OK;
 }
 
-size_t batch_stage_bytes(const gprn_ctx* c, int cap)
+int batch_reserve(gprn_ctx* c, int (*reserve)(gprn_ctx*, int, int*), int n_eval, int* cap)
 {
-    return (size_t)cap * c->G * fill_program_bytes() + 2 * (size_t)cap * ((size_t)c->p * c->N + (size_t)(c->p + 1) * c->q * c->N) * sizeof(double);
+    int want = n_eval, rc;
+    while ((rc = reserve(c, want, cap)) == GPRN_E_NOMEM && *cap > 1) want = *cap / 2;
+    if (rc) return rc;
+    if (want != n_eval) c->err.clear();
+    c->last_batch_chunk = std::min(*cap, n_eval);
+    return GPRN_OK;
 }
 
-int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchDst& dst, hipStream_t stream, LapTimer& t, double* us_host)
+int batch_stage_programs(gprn_ctx* c, const double* kparams, int n_kpar, int B, char* pin, double nugget, const char* who)
 {
-    const int B = io.n, G = c->G, p = c->p, N = c->N;
     const size_t pb = fill_program_bytes();
-    double* const yres_h = (double*)(pin + (size_t)cap * G * pb);
-    double* const var_h = yres_h + (size_t)cap * io.yv;
-    double* const mu_h = var_h + (size_t)cap * io.yv;
-    double* const v_h = mu_h + (size_t)cap * io.state;
     for (int b = 0; b < B; ++b) {
-        const double* kp = io.kparams + (size_t)b * io.n_kpar;
-        for (int g = 0; g < G; ++g) {
-            if (!fill_program_with(c->kspec[g], kp, pin + ((size_t)b * G + g) * pb, 1e-6)) {
-                c->err = "elbocalc_batch: a kernel that is not an even function of t_i - t_j"; return GPRN_E_UNSUPPORTED;
+        const double* kp = kparams + (size_t)b * n_kpar;
+        for (int g = 0; g < c->G; ++g) {
+            if (!fill_program_with(c->kspec[g], kp, pin + ((size_t)b * c->G + g) * pb, nugget)) {
+                c->err = std::string(who) + ": a kernel that is not an even function of t_i - t_j"; return GPRN_E_UNSUPPORTED;
             }
             kp += c->kspec[g].n_params;
         }
+    }
+    return GPRN_OK;
+}
+
+int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchBufs& dst, hipStream_t stream, LapTimer& t, double* us_host)
+{
+    const int B = io.n, G = c->G, p = c->p, N = c->N;
+    const BatchBufs h = layout_at(pin, batch_pin_in, cap, G, fill_program_bytes(), io.yv, io.state);
+    TRY(batch_stage_programs(c, io.kparams, io.n_kpar, B, h.programs, 1e-6, "elbocalc_batch"));
+    for (int b = 0; b < B; ++b)
         for (int i = 0; i < p; ++i) {
             const double j2 = io.jitters[(size_t)b * p + i] * io.jitters[(size_t)b * p + i];
-            for (int n = 0; n < N; ++n) var_h[b * io.yv + (size_t)i * N + n] = j2 + c->h_yerr2[(size_t)i * N + n];
+            for (int n = 0; n < N; ++n) h.variance[b * io.yv + (size_t)i * N + n] = j2 + c->h_yerr2[(size_t)i * N + n];
         }
-    }
-    memcpy(yres_h, io.y_resid, B * io.yv * sizeof(double));
-    memcpy(mu_h, io.mu, B * io.state * sizeof(double));
-    memcpy(v_h, io.var, B * io.state * sizeof(double));
+    memcpy(h.yres, io.y_resid, B * io.yv * sizeof(double));
+    memcpy(h.mu, io.mu, B * io.state * sizeof(double));
+    memcpy(h.var, io.var, B * io.state * sizeof(double));
     *us_host = t.lap();
-    HIP_TRY(c, hipMemcpyAsync(dst.programs, pin, (size_t)B * G * pb, hipMemcpyHostToDevice, stream));
-    HIP_TRY(c, hipMemcpyAsync(dst.yres, yres_h, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_TRY(c, hipMemcpyAsync(dst.variance, var_h, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_TRY(c, hipMemcpyAsync(dst.mu, mu_h, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_TRY(c, hipMemcpyAsync(dst.var, v_h, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.programs, h.programs, (size_t)B * G * fill_program_bytes(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.yres, h.yres, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.variance, h.variance, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.mu, h.mu, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_TRY(c, hipMemcpyAsync(dst.var, h.var, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
     return GPRN_OK;
 }
 

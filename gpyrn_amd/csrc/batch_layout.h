@@ -1,0 +1,91 @@
+// The layouts of the blocks a context keeps between side-by-side calls (smalln.hip, midn.hip, api_sweep.hip's staging): ONE
+// function per block, walked with a null base for the block's size (layout_count) and with the real base for the pointers
+// into it (layout_at).  A layout's struct lists its ranges in the block's order.  No HIP in here (tests/layout_check.cpp).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+// Hands out typed, aligned sub-ranges of a block, one behind the other.  Null base: sizes only, every range comes back null.
+struct LayoutCursor {
+    char* const base;
+    size_t at = 0;                    // bytes handed out so far: the block's size once the walk is over
+    explicit LayoutCursor(void* b) : base((char*)b) {}
+    template <typename T> T* take(size_t count, size_t align = alignof(T))
+    {
+        at = (at + align - 1) / align * align;
+        T* const p = base ? (T*)(base + at) : nullptr;
+        at += count * sizeof(T);
+        return p;
+    }
+};
+template <class T, class F, class... A>     // elements of T the block of `layout` takes
+static inline size_t layout_count(F layout, A... a) { LayoutCursor c(nullptr); layout(c, a...); return (c.at + sizeof(T) - 1) / sizeof(T); }
+template <class F, class... A>
+static inline auto layout_at(void* base, F layout, A... a) { LayoutCursor c(base); return layout(c, a...); }
+
+// One lane of mask.hip's batched rows U: per (evaluation, latent GP of the phase with a non-empty U)
+struct MaskLane {
+    const double *K, *s, *ct;  // the latent GP's prior matrix of this evaluation, its s = sqrt(d) and ct = X^T X z (ld each)
+    double *WT, *C;            // upad x ld each: K[U, :] diag(s), then WT X^T
+    double *mu, *var;          // the evaluation's state copy the half-sweep writes, (p + 1, q, N)
+    const int* done;           // the evaluation's stop word (one tile: its workgroups are no-ops once it is set), or null
+    int gp;
+};
+
+// ---- above one tile (midn.hip): the device tables and their pinned image, for cap evaluations of G = q (p + 1) latent GPs,
+// ne0 / ne1 of the node / weight phase with a non-empty U, rows of nb pointers.  Two constraints on the order, stated here
+// once: the tables of the set-up (everything ahead of `node` / `gp_node`) never change and are uploaded once by
+// mid_batch_reserve; the per-sweep tables -- node, weight and, in the pointer block, the mask's rows -- are ONE contiguous
+// tail of each block, which mid_upload_active sends with one copy per block.
+struct MidShape { size_t cap, G, q, p, ne0, ne1, nb; };
+struct MidPtrTab {
+    double **kptr, **kptr2;          // [cap G]: where the fill puts K, and its second copy
+    double **setup, **kinv, **pred;  // [cap G][nb], [cap (q - 1)][nb], [cap G][nb]
+    double **diag;                   // [cap G]: the variances' row behind the prediction fill's diagonal
+    double **node, **weight;         // [cap q][nb], [cap q p][nb]: the active evaluations, node-major
+    double **mask[2], **end;         // [cap ne][nb] per phase
+};
+static inline MidPtrTab mid_ptr_tab(LayoutCursor& c, const MidShape& s)
+{
+    const size_t nslot = s.cap * s.G, nb = s.nb;
+    return {c.take<double*>(nslot), c.take<double*>(nslot), c.take<double*>(nslot * nb), c.take<double*>(s.cap * (s.q - 1) * nb),
+            c.take<double*>(nslot * nb), c.take<double*>(nslot), c.take<double*>(s.cap * s.q * nb), c.take<double*>(s.cap * s.q * s.p * nb),
+            {c.take<double*>(s.cap * s.ne0 * nb), c.take<double*>(s.cap * s.ne1 * nb)}, c.take<double*>(0)};
+}
+struct MidIntTab {
+    int *gp_setup, *ev_setup, *row_pred;             // [cap G] each
+    int *gp_node, *ev_node, *gp_weight, *ev_weight;  // [cap q] twice, [cap q p] twice
+    int *evals, *end;                                // [cap]
+};
+static inline MidIntTab mid_int_tab(LayoutCursor& c, const MidShape& s)
+{
+    const size_t nslot = s.cap * s.G, nq = s.cap * s.q;
+    return {c.take<int>(nslot), c.take<int>(nslot), c.take<int>(nslot), c.take<int>(nq), c.take<int>(nq), c.take<int>(nq * s.p),
+            c.take<int>(nq * s.p), c.take<int>(s.cap), c.take<int>(0)};
+}
+// the pinned image of both tables and of the mask's lanes [cap ne0 | cap ne1]
+struct MidPinTab { MidPtrTab ptr; MidIntTab ints; MaskLane* lanes; };
+static inline MidPinTab mid_pin_tab(LayoutCursor& c, const MidShape& s)
+{
+    return {mid_ptr_tab(c, s), mid_int_tab(c, s), c.take<MaskLane>(s.cap * (s.ne0 + s.ne1))};
+}
+// what comes back: 4 doubles per evaluation of up to `lead` sweeps enqueued ahead, pivot verdicts, the final states' halves
+struct MidPinOut { double* out4; int* info; double *mu, *var; };
+static inline MidPinOut mid_pin_out(LayoutCursor& c, size_t cap, size_t G, size_t state, size_t lead)
+{
+    return {c.take<double>(lead * cap * 4), c.take<int>(3 * cap * G), c.take<double>(cap * state, 64), c.take<double>(cap * state)};
+}
+// ---- one tile (smalln.hip): control words, ELBO histories of `hist` values, pivot verdicts, the state copies [4][cap][state]
+struct SmallPinOut { int* ctl; double* hist; int* info; double* state; };
+static inline SmallPinOut small_pin_out(LayoutCursor& c, size_t cap, size_t G, size_t state, size_t hist)
+{
+    return {c.take<int>(cap * 4), c.take<double>(cap * hist), c.take<int>(cap * 3 * G), c.take<double>(4 * cap * state, 64)};
+}
+// ---- the pinned input of a chunk (batch_stage; gprn_predict_batch stages its programs, states and, in `variance`, jitters):
+// cap G fill programs of `program` bytes, yv doubles of y - mean and of the variances and `state` of mu and var per evaluation
+struct BatchBufs { char* programs; double *yres, *variance, *mu, *var; };    // (also: where the five go on the device)
+static inline BatchBufs batch_pin_in(LayoutCursor& c, size_t cap, size_t G, size_t program, size_t yv, size_t state)
+{
+    return {c.take<char>(cap * G * program), c.take<double>(cap * yv), c.take<double>(cap * yv), c.take<double>(cap * state),
+            c.take<double>(cap * state)};
+}

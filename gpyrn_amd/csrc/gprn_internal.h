@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/gprn_hip.h"
+#include "batch_layout.h"
 
 #define GPRN_TILE 128          // tile edge of the blocked factorisation (nb)
 #define GPRN_KC 16             // K chunk staged through LDS per pipeline stage
@@ -103,13 +104,6 @@ struct EvalMap {
 // The rows U of many evaluations side by side (mask.hip's _b kernels; gprn_elbocalc_batch under option "batch_mask"): one
 // lane per (evaluation, latent GP of the phase with a non-empty U).  The mask, and with it every U, is the data's: the same
 // for all evaluations.
-struct MaskLane {
-    const double *K, *s, *ct;  // the latent GP's prior matrix of this evaluation, its s = sqrt(d) and ct = X^T X z (ld each)
-    double *WT, *C;            // upad x ld each: K[U, :] diag(s), then WT X^T
-    double *mu, *var;          // the evaluation's state copy the half-sweep writes, (p + 1, q, N)
-    const int* done;           // the evaluation's stop word (one tile: its workgroups are no-ops once it is set), or null
-    int gp;
-};
 struct MaskBatch {
     const MaskLane* lanes = nullptr;   // [n] (device)
     double** tab = nullptr;            // [n][GPRN_NBUF]: BUF_X = the slot's X, BUF_K = WT, BUF_KLINV = C
@@ -558,13 +552,29 @@ struct LapTimer {
     double lap() { const auto now = clock::now(); const double t = us(mark, now); mark = now; return t; }   // since the last lap
     double total() const { return us(begin, clock::now()); }
 };
-// The inputs of io's evaluations through a pinned buffer laid out for `cap` of them -- programs | y - mean | variance | mu |
-// var -- and from there to the driver's device buffers, five copies enqueued on `stream`; the host's part is a lap of the
-// driver's timer: *us_host
-struct BatchDst { void* programs; double *yres, *variance, *mu, *var; };
-int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchDst& dst, hipStream_t stream, LapTimer& t,
-                double* us_host);
-size_t batch_stage_bytes(const gprn_ctx* c, int cap);        // ... and the pinned buffer's size
+// The inputs of io's evaluations through a pinned buffer laid out for `cap` of them (batch_pin_in) and from there to the
+// driver's device buffers, five copies enqueued on `stream`; the host's part is a lap of the driver's timer: *us_host
+int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchBufs& dst, hipStream_t stream, LapTimer& t, double* us_host);
+// ... its first step, for gprn_predict_batch too: the fill programs [B][G] with `nugget` on the diagonal; who: for the error text
+int batch_stage_programs(gprn_ctx* c, const double* kparams, int n_kpar, int B, char* pin, double nugget, const char* who);
+// Room for up to n_eval evaluations from a driver's reserve: the budget is an estimate, so when the device has less in one
+// piece than it reports free the chunk is halved until it fits (nothing has run yet: the buffers come before any launch)
+int batch_reserve(gprn_ctx* c, int (*reserve)(gprn_ctx*, int, int*), int n_eval, int* cap);
+size_t batch_budget_bytes(gprn_ctx* c);        // device memory a chunk of evaluations may take (option "batch_mem_mb")
+// Evaluation b of a chunk enters the gradient pass (the driver appends its rows, s, kinv, state_idx) -- unless its pivot
+// failed: a row of zeros, left out (false).  grad_batch_left: the scratch gets what the chunk's `held` bytes left of the budget
+static inline bool grad_batch_enter(const BatchIo& io, int b, GradBatchIn& in)
+{
+    double* const row = io.grad_out + (size_t)b * io.n_kpar;
+    if (io.info[b] > 0) { std::fill(row, row + io.n_kpar, 0.0); return false; }
+    in.kparams.push_back(io.kparams + (size_t)b * io.n_kpar); in.out.push_back(row); in.n += 1;
+    return true;
+}
+static inline size_t grad_batch_left(gprn_ctx* c, size_t held) { const size_t b = batch_budget_bytes(c); return b > held ? b - held : 0; }
+// one row of a pointer table; the first positive pivot verdict among n (LAPACK style: the failing latent GP's), or 0
+static inline void buf_row(double** r, double* B, double* X, double* K, double* KLinv) { r[BUF_B] = B; r[BUF_X] = X; r[BUF_K] = K; r[BUF_KLINV] = KLinv; }
+static inline int first_failed(const int* info, size_t n, size_t stride = 1)
+{ for (size_t i = 0; i < n; ++i) if (info[i * stride] > 0) return info[i * stride]; return 0; }
 // The two drivers of gprn_elbocalc_batch (one tile: smalln.hip, one launch per half-sweep of ALL evaluations; above:
 // midn.hip, the launch schedule with batch = evaluations x latent GPs).  reserve: room for up to `want` evaluations, never
 // more than the memory budget pays for; *cap: what there is room for -- on GPRN_E_NOMEM what was tried (the caller halves).
@@ -594,7 +604,6 @@ struct PredBatchIo {
 int mid_predict_run(gprn_ctx* c, const PredBatchIo& io);
 // ... and its two fills alone for slot (eval, gp), read back before anything is factored (gprn_test_predict_fill)
 int mid_predict_fill_test(gprn_ctx* c, const PredBatchIo& io, int eval, int gp, double* K_out, double* Ks_out, double* kss_out);
-size_t batch_budget_bytes(gprn_ctx* c);        // device memory a chunk of evaluations may take (option "batch_mem_mb")
 // api_sweep.hip: one half-sweep's factorisation with its head and tail (run_phase, midn.hip); scal: the sweep's scalars;
 // chain_started: see FactorHooks (left set when the factorisation did not take it)
 int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::function<int()>& chain_started);
@@ -603,6 +612,11 @@ int phase_core(gprn_ctx* c, const Phase& ph, bool weights, double* scal, std::fu
 int mask_rows(gprn_ctx* c, const Phase& ph, bool weights, double* mu, double* var, const int* done);
 // ... of the lanes of a batch (a Phase with an EvalMap gets here from mask_rows: the context's mask_batch)
 int mask_rows_lanes(gprn_ctx* c, const MaskBatch& mb, int N, int ld);
+// the latent GPs of a phase with a non-empty U under c's mask, when batches run under it (one rank: slot = latent GP, nodes
+// first), and what a MaskBatch of that phase takes from c's mask (lanes, tab, n: the driver's)
+std::vector<int> batch_mask_entries(const gprn_ctx* c, bool weights);
+static inline MaskBatch mask_batch_of(const gprn_ctx* c, int ph)
+{ return MaskBatch{nullptr, nullptr, 0, c->mask_upad_ph[ph], c->d_mask_tasks[ph], c->mask_ntasks[ph], c->d_mask_U, c->d_mask_nU, c->mask_upad}; }
 int mask_prepare(gprn_ctx* c);       // buffers, tables and task lists for the current slots (build_tables: the set-up)
 void mask_free(gprn_ctx* c);
 void mask_invalidate(gprn_ctx* c);   // the slots changed (build_tables rebuilds them)

@@ -149,6 +149,15 @@ int mask_rows_lanes(gprn_ctx* c, const MaskBatch& mb, int N, int ld)
     return GPRN_OK;
 }
 
+std::vector<int> batch_mask_entries(const gprn_ctx* c, bool weights)
+{
+    std::vector<int> e;
+    if (c->d_mask && c->batch_mask)
+        for (int g = weights ? c->q : 0; g < (weights ? c->G : c->q); ++g)
+            if (!c->mask_U[g].empty()) e.push_back(g);
+    return e;
+}
+
 void mask_invalidate(gprn_ctx* c)
 {
     c->mask_ready = false;

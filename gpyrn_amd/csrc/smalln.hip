@@ -600,6 +600,7 @@ int small_prior(gprn_ctx* c, double** d_tab, const int* d_job_gp, double** d_kin
 struct SmallBatchMem {
     int cap = 0;                      // evaluations the buffers hold
     int G = 0, q = 0, p = 0, N = 0, ld = 0;
+    DeviceOwner own;                  // every device and pinned buffer below
     double *mats = nullptr;           // [cap][4 G + q][ld * ld]: K, KLinv, wsB, wsX per latent GP, K_j^-1 per node
     double *vecs = nullptr;           // [cap][7][G * ld]
     double *state = nullptr;          // [4][cap][d]: mu A, var A, mu B, var B
@@ -621,50 +622,33 @@ struct SmallBatchMem {
     double* mask_wc = nullptr;        // [cap][ne node + ne weight][2][128 * ld]
     MaskLane* mask_lanes = nullptr;   // [2 parity][cap ne node | cap ne weight], evaluation-major
     double** mask_tab = nullptr;      // [cap ne node | cap ne weight][GPRN_NBUF]
-    char *pin_in = nullptr, *pin_out = nullptr;
+    char* pin_in = nullptr;           // pinned: batch_pin_in
+    SmallPinOut out{};                // pinned: what a group of sweeps sends back, the four state copies
     double us_reserve = 0.0;          // GPRN_BATCH_TIMERS: what making room took, reported with the next chunk
 };
 #define SB_K 8                         // sweeps per batch of launches (one synchronisation each)
 
 void small_batch_free(gprn_ctx* c)
 {
-    SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
-    if (!m) return;
-    void* dev[] = {m->mats, m->vecs, m->state, m->yv, m->scal, m->logdetK, m->out4, m->hist, m->ctl, m->info, m->gp_ids,
-                   m->ticket, m->ptrs, m->kptr_dense, m->programs, m->phase_args, m->tail_args, m->prior_args, m->mask_wc,
-                   m->mask_lanes, m->mask_tab};
-    for (void* ptr : dev) if (ptr) hipFree(ptr);
-    if (m->pin_in) hipHostFree(m->pin_in);
-    if (m->pin_out) hipHostFree(m->pin_out);
-    delete m;
+    delete (SmallBatchMem*)c->small_batch;
     c->small_batch = nullptr;
-}
-
-// evaluations one chunk may hold: what the memory budget pays for (4 G + q matrices of ld^2 doubles each and small change
-// per evaluation), 16 at least -- an emcee run with thousands of walkers is split, not refused
-// the latent GPs of a phase with a non-empty U under the context's mask (one rank: slot = latent GP, nodes first)
-static std::vector<int> small_mask_entries(const gprn_ctx* c, bool weights)
-{
-    std::vector<int> e;
-    if (c->d_mask)
-        for (int g = weights ? c->q : 0; g < (weights ? c->G : c->q); ++g)
-            if (!c->mask_U[g].empty()) e.push_back(g);
-    return e;
 }
 
 static size_t small_bytes_per_eval(const gprn_ctx* c)
 {
     const size_t nn = (size_t)c->ld * c->ld, d = (size_t)(c->p + 1) * c->q * c->N;
-    const size_t ne = small_mask_entries(c, false).size() + small_mask_entries(c, true).size();   // (WT and C per entry)
+    const size_t ne = batch_mask_entries(c, false).size() + batch_mask_entries(c, true).size();   // (WT and C per entry)
     return ((4 * (size_t)c->G + c->q) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256 +
             ne * 2 * GPRN_TILE * c->ld) * sizeof(double) + (size_t)c->G * fill_program_bytes() * 2 + ne * 2 * sizeof(MaskLane);
 }
 
+// evaluations one chunk may hold: what the memory budget pays for (4 G + q matrices of ld^2 doubles each and small change
+// per evaluation), 16 at least -- an emcee run with thousands of walkers is split, not refused
 static int small_batch_chunk(gprn_ctx* c)
 {
     const size_t per = small_bytes_per_eval(c);
     // (grid y = evaluations; under a mask the rows' launches have evaluations x entries of a phase in grid y / z: below 65 535)
-    const size_t ne = std::max<size_t>(1, std::max(small_mask_entries(c, false).size(), small_mask_entries(c, true).size()));
+    const size_t ne = std::max<size_t>(1, std::max(batch_mask_entries(c, false).size(), batch_mask_entries(c, true).size()));
     return (int)std::max<size_t>(16, std::min<size_t>(batch_budget_bytes(c) / per, std::min<size_t>(32768, 65535 / ne)));
 }
 
@@ -679,33 +663,33 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     const int cap = std::max(n_eval, 16);
     m->G = G; m->q = q; m->p = p; m->N = N; m->ld = ld;
     m->mask = c->d_mask;
-    const std::vector<int> ent[2] = {small_mask_entries(c, false), small_mask_entries(c, true)};
+    const std::vector<int> ent[2] = {batch_mask_entries(c, false), batch_mask_entries(c, true)};
     const size_t ne0 = ent[0].size(), ne_all = ne0 + ent[1].size(), wc = (size_t)GPRN_TILE * ld;
     m->mask_ne[0] = (int)ne0; m->mask_ne[1] = (int)ent[1].size();
     const size_t nn = (size_t)ld * ld, d = (size_t)(p + 1) * q * N, pn = (size_t)p * N, nscal = 3 * (size_t)G + (size_t)q * q;
     const size_t nmat = 4 * (size_t)G + q, nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
-    TRY(dev_alloc(c, &m->mats, (size_t)cap * nmat * nn));
-    TRY(dev_alloc(c, &m->vecs, (size_t)cap * 7 * G * ld));
-    TRY(dev_alloc(c, &m->state, 4 * (size_t)cap * d));
-    TRY(dev_alloc(c, &m->yv, 2 * (size_t)cap * pn));
-    TRY(dev_alloc(c, &m->scal, (size_t)cap * nscal));
-    TRY(dev_alloc(c, &m->logdetK, (size_t)cap * G));
-    TRY(dev_alloc(c, &m->out4, (size_t)cap * 4));
-    TRY(dev_alloc(c, &m->hist, (size_t)cap * (SB_K + 4)));
-    TRY(dev_alloc(c, &m->ctl, (size_t)cap * 4));
-    TRY(dev_alloc(c, &m->info, (size_t)cap * 3 * G));
-    TRY(dev_alloc(c, &m->gp_ids, (size_t)G));
-    TRY(dev_alloc(c, &m->ticket, (size_t)cap));
-    TRY(dev_alloc(c, &m->ptrs, (size_t)cap * nptr));
-    TRY(dev_alloc(c, &m->kptr_dense, (size_t)cap * G));
-    TRY(dev_alloc(c, &m->programs, (size_t)cap * G * fill_program_bytes()));
-    TRY(dev_alloc(c, &m->phase_args, 4 * (size_t)cap));
-    TRY(dev_alloc(c, &m->tail_args, 2 * (size_t)cap));
-    TRY(dev_alloc(c, &m->prior_args, (size_t)cap));
+    TRY(m->own.alloc(c, &m->mats, (size_t)cap * nmat * nn));
+    TRY(m->own.alloc(c, &m->vecs, (size_t)cap * 7 * G * ld));
+    TRY(m->own.alloc(c, &m->state, 4 * (size_t)cap * d));
+    TRY(m->own.alloc(c, &m->yv, 2 * (size_t)cap * pn));
+    TRY(m->own.alloc(c, &m->scal, (size_t)cap * nscal));
+    TRY(m->own.alloc(c, &m->logdetK, (size_t)cap * G));
+    TRY(m->own.alloc(c, &m->out4, (size_t)cap * 4));
+    TRY(m->own.alloc(c, &m->hist, (size_t)cap * (SB_K + 4)));
+    TRY(m->own.alloc(c, &m->ctl, (size_t)cap * 4));
+    TRY(m->own.alloc(c, &m->info, (size_t)cap * 3 * G));
+    TRY(m->own.alloc(c, &m->gp_ids, (size_t)G));
+    TRY(m->own.alloc(c, &m->ticket, (size_t)cap));
+    TRY(m->own.alloc(c, &m->ptrs, (size_t)cap * nptr));
+    TRY(m->own.alloc(c, &m->kptr_dense, (size_t)cap * G));
+    TRY(m->own.alloc(c, &m->programs, (size_t)cap * G * fill_program_bytes()));
+    TRY(m->own.alloc(c, &m->phase_args, 4 * (size_t)cap));
+    TRY(m->own.alloc(c, &m->tail_args, 2 * (size_t)cap));
+    TRY(m->own.alloc(c, &m->prior_args, (size_t)cap));
     if (ne_all) {
-        TRY(dev_alloc(c, &m->mask_wc, (size_t)cap * ne_all * 2 * wc));
-        TRY(dev_alloc(c, &m->mask_lanes, 2 * (size_t)cap * ne_all));
-        TRY(dev_alloc(c, &m->mask_tab, (size_t)cap * ne_all * GPRN_NBUF));
+        TRY(m->own.alloc(c, &m->mask_wc, (size_t)cap * ne_all * 2 * wc));
+        TRY(m->own.alloc(c, &m->mask_lanes, 2 * (size_t)cap * ne_all));
+        TRY(m->own.alloc(c, &m->mask_tab, (size_t)cap * ne_all * GPRN_NBUF));
     }
     HIP_TRY(c, hipMemset(m->ticket, 0, (size_t)cap * sizeof(unsigned)));
     HIP_TRY(c, hipMemset(m->info, 0, (size_t)cap * 3 * G * sizeof(int)));      // (the kernels write the entries they use)
@@ -719,7 +703,7 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     std::vector<SmallTailArgs> ta(2 * (size_t)cap);
     std::vector<SmallPriorArgs> pr((size_t)cap);
     std::vector<MaskLane> ml(2 * (size_t)cap * ne_all);
-    std::vector<double*> mt((size_t)cap * ne_all * GPRN_NBUF, nullptr);
+    std::vector<double*> mt((size_t)cap * ne_all * GPRN_NBUF, nullptr), kd((size_t)cap * G);   // (kd: kptr_dense)
     for (int b = 0; b < cap; ++b) {
         double* const mb = m->mats + (size_t)b * nmat * nn;
         auto Kp = [&](int g) { return mb + (size_t)g * nn; };
@@ -732,13 +716,11 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
         double** const h_setup = hb; double** const h_node = hb + (size_t)G * GPRN_NBUF; double** const h_weight = hb + 2 * (size_t)G * GPRN_NBUF;
         double** const h_kinv_tab = hb + 3 * (size_t)G * GPRN_NBUF; double** const h_kinv_out = h_kinv_tab + q; double** const h_Kptr = h_kinv_out + G;
         for (int g = 0; g < G; ++g) {
-            double* row[GPRN_NBUF] = {Bp(g), KLp(g), Kp(g), KLp(g)};      // set-up: BUF_B scratch, BUF_X = chol(K)^-1, BUF_K
-            for (int k = 0; k < GPRN_NBUF; ++k) h_setup[(size_t)g * GPRN_NBUF + k] = row[k];
-            double* srow[GPRN_NBUF] = {Bp(g), Xp(g), Kp(g), KLp(g)};       // sweeps: B, X, K, chol(K)^-1
-            double** const dst = g < q ? h_node + (size_t)g * GPRN_NBUF : h_weight + (size_t)(g - q) * GPRN_NBUF;
-            for (int k = 0; k < GPRN_NBUF; ++k) dst[k] = srow[k];
+            buf_row(h_setup + (size_t)g * GPRN_NBUF, Bp(g), KLp(g), Kp(g), KLp(g));   // set-up: BUF_B scratch, BUF_X = chol(K)^-1, BUF_K
+            buf_row(g < q ? h_node + (size_t)g * GPRN_NBUF : h_weight + (size_t)(g - q) * GPRN_NBUF,
+                    Bp(g), Xp(g), Kp(g), KLp(g));                                     // sweeps: B, X, K, chol(K)^-1
             h_kinv_out[g] = (g >= 1 && g < q) ? Kinvp(g) : nullptr;
-            h_Kptr[g] = Kp(g);
+            h_Kptr[g] = kd[(size_t)b * G + g] = Kp(g);
         }
         for (int j = 0; j < q; ++j) h_kinv_tab[j] = j >= 1 ? Kinvp(j) : nullptr;
         double** const d_setup = db; double** const d_node = db + (size_t)G * GPRN_NBUF; double** const d_weight = db + 2 * (size_t)G * GPRN_NBUF;
@@ -768,8 +750,7 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
                     double* const wt = m->mask_wc + (((size_t)b * ne_all + (ph ? ne0 : 0) + e) * 2) * wc;
                     ml[(size_t)par * cap * ne_all + first + (size_t)b * ne + e] =
                         MaskLane{Kp(g), vec(1, g), vec(6, g), wt, wt + wc, mu_out, var_out, ctl, g};
-                    double** const r = mt.data() + (first + (size_t)b * ne + e) * GPRN_NBUF;
-                    r[BUF_B] = Bp(g); r[BUF_X] = Xp(g); r[BUF_K] = wt; r[BUF_KLINV] = wt + wc;
+                    buf_row(mt.data() + (first + (size_t)b * ne + e) * GPRN_NBUF, Bp(g), Xp(g), wt, wt + wc);
                 }
             }
             ta[(size_t)par * cap + b] = SmallTailArgs{
@@ -781,12 +762,7 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
         pr[b] = SmallPriorArgs{(double* const*)d_setup, m->gp_ids, (double* const*)d_kinv_out, N, ld, m->logdetK + (size_t)b * G, info};
     }
     HIP_TRY(c, hipMemcpy(m->ptrs, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice));
-    {
-        std::vector<double*> kd((size_t)cap * G);
-        for (int b = 0; b < cap; ++b)
-            for (int g = 0; g < G; ++g) kd[(size_t)b * G + g] = m->mats + ((size_t)b * nmat + g) * nn;
-        HIP_TRY(c, hipMemcpy(m->kptr_dense, kd.data(), kd.size() * sizeof(double*), hipMemcpyHostToDevice));
-    }
+    HIP_TRY(c, hipMemcpy(m->kptr_dense, kd.data(), kd.size() * sizeof(double*), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(m->phase_args, pa.data(), pa.size() * sizeof(SmallPhaseArgs), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(m->tail_args, ta.data(), ta.size() * sizeof(SmallTailArgs), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(m->prior_args, pr.data(), pr.size() * sizeof(SmallPriorArgs), hipMemcpyHostToDevice));
@@ -794,10 +770,10 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
         HIP_TRY(c, hipMemcpy(m->mask_lanes, ml.data(), ml.size() * sizeof(MaskLane), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(m->mask_tab, mt.data(), mt.size() * sizeof(double*), hipMemcpyHostToDevice));
     }
-    // pinned staging: in = programs | y - mean | variance | mu | var;  out = ctl | hist | info | the four state copies
-    const size_t pin_out_bytes = (size_t)cap * (4 * sizeof(int) + (SB_K + 4) * sizeof(double) + 3 * G * sizeof(int)) + 4 * (size_t)cap * d * sizeof(double) + 64;
-    HIP_TRY(c, hipHostMalloc((void**)&m->pin_in, batch_stage_bytes(c, cap), hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc((void**)&m->pin_out, pin_out_bytes, hipHostMallocDefault));
+    char* pin_out = nullptr;
+    TRY(m->own.pin(c, &m->pin_in, layout_count<char>(batch_pin_in, cap, G, fill_program_bytes(), pn, d)));
+    TRY(m->own.pin(c, &pin_out, layout_count<char>(small_pin_out, cap, G, d, SB_K + 4)));
+    m->out = layout_at(pin_out, small_pin_out, cap, G, d, SB_K + 4);
     m->cap = cap;
     return GPRN_OK;
 }
@@ -823,7 +799,7 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     const double us_ensure = m->us_reserve;
     m->us_reserve = 0.0;
     hipStream_t st = c->stream;
-    TRY(batch_stage(c, io, m->pin_in, cap, BatchDst{m->programs, m->yv, m->yv + (size_t)cap * io.yv, m->state, m->state + (size_t)cap * d},
+    TRY(batch_stage(c, io, m->pin_in, cap, BatchBufs{m->programs, m->yv, m->yv + (size_t)cap * io.yv, m->state, m->state + (size_t)cap * d},
                     st, t, &us_stage));
     HIP_TRY(c, hipMemsetAsync(m->ctl, 0, (size_t)B * 4 * sizeof(int), st));
     HIP_TRY(c, hipMemsetAsync(m->info, 0, (size_t)B * 3 * G * sizeof(int), st));    // (the kernels only raise them)
@@ -835,11 +811,6 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     // ---- the loop, SB_K sweeps per synchronisation
-    char* const po = m->pin_out;
-    int* const ctl_h = (int*)po;
-    double* const hist_h = (double*)(po + (size_t)cap * 4 * sizeof(int));
-    int* const info_h = (int*)(hist_h + (size_t)cap * (SB_K + 4));
-    double* const st_h = (double*)(((uintptr_t)(info_h + (size_t)cap * 3 * G) + 63) & ~(uintptr_t)63);
     std::vector<char> was_done(B, 0);
     for (int b = 0; b < B; ++b) { elbo[b] = 0.0; iters[b] = 0; conv[b] = 0; info[b] = 0; }
     // (quirk Q7: sweep 0 -- the first ELBOaux call, whose update is discarded -- and trip 1 are the same computation on the
@@ -854,10 +825,9 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     auto rows_u = [&](int par, int ph) -> int {
         if (!m->mask_ne[ph]) return GPRN_OK;
         const size_t first = ph ? (size_t)cap * m->mask_ne[0] : 0;
-        MaskBatch mb;
+        MaskBatch mb = mask_batch_of(c, ph);
         mb.lanes = m->mask_lanes + (size_t)par * cap * ne_all + first; mb.tab = m->mask_tab + first * GPRN_NBUF;
-        mb.n = B * m->mask_ne[ph]; mb.upad = c->mask_upad_ph[ph]; mb.tasks = c->d_mask_tasks[ph]; mb.ntasks = c->mask_ntasks[ph];
-        mb.U = c->d_mask_U; mb.nU = c->d_mask_nU; mb.upad_all = c->mask_upad;
+        mb.n = B * m->mask_ne[ph];
         return mask_rows_lanes(c, mb, c->N, c->ld);
     };
     while (!all_done && s <= max_iter) {
@@ -892,22 +862,21 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
             prof_end(c);
         }
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(ctl_h, m->ctl, (size_t)B * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(hist_h, m->hist, (size_t)B * (SB_K + 4) * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(info_h, m->info, (size_t)B * 3 * G * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(m->out.ctl, m->ctl, (size_t)B * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(m->out.hist, m->hist, (size_t)B * (SB_K + 4) * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(m->out.info, m->info, (size_t)B * 3 * G * sizeof(int), hipMemcpyDeviceToHost, st));
         us_enqueue += t.lap();
         HIP_TRY(c, hipStreamSynchronize(st));
         us_wait += t.lap();
         all_done = true;
         for (int b = 0; b < B; ++b) {
             if (was_done[b]) continue;
-            const int* cb = ctl_h + (size_t)b * 4;
+            const int* cb = m->out.ctl + (size_t)b * 4;
             const int ran = cb[0] ? std::min(nb, cb[3] - s0 + 1) : nb;
-            if (ran > 0) elbo[b] = hist_h[(size_t)b * (SB_K + 4) + ran - 1];
+            if (ran > 0) elbo[b] = m->out.hist[(size_t)b * (SB_K + 4) + ran - 1];
             iters[b] = cb[1];
             conv[b] = cb[2];
-            for (int k = 0; k < 3 * G && !info[b]; ++k)
-                if (info_h[(size_t)b * 3 * G + k] > 0) info[b] = info_h[(size_t)b * 3 * G + k];
+            if (!info[b]) info[b] = first_failed(m->out.info + (size_t)b * 3 * G, 3 * (size_t)G);
             if (info[b]) elbo[b] = NAN;                       // (jax's cholesky: NaN from the failed pivot on, no exception)
             if (cb[0]) was_done[b] = 1;
             else all_done = false;
@@ -916,45 +885,37 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     }
     if (io.mu_out && io.var_out) {
         for (int k = 0; k < 4; ++k)                            // (B evaluations of each copy, not the buffers' capacity)
-            HIP_TRY(c, hipMemcpyAsync(st_h + (size_t)k * cap * d, m->state + (size_t)k * cap * d, (size_t)B * d * sizeof(double),
+            HIP_TRY(c, hipMemcpyAsync(m->out.state + (size_t)k * cap * d, m->state + (size_t)k * cap * d, (size_t)B * d * sizeof(double),
                                       hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         for (int b = 0; b < B; ++b) {
             const bool in_b = iters[b] >= 1 && (iters[b] & 1);     // odd trips wrote copy B
-            memcpy(io.mu_out + (size_t)b * d, st_h + ((in_b ? 2 : 0) * (size_t)cap + b) * d, d * sizeof(double));
-            memcpy(io.var_out + (size_t)b * d, st_h + ((in_b ? 3 : 1) * (size_t)cap + b) * d, d * sizeof(double));
+            memcpy(io.mu_out + (size_t)b * d, m->out.state + ((in_b ? 2 : 0) * (size_t)cap + b) * d, d * sizeof(double));
+            memcpy(io.var_out + (size_t)b * d, m->out.state + ((in_b ? 3 : 1) * (size_t)cap + b) * d, d * sizeof(double));
         }
     }
     const double us_states = t.lap();
     if (io.grad_out) {
         // ---- the gradient of every evaluation's last committed sweep: grad.hip's batched pass over the B x G one-tile slots
         // (T = 1).  A stopped evaluation's launches were no-ops: X, s and both copies of its state are its last trip's; that
-        // trip wrote copy B when odd.  An evaluation whose pivot failed gets a row of zeros.
+        // trip wrote copy B when odd.
         const size_t nn = (size_t)c->ld * c->ld, nmat = 4 * (size_t)G + q;
         GradBatchIn in;
         in.N = c->N; in.ld = c->ld; in.T = 1; in.q = q; in.G = G; in.t = c->d_time;
         in.state = m->state; in.state_stride = d;
         for (int b = 0; b < B; ++b) {
-            double* const row = io.grad_out + (size_t)b * io.n_kpar;
-            if (info[b] > 0) { for (int k = 0; k < io.n_kpar; ++k) row[k] = 0.0; continue; }
+            if (!grad_batch_enter(io, b, in)) continue;
             double* const mb = m->mats + (size_t)b * nmat * nn;
             for (int g = 0; g < G; ++g) {
-                double* r4[GPRN_NBUF];
-                r4[BUF_B] = mb + (2 * (size_t)G + g) * nn; r4[BUF_X] = mb + (3 * (size_t)G + g) * nn;
-                r4[BUF_K] = mb + (size_t)g * nn; r4[BUF_KLINV] = mb + ((size_t)G + g) * nn;
-                in.rows.insert(in.rows.end(), r4, r4 + GPRN_NBUF);
+                in.rows.resize(in.rows.size() + GPRN_NBUF);
+                buf_row(&in.rows[in.rows.size() - GPRN_NBUF], mb + (2 * (size_t)G + g) * nn, mb + (3 * (size_t)G + g) * nn,
+                        mb + (size_t)g * nn, mb + ((size_t)G + g) * nn);
                 in.s.push_back(m->vecs + (size_t)b * 7 * G * c->ld + ((size_t)G + g) * c->ld);
             }
             for (int j = 1; j < q; ++j) in.kinv.push_back(mb + (4 * (size_t)G + j) * nn);
-            const bool in_b = iters[b] >= 1 && (iters[b] & 1);
-            in.state_idx.push_back((in_b ? 2 * cap : 0) + b);
-            in.kparams.push_back(io.kparams + (size_t)b * io.n_kpar);
-            in.out.push_back(row);
-            in.n += 1;
+            in.state_idx.push_back((iters[b] >= 1 && (iters[b] & 1) ? 2 * cap : 0) + b);
         }
-        // (its scratch gets what the buffers left of the budget; one evaluation's worth at the least)
-        const size_t budget = batch_budget_bytes(c), held = (size_t)cap * small_bytes_per_eval(c);
-        TRY(grad_batch_pass(c, c->kspec, in, budget > held ? budget - held : 0));
+        TRY(grad_batch_pass(c, c->kspec, in, grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c))));
     }
     const double us_grad = t.lap();
     if (batch_timers_on())
