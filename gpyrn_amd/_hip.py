@@ -92,6 +92,7 @@ SIGNATURES = {
     'gprn_grad_elbo': (c_int, [c_void_p, _dp, c_int]),
     'gprn_grad_matrix': (c_int, [c_void_p, c_int, _dp]),
     'gprn_eval_kernel': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, c_double, _dp]),
+    'gprn_eval_kernel_grad': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, _dp]),
     'gprn_sample_prior': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, c_double, c_int, _dp, _dp]),
 }
 
@@ -350,6 +351,16 @@ class Context:
         self._check(self._lib.gprn_eval_kernel(self._h, flat.ctypes.data_as(POINTER(c_int32)), flat.shape[0],
                                                _ptr(par), par.size, float(nugget), _ptr(K)), 'eval_kernel')
         return K
+
+    def eval_kernel_grad(self, ops, params):
+        """dK/dparams[l] of expr(t_i, t_j) at the data times, (n_params, N, N): the exact parameter derivatives of the
+        kernel program, evaluated on the device; each matrix symmetric to the bit, the nugget not differentiated."""
+        flat = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1, 3))
+        par = _f64(np.atleast_1d(params))
+        dK = np.empty((par.size, self.N, self.N))
+        self._check(self._lib.gprn_eval_kernel_grad(self._h, flat.ctypes.data_as(POINTER(c_int32)), flat.shape[0],
+                                                    _ptr(par), par.size, _ptr(dK)), 'eval_kernel_grad')
+        return dK
 
     def sample_prior(self, ops, params, nugget, z):
         """L z for every row z of standard normals, K + nugget I = L L^T; returns (samples, info)."""

@@ -167,6 +167,9 @@ static void watch_unregister(gprn_ctx* c)
 //                    as in rounds 1-2; -1: the default (31).  Results are bit-identical for every value
 //   "batch_mem_mb"   device memory (MiB) one chunk of gprn_elbocalc_batch's evaluations may take; longer lists run chunk by chunk
 //   "batch_mask"     1: gprn_elbocalc_batch / _batch_grad run under a data mask (gprn_set_mask); 0 (default): they refuse it
+//   "grad_exact"     1: gprn_grad_kernel, gprn_grad_elbo and gprn_elbocalc_batch_grad differentiate every kernel program exactly
+//                    (dk_eval.h) where they took Richardson-extrapolated differences; 0 (default): today's bits.  Read when a
+//                    gradient is asked for: nothing on the device changes, a committed sweep stays good for gprn_grad_elbo
 //   "comm_budget_s"  seconds an entry point may stay inside its collective section before the watchdog ends the process
 //   "accurate_factor" panel steps of a factorisation by substitution instead of products with explicit inverses (diag_tile.h
 //                    ACC): 0 never, 1 always (the launch path's sweeps too), -2 back to the default = every factorisation of a
@@ -188,6 +191,7 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     else if (!strcmp(name, "small_pad_kb")) field = &c->pad_small_kb_opt;
     else if (!strcmp(name, "batch_mem_mb")) field = &c->batch_mem_mb;
     else if (!strcmp(name, "batch_mask")) field = &c->batch_mask;
+    else if (!strcmp(name, "grad_exact")) field = &c->grad_exact;
     else if (!strcmp(name, "comm_budget_s")) field = &c->comm_budget_s;
     else if (!strcmp(name, "accurate_factor")) field = &c->acc_opt;
     else if (!strcmp(name, "fenced_finalize")) field = &c->fenced_finalize;
@@ -207,6 +211,7 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
         if (field == &c->batch_mem_mb && value < 1) return bad(c, "set_option: batch_mem_mb >= 1");
         if (field == &c->comm_budget_s && value < 1) return bad(c, "set_option: comm_budget_s >= 1");
         if (field == &c->batch_mask && value > 1) return bad(c, "set_option: batch_mask is 0 or 1");
+        if (field == &c->grad_exact && value > 1) return bad(c, "set_option: grad_exact is 0 or 1");
         *field = value;
         if (field == &c->comm_budget_s && c->watch) ((WatchEntry*)c->watch)->budget_s = value;
     }

@@ -769,6 +769,29 @@ extern "C" int gprn_sample_prior(gprn_ctx* c, const int32_t* ops, int n_ops, con
     return with_event_fallback(c, "sample_prior", [&](bool) { return sample_prior_impl(c, ks, nugget, n_samples, z, out); });
 }
 
+// dK/dtheta_l = d expr(t_i, t_j) / d params[l] at the data times for every parameter of the program, by the exact
+// derivatives of csrc/dk_eval.h (not in the reference; derivative hooks covfunc.py:172-185, 215-221, 257-266): the matrices
+// a caller contracts gprn_grad_matrix / gprn_grad_matrices with.  Symmetric to the bit; the nugget is not differentiated.
+// dK_out: (n_params, N, N) host.
+extern "C" int gprn_eval_kernel_grad(gprn_ctx* c, const int32_t* ops, int n_ops, const double* params, int n_params,
+                                     double* dK_out)
+{
+    DeviceLock lock_(c);
+    if (!c || !c->N || !dK_out) return bad(c, "eval_kernel_grad: call set_data first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    KernelSpec ks;
+    TRY(spec_from_args(c, ks, ops, n_ops, params, n_params, false));
+    if (!n_params) return GPRN_OK;
+    CallScratch scr(c);
+    double* d_dK = nullptr;
+    const size_t count = (size_t)n_params * c->N * c->N;
+    TRY(scr.alloc(&d_dK, count));
+    TRY(launch_fill_grad(c, ks, d_dK));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
+    HIP_TRY(c, hipMemcpy(dK_out, d_dK, count * sizeof(double), hipMemcpyDeviceToHost));
+    return GPRN_OK;
+}
+
 // ------------------------------------------------------------------ gradient pieces
 // At fixed variational state only the expected log prior depends on the hyper-parameters of latent GP g's
 // kernel (meanfield.py:992-1067):  -1/2 log det K - 1/2 (m^T K^-1 m + tr(K^-1 S)),  S = the covariance the
@@ -779,9 +802,11 @@ extern "C" int gprn_sample_prior(gprn_ctx* c, const int32_t* ops, int n_ops, con
 // O(N^2) contraction with dK/dtheta stays with the caller, who owns the kernel classes.
 // Kinv_out, P_out: (N, N), both symmetric (full).  One rank only (the node sum needs every node's Sigma).
 // kernel_grad != NULL: contract on the device instead of copying the matrices out -- needs a single SE / Periodic
-// / QuasiPeriodic kernel on latent GP `gp` and its mean vector m (N); kernel_grad[l], l < n_params.
+// / QuasiPeriodic kernel on latent GP `gp` (form 0), else differences of the program (1) or its exact derivatives (2: option
+// "grad_exact"), and its mean vector m (N); kernel_grad[l], l < n_params.
+enum { GRAD_FORM_CLOSED = 0, GRAD_FORM_FD = 1, GRAD_FORM_EXACT = 2 };
 static int grad_impl(gprn_ctx* c, int gp, double* Kinv_out, double* P_out, const double* m, double* kernel_grad,
-                     bool closed_form = false)
+                     int form = GRAD_FORM_FD)
 {
     if (c->world != 1) return bad(c, "grad_matrices: not available on a sharded context");
     if (!c->factored || !c->keep_sigma) return bad(c, "grad_matrices: needs factor_priors and a sweep with keep_sigma");
@@ -832,15 +857,23 @@ static int grad_impl(gprn_ctx* c, int gp, double* Kinv_out, double* P_out, const
         // slot 1's X workspace is free: [0, ld) the mean vector, [ld, 2 ld) a = K^-1 m, then the per-row partial sums
         const KernelSpec& ks = c->kspec[gp];
         double* const w = c->wsX[1];
-        const int np_out = closed_form ? 4 : ks.n_params;
+        const int np_out = form == GRAD_FORM_CLOSED ? 4 : ks.n_params;
+        double* d_sums = w + 6 * (size_t)ld;
         HIP_TRY(c, hipMemcpyAsync(w, m, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (closed_form)
-            TRY(vec_grad_contract(c, ks.ops[1], ks.params, dKinv, dS, w, w + ld, w + 2 * (size_t)ld, w + 6 * (size_t)ld));
-        else {
+        if (form == GRAD_FORM_CLOSED)
+            TRY(vec_grad_contract(c, ks.ops[1], ks.params, dKinv, dS, w, w + ld, w + 2 * (size_t)ld, d_sums));
+        else if (form == GRAD_FORM_EXACT) {
+            // (n_params rows of N partial sums: more than the workspace's spare vectors hold)
+            double* d_part = nullptr;
+            TRY(scr.alloc(&d_part, (size_t)ks.n_params * N));
+            TRY(scr.alloc(&d_sums, (size_t)ks.n_params));
             TRY(vec_symv(c, dKinv, w, w + ld));
-            TRY(launch_grad_fd(c, ks, dKinv, dS, w + ld, w + 2 * (size_t)ld, w + 6 * (size_t)ld));
+            TRY(launch_grad_exact(c, ks, dKinv, dS, w + ld, d_part, d_sums));
+        } else {
+            TRY(vec_symv(c, dKinv, w, w + ld));
+            TRY(launch_grad_fd(c, ks, dKinv, dS, w + ld, w + 2 * (size_t)ld, d_sums));
         }
-        HIP_TRY(c, hipMemcpyAsync(gh, w + 6 * (size_t)ld, (size_t)np_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(gh, d_sums, (size_t)np_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (int l = 0; l < ks.n_params && l < np_out; ++l) kernel_grad[l] = gh[l];
     } else {
@@ -864,7 +897,8 @@ extern "C" int gprn_grad_matrices(gprn_ctx* c, int gp, double* Kinv_out, double*
 // The whole kernel-parameter gradient of latent GP `gp` on the device: < 1/2 (K^-1 S K^-1 + a a^T - K^-1), dK/dtheta_l >,
 // a = K^-1 m -- closed-form dK/dtheta for a single SquaredExponential, Periodic or QuasiPeriodic (csrc/vecops.hip), the
 // central difference of the kernel program itself for every other built-in and Sum / Multiplication tree
-// (csrc/fill.hip, launch_grad_fd); GPRN_E_ARG for a latent GP whose K was uploaded (user kernels: the caller then
+// (csrc/fill.hip, launch_grad_fd) -- under option "grad_exact" its exact derivatives instead (csrc/dk_eval.h,
+// launch_grad_exact); GPRN_E_ARG for a latent GP whose K was uploaded (user kernels: the caller then
 // contracts gprn_grad_matrices' output itself).  m: the mean the reference pairs with that kernel (N); grad_out:
 // n_params values (NOT yet divided by q).
 extern "C" int gprn_grad_kernel(gprn_ctx* c, int gp, const double* m, double* grad_out)
@@ -880,7 +914,8 @@ extern "C" int gprn_grad_kernel(gprn_ctx* c, int gp, const double* m, double* gr
     const int kid = (ks.n_ops == 1 && ks.ops[0] == GPRN_OP_PUSH && ks.ops[2] == 0) ? ks.ops[1] : -1;
     const bool closed = kid == GPRN_K_SE || kid == GPRN_K_PERIODIC || kid == GPRN_K_QP;
     if (c->ld < 8 + GPRN_MAX_KPARAMS / 8) return bad(c, "grad_kernel: problem too small");
-    return grad_impl(c, gp, nullptr, nullptr, m, grad_out, closed);
+    const int form = closed ? GRAD_FORM_CLOSED : (c->grad_exact && grad_exact_applies(ks) ? GRAD_FORM_EXACT : GRAD_FORM_FD);
+    return grad_impl(c, gp, nullptr, nullptr, m, grad_out, form);
 }
 
 // ------------------------------------------------------------------ the ELBO's terms on their own

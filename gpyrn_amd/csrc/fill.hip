@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "fill_eval.h"
+#include "dk_eval.h"
 
 // One instantiation per built-in kernel id (KID >= 0: the switch in eval_kernel folds away, each
 // kernel carries only its own registers -- the all-in-one version needed 288 VGPRs, one wave per
@@ -182,10 +183,12 @@ void k_grad_fd_rows(FillProgram pp, FillProgram pm, double coef, int accumulate,
     if (lane == 0) part[m] = (accumulate ? part[m] : 0.0) + acc * coef;
 }
 
+// out[b] = sum_i part[b * n + i] in a fixed order, b = blockIdx.x (one sum per workgroup)
 __global__ __launch_bounds__(256)
 void k_sum_fixed(const double* __restrict__ part, int n, double* __restrict__ out)
 {
     __shared__ double sh[256];
+    part += (size_t)blockIdx.x * n;
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) acc += part[i];
     sh[threadIdx.x] = acc;
@@ -194,7 +197,7 @@ void k_sum_fixed(const double* __restrict__ part, int n, double* __restrict__ ou
         if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[0] = sh[0];
+    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
 // out[l], l < ks.n_params (device memory); a = Kinv m already formed; part: N doubles of scratch
@@ -218,6 +221,133 @@ int launch_grad_fd(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const 
         }
         hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(256), 0, c->stream, (const double*)part, c->N, out + l);
     }
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
+// ---- the same gradient with the EXACT parameter derivatives of the program (dk_eval.h; option "grad_exact"): one launch in
+// k_grad_rows' shape -- one wave per row of G, the program's leaves outermost so that at most five sums are live --
+//   part[(off + l) * N + m] += sum_n G[m][n] adj[m][n] dk_leaf/dq_l [m][n]     (off: the leaf's parameter offset)
+// into sums the host zeroed (two leaves that read one parameter add up, a parameter no leaf reads keeps 0, as a difference
+// of the program gives), then k_sum_fixed with one workgroup per parameter: 2 launches where launch_grad_fd needs 5 n_params.
+// Cost per element (dk_eval.h, dk_leaf): n_leaves kernel derivatives for a program without a MUL, n_leaves^2 kernel
+// evaluations with one -- every leaf's adjoint evaluates the other leaves' values.
+__global__ __launch_bounds__(256)
+void k_grad_exact_rows(FillProgram pg, const double* __restrict__ t, const double* __restrict__ Kinv,
+                       const double* __restrict__ P, const double* __restrict__ a, int N, int ld, double* __restrict__ part)
+{
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (m >= N) return;
+    const double tm = t[m], am = a[m];
+#pragma unroll 1
+    for (int leaf = 0; leaf < pg.n_ops; ++leaf) {
+        if (pg.ops[3 * leaf] != GPRN_OP_PUSH) continue;
+        double g0 = 0.0, g1 = 0.0, g2 = 0.0, g3 = 0.0, g4 = 0.0;
+#pragma unroll 1
+        for (int n = lane; n < N; n += 64) {
+            const double G = 0.5 * (P[(size_t)m * ld + n] - Kinv[(size_t)m * ld + n] + am * a[n]);
+            double d0, d1, d2, d3, d4;
+            dk_leaf(pg.ops, pg.n_ops, pg.par, leaf, tm, t[n], m == n, d0, d1, d2, d3, d4);
+            g0 += G * d0; g1 += G * d1; g2 += G * d2; g3 += G * d3; g4 += G * d4;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            g0 += __shfl_xor(g0, o); g1 += __shfl_xor(g1, o); g2 += __shfl_xor(g2, o); g3 += __shfl_xor(g3, o);
+            g4 += __shfl_xor(g4, o);
+        }
+        if (lane == 0) {
+            const int np = dk_nparams(pg.ops[3 * leaf + 1]);
+            double* const p = part + (size_t)pg.ops[3 * leaf + 2] * N + m;
+            p[0] += g0;
+            if (np > 1) p[(size_t)N] += g1;
+            if (np > 2) p[2 * (size_t)N] += g2;
+            if (np > 3) p[3 * (size_t)N] += g3;
+            if (np > 4) p[4 * (size_t)N] += g4;
+        }
+    }
+}
+
+// a leaf's parameters lie inside the program's (spec_from_args checks the offset alone)
+static bool leaves_in_range(const KernelSpec& ks)
+{
+    for (int o = 0; o < ks.n_ops; ++o)
+        if (ks.ops[3 * o] == GPRN_OP_PUSH && ks.ops[3 * o + 2] + dk_nparams(ks.ops[3 * o + 1]) > ks.n_params) return false;
+    return true;
+}
+
+bool grad_exact_applies(const KernelSpec& ks)
+{
+    return ks.set && !ks.uploaded && ks.n_ops >= 1 && ks.n_params >= 1 && leaves_in_range(ks);
+}
+
+// out[l], l < ks.n_params (device memory); a = Kinv m already formed; part: n_params * N doubles of scratch
+int launch_grad_exact(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const double* P, const double* a,
+                      double* part, double* out)
+{
+    FillProgram pg;
+    make_program(ks, 0.0, pg);
+    HIP_TRY(c, hipMemsetAsync(part, 0, (size_t)ks.n_params * c->N * sizeof(double), c->stream));
+    prof_begin(c, GPRN_T_VEC);
+    hipLaunchKernelGGL(k_grad_exact_rows, dim3((c->N + 3) / 4), dim3(256), 0, c->stream, pg, c->d_time, Kinv, P, a, c->N,
+                       c->ld, part);
+    hipLaunchKernelGGL(k_sum_fixed, dim3(ks.n_params), dim3(256), 0, c->stream, (const double*)part, c->N, out);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
+// ---- dK/dtheta_l itself (gprn_eval_kernel_grad): dK[(l * N + m) * N + n] for every parameter l of the program, by the exact
+// derivatives of dk_eval.h, in the symmetric fill's shape -- one workgroup per lower 64 x 64 block, a thread two adjacent
+// columns x 8 rows.  Only the elements n <= m are evaluated and each is written twice, so that dK = dK^T to the bit for
+// Polynomial as well (whose products t_i t_j commute only mathematically).  Leaves outermost as in k_grad_exact_rows, added
+// into a matrix the host zeroed: an element and its mirror image belong to one thread.
+__global__ __launch_bounds__(256)
+void k_fill_grad(FillProgram pg, const double* __restrict__ t, double* __restrict__ dK, int N)
+{
+    const int L = blockIdx.x;
+    int bi = (int)((sqrt(8.0 * L + 1.0) - 1.0) * 0.5);
+    while ((bi + 1) * (bi + 2) / 2 <= L) ++bi;
+    while (bi * (bi + 1) / 2 > L) --bi;
+    const int bj = L - bi * (bi + 1) / 2;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const size_t nn = (size_t)N * N;
+#pragma unroll 1
+    for (int leaf = 0; leaf < pg.n_ops; ++leaf) {
+        if (pg.ops[3 * leaf] != GPRN_OP_PUSH) continue;
+        const int np = dk_nparams(pg.ops[3 * leaf + 1]);
+        double* const base = dK + (size_t)pg.ops[3 * leaf + 2] * nn;
+#pragma unroll 1
+        for (int i = 0; i < 16; ++i) {
+            const int m = bi * 64 + ty + 8 * (i >> 1), n = bj * 64 + 2 * tx + (i & 1);
+            if (m >= N || n > m) continue;
+            double d0, d1, d2, d3, d4;
+            dk_leaf(pg.ops, pg.n_ops, pg.par, leaf, t[m], t[n], m == n, d0, d1, d2, d3, d4);
+            auto put = [&](int l, double v) {
+                double* const p = base + (size_t)l * nn;
+                const double s = p[(size_t)m * N + n] + v;
+                p[(size_t)m * N + n] = s;
+                if (n != m) p[(size_t)n * N + m] = s;
+            };
+            put(0, d0);
+            if (np > 1) put(1, d1);
+            if (np > 2) put(2, d2);
+            if (np > 3) put(3, d3);
+            if (np > 4) put(4, d4);
+        }
+    }
+}
+
+// dK: n_params * N * N doubles (device), row-major per parameter without padding
+int launch_fill_grad(gprn_ctx* c, const KernelSpec& ks, double* dK)
+{
+    if (!leaves_in_range(ks)) { c->err = "eval_kernel_grad: a kernel's parameters run past n_params"; return GPRN_E_ARG; }
+    FillProgram pg;
+    make_program(ks, 0.0, pg);
+    const int nb = (c->N + 63) / 64;
+    HIP_TRY(c, hipMemsetAsync(dK, 0, (size_t)ks.n_params * c->N * c->N * sizeof(double), c->stream));
+    prof_begin(c, GPRN_T_FILL);
+    hipLaunchKernelGGL(k_fill_grad, dim3(nb * (nb + 1) / 2), dim3(256), 0, c->stream, pg, c->d_time, dK, c->N);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

@@ -270,6 +270,7 @@ struct gprn_ctx {
     int mask_upad_ph[2] = {0, 0};        // max |U| over the entries, rounded up to 128
     bool mask_ready = false;             // the buffers, tables and task lists above match the problem and the slots
     int batch_mask = 0;                  // gprn_set_option "batch_mask": gprn_elbocalc_batch* run under a data mask (default: refused)
+    int grad_exact = 0;                  // gprn_set_option "grad_exact": the gradient entry points take dK/dtheta from dk_eval.h, not from differences
     MaskBatch mask_batch[2];             // a batch's worker context (midn.hip): the lanes of its node / weight phase
 
     // ---- small-N path (smalln.hip): problems of one or two tiles run a half-sweep as ONE launch, one workgroup per latent GP
@@ -387,6 +388,15 @@ int launch_tiles(gprn_ctx* c, const TileTask* d_tasks, size_t ntasks, double** d
 // program, on the device (fill.hip); out: n_params doubles of device memory, part: N doubles of scratch
 int launch_grad_fd(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const double* P, const double* a,
                    double* part, double* out);
+// the same by the exact derivatives of the program (dk_eval.h; option "grad_exact"): part: n_params * N doubles of scratch.
+// grad_exact_applies: the kernel has a device program whose leaves' parameters all lie inside its own (what the parameter
+// sums are sized by); a program that fails it keeps the difference path under the option
+bool grad_exact_applies(const KernelSpec& ks);
+int launch_grad_exact(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const double* P, const double* a,
+                      double* part, double* out);
+// dK/dtheta_l at the data times for every parameter of the program, exact derivatives, symmetric to the bit (fill.hip);
+// dK: n_params * N * N doubles of device memory without padding
+int launch_fill_grad(gprn_ctx* c, const KernelSpec& ks, double* dK);
 // the L part (n_l tasks) and the X part (n_x tasks) of a tile step's panel in one launch (gemm_tile.hip); acc: the L part
 // by substitution
 int launch_panel(gprn_ctx* c, const TileTask* d_tasks, size_t n_l, size_t n_x, double** d_ptrs, int nbatch, int ld,
@@ -536,6 +546,7 @@ struct GradBatchIn {
     std::vector<int> state_idx;            // [n]
     std::vector<const double*> kparams;    // [n] (host): the evaluation's kernel parameters
     std::vector<double*> out;              // [n] (host): its row of grad_out
+    int grad_exact = 0;                    // the caller's option "grad_exact"
 };
 // w: the context the launches go through (its stream, its task lists, its grad_scratch); budget: bytes the pass's scratch may
 // take -- beyond it (or when the device refuses) the evaluations go in groups; GPRN_E_NOMEM when one evaluation's scratch does

@@ -14,7 +14,7 @@
 //   k_grad_cross_prep        sum_{k<j} Sigma_fk and the full K_j^-1 of the nodes j >= 1 (operands of the two GEMMs)
 //   k_lower_tmatvec_*        a = L^-T u: column sums over 128-row chunks, then the chunks in a fixed order
 //   k_grad_residual          m - K a, for one step of iterative refinement of a
-//   k_grad_contract_b<FD>    < G, dK/dtheta_l > for all parameters of all latent GPs: 64 x 64 lower blocks, grid.y = latent GP
+//   k_grad_contract_b<MODE>  < G, dK/dtheta_l > for all parameters of all latent GPs: 64 x 64 lower blocks, grid.y = latent GP
 //   k_grad_final             the blocks' partial sums in a fixed order (no floating-point atomics: two calls, same bits)
 //   k_grad_matrix_full       G itself, symmetric, for kernels the caller differentiates (gprn_grad_matrix)
 //
@@ -23,11 +23,13 @@
 #include "api_internal.h"
 #include "fill_eval.h"
 #include "grad_elem.h"
+#include "dk_eval.h"
 
 // what k_grad_contract_b knows of one latent GP
 struct GradSlot {
     FillProgram pg;            // the kernel program at the current parameters
-    int mode;                  // -1: no entry (K was uploaded), 0: closed forms (single SE / Periodic / QP), 1: Richardson differences
+    int mode;                  // -1: no entry (K was uploaded), 0: closed forms (single SE / Periodic / QP), 1: Richardson differences,
+                               // 2: the exact derivatives of the program (dk_eval.h; option "grad_exact")
     int kid, n_params, out_off;
     const double* Binv;        // lower(B^-1), pitch ld
     const double* s;           // sqrt(d) of the last sweep
@@ -146,13 +148,17 @@ void k_grad_residual(double* const* __restrict__ Ks, const double* __restrict__ 
 // Periodic / QP, else Richardson's extrapolation of two central differences of the kernel program, steps h and h / 2 with
 // h = 1e-6 max(1, |theta_l|) (grad_fd_elem: the arithmetic of k_grad_rows / k_grad_fd_rows) -- the program with theta_l
 // moved lives in LDS four times (+h, -h, +h/2, -h/2), and a parameter's pass re-reads the block from the cache, not from HBM.
-template <bool FD>
+// MODE 2 (option "grad_exact"): the exact derivatives of the program (dk_eval.h), its leaves outermost -- one pass over the
+// block per LEAF with at most five sums live, (adjoint of the leaf) x (leaf derivative) per element, added to the sums of the
+// leaf's parameters by thread 0, which zeroed them: leaves that share a parameter add up, a parameter no leaf reads keeps 0.
+// The program is read where it lies in the slot's LDS copy: no moved copies.
+template <int MODE>
 __global__ __launch_bounds__(256)
 void k_grad_contract_b(const GradSlot* __restrict__ slots, const double* __restrict__ t, int N, int ld, int nblk, int pmax,
                        double* __restrict__ part)
 {
     __shared__ GradSlot sl;
-    __shared__ FillProgram spg[4];
+    __shared__ FillProgram spg[MODE == 2 ? 1 : 4];
     __shared__ double st[2][64], ss[2][64], sa[2][64];
     __shared__ double sh[4];
     const int tid = threadIdx.x, g = blockIdx.y, blk = blockIdx.x;
@@ -162,7 +168,7 @@ void k_grad_contract_b(const GradSlot* __restrict__ slots, const double* __restr
         for (int i = tid; i < (int)(sizeof(GradSlot) / sizeof(int)); i += 256) dst[i] = src[i];
     }
     __syncthreads();
-    if (sl.mode != (FD ? 1 : 0)) return;               // (uniform: the other instantiation's slot, or no entry at all)
+    if (sl.mode != MODE) return;                       // (uniform: another instantiation's slot, or no entry at all)
     // lower-triangular block index -> (bi, bj), bi >= bj
     int bi = (int)((sqrt(8.0 * blk + 1.0) - 1.0) * 0.5);
     while ((bi + 1) * (bi + 2) / 2 <= blk) ++bi;
@@ -175,7 +181,7 @@ void k_grad_contract_b(const GradSlot* __restrict__ slots, const double* __restr
         ss[side][k] = in ? sl.s[idx] : 0.0;
         sa[side][k] = in ? sl.a[idx] : 0.0;
     }
-    if (FD) {
+    if (MODE == 1) {
         const int* src = reinterpret_cast<const int*>(&slots[g].pg);
         for (int k = 0; k < 4; ++k) {
             int* dst = reinterpret_cast<int*>(&spg[k]);
@@ -203,7 +209,7 @@ void k_grad_contract_b(const GradSlot* __restrict__ slots, const double* __restr
         G1 = (m < N && n + 1 <= m) ? (n + 1 == m ? e1 : 2.0 * e1) : 0.0;
     };
     double* const out = part + ((size_t)g * pmax) * nblk + blk;
-    if constexpr (!FD) {
+    if constexpr (MODE == 0) {
         const int kid = sl.kid;
         const double q0 = sl.pg.par[0], q1 = sl.pg.par[1], q2 = sl.pg.par[2], q3 = sl.pg.par[3];
         double g0 = 0.0, g1 = 0.0, g2 = 0.0, g3 = 0.0;
@@ -226,6 +232,43 @@ void k_grad_contract_b(const GradSlot* __restrict__ slots, const double* __restr
             if (pmax > 1) out[(size_t)nblk] = g1;
             if (pmax > 2) out[2 * (size_t)nblk] = g2;
             if (pmax > 3) out[3 * (size_t)nblk] = g3;
+        }
+    } else if constexpr (MODE == 2) {
+        if (tid == 0)
+            for (int l = 0; l < sl.n_params; ++l) out[(size_t)l * nblk] = 0.0;
+#pragma unroll 1
+        for (int leaf = 0; leaf < sl.pg.n_ops; ++leaf) {
+            if (sl.pg.ops[3 * leaf] != GPRN_OP_PUSH) continue;         // (uniform)
+            double g0 = 0.0, g1 = 0.0, g2 = 0.0, g3 = 0.0, g4 = 0.0;
+#pragma unroll 1
+            for (int i = 0; i < 8; ++i) {
+                const int r = ty + 8 * i, m = bi * 64 + r;
+                double G01[2];
+                weighted_G(r, G01[0], G01[1]);
+                const double tm = st[0][r];
+#pragma unroll 1
+                for (int e = 0; e < 2; ++e) {
+                    const double tn = e ? tn1 : tn0, G = e ? G01[1] : G01[0];
+                    if (G == 0.0) continue;                            // (above the diagonal, the padding)
+                    double d0, d1, d2, d3, d4;
+                    dk_leaf(sl.pg.ops, sl.pg.n_ops, sl.pg.par, leaf, tm, tn, m == n + e, d0, d1, d2, d3, d4);
+                    g0 += G * d0; g1 += G * d1; g2 += G * d2; g3 += G * d3; g4 += G * d4;
+                }
+            }
+            const int np = dk_nparams(sl.pg.ops[3 * leaf + 1]);
+            double* const o = out + (size_t)sl.pg.ops[3 * leaf + 2] * nblk;
+            g0 = grad_block_sum(g0, sh);
+            if (np > 1) g1 = grad_block_sum(g1, sh);
+            if (np > 2) g2 = grad_block_sum(g2, sh);
+            if (np > 3) g3 = grad_block_sum(g3, sh);
+            if (np > 4) g4 = grad_block_sum(g4, sh);
+            if (tid == 0) {
+                o[0] += g0;
+                if (np > 1) o[(size_t)nblk] += g1;
+                if (np > 2) o[2 * (size_t)nblk] += g2;
+                if (np > 3) o[3 * (size_t)nblk] += g3;
+                if (np > 4) o[4 * (size_t)nblk] += g4;
+            }
         }
     } else
     for (int l = 0; l < sl.n_params; ++l) {
@@ -304,12 +347,12 @@ struct GradWork {
 };
 
 // the kernel's part of a slot: the program at `params`, which derivative applies (gprn_grad_kernel's rules), where its sums go
-static void grad_slot_kernel(const KernelSpec& ks, const double* params, int out_off, GradSlot* s)
+static void grad_slot_kernel(const KernelSpec& ks, const double* params, int out_off, GradSlot* s, int exact)
 {
     fill_program_with(ks, params, &s->pg, 1e-6);
     const int kid = (ks.n_ops == 1 && ks.ops[0] == GPRN_OP_PUSH && ks.ops[2] == 0) ? ks.ops[1] : -1;
     const bool closed = kid == GPRN_K_SE || kid == GPRN_K_PERIODIC || kid == GPRN_K_QP;
-    s->mode = closed ? 0 : 1;
+    s->mode = closed ? 0 : (exact && grad_exact_applies(ks) ? 2 : 1);
     s->kid = kid; s->n_params = ks.n_params; s->out_off = out_off;
 }
 
@@ -455,7 +498,7 @@ extern "C" int gprn_grad_elbo(gprn_ctx* c, double* grad_out, int n_out)
         s.Binv = c->wsB[g]; s.s = c->d_s + (size_t)g * ld; s.a = w.a + (size_t)g * ld;
         s.cross = g < q ? w.cross[g] : nullptr;
         if (ks.uploaded) continue;
-        grad_slot_kernel(ks, ks.params, off, &s);
+        grad_slot_kernel(ks, ks.params, off, &s, c->grad_exact);
         off += ks.n_params;
         if (s.mode == 0) pmax = std::max(pmax, 4);     // (k_grad_contract_b's closed forms write four sums)
     }
@@ -467,15 +510,20 @@ extern "C" int gprn_grad_elbo(gprn_ctx* c, double* grad_out, int n_out)
     TRY(scr.alloc(&d_out, (size_t)total));
     HIP_TRY(c, hipMemcpyAsync(d_slots, slots.data(), slots.size() * sizeof(GradSlot), hipMemcpyHostToDevice, c->stream));
     prof_begin(c, GPRN_T_VEC);
-    bool any_closed = false, any_fd = false;
-    for (const GradSlot& s : slots) { any_closed = any_closed || s.mode == 0; any_fd = any_fd || s.mode == 1; }
-    // (one instantiation per kind of derivative: the generic program costs 241 VGPRs, the closed forms half of that; a
-    // workgroup whose slot belongs to the other one returns at once)
+    bool any_closed = false, any_fd = false, any_exact = false;
+    for (const GradSlot& s : slots) { any_closed = any_closed || s.mode == 0; any_fd = any_fd || s.mode == 1; any_exact = any_exact || s.mode == 2; }
+    // (one instantiation per kind of derivative -- <0> closed forms 148 VGPRs, <1> differences of the program 256 VGPRs and
+    // four copies of it in LDS, as before the exact form came, <2> its exact derivatives, a few registers fewer and no copy
+    // (profiles/grad_exact_isa_resources.txt); a workgroup
+    // whose slot belongs to another instantiation returns at once)
     if (any_closed)
-        hipLaunchKernelGGL(k_grad_contract_b<false>, dim3(nblk, G), dim3(256), 0, c->stream, (const GradSlot*)d_slots,
+        hipLaunchKernelGGL(k_grad_contract_b<0>, dim3(nblk, G), dim3(256), 0, c->stream, (const GradSlot*)d_slots,
                            (const double*)c->d_time, c->N, ld, nblk, pmax, d_part);
     if (any_fd)
-        hipLaunchKernelGGL(k_grad_contract_b<true>, dim3(nblk, G), dim3(256), 0, c->stream, (const GradSlot*)d_slots,
+        hipLaunchKernelGGL(k_grad_contract_b<1>, dim3(nblk, G), dim3(256), 0, c->stream, (const GradSlot*)d_slots,
+                           (const double*)c->d_time, c->N, ld, nblk, pmax, d_part);
+    if (any_exact)
+        hipLaunchKernelGGL(k_grad_contract_b<2>, dim3(nblk, G), dim3(256), 0, c->stream, (const GradSlot*)d_slots,
                            (const double*)c->d_time, c->N, ld, nblk, pmax, d_part);
     hipLaunchKernelGGL(k_grad_final, dim3(pmax, G), dim3(256), 0, c->stream, (const GradSlot*)d_slots, (const double*)d_part, nblk,
                        pmax, d_out);
@@ -514,12 +562,12 @@ extern "C" int gprn_grad_matrix(gprn_ctx* c, int gp, double* G_out)
 
 // ------------------------------------------------------------------ many evaluations (gprn_elbocalc_batch_grad)
 // what the kernels of one latent GP ask of the contraction's partial sums: total parameters, widest row of `part`
-static void grad_batch_counts(const std::vector<KernelSpec>& kspec, int* total, int* pmax)
+static void grad_batch_counts(const std::vector<KernelSpec>& kspec, int exact, int* total, int* pmax)
 {
     *total = 0; *pmax = 1;
     GradSlot probe;
     for (const KernelSpec& ks : kspec) {
-        grad_slot_kernel(ks, ks.params, 0, &probe);
+        grad_slot_kernel(ks, ks.params, 0, &probe, exact);
         *total += ks.n_params;
         *pmax = std::max(*pmax, probe.mode == 0 ? std::max(4, ks.n_params) : ks.n_params);
     }
@@ -614,7 +662,7 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
             }
             GradSlot& s = slots[sl];
             memset(&s, 0, sizeof(s));
-            grad_slot_kernel(kspec[g], kp + off, e * total + off, &s);
+            grad_slot_kernel(kspec[g], kp + off, e * total + off, &s, in.grad_exact);
             s.Binv = row[BUF_B]; s.s = in.s[(size_t)ev * G + g]; s.a = a + sl * ld; s.cross = cr;
             off += kspec[g].n_params;
         }
@@ -660,14 +708,19 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
         HIP_TRY(w, hipGetLastError());
     }
     // (4) the contraction and its fixed-order sums, grid y = slot
-    bool any_closed = false, any_fd = false;
-    for (int g = 0; g < G; ++g) { any_closed = any_closed || slots[g].mode == 0; any_fd = any_fd || slots[g].mode == 1; }
+    bool any_closed = false, any_fd = false, any_exact = false;
+    for (int g = 0; g < G; ++g) {
+        any_closed = any_closed || slots[g].mode == 0; any_fd = any_fd || slots[g].mode == 1; any_exact = any_exact || slots[g].mode == 2;
+    }
     prof_begin(w, GPRN_T_VEC);
     if (any_closed)
-        hipLaunchKernelGGL(k_grad_contract_b<false>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+        hipLaunchKernelGGL(k_grad_contract_b<0>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
                            N, ld, nblk, pmax, part);
     if (any_fd)
-        hipLaunchKernelGGL(k_grad_contract_b<true>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+        hipLaunchKernelGGL(k_grad_contract_b<1>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+                           N, ld, nblk, pmax, part);
+    if (any_exact)
+        hipLaunchKernelGGL(k_grad_contract_b<2>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
                            N, ld, nblk, pmax, part);
     hipLaunchKernelGGL(k_grad_final, dim3(pmax, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, (const double*)part,
                        nblk, pmax, d_out);
@@ -683,7 +736,7 @@ int grad_batch_pass(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const Gra
 {
     if (!in.n) return GPRN_OK;
     int total = 0, pmax = 1;
-    grad_batch_counts(kspec, &total, &pmax);
+    grad_batch_counts(kspec, in.grad_exact, &total, &pmax);
     if (!total) return GPRN_OK;
     const size_t per = grad_batch_bytes(in, total, pmax);
     // (a launch's grid y or z is the number of slots of the group: far below its 65 535 limit)

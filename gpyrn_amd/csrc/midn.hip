@@ -444,7 +444,7 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
         const size_t nn = (size_t)m->ld * m->ld;
         GradBatchIn in;
         in.N = N; in.ld = m->ld; in.T = w->T; in.q = q; in.G = G; in.t = w->d_time;
-        in.state = w->d_mu; in.state_stride = d;
+        in.state = w->d_mu; in.state_stride = d; in.grad_exact = c->grad_exact;
         for (int b = 0; b < B; ++b) {
             if (!grad_batch_enter(io, b, in)) continue;
             for (int g = 0; g < G; ++g) {

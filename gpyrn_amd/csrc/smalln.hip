@@ -902,7 +902,7 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
         const size_t nn = (size_t)c->ld * c->ld, nmat = 4 * (size_t)G + q;
         GradBatchIn in;
         in.N = c->N; in.ld = c->ld; in.T = 1; in.q = q; in.G = G; in.t = c->d_time;
-        in.state = m->state; in.state_stride = d;
+        in.state = m->state; in.state_stride = d; in.grad_exact = c->grad_exact;
         for (int b = 0; b < B; ++b) {
             if (!grad_batch_enter(io, b, in)) continue;
             double* const mb = m->mats + (size_t)b * nmat * nn;

@@ -75,12 +75,20 @@ class inference:
             evaluates one vector after the other, each from its predecessor's state; on, all of them start from one
             shared state, which moves rule-stopped values within the stop rule's 1e-3.  An attribute that may be set
             later, as ``batch_max_N``.  Without a mask it changes nothing.
+        exact_derivatives: bool (default False), keyword only
+            Whether the gradients (``grad_ELBO`` in both forms, ``nELBO_and_grad``, ``nELBO_and_grad_batch``,
+            ``optimize(jac=True, ...)``) differentiate every kernel with a device program exactly on the GPU (option
+            ``"grad_exact"`` of the library: Matern, RationalQuadratic, ..., every Sum / Multiplication) where they take
+            Richardson-extrapolated central differences of the program by default.  A single SquaredExponential, Periodic
+            or QuasiPeriodic keeps its closed form and its bits; kernels without a device program (user subclasses, a Sum
+            that holds a two-argument kernel) are contracted on the host as before.  An attribute that may be set later:
+            it goes to the device with every set-up.
     """
 
     _SWEEP_ORDERS = {'reference': _hip.ORDER_REFERENCE, 'sequential': _hip.ORDER_SEQUENTIAL}
 
     def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference',
-                 batch_under_mask=False):
+                 batch_under_mask=False, exact_derivatives=False):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -104,6 +112,7 @@ class inference:
             self.yerr = np.where(self.mask, self.yerr, 1.0)
         self.yerr2 = self.yerr**2
         self.batch_under_mask = bool(batch_under_mask)
+        self.exact_derivatives = bool(exact_derivatives)
 
         self._components_set = False
         self._frozen_mask = np.array([])
@@ -524,6 +533,7 @@ class inference:
     def _setup_device(self, nodes, weights, means, jitters):
         """The setup block of ELBOcalc (meanfield.py:618-624) on the GPU."""
         ctx = self._backend()
+        ctx.option('grad_exact', 1 if self.exact_derivatives else 0)   # (every set-up: the attribute may have changed)
         specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
         key = tuple(self._spec_key(s) for s in specs)
         if key != self._prior_key:             # unchanged hyper-parameters keep their factors
@@ -1090,6 +1100,7 @@ class inference:
             return None
         ctx = self._backend()
         ctx.option('batch_mask', 1 if self.batch_under_mask else 0)   # (every call: the attribute may have changed)
+        ctx.option('grad_exact', 1 if self.exact_derivatives else 0)
         y_raw = np.concatenate(self.y)
         B = len(sets)
         state = (self._mu, self._var) if start is None else (np.asarray(start[0], dtype=float), np.asarray(start[1], dtype=float))

@@ -195,7 +195,18 @@ int gprn_predict_upload_kss(gprn_ctx* ctx, int gp, int ns, const double* Kss);
  * sample_prior: out[s] = L z[s], K + nugget I = L L^T by the blocked factorisation: replaces
  * inference._sample_from_gp / sample (:517-539), which draw from scipy's multivariate_normal.  z, out:
  * (n_samples, N); z = standard normals of the caller's generator.  Returns info > 0 when K + nugget I is
- * not positive definite in fp64. */
+ * not positive definite in fp64.
+ * eval_kernel_grad (not in the reference; derivative hooks covfunc.py:172-185, 215-221, 257-266): dK_out[l] =
+ * d expr(t_i, t_j) / d params[l] at the data times for every parameter of the expression, (n_params, N, N), by the exact
+ * parameter derivatives of every built-in kernel (csrc/dk_eval.h: the two-argument and the derivative kernels included) and
+ * the product rule over the expression's Sum / Multiplication tree; the nugget is not differentiated, WhiteNoise contributes
+ * on the diagonal only.  Each matrix is symmetric to the bit; within 2e-11 max |dK/dtheta_l| of a long-double derivative of
+ * the kernel formulas (tests/test_grad_exact_gpu.py: every kernel id, periods down to 0.3 over a span of 60 -- the harmonic
+ * kernels reduce their phases by whole periods before they multiply by pi).  Finite on the diagonal, 0 beyond
+ * Piecewise's support, NaN where a NaN parameter makes the kernel NaN.  It always takes the exact form (no option).
+ * GPRN_E_ARG for an expression one of whose kernels reads parameters past n_params. */
+int gprn_eval_kernel_grad(gprn_ctx* ctx, const int32_t* ops, int n_ops, const double* params, int n_params,
+                          double* dK_out);
 int gprn_eval_kernel(gprn_ctx* ctx, const int32_t* ops, int n_ops, const double* params, int n_params,
                      double nugget, double* K_out);
 int gprn_sample_prior(gprn_ctx* ctx, const int32_t* ops, int n_ops, const double* params, int n_params,
@@ -218,7 +229,17 @@ int gprn_grad_matrices(gprn_ctx* ctx, int gp, double* Kinv_out, double* P_out);
  * tests/test_fill_gpu.py against a long-double reference dK/dtheta: closed forms within 1e-12 sum |G| |dK/dtheta|,
  * differences within 1e-7 sum |G| |dK/dtheta| + 8 2^-53 sum |G| |K| / h (G = 1/2 (K^-1 S K^-1 + a a^T - K^-1); the second
  * term is the rounding of K that any difference of step h carries), periods down to 0.3 over a span of 60 and length
- * scales down to a third of the sampling included.  GPRN_E_UNSUPPORTED for a latent GP whose matrix was uploaded (gprn_upload_K). */
+ * scales down to a third of the sampling included.  GPRN_E_UNSUPPORTED for a latent GP whose matrix was uploaded (gprn_upload_K).
+ * Option "grad_exact" = 1 (gprn_set_option; default 0): every kernel that is not one of the three closed forms takes the
+ * EXACT dK/dtheta of its program (csrc/dk_eval.h, what gprn_eval_kernel_grad returns) in place of the differences: one
+ * derivative per kernel of the expression (with a Multiplication, each with the values of the other kernels) instead of four
+ * evaluations of the program per parameter, and the closed forms' accuracy for every kernel: 1e-12 sum |G| |dK/dtheta|, no
+ * noise term.  tests/test_grad_exact_gpu.py holds every kernel of its list to that in three regimes, but for the few it
+ * names (BEYOND_THE_REFERENCE: the WhiteNoise amplitude beside the large diagonal of a derivative kernel, parameters that a
+ * decay of 0.2 hides), where the long-double reference itself is the noisy side: a plain fp64 NumPy evaluation of the same
+ * derivative misses 1e-12 there by the same amount to three digits, and the bound is four times its error.  The three closed forms keep their code and their bits; with the option
+ * at 0 every result has the bits it had.  A program one of whose kernels reads parameters past n_params keeps the
+ * differences under the option. */
 int gprn_grad_kernel(gprn_ctx* ctx, int gp, const double* m, double* grad_out);
 /* ---- the same gradient for EVERY latent GP in one call, in the B-form: no gprn_keep_sigma, no K^-1, no
  * explicit Sigma, one host synchronisation.  With B = I + S K S, S = diag(s), and X = chol(B)^-1 as the last sweep left it,
@@ -227,7 +248,10 @@ int gprn_grad_kernel(gprn_ctx* ctx, int gp, const double* m, double* grad_out);
  * a = K_gp^-1 m_gp, m_gp = the state row of latent GP gp as it lies in memory (quirk Q2),
  *   weight:  M = - S B^-1 S;    node j:  M = - S B^-1 S + sum_{k<j} K_j^-1 Sigma_fk K_j^-1   (quirk Q1),
  * the nugget not differentiated.  dK/dtheta by gprn_grad_kernel's rules (closed forms for a single SE / Periodic /
- * QuasiPeriodic, Richardson-extrapolated central differences of the kernel program with h = 1e-6 max(1, |theta|) otherwise).
+ * QuasiPeriodic, Richardson-extrapolated central differences of the kernel program with h = 1e-6 max(1, |theta|) otherwise --
+ * under option "grad_exact" the exact derivatives of the program in their place, as there; gprn_elbocalc_batch_grad follows
+ * the same option).  The option is read when a gradient is asked for and changes nothing on the device: setting it does not
+ * end a committed sweep's validity.
  * gprn_grad_elbo: d/dtheta of the expected log prior of the LAST COMMITTED sweep for every kernel parameter of every latent
  * GP: grad_out = concatenation over gp = 0 .. G-1 of n_params[gp] values (the layout of gprn_elbocalc_batch's kernel_params; a
  * latent GP whose K was uploaded contributes no entry), NOT divided by q.  n_out: the length of grad_out (GPRN_E_ARG if it
@@ -416,6 +440,10 @@ int gprn_predict_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, i
  * evaluations per chunk in the last gprn_elbocalc_batch call); "batch_mask" (0, the default: gprn_elbocalc_batch and
  * gprn_elbocalc_batch_grad refuse a context with a data mask; 1: they run under it -- side by side every evaluation starts from
  * one shared state, which moves rule-stopped values within the stop rule's 1e-3 against one evaluation after the other);
+ * "grad_exact" (0, the default: gprn_grad_kernel, gprn_grad_elbo and gprn_elbocalc_batch_grad differentiate a kernel that is
+ * not a single SE / Periodic / QuasiPeriodic by Richardson-extrapolated differences of its program; 1: by the program's exact
+ * parameter derivatives, csrc/dk_eval.h -- the rules and the accuracy at gprn_grad_kernel; any other value: GPRN_E_ARG.  It is
+ * read when a gradient is asked for and touches nothing on the device: a committed sweep stays good for gprn_grad_elbo);
  * "comm_budget_s" (sharded contexts: seconds an entry point may stay inside its collective section -- a rank that
  * died leaves the others there -- before the library's watchdog names the entry point, the collective and the rank on
  * stderr and ends the process with status 86; default 600, or GPRN_COMM_BUDGET_S); "accurate_factor" (the panel steps of
