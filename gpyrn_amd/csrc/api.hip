@@ -167,6 +167,8 @@ static void watch_unregister(gprn_ctx* c)
 //                    as in rounds 1-2; -1: the default (31).  Results are bit-identical for every value
 //   "batch_mem_mb"   device memory (MiB) one chunk of gprn_elbocalc_batch's evaluations may take; longer lists run chunk by chunk
 //   "batch_mask"     1: gprn_elbocalc_batch / _batch_grad run under a data mask (gprn_set_mask); 0 (default): they refuse it
+//   "order_mask"     1: a data mask (gprn_set_mask) and the sequential sweep order (gprn_set_sweep_order) may be in force together
+//                    (order.hip's masked refresh); 0 (default): each refuses the other.  Not switched off while both are in force
 //   "grad_exact"     1: gprn_grad_kernel, gprn_grad_elbo and gprn_elbocalc_batch_grad differentiate every kernel program exactly
 //                    (dk_eval.h) where they took Richardson-extrapolated differences; 0 (default): today's bits.  Read when a
 //                    gradient is asked for: nothing on the device changes, a committed sweep stays good for gprn_grad_elbo
@@ -191,6 +193,7 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     else if (!strcmp(name, "small_pad_kb")) field = &c->pad_small_kb_opt;
     else if (!strcmp(name, "batch_mem_mb")) field = &c->batch_mem_mb;
     else if (!strcmp(name, "batch_mask")) field = &c->batch_mask;
+    else if (!strcmp(name, "order_mask")) field = &c->order_mask;
     else if (!strcmp(name, "grad_exact")) field = &c->grad_exact;
     else if (!strcmp(name, "comm_budget_s")) field = &c->comm_budget_s;
     else if (!strcmp(name, "accurate_factor")) field = &c->acc_opt;
@@ -211,6 +214,12 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
         if (field == &c->batch_mem_mb && value < 1) return bad(c, "set_option: batch_mem_mb >= 1");
         if (field == &c->comm_budget_s && value < 1) return bad(c, "set_option: comm_budget_s >= 1");
         if (field == &c->batch_mask && value > 1) return bad(c, "set_option: batch_mask is 0 or 1");
+        if (field == &c->order_mask && value > 1) return bad(c, "set_option: order_mask is 0 or 1");
+        if (field == &c->order_mask && !value && c->d_mask && c->sweep_order != GPRN_ORDER_REFERENCE) {
+            c->err = "set_option: order_mask stays 1 while a data mask (gprn_set_mask) and the sequential sweep order "
+                     "(gprn_set_sweep_order) are both in force";
+            return GPRN_E_UNSUPPORTED;
+        }
         if (field == &c->grad_exact && value > 1) return bad(c, "set_option: grad_exact is 0 or 1");
         *field = value;
         if (field == &c->comm_budget_s && c->watch) ((WatchEntry*)c->watch)->budget_s = value;

@@ -300,6 +300,7 @@ struct gprn_ctx {
     int last_batch_chunk = 0;        // read-only option "batch_chunk": evaluations per chunk in the last gprn_elbocalc_batch call
     // ---- sweep order (gprn_set_sweep_order, order.hip)
     int sweep_order = 0;             // GPRN_ORDER_REFERENCE (Jacobi, quirk Q6) or GPRN_ORDER_SEQUENTIAL
+    int order_mask = 0;              // gprn_set_option "order_mask": the sequential order and a data mask together (default: each refuses the other)
     double* d_mu_old = nullptr;      // sequential order on the launch path: the means a phase started from (order_snapshot)
     size_t mu_old_cap = 0;
     int n_states = 1;                // copies of the state behind d_mu (a batch's worker context: its evaluations)
@@ -639,7 +640,7 @@ int order_snapshot(gprn_ctx* c, const Phase& ph);
 int order_refresh(gprn_ctx* c, const Phase& ph, bool weights);
 int order_small(gprn_ctx* c, const Phase& ph, bool weights, const double* mu_in, const double* var_in,
                 double* mu_out, double* var_out, const int* done);
-int order_small_batch(gprn_ctx* c, const void* lanes, bool weights, int n_eval);
+int order_small_batch(gprn_ctx* c, const void* lanes, bool weights, int n_eval, bool masked);
 
 // meanfield.py:640-643: np.std / np.mean of the last three values, operation by operation (one rounding each)
 static inline bool elbo_stop_rule(double e0, double e1, double e2)

@@ -269,7 +269,7 @@ extern "C" int gprn_set_mask(gprn_ctx* c, const uint8_t* mask)
         c->err = "set_mask: a data mask is not supported on a context with a communicator";
         return GPRN_E_UNSUPPORTED;
     }
-    if (mask && c->sweep_order != GPRN_ORDER_REFERENCE) {
+    if (mask && c->sweep_order != GPRN_ORDER_REFERENCE && !c->order_mask) {
         c->err = "set_mask: a data mask is not supported under the sequential sweep order (gprn_set_sweep_order)";
         return GPRN_E_UNSUPPORTED;
     }

@@ -474,6 +474,7 @@ static void mid_follow(const gprn_ctx* c, gprn_ctx* w)
     w->acc_opt = c->acc_opt;
     w->fenced_finalize = c->fenced_finalize;
     w->sweep_order = c->sweep_order;
+    w->order_mask = c->order_mask;                   // (with the borrowed mask, MidMaskLoan: order.hip's masked refresh)
     w->pad_kb_opt = c->pad_kb_opt; w->pad_small_kb_opt = c->pad_small_kb_opt;
     w->prof.on = false;
 }

@@ -18,6 +18,16 @@
 //                 j = 1 .. q - 1, the weight refresh as p workgroups (the outputs are independent chains) each walking
 //                 j = 1 .. q - 1; X is read from the workspace the half-sweep left, new means from the copy of the state
 //                 being written, old ones from the copy being read.  k_order_small_b: grid y = evaluation.
+//
+// MASKED (gprn_set_mask beside this order: option "order_mask").  What a phase shares between the orders above does not
+// read the mask differently either, and the rows U of zero precision get mu_n = < WT_u, c > from the phase's ct (mask.hip),
+// which the refresh rewrites per slot BEFORE mask_rows runs (phase_core, small_sweep, the one-tile batch loop).  So only
+// the refresh's own arithmetic knows the mask, with k_prep_*<true>'s rules: a masked (i, n) is SELECTED away (its y, yerr
+// and state rows never enter arithmetic), a node sums over its observed outputs, a weight has pred = 0 where its output is
+// masked; where s = 0, z = 0 without a division and the mean's row is not written (the finalize's placeholder stays until
+// mask_rows replaces it).  No refresh reads a row of U of an earlier group: weight (j, i) reads the weights (k, i) only
+// where output i is observed, which is off U for every (k, i); nodes have a U at q = 1 only, where nothing is refreshed.
+// The unmasked instantiations keep their code and registers.
 #include "api_internal.h"
 #include "smalln.h"
 
@@ -25,12 +35,13 @@
 // pred and z = pred / s of the slots of ONE group (all of the same node index): k_prep_nodes' / k_prep_weights' sums in
 // their order, with the means of the groups before this one from `mu` (already refreshed) and of those behind it from
 // `mu_old` (the state the sweep started from)
-template <bool WEIGHTS>
+template <bool WEIGHTS, bool MASKED>
 __global__ __launch_bounds__(256)
 void k_order_rhs(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
                  const double* __restrict__ mu, const double* __restrict__ mu_old,
                  const double* __restrict__ yres, const double* __restrict__ variance,
-                 const double* __restrict__ s, double* __restrict__ pred, double* __restrict__ z, EvalMap ev)
+                 const double* __restrict__ s, double* __restrict__ pred, double* __restrict__ z, EvalMap ev,
+                 const uint8_t* __restrict__ mask)
 {
     const int slot = blockIdx.y, gp = slot_gp[slot];
     const int n = blockIdx.x * 256 + threadIdx.x;
@@ -41,6 +52,11 @@ void k_order_rhs(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
     if (n < N) {
         if (WEIGHTS) {
             const int kk = gp - q, j = kk / p, i = kk % p;
+            if (MASKED && !mask[(size_t)i * N + n]) {            // (a row of U: pred = z = 0, as k_prep_weights<true> left them)
+                const size_t o = (size_t)slot * ld + n;
+                pred[o] = 0.0; z[o] = 0.0;
+                return;
+            }
             const double vi = variance[(size_t)i * N + n];
             const double mfj = mu[(size_t)j * N + n];
             const size_t wrow = (size_t)(1 + i) * q;
@@ -51,6 +67,7 @@ void k_order_rhs(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
         } else {
             const int j = gp;
             for (int i = 0; i < p; ++i) {
+                if (MASKED && !mask[(size_t)i * N + n]) continue;
                 const double vi = variance[(size_t)i * N + n];
                 const size_t wrow = (size_t)(1 + i) * q;
                 const double mwj = mu[(wrow + j) * N + n];
@@ -63,7 +80,8 @@ void k_order_rhs(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
     }
     const size_t o = (size_t)slot * ld + n;
     pred[o] = pv;
-    z[o] = pv / s[o];                    // (s = sqrt(d) as k_prep_* left it; 1 on the padding)
+    const double sv = s[o];              // (s = sqrt(d) as k_prep_* left it; 1 on the padding)
+    z[o] = (MASKED && sv == 0.0) ? 0.0 : pv / sv;
 }
 
 // X^T u over one tile row (128 rows) of X: k_colops_partial's second sum alone, into its half of the partial sums
@@ -98,6 +116,8 @@ void k_order_xtu_partial(double* const* __restrict__ ptrs, int ld, int T,
 }
 
 // the tile rows added up (k_colops_reduce's order) and the mean's row of the state: mu = (z - X^T X z) / s
+// (MASKED: not where s = 0 -- mask.hip's rows, from the ct written here)
+template <bool MASKED>
 __global__ __launch_bounds__(256)
 void k_order_mean(const int* __restrict__ slot_gp, int N, int ld, int T, int p, int q,
                   const double* __restrict__ part, const double* __restrict__ s, const double* __restrict__ z,
@@ -113,7 +133,10 @@ void k_order_mean(const int* __restrict__ slot_gp, int N, int ld, int T, int p, 
     for (int ch = n >> 7; ch < T; ++ch) b += part[(((size_t)slot * T + ch) * 2) * ld + ld + n];
     const size_t o = (size_t)slot * ld + n;
     ct[o] = b;
-    if (n < N) mu[row * N + n] = (z[o] - b) / s[o];
+    if (n < N) {
+        const double sv = s[o];
+        if (!(MASKED && sv == 0.0)) mu[row * N + n] = (z[o] - b) / sv;
+    }
 }
 
 static bool order_on(const gprn_ctx* c) { return c->sweep_order == GPRN_ORDER_SEQUENTIAL && c->q > 1; }
@@ -151,23 +174,24 @@ int order_refresh(gprn_ctx* c, const Phase& ph, bool weights)
         const size_t o = (size_t)g.slot0 * g.ld, po = (size_t)g.slot0 * g.T * 2 * g.ld;
         prof_begin(c, GPRN_T_VEC);
         const dim3 grid((g.ld + 255) / 256, gs);
-        if (weights)
-            hipLaunchKernelGGL(k_order_rhs<true>, grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, c->p, c->q,
-                               (const double*)c->d_mu, (const double*)c->d_mu_old, (const double*)c->d_yres,
-                               (const double*)c->d_variance, (const double*)(c->d_s + o), c->d_pred + o, c->d_z + o, g.ev);
-        else
-            hipLaunchKernelGGL(k_order_rhs<false>, grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, c->p, c->q,
-                               (const double*)c->d_mu, (const double*)c->d_mu_old, (const double*)c->d_yres,
-                               (const double*)c->d_variance, (const double*)(c->d_s + o), c->d_pred + o, c->d_z + o, g.ev);
+#define GO_RHS(W, M) hipLaunchKernelGGL((k_order_rhs<W, M>), grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, c->p, c->q, \
+                               (const double*)c->d_mu, (const double*)c->d_mu_old, (const double*)c->d_yres,                   \
+                               (const double*)c->d_variance, (const double*)(c->d_s + o), c->d_pred + o, c->d_z + o, g.ev,     \
+                               (const uint8_t*)c->d_mask)
+        if (weights) { if (c->d_mask) GO_RHS(true, true); else GO_RHS(true, false); }
+        else         { if (c->d_mask) GO_RHS(false, true); else GO_RHS(false, false); }
+#undef GO_RHS
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         TRY(vec_lower_matvec(c, g, BUF_X, c->d_z + o, g.ld, 0, c->d_u + o));
         prof_begin(c, GPRN_T_VEC);
         hipLaunchKernelGGL(k_order_xtu_partial, dim3(g.ld / 64, g.T, gs), dim3(256), 0, c->stream,
                            (double* const*)g.ptrs, g.ld, g.T, (const double*)(c->d_u + o), c->d_part + po);
-        hipLaunchKernelGGL(k_order_mean, grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, g.T, c->p, c->q,
-                           (const double*)(c->d_part + po), (const double*)(c->d_s + o), (const double*)(c->d_z + o),
-                           c->d_ct + o, c->d_mu, g.ev);
+#define GO_MEAN(M) hipLaunchKernelGGL(k_order_mean<M>, grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, g.T, c->p, c->q,   \
+                           (const double*)(c->d_part + po), (const double*)(c->d_s + o), (const double*)(c->d_z + o),        \
+                           c->d_ct + o, c->d_mu, g.ev)
+        if (c->d_mask) GO_MEAN(true); else GO_MEAN(false);
+#undef GO_MEAN
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
     }
@@ -177,7 +201,7 @@ int order_refresh(gprn_ctx* c, const Phase& ph, bool weights)
 // ------------------------------------------------------------------ one tile
 // The refresh of the groups 1 .. q - 1 behind a half-sweep launch of smalln.hip, by the workgroup of output blockIdx.x
 // (weights) or the one workgroup of the node phase.  Sums in the order of small_phase_body.
-template <bool WEIGHTS, int T>
+template <bool WEIGHTS, int T, bool MASKED>
 __device__ __forceinline__ void order_small_body(const SmallPhaseArgs& a)
 {
     __shared__ double sZ[SMALL_MAXLD], sU[SMALL_MAXLD];
@@ -193,7 +217,9 @@ __device__ __forceinline__ void order_small_body(const SmallPhaseArgs& a)
         // starting ones (the copy being read) of those behind it
         for (int n = tid; n < ld; n += 256) {
             double pv = 0.0;
-            if (n < N) {
+            // (MASKED: a weight's row of U keeps pred = 0 and nothing of it is read; a node sums over its observed outputs)
+            const bool in_U = MASKED && WEIGHTS && n < N && !a.mask[(size_t)((gp - q) % p) * N + n];
+            if (n < N && !in_U) {
                 if (WEIGHTS) {
                     const int i = (gp - q) % p;
                     const double vi = a.variance[(size_t)i * N + n];
@@ -205,6 +231,7 @@ __device__ __forceinline__ void order_small_body(const SmallPhaseArgs& a)
                     pv = (a.yres[(size_t)i * N + n] - other) * mfj / vi;
                 } else {
                     for (int i = 0; i < p; ++i) {
+                        if (MASKED && !a.mask[(size_t)i * N + n]) continue;
                         const double vi = a.variance[(size_t)i * N + n];
                         const size_t wrow = (size_t)(1 + i) * q;
                         const double mwj = a.mu_in[(wrow + j) * N + n];
@@ -215,7 +242,8 @@ __device__ __forceinline__ void order_small_body(const SmallPhaseArgs& a)
                     }
                 }
             }
-            const double zv = pv / a.s[vo + n];
+            const double sv = a.s[vo + n];
+            const double zv = (MASKED && sv == 0.0) ? 0.0 : pv / sv;
             sZ[n] = zv;
             a.pred[vo + n] = pv; a.z[vo + n] = zv;
         }
@@ -252,18 +280,21 @@ __device__ __forceinline__ void order_small_body(const SmallPhaseArgs& a)
         else { const int kk = gp - q; row = (size_t)(1 + kk % p) * q + kk / p; }
         if (tid < ld) {
             a.ct[vo + tid] = my_ct;
-            if (tid < N) a.mu_out[row * N + tid] = (sZ[tid] - my_ct) / a.s[vo + tid];
+            if (tid < N) {
+                const double sv = a.s[vo + tid];
+                if (!(MASKED && sv == 0.0)) a.mu_out[row * N + tid] = (sZ[tid] - my_ct) / sv;   // (s = 0: mask.hip's row)
+            }
         }
         sm_publish();                                // (the next group of this workgroup reads the row)
     }
 }
 
-template <bool WEIGHTS, int T>
+template <bool WEIGHTS, int T, bool MASKED>
 __global__ __launch_bounds__(256)
-void k_order_small(SmallPhaseArgs a) { order_small_body<WEIGHTS, T>(a); }
-template <bool WEIGHTS>
+void k_order_small(SmallPhaseArgs a) { order_small_body<WEIGHTS, T, MASKED>(a); }
+template <bool WEIGHTS, bool MASKED>
 __global__ __launch_bounds__(256)
-void k_order_small_b(const SmallPhaseArgs* __restrict__ lanes) { order_small_body<WEIGHTS, 1>(lanes[blockIdx.y]); }
+void k_order_small_b(const SmallPhaseArgs* __restrict__ lanes) { order_small_body<WEIGHTS, 1, MASKED>(lanes[blockIdx.y]); }
 
 int order_small(gprn_ctx* c, const Phase& ph, bool weights, const double* mu_in, const double* var_in,
                 double* mu_out, double* var_out, const int* done)
@@ -275,25 +306,33 @@ int order_small(gprn_ctx* c, const Phase& ph, bool weights, const double* mu_in,
     SmallPhaseArgs a{(double* const*)ph.ptrs, ph.slot_gp, ph.N, ph.ld, c->p, c->q, c->d_yres, c->d_variance,
                      mu_in, var_in, mu_out, var_out, done,
                      c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, c->d_u + o, c->d_cs + o, c->d_ct + o,
-                     nullptr, nullptr, ph.info, nullptr, nullptr};
+                     nullptr, nullptr, ph.info, nullptr, c->d_mask};
     const dim3 grid(weights ? c->p : 1);
-#define GO(W, TT) hipLaunchKernelGGL((k_order_small<W, TT>), grid, dim3(256), 0, c->stream, a)
-    if (ph.T == 1) { if (weights) GO(true, 1); else GO(false, 1); }
-    else { if (weights) GO(true, 2); else GO(false, 2); }
+#define GO(W, TT, M) hipLaunchKernelGGL((k_order_small<W, TT, M>), grid, dim3(256), 0, c->stream, a)
+    if (c->d_mask) {
+        if (ph.T == 1) { if (weights) GO(true, 1, true); else GO(false, 1, true); }
+        else { if (weights) GO(true, 2, true); else GO(false, 2, true); }
+    } else {
+        if (ph.T == 1) { if (weights) GO(true, 1, false); else GO(false, 1, false); }
+        else { if (weights) GO(true, 2, false); else GO(false, 2, false); }
+    }
 #undef GO
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
 }
 
-// ... of n_eval evaluations side by side: `lanes` is the half-sweep's own argument block per evaluation (smalln.hip)
-int order_small_batch(gprn_ctx* c, const void* lanes, bool weights, int n_eval)
+// ... of n_eval evaluations side by side: `lanes` is the half-sweep's own argument block per evaluation (smalln.hip);
+// masked: the batch runs under a data mask (its argument blocks carry it)
+int order_small_batch(gprn_ctx* c, const void* lanes, bool weights, int n_eval, bool masked)
 {
     if (!order_on(c) || !n_eval) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
     const dim3 grid(weights ? c->p : 1, n_eval);
-    if (weights) hipLaunchKernelGGL(k_order_small_b<true>, grid, dim3(256), 0, c->stream, (const SmallPhaseArgs*)lanes);
-    else hipLaunchKernelGGL(k_order_small_b<false>, grid, dim3(256), 0, c->stream, (const SmallPhaseArgs*)lanes);
+#define GO(W, M) hipLaunchKernelGGL((k_order_small_b<W, M>), grid, dim3(256), 0, c->stream, (const SmallPhaseArgs*)lanes)
+    if (masked) { if (weights) GO(true, true); else GO(false, true); }
+    else { if (weights) GO(true, false); else GO(false, false); }
+#undef GO
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
@@ -310,7 +349,7 @@ extern "C" int gprn_set_sweep_order(gprn_ctx* c, int order)
             c->err = "set_sweep_order: the sequential order is not supported on a context with a communicator";
             return GPRN_E_UNSUPPORTED;
         }
-        if (c->d_mask) {
+        if (c->d_mask && !c->order_mask) {
             c->err = "set_sweep_order: the sequential order is not supported under a data mask (gprn_set_mask)";
             return GPRN_E_UNSUPPORTED;
         }

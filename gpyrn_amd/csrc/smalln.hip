@@ -841,14 +841,14 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
             else
             hipLaunchKernelGGL((k_small_phase_b<false>), dim3(q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 0) * cap));
             prof_end(c);
-            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 0) * cap, false, B));   // (sequential order only)
+            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 0) * cap, false, B, masked));   // (sequential order only)
             if (masked) TRY(rows_u(par, 0));
             prof_begin(c, GPRN_T_DIAG);
             if (masked) hipLaunchKernelGGL((k_small_phase_bm<true>), dim3(G - q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 1) * cap));
             else
             hipLaunchKernelGGL((k_small_phase_b<true>), dim3(G - q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 1) * cap));
             prof_end(c);
-            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B));
+            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B, masked));
             if (masked) TRY(rows_u(par, 1));
             prof_begin(c, GPRN_T_VEC);
             if (masked && (io.flags & GPRN_BATCH_FORCED))

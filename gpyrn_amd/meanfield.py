@@ -68,7 +68,14 @@ class inference:
             the NEW means of the nodes before it, then the weight means in turn over the node index: a proper coordinate
             ascent.  With q = 1 the two are the same computation.  Everything
             that sweeps follows it (``ELBOcalc``, ``nELBO``, ``optimize``, ``mcmc``, ``nELBO_batch``, ``grad_ELBO``, ...)
-            except ``ELBOaux`` and ``_updateSigMu``, which restate reference functions.  Not with ``mask`` or ``comm``.
+            except ``ELBOaux`` and ``_updateSigMu``, which restate reference functions.  Not with ``comm``; with ``mask``
+            only when ``sequential_under_mask`` is set.
+        sequential_under_mask: bool (default False), keyword only
+            Whether ``sweep_order='sequential'`` is accepted on an object with a data mask (option ``"order_mask"`` of the
+            library).  Off, the two refuse each other as they always have; on, every sweep under the mask runs in the
+            sequential order -- what series on different time grids (``from_series``) with q >= 3 nodes need, where the
+            reference's order diverges.  An attribute that may be set later (before the order is): it goes to the device
+            with every set-up.
         batch_under_mask: bool (default False), keyword only
             Whether the side-by-side forms (``nELBO_batch``, ``mcmc(batch=True)``, ``nELBO_and_grad_batch`` and the states
             behind ``predict_batch`` / ``posterior_predictive``) also run under a data mask.  Off, a masked object
@@ -88,7 +95,7 @@ class inference:
     _SWEEP_ORDERS = {'reference': _hip.ORDER_REFERENCE, 'sequential': _hip.ORDER_SEQUENTIAL}
 
     def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference',
-                 batch_under_mask=False, exact_derivatives=False):
+                 batch_under_mask=False, exact_derivatives=False, sequential_under_mask=False):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -113,6 +120,7 @@ class inference:
         self.yerr2 = self.yerr**2
         self.batch_under_mask = bool(batch_under_mask)
         self.exact_derivatives = bool(exact_derivatives)
+        self.sequential_under_mask = bool(sequential_under_mask)
 
         self._components_set = False
         self._frozen_mask = np.array([])
@@ -152,7 +160,7 @@ class inference:
         if not isinstance(order, str) or order not in self._SWEEP_ORDERS:
             raise ValueError(f"sweep_order must be 'reference' or 'sequential', got {order!r}")
         if order != 'reference':
-            if self.mask is not None:
+            if self.mask is not None and not self.sequential_under_mask:
                 raise NotImplementedError('sweep_order: the sequential order is not supported under a data mask')
             if self._comm is not None:
                 raise NotImplementedError('sweep_order: the sequential order is not supported on a sharded inference object')
@@ -167,7 +175,18 @@ class inference:
     def sweep_order(self, order):
         self._sweep_order = self._check_sweep_order(order)
         if self._ctx is not None:
+            # (the device lets "order_mask" go only once the mask and the sequential order are no longer both in force)
+            if self._sweep_order != 'reference':
+                self._send_order_mask(self._ctx)
             self._ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
+            if self._sweep_order == 'reference':
+                self._send_order_mask(self._ctx)
+
+    def _send_order_mask(self, ctx):
+        """Option "order_mask" from ``sequential_under_mask``, the object's order validated against it first (the attribute
+        may have changed since the order was set)."""
+        self._check_sweep_order(self._sweep_order)
+        ctx.option('order_mask', 1 if self.sequential_under_mask else 0)
 
     @classmethod
     def from_series(cls, q, series, **kwargs):
@@ -405,6 +424,7 @@ class inference:
                 ctx.comm_init(comm.world, comm.rank, comm.unique_id())
                 comm.done()
             ctx.set_data(np.asarray(self.time, dtype=float), self.y, self.yerr, self.q)
+            self._send_order_mask(ctx)                            # (before the order and the mask: each asks for it)
             if self._sweep_order != 'reference':
                 ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
             if self.mask is not None and not self.mask.all():     # (an all-True mask is no mask: the same kernels run)
@@ -534,6 +554,7 @@ class inference:
         """The setup block of ELBOcalc (meanfield.py:618-624) on the GPU."""
         ctx = self._backend()
         ctx.option('grad_exact', 1 if self.exact_derivatives else 0)   # (every set-up: the attribute may have changed)
+        self._send_order_mask(ctx)
         specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
         key = tuple(self._spec_key(s) for s in specs)
         if key != self._prior_key:             # unchanged hyper-parameters keep their factors
@@ -1101,6 +1122,7 @@ class inference:
         ctx = self._backend()
         ctx.option('batch_mask', 1 if self.batch_under_mask else 0)   # (every call: the attribute may have changed)
         ctx.option('grad_exact', 1 if self.exact_derivatives else 0)
+        self._send_order_mask(ctx)
         y_raw = np.concatenate(self.y)
         B = len(sets)
         state = (self._mu, self._var) if start is None else (np.asarray(start[0], dtype=float), np.asarray(start[1], dtype=float))

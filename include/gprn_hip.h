@@ -98,7 +98,8 @@ int gprn_set_data(gprn_ctx* ctx, int N, int p, int q,
  * GPRN_E_ARG: an output with no observed entry, or q >= 2 with a time at which every output is masked (drop that time;
  * predict still reaches it).  Both paths (one-tile kernels and launch schedule) have a masked form;
  * gprn_keep_sigma(1), gprn_grad_matrices, gprn_grad_kernel, gprn_elbocalc_batch (unless option "batch_mask" is 1) and
- * contexts with a communicator return GPRN_E_UNSUPPORTED.  Setting or clearing a mask frees the buffers of
+ * contexts with a communicator return GPRN_E_UNSUPPORTED, and so does a context in the sequential sweep order
+ * (gprn_set_sweep_order) unless option "order_mask" is 1.  Setting or clearing a mask frees the buffers of
  * gprn_elbocalc_batch (their argument blocks carry the mask).  The masked gradient is gprn_grad_elbo / gprn_grad_matrix (the B-form needs no division by s). */
 int gprn_set_mask(gprn_ctx* ctx, const uint8_t* mask);
 
@@ -335,7 +336,12 @@ int gprn_elbocalc(gprn_ctx* ctx, int do_setup, const double* y_resid, const doub
  * GPs of the phase side by side; node 0 and the weights of node 0 are updated by the reference order's own formula; with
  * q = 1 the two orders are the same computation (same launches, same bits).
  * Governs gprn_sweep, gprn_elbocalc and gprn_elbocalc_batch; factors and state are kept.  GPRN_E_ARG for another value;
- * GPRN_E_UNSUPPORTED when the sequential order meets a communicator or a data mask, whichever is set second. */
+ * GPRN_E_UNSUPPORTED when the sequential order meets a communicator or a data mask, whichever is set second.
+ * Option "order_mask" = 1 (default 0) lifts the refusal between the order and a data mask, in either call order: the mean
+ * refresh of the later groups then selects masked entries away as the phase's own head does, leaves the rows of zero
+ * precision to the mask's row kernels and hands them the X^T X z it has rewritten, so they are the sequential order's too.
+ * With it gprn_sweep, gprn_elbocalc, gprn_grad_elbo and (under option "batch_mask") gprn_elbocalc_batch / _batch_grad run
+ * the combination on every path.  The communicator's refusal and gprn_keep_sigma's under a mask stay. */
 enum { GPRN_ORDER_REFERENCE = 0, GPRN_ORDER_SEQUENTIAL = 1 };
 int gprn_set_sweep_order(gprn_ctx* ctx, int order);
 
@@ -440,6 +446,10 @@ int gprn_predict_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, i
  * evaluations per chunk in the last gprn_elbocalc_batch call); "batch_mask" (0, the default: gprn_elbocalc_batch and
  * gprn_elbocalc_batch_grad refuse a context with a data mask; 1: they run under it -- side by side every evaluation starts from
  * one shared state, which moves rule-stopped values within the stop rule's 1e-3 against one evaluation after the other);
+ * "order_mask" (0, the default: gprn_set_mask refuses a context in the sequential sweep order and gprn_set_sweep_order refuses
+ * the sequential order under a data mask; 1: both accept, in either call order, and the sweeps run the sequential order under
+ * the mask; any other value: GPRN_E_ARG; back to 0 while a mask and the sequential order are both in force:
+ * GPRN_E_UNSUPPORTED -- drop one of them first);
  * "grad_exact" (0, the default: gprn_grad_kernel, gprn_grad_elbo and gprn_elbocalc_batch_grad differentiate a kernel that is
  * not a single SE / Periodic / QuasiPeriodic by Richardson-extrapolated differences of its program; 1: by the program's exact
  * parameter derivatives, csrc/dk_eval.h -- the rules and the accuracy at gprn_grad_kernel; any other value: GPRN_E_ARG.  It is
