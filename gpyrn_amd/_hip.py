@@ -17,6 +17,7 @@ GPRN_E_ARG, GPRN_E_HIP, GPRN_E_NODEV, GPRN_E_COMM, GPRN_E_NOMEM, GPRN_E_UNSUPPOR
 GPRN_BATCH_FORCED = 1          # gprn_elbocalc_batch_grad: no stop rule, max_iter committed sweeps per evaluation
 COV_JOINT = 1
 ORDER_REFERENCE, ORDER_SEQUENTIAL = 0, 1
+ELBO_REFERENCE, ELBO_BOUND = 0, 1    # option "elbo_form": the reference's number (quirks Q1-Q3, Q5) or the model's bound
 M_K, M_KLINV, M_SIGMA, M_BX, M_BL = 0, 1, 2, 3, 4
 T_NAMES = ('fill', 'build_B', 'diag', 'panel', 'update', 'lauum', 'vec', 'update_ahead')
 TILE = 128

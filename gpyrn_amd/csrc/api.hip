@@ -172,6 +172,8 @@ static void watch_unregister(gprn_ctx* c)
 //   "grad_exact"     1: gprn_grad_kernel, gprn_grad_elbo and gprn_elbocalc_batch_grad differentiate every kernel program exactly
 //                    (dk_eval.h) where they took Richardson-extrapolated differences; 0 (default): today's bits.  Read when a
 //                    gradient is asked for: nothing on the device changes, a committed sweep stays good for gprn_grad_elbo
+//   "elbo_form"      GPRN_ELBO_REFERENCE (default) / GPRN_ELBO_BOUND: the reported ELBO with or without quirks Q1-Q3 and Q5
+//                    (include/gprn_hip.h).  A change clears the set-up, the committed sweep and the batches' buffers
 //   "comm_budget_s"  seconds an entry point may stay inside its collective section before the watchdog ends the process
 //   "accurate_factor" panel steps of a factorisation by substitution instead of products with explicit inverses (diag_tile.h
 //                    ACC): 0 never, 1 always (the launch path's sweeps too), -2 back to the default = every factorisation of a
@@ -195,6 +197,7 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     else if (!strcmp(name, "batch_mask")) field = &c->batch_mask;
     else if (!strcmp(name, "order_mask")) field = &c->order_mask;
     else if (!strcmp(name, "grad_exact")) field = &c->grad_exact;
+    else if (!strcmp(name, "elbo_form")) field = &c->elbo_form;
     else if (!strcmp(name, "comm_budget_s")) field = &c->comm_budget_s;
     else if (!strcmp(name, "accurate_factor")) field = &c->acc_opt;
     else if (!strcmp(name, "fenced_finalize")) field = &c->fenced_finalize;
@@ -221,6 +224,28 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
             return GPRN_E_UNSUPPORTED;
         }
         if (field == &c->grad_exact && value > 1) return bad(c, "set_option: grad_exact is 0 or 1");
+        if (field == &c->elbo_form) {
+            if (value != GPRN_ELBO_REFERENCE && value != GPRN_ELBO_BOUND) return bad(c, "set_option: elbo_form is GPRN_ELBO_REFERENCE or GPRN_ELBO_BOUND");
+            if (value == GPRN_ELBO_BOUND && (c->comm || c->shm || c->world > 1)) {
+                c->err = "set_option: the bound form of the ELBO is not supported on a context with a communicator";
+                return GPRN_E_UNSUPPORTED;
+            }
+            if (value == GPRN_ELBO_BOUND && c->keep_sigma) {
+                c->err = "set_option: the bound form of the ELBO is not supported with gprn_keep_sigma(1)";
+                return GPRN_E_UNSUPPORTED;
+            }
+            if (value != c->elbo_form) {
+                // the set-up of the other form holds (or lacks) K_j^-1, and the batches' argument blocks carry the form
+                if (c->stream && hipSetDevice(c->device) == hipSuccess) hipStreamSynchronize(c->stream);
+                // (the q1 block of the sweep's scalars stays zero in the bound form, whatever the other form left there)
+                if (c->d_scal_base) hipMemset(c->d_scal_base, 0, 2 * (size_t)(3 * c->G + c->q * c->q) * sizeof(double));
+                small_batch_free(c);
+                mid_batch_free(c);
+                c->factored = false;
+                c->grad_ready = false;
+                c->small_tabs_ready = false; c->small_sweep_ready = false; c->setup1_ready = false;
+            }
+        }
         *field = value;
         if (field == &c->comm_budget_s && c->watch) ((WatchEntry*)c->watch)->budget_s = value;
     }
@@ -802,6 +827,10 @@ extern "C" int gprn_comm_init(gprn_ctx* c, int world, int rank, const char* id12
         c->err = "comm_init: a communicator is not supported under the sequential sweep order (gprn_set_sweep_order)";
         return GPRN_E_UNSUPPORTED;
     }
+    if (c->elbo_form != GPRN_ELBO_REFERENCE && (world > 1 || getenv("GPRN_FORCE_RCCL"))) {
+        c->err = "comm_init: a communicator is not supported under the bound form of the ELBO (option \"elbo_form\")";
+        return GPRN_E_UNSUPPORTED;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     comm_teardown(c);
     c->world = world; c->rank = rank;
@@ -985,6 +1014,7 @@ extern "C" int gprn_keep_sigma(gprn_ctx* c, int on)
     DeviceLock lock_(c);
     if (!c) return GPRN_E_ARG;
     if (on && c->d_mask) { c->err = "keep_sigma: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
+    if (on && c->elbo_form != GPRN_ELBO_REFERENCE) { c->err = "keep_sigma: not supported under the bound form of the ELBO (option \"elbo_form\")"; return GPRN_E_UNSUPPORTED; }
     c->keep_sigma = on != 0;
     return GPRN_OK;
 }

@@ -891,6 +891,7 @@ extern "C" int gprn_grad_matrices(gprn_ctx* c, int gp, double* Kinv_out, double*
     DeviceLock lock_(c);
     if (!c || !c->N || gp < 0 || gp >= c->G || !Kinv_out || !P_out) return bad(c, "grad_matrices: bad argument");
     if (c->d_mask) { c->err = "grad_matrices: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
+    if (c->elbo_form != GPRN_ELBO_REFERENCE) { c->err = "grad_matrices: not supported under the bound form of the ELBO (option \"elbo_form\"); gprn_grad_matrix is"; return GPRN_E_UNSUPPORTED; }
     return grad_impl(c, gp, Kinv_out, P_out, nullptr, nullptr);
 }
 
@@ -906,6 +907,7 @@ extern "C" int gprn_grad_kernel(gprn_ctx* c, int gp, const double* m, double* gr
     DeviceLock lock_(c);
     if (!c || !c->N || gp < 0 || gp >= c->G || !m || !grad_out) return bad(c, "grad_kernel: bad argument");
     if (c->d_mask) { c->err = "grad_kernel: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
+    if (c->elbo_form != GPRN_ELBO_REFERENCE) { c->err = "grad_kernel: not supported under the bound form of the ELBO (option \"elbo_form\"); gprn_grad_elbo is"; return GPRN_E_UNSUPPORTED; }
     const KernelSpec& ks = c->kspec[gp];
     if (!ks.set || ks.uploaded || ks.n_ops < 1) {
         c->err = "grad_kernel: the kernel of this latent GP has no device program (uploaded matrix)";
@@ -927,6 +929,8 @@ extern "C" int gprn_expected_loglike(gprn_ctx* c, double* logl_out)
     DeviceLock lock_(c);
     if (!c || !c->N || !logl_out) return bad(c, "expected_loglike: bad argument");
     if (!c->have_jit || !c->have_muvar) return bad(c, "expected_loglike: set_jitters and set_muvar first");
+    // (in the bound form of the ELBO, option "elbo_form", the term reads y - mean: the bound's own expected log-likelihood)
+    if (c->elbo_form == GPRN_ELBO_BOUND && !c->have_yres) return bad(c, "expected_loglike: the bound form reads y - mean: set_y_resid first");
     HIP_TRY(c, hipSetDevice(c->device));
     // (scal is not read by the launch we keep: a throw-away ELBO assembly over whatever the scalars hold)
     double* part = c->d_elbo_part;

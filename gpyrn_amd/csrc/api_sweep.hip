@@ -30,7 +30,8 @@ static int ensure_small_sweep_tabs(gprn_ctx* c)
 {
     if (c->small_sweep_ready) return GPRN_OK;
     std::vector<double*> ktab(c->q, nullptr);
-    for (int j = 1; j < c->q; ++j) {
+    // (the bound form of the ELBO has no quirk Q1: no K_j^-1 is formed, held or read)
+    for (int j = 1; j < c->q && c->elbo_form == GPRN_ELBO_REFERENCE; ++j) {
         if (!c->Kinv[j]) return bad(c, "small path: K_j^-1 of a node is missing (no set-up yet?)");
         ktab[j] = c->Kinv[j];
     }
@@ -63,7 +64,7 @@ static int factor_priors_small(gprn_ctx* c, bool sync = true)
             rows[s * GPRN_NBUF + BUF_X] = c->KLinv[g];
             rows[s * GPRN_NBUF + BUF_K] = c->K[g];
             rows[s * GPRN_NBUF + BUF_KLINV] = c->KLinv[g];
-            if (g >= 1 && g < c->q) {                  // quirk Q1: node k < j needs K_j^-1
+            if (g >= 1 && g < c->q && c->elbo_form == GPRN_ELBO_REFERENCE) {   // quirk Q1: node k < j needs K_j^-1
                 if (!c->Kinv[g]) { TRY(dev_alloc(c, &c->Kinv[g], nn)); c->small_sweep_ready = false; }
                 kout[s] = c->Kinv[g];
             }
@@ -104,8 +105,8 @@ static int factor_priors_single(gprn_ctx* c)
     const size_t nn = (size_t)c->ld * c->ld;
     std::vector<int> gps(c->loc_nodes);
     gps.insert(gps.end(), c->loc_weights.begin(), c->loc_weights.end());
-    const int nb = (int)gps.size(), n_inv = c->q - 1;
-    for (int j = 1; j < c->q; ++j)
+    const int nb = (int)gps.size(), n_inv = c->elbo_form == GPRN_ELBO_REFERENCE ? c->q - 1 : 0;   // (bound form: no quirk Q1)
+    for (int j = 1; j <= n_inv; ++j)
         if (!c->Kinv[j]) { TRY(dev_alloc(c, &c->Kinv[j], nn)); c->setup1_ready = false; }
     if (!c->setup1_ready) {
         std::vector<double*> rows((size_t)c->nslot * GPRN_NBUF, nullptr);
@@ -162,7 +163,7 @@ static int factor_priors_impl(gprn_ctx* c)
 
     // which nodes need an explicit K_j^-1 here: j >= 1 with a local node k < j
     std::vector<char> need_inv(c->q, 0);
-    if (c->q > 1 && !c->loc_nodes.empty())
+    if (c->q > 1 && !c->loc_nodes.empty() && c->elbo_form == GPRN_ELBO_REFERENCE)
         for (int j = c->loc_nodes.front() + 1; j < c->q; ++j) need_inv[j] = 1;
 
     struct Job { int g; bool owned; };
@@ -318,9 +319,10 @@ static int mu_k_mu(gprn_ctx* c, bool weights, double* out, hipStream_t stream = 
 {
     const Phase ph = sweep_phase(c, weights);
     if (!ph.nslots) return GPRN_OK;
-    // a = L_K^-1 m_g with m_g = state row g (nodes: mu_f[g]; weights: the raw-reshape row, quirk Q2)
+    // a = L_K^-1 m_g with m_g = state row g (nodes: mu_f[g]; weights: the raw-reshape row, quirk Q2) -- in the bound form the
+    // latent GP's own mean (own_state_row)
     double* a = c->d_u + (size_t)ph.slot0 * ph.ld;
-    TRY(vec_lower_matvec(c, ph, BUF_KLINV, c->d_mu, c->N, 1, a, stream));
+    TRY(vec_lower_matvec(c, ph, BUF_KLINV, c->d_mu, c->N, c->elbo_form == GPRN_ELBO_BOUND ? 2 : 1, a, stream));
     return vec_dot_self(c, ph, a, out, stream);
 }
 
@@ -353,7 +355,9 @@ static int run_phase(gprn_ctx* c, bool weights, double* scal, std::function<int(
                 TRY(vec_sigma(c, c->wsB[ph.slot0 + s], c->d_s + o + (size_t)s * c->ld, c->Sig[gps[s]]));
             }
         }
-        if (!weights && c->q > 1) {
+        const bool bound = c->elbo_form == GPRN_ELBO_BOUND;
+        // (the bound form has no quirk Q1: what is left for the bulk stream is the node term, where overlap bit 4 puts it there)
+        if (!weights && c->q > 1 && (!bound || ((overlap & 4) && !c->loc_weights.empty()))) {
             // quirk Q1: <K_j^-1, Sigma_k> for k < j needs the explicit B_k^-1 = X^T X of every node
             // but the last.  Nothing in the weight phase reads it, so it runs beside that phase on
             // the second stream and is joined before the ELBO assembly.  It is handed to the weight
@@ -367,12 +371,12 @@ static int run_phase(gprn_ctx* c, bool weights, double* scal, std::function<int(
             const bool early_term = (overlap & 4) && !c->loc_weights.empty();
             nodes->term_done = early_term;
             nodes->q1 = true;
-            nodes->work = [c, scal, early_term, inv, node_gps, node_B]() -> int {
+            nodes->work = [c, scal, early_term, inv, node_gps, node_B, bound]() -> int {
                 HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_nodes, 0));
                 // mu_f^T K_f^-1 mu_f needs the node phase's result only: HBM-bound work beside the MFMA-bound weight phase
                 if (early_term) TRY(mu_k_mu(c, false, scal + 2 * (size_t)c->G, c->stream2));
-                if (inv.nslots && !c->keep_sigma) TRY(lauum_lower(c, inv, c->stream2));
-                for (size_t s = 0; s < node_gps.size(); ++s) {
+                if (inv.nslots && !c->keep_sigma && !bound) TRY(lauum_lower(c, inv, c->stream2));
+                for (size_t s = 0; s < node_gps.size() && !bound; ++s) {
                     const int k = node_gps[s];
                     for (int j = k + 1; j < c->q; ++j)
                         TRY(vec_q1(c, c->Kinv[j], node_B[s], c->d_s + s * c->ld, c->d_u,

@@ -301,6 +301,7 @@ struct gprn_ctx {
     // ---- sweep order (gprn_set_sweep_order, order.hip)
     int sweep_order = 0;             // GPRN_ORDER_REFERENCE (Jacobi, quirk Q6) or GPRN_ORDER_SEQUENTIAL
     int order_mask = 0;              // gprn_set_option "order_mask": the sequential order and a data mask together (default: each refuses the other)
+    int elbo_form = 0;               // gprn_set_option "elbo_form": GPRN_ELBO_REFERENCE (quirks Q1-Q3, Q5) or GPRN_ELBO_BOUND
     double* d_mu_old = nullptr;      // sequential order on the launch path: the means a phase started from (order_snapshot)
     size_t mu_old_cap = 0;
     int n_states = 1;                // copies of the state behind d_mu (a batch's worker context: its evaluations)
@@ -419,6 +420,14 @@ int launch_tile_rows(gprn_ctx* c, int k, double** d_ptrs, int nbatch, int ld, in
                      hipStream_t stream, Signal sig, Await aw, unsigned* raise_at_start = nullptr, unsigned raise_value = 0);
 // diagonal block kblk of every slot of the phase (factor.hip); acc: the ACC form of diag_tile
 int launch_diag(gprn_ctx* c, const Phase& ph, int kblk, bool acc, hipStream_t stream, Signal sig, Await aw);
+
+// The state row that holds latent GP gp's OWN mean and variance (the bound form of the ELBO, option "elbo_form"): node j is row
+// j; weight (j, i), gp = q + j p + i, is row q + i q + j -- mu[1 + i, j] of the reference's layout -- where the reference's
+// prior term reads row gp itself (quirk Q2)
+static inline __host__ __device__ int own_state_row(int gp, int p, int q)
+{
+    return gp < q ? gp : q + ((gp - q) % p) * q + (gp - q) / p;
+}
 
 #ifdef __HIPCC__
 __device__ __forceinline__ size_t ev_of(const EvalMap& e, int slot) { return e.slot_eval ? (size_t)e.slot_eval[slot] : 0; }
@@ -548,6 +557,8 @@ struct GradBatchIn {
     std::vector<const double*> kparams;    // [n] (host): the evaluation's kernel parameters
     std::vector<double*> out;              // [n] (host): its row of grad_out
     int grad_exact = 0;                    // the caller's option "grad_exact"
+    bool bound = false;                    // the caller's option "elbo_form" is GPRN_ELBO_BOUND: a from the latent GP's own mean, no cross
+    int p = 0;                             // terms (kinv is empty); p: outputs, for the own-mean row
 };
 // w: the context the launches go through (its stream, its task lists, its grad_scratch); budget: bytes the pass's scratch may
 // take -- beyond it (or when the device refuses) the evaluations go in groups; GPRN_E_NOMEM when one evaluation's scratch does

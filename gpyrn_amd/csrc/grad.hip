@@ -127,13 +127,15 @@ void k_lower_tmatvec_reduce(const double* __restrict__ part, int N, int ld, int 
 template <bool BATCH>
 __global__ __launch_bounds__(256)
 void k_grad_residual(double* const* __restrict__ Ks, const double* __restrict__ mu, const double* __restrict__ a, int N, int ld,
-                     double* __restrict__ r, const int* __restrict__ slot_gp = nullptr, EvalMap ev = EvalMap{nullptr, 0, 0, 0, 0})
+                     double* __restrict__ r, const int* __restrict__ slot_gp = nullptr, EvalMap ev = EvalMap{nullptr, 0, 0, 0, 0},
+                     int p = 0, int q = 0)                       // q > 0 (the bound form of the ELBO): the latent GP's own mean
 {
     const int g = blockIdx.y, i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= N) return;
     const double* Kr = Ks[g] + (size_t)i * ld;
     const double* ag = a + (size_t)g * ld;
-    const double* mg = BATCH ? mu + ev_of(ev, g) * ev.state + (size_t)slot_gp[g] * N : mu + (size_t)g * N;
+    const int gp = BATCH ? slot_gp[g] : g;
+    const double* mg = mu + (BATCH ? ev_of(ev, g) * ev.state : 0) + (size_t)(q > 0 ? own_state_row(gp, p, q) : gp) * N;
     double acc = 0.0;
     for (int c = lane; c < N; c += 64) acc += Kr[c] * ag[c];
     acc = grad_wave_sum(acc);
@@ -383,13 +385,17 @@ static int grad_prelude(gprn_ctx* c, CallScratch& scr, int only_gp, GradWork& w)
         double** tab = (weights ? c->tab_weight : c->tab_node) + (size_t)first * GPRN_NBUF;
         return lauum_lower(c, problem_phase(c, tab, nullptr, count, 0, nullptr));
     };
+    // (the bound form of the ELBO, option "elbo_form": G_g = 1/2 (a a^T - S B^-1 S) with a from the latent GP's own mean -- no
+    // quirk Q1, so no cross term, no K_j^-1 and none of the three ld x ld scratch matrices per node j >= 1; no quirk Q2)
+    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;
     if (only_gp < 0) { TRY(lauum(false, 0, q)); TRY(lauum(true, 0, G - q)); }
+    else if (only_gp < q && bound) TRY(lauum(false, only_gp, 1));
     else if (only_gp < q) TRY(lauum(false, 0, only_gp + 1));          // (node j meets Sigma_fk, k < j, too)
     else TRY(lauum(true, only_gp - q, 1));
     // (2) the cross terms: P_j = K_j^-1 (sum_{k<j} Sigma_fk) K_j^-1 -- by linearity one pair of GEMMs per node j >= 1
     // whatever the number of pairs (k, j); C1 = -K_j^-1 S in full, then the lower tiles of P = -C1 K_j^-1 (S is dead by then)
     w.cross.assign(q, nullptr);
-    const int j0 = only_gp < 0 ? 1 : only_gp, nj = only_gp < 0 ? q - 1 : (only_gp >= 1 && only_gp < q ? 1 : 0);
+    const int j0 = only_gp < 0 ? 1 : only_gp, nj = bound ? 0 : (only_gp < 0 ? q - 1 : (only_gp >= 1 && only_gp < q ? 1 : 0));
     if (nj > 0) {
         std::vector<double*> rows((size_t)nj * GPRN_NBUF, nullptr);
         for (int z = 0; z < nj; ++z) {
@@ -444,13 +450,13 @@ static int grad_prelude(gprn_ctx* c, CallScratch& scr, int only_gp, GradWork& w)
     HIP_TRY(c, hipMemsetAsync(resid, 0, (size_t)G * ld * sizeof(double), c->stream));
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 0) {
-            TRY(vec_lower_matvec(c, nodes, BUF_KLINV, c->d_mu, N, 1, w.u));
-            TRY(vec_lower_matvec(c, weights, BUF_KLINV, c->d_mu, N, 1, w.u + (size_t)q * ld));
+            TRY(vec_lower_matvec(c, nodes, BUF_KLINV, c->d_mu, N, bound ? 2 : 1, w.u));
+            TRY(vec_lower_matvec(c, weights, BUF_KLINV, c->d_mu, N, bound ? 2 : 1, w.u + (size_t)q * ld));
         } else {
             prof_begin(c, GPRN_T_VEC);
             hipLaunchKernelGGL(k_grad_residual<false>, dim3((N + 3) / 4, G), dim3(256), 0, c->stream, (double* const*)d_k,
                                (const double*)c->d_mu, (const double*)w.a, N, ld, resid, (const int*)nullptr,
-                               EvalMap{nullptr, 0, 0, 0, 0});
+                               EvalMap{nullptr, 0, 0, 0, 0}, c->p, bound ? q : 0);
             prof_end(c);
             HIP_TRY(c, hipGetLastError());
             TRY(vec_lower_matvec(c, nodes, BUF_KLINV, resid, ld, 0, w.u));
@@ -578,8 +584,9 @@ static void grad_batch_counts(const std::vector<KernelSpec>& kspec, int exact, i
 static size_t grad_batch_bytes(const GradBatchIn& in, int total, int pmax)
 {
     const size_t ld = in.ld, nn = ld * ld, G = in.G, nb = ld / 64, nblk = nb * (nb + 1) / 2;
-    return (G * ld * (3 + (size_t)in.T) + G * pmax * nblk + total + 3 * (size_t)(in.q - 1) * nn) * sizeof(double) +
-           G * (sizeof(GradSlot) + (GPRN_NBUF + 3) * sizeof(double*) + 2 * sizeof(int)) + (size_t)(in.q - 1) * GPRN_NBUF * sizeof(double*) +
+    const size_t nq1 = in.bound ? 0 : (size_t)(in.q - 1);          // (nodes with a cross term: none in the bound form)
+    return (G * ld * (3 + (size_t)in.T) + G * pmax * nblk + total + 3 * nq1 * nn) * sizeof(double) +
+           G * (sizeof(GradSlot) + (GPRN_NBUF + 3) * sizeof(double*) + 2 * sizeof(int)) + nq1 * GPRN_NBUF * sizeof(double*) +
            256 * 11;                                         // (each piece is rounded up to 256 bytes; the task list is per group)
 }
 
@@ -588,7 +595,7 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
                             int pmax)
 {
     const int N = in.N, ld = in.ld, T = in.T, q = in.q, G = in.G;
-    const size_t nn = (size_t)ld * ld, nslots = (size_t)ne * G, nj = (size_t)ne * (q - 1);
+    const size_t nn = (size_t)ld * ld, nslots = (size_t)ne * G, nj = in.bound ? 0 : (size_t)ne * (q - 1);
     const int nb = ld / 64, nblk = nb * (nb + 1) / 2;
     hipStream_t st = w->stream;
     std::vector<double> h((size_t)ne * total);
@@ -653,7 +660,7 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
             hi[sl] = g;
             hi[nslots + sl] = in.state_idx[ev];
             double* cr = nullptr;
-            if (g >= 1 && g < q) {
+            if (g >= 1 && g < q && !in.bound) {
                 const size_t z = (size_t)e * (q - 1) + (g - 1);
                 double** cp = hp.data() + o_cp + z * GPRN_NBUF;
                 cp[0] = cross + (3 * z) * nn; cp[1] = in.kinv[(size_t)ev * (q - 1) + (g - 1)];
@@ -690,11 +697,12 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
     // (3) a = L_K^-T L_K^-1 m and one refinement step, per slot
     HIP_TRY(w, hipMemsetAsync(resid, 0, nslots * ld * sizeof(double), st));
     for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 0) TRY(vec_lower_matvec(w, ph, BUF_KLINV, in.state, N, 1, u));
+        if (pass == 0) TRY(vec_lower_matvec(w, ph, BUF_KLINV, in.state, N, in.bound ? 2 : 1, u));
         else {
             prof_begin(w, GPRN_T_VEC);
             hipLaunchKernelGGL(k_grad_residual<true>, dim3((N + 3) / 4, (unsigned)nslots), dim3(256), 0, st,
-                               (double* const*)(d_ptr + o_k), in.state, (const double*)a, N, ld, resid, (const int*)d_int, ph.ev);
+                               (double* const*)(d_ptr + o_k), in.state, (const double*)a, N, ld, resid, (const int*)d_int, ph.ev,
+                               in.p, in.bound ? q : 0);
             prof_end(w);
             HIP_TRY(w, hipGetLastError());
             TRY(vec_lower_matvec(w, ph, BUF_KLINV, resid, ld, 0, u));

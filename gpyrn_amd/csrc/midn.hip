@@ -57,7 +57,7 @@ struct MidBatch {
     int N = 0, p = 0, q = 0, G = 0, ld = 0;
     DeviceOwner own;                  // every slab, table and pinned block below (the worker's arrays are the worker's)
     double *K = nullptr, *KL = nullptr, *Bw = nullptr, *Xw = nullptr;   // [cap][G][ld * ld]
-    double *Kinv = nullptr;           // [cap][q - 1][ld * ld]: K_j^-1 (lower), j = 1 .. q - 1
+    double *Kinv = nullptr;           // [cap][q - 1][ld * ld]: K_j^-1 (lower), j = 1 .. q - 1 (quirk Q1: not in the bound form of the ELBO)
     double *q1_scratch = nullptr;     // [cap q (q - 1) / 2][ld]
     double *keep_s = nullptr;         // [cap][G][ld]: s of each evaluation's last sweep, there from the first call that asks for gradients
     char* programs = nullptr;         // [cap][G] fill programs
@@ -93,9 +93,10 @@ static size_t mid_bytes_per_eval(const gprn_ctx* c)
 {
     const size_t nn = (size_t)c->ld * c->ld, G = c->G, ld = c->ld;
     const size_t d = (size_t)(c->p + 1) * c->q * c->N;
-    size_t dbl = (4 * G + (size_t)(c->q - 1)) * nn             // K, KL, B, X, K_j^-1
+    const size_t n_q1 = c->elbo_form == GPRN_ELBO_REFERENCE ? (size_t)(c->q - 1) : 0;   // (quirk Q1 only)
+    size_t dbl = (4 * G + n_q1) * nn                            // K, KL, B, X, K_j^-1
                + G * ld * (7 + 2 * (size_t)c->T + 2)           // per-slot vectors, partial column sums, finalising terms
-               + (size_t)c->q * (c->q - 1) / 2 * ld + 2 * d + 2 * (size_t)c->p * c->N + 64;
+               + n_q1 * c->q / 2 * ld + 2 * d + 2 * (size_t)c->p * c->N + 64;
     // (under a data mask: WT and C of every latent GP with a U, mask_upad x ld each, its lane and pointer row)
     const size_t ne = batch_mask_entries(c, false).size() + batch_mask_entries(c, true).size();
     dbl += ne * (2 * (size_t)c->mask_upad * ld + GPRN_NBUF);
@@ -142,7 +143,8 @@ static int mid_make(gprn_ctx* c, MidBatch* m, int cap)
     TRY(m->own.alloc(c, &m->KL, nslot * nn));
     TRY(m->own.alloc(c, &m->Bw, nslot * nn));
     TRY(m->own.alloc(c, &m->Xw, nslot * nn));
-    if (q > 1) {
+    const bool q1 = q > 1 && c->elbo_form == GPRN_ELBO_REFERENCE;   // (a change of the form frees the batch: gprn_set_option)
+    if (q1) {
         TRY(m->own.alloc(c, &m->Kinv, (size_t)cap * (q - 1) * nn));
         TRY(m->own.alloc(c, &m->q1_scratch, (size_t)cap * (q * (q - 1) / 2) * ld));
     }
@@ -181,7 +183,7 @@ static int mid_make(gprn_ctx* c, MidBatch* m, int cap)
             hp.diag[s] = w->d_var + (size_t)b * d + (size_t)srow * N;
         }
     for (int b = 0; b < cap; ++b)
-        for (int j = 1; j < q; ++j) {                          // lower(K_j^-1) = lower(X^T X), X = chol(K_j)^-1
+        for (int j = 1; j < q && q1; ++j) {                    // lower(K_j^-1) = lower(X^T X), X = chol(K_j)^-1
             const size_t s = (size_t)b * (q - 1) + (j - 1);
             buf_row(hp.kinv + s * GPRN_NBUF, m->Kinv + s * nn, m->KL + ((size_t)b * G + j) * nn, nullptr, nullptr);
         }
@@ -286,12 +288,13 @@ static Phase mid_phase(const gprn_ctx* w, const MidBatch* m, bool weights, int n
                  mid_ev(m, weights ? m->di.ev_weight : m->di.ev_node), w->N, w->ld, w->T};
 }
 
-// m^T K^-1 m = |L_K^-1 m|^2 per latent GP of the phase, m the state row as it lies in memory (quirk Q2)
+// m^T K^-1 m = |L_K^-1 m|^2 per latent GP of the phase, m the state row as it lies in memory (quirk Q2) -- in the bound form
+// of the ELBO the latent GP's own mean
 static int mid_prior_term(gprn_ctx* w, MidBatch* m, bool weights, int nA, hipStream_t st)
 {
     const Phase ph = mid_phase(w, m, weights, nA);
     double* a = w->d_u + (size_t)ph.slot0 * ph.ld;
-    TRY(vec_lower_matvec(w, ph, BUF_KLINV, w->d_mu, w->N, 1, a, st));
+    TRY(vec_lower_matvec(w, ph, BUF_KLINV, w->d_mu, w->N, w->elbo_form == GPRN_ELBO_BOUND ? 2 : 1, a, st));
     return vec_dot_self(w, ph, a, w->d_scal_base + 2 * (size_t)m->G, st);
 }
 
@@ -310,7 +313,7 @@ static int mid_sweep(gprn_ctx* w, MidBatch* m, int nA, double* out4)
     side = [w, m, nA, scal]() -> int {
         HIP_TRY(w, hipStreamWaitEvent(w->stream2, w->ev_nodes, 0));
         TRY(mid_prior_term(w, m, false, nA, w->stream2));
-        if (m->q > 1) {
+        if (m->q > 1 && w->elbo_form == GPRN_ELBO_REFERENCE) {
             const Phase nodes = mid_phase(w, m, false, nA);
             Phase inv = nodes;
             inv.nslots = (m->q - 1) * nA;
@@ -345,7 +348,7 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
     const Phase setup{m->dp.setup, m->di.gp_setup, B * G, 0, w->d_info, mid_ev(m, m->di.ev_setup), w->N, w->ld, w->T};
     TRY(factor_invert(w, setup, true));
     TRY(vec_logdet(w, setup, BUF_B, w->d_logdetK));
-    if (q > 1) {
+    if (q > 1 && w->elbo_form == GPRN_ELBO_REFERENCE) {
         Phase kinv = setup;
         kinv.ptrs = m->dp.kinv;
         kinv.nslots = B * (q - 1);
@@ -444,7 +447,7 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
         const size_t nn = (size_t)m->ld * m->ld;
         GradBatchIn in;
         in.N = N; in.ld = m->ld; in.T = w->T; in.q = q; in.G = G; in.t = w->d_time;
-        in.state = w->d_mu; in.state_stride = d; in.grad_exact = c->grad_exact;
+        in.state = w->d_mu; in.state_stride = d; in.grad_exact = c->grad_exact; in.bound = c->elbo_form == GPRN_ELBO_BOUND; in.p = p;
         for (int b = 0; b < B; ++b) {
             if (!grad_batch_enter(io, b, in)) continue;
             for (int g = 0; g < G; ++g) {
@@ -452,7 +455,7 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
                 m->row(&in.rows[in.rows.size() - GPRN_NBUF], (size_t)b * G + g);
                 in.s.push_back(keep_s + ((size_t)b * G + g) * m->ld);
             }
-            for (int j = 1; j < q; ++j) in.kinv.push_back(m->Kinv + ((size_t)b * (q - 1) + (j - 1)) * nn);
+            for (int j = 1; j < q && m->Kinv; ++j) in.kinv.push_back(m->Kinv + ((size_t)b * (q - 1) + (j - 1)) * nn);
             in.state_idx.push_back(b);
         }
         TRY(grad_batch_pass(w, c->kspec, in, grad_batch_left(c, (size_t)m->cap * mid_bytes_per_eval(c))));
@@ -474,6 +477,7 @@ static void mid_follow(const gprn_ctx* c, gprn_ctx* w)
     w->acc_opt = c->acc_opt;
     w->fenced_finalize = c->fenced_finalize;
     w->sweep_order = c->sweep_order;
+    w->elbo_form = c->elbo_form;
     w->order_mask = c->order_mask;                   // (with the borrowed mask, MidMaskLoan: order.hip's masked refresh)
     w->pad_kb_opt = c->pad_kb_opt; w->pad_small_kb_opt = c->pad_small_kb_opt;
     w->prof.on = false;

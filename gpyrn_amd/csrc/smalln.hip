@@ -247,7 +247,8 @@ struct SmallTailArgs {
     const int *gp_node, *gp_weight;
     int n_node, n_weight;
     int N, ld, p, q, G;
-    const double *mu, *var, *yraw, *variance;   // the NEW state of the sweep (the half-sweeps' mu_out / var_out)
+    const double *mu, *var, *yraw, *variance;   // the NEW state of the sweep (the half-sweeps' mu_out / var_out); yraw: the raw
+                                                // data (quirk Q3) -- in the bound form y - mean, the evaluation's own
     const double* s_node;       // s = sqrt(d) of the node slots
     double* const* Kinv;        // [q] device pointers: K_j^-1 (lower), null where not held
     double* scratch;            // [n_node + n_weight][ld]
@@ -297,7 +298,9 @@ __device__ __forceinline__ void small_loglike(const SmallTailArgs& a, double* sh
 }
 
 // FORCED (GPRN_BATCH_FORCED): the stop rule is not applied -- max_iter committed trips, converged = 0
-template <int T, bool MASKED = false, bool FORCED = false>
+// BOUND (option "elbo_form" = GPRN_ELBO_BOUND): the latent GP's own mean in mu^T K^-1 mu (no quirk Q2), no quirk Q1 -- its
+// product, traces and table reads are compiled out --, the residual in a.yraw (the launchers': no Q3), no division by q
+template <int T, bool MASKED = false, bool FORCED = false, bool BOUND = false>
 __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
 {
     __shared__ __attribute__((aligned(16))) double lds[SMALL_MMA_DOUBLES];
@@ -315,7 +318,7 @@ __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
     double* const q1 = a.scal + 3 * (size_t)G;
     // ---- mu^T K^-1 mu = |L_K^-1 m|^2, m = row gp of the state as it lies in memory (quirk Q2 for the weights)
     {
-        small_lower_matvec<T>(row[BUF_KLINV], ld, N, a.mu + (size_t)gp * N, nullptr, tmp);
+        small_lower_matvec<T>(row[BUF_KLINV], ld, N, a.mu + (size_t)(BOUND ? own_state_row(gp, a.p, q) : gp) * N, nullptr, tmp);
         sm_publish();
         double acc = 0.0;
         for (int n = tid; n < N; n += 256) { const double x = tmp[n]; acc += x * x; }
@@ -325,7 +328,7 @@ __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
     }
     // ---- quirk Q1: node k < q - 1 forms lower(B_k^-1) = lower(X^T X) in its B buffer (L is not needed any more) and the
     // traces <K_j^-1, Sigma_k>, j > k (k_q1_rows, k_sum_to)
-    if (is_node && gp < q - 1) {
+    if (!BOUND && is_node && gp < q - 1) {
         double* const Bm = row[BUF_B];
         const double* const Xm = row[BUF_X];
         for (int ta = T - 1; ta >= 0; --ta)
@@ -381,14 +384,14 @@ __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
         for (int g = 0; g < G; ++g) {
             ent += 0.5 * (logdetK[g] - sc_at(g));
             double tr = sc_at(G + g);
-            if (g < q)
+            if (!BOUND && g < q)
                 for (int k = 0; k < g; ++k) tr += sc_at(3 * (size_t)G + g * q + k);   // cumulative sumSigmaF, quirk Q1
             logp += -0.5 * logdetK[g] - 0.5 * (sc_at(2 * (size_t)G + g) + tr);
         }
         const double cst = (double)q * (p + 1) * N;
         ent += 0.5 * cst * (1.0 + log(TWO_PI));
         logp += -0.5 * cst * log(TWO_PI);
-        const double elbo = (logl + logp + ent) / q;
+        const double elbo = BOUND ? logl + logp + ent : (logl + logp + ent) / q;
         a.out4[0] = elbo;
         a.out4[1] = logl;
         a.out4[2] = logp;
@@ -511,6 +514,19 @@ void k_small_tail_bm(const SmallTailArgs* __restrict__ lanes, int sweep, int his
     small_tail_body<T, true, FORCED>(a);
 }
 
+// ... in the bound form of the ELBO (option "elbo_form"): kernels of their own, so that the others keep their code and registers
+template <int T, bool MASKED>
+__global__ __launch_bounds__(256)
+void k_small_tail_bound(SmallTailArgs a) { small_tail_body<T, MASKED, false, true>(a); }
+template <int T, bool MASKED, bool FORCED>
+__global__ __launch_bounds__(256)
+void k_small_tail_bound_b(const SmallTailArgs* __restrict__ lanes, int sweep, int hist_at, int max_iter)
+{
+    SmallTailArgs a = lanes[blockIdx.y];
+    a.sweep = sweep; a.hist_at = hist_at; a.max_iter = max_iter;
+    small_tail_body<T, MASKED, FORCED, true>(a);
+}
+
 template <int T, bool ACC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_small_prior(SmallPriorArgs a) { small_prior_body<T, ACC>(a); }
@@ -557,13 +573,19 @@ int small_tail(gprn_ctx* c, double* out4, double* scal, const double* mu, const 
     const int nn = (int)c->loc_nodes.size(), nw = (int)c->loc_weights.size();
     if (nn + nw == 0) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
+    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;
     SmallTailArgs a{(double* const*)c->tab_node, (double* const*)c->tab_weight, c->d_slotgp_node, c->d_slotgp_weight, nn, nw,
-                    c->N, c->ld, c->p, c->q, c->G, mu, var, c->d_yraw, c->d_variance, c->d_s,
+                    c->N, c->ld, c->p, c->q, c->G, mu, var, bound ? c->d_yres : c->d_yraw, c->d_variance, c->d_s,
                     (double* const*)c->d_kinv_tab, c->d_u, c->d_logdetK, scal, out4, c->d_small_ticket,
                     loop ? loop->ctl : nullptr, loop ? loop->hist : nullptr, loop ? loop->last3 : nullptr,
                     loop ? loop->sweep : 0, loop ? loop->hist_at : 0, loop ? loop->max_iter : 0,
                     c->d_info, 3 * c->nslot, c->d_mask};
-    if (c->d_mask) {
+    if (bound) {
+#define GO_TB(TT, M) hipLaunchKernelGGL((k_small_tail_bound<TT, M>), dim3(nn + nw), dim3(256), 0, c->stream, a)
+        if (c->d_mask) { if (c->T == 1) GO_TB(1, true); else GO_TB(2, true); }
+        else { if (c->T == 1) GO_TB(1, false); else GO_TB(2, false); }
+#undef GO_TB
+    } else if (c->d_mask) {
         if (c->T == 1) hipLaunchKernelGGL(k_small_tail_m<1>, dim3(nn + nw), dim3(256), 0, c->stream, a);
         else hipLaunchKernelGGL(k_small_tail_m<2>, dim3(nn + nw), dim3(256), 0, c->stream, a);
     } else {
@@ -628,6 +650,9 @@ struct SmallBatchMem {
 };
 #define SB_K 8                         // sweeps per batch of launches (one synchronisation each)
 
+// matrices per evaluation: K, chol(K)^-1, B, X per latent GP -- and K_j^-1 per node where quirk Q1 is in force
+static size_t small_nmat(const gprn_ctx* c) { return 4 * (size_t)c->G + (c->elbo_form == GPRN_ELBO_REFERENCE ? c->q : 0); }
+
 void small_batch_free(gprn_ctx* c)
 {
     delete (SmallBatchMem*)c->small_batch;
@@ -638,7 +663,7 @@ static size_t small_bytes_per_eval(const gprn_ctx* c)
 {
     const size_t nn = (size_t)c->ld * c->ld, d = (size_t)(c->p + 1) * c->q * c->N;
     const size_t ne = batch_mask_entries(c, false).size() + batch_mask_entries(c, true).size();   // (WT and C per entry)
-    return ((4 * (size_t)c->G + c->q) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256 +
+    return (small_nmat(c) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256 +
             ne * 2 * GPRN_TILE * c->ld) * sizeof(double) + (size_t)c->G * fill_program_bytes() * 2 + ne * 2 * sizeof(MaskLane);
 }
 
@@ -667,7 +692,8 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     const size_t ne0 = ent[0].size(), ne_all = ne0 + ent[1].size(), wc = (size_t)GPRN_TILE * ld;
     m->mask_ne[0] = (int)ne0; m->mask_ne[1] = (int)ent[1].size();
     const size_t nn = (size_t)ld * ld, d = (size_t)(p + 1) * q * N, pn = (size_t)p * N, nscal = 3 * (size_t)G + (size_t)q * q;
-    const size_t nmat = 4 * (size_t)G + q, nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
+    const size_t nmat = small_nmat(c), nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
+    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;          // (a change of the form frees these buffers: gprn_set_option)
     TRY(m->own.alloc(c, &m->mats, (size_t)cap * nmat * nn));
     TRY(m->own.alloc(c, &m->vecs, (size_t)cap * 7 * G * ld));
     TRY(m->own.alloc(c, &m->state, 4 * (size_t)cap * d));
@@ -719,10 +745,10 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
             buf_row(h_setup + (size_t)g * GPRN_NBUF, Bp(g), KLp(g), Kp(g), KLp(g));   // set-up: BUF_B scratch, BUF_X = chol(K)^-1, BUF_K
             buf_row(g < q ? h_node + (size_t)g * GPRN_NBUF : h_weight + (size_t)(g - q) * GPRN_NBUF,
                     Bp(g), Xp(g), Kp(g), KLp(g));                                     // sweeps: B, X, K, chol(K)^-1
-            h_kinv_out[g] = (g >= 1 && g < q) ? Kinvp(g) : nullptr;
+            h_kinv_out[g] = (g >= 1 && g < q && !bound) ? Kinvp(g) : nullptr;
             h_Kptr[g] = kd[(size_t)b * G + g] = Kp(g);
         }
-        for (int j = 0; j < q; ++j) h_kinv_tab[j] = j >= 1 ? Kinvp(j) : nullptr;
+        for (int j = 0; j < q; ++j) h_kinv_tab[j] = (j >= 1 && !bound) ? Kinvp(j) : nullptr;
         double** const d_setup = db; double** const d_node = db + (size_t)G * GPRN_NBUF; double** const d_weight = db + 2 * (size_t)G * GPRN_NBUF;
         double** const d_kinv_tab = db + 3 * (size_t)G * GPRN_NBUF; double** const d_kinv_out = d_kinv_tab + q;
         double* const vb = m->vecs + (size_t)b * 7 * G * ld;
@@ -755,7 +781,7 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
             }
             ta[(size_t)par * cap + b] = SmallTailArgs{
                 (double* const*)d_node, (double* const*)d_weight, m->gp_ids, m->gp_ids + q, q, G - q, N, ld, p, q, G,
-                mu_out, var_out, c->d_yraw, variance, vec(1, 0), (double* const*)d_kinv_tab, vec(4, 0), m->logdetK + (size_t)b * G,
+                mu_out, var_out, bound ? yres : c->d_yraw, variance, vec(1, 0), (double* const*)d_kinv_tab, vec(4, 0), m->logdetK + (size_t)b * G,
                 scal, m->out4 + (size_t)b * 4, m->ticket + b, ctl, m->hist + (size_t)b * (SB_K + 4),
                 m->hist + (size_t)b * (SB_K + 4) + SB_K, 0, 0, 0, info, 3 * G, c->d_mask};
         }
@@ -851,7 +877,11 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
             TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B, masked));
             if (masked) TRY(rows_u(par, 1));
             prof_begin(c, GPRN_T_VEC);
-            if (masked && (io.flags & GPRN_BATCH_FORCED))
+#define GO_TBB(M, F) hipLaunchKernelGGL((k_small_tail_bound_b<1, M, F>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter)
+            if (c->elbo_form == GPRN_ELBO_BOUND) {
+                if (masked) { if (io.flags & GPRN_BATCH_FORCED) GO_TBB(true, true); else GO_TBB(true, false); }
+                else { if (io.flags & GPRN_BATCH_FORCED) GO_TBB(false, true); else GO_TBB(false, false); }
+            } else if (masked && (io.flags & GPRN_BATCH_FORCED))
                 hipLaunchKernelGGL((k_small_tail_bm<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
             else if (masked)
                 hipLaunchKernelGGL((k_small_tail_bm<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
@@ -859,6 +889,7 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
                 hipLaunchKernelGGL((k_small_tail_b<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
             else
                 hipLaunchKernelGGL((k_small_tail_b<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
+#undef GO_TBB
             prof_end(c);
         }
         HIP_TRY(c, hipGetLastError());
@@ -899,10 +930,10 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
         // ---- the gradient of every evaluation's last committed sweep: grad.hip's batched pass over the B x G one-tile slots
         // (T = 1).  A stopped evaluation's launches were no-ops: X, s and both copies of its state are its last trip's; that
         // trip wrote copy B when odd.
-        const size_t nn = (size_t)c->ld * c->ld, nmat = 4 * (size_t)G + q;
+        const size_t nn = (size_t)c->ld * c->ld, nmat = small_nmat(c);
         GradBatchIn in;
         in.N = c->N; in.ld = c->ld; in.T = 1; in.q = q; in.G = G; in.t = c->d_time;
-        in.state = m->state; in.state_stride = d; in.grad_exact = c->grad_exact;
+        in.state = m->state; in.state_stride = d; in.grad_exact = c->grad_exact; in.bound = c->elbo_form == GPRN_ELBO_BOUND; in.p = c->p;
         for (int b = 0; b < B; ++b) {
             if (!grad_batch_enter(io, b, in)) continue;
             double* const mb = m->mats + (size_t)b * nmat * nn;
@@ -912,7 +943,7 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
                         mb + (size_t)g * nn, mb + ((size_t)G + g) * nn);
                 in.s.push_back(m->vecs + (size_t)b * 7 * G * c->ld + ((size_t)G + g) * c->ld);
             }
-            for (int j = 1; j < q; ++j) in.kinv.push_back(mb + (4 * (size_t)G + j) * nn);
+            for (int j = 1; j < q && c->elbo_form == GPRN_ELBO_REFERENCE; ++j) in.kinv.push_back(mb + (4 * (size_t)G + j) * nn);
             in.state_idx.push_back((iters[b] >= 1 && (iters[b] & 1) ? 2 * cap : 0) + b);
         }
         TRY(grad_batch_pass(c, c->kspec, in, grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c))));

@@ -204,18 +204,21 @@ void k_logdet(double* const* __restrict__ ptrs, int buf, int N, int ld,
 }
 
 // out[slot][i] = sum_{c<=i} M[i][c] v[c]   (i < N), M = ptrs[slot][buf];
-// v = vin + (vin_by_gp ? slot_gp[slot] : slot) * vstride; rows row0 + 4 * blockIdx.x .. of the matrix
+// v = vin + (vin_by_gp ? slot_gp[slot] : slot) * vstride; rows row0 + 4 * blockIdx.x .. of the matrix.
+// vin_by_gp = 2 (the prior term of the bound form, p and q given): the row of the latent GP's own mean, own_state_row
 __global__ __launch_bounds__(256)
 void k_lower_matvec(double* const* __restrict__ ptrs, int buf, int N, int ld,
                     const double* __restrict__ vin, size_t vstride, int vin_by_gp,
-                    const int* __restrict__ slot_gp, double* __restrict__ out, int row0, EvalMap ev)
+                    const int* __restrict__ slot_gp, double* __restrict__ out, int row0, EvalMap ev, int p, int q)
 {
     const int slot = blockIdx.y;
     const int i = row0 + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= ld) return;
     const double* M = ptrs[(size_t)slot * GPRN_NBUF + buf] + (size_t)i * ld;
     // (vin_by_gp: a row of the state -- of this slot's evaluation)
-    const double* v = vin + (vin_by_gp ? ev_of(ev, slot) * ev.state + (size_t)slot_gp[slot] * vstride : (size_t)slot * vstride);
+    const double* v = vin + (vin_by_gp ? ev_of(ev, slot) * ev.state +
+                                         (size_t)(vin_by_gp == 2 ? own_state_row(slot_gp[slot], p, q) : slot_gp[slot]) * vstride
+                                       : (size_t)slot * vstride);
     double acc = 0.0;
     if (i < N) {
         for (int c = 2 * lane; c <= i; c += 128) {
@@ -452,8 +455,9 @@ void k_dot_self(const int* __restrict__ slot_gp, int N, int ld, const double* __
 // Expected log-likelihood (meanfield.py:895-990; y_raw is the RAW data, quirk Q3): partial sums
 // of its three terms over a slice of the time stamps per block (fixed slices -> deterministic).
 // MASKED: the three terms over the observed (i, n) only, log(2 pi v) included.
+// BOUND (option "elbo_form"): `yraw` is y - mean instead (no quirk Q3) -- d_yres, one copy per evaluation of a batch.
 #define ELBO_BLOCKS 32
-template <bool MASKED>
+template <bool MASKED, bool BOUND = false>
 __global__ __launch_bounds__(256)
 void k_loglike_partial(int N, int p, int q, const double* __restrict__ mu, const double* __restrict__ var,
                        const double* __restrict__ yraw, const double* __restrict__ variance,
@@ -465,6 +469,7 @@ void k_loglike_partial(int N, int p, int q, const double* __restrict__ mu, const
     // (several evaluations side by side: grid y = position in the list `evals` of evaluations still running)
     const size_t eb = evals ? (size_t)evals[blockIdx.y] : 0;
     mu += eb * ev.state; var += eb * ev.state; variance += eb * ev.yv;
+    if (BOUND) yraw += eb * ev.yv;
     part += (size_t)blockIdx.y * 3 * ELBO_BLOCKS;
     double t1 = 0.0, t2 = 0.0, t3 = 0.0;
     for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += 256 * ELBO_BLOCKS) {
@@ -496,7 +501,8 @@ void k_loglike_partial(int N, int p, int q, const double* __restrict__ mu, const
 }
 
 // Final assembly  ELBO = (LogL + LogP + Ent) / q  (meanfield.py:709, :1023-1065, :1085-1093).
-// out[0..3] = ELBO, LogL, LogP, Ent.
+// out[0..3] = ELBO, LogL, LogP, Ent.  BOUND: LogL + LogP + Ent with no Q1 traces in LogP (include/gprn_hip.h).
+template <bool BOUND = false>
 __global__ void k_elbo_final(int N, int p, int q, const double* __restrict__ part,
                              const double* __restrict__ logdetK, const double* __restrict__ logdetB,
                              const double* __restrict__ trBinv, const double* __restrict__ muKmu,
@@ -516,14 +522,14 @@ __global__ void k_elbo_final(int N, int p, int q, const double* __restrict__ par
     for (int g = 0; g < G; ++g) {
         ent += 0.5 * (logdetK[g] - logdetB[g]);
         double tr = trBinv[g];
-        if (g < q)
+        if (!BOUND && g < q)
             for (int k = 0; k < g; ++k) tr += q1[g * q + k];   // cumulative sumSigmaF, quirk Q1
         logp += -0.5 * logdetK[g] - 0.5 * (muKmu[g] + tr);
     }
     const double c = (double)q * (p + 1) * N;
     ent += 0.5 * c * (1.0 + log(TWO_PI));
     logp += -0.5 * c * log(TWO_PI);
-    out[0] = (logl + logp + ent) / q;
+    out[0] = BOUND ? logl + logp + ent : (logl + logp + ent) / q;
     out[1] = logl;
     out[2] = logp;
     out[3] = ent;
@@ -584,7 +590,7 @@ int vec_lower_matvec(gprn_ctx* c, const Phase& ph, int buf, const double* vin, s
     prof_begin(c, GPRN_T_VEC, stream);
     hipLaunchKernelGGL(k_lower_matvec, dim3((nrows + 3) / 4, ph.nslots), dim3(256), 0, stream,
                        (double* const*)ph.ptrs, buf, ph.N, ph.ld, vin, vstride, vin_by_gp,
-                       ph.slot_gp, out, row0, ph.ev);
+                       ph.slot_gp, out, row0, ph.ev, c->p, c->q);
     LAUNCH_END(c);
 }
 
@@ -675,17 +681,21 @@ int vec_elbo(gprn_ctx* c, double* out4, const double* scal, double* part, hipStr
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
     const EvalMap one{nullptr, 0, 0, 0, 0};
-    if (c->d_mask)
-        hipLaunchKernelGGL(k_loglike_partial<true>, dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q,
-                           c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, (const int*)nullptr, one,
-                           (const uint8_t*)c->d_mask);
-    else
-        hipLaunchKernelGGL(k_loglike_partial<false>, dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q,
-                           c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, (const int*)nullptr, one,
-                           (const uint8_t*)nullptr);
-    hipLaunchKernelGGL(k_elbo_final, dim3(1), dim3(64), 0, stream, c->N, c->p, c->q, part,
-                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4,
-                       (const int*)nullptr, one);
+    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;
+#define GO_LL(M, B, Y, MASK) hipLaunchKernelGGL((k_loglike_partial<M, B>), dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q, \
+                           c->d_mu, c->d_var, Y, c->d_variance, part, (const int*)nullptr, one, (const uint8_t*)MASK)
+#define GO_EF(B) hipLaunchKernelGGL(k_elbo_final<B>, dim3(1), dim3(64), 0, stream, c->N, c->p, c->q, part, \
+                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, \
+                       (const int*)nullptr, one)
+    if (bound) {
+        if (c->d_mask) GO_LL(true, true, c->d_yres, c->d_mask); else GO_LL(false, true, c->d_yres, nullptr);
+        GO_EF(true);
+    } else {
+        if (c->d_mask) GO_LL(true, false, c->d_yraw, c->d_mask); else GO_LL(false, false, c->d_yraw, nullptr);
+        GO_EF(false);
+    }
+#undef GO_LL
+#undef GO_EF
     LAUNCH_END(c);
 }
 
@@ -697,14 +707,21 @@ int vec_elbo_evals(gprn_ctx* c, const EvalMap& ev, const int* d_evals, int n, do
     if (!n) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
-    if (c->d_mask)                                   // (the mask is the data's: one for all evaluations)
-        hipLaunchKernelGGL(k_loglike_partial<true>, dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
-                           c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)c->d_mask);
-    else
-    hipLaunchKernelGGL(k_loglike_partial<false>, dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
-                       c->d_mu, c->d_var, c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)nullptr);
-    hipLaunchKernelGGL(k_elbo_final, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part,
-                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, ev);
+    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;
+    // (the mask is the data's: one for all evaluations; the bound form's residual is the evaluation's own, stride ev.yv)
+#define GO_LL(M, B, Y, MASK) hipLaunchKernelGGL((k_loglike_partial<M, B>), dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q, \
+                           c->d_mu, c->d_var, Y, c->d_variance, part, d_evals, ev, (const uint8_t*)MASK)
+#define GO_EF(B) hipLaunchKernelGGL(k_elbo_final<B>, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part, \
+                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, ev)
+    if (bound) {
+        if (c->d_mask) GO_LL(true, true, c->d_yres, c->d_mask); else GO_LL(false, true, c->d_yres, nullptr);
+        GO_EF(true);
+    } else {
+        if (c->d_mask) GO_LL(true, false, c->d_yraw, c->d_mask); else GO_LL(false, false, c->d_yraw, nullptr);
+        GO_EF(false);
+    }
+#undef GO_LL
+#undef GO_EF
     LAUNCH_END(c);
 }
 

@@ -90,12 +90,27 @@ class inference:
             or QuasiPeriodic keeps its closed form and its bits; kernels without a device program (user subclasses, a Sum
             that holds a two-argument kernel) are contracted on the host as before.  An attribute that may be set later:
             it goes to the device with every set-up.
+        elbo: 'reference' (default) or 'bound', keyword only
+            WHICH function is reported as the ELBO (option ``"elbo_form"`` of the library; not in the reference).
+            'reference': the reference's number, quirk for quirk -- node j >= 1 paired with the cumulative covariance
+            ``Sigma_f0 + ... + Sigma_fj`` (Q1), weight (j, i) with the raw-reshape row of ``mu_w`` (Q2), the raw ``y`` in the
+            likelihood term (Q3), the sum divided by q (Q5) -- which is not the function the updates ascend.  'bound': the
+            mean-field lower bound on ``log p(y)`` itself -- every latent GP with its OWN mean and covariance, ``y - mean``
+            in the likelihood term, no division -- the objective the coordinate ascent maximises: it rises on every sweep
+            of the sequential order and is stationary in the variational state at convergence, so its fixed-state gradient
+            IS the total gradient, mean-function parameters included.  The updates, ``_initMuVar``, both sweep orders, the
+            stop rule (applied to the new values) and the state are unchanged: the two forms leave the same ``mu`` /
+            ``var`` from the same start.  ``ELBOcalc``, ``ELBO``, ``nELBO``, ``nELBO_batch``, ``optimize``, ``mcmc`` and
+            the gradients follow it; ``ELBOaux`` and the four step methods restate reference functions and stay in the
+            reference's form.  Not with ``comm``.  An attribute that may be set later: it goes to the device with every
+            set-up, and a change drops the cached set-up and the stored state.
     """
 
     _SWEEP_ORDERS = {'reference': _hip.ORDER_REFERENCE, 'sequential': _hip.ORDER_SEQUENTIAL}
+    _ELBO_FORMS = {'reference': _hip.ELBO_REFERENCE, 'bound': _hip.ELBO_BOUND}
 
     def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference',
-                 batch_under_mask=False, exact_derivatives=False, sequential_under_mask=False):
+                 batch_under_mask=False, exact_derivatives=False, sequential_under_mask=False, elbo='reference'):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -133,6 +148,7 @@ class inference:
         self._comm = comm
         self._ctx = None
         self._sweep_order = self._check_sweep_order(sweep_order)
+        self._elbo = self._check_elbo(elbo)
         self._prior_key = None
         self.last_info = 0
 
@@ -181,6 +197,37 @@ class inference:
             self._ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
             if self._sweep_order == 'reference':
                 self._send_order_mask(self._ctx)
+
+    def _check_elbo(self, form):
+        """'reference' or 'bound', validated before anything touches a device."""
+        if not isinstance(form, str) or form not in self._ELBO_FORMS:
+            raise ValueError(f"elbo must be 'reference' or 'bound', got {form!r}")
+        if form != 'reference' and self._comm is not None:
+            raise NotImplementedError('elbo: the bound form is not supported on a sharded inference object')
+        return form
+
+    @property
+    def elbo(self):
+        """ 'reference' or 'bound': which function is reported as the ELBO """
+        return self._elbo
+
+    @elbo.setter
+    def elbo(self, form):
+        form = self._check_elbo(form)
+        if form != self._elbo:
+            # (the device's set-up belongs to the other form, and a stored state was accepted by the other form's stop rule)
+            self._prior_key = None
+            self._mu, self._var = None, None
+        self._elbo = form
+        if self._ctx is not None:
+            self._send_elbo_form(self._ctx)
+
+    def _send_elbo_form(self, ctx, form=None):
+        """Option "elbo_form" from the object's form (or `form`: the reference restatements ask for 'reference').  A change
+        clears the device's set-up: the cached key goes with it."""
+        want = self._ELBO_FORMS[self._check_elbo(self._elbo if form is None else form)]
+        if ctx.option('elbo_form', want) != want:
+            self._prior_key = None
 
     def _send_order_mask(self, ctx):
         """Option "order_mask" from ``sequential_under_mask``, the object's order validated against it first (the attribute
@@ -429,6 +476,8 @@ class inference:
                 ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
             if self.mask is not None and not self.mask.all():     # (an all-True mask is no mask: the same kernels run)
                 ctx.set_mask(self.mask)
+            if self._elbo != 'reference':
+                self._send_elbo_form(ctx)
             if comm is not None and comm.world > 1:
                 ctx.set_owners(sharding.owners(self.p, self.q, comm.world))
             self._ctx = ctx
@@ -555,6 +604,7 @@ class inference:
         ctx = self._backend()
         ctx.option('grad_exact', 1 if self.exact_derivatives else 0)   # (every set-up: the attribute may have changed)
         self._send_order_mask(ctx)
+        self._send_elbo_form(ctx)
         specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
         key = tuple(self._spec_key(s) for s in specs)
         if key != self._prior_key:             # unchanged hyper-parameters keep their factors
@@ -612,6 +662,7 @@ class inference:
         # unchanged ones keep their factors), y - mean and the jitters, the starting state, then the loop -- the first
         # sweep's update thrown away and only its ELBO kept, sweeps to the stop rule or max_iter
         ctx = self._backend()
+        self._send_elbo_form(ctx)
         specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
         key = tuple(self._spec_key(s) for s in specs)
         setup = key != self._prior_key
@@ -647,6 +698,7 @@ class inference:
         """
         self._refuse_masked('ELBOaux')
         ctx = self._backend()
+        self._send_elbo_form(ctx, 'reference')             # (a restatement of the reference's function: its form, always)
         Kf = np.asarray(Kf, dtype=float).reshape(self.q, self.N, self.N)
         Kw = np.asarray(Kw, dtype=float).reshape(self.qp, self.N, self.N)
         for gp, K in enumerate(chain(Kf, Kw)):
@@ -663,11 +715,12 @@ class inference:
             sigmaF = np.array([ctx.get_matrix(_hip.M_SIGMA, j) for j in range(self.q)])
             sigmaW = np.array([ctx.get_matrix(_hip.M_SIGMA, self.q + k)
                                for k in range(self.qp)]).reshape(self.q, self.p, self.N, self.N)
+            new_mu, new_var = ctx.get_muvar()
         finally:
             ctx.keep_sigma(False)
             ctx.set_sweep_order(self._SWEEP_ORDERS[self._sweep_order])
+            self._send_elbo_form(ctx)
         self.last_info = self.last_info or info
-        new_mu, new_var = ctx.get_muvar()
         return np.float64(e[0]), new_mu, new_var, sigmaF, sigmaW
 
     # ------------------------------------------------- the four step methods ELBOaux is made of (meanfield.py:713, 895, 992, 1069)
@@ -757,9 +810,13 @@ class inference:
             for i in range(p):
                 var[1 + i, j] = np.diag(sigma_w[j, i])
         ctx = self._backend()
-        ctx.set_jitters(np.sqrt(np.asarray(jitt2, dtype=float)))
-        ctx.set_muvar(mu, var)
-        return np.float64(ctx.expected_loglike())
+        self._send_elbo_form(ctx, 'reference')             # (the reference's term: raw y, quirk Q3)
+        try:
+            ctx.set_jitters(np.sqrt(np.asarray(jitt2, dtype=float)))
+            ctx.set_muvar(mu, var)
+            return np.float64(ctx.expected_loglike())
+        finally:
+            self._send_elbo_form(ctx)
 
     def nELBO(self, parameters, max_iter=None):
         """ Negative ELBO at `parameters` (warm-started, meanfield.py:1095-1111) """
@@ -786,6 +843,8 @@ class inference:
         and ``res.fun_reference`` is ``nELBO(res.x)``, the reference's objective at the point found.
         ``fused=True`` (with ``jac=True``): the gradient through ``grad_ELBO(fused=True)`` -- one device call per
         evaluation, and the only gradient there is under a data mask (``from_series``).
+        With ``elbo='bound'`` everything follows that form, and ``jac=True`` needs no ``fused=`` (the B-form is the only
+        one) and no finite differences: the gradient handed to scipy is the fixed-state one, exact at a converged state.
         """
         from scipy.optimize import minimize
         self._select_vars(vars)
@@ -796,7 +855,7 @@ class inference:
         # state this call starts at -- the reference's own objective (ELBOcalc under its 1e-3 stop rule, warm-started
         # from the previous evaluation) jumps by 1e-3 relative whenever the trip count changes, which a line search
         # cannot work with
-        fused = bool(kwargs.pop('fused', False))
+        fused = bool(kwargs.pop('fused', self._elbo == 'bound' and kwargs.get('jac') is True))
         if fused and kwargs.get('jac') is not True:
             raise ValueError('optimize(fused=True) chooses the form of the gradient: it needs jac=True')
         if kwargs.get('jac') is True:
@@ -1123,6 +1182,7 @@ class inference:
         ctx.option('batch_mask', 1 if self.batch_under_mask else 0)   # (every call: the attribute may have changed)
         ctx.option('grad_exact', 1 if self.exact_derivatives else 0)
         self._send_order_mask(ctx)
+        self._send_elbo_form(ctx)
         y_raw = np.concatenate(self.y)
         B = len(sets)
         state = (self._mu, self._var) if start is None else (np.asarray(start[0], dtype=float), np.asarray(start[1], dtype=float))
@@ -1366,8 +1426,20 @@ class inference:
         the accuracy of the explicit one (the B-form is the better conditioned: DESIGN.md 9 f-3).  Where the sweep meets
         a non-positive pivot (``last_info != 0``) this form returns ``(-inf, zeros)`` and keeps the stored state.
 
+        ``elbo='bound'``: the gradient of the bound form, at fixed state, for EVERY parameter class -- kernel parameters
+        ``< 1/2 (a a^T - S B^-1 S), dK/dtheta >`` with ``a = K^-1 m`` from the latent GP's own mean (no cross term, nothing
+        divided by q), jitters in closed form with ``y - mean``, mean-function parameter theta of output i
+        ``sum_n ((y - mean)_in - fit_in) / v_in  d mean_i(t_n) / d theta`` over the observed entries
+        (``meanFunction._dm_dpars``).  The B-form is the only one there is (``fused`` left at its default selects it; the
+        explicit form, which needs the reference's pairing, is not offered).  The bound is the function the updates
+        maximise, so at a converged state it is stationary in the variational state and this fixed-state gradient is the
+        total one (envelope theorem): ``total=True`` and ``mean_sweeps`` change nothing, and no differences of forced
+        sweeps are ever run.
+
         Returns ``(ELBO, gradient)``.  Unsharded problems only.
         """
+        bound = self._elbo == 'bound'
+        fused = bool(fused) or bound
         if fused:
             if self._comm is not None:
                 raise NotImplementedError('grad_ELBO(fused=True) is not available on a sharded inference object')
@@ -1388,7 +1460,7 @@ class inference:
                 self.last_info = info
                 return -np.inf, np.zeros(len(self.get_parameters(include_frozen=True)))
             mu, var = ctx.get_muvar()
-            grads = self._grad_from_state(nodes, weights, means, jitters, mu, var, None, fused=ctx)
+            grads = self._grad_from_state(nodes, weights, means, jitters, mu, var, None, fused=ctx, bound=bound)
         else:
             ctx.keep_sigma(True)
             try:
@@ -1403,7 +1475,9 @@ class inference:
         grads = np.array(grads)
         n_k = sum(k.pars.size for k in chain(nodes, weights))
         n_m = sum(0 if m_ is None else int(m_._parsize) for m_ in means)
-        if total and mean_sweeps > 0 and np.any(self._mean(means) != 0.0):
+        if bound:
+            pass                                   # (the fixed-state gradient is the whole of it: see the docstring)
+        elif total and mean_sweeps > 0 and np.any(self._mean(means) != 0.0):
             m0, v0 = (mu_in, var_in) if mean_start is None else mean_start
             grads[:] = self._mean_parameter_differences(0, grads.size, m0, v0, int(mean_sweeps), (mu, var), rel_step=1e-5)
         elif mean_sweeps > 0:
@@ -1440,19 +1514,22 @@ class inference:
             self._setup_device(nodes, weights, means, jitters).set_muvar(*restore)
         return out
 
-    def _grad_from_state(self, nodes, weights, means, jitters, mu, var, matrices, device=None, fused=None):
+    def _grad_from_state(self, nodes, weights, means, jitters, mu, var, matrices, device=None, fused=None, bound=False):
         """The O(N^2) and O(pqN) part of grad_ELBO: `matrices(gp)` returns ``(K^-1, K^-1 S K^-1)`` of latent GP
         `gp` (the GPU's ``gprn_grad_matrices``; a NumPy stand-in in the CPU tests).  `device(gp, m, n)`, when
         given, is tried first: the whole contraction on the GPU (``gprn_grad_kernel``: closed-form or
         central-difference dK/dtheta of the kernel's device program), None for kernels without one.
         `fused`: the device context after a committed sweep -- the B-form instead: every kernel with a device program in
         ONE call (``gprn_grad_elbo``), the others through ``gprn_grad_matrix`` (G itself) and the host contraction
-        below; `matrices` and `device` are not used then."""
+        below; `matrices` and `device` are not used then.
+        `bound`: the entries of the bound form (``elbo='bound'``): every latent GP with its own mean, nothing divided by q,
+        ``y - mean`` in the jitter entries, the mean-function entries from ``meanFunction._dm_dpars``."""
         t = np.asarray(self.time, dtype=float)
         # (N x N on the host: formed only for a kernel that is contracted here -- 134 MB and 16 ms at N = 4096)
         r = None
         q, p, N = self.q, self.p, self.N
         m_scr = mu[1:].reshape(q, p, N)                      # quirk Q2 (meanfield.py:1021)
+        qdiv = 1.0 if bound else float(q)                    # ELBO = (...) / q, meanfield.py:709 -- not in the bound form
         grads = []
         on_dev = None
         if fused is not None:
@@ -1462,9 +1539,9 @@ class inference:
         for gp, kernel in enumerate(chain(nodes, weights)):
             if fused is not None:
                 if counts[gp]:
-                    grads += [float(on_dev.pop(0)) / q for _ in range(counts[gp])]
+                    grads += [float(on_dev.pop(0)) / qdiv for _ in range(counts[gp])]
                     continue
-                G = fused.grad_matrix(gp) / q
+                G = fused.grad_matrix(gp) / qdiv
                 if isinstance(kernel, _TWO_ARGUMENT):
                     dks = covfunc._richardson(kernel, lambda: np.asarray(kernel(t[:, None], t[None, :]), dtype=float))
                 else:
@@ -1476,33 +1553,45 @@ class inference:
                 m = mu[0, gp]
             else:
                 jj, ii = divmod(gp - q, p)
-                m = m_scr[jj, ii]
+                m = mu[1 + ii, jj] if bound else m_scr[jj, ii]
             if device is not None and kernel._device_program() is not None:
                 on_device = device(gp, m, kernel.pars.size)
                 if on_device is not None:
-                    grads += [float(v) / q for v in on_device]
+                    grads += [float(v) / qdiv for v in on_device]
                     continue
             Kinv, P = matrices(gp)
             a = Kinv @ m
-            G = 0.5 * (P - Kinv + np.outer(a, a)) / q        # ELBO = (...) / q, meanfield.py:709
+            G = 0.5 * (P - Kinv + np.outer(a, a)) / qdiv
             if isinstance(kernel, _TWO_ARGUMENT):             # kernel(t_i, t_j): differences only
                 dks = covfunc._richardson(kernel, lambda: np.asarray(kernel(t[:, None], t[None, :]), dtype=float))
             else:
                 r = t[:, None] - t[None, :] if r is None else r
                 dks = kernel._dk_dpars(r)
             grads += [float(np.sum(G * dk)) for dk in dks]
-        grads += [0.0] * sum(0 if m_ is None else int(m_._parsize) for m_ in means)
         # jitters: LogL = -1/2 sum [log(2 pi v) + ((Y - fit)^2 + A) / v],  v = jitter^2 + yerr^2
         variance = np.asarray(jitters, dtype=float)[:, None]**2 + self.yerr2
         fit = np.einsum('iqn,qn->in', mu[1:], mu[0])
+        # (Y: the raw data, quirk Q3 -- y - mean in the bound form, which therefore sees the mean-function parameters)
+        Y = self.y - self._mean(means).reshape(p, N) if bound else self.y
+        if bound:
+            w = (Y - fit) / variance
+            if self.mask is not None:
+                w = np.where(self.mask, w, 0.0)
+            for i, m_ in enumerate(means):
+                if m_ is None:
+                    continue
+                dm = m_._dm_dpars(t)
+                grads += [0.0] * int(m_._parsize) if dm is None else [float(v) for v in np.asarray(dm, dtype=float) @ w[i]]
+        else:
+            grads += [0.0] * sum(0 if m_ is None else int(m_._parsize) for m_ in means)
         A = np.zeros((p, N))
         for i in range(p):
             for j in range(q):
                 A[i] += var[0, j] * mu[1 + i, j]**2 + var[1 + i, j] * mu[0, j]**2 + var[0, j] * var[1 + i, j]
-        dv = -0.5 * (1.0 / variance - ((self.y - fit)**2 + A) / variance**2)
+        dv = -0.5 * (1.0 / variance - ((Y - fit)**2 + A) / variance**2)
         if self.mask is not None:                            # observed entries only (whatever a masked y / yerr holds)
             dv = np.where(self.mask, dv, 0.0)
-        grads += [float(np.sum(dv[i]) * 2 * jitters[i]) / q for i in range(p)]
+        grads += [float(np.sum(dv[i]) * 2 * jitters[i]) / qdiv for i in range(p)]
         return grads
 
     def nELBO_and_grad(self, parameters, max_iter=None, sweeps=None, start=None, fused=False):
@@ -1510,7 +1599,9 @@ class inference:
         ``nELBO(parameters)`` (warm-started ELBOcalc, as the reference's objective), then ``grad_ELBO``.  With
         ``sweeps`` (and a start state ``(mu, var)``): the ELBO after exactly that many forced sweeps from ``start``
         plus the one ``grad_ELBO`` adds -- a deterministic, smooth function of the parameters.  ``fused``: as in
-        ``grad_ELBO`` (one device call for the kernel parameters; allowed under a data mask)."""
+        ``grad_ELBO`` (one device call for the kernel parameters; allowed under a data mask).  With ``elbo='bound'`` the
+        B-form is the only one and the gradient is exact for every parameter (``grad_ELBO``)."""
+        fused = bool(fused) or self._elbo == 'bound'
         if fused:
             if self._comm is not None:
                 raise NotImplementedError('nELBO_and_grad(fused=True) is not available on a sharded inference object')
@@ -1535,20 +1626,45 @@ class inference:
             return np.inf, np.zeros(int((~self.frozen_mask).sum()))
         return -elbo, -grad[~self.frozen_mask]
 
-    def _jitter_grads_batch(self, jitters, mu, var):
+    def _jitter_grads_batch(self, jitters, mu, var, resid=None):
         """``_grad_from_state``'s jitter entries for B states at once: ``jitters (B, p)``, ``mu`` / ``var (B, p + 1, q, N)``
         -> ``(B, p)``, d ELBO / d jitter_i at fixed state (LogL = -1/2 sum [log(2 pi v) + ((Y - fit)^2 + A) / v],
-        v = jitter^2 + yerr^2; divided by q as the ELBO is, meanfield.py:709)."""
+        v = jitter^2 + yerr^2; divided by q as the ELBO is, meanfield.py:709).  `resid` ``(B, p, N)``: the bound form's
+        entries -- Y is each vector's own ``y - mean``, and nothing is divided by q."""
         jitters = np.asarray(jitters, dtype=float)
         mu, var = np.asarray(mu, dtype=float), np.asarray(var, dtype=float)
         variance = jitters[:, :, None]**2 + self.yerr2[None]
         fit = np.einsum('biqn,bqn->bin', mu[:, 1:], mu[:, 0])
         mf2, vf = mu[:, :1]**2, var[:, :1]
         A = np.sum(vf * mu[:, 1:]**2 + var[:, 1:] * mf2 + vf * var[:, 1:], axis=2)
-        dv = -0.5 * (1.0 / variance - ((self.y[None] - fit)**2 + A) / variance**2)
+        Y = self.y[None] if resid is None else np.asarray(resid, dtype=float)
+        dv = -0.5 * (1.0 / variance - ((Y - fit)**2 + A) / variance**2)
         if self.mask is not None:
             dv = np.where(self.mask[None], dv, 0.0)
-        return np.sum(dv, axis=2) * 2 * jitters / self.q
+        return np.sum(dv, axis=2) * 2 * jitters / (self.q if resid is None else 1.0)
+
+    def _mean_grads_batch(self, sets, jitters, mu, resid):
+        """The bound form's mean-function entries for B vectors: ``sum_n ((y - mean)_in - fit_in) / v_in d mean_i / d theta``
+        over the observed entries, each vector at its own parameters.  ``(B, n_mean_parameters)``; the object's parameters
+        end at the last vector."""
+        jitters = np.asarray(jitters, dtype=float)
+        mu = np.asarray(mu, dtype=float)
+        t = np.asarray(self.time, dtype=float)
+        fit = np.einsum('biqn,bqn->bin', mu[:, 1:], mu[:, 0])
+        w = (np.asarray(resid, dtype=float) - fit) / (jitters[:, :, None]**2 + self.yerr2[None])
+        if self.mask is not None:
+            w = np.where(self.mask[None], w, 0.0)
+        rows = []
+        for b, x in enumerate(sets):
+            self.set_parameters(x)
+            row = []
+            for i, m_ in enumerate(self.means):
+                if m_ is None:
+                    continue
+                dm = m_._dm_dpars(t)
+                row += [0.0] * int(m_._parsize) if dm is None else list(np.asarray(dm, dtype=float) @ w[b, i])
+            rows.append(row)
+        return np.array(rows, dtype=float).reshape(len(sets), -1)
 
     def nELBO_and_grad_batch(self, parameter_sets, max_iter=None, sweeps=None, start=None):
         """
@@ -1575,6 +1691,10 @@ class inference:
         the object holds, as ``nELBO_batch``; the object then keeps the state of the last vector whose loop converged
         (``start`` without ``sweeps`` is a ``ValueError``).
         A vector whose factorisation meets a non-positive pivot returns ``(inf, zeros)``.
+
+        ``elbo='bound'``: the entries of the bound form (``grad_ELBO``) -- own means, no cross terms, nothing divided by q,
+        the jitter entries with each vector's own ``y - mean``, and the mean-function entries filled in from
+        ``meanFunction._dm_dpars``: the whole gradient, exact at a converged state.
 
         Where the side-by-side form does not apply (user-defined kernels, N above ``batch_max_N``, a data mask without
         ``batch_under_mask``, kernel expressions that change shape between vectors) the vectors are evaluated one by one with the same meaning: the
@@ -1611,7 +1731,12 @@ class inference:
         if res is not None:
             elbo, _, _, info, mu_f, var_f, g_k = self._batch_keep(res)
             n_m = n_all - n_k - self.p
-            grads = np.concatenate((g_k / self.q, np.zeros((len(sets), n_m)), self._jitter_grads_batch(jt, mu_f, var_f)), axis=1)
+            if self._elbo == 'bound':
+                resid = np.reshape(yr, (len(sets), self.p, self.N))
+                grads = np.concatenate((g_k, self._mean_grads_batch(sets, jt, mu_f, resid).reshape(len(sets), n_m),
+                                        self._jitter_grads_batch(jt, mu_f, var_f, resid=resid)), axis=1)
+            else:
+                grads = np.concatenate((g_k / self.q, np.zeros((len(sets), n_m)), self._jitter_grads_batch(jt, mu_f, var_f)), axis=1)
             bad = (info > 0) | ~np.isfinite(elbo)
             grads[bad] = 0.0
             values = [float('inf') if b else float(-e) for e, b in zip(elbo, bad)]
@@ -1637,7 +1762,8 @@ class inference:
             if info or not np.isfinite(e):
                 values.append(float('inf'))
                 continue
-            g = np.array(self._grad_from_state(nodes, weights, means, jitters, mu, var, None, fused=ctx))
+            g = np.array(self._grad_from_state(nodes, weights, means, jitters, mu, var, None, fused=ctx,
+                                               bound=self._elbo == 'bound'))
             values.append(float(-e))
             grads[b] = -g[free]
             if conv:

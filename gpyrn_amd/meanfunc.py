@@ -33,6 +33,31 @@ class meanFunction:
     def set_parameters(self, p):
         return _take_leading(self, p, 'mean')
 
+    def _dm_dpars(self, t):
+        """d mean(t) / d pars, ``(n_pars, N)``: what the gradient of the bound form of the ELBO contracts with the weighted
+        residual (``inference(..., elbo='bound')``).  Here Richardson-extrapolated central differences of the function itself
+        (steps h and h / 2, h = 1e-4 max(1, |theta|): O(h^4), rounding near 1e-12 of the function's size); the polynomial means,
+        ``Sine``, ``MultiConstant``, ``Sum`` and ``Product`` have closed forms.  ``None`` would mean: contributes nothing."""
+        t = np.asarray(t, dtype=float)
+        pars = np.array(self.pars, dtype=float)
+        out = np.zeros((pars.size, t.size))
+
+        def at(k, v):
+            x = pars.copy()
+            x[k] = v
+            self.set_parameters(x)
+            return np.asarray(self(t), dtype=float)
+
+        try:
+            for k in range(pars.size):
+                h = 1e-4 * max(1.0, abs(pars[k]))
+                d1 = (at(k, pars[k] + h) - at(k, pars[k] - h)) / (2.0 * h)
+                d2 = (at(k, pars[k] + 0.5 * h) - at(k, pars[k] - 0.5 * h)) / h
+                out[k] = (4.0 * d2 - d1) / 3.0
+        finally:
+            self.set_parameters(pars)
+        return out
+
     def __add__(self, other):
         return Sum(self, other)
 
@@ -84,6 +109,9 @@ class Sum(_pair):
     def __call__(self, t):
         return self.m1(t) + self.m2(t)
 
+    def _dm_dpars(self, t):
+        return np.concatenate((self.m1._dm_dpars(t), self.m2._dm_dpars(t)))
+
 
 class Product(_pair):
     """m1 * m2 (meanfunc.py:85-117)."""
@@ -94,6 +122,9 @@ class Product(_pair):
     @_array_input
     def __call__(self, t):
         return self.m1(t) * self.m2(t)
+
+    def _dm_dpars(self, t):
+        return np.concatenate((self.m1._dm_dpars(t) * self.m2(t)[None], self.m2._dm_dpars(t) * self.m1(t)[None]))
 
 
 class Constant(meanFunction):
@@ -107,6 +138,9 @@ class Constant(meanFunction):
     @_array_input
     def __call__(self, t):
         return np.full(t.shape, self.pars[0])
+
+    def _dm_dpars(self, t):
+        return np.ones((1, np.size(t)))
 
 
 class MultiConstant(meanFunction):
@@ -147,6 +181,15 @@ class MultiConstant(meanFunction):
             which = np.digitize(t, self.time_bins()) - 1
         return np.full_like(t, self.pars[-1]) + np.take(offsets, which)
 
+    def _dm_dpars(self, t):
+        t = np.asarray(t, dtype=float)
+        which = self.ii if t.size == self.time.size else np.digitize(t, self.time_bins()) - 1
+        out = np.zeros((self.pars.size, t.size))
+        for k in range(self.pars.size - 1):
+            out[k] = which == k
+        out[-1] = 1.0
+        return out
+
 
 class Linear(meanFunction):
     """m(t) = slope (t - mean(t)) + intercept (meanfunc.py:190-208)."""
@@ -159,6 +202,10 @@ class Linear(meanFunction):
     @_array_input
     def __call__(self, t):
         return self.pars[0] * (t - t.mean()) + self.pars[1]
+
+    def _dm_dpars(self, t):
+        t = np.asarray(t, dtype=float)
+        return np.array([t - t.mean(), np.ones(t.size)])
 
 
 class Parabola(meanFunction):
@@ -174,6 +221,10 @@ class Parabola(meanFunction):
     def __call__(self, t):
         return np.polyval(self.pars, t)
 
+    def _dm_dpars(self, t):
+        t = np.asarray(t, dtype=float)
+        return np.array([t ** k for k in range(self.pars.size - 1, -1, -1)])
+
 
 class Cubic(meanFunction):
     """m(t) = cub t^3 + quad t^2 + slope t + intercept (meanfunc.py:232-251)."""
@@ -186,6 +237,10 @@ class Cubic(meanFunction):
     @_array_input
     def __call__(self, t):
         return np.polyval(self.pars, t)
+
+    def _dm_dpars(self, t):
+        t = np.asarray(t, dtype=float)
+        return np.array([t ** k for k in range(self.pars.size - 1, -1, -1)])
 
 
 class Sine(meanFunction):
@@ -200,3 +255,9 @@ class Sine(meanFunction):
     def __call__(self, t):
         amplitude, period, phase = self.pars
         return amplitude * np.sin((2 * np.pi * t / period) + phase)
+
+    def _dm_dpars(self, t):
+        t = np.asarray(t, dtype=float)
+        amplitude, period, phase = self.pars
+        arg = (2 * np.pi * t / period) + phase
+        return np.array([np.sin(arg), -amplitude * np.cos(arg) * 2 * np.pi * t / period**2, amplitude * np.cos(arg)])

@@ -271,7 +271,8 @@ int gprn_grad_matrix(gprn_ctx* ctx, int gp, double* G_out);
 /* ---- the terms of the ELBO on their own: what the reference's private step methods return (meanfield.py:895-990 and
  * 992-1067; ELBOaux :651-710 calls them in turn, and scripts written against the reference may too).
  * expected_loglike: inference._expectedLogLike of the state last set (gprn_set_muvar: var = the diagonals of Sigma_f, Sigma_w)
- * under the jitters last set (gprn_set_jitters); the raw data enter as in the reference (quirk Q3).
+ * under the jitters last set (gprn_set_jitters); the raw data enter as in the reference (quirk Q3) -- in the bound form of
+ * the ELBO (option "elbo_form") y - mean as last set by gprn_set_y_resid (GPRN_E_ARG without one).
  * prior_terms: for latent GP `gp` and a covariance S (N, N) / mean m (N) of the caller's choosing -- the reference pairs node j
  * with the cumulative Sigma_f0 + ... + Sigma_fj and weight (j, i) with the raw-reshape row of mu_w (quirks Q1, Q2) -- from the
  * factor of K_gp that gprn_factor_priors left on the device: out3 = { log det K_gp, m^T K_gp^-1 m, tr(K_gp^-1 S) }
@@ -463,9 +464,36 @@ int gprn_predict_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, i
  * product costs eps cond(K) on m^T K^-1 m (meanfield.py:1032, 1050); 0: never; 1: in the sweeps of the launch path as well).
  * "fenced_finalize" (test hook: the finalising kernel of a phase hands its partial terms to its last workgroup with
  * release / acquire fences instead of the gfx942 / gfx950 shortcut documented in csrc/vecops.hip; same bits).
+ * "elbo_form" (GPRN_ELBO_REFERENCE, the default, or GPRN_ELBO_BOUND: which function gprn_sweep, gprn_elbocalc and
+ * gprn_elbocalc_batch report as the ELBO -- see the two constants below; any other value: GPRN_E_ARG).
  * value == -1 only reads; *old (may be
  * NULL) receives the previous value. */
 int gprn_set_option(gprn_ctx* ctx, const char* name, int value, int* old);
+
+/* ---- the form of the reported ELBO (option "elbo_form").
+ * GPRN_ELBO_REFERENCE (default): the reference's number, quirk for quirk (Q1 cumulative node covariance in
+ * tr(K_j^-1 .), Q2 raw-reshape pairing of the weight means, Q3 raw y in the likelihood, Q5 division by q).  Every result
+ * keeps the bits it had.
+ * GPRN_ELBO_BOUND: the mean-field lower bound on log p(y) that the updates ascend.  With variance = jitter^2 + yerr^2, sums
+ * over observed entries only under a mask, m_g / Sigma_g the latent GP's OWN mean and covariance (node j: state row mu[0, j];
+ * weight (j, i): mu[1 + i, j]; K keeps its index gp = q + j p + i):
+ *   LogL = -1/2 sum_{i,n} [ log(2 pi v_in) + ((y - mean)_in - sum_j mu_w,ij mu_f,j)^2 / v_in + cross_in / v_in ]
+ *   LogP = sum_g [ -1/2 log det K_g - 1/2 (m_g^T K_g^-1 m_g + tr B_g^-1) ] - 1/2 N q (p + 1) log 2 pi
+ *   Ent  = as in the reference form
+ *   ELBO = LogL + LogP + Ent     (not divided by q)
+ * cross as in the reference form.  The updates, the initial state, both sweep orders, the stop rule (applied to the new
+ * values), quirk Q7, the nugget and the state layout are unchanged: from the same state the two forms leave the same bits
+ * in mu / var.  The bound form forms no K_j^-1 at set-up and no X^T X of a node during a sweep; the q1 block of
+ * gprn_get_scalars stays zero.
+ * Setting a DIFFERENT value clears the set-up and the committed sweep (gprn_factor_priors -- or do_setup = 1 -- is needed
+ * again) and frees the buffers of gprn_elbocalc_batch, as gprn_set_mask does.  GPRN_E_UNSUPPORTED with a message: the bound
+ * form on a context with a communicator (and gprn_comm_init on a context in the bound form) or with gprn_keep_sigma(1), and
+ * while it is on gprn_keep_sigma(1), gprn_grad_matrices and gprn_grad_kernel.
+ * gprn_grad_elbo, gprn_grad_matrix and gprn_elbocalc_batch_grad in the bound form: G_g = 1/2 (a a^T - S B^-1 S) for EVERY latent
+ * GP, a = K_g^-1 m_g with the latent GP's own mean -- no cross term (and none of its scratch), nothing divided by q.  At a
+ * converged state that is the total derivative of the bound with respect to the kernel parameters (envelope theorem). */
+#define GPRN_ELBO_REFERENCE 0
+#define GPRN_ELBO_BOUND 1
 
 /* ---- diagnostic entry points: one kernel each, for tests/test_kernels_gpu.py ----
  * C (+)= A.B on host matrices through the MFMA tile kernel; modes as in
