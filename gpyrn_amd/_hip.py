@@ -18,6 +18,8 @@ GPRN_BATCH_FORCED = 1          # gprn_elbocalc_batch_grad: no stop rule, max_ite
 COV_JOINT = 1
 ORDER_REFERENCE, ORDER_SEQUENTIAL = 0, 1
 ELBO_REFERENCE, ELBO_BOUND = 0, 1    # option "elbo_form": the reference's number (quirks Q1-Q3, Q5) or the model's bound
+# option "predict_form": _gp.GP.prediction restated, or the predictive of the posterior the committed sweep left
+PREDICT_REFERENCE, PREDICT_POSTERIOR = 0, 1
 M_K, M_KLINV, M_SIGMA, M_BX, M_BL = 0, 1, 2, 3, 4
 T_NAMES = ('fill', 'build_B', 'diag', 'panel', 'update', 'lauum', 'vec', 'update_ahead')
 TILE = 128
@@ -553,7 +555,9 @@ class Context:
         return K, Ks, kss
 
     def option(self, name, value=-1):
-        """Read (value < 0) or set a per-context switch of the library; returns the previous value."""
+        """Read (value < 0) or set a per-context switch of the library; returns the previous value.  Among them
+        ``'predict_form'`` (PREDICT_REFERENCE / PREDICT_POSTERIOR: what predict, predict_cov and predict_draws compute) and
+        the read-only ``'state_ready'`` (1 while a committed sweep's factors are still in the workspaces)."""
         old = c_int(0)
         self._check(self._lib.gprn_set_option(self._h, name.encode(), int(value), byref(old)), 'set_option')
         return old.value

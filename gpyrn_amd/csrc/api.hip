@@ -174,6 +174,11 @@ static void watch_unregister(gprn_ctx* c)
 //                    gradient is asked for: nothing on the device changes, a committed sweep stays good for gprn_grad_elbo
 //   "elbo_form"      GPRN_ELBO_REFERENCE (default) / GPRN_ELBO_BOUND: the reported ELBO with or without quirks Q1-Q3 and Q5
 //                    (include/gprn_hip.h).  A change clears the set-up, the committed sweep and the batches' buffers
+//   "predict_form"   GPRN_PREDICT_REFERENCE (default) / GPRN_PREDICT_POSTERIOR: gprn_predict, gprn_predict_cov and gprn_predict_draws
+//                    restate _gp.GP.prediction or read the posterior the committed sweep left (include/gprn_hip.h).  Read when
+//                    a prediction is asked for: nothing on the device changes
+//   "state_ready"    read-only: 1 while a committed sweep's X, s and X^T X z are still in the workspaces (what gprn_grad_elbo
+//                    and the posterior form of prediction need)
 //   "comm_budget_s"  seconds an entry point may stay inside its collective section before the watchdog ends the process
 //   "accurate_factor" panel steps of a factorisation by substitution instead of products with explicit inverses (diag_tile.h
 //                    ACC): 0 never, 1 always (the launch path's sweeps too), -2 back to the default = every factorisation of a
@@ -198,6 +203,8 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     else if (!strcmp(name, "order_mask")) field = &c->order_mask;
     else if (!strcmp(name, "grad_exact")) field = &c->grad_exact;
     else if (!strcmp(name, "elbo_form")) field = &c->elbo_form;
+    else if (!strcmp(name, "predict_form")) field = &c->predict_form;
+    else if (!strcmp(name, "state_ready")) { if (old) *old = c->grad_ready ? 1 : 0; return GPRN_OK; }
     else if (!strcmp(name, "comm_budget_s")) field = &c->comm_budget_s;
     else if (!strcmp(name, "accurate_factor")) field = &c->acc_opt;
     else if (!strcmp(name, "fenced_finalize")) field = &c->fenced_finalize;
@@ -207,6 +214,8 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     if (old) *old = *field;
     const bool is_pad = field == &c->pad_kb_opt || field == &c->pad_small_kb_opt;
     if ((is_pad || field == &c->acc_opt) && value == -2) { *field = -1; return GPRN_OK; }      // -2: back to the environment / default
+    if (field == &c->predict_form && value < -1)
+        return bad(c, "set_option: predict_form is GPRN_PREDICT_REFERENCE or GPRN_PREDICT_POSTERIOR");
     if (value >= 0) {
         if (field == &c->use_flags && value) {
             int can = 0;
@@ -224,6 +233,14 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
             return GPRN_E_UNSUPPORTED;
         }
         if (field == &c->grad_exact && value > 1) return bad(c, "set_option: grad_exact is 0 or 1");
+        if (field == &c->predict_form) {
+            if (value != GPRN_PREDICT_REFERENCE && value != GPRN_PREDICT_POSTERIOR)
+                return bad(c, "set_option: predict_form is GPRN_PREDICT_REFERENCE or GPRN_PREDICT_POSTERIOR");
+            if (value == GPRN_PREDICT_POSTERIOR && (c->comm || c->shm || c->world > 1)) {
+                c->err = "set_option: the posterior form of prediction is not supported on a context with a communicator";
+                return GPRN_E_UNSUPPORTED;
+            }
+        }
         if (field == &c->elbo_form) {
             if (value != GPRN_ELBO_REFERENCE && value != GPRN_ELBO_BOUND) return bad(c, "set_option: elbo_form is GPRN_ELBO_REFERENCE or GPRN_ELBO_BOUND");
             if (value == GPRN_ELBO_BOUND && (c->comm || c->shm || c->world > 1)) {
@@ -829,6 +846,10 @@ extern "C" int gprn_comm_init(gprn_ctx* c, int world, int rank, const char* id12
     }
     if (c->elbo_form != GPRN_ELBO_REFERENCE && (world > 1 || getenv("GPRN_FORCE_RCCL"))) {
         c->err = "comm_init: a communicator is not supported under the bound form of the ELBO (option \"elbo_form\")";
+        return GPRN_E_UNSUPPORTED;
+    }
+    if (c->predict_form != GPRN_PREDICT_REFERENCE && (world > 1 || getenv("GPRN_FORCE_RCCL"))) {
+        c->err = "comm_init: a communicator is not supported under the posterior form of prediction (option \"predict_form\")";
         return GPRN_E_UNSUPPORTED;
     }
     HIP_TRY(c, hipSetDevice(c->device));

@@ -11,6 +11,14 @@
 // the blocked factor+inverse (X = L^-1), sol = X^T X mu, W^T = K* X^T by the tile kernel.
 // after (may be empty): more work on the device state of the call once the latent means are formed -- gprn_predict_cov /
 // gprn_predict_draws, below.  gps: slot -> latent GP; mean: (slots, ns_pad); WT: per slot W^T = K* X^T (ns_pad x ld).
+//
+// The posterior form (option "predict_form" = GPRN_PREDICT_POSTERIOR; include/gprn_hip.h): the predictive of
+// q(f_g) = N(mu_g, Sigma_g), Sigma_g = K - K S B^-1 S K, which the committed sweep left in the B-form -- X = chol(B)^-1 in the
+// slot's X workspace, s = sqrt(d) and c = X^T X z (the phase's ct) in its vectors:
+//     mean*_g = K*_g S c,     C*_g = K**_g - W W^T,  W^T = (K*_g S) X^T,     var*_g = diag C*_g
+// Nothing is filled at the data times, nothing is factored, no matvec runs: the rectangular fill writes K* S (fill.hip, the
+// nugget and WhiteNoise as delta(t, t')), then predict_impl's own task list and row kernel.  Read: wsX, d_s, d_ct; written:
+// predKs, predWT and the call's scratch -- no flag a sweep or gprn_grad_elbo depends on is touched.
 struct PredState { const std::vector<int>& gps; int ns, ns_pad; const double* d_ts; const double* d_mean; };
 typedef std::function<int(const PredState&)> PredAfter;
 static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out,
@@ -40,6 +48,31 @@ static bool pred_staged(const gprn_ctx* c, int g, int ns, bool with_kss)
     return it != c->pred_stage.end() && it->second.ns == ns && (!with_kss || it->second.kss_ns == ns);
 }
 
+// What the three calls need in the posterior form, before anything is launched
+static int post_checks(gprn_ctx* c, const char* what)
+{
+    if (c->world > 1 || c->comm || c->shm) {
+        c->err = std::string(what) + ": the posterior form of prediction (option \"predict_form\") is not supported on a context "
+                 "with a communicator";
+        return GPRN_E_UNSUPPORTED;
+    }
+    for (int g = 0; g < c->G; ++g)
+        if (c->kspec[g].set && c->kspec[g].uploaded) {
+            c->err = std::string(what) + ": the posterior form of prediction (option \"predict_form\") needs a device program for "
+                     "every latent GP (gprn_set_kernel); latent GP " + std::to_string(g) + " was given by gprn_upload_K";
+            return GPRN_E_UNSUPPORTED;
+        }
+    if (!c->grad_ready || !c->factored || !c->tables_ready || (int)c->loc_nodes.size() != c->q ||
+        (int)c->loc_weights.size() != c->G - c->q) {
+        c->err = std::string(what) + ": the posterior form needs a committed sweep (gprn_sweep with commit = 1, or gprn_elbocalc) "
+                 "right before it";
+        return GPRN_E_ARG;
+    }
+    for (int g = 0; g < c->G; ++g)
+        if (!c->kspec[g].set) return bad(c, "predict: a latent GP has no kernel");
+    return GPRN_OK;
+}
+
 __global__ void k_add_to_diagonal(double* __restrict__ A, int ld, const double* __restrict__ v, int N)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,6 +88,7 @@ extern "C" int gprn_predict(gprn_ctx* c, int ns, const double* tstar, double* me
     HIP_TRY(c, hipSetDevice(c->device));
     int pre = GPRN_OK;
     if (ns <= 0 || !tstar || !mean_out || !var_out) pre = bad(c, "predict: bad argument");
+    else if (c->predict_form == GPRN_PREDICT_POSTERIOR) pre = post_checks(c, "predict");
     else if (!c->have_muvar) pre = bad(c, "predict: set_muvar (or a sweep) first");
     else
         for (int g = 0; g < c->G && !pre; ++g) {
@@ -98,8 +132,12 @@ extern "C" int gprn_predict_batch(gprn_ctx* c, int n_eval, const double* kernel_
 
 static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_out, double* var_out, const PredAfter& after)
 {
-    TRY(build_tables(c));
-    c->grad_ready = false;                           // (the sweep's workspaces hold the prediction's factors from here on)
+    // (the posterior form reads what the committed sweep left and writes none of it: its tables and flags stay)
+    const bool post = c->predict_form == GPRN_PREDICT_POSTERIOR;
+    if (!post) {
+        TRY(build_tables(c));
+        c->grad_ready = false;                       // (the sweep's workspaces hold the prediction's factors from here on)
+    }
     std::vector<int> gps = c->loc_nodes;
     gps.insert(gps.end(), c->loc_weights.begin(), c->loc_weights.end());
     const int nloc = (int)gps.size();
@@ -152,6 +190,11 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
         HIP_TRY(c, hipMemcpy(c->d_slotgp_all, staterow.data(), nloc * sizeof(int), hipMemcpyHostToDevice));
         for (int s = 0; s < nloc; ++s) {
             const KernelSpec& ks = c->kspec[gps[s]];
+            if (post) {                               // K* S and k** (slot s = latent GP s: one rank, post_checks)
+                TRY(launch_fill_rect_post(c, ks, GPRN_SETUP_NUGGET, d_ts, ns, ns_pad, c->d_s + (size_t)s * ld, c->predKs[s],
+                                          d_kss + (size_t)s * ns_pad));
+                continue;
+            }
             if (!ks.uploaded) {
                 TRY(launch_fill(c, ks, c->wsB[s], 1.25e-12, c->d_var + (size_t)staterow[s] * N));
                 TRY(launch_fill_rect(c, ks, 1.25e-12, d_ts, ns, ns_pad, c->predKs[s], d_kss + (size_t)s * ns_pad));
@@ -175,10 +218,13 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
             memcpy(pad.data(), st.kss.data(), ns * sizeof(double));
             HIP_TRY(c, hipMemcpy(d_kss + (size_t)s * ns_pad, pad.data(), ns_pad * sizeof(double), hipMemcpyHostToDevice));
         }
-        HIP_TRY(c, hipMemsetAsync(c->d_info, 0, 3 * (size_t)c->nslot * sizeof(int), c->stream));
-        TRY(factor_invert(c, pred, true));
-        TRY(vec_lower_matvec(c, pred, BUF_X, c->d_mu, N, 1, c->d_u));   // u = X mu
-        TRY(vec_colops(c, pred));                                        // ct = X^T u
+        if (!post) {
+            HIP_TRY(c, hipMemsetAsync(c->d_info, 0, 3 * (size_t)c->nslot * sizeof(int), c->stream));
+            TRY(factor_invert(c, pred, true));
+            TRY(vec_lower_matvec(c, pred, BUF_X, c->d_mu, N, 1, c->d_u));   // u = X mu
+            TRY(vec_colops(c, pred));                                        // ct = X^T u
+        }
+        // (the posterior form: X and ct = X^T X z are the committed sweep's, every path leaves both -- DESIGN.md 9 f-2)
         for (int bt = 0; bt < ns_pad / GPRN_TILE; ++bt)
             for (int at = 0; at < T; ++at)
                 tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE,
@@ -221,6 +267,7 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
             memcpy(var_out + (size_t)gps[s] * ns, &hv[(size_t)s * ns_pad], ns * sizeof(double));
         }
     }
+    if (post) return GPRN_OK;                        // (nothing was factored: the verdict rows are the sweep's)
     c->info_gp = -1;
     TRY(factor_check_waits(c));
     int first = 0;
@@ -306,6 +353,8 @@ void k_zero_diag_upper(double* const* __restrict__ Ls, int n_pad)
 // R = i ns + t.  Each workgroup takes one lower 32 x 32 block of an output matrix, writes it and its mirror image (LDS
 // transpose): exactly symmetric, and only the lower half of the latent matrices is read.  Memory-bound: per lower element
 // 2q (diagonal blocks i = k) or q (cross blocks) doubles are read and two are written.
+// ONCE (the posterior form of prediction): jitter_i^2 delta(t, t') once, not once per node.
+template <bool ONCE = false>
 __global__ __launch_bounds__(256)
 void k_output_cov(const double* const* __restrict__ Cs, const double* __restrict__ mean, const double* __restrict__ jit2,
                   int q, int p, int ns, int ns_pad, int joint, double* __restrict__ out)
@@ -331,7 +380,7 @@ void k_output_cov(const double* const* __restrict__ Cs, const double* __restrict
                     // (meanfield.py:1372-1373, term by term: w w C_f + C_w (C_f + f f) + jitter^2, once per node)
                     double term = a * cf + Cs[gi][(size_t)t * ns_pad + u] *
                                                (cf + mean[(size_t)j * ns_pad + t] * mean[(size_t)j * ns_pad + u]);
-                    if (t == u) term += jit2[i];
+                    if (t == u && (!ONCE || j == 0)) term += jit2[i];
                     v += term;
                 } else
                     v += a * cf;
@@ -399,6 +448,12 @@ static int cov_conditional(gprn_ctx* c, CallScratch& scr, const PredState& st, C
     for (int g = 0; g < G; ++g) {
         double* Cg = w.C + (size_t)g * nn;
         const KernelSpec& ks = c->kspec[g];
+        if (c->predict_form == GPRN_PREDICT_POSTERIOR) {
+            // (the set-up's nugget; between EQUAL prediction times the delta terms go off the diagonal too)
+            TRY(launch_fill_times(c, ks, Cg, GPRN_SETUP_NUGGET, nullptr, st.d_ts, ns, ns_pad));
+            TRY(launch_fill_coincide(c, Cg, st.d_ts, ns, ns_pad));
+            continue;
+        }
         if (!ks.uploaded) { TRY(launch_fill_times(c, ks, Cg, 1.25e-12, nullptr, st.d_ts, ns, ns_pad)); continue; }
         const gprn_ctx::PredStage& ps = c->pred_stage[g];
         std::vector<double> pad(nn, 0.0);
@@ -456,8 +511,12 @@ static int cov_outputs(gprn_ctx* c, CallScratch& scr, const PredState& st, const
         TRY(scr.alloc(&d_jit2, c->p));
         HIP_TRY(c, hipMemcpyAsync(d_jit2, j2.data(), c->p * sizeof(double), hipMemcpyHostToDevice, c->stream));
         prof_begin(c, GPRN_T_VEC);
-        hipLaunchKernelGGL(k_output_cov, dim3(nb * (nb + 1) / 2, joint ? 1 : c->p), dim3(256), 0, c->stream,
-                           (const double* const*)w.t_C, st.d_mean, (const double*)d_jit2, c->q, c->p, ns, ns_pad, joint ? 1 : 0, w.out);
+        if (c->predict_form == GPRN_PREDICT_POSTERIOR)
+            hipLaunchKernelGGL(k_output_cov<true>, dim3(nb * (nb + 1) / 2, joint ? 1 : c->p), dim3(256), 0, c->stream,
+                               (const double* const*)w.t_C, st.d_mean, (const double*)d_jit2, c->q, c->p, ns, ns_pad, joint ? 1 : 0, w.out);
+        else
+            hipLaunchKernelGGL(k_output_cov<false>, dim3(nb * (nb + 1) / 2, joint ? 1 : c->p), dim3(256), 0, c->stream,
+                               (const double* const*)w.t_C, st.d_mean, (const double*)d_jit2, c->q, c->p, ns, ns_pad, joint ? 1 : 0, w.out);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(rq.out_cov, w.out, (joint ? (size_t)M * M : (size_t)c->p * M * M) * sizeof(double),
@@ -623,6 +682,11 @@ static int cov_entry(gprn_ctx* c, const char* what, int ns, const double* tstar,
     HIP_TRY(c, hipSetDevice(c->device));
     int pre = GPRN_OK;
     if (ns <= 0 || !tstar) pre = bad(c, "predict_cov: bad argument");
+    else if (c->predict_form == GPRN_PREDICT_POSTERIOR) {
+        // (the committed sweep vouches for the state and the kernels; the jitters are the sweep's)
+        pre = post_checks(c, what);
+        if (!pre && rq.out_cov && (int)c->h_jit.size() != c->p) pre = bad(c, "predict_cov: set_jitters first");
+    }
     else if (!c->have_muvar) pre = bad(c, "predict_cov: set_muvar (or a sweep) first");
     else if (rq.out_cov && (int)c->h_jit.size() != c->p) pre = bad(c, "predict_cov: set_jitters first");
     else

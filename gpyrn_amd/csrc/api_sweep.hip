@@ -853,7 +853,7 @@ int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchB
 {
     const int B = io.n, G = c->G, p = c->p, N = c->N;
     const BatchBufs h = layout_at(pin, batch_pin_in, cap, G, fill_program_bytes(), io.yv, io.state);
-    TRY(batch_stage_programs(c, io.kparams, io.n_kpar, B, h.programs, 1e-6, "elbocalc_batch"));
+    TRY(batch_stage_programs(c, io.kparams, io.n_kpar, B, h.programs, GPRN_SETUP_NUGGET, "elbocalc_batch"));
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < p; ++i) {
             const double j2 = io.jitters[(size_t)b * p + i] * io.jitters[(size_t)b * p + i];

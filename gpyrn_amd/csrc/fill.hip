@@ -525,28 +525,57 @@ int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, 
 // Rectangular cross-covariance K*[i][n] = k(t*_i, t_n), no nugget (_gp.py:50-61, meanfield.py:455-471),
 // rows padded to a multiple of 128 with zeros; and the prior variance at the prediction points,
 // kss[i] = k(t*_i, t*_i) + nugget (the diagonal of _gp.py:40-48 evaluated at tstar).
-template <int KID>
+// POST (the posterior form of prediction, option "predict_form"): K* diag(s) instead, s = sqrt(d) of the slot as the committed
+// sweep left it (zero on the rows of zero precision: zero columns, nothing is divided), and the nugget and WhiteNoise are
+// delta(t, t') -- in K* exactly where t*_i == t_n, so that at a data time the row is the row of the set-up's K.  The other
+// instantiation is the kernel prediction always had.
+template <int KID, bool POST = false>
 __global__ __launch_bounds__(256)
 void k_fill_rect(FillProgram pg, const double* __restrict__ ts, int ns, int ns_pad,
                  const double* __restrict__ t, int N, int ld, double* __restrict__ Ks,
-                 double* __restrict__ kss)
+                 double* __restrict__ kss, const double* __restrict__ s)
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
-    const int i0 = blockIdx.y * 8;
-    if (n >= ld) return;
-    const double tn = (n < N) ? t[n] : 0.0;
+    constexpr int ROWS = (POST && KID < 0) ? 1 : 8;
+    const int i0 = blockIdx.y * ROWS;
+    if constexpr (POST) {
+        // ROWS rows per thread: 8 as in the other form, 1 for the postfix program (no scratch that way);
+        // column ld (one thread of an extra workgroup per row group) is k**: ONE call site of the element code for both, the
+        // delta terms wherever the two times are equal -- k** always
+        if (n > ld) return;
+        const bool is_kss = n == ld;
+        const double tn = (n < N) ? t[n] : 0.0;
+        const double sn = (n < N) ? s[n] : 0.0;
 #pragma unroll 1
-    for (int r = 0; r < 8; ++r) {
-        const int i = i0 + r;
-        if (i >= ns_pad) break;
-        double v = 0.0;
-        if (i < ns && n < N)
-            v = eval_any<KID>(pg, ts[i], tn, false);
-        Ks[(size_t)i * ld + n] = v;
-        if (n == 0 && i < ns) {
-            double d = eval_any<KID>(pg, ts[i], ts[i], true);
-            if (pg.nugget) d += pg.nugget_val;
-            kss[i] = d;
+        for (int r = 0; r < ROWS; ++r) {
+            const int i = i0 + r;
+            if (i >= ns_pad) break;
+            double v = 0.0;
+            if (i < ns && (n < N || is_kss)) {
+                const double ti = ts[i], tj = is_kss ? ti : tn;
+                const bool same = ti == tj;
+                v = eval_any<KID>(pg, ti, tj, same);
+                if (same && pg.nugget) v += pg.nugget_val;
+            }
+            if (!is_kss) Ks[(size_t)i * ld + n] = v * sn;
+            else if (i < ns) kss[i] = v;
+        }
+    } else {
+        if (n >= ld) return;
+        const double tn = (n < N) ? t[n] : 0.0;
+#pragma unroll 1
+        for (int r = 0; r < 8; ++r) {
+            const int i = i0 + r;
+            if (i >= ns_pad) break;
+            double v = 0.0;
+            if (i < ns && n < N)
+                v = eval_any<KID>(pg, ts[i], tn, false);
+            Ks[(size_t)i * ld + n] = v;
+            if (n == 0 && i < ns) {
+                double d = eval_any<KID>(pg, ts[i], ts[i], true);
+                if (pg.nugget) d += pg.nugget_val;
+                kss[i] = d;
+            }
         }
     }
 }
@@ -559,11 +588,57 @@ int launch_fill_rect(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const
     prof_begin(c, GPRN_T_FILL);
     dim3 grid((c->ld + 255) / 256, (ns_pad + 7) / 8);
     switch (program_kid(pg)) {
-#define X(id) case id: hipLaunchKernelGGL(k_fill_rect<id>, grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss); break;
+#define X(id) case id: hipLaunchKernelGGL(k_fill_rect<id>, grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, (const double*)nullptr); break;
     GPRN_FOR_EACH_KID(X)
 #undef X
-    default: hipLaunchKernelGGL(k_fill_rect<-1>, grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss);
+    default: hipLaunchKernelGGL(k_fill_rect<-1>, grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, (const double*)nullptr);
     }
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
+int launch_fill_rect_post(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
+                          int ns, int ns_pad, const double* s, double* Ks, double* kss)
+{
+    FillProgram pg;
+    make_program(ks, nugget_val, pg);
+    prof_begin(c, GPRN_T_FILL);
+    dim3 grid((c->ld + 1 + 255) / 256, (ns_pad + 7) / 8);     // (column ld: k**)
+    switch (program_kid(pg)) {
+#define X(id) case id: hipLaunchKernelGGL((k_fill_rect<id, true>), grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, s); break;
+    GPRN_FOR_EACH_KID(X)
+#undef X
+    // (the program form: one row per thread -- with the row loop around the whole switch the compiler reserves scratch)
+    default:
+        if (ns_pad > 65535) {
+            prof_end(c);
+            c->err = "predict: the posterior form takes at most 65535 times per call for a composite kernel";
+            return GPRN_E_ARG;
+        }
+        grid.y = ns_pad; hipLaunchKernelGGL((k_fill_rect<-1, true>), grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, s);
+    }
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
+// The delta terms of K** between EQUAL prediction times (the posterior form): with t_i == t_j bit for bit, k(t_i, t_j) with its
+// delta terms IS the diagonal entry k(t_i, t_i) + nugget the fill has written, so entry (i, j) takes K[i][i] -- no kernel is
+// evaluated again, and the matrix stays symmetric (K[i][i] and K[j][j] are the same evaluation of the same arguments).
+// Reads the diagonal only, writes off-diagonal entries only.  grid (ld / 256, N)
+__global__ __launch_bounds__(256)
+void k_fill_coincide(double* __restrict__ K, const double* __restrict__ t, int N, int ld)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (j >= N || i >= N || i == j) return;
+    if (t[i] == t[j]) K[(size_t)i * ld + j] = K[(size_t)i * ld + i];
+}
+
+int launch_fill_coincide(gprn_ctx* c, double* K, const double* t, int N, int ld)
+{
+    prof_begin(c, GPRN_T_FILL);
+    hipLaunchKernelGGL(k_fill_coincide, dim3((N + 255) / 256, N), dim3(256), 0, c->stream, K, t, N, ld);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

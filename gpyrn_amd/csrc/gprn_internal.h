@@ -302,6 +302,7 @@ struct gprn_ctx {
     int sweep_order = 0;             // GPRN_ORDER_REFERENCE (Jacobi, quirk Q6) or GPRN_ORDER_SEQUENTIAL
     int order_mask = 0;              // gprn_set_option "order_mask": the sequential order and a data mask together (default: each refuses the other)
     int elbo_form = 0;               // gprn_set_option "elbo_form": GPRN_ELBO_REFERENCE (quirks Q1-Q3, Q5) or GPRN_ELBO_BOUND
+    int predict_form = 0;            // gprn_set_option "predict_form": GPRN_PREDICT_REFERENCE (_gp.GP.prediction) or GPRN_PREDICT_POSTERIOR
     double* d_mu_old = nullptr;      // sequential order on the launch path: the means a phase started from (order_snapshot)
     size_t mu_old_cap = 0;
     int n_states = 1;                // copies of the state behind d_mu (a batch's worker context: its evaluations)
@@ -334,7 +335,11 @@ struct DeviceLock {                                // no-op for a null context (
 void prof_begin(gprn_ctx* c, int fam, hipStream_t stream = nullptr);   // nullptr = ctx->stream
 void prof_end(gprn_ctx* c);
 
-int launch_fill(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val = 1e-6,
+// the nugget of the set-up (meanfield.py:433; quirk Q9: none for the two-argument kernels) -- the ONE definition: the priors'
+// fills, the batches' programs and the posterior form of prediction, whose "at a data time the prediction is the state" rests
+// on reading the very value the sweeps' K was filled with
+static const double GPRN_SETUP_NUGGET = 1e-6;
+int launch_fill(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val = GPRN_SETUP_NUGGET,
                 const double* diag_add = nullptr);
 // ... over a time vector of the caller's (N entries, device) into a matrix of pitch ld = 128 k (K** at prediction times)
 int launch_fill_times(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val, const double* diag_add,
@@ -350,6 +355,12 @@ int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d
                            int ns, int ns_pad, double* kss, size_t kss_stride);
 int launch_fill_rect(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
                      int ns, int ns_pad, double* Ks, double* kss);
+// the posterior form of prediction (option "predict_form"): K* diag(s) and k**, the nugget and WhiteNoise as delta(t, t') --
+// in K* where t*_i == t_n, in k** always (s: the slot's sqrt(d), ld entries)
+int launch_fill_rect_post(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
+                          int ns, int ns_pad, const double* s, double* Ks, double* kss);
+// ... and in K** (filled by launch_fill_times, pitch ld): entry (i, j), i != j, of two EQUAL times becomes the diagonal's
+int launch_fill_coincide(gprn_ctx* c, double* K, const double* t, int N, int ld);
 // workgroup output shape of a tile launch (csrc/gemm_tile.hip)
 enum { TS_128x128 = 0, TS_64x64 = 1, TS_64x128 = 2, TS_128x64 = 3,
        TS_64x128_BTRI = 4, TS_128x64_ATRI = 5 };   // panel products with the triangular X_kk (gemm_tile.hip TRI)

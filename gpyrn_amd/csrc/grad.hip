@@ -351,7 +351,7 @@ struct GradWork {
 // the kernel's part of a slot: the program at `params`, which derivative applies (gprn_grad_kernel's rules), where its sums go
 static void grad_slot_kernel(const KernelSpec& ks, const double* params, int out_off, GradSlot* s, int exact)
 {
-    fill_program_with(ks, params, &s->pg, 1e-6);
+    fill_program_with(ks, params, &s->pg, GPRN_SETUP_NUGGET);
     const int kid = (ks.n_ops == 1 && ks.ops[0] == GPRN_OP_PUSH && ks.ops[2] == 0) ? ks.ops[1] : -1;
     const bool closed = kid == GPRN_K_SE || kid == GPRN_K_PERIODIC || kid == GPRN_K_QP;
     s->mode = closed ? 0 : (exact && grad_exact_applies(ks) ? 2 : 1);

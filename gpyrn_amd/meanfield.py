@@ -104,13 +104,24 @@ class inference:
             the gradients follow it; ``ELBOaux`` and the four step methods restate reference functions and stay in the
             reference's form.  Not with ``comm``.  An attribute that may be set later: it goes to the device with every
             set-up, and a change drops the cached set-up and the stored state.
+        predict: 'reference' (default) or 'variational', keyword only
+            WHAT ``predict``, ``_Prediction``, ``predict_cov`` and ``sample_posterior`` compute (option ``"predict_form"`` of
+            the library; not in the reference; the attribute is ``predict_form``).  'reference': the reference's
+            ``_gp.GP.prediction`` -- the variational variances treated as observation noise on ``K + 1.25e-12 I``, factored
+            per call, the jitter added once per node.  'variational': the predictive of the posterior the sweeps computed,
+            ``q(f_g) = N(mu_g, Sigma_g)``: ``mean* = K* S c``, ``C* = K** - W W^T`` from the factors of the last committed
+            sweep, with the set-up's nugget and the jitter added once.  At the data times it returns the stored state --
+            the imputation under a data mask included.  Not with ``comm``, not for user-defined kernels, and not (yet) for
+            ``predict_batch`` / ``posterior_predictive``.  An attribute that may be set later.
     """
 
     _SWEEP_ORDERS = {'reference': _hip.ORDER_REFERENCE, 'sequential': _hip.ORDER_SEQUENTIAL}
     _ELBO_FORMS = {'reference': _hip.ELBO_REFERENCE, 'bound': _hip.ELBO_BOUND}
+    _PREDICT_FORMS = {'reference': _hip.PREDICT_REFERENCE, 'variational': _hip.PREDICT_POSTERIOR}
 
     def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference',
-                 batch_under_mask=False, exact_derivatives=False, sequential_under_mask=False, elbo='reference'):
+                 batch_under_mask=False, exact_derivatives=False, sequential_under_mask=False, elbo='reference',
+                 predict='reference'):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -149,6 +160,9 @@ class inference:
         self._ctx = None
         self._sweep_order = self._check_sweep_order(sweep_order)
         self._elbo = self._check_elbo(elbo)
+        self._predict_form = self._check_predict_form(predict)
+        self._predict_sent = 'reference'   # what the context was last told (a new context is in the reference form)
+        self._swept = None                 # (the stored state, the parameters, the set-up's key): whose committed sweep the device holds
         self._prior_key = None
         self.last_info = 0
 
@@ -218,6 +232,7 @@ class inference:
             # (the device's set-up belongs to the other form, and a stored state was accepted by the other form's stop rule)
             self._prior_key = None
             self._mu, self._var = None, None
+            self._swept = None
         self._elbo = form
         if self._ctx is not None:
             self._send_elbo_form(self._ctx)
@@ -228,6 +243,70 @@ class inference:
         want = self._ELBO_FORMS[self._check_elbo(self._elbo if form is None else form)]
         if ctx.option('elbo_form', want) != want:
             self._prior_key = None
+
+    @property
+    def _prior_key(self):
+        """What names the kernels whose factors the device holds (None: nothing does)."""
+        return self._prior_key_value
+
+    @_prior_key.setter
+    def _prior_key(self, key):
+        # (whoever touches the device's kernels or their factors -- a set-up, ELBOaux and the step methods with their uploaded
+        # matrices, a prediction with other components -- assigns here: the committed sweep the marker vouched for is gone)
+        self._prior_key_value = key
+        self._swept = None
+
+    def _check_predict_form(self, form):
+        """'reference' or 'variational', validated before anything touches a device."""
+        if not isinstance(form, str) or form not in self._PREDICT_FORMS:
+            raise ValueError(f"predict must be 'reference' or 'variational', got {form!r}")
+        if form != 'reference' and self._comm is not None:
+            raise NotImplementedError('predict: the variational form is not supported on a sharded inference object')
+        return form
+
+    @property
+    def predict_form(self):
+        """ 'reference' or 'variational': what predict, _Prediction, predict_cov and sample_posterior compute """
+        return self._predict_form
+
+    @predict_form.setter
+    def predict_form(self, form):
+        self._predict_form = self._check_predict_form(form)
+
+    def _send_predict_form(self, ctx):
+        """Option "predict_form" from the object's form, before every prediction (nothing on the device changes with it).
+        A context that never left the reference form is not asked."""
+        form = self._check_predict_form(self._predict_form)
+        if form != self._predict_sent:
+            ctx.option('predict_form', self._PREDICT_FORMS[form])
+            self._predict_sent = form
+
+    def _mark_swept(self, nodes, weights, means, jitters):
+        """The private marker of the variational form of prediction: the device's committed sweep is the one that produced
+        the stored state -- kept as (that very state array, the parameter vector it belongs to, the key of the set-up), so
+        that a new stored state, ``set_parameters``, ``set_components`` or a component changed in place all make it stale;
+        every assignment to ``_prior_key`` drops it (a set-up, ``ELBOaux`` and the step methods, a prediction with other
+        components), as does a new context; what else stages another state on the device shows in the library's read-only
+        option "state_ready"."""
+        own = self._components_set and nodes is self.nodes and weights is self.weights and means is self.means \
+            and jitters is self.jitters
+        ok = own and self._mu is not None and self._prior_key is not None
+        self._swept = (self._mu, self._parameter_snapshot(), self._prior_key) if ok else None
+
+    def _parameter_snapshot(self):
+        """Every parameter value of the object's components (a mean function may be None), as one vector."""
+        pieces = [np.ravel(np.asarray(c.pars, dtype=float)) for c in self._component_chain() if c is not None and hasattr(c, 'pars')]
+        pieces.append(np.ravel(np.asarray(self.jitters, dtype=float)))
+        return np.concatenate(pieces)
+
+    def _is_swept(self, ctx):
+        if self._swept is None or self._mu is None or self._swept[0] is not self._mu:
+            return False
+        if not np.array_equal(self._swept[1], self._parameter_snapshot()):
+            return False
+        if self._prior_key is None or self._swept[2] != self._prior_key:
+            return False
+        return ctx.option('state_ready') == 1
 
     def _send_order_mask(self, ctx):
         """Option "order_mask" from ``sequential_under_mask``, the object's order validated against it first (the attribute
@@ -292,6 +371,7 @@ class inference:
         self.means = means
         self.jitters = np.array(jitters, dtype=float)
         self._components_set = True
+        self._swept = None
 
     def _component_chain(self):
         return chain.from_iterable([self.nodes, self.weights, self.means])
@@ -338,6 +418,7 @@ class inference:
         for component in self._component_chain():
             parameters = component.set_parameters(parameters)
         self.jitters = parameters
+        self._swept = None
 
     @property
     def n_parameters(self):
@@ -466,6 +547,8 @@ class inference:
                 # one rank per GPU; with fewer GPUs than ranks (rehearsals) ranks share devices
                 device = comm.local_rank % max(1, _hip.device_count()) if comm is not None else 0
             ctx = _hip.Context(device)
+            self._predict_sent = 'reference'                      # (a new context is in the reference form)
+            self._prior_key = None                                # (... holds no set-up and no sweep: the marker goes too)
             forced = bool(os.environ.get('GPRN_FORCE_RCCL'))      # one-rank communicator, for tests
             if comm is not None and (comm.world > 1 or forced):
                 ctx.comm_init(comm.world, comm.rank, comm.unique_id())
@@ -478,6 +561,8 @@ class inference:
                 ctx.set_mask(self.mask)
             if self._elbo != 'reference':
                 self._send_elbo_form(ctx)
+            if self._predict_form != 'reference':
+                self._send_predict_form(ctx)
             if comm is not None and comm.world > 1:
                 ctx.set_owners(sharding.owners(self.p, self.q, comm.world))
             self._ctx = ctx
@@ -663,6 +748,7 @@ class inference:
         # sweep's update thrown away and only its ELBO kept, sweeps to the stop rule or max_iter
         ctx = self._backend()
         self._send_elbo_form(ctx)
+        self._swept = None
         specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
         key = tuple(self._spec_key(s) for s in specs)
         setup = key != self._prior_key
@@ -684,6 +770,8 @@ class inference:
         ELBO = np.float64(history[-1])
         if converged:
             self._mu, self._var = mu, var
+            if info == 0 and iterNumber >= 1:
+                self._mark_swept(nodes, weights, means, jitters)
             return ELBO, mu, var, iterNumber
 
         print('\nMax iterations reached')
@@ -905,11 +993,22 @@ class inference:
         owner, every rank receiving all rows); the O(p q N*) combination below is
         the reference's, including the jitter added once per node.
 
+        The variational form (``predict='variational'``; not in the reference): every latent GP's mean and variance are
+        those of the posterior the sweeps computed, ``mean* = K* S c`` and ``var* = k** - |X S K*^T e|^2`` from the
+        factors a committed sweep leaves on the device (``_variational_sweep``), and the combination is
+        ``mean_i + sum_j w_ij f_j`` and ``sum_j [w_ij^2 v_fj + v_wij (v_fj + f_j^2)] + jitter_i^2`` -- the jitter ONCE.
+        With `mu`, `var` given, one sweep runs from that state, the prediction is of the state it leaves, and the
+        stored state stays as it is.
+
         Returns (mean (N*, p), variance (N*, p)) and, with `separate`, the
         object array [node means (q, N*), weight means (q*p, N*)].
         """
         nodes, weights, means, jitters = self._get_components(nodes, weights, means, jitters)
         tstar = self.time if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
+        if self._predict_form == 'variational':
+            ctx = self._variational_sweep(nodes, weights, means, jitters, mu, var)
+            gmean, gvar, _ = ctx.predict(tstar)
+            return self._combine_prediction(gmean, gvar, means, jitters, tstar, separate, once=True)
         if mu is None and var is None:
             if self._mu is None and self._var is None:
                 mu, var = self._initMuVar(nodes, weights, jitters)
@@ -932,10 +1031,15 @@ class inference:
                 continue
             ctx.predict_upload(gp, self._tinyNuggetKMatrix(kernel, data_t),
                                self._predictKMatrix(kernel, tstar), self._kss_diagonal(kernel, tstar))
+        self._send_predict_form(ctx)
         ctx.set_muvar(np.asarray(mu, dtype=float), np.asarray(var, dtype=float))
         gmean, gvar, info = ctx.predict(tstar)
         self.last_info = info
+        return self._combine_prediction(gmean, gvar, means, jitters, tstar, separate)
 
+    def _combine_prediction(self, gmean, gvar, means, jitters, tstar, separate, once=False):
+        """The O(p q N*) combination of _Prediction (meanfield.py:1346-1373) from the latent rows (G, N*): the jitter once
+        per node as the reference has it, or -- `once`, the variational form -- once."""
         q, p = self.q, self.p
         nPred, nVar = gmean[:q], gvar[:q]
         wPred, wVar = gmean[q:], gvar[q:]
@@ -948,16 +1052,71 @@ class inference:
             predictives[:, i] += meanVal[i]
             for j in range(q):
                 predictives[:, i] += nPred[j] * wP[j, i]
-                predictivesVar[:, i] += wP[j, i] * wP[j, i] * nVar[j] \
-                    + wV[j, i] * (nVar[j] + nPred[j] * nPred[j]) + jitt2[i]
+                if once:
+                    predictivesVar[:, i] += wP[j, i] * wP[j, i] * nVar[j] + wV[j, i] * (nVar[j] + nPred[j] * nPred[j])
+                else:
+                    predictivesVar[:, i] += wP[j, i] * wP[j, i] * nVar[j] \
+                        + wV[j, i] * (nVar[j] + nPred[j] * nPred[j]) + jitt2[i]
+            if once:
+                predictivesVar[:, i] += jitt2[i]
         if separate:
             return predictives, predictivesVar, np.array([nPred, wPred], dtype=object)
         return predictives, predictivesVar
 
+    def _variational_sweep(self, nodes, weights, means, jitters, mu=None, var=None):
+        """The device state the variational form of prediction reads: the factors of a committed sweep that produced the
+        state the prediction is of.  Returns the context, the option ``"predict_form"`` set.
+
+        * No stored state (``self._mu is None``): ``ELBOcalc()`` runs first.
+        * The object knows that the device's committed sweep is the one that produced the stored state -- the private
+          marker ``ELBOcalc`` / ``nELBO`` / ``grad_ELBO(fused=True)`` leave, stale after ``set_parameters``,
+          ``set_components``, a new stored state or a changed component -- and the library's ``"state_ready"`` reads 1:
+          NO sweep is run, the stored state is untouched.
+        * Otherwise the set-up, ``set_muvar(stored state)`` and one committed sweep, exactly as ``grad_ELBO(fused=True)``
+          does; the object keeps the state that sweep leaves and ``last_info`` is set.
+        * `mu`, `var` given: one sweep from that state; the stored state is left alone (and the marker dropped: the device
+          no longer holds the stored state's sweep).
+        A non-positive pivot raises ``np.linalg.LinAlgError``; a user-defined kernel ``NotImplementedError``."""
+        for k in chain(nodes, weights):
+            if not isinstance(k, covfunc.covFunction) or k._device_program() is None:
+                raise NotImplementedError("predict='variational' needs a device program for every kernel: user-defined "
+                                          'kernels (and sums that hold a two-argument kernel) are not supported')
+        explicit = mu is not None or var is not None
+        if explicit and (mu is None or var is None):
+            raise ValueError('_Prediction: give both mu and var, or neither')
+        if not explicit:
+            if self._mu is None:
+                _, mu, var, _ = self.ELBOcalc(nodes, weights, means, jitters)
+                if self._mu is not None:                 # (converged: the stored state; else the state the loop ended in)
+                    mu, var = self._mu, self._var
+            else:
+                mu, var = self._mu, self._var
+            ctx = self._backend()
+            own = nodes is self.nodes and weights is self.weights and means is self.means and jitters is self.jitters
+            if own and mu is self._mu and self._is_swept(ctx):
+                self._send_predict_form(ctx)
+                return ctx
+        self._swept = None
+        ctx = self._setup_device(nodes, weights, means, jitters)
+        self._send_predict_form(ctx)
+        ctx.set_muvar(np.array(mu, dtype=float), np.array(var, dtype=float))
+        _, _, info = ctx.sweep(1, commit=True)
+        self.last_info = info
+        if info:
+            raise np.linalg.LinAlgError(f'predict: the sweep met a non-positive pivot ({info}) in latent GP '
+                                        f'{ctx.last_info_gp}')
+        if not explicit:
+            self._mu, self._var = ctx.get_muvar()
+            self._mark_swept(nodes, weights, means, jitters)
+        return ctx
+
     def _stage_posterior(self, nodes, weights, means, jitters, tstar):
         """What predict_cov / sample_posterior hand the device before their call: the kernels (as _Prediction does), the
         host-evaluated matrices of user-defined kernels -- K + 1.25e-12 I, K*, k** and the whole K** -- the state and the
-        jitters.  Returns the context."""
+        jitters.  Returns the context.  The variational form: ``_variational_sweep``'s context (the jitters are the
+        sweep's)."""
+        if self._predict_form == 'variational':
+            return self._variational_sweep(nodes, weights, means, jitters)
         if self._mu is None and self._var is None:
             mu, var = self._initMuVar(nodes, weights, jitters)
         else:
@@ -976,6 +1135,7 @@ class inference:
             ctx.predict_upload(gp, self._tinyNuggetKMatrix(kernel, data_t),
                                self._predictKMatrix(kernel, tstar), self._kss_diagonal(kernel, tstar))
             ctx.predict_upload_kss(gp, self._tinyNuggetKMatrix(kernel, tstar))
+        self._send_predict_form(ctx)
         ctx.set_muvar(np.asarray(mu, dtype=float), np.asarray(var, dtype=float))
         ctx.set_jitters(np.asarray(jitters, dtype=float))
         return ctx
@@ -992,6 +1152,11 @@ class inference:
             Cov(y_i(t), y_k(t')) = sum_j w_ij w_kj' C_fj(t, t')                    (i != k, `joint` only)
 
         whose diagonal is _Prediction's variance, quirk included (jitter_i^2 added once per node).
+
+        The variational form (``predict='variational'``): C_g = K** - W W^T of the posterior the sweeps computed
+        (``_variational_sweep``: no sweep where the device still holds the stored state's), the set-up's nugget as
+        delta(t, t') -- between equal times of `tstar` too -- and ``jitter_i^2 delta(t, t')`` once instead of q times.
+        At the data times the latent matrices are the Sigma_g of the stored state.
 
         Returns (mean (N*, p), cov): cov (p, N*, N*), or (p N*, p N*) with `joint` (row i N* + t); with `separate` also
         the node covariances (q, N*, N*) and the weight covariances (q p, N*, N*), weight (j, i) at j p + i.
@@ -1021,6 +1186,7 @@ class inference:
         values used are left in ``self.last_nuggets``).  Output i is mean function_i + sum_j w_ij o f_j, and with `noise`
         also N(0, q jitter_i^2) per time (q: _Prediction's jitter counted once per node).  The first two moments of the
         draws are _Prediction's mean and variance.  The standard normals come from ``np.random.default_rng(rng)``.
+        The variational form (``predict='variational'``): predict_cov's C_g of that form, and `noise` is N(0, jitter_i^2).
 
         Returns draws (n, N*, p); with `separate` also the node draws (q, n, N*) and weight draws (q p, n, N*).
         """
@@ -1038,7 +1204,8 @@ class inference:
         meanVal = np.array(np.array_split(self._mean(means, tstar), p))
         draws = np.transpose(out, (1, 2, 0)) + meanVal.T[None]
         if noise:
-            sd = np.sqrt(q) * np.abs(np.asarray(jitters, dtype=float))
+            once = self._predict_form == 'variational'
+            sd = (1.0 if once else np.sqrt(q)) * np.abs(np.asarray(jitters, dtype=float))
             draws = draws + gen.standard_normal(draws.shape) * sd
         if separate:
             return draws, lat[:q], lat[q:]
@@ -1048,7 +1215,7 @@ class inference:
         """
         GPRN prediction at `tstar`, or on `nn` points spanning the data padded by
         20 % on each side (meanfield.py:1383-1400).  Returns (tstar, mean,
-        standard deviation, [node means, weight means]).
+        standard deviation, [node means, weight means]).  What is predicted follows ``predict_form`` (``_Prediction``).
         """
         if tstar is None:
             lo, hi = self.time.min(), self.time.max()
@@ -1316,9 +1483,12 @@ class inference:
         user-defined kernels, expressions that change shape between vectors, a sharded object, N > ``batch_max_N`` -- one
         ``_Prediction`` per vector, same return value.  Mean functions are evaluated per vector on the host.
 
+        Always the reference form of prediction: with ``predict='variational'`` this raises ``NotImplementedError``.
+
         Returns (mean (B, N*, p), variance (B, N*, p)) and, with `separate`, the latent means (B, G, N*): nodes first,
         then weight (j, i) at q + j p + i.
         """
+        self._refuse_variational_batch('predict_batch')
         assert self._components_set, _NOT_SET
         sets = [np.array(x, dtype=float) for x in parameter_sets]
         B = len(sets)
@@ -1361,6 +1531,13 @@ class inference:
         mean, var = np.array(means_), np.array(vars_)
         return (mean, var, np.array(lats)) if separate else (mean, var)
 
+    def _refuse_variational_batch(self, what):
+        if self._predict_form == 'variational':
+            raise NotImplementedError(
+                f"{what} is not available with predict='variational': the side-by-side evaluations keep no committed "
+                "sweep per vector.  The follow-up is a prediction pass at the end of a batch chunk, where the slabs still "
+                "hold each evaluation's X, as the gradient pass runs today; until then set predict_form = 'reference'")
+
     def posterior_predictive(self, parameter_sets, tstar=None, weights=None, **kw):
         """
         The first two moments of the mixture of ``predict_batch``'s predictions over `parameter_sets` -- the posterior
@@ -1368,6 +1545,7 @@ class inference:
         (B,): default uniform, normalised to sum 1.  Further keywords go to ``predict_batch`` (``states``, ``max_iter``).
         Returns (mean (N*, p), variance (N*, p)).
         """
+        self._refuse_variational_batch('posterior_predictive')
         kw.pop('separate', None)
         mean_b, var_b = self.predict_batch(parameter_sets, tstar=tstar, **kw)
         B = mean_b.shape[0]
@@ -1472,6 +1650,8 @@ class inference:
                 ctx.keep_sigma(False)
         self._mu, self._var = mu, var
         self.last_info = info
+        if fused:
+            self._mark_swept(nodes, weights, means, jitters)     # (gprn_grad_elbo keeps X, s and X^T X z)
         grads = np.array(grads)
         n_k = sum(k.pars.size for k in chain(nodes, weights))
         n_m = sum(0 if m_ is None else int(m_._parsize) for m_ in means)

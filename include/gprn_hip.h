@@ -466,6 +466,10 @@ int gprn_predict_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, i
  * release / acquire fences instead of the gfx942 / gfx950 shortcut documented in csrc/vecops.hip; same bits).
  * "elbo_form" (GPRN_ELBO_REFERENCE, the default, or GPRN_ELBO_BOUND: which function gprn_sweep, gprn_elbocalc and
  * gprn_elbocalc_batch report as the ELBO -- see the two constants below; any other value: GPRN_E_ARG).
+ * "predict_form" (GPRN_PREDICT_REFERENCE, the default, or GPRN_PREDICT_POSTERIOR: what gprn_predict, gprn_predict_cov and
+ * gprn_predict_draws compute -- see the two constants below; any other value: GPRN_E_ARG).
+ * "state_ready" (read-only: 1 while the X, s and X^T X z of a committed sweep are still in the workspaces -- what gprn_grad_elbo
+ * and the posterior form of prediction read; 0 after anything that stages another state or uses the workspaces).
  * value == -1 only reads; *old (may be
  * NULL) receives the previous value. */
 int gprn_set_option(gprn_ctx* ctx, const char* name, int value, int* old);
@@ -494,6 +498,39 @@ int gprn_set_option(gprn_ctx* ctx, const char* name, int value, int* old);
  * converged state that is the total derivative of the bound with respect to the kernel parameters (envelope theorem). */
 #define GPRN_ELBO_REFERENCE 0
 #define GPRN_ELBO_BOUND 1
+
+/* ---- the form of prediction (option "predict_form").
+ * GPRN_PREDICT_REFERENCE (default): the reference's _gp.GP.prediction, quirk for quirk -- per latent GP K + 1.25e-12 I + diag(v_g)
+ * with the variational variances as observation noise, factored in every call; the per-output combination of
+ * gprn_predict_cov adds jitter_i^2 once per node.  Every result keeps the bits it had.
+ * GPRN_PREDICT_POSTERIOR: the predictive distribution of the posterior the sweeps computed, q(f_g) = N(mu_g, Sigma_g) with
+ * Sigma_g = K - K S B^-1 S K.  With X = chol(B)^-1, S = diag(s), s = sqrt(d), and c = X^T X z as the last COMMITTED sweep left
+ * them (what gprn_grad_elbo reads):
+ *     mean*_g = K*_g S c          C*_g = K**_g - W W^T,   W = (X S K*_g^T)^T          var*_g = diag C*_g
+ * Nothing is filled at the data times and nothing is factored; a rectangular fill, one N^2 ns tile product and a row kernel run.
+ *   - The nugget is the set-up's: 1e-6 for the kernels in t_i - t_j, none for the two-argument ones (quirk Q9), not 1.25e-12.
+ *   - The nugget and WhiteNoise are delta(t, t'): in K* they are added exactly where t*_m == t_n (equality of the doubles given to
+ *     gprn_set_data and to the call), in k** always, in K** (covariances, draws) also between two equal prediction times.  So at a
+ *     data time the prediction IS the state the sweep left: (z - c) / s and (1 - colnorm^2) / d where the precision is positive,
+ *     the data mask's rows (csrc/mask.hip) where it is zero.  (Data times are taken to be distinct.)
+ *   - s is read per latent GP; s = 0 (a masked entry) gives a zero column.  Nothing is divided by s.
+ *   - gprn_predict_cov's per-output matrices carry jitter_i^2 delta(t, t') ONCE; every returned matrix is exactly symmetric.
+ * Validity: the three calls need a committed sweep right before them (gprn_sweep with commit = 1, gprn_elbocalc), as
+ * gprn_grad_elbo does -- GPRN_E_ARG "needs a committed sweep" otherwise.  They read the sweep's X, s and c and write only the
+ * prediction's own buffers: option "state_ready" stays 1, a second prediction at other times needs no new sweep, and a
+ * gprn_grad_elbo or gprn_sweep behind them returns the bits it would have returned without them.  What ends a committed sweep's
+ * validity is what stages another state or uses the workspaces (gprn_set_muvar, gprn_set_kernel / gprn_upload_K,
+ * gprn_factor_priors, gprn_set_mask, a sweep, the reference form of prediction, the batches).  gprn_set_y_resid and
+ * gprn_set_jitters do NOT: "state_ready" stays 1 behind them although the kept X, s and c belong to the residuals and jitters the
+ * sweep ran with -- the posterior form then predicts from that sweep (and gprn_grad_elbo differentiates it) without a message;
+ * sweep again after changing either.  Data masks, both sweep orders
+ * (with "order_mask"), both forms of the ELBO and both paths are served: all end in a committed sweep.
+ * GPRN_E_UNSUPPORTED with a message: the posterior form on a context with a communicator (and gprn_comm_init on a context in
+ * the posterior form); the three calls when a latent GP has no device program (gprn_upload_K; gprn_predict_upload* are not
+ * consulted).  Setting the option changes nothing on the device.  gprn_predict_batch ignores it: it always computes the
+ * reference form. */
+#define GPRN_PREDICT_REFERENCE 0
+#define GPRN_PREDICT_POSTERIOR 1
 
 /* ---- diagnostic entry points: one kernel each, for tests/test_kernels_gpu.py ----
  * C (+)= A.B on host matrices through the MFMA tile kernel; modes as in
