@@ -989,7 +989,8 @@ def test_overlap_modes_are_bit_identical():
     """What runs beside the factorisations instead of before / behind them (option "overlap": B formed inside the first
     panel's update, the row reductions over X panel by panel, the node term beside the weight phase, log det B inside
     k_finalize, a sweep's end beside the next sweep's node phase) changes WHEN kernels run, never a rounding: four forced
-    sweeps of an N = 4096, q = 2 problem (two outer-panel schedules per sweep, T = 32) give the same bits for every mask."""
+    sweeps of an N = 4096, q = 2 problem (two outer-panel schedules per sweep, T = 32) give the same bits for every mask.
+    Data masks, the sequential order, the bound form and the event schedule: tests/test_schedule_matrix_gpu.py."""
     N, p, q = 4096, 1, 2
     t, ys, es = synth.rv_series(N, p)
     spec = synth.component_spec(p, q, 'QuasiPeriodic')
