@@ -84,6 +84,8 @@ SIGNATURES = {
                             POINTER(c_int), _dp, _dp]),
     'gprn_elbocalc_batch_grad': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, _dp, POINTER(c_int),
                                  POINTER(c_int), POINTER(c_int), _dp, _dp, _dp]),
+    'gprn_elbocalc_batch_predict': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, _dp,
+                                            POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp, _dp]),
     'gprn_predict_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
     'gprn_test_predict_fill': (c_int, [c_void_p, c_int, c_int, _dp, c_int, _dp, c_int, c_int, c_int, _dp, _dp, _dp, _dp]),
     'gprn_elbocalc': (c_int, [c_void_p, c_int, _dp, _dp, _dp, _dp, c_int, _dp, c_int, POINTER(c_int), POINTER(c_int),
@@ -499,6 +501,54 @@ class Context:
         if want_grad:
             out += (grads,)
         return out
+
+    def elbocalc_batch_predict(self, kernel_params, y_resid, jitters, mu, var, max_iter, tstar, forced=False, latent=True,
+                               outputs=True):
+        """B independent ELBOcalc loops side by side, each followed by the prediction of the posterior it leaves
+        (gprn_elbocalc_batch_predict): the arrays of ``elbocalc_batch``, tstar (n*).  Returns (elbo, iterations, converged,
+        info, mu_out, var_out, lat_mean, lat_var, out_mean, out_var): the first six what ``elbocalc_batch(want_state=True)``
+        returns, to the bit; the latent rows (B, G, n*) -- row b what ``predict()`` returns in the posterior form right after
+        ``elbocalc`` ran vector b's loop alone from (mu_b, var_b) -- or None without `latent`; the per-output combination
+        with the jitter once and without the mean functions, (B, p, n*), or None without `outputs`.  Rows of an evaluation
+        with info > 0 are NaN.  forced (GPRN_BATCH_FORCED): no stop rule, exactly max_iter committed sweeps each.  None
+        where the library has no side-by-side form for this problem."""
+        if not (latent or outputs):
+            raise ValueError('elbocalc_batch_predict: ask for the latent pair, the output pair or both')
+        kp = _f64(kernel_params)
+        if kp.ndim != 2 or kp.shape[0] < 1:
+            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        B = kp.shape[0]
+        d = (self.p + 1) * self.q * self.N
+        yr, jt, m0, v0 = _f64(y_resid), _f64(jitters), _f64(mu), _f64(var)
+        if yr.size != B * self.p * self.N:
+            raise ValueError(f'y_resid must be (B, p, N) = ({B}, {self.p}, {self.N}), got {yr.shape}')
+        if jt.size != B * self.p:
+            raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
+        if m0.size != B * d or v0.size != B * d:
+            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
+        ts = _f64(np.ravel(tstar))
+        if ts.size < 1:
+            raise ValueError('tstar is empty')
+        if int(max_iter) < 1:
+            raise ValueError('elbocalc_batch_predict: a prediction needs a committed sweep (max_iter >= 1)')
+        ns = ts.size
+        elbo = np.empty(B)
+        it, cv, info = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        mo, vo = np.empty((B, d)), np.empty((B, d))
+        lm = np.empty((B, self.G, ns)) if latent else None
+        lv = np.empty((B, self.G, ns)) if latent else None
+        om = np.empty((B, self.p, ns)) if outputs else None
+        ov = np.empty((B, self.p, ns)) if outputs else None
+        ip = lambda a: a.ctypes.data_as(POINTER(c_int))
+        opt = lambda a: None if a is None else _ptr(a)
+        rc = self._lib.gprn_elbocalc_batch_predict(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
+                                                   int(max_iter), GPRN_BATCH_FORCED if forced else 0, ns, _ptr(ts), _ptr(elbo),
+                                                   ip(it), ip(cv), ip(info), _ptr(mo), _ptr(vo), opt(lm), opt(lv), opt(om), opt(ov))
+        if rc == GPRN_E_UNSUPPORTED:
+            return None
+        self._check(rc, 'elbocalc_batch_predict')
+        shape = (B, self.p + 1, self.q, self.N)
+        return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), lm, lv, om, ov)
 
     def predict_batch(self, kernel_params, mu, var, tstar, jitters=None, latent=True, outputs=True):
         """gprn_predict for B parameter vectors side by side (gprn_predict_batch): kernel_params (B, n_kpar), mu / var (B, d)

@@ -771,19 +771,21 @@ size_t batch_budget_bytes(gprn_ctx* c)
 // B independent evaluations of the loop above, side by side on the device: see include/gprn_hip.h.  One-tile problems run a
 // half-sweep of ALL evaluations as one launch (smalln.hip); larger ones go through the launch schedule with
 // batch = evaluations x latent GPs (midn.hip).  Either way a list longer than the memory budget holds runs chunk by chunk.
-extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
-                                        const double* y_resid, const double* jitters, const double* mu, const double* var,
-                                        int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
-                                        double* mu_out, double* var_out, double* grad_out)
+// pred: the prediction each chunk ends with (gprn_elbocalc_batch_predict), or null
+static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                               const double* y_resid, const double* jitters, const double* mu, const double* var,
+                               int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
+                               double* mu_out, double* var_out, double* grad_out, const BatchPred* pred)
 {
-    DeviceLock lock_(c);
     if (!c || !c->N || n_eval < 1 || !kernel_params || !y_resid || !jitters || !mu || !var || max_iter < 0 || !elbo ||
         !iterations || !converged || !info || (!mu_out != !var_out) || (flags & ~GPRN_BATCH_FORCED))
         return bad(c, "elbocalc_batch: bad argument");
     if (grad_out && max_iter < 1) return bad(c, "elbocalc_batch_grad: a gradient needs a committed sweep (max_iter >= 1)");
     // (side by side every evaluation starts from one shared state: under a mask that is the caller's choice, option "batch_mask")
     if (c->d_mask && !c->batch_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
-    c->grad_ready = false;
+    // (a prediction's call reads what the loops left in the batch's own buffers and writes nothing of the context's: a committed
+    // sweep of the context stays what it was, as under gprn_predict_batch)
+    if (!pred) c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "elbocalc_batch: call set_owners first");
     if (comm_active(c) || c->world != 1) { c->err = "elbocalc_batch: one rank only (a pool of ranks splits the list itself)"; return GPRN_E_UNSUPPORTED; }
@@ -797,10 +799,44 @@ extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* k
     int cap = 0;
     TRY(batch_reserve(c, small ? small_batch_reserve : mid_batch_reserve, n_eval, &cap));
     const BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info,
-                     mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N, flags, grad_out};
-    // (with grad_out each chunk ends with the gradient pass of its evaluations, before the next chunk overwrites the slabs)
+                     mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N, flags, grad_out,
+                     pred ? *pred : BatchPred{}};
+    // (with grad_out each chunk ends with the gradient pass of its evaluations, before the next chunk overwrites the slabs;
+    // with a prediction, with the prediction pass)
     for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(run(c, io.slice(e0, std::min(cap, n_eval - e0))));
     return GPRN_OK;
+}
+
+extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                        const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                        int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
+                                        double* mu_out, double* var_out, double* grad_out)
+{
+    DeviceLock lock_(c);
+    return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
+                               iterations, converged, info, mu_out, var_out, grad_out, nullptr);
+}
+
+// gprn_elbocalc_batch_grad(grad_out = NULL) with, per evaluation, gprn_predict's posterior form at the end of its loop (include/
+// gprn_hip.h): the reference's _Prediction (meanfield.py:1289-1381) once per kept vector, behind nELBO -- each chunk ends with
+// midn.hip's batch_pred_pass over what its loops left in the slabs
+extern "C" int gprn_elbocalc_batch_predict(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                           const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                           int max_iter, int flags, int ns, const double* tstar,
+                                           double* elbo, int* iterations, int* converged, int* info,
+                                           double* mu_out, double* var_out,
+                                           double* lat_mean, double* lat_var, double* out_mean, double* out_var)
+{
+    DeviceLock lock_(c);
+    WatchScope watch_(c, "gprn_elbocalc_batch_predict");
+    if (!c || !c->N) return bad(c, "elbocalc_batch_predict: bad argument");
+    if (ns < 1 || !tstar) return bad(c, "elbocalc_batch_predict: ns >= 1 prediction times expected");
+    if (max_iter < 1) return bad(c, "elbocalc_batch_predict: a prediction needs a committed sweep (max_iter >= 1)");
+    if ((!lat_mean != !lat_var) || (!out_mean != !out_var)) return bad(c, "elbocalc_batch_predict: each pair is both or neither NULL");
+    if (!lat_mean && !out_mean) return bad(c, "elbocalc_batch_predict: neither the latent nor the output pair was asked for");
+    const BatchPred pred{ns, tstar, lat_mean, lat_var, out_mean, out_var, c->G, c->p};
+    return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
+                               iterations, converged, info, mu_out, var_out, nullptr, &pred);
 }
 
 extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,

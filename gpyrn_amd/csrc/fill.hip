@@ -727,3 +727,118 @@ int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
 }
+
+// ---- ... in the POSTERIOR form (gprn_elbocalc_batch_predict: the prediction pass behind a chunk's loop, midn.hip
+// batch_pred_pass): K* diag(s) and k** of many matrices, matrix z with its own program and its own s = sqrt(d) at s + z * ld.
+// The delta handling of k_fill_rect<KID, true>: the nugget and WhiteNoise apply in K* exactly where t*_i == t_n as doubles,
+// in k** always; column ld of a row group (one thread of an extra workgroup) is k**, so the element code has ONE call site
+// for both.  A point of zero precision has s = 0: a zero column, nothing is divided.  Rows [ns, ns_pad) and columns [N, ld)
+// are zeros.  A thread one column, consecutive threads consecutive columns: a row goes out as 2 KiB contiguous.
+// Two instruction streams in two kernels, so that neither carries the other's registers (k_fill_rect_batch, which holds all
+// four behind one switch, spills): PROGRAM = false -- the one-kernel SE / Periodic / QP programs, parameters and host-computed
+// reciprocals in registers behind the uniform branch, GPRN_RECT_ROWS rows per thread; PROGRAM = true -- everything else
+// through the postfix program, ONE row per thread as k_fill_rect<-1, true> takes it (with a row loop around the program's
+// stack the compiler reserves scratch).  A workgroup whose matrix belongs to the other kernel returns at once (uniform: it
+// reads the program's head through scalar loads); the host launches only the kernels its programs need.  The program comes
+// into LDS once per workgroup.
+template <int KID, int ROWS>
+__device__ __forceinline__ void fill_rect_batch_rows_post(const FillProgram& pg, const double* __restrict__ ts, int ns, int ns_pad,
+                                                          const double* __restrict__ t, int N, int ld,
+                                                          const double* __restrict__ s, double* __restrict__ Ks,
+                                                          double* __restrict__ kss)
+{
+    double par[4] = {0.0, 0.0, 0.0, 0.0}, aux[3] = {0.0, 0.0, 0.0};
+    if (KID >= 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) par[i] = pg.par[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) aux[i] = pg.aux[i];
+    }
+    const int nugget = pg.nugget;
+    const double nugget_val = pg.nugget_val;
+    auto eval = [&](double ti, double tj, bool diag) {
+        if constexpr (KID >= 0) return eval_kernel(KID, par, ti, tj, diag, aux);
+        else return eval_program(pg, ti, tj, diag);
+    };
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int i0 = blockIdx.y * ROWS;
+    if (n > ld) return;
+    const bool is_kss = n == ld;
+    const double tn = (n < N) ? t[n] : 0.0;
+    const double sn = (n < N) ? s[n] : 0.0;
+#pragma unroll 1
+    for (int r = 0; r < ROWS; ++r) {
+        const int i = i0 + r;
+        if (i >= ns_pad) break;
+        double v = 0.0;
+        if (i < ns && (n < N || is_kss)) {
+            const double ti = ts[i], tj = is_kss ? ti : tn;
+            const bool same = ti == tj;
+            v = eval(ti, tj, same);
+            if (same && nugget) v += nugget_val;
+        }
+        if (!is_kss) Ks[(size_t)i * ld + n] = v * sn;
+        else if (i < ns) kss[i] = v;
+    }
+}
+
+// does this program run on the register form (a single SE, Periodic or QP kernel)?
+static __host__ __device__ __forceinline__ bool program_in_registers(const FillProgram& pg)
+{
+    if (!(pg.n_ops == 1 && pg.ops[0] == GPRN_OP_PUSH && pg.ops[2] == 0)) return false;
+    return pg.ops[1] == GPRN_K_SE || pg.ops[1] == GPRN_K_PERIODIC || pg.ops[1] == GPRN_K_QP;
+}
+
+// grid (ceil((ld + 1) / 256), ceil(ns_pad / rows per thread), matrices)
+template <bool PROGRAM>
+__global__ __launch_bounds__(256)
+void k_fill_rect_batch_post(const FillProgram* __restrict__ pgs, const double* __restrict__ ts, int ns, int ns_pad,
+                            const double* __restrict__ t, int N, int ld, const double* __restrict__ s,
+                            double* const* __restrict__ Kss, double* __restrict__ kss, size_t kss_stride)
+{
+    if (program_in_registers(pgs[blockIdx.z]) == PROGRAM) return;     // (the other kernel's matrix: uniform)
+    __shared__ FillProgram spg;
+    {
+        const int* src = reinterpret_cast<const int*>(pgs + blockIdx.z);
+        int* dst = reinterpret_cast<int*>(&spg);
+        for (int i = threadIdx.x; i < (int)(sizeof(FillProgram) / sizeof(int)); i += 256) dst[i] = src[i];
+    }
+    __syncthreads();
+    double* const Ks = Kss[blockIdx.z];
+    double* const kd = kss + (size_t)blockIdx.z * kss_stride;
+    const double* const sz = s + (size_t)blockIdx.z * ld;
+    if constexpr (PROGRAM) fill_rect_batch_rows_post<-1, 1>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd);
+    else
+        switch (spg.ops[1]) {                    // (uniform per workgroup: a scalar branch)
+        case GPRN_K_SE: fill_rect_batch_rows_post<GPRN_K_SE, GPRN_RECT_ROWS>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd); break;
+        case GPRN_K_PERIODIC: fill_rect_batch_rows_post<GPRN_K_PERIODIC, GPRN_RECT_ROWS>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd); break;
+        default: fill_rect_batch_rows_post<GPRN_K_QP, GPRN_RECT_ROWS>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd);
+        }
+}
+
+// ns <= ns_pad <= ld rows (ns_pad a multiple of 128) of n_matrices matrices: K* diag(s) into d_Ks[i], k** into
+// kss + i * kss_stride; s: [n_matrices][ld]; h_programs: the host image of d_programs
+int launch_fill_rect_batch_post(gprn_ctx* c, const void* d_programs, const char* h_programs, double* const* d_Ks, int n_matrices,
+                                const double* d_tstar, int ns, int ns_pad, const double* s, double* kss, size_t kss_stride)
+{
+    if (n_matrices <= 0) return GPRN_OK;
+    bool any[2] = {false, false};                // [0]: the register form, [1]: the postfix program
+    for (int i = 0; i < n_matrices && !(any[0] && any[1]); ++i) {
+        FillProgram pg;
+        memcpy(&pg, h_programs + (size_t)i * sizeof(FillProgram), sizeof(pg));
+        any[program_in_registers(pg) ? 0 : 1] = true;
+    }
+    prof_begin(c, GPRN_T_FILL);
+    const unsigned gx = (c->ld + 1 + 255) / 256;             // (column ld: k**)
+    if (any[0])
+        hipLaunchKernelGGL(k_fill_rect_batch_post<false>, dim3(gx, (ns_pad + GPRN_RECT_ROWS - 1) / GPRN_RECT_ROWS, n_matrices),
+                           dim3(256), 0, c->stream, (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time,
+                           c->N, c->ld, s, d_Ks, kss, kss_stride);
+    if (any[1])
+        hipLaunchKernelGGL(k_fill_rect_batch_post<true>, dim3(gx, ns_pad, n_matrices), dim3(256), 0, c->stream,
+                           (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time, c->N, c->ld, s, d_Ks,
+                           kss, kss_stride);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}

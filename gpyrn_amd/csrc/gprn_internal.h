@@ -353,6 +353,10 @@ int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, 
 // K* (ns rows, zero-padded to ns_pad <= ld) and k** of many matrices at the same prediction times in one launch
 int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* d_tstar,
                            int ns, int ns_pad, double* kss, size_t kss_stride);
+// ... in the posterior form (launch_fill_rect_post's element code): K* diag(s) with matrix i's s at s + i * ld, the nugget and
+// WhiteNoise as delta(t, t'); h_programs: the programs' host image
+int launch_fill_rect_batch_post(gprn_ctx* c, const void* d_programs, const char* h_programs, double* const* d_Ks, int n_matrices,
+                                const double* d_tstar, int ns, int ns_pad, const double* s, double* kss, size_t kss_stride);
 int launch_fill_rect(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
                      int ns, int ns_pad, double* Ks, double* kss);
 // the posterior form of prediction (option "predict_form"): K* diag(s) and k**, the nugget and WhiteNoise as delta(t, t') --
@@ -537,6 +541,19 @@ struct SmallLoop { int* ctl; double *hist, *last3; int sweep, hist_at, max_iter;
 // mu^T K^-1 mu, Q1 traces, ELBO assembly of the sweep whose new state is (mu, var); loop: the stop rule too, or null
 int small_tail(gprn_ctx* c, double* out4, double* scal, const double* mu, const double* var, const SmallLoop* loop = nullptr);
 int small_prior(gprn_ctx* c, double** d_tab, const int* d_job_gp, double** d_kinv_out, int njobs, int* d_info);
+// The prediction a chunk of gprn_elbocalc_batch_predict ends with: ns times (0: none asked for), the caller's rows of its
+// evaluations -- lat_* [n][G][ns], out_* [n][p][ns], each pair both or neither
+struct BatchPred {
+    int ns = 0; const double* tstar = nullptr;
+    double *lat_mean = nullptr, *lat_var = nullptr, *out_mean = nullptr, *out_var = nullptr;
+    int G = 0, p = 0;
+    BatchPred from(int e0) const               // evaluations [e0, ...)
+    {
+        const size_t lat = (size_t)e0 * G * ns, out = (size_t)e0 * p * ns;
+        return BatchPred{ns, tstar, lat_mean ? lat_mean + lat : nullptr, lat_var ? lat_var + lat : nullptr,
+                         out_mean ? out_mean + out : nullptr, out_var ? out_var + out : nullptr, G, p};
+    }
+};
 // One call of gprn_elbocalc_batch -- its pointers and counts -- or a run of its evaluations (slice)
 struct BatchIo {
     int n; const double* kparams; int n_kpar; const double *y_resid, *jitters, *mu, *var; int max_iter;
@@ -544,12 +561,13 @@ struct BatchIo {
     int p; size_t state, yv;               // per evaluation: jitters, doubles of mu / var, doubles of y_resid
     int flags;                             // GPRN_BATCH_FORCED: no stop rule, max_iter committed trips each
     double* grad_out;                      // [n][n_kpar]: the gradient of each evaluation's last committed sweep, or null
+    BatchPred pred{};                      // gprn_elbocalc_batch_predict: the prediction pass behind the chunk's loop (ns = 0: none)
     BatchIo slice(int e0, int ne) const    // evaluations [e0, e0 + ne)
     {
         return BatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, y_resid + e0 * yv, jitters + (size_t)e0 * p, mu + e0 * state,
                        var + e0 * state, max_iter, elbo + e0, iters + e0, conv + e0, info + e0,
                        mu_out ? mu_out + e0 * state : nullptr, var_out ? var_out + e0 * state : nullptr, p, state, yv,
-                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr};
+                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0)};
     }
 };
 // grad.hip: the steps of gprn_grad_elbo over the evaluations of a batch's chunk whose loops have ended, slots = evaluations x
@@ -575,6 +593,30 @@ struct GradBatchIn {
 // take -- beyond it (or when the device refuses) the evaluations go in groups; GPRN_E_NOMEM when one evaluation's scratch does
 // not fit.  The scratch is an allocation class of its own: the drivers give it what the chunk's slabs left of the budget
 int grad_batch_pass(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const GradBatchIn& in, size_t budget);
+// midn.hip: the prediction pass behind a chunk's loop (gprn_elbocalc_batch_predict), for both drivers -- the posterior form of
+// gprn_predict (api_more.hip) over slots = evaluations x latent GPs in the set-up's order (slot = evaluation * G + latent GP),
+// t* in blocks of at most ld rows: the batched posterior fill, (K* S) X^T by the tile kernel, the row kernel, the jitter-once
+// combination, the block's rows through a pinned buffer into the caller's rows.  The driver says where each slot's X lies and which two ld x ld
+// buffers per slot the loop has finished with; evaluations whose info > 0 get NaN rows.
+struct PredPassIn {
+    int n, G, p, N, ld, T;                 // evaluations of the launches, the problem's geometry
+    double** tab;                          // device [n G][GPRN_NBUF]: BUF_X = X (read), BUF_K = a block of K* S, BUF_KLINV = of W^T
+    double* const* kptr;                   // device [n G]: the BUF_K pointers again (where the fill writes)
+    const void* d_programs;                // device [n G] fill programs (the set-up's: they carry the sweeps' nugget)
+    const char* h_programs;                // ... and their staged host image (which instruction streams the fill needs)
+    const double *s, *ct;                  // device [n G][ld]: sqrt(d) and X^T X z of each slot's last committed sweep
+    double *kss, *lmean, *lvar;            // device [n G][ld]: a block's k**, latent means and variances
+    double *omean, *ovar;                  // device [n p][ld]: a block's outputs
+    const double* jitters;                 // host [n][p]
+    const int* info;                       // host [n]
+    // the pass's own small buffers, kept by the driver between calls (a call allocates and frees nothing on the device):
+    double *d_ts, *d_jit;                  // device: ns prediction times, n p jitters
+    const TileTask* d_tasks;               // device: pred_pass_tasks(T), uploaded once
+    double* pin;                           // pinned host: a block's rows on their way out, 2 (n G + n p) ld doubles
+};
+int batch_pred_pass(gprn_ctx* w, const PredPassIn& in, const BatchPred& out);
+// W^T = (K* S) X^T over T x T tiles, row block by row block: a ragged last block of t* runs a prefix of the list
+std::vector<TileTask> pred_pass_tasks(int T, int ld);
 // What both drivers of gprn_elbocalc_batch ask of the caller's kernels and kernel_params (api_sweep.hip)
 int batch_validate(gprn_ctx* c, int n_kpar);
 // GPRN_BATCH_TIMERS=1 (probes): where the host's time of a chunk goes -- staging, enqueue, waits, read-back -- on stderr

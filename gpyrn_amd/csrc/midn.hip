@@ -24,6 +24,11 @@
 // per (evaluation, latent GP) behind each group of sweeps (k_mid_keep_s: reads only, the values' bits do not change).  The pass's
 // scratch is an allocation of its own (gprn_ctx::grad_scratch of the worker) that takes what the slabs left of the budget.
 //
+// With a prediction asked for (gprn_elbocalc_batch_predict) a chunk ends with batch_pred_pass over its evaluations -- the
+// posterior form of gprn_predict, from the X, s = sqrt(d) and ct = X^T X z each evaluation's last committed sweep left: ct is
+// kept beside s (keep_ct), and the pass's two ld x ld buffers per slot are slabs the loop has finished with (a block of K* S
+// in the B workspace, of (K* S) X^T in K) through a pointer table of its own -- no new ld x ld allocation.
+//
 // PREDICTION for many parameter vectors (gprn_predict_batch: mid_predict_chunk, at the end of this file) walks gprn_predict's
 // steps over the same slot table, in the same slabs, at every T >= 1: B holds K + 1.25e-12 I + diag v and then its factor, X
 // its inverse, K and KL a block of K* and of (X K*^T)^T.
@@ -60,6 +65,12 @@ struct MidBatch {
     double *Kinv = nullptr;           // [cap][q - 1][ld * ld]: K_j^-1 (lower), j = 1 .. q - 1 (quirk Q1: not in the bound form of the ELBO)
     double *q1_scratch = nullptr;     // [cap q (q - 1) / 2][ld]
     double *keep_s = nullptr;         // [cap][G][ld]: s of each evaluation's last sweep, there from the first call that asks for gradients
+    double *keep_ct = nullptr;        // [cap][G][ld]: ct = X^T X z likewise, from the first call that asks for a prediction
+    double **pass_tab = nullptr;      // [cap G][GPRN_NBUF], device: the prediction pass's rows (X; K* S in Bw, its W^T in K), likewise
+    double *pass_jit = nullptr, *pass_ts = nullptr;   // [cap p] jitters, [pass_ns] prediction times (it only grows)
+    TileTask* pass_tasks = nullptr;   // pred_pass_tasks(T)
+    int pass_ns = 0;
+    double* pass_pin = nullptr;       // pinned: a block's rows on their way to the caller, 2 cap (G + p) ld doubles
     char* programs = nullptr;         // [cap][G] fill programs
     // tables and pinned blocks, each laid out by its one function of batch_layout.h
     MidPtrTab dp{};                   // device pointer tables (one allocation)
@@ -363,8 +374,30 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
     std::vector<ElboLoop> loops(B);
     const bool forced = (io.flags & GPRN_BATCH_FORCED) != 0;
     // gradients: s of every (evaluation, latent GP) as its last sweep left it (G ld doubles per evaluation beside the slabs)
-    if (io.grad_out && !m->keep_s) TRY(m->own.alloc(c, &m->keep_s, (size_t)m->cap * G * m->ld));
-    double* const keep_s = io.grad_out ? m->keep_s : nullptr;
+    const bool predict = io.pred.ns > 0;
+    if ((io.grad_out || predict) && !m->keep_s) TRY(m->own.alloc(c, &m->keep_s, (size_t)m->cap * G * m->ld));
+    double* const keep_s = io.grad_out || predict ? m->keep_s : nullptr;
+    // a prediction: ct = X^T X z too, and the pass's pointer rows -- X where the sweeps leave it, the two blocks in slabs the
+    // loop has finished with when the pass runs (B's workspace and the prior's K; the next chunk's set-up refills both)
+    if (predict && !m->keep_ct) TRY(m->own.alloc(c, &m->keep_ct, (size_t)m->cap * G * m->ld));
+    if (predict && !m->pass_tab) {
+        const size_t nslot = (size_t)m->cap * G, nn = (size_t)m->ld * m->ld;
+        std::vector<double*> rows(nslot * GPRN_NBUF);
+        for (size_t sl = 0; sl < nslot; ++sl)
+            buf_row(&rows[sl * GPRN_NBUF], m->Bw + sl * nn, m->Xw + sl * nn, m->Bw + sl * nn, m->K + sl * nn);
+        TRY(m->own.alloc(c, &m->pass_tab, rows.size()));
+        HIP_TRY(c, hipMemcpy(m->pass_tab, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice));
+        const std::vector<TileTask> tasks = pred_pass_tasks(w->T, m->ld);
+        TRY(m->own.alloc(c, &m->pass_tasks, tasks.size()));
+        HIP_TRY(c, hipMemcpy(m->pass_tasks, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice));
+        TRY(m->own.alloc(c, &m->pass_jit, (size_t)m->cap * p));
+        TRY(m->own.pin(c, &m->pass_pin, 2 * (size_t)m->cap * (G + p) * m->ld * sizeof(double)));
+    }
+    if (predict && io.pred.ns > m->pass_ns) {           // (a longer t* than any before: a new array; the old one goes with the batch)
+        TRY(m->own.alloc(c, &m->pass_ts, (size_t)io.pred.ns));
+        m->pass_ns = io.pred.ns;
+    }
+    double* const keep_ct = predict ? m->keep_ct : nullptr;
     int trips = 0;                                       // (forced: every running evaluation has made this many)
     bool tables_stale = true, first = true;
     while (!act.empty()) {
@@ -386,6 +419,11 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
                 const Phase ph = mid_phase(w, m, wt != 0, nA);
                 hipLaunchKernelGGL(k_mid_keep_s, dim3(ph.nslots), dim3(256), 0, st, (const double*)(w->d_s + (size_t)ph.slot0 * ph.ld),
                                    ph.slot_gp, ph.ev.slot_eval, G, ph.ld, keep_s);
+                // (the ct kept is the one the group's last sweep ends with: in the sequential order the one its refresh
+                // rewrote, under a mask the one mask_rows read -- both run inside phase_core, ahead of this launch on this stream)
+                if (keep_ct)
+                    hipLaunchKernelGGL(k_mid_keep_s, dim3(ph.nslots), dim3(256), 0, st, (const double*)(w->d_ct + (size_t)ph.slot0 * ph.ld),
+                                       ph.slot_gp, ph.ev.slot_eval, G, ph.ld, keep_ct);
             }
             prof_end(w);
             HIP_TRY(w, hipGetLastError());
@@ -461,10 +499,92 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
         TRY(grad_batch_pass(w, c->kspec, in, grad_batch_left(c, (size_t)m->cap * mid_bytes_per_eval(c))));
     }
     const double us_grad = t.lap();
+    if (predict) {
+        // ---- the prediction of every evaluation's last committed sweep, over the full chunk in the set-up's order
+        const PredPassIn in{B, G, p, N, m->ld, w->T, m->pass_tab, (double* const*)m->dp.kptr2, m->programs, m->in.programs,
+                            keep_s, keep_ct, w->d_d, w->d_pred, w->d_s, w->d_z, w->d_cs, io.jitters, io.info,
+                            m->pass_ts, m->pass_jit, m->pass_tasks, m->pass_pin};
+        TRY(batch_pred_pass(w, in, io.pred));
+    }
+    const double us_pred = t.lap();
     if (batch_timers_on())
         fprintf(stderr, "[gprn] elbocalc_batch (N = %d, T = %d), %d evaluations, us: staging %.0f | set-up enqueued %.0f | %d sweeps: enqueue %.0f, "
-                        "waiting for the device %.0f, verdicts %.0f | states back %.0f | gradient pass %.0f | total %.0f\n", N, w->T, B, us_stage, us_setup, n_sweeps,
-                us_enqueue, us_wait, us_host, us_states, us_grad, t.total());
+                        "waiting for the device %.0f, verdicts %.0f | states back %.0f | gradient pass %.0f | prediction pass %.0f | total %.0f\n", N, w->T, B, us_stage, us_setup, n_sweeps,
+                us_enqueue, us_wait, us_host, us_states, us_grad, us_pred, t.total());
+    return GPRN_OK;
+}
+
+// The prediction pass of both drivers (gprn_internal.h PredPassIn): gprn_predict's posterior form (api_more.hip predict_impl)
+// with batch = evaluations x latent GPs.  Launches per block of at most ld prediction times: the posterior fill (one per
+// instruction stream its programs need: one or two), one tile product, one row kernel and, for the out_* pair, the
+// combination, then the block's rows back.  The rows go through a PINNED buffer of the driver's and from there, row by
+// row, into the caller's arrays -- not straight into them: a pitched device-to-host copy into pageable memory makes the
+// runtime register the caller's pages, and when the caller frees such an array (a NumPy result dropped) the process's
+// queues are evicted and restored, which stalled the sweeps of the NEXT batch call by 10-25 ms.  Per call one copy of t* and of the jitters.  Nothing is filled at the data times, nothing is factored, and
+// nothing is allocated or freed on the device: t*, the jitters and the task list live in buffers the driver keeps.  Reads X,
+// s, ct and the programs; writes the two blocks and the per-slot rows it was given.
+std::vector<TileTask> pred_pass_tasks(int T, int ld)
+{
+    std::vector<TileTask> tasks;
+    for (int bt = 0; bt < T; ++bt)
+        for (int at = 0; at < T; ++at)
+            tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE, (int64_t)bt * GPRN_TILE * ld,
+                                     (int64_t)at * GPRN_TILE * ld, (at + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_X,
+                                     tile_modes(CM_SET, 0, 0)});
+    return tasks;
+}
+
+int batch_pred_pass(gprn_ctx* w, const PredPassIn& in, const BatchPred& out)
+{
+    const int B = in.n, G = in.G, p = in.p, ld = in.ld, T = in.T, ns = out.ns, nslots = B * G;
+    hipStream_t st = w->stream;
+    double *const d_ts = in.d_ts, *const d_jit = in.d_jit;
+    const TileTask* const d_t = in.d_tasks;
+    HIP_TRY(w, hipMemcpyAsync(d_ts, out.tstar, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, st));
+    if (out.out_mean)
+        HIP_TRY(w, hipMemcpyAsync(d_jit, in.jitters, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, st));
+    const Phase pass{in.tab, nullptr, nslots, 0, nullptr, EvalMap{nullptr, 0, 0, 0, 0}, in.N, ld, T};
+    const size_t row = sizeof(double), n_lat = (size_t)nslots * ld, n_out = (size_t)B * p * ld;
+    double *const pin_lm = in.pin, *const pin_lv = pin_lm + n_lat, *const pin_om = pin_lv + n_lat, *const pin_ov = pin_om + n_out;
+    for (int t0 = 0; t0 < ns; t0 += ld) {
+        const int nsb = std::min(ld, ns - t0), nsb_pad = ((nsb + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+        TRY(launch_fill_rect_batch_post(w, in.d_programs, in.h_programs, in.kptr, nslots, d_ts + t0, nsb, nsb_pad, in.s, in.kss, ld));
+        TRY(launch_tiles(w, d_t, (size_t)(nsb_pad / GPRN_TILE) * T, pass.ptrs, nslots, ld, GPRN_T_UPDATE));
+        TRY(vec_pred_rows(w, pass, nsb, ld, in.ct, in.kss, in.lmean, in.lvar));
+        if (out.lat_mean) {
+            HIP_TRY(w, hipMemcpyAsync(pin_lm, in.lmean, n_lat * row, hipMemcpyDeviceToHost, st));
+            HIP_TRY(w, hipMemcpyAsync(pin_lv, in.lvar, n_lat * row, hipMemcpyDeviceToHost, st));
+        }
+        if (out.out_mean) {
+            TRY(vec_predict_outputs(w, B, nsb, ld, in.lmean, in.lvar, d_jit, in.omean, in.ovar, true));
+            HIP_TRY(w, hipMemcpyAsync(pin_om, in.omean, n_out * row, hipMemcpyDeviceToHost, st));
+            HIP_TRY(w, hipMemcpyAsync(pin_ov, in.ovar, n_out * row, hipMemcpyDeviceToHost, st));
+        }
+        // (the next block rewrites the rows these copies read)
+        HIP_TRY(w, hipStreamSynchronize(st));
+        if (out.lat_mean)
+            for (int r = 0; r < nslots; ++r) {
+                memcpy(out.lat_mean + (size_t)r * ns + t0, pin_lm + (size_t)r * ld, nsb * row);
+                memcpy(out.lat_var + (size_t)r * ns + t0, pin_lv + (size_t)r * ld, nsb * row);
+            }
+        if (out.out_mean)
+            for (int r = 0; r < B * p; ++r) {
+                memcpy(out.out_mean + (size_t)r * ns + t0, pin_om + (size_t)r * ld, nsb * row);
+                memcpy(out.out_var + (size_t)r * ns + t0, pin_ov + (size_t)r * ld, nsb * row);
+            }
+    }
+    // an evaluation whose pivot failed: NaN in all of its rows (its X holds whatever the failed factorisation left)
+    for (int b = 0; b < B; ++b) {
+        if (in.info[b] <= 0) continue;
+        if (out.lat_mean) {
+            std::fill(out.lat_mean + (size_t)b * G * ns, out.lat_mean + (size_t)(b + 1) * G * ns, NAN);
+            std::fill(out.lat_var + (size_t)b * G * ns, out.lat_var + (size_t)(b + 1) * G * ns, NAN);
+        }
+        if (out.out_mean) {
+            std::fill(out.out_mean + (size_t)b * p * ns, out.out_mean + (size_t)(b + 1) * p * ns, NAN);
+            std::fill(out.out_var + (size_t)b * p * ns, out.out_var + (size_t)(b + 1) * p * ns, NAN);
+        }
+    }
     return GPRN_OK;
 }
 

@@ -644,6 +644,15 @@ struct SmallBatchMem {
     double* mask_wc = nullptr;        // [cap][ne node + ne weight][2][128 * ld]
     MaskLane* mask_lanes = nullptr;   // [2 parity][cap ne node | cap ne weight], evaluation-major
     double** mask_tab = nullptr;      // [cap ne node | cap ne weight][GPRN_NBUF]
+    // a prediction behind the loop (gprn_elbocalc_batch_predict), there from the first call that asks for one: the pass's
+    // pointer rows (X; a block of K* S in the B workspace, of its W^T in K), where its fill writes, and its vectors
+    double** pred_tab = nullptr;      // [cap G][GPRN_NBUF]
+    double** pred_kptr = nullptr;     // [cap G]
+    double* pred_vecs = nullptr;      // [7][cap G ld]: s, ct (gathered from vecs), k**, latent means and variances, outputs (twice cap p ld)
+    double *pred_jit = nullptr, *pred_ts = nullptr;   // [cap p] jitters, [pred_ns] prediction times (it only grows)
+    TileTask* pred_tasks = nullptr;   // pred_pass_tasks(1)
+    int pred_ns = 0;
+    double* pred_pin = nullptr;       // pinned: a block's rows on their way to the caller, 2 cap (G + p) ld doubles
     char* pin_in = nullptr;           // pinned: batch_pin_in
     SmallPinOut out{};                // pinned: what a group of sweeps sends back, the four state copies
     double us_reserve = 0.0;          // GPRN_BATCH_TIMERS: what making room took, reported with the next chunk
@@ -949,9 +958,58 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
         TRY(grad_batch_pass(c, c->kspec, in, grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c))));
     }
     const double us_grad = t.lap();
+    if (io.pred.ns > 0) {
+        // ---- the prediction of every evaluation's last committed sweep: midn.hip's pass over the B x G one-tile slots (T = 1),
+        // in the set-up's order.  s and ct are rows G + g and 6 G + g of the evaluation's vectors -- per (evaluation, latent
+        // GP) already, a stopped evaluation's are its last trip's: nothing was kept, two pitched copies bring them to the
+        // pass's layout.  Its two blocks per slot live in matrices the loop has finished with (B's workspace, the prior's K).
+        const size_t nn = (size_t)c->ld * c->ld, nmat = small_nmat(c), gl = (size_t)G * c->ld, nv = (size_t)cap * gl;
+        if (!m->pred_tab) {
+            std::vector<double*> rows((size_t)cap * G * GPRN_NBUF), kp((size_t)cap * G);
+            for (int b = 0; b < cap; ++b)
+                for (int g = 0; g < G; ++g) {
+                    double* const mb = m->mats + (size_t)b * nmat * nn;
+                    const size_t sl = (size_t)b * G + g;
+                    buf_row(&rows[sl * GPRN_NBUF], mb + (2 * (size_t)G + g) * nn, mb + (3 * (size_t)G + g) * nn, mb + (2 * (size_t)G + g) * nn,
+                            mb + (size_t)g * nn);
+                    kp[sl] = mb + (2 * (size_t)G + g) * nn;
+                }
+            TRY(m->own.alloc(c, &m->pred_vecs, 7 * nv));
+            TRY(m->own.alloc(c, &m->pred_kptr, kp.size()));
+            TRY(m->own.alloc(c, &m->pred_tab, rows.size()));
+            HIP_TRY(c, hipMemcpy(m->pred_kptr, kp.data(), kp.size() * sizeof(double*), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(m->pred_tab, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice));
+            const std::vector<TileTask> tasks = pred_pass_tasks(1, c->ld);
+            TRY(m->own.alloc(c, &m->pred_tasks, tasks.size()));
+            HIP_TRY(c, hipMemcpy(m->pred_tasks, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice));
+            TRY(m->own.alloc(c, &m->pred_jit, (size_t)cap * c->p));
+            TRY(m->own.pin(c, &m->pred_pin, 2 * (size_t)cap * (G + c->p) * c->ld * sizeof(double)));
+        }
+        if (io.pred.ns > m->pred_ns) {                  // (a longer t* than any before: a new array; the old one goes with the buffers)
+            TRY(m->own.alloc(c, &m->pred_ts, (size_t)io.pred.ns));
+            m->pred_ns = io.pred.ns;
+        }
+        double* const pv = m->pred_vecs;
+        const size_t rowb = gl * sizeof(double);
+        HIP_TRY(c, hipMemcpy2DAsync(pv, rowb, m->vecs + gl, 7 * rowb, rowb, B, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpy2DAsync(pv + nv, rowb, m->vecs + 6 * gl, 7 * rowb, rowb, B, hipMemcpyDeviceToDevice, st));
+        // (a launch's grid z / y is the number of slots: groups of evaluations that stay below its limit)
+        const int group = std::max(1, 32768 / G);
+        for (int e0 = 0; e0 < B; e0 += group) {
+            const int nb = std::min(group, B - e0);
+            const size_t s0 = (size_t)e0 * G, o0 = (size_t)e0 * c->p * c->ld;
+            const PredPassIn in{nb, G, c->p, c->N, c->ld, 1, m->pred_tab + s0 * GPRN_NBUF, m->pred_kptr + s0,
+                                m->programs + s0 * fill_program_bytes(), m->pin_in + s0 * fill_program_bytes(),
+                                pv + s0 * c->ld, pv + nv + s0 * c->ld, pv + 2 * nv + s0 * c->ld, pv + 3 * nv + s0 * c->ld,
+                                pv + 4 * nv + s0 * c->ld, pv + 5 * nv + o0, pv + 6 * nv + o0, io.jitters + (size_t)e0 * c->p, info + e0,
+                                m->pred_ts, m->pred_jit, m->pred_tasks, m->pred_pin};
+            TRY(batch_pred_pass(c, in, io.pred.from(e0)));
+        }
+    }
+    const double us_pred = t.lap();
     if (batch_timers_on())
         fprintf(stderr, "[gprn] elbocalc_batch (one tile), %d evaluations, us: buffers %.0f | staging %.0f | enqueue %.0f | waiting for the device "
-                        "%.0f | verdicts %.0f | states back %.0f | gradient pass %.0f | total %.0f (%d launches of sweeps)\n", B, us_ensure, us_stage,
-                us_enqueue, us_wait, us_host, us_states, us_grad, us_ensure + t.total(), s - (max_iter >= 1 ? 1 : 0));
+                        "%.0f | verdicts %.0f | states back %.0f | gradient pass %.0f | prediction pass %.0f | total %.0f (%d launches of sweeps)\n", B, us_ensure, us_stage,
+                us_enqueue, us_wait, us_host, us_states, us_grad, us_pred, us_ensure + t.total(), s - (max_iter >= 1 ? 1 : 0));
     return GPRN_OK;
 }

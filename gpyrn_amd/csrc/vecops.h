@@ -31,9 +31,10 @@ int vec_sigma(gprn_ctx* c, const double* Binv, const double* s, double* out);
 int vec_pred_rows(gprn_ctx* c, const Phase& ph, int ns, int ns_pad, const double* sol, const double* kss,
                   double* mean, double* var);
 // gprn_predict_batch: per (evaluation, output, t*) the combination inference._Prediction forms from the latent rows
-// (slot = evaluation * G + latent GP, pitch `pitch`); jit: (n_eval, p); out_mean / out_var: (n_eval * p) rows of `pitch`
+// (slot = evaluation * G + latent GP, pitch `pitch`); jit: (n_eval, p); out_mean / out_var: (n_eval * p) rows of `pitch`;
+// jitter_once (gprn_elbocalc_batch_predict): jitter_i^2 once per output instead of once per node
 int vec_predict_outputs(gprn_ctx* c, int n_eval, int ns, size_t pitch, const double* lat_mean, const double* lat_var,
-                        const double* jit, double* out_mean, double* out_var);
+                        const double* jit, double* out_mean, double* out_var, bool jitter_once = false);
 int vec_axpy_matrix(gprn_ctx* c, const double* src, double* dst, int N);   // dst += src on the N x N block (pitch ld)
 int vec_symmetrize(gprn_ctx* c, double* M);                                 // upper := lower^T on the ld x ld matrix
 // out4[l] = < 1/2 (P - Kinv + a a^T), dK/dtheta_l >, a = Kinv m, for a single SE / Periodic / QP kernel (kid, par[4])

@@ -935,6 +935,9 @@ int vec_pred_rows(gprn_ctx* c, const Phase& ph, int ns, int ns_pad, const double
 //   mean_i = sum_j f_j w_ji,   var_i = sum_j [w_ji^2 v_fj + v_wji (v_fj + f_j^2) + jitter_i^2]
 // (the jitter once per node j, as the reference has it), rounded operation by operation as NumPy does.  One thread per
 // (evaluation, output, t*), consecutive threads at consecutive t*: 4 q coalesced reads, two writes.  grid (ns / 256, p, n_eval)
+// ONCE (gprn_elbocalc_batch_predict: the variational form of inference.predict): the jitter enters once, behind the sum over the
+// nodes -- var_i = sum_j [w_ji^2 v_fj + v_wji (v_fj + f_j^2)] + jitter_i^2 -- with the same operation-by-operation rounding.
+template <bool ONCE>
 __global__ __launch_bounds__(256)
 void k_predict_outputs_b(int q, int p, int ns, size_t pitch, const double* __restrict__ lat_mean,
                          const double* __restrict__ lat_var, const double* __restrict__ jit,
@@ -950,18 +953,24 @@ void k_predict_outputs_b(int q, int p, int ns, size_t pitch, const double* __res
         const size_t f_at = (slot0 + j) * pitch + t, w_at = (slot0 + q + (size_t)j * p + i) * pitch + t;
         const double f = lat_mean[f_at], vf = lat_var[f_at], w = lat_mean[w_at], vw = lat_var[w_at];
         m += f * w;
-        v += w * w * vf + vw * (vf + f * f) + j2;
+        if constexpr (ONCE) v += w * w * vf + vw * (vf + f * f);
+        else v += w * w * vf + vw * (vf + f * f) + j2;
     }
+    if constexpr (ONCE) v += j2;
     out_mean[((size_t)b * p + i) * pitch + t] = m;
     out_var[((size_t)b * p + i) * pitch + t] = v;
 }
 
 int vec_predict_outputs(gprn_ctx* c, int n_eval, int ns, size_t pitch, const double* lat_mean, const double* lat_var,
-                        const double* jit, double* out_mean, double* out_var)
+                        const double* jit, double* out_mean, double* out_var, bool jitter_once)
 {
     if (n_eval <= 0 || ns <= 0) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
-    hipLaunchKernelGGL(k_predict_outputs_b, dim3((ns + 255) / 256, c->p, n_eval), dim3(256), 0, c->stream, c->q, c->p, ns, pitch,
-                       lat_mean, lat_var, jit, out_mean, out_var);
+    if (jitter_once)
+        hipLaunchKernelGGL(k_predict_outputs_b<true>, dim3((ns + 255) / 256, c->p, n_eval), dim3(256), 0, c->stream, c->q, c->p, ns,
+                           pitch, lat_mean, lat_var, jit, out_mean, out_var);
+    else
+        hipLaunchKernelGGL(k_predict_outputs_b<false>, dim3((ns + 255) / 256, c->p, n_eval), dim3(256), 0, c->stream, c->q, c->p, ns,
+                           pitch, lat_mean, lat_var, jit, out_mean, out_var);
     LAUNCH_END(c);
 }

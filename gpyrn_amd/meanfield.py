@@ -1467,7 +1467,8 @@ class inference:
             vars_.append(var)
         return np.array(mus), np.array(vars_)
 
-    def predict_batch(self, parameter_sets, tstar=None, states=None, max_iter=None, separate=False):
+    def predict_batch(self, parameter_sets, tstar=None, states=None, max_iter=None, separate=False, from_sweeps=False,
+                      sweeps=None, start=None):
         """
         ``_Prediction`` for several free-parameter vectors -- the step that follows an ``mcmc`` run, whose posterior
         predictive averages the prediction over the hyper-parameter vectors the chain kept (the reference calls
@@ -1483,11 +1484,30 @@ class inference:
         user-defined kernels, expressions that change shape between vectors, a sharded object, N > ``batch_max_N`` -- one
         ``_Prediction`` per vector, same return value.  Mean functions are evaluated per vector on the host.
 
-        Always the reference form of prediction: with ``predict='variational'`` this raises ``NotImplementedError``.
+        ``from_sweeps=False`` (the default) is always the reference form of prediction: with ``predict='variational'`` it
+        raises ``NotImplementedError``.
+
+        ``from_sweeps=True`` (``predict='variational'`` only, else ``ValueError``): each vector's loop runs and the vector is
+        predicted from the posterior ``q(f_g) = N(mu_g, Sigma_g)`` THAT loop leaves -- ``_Prediction``'s variational form
+        per vector, the jitter once -- all vectors SIDE BY SIDE (``gprn_elbocalc_batch_predict``: a prediction pass at the
+        end of each batch chunk, from the X, s and c every evaluation's last committed sweep left in the chunk's slabs).
+        ``states`` is a ``ValueError`` (a state carries no X).  ``sweeps=n`` / ``start=(mu, var)`` mean what they mean in
+        ``nELBO_and_grad_batch``: exactly n forced sweeps per vector from ``start``, else the stored state, else
+        ``_initMuVar``; without ``sweeps`` the warm-started loop under the stop rule (``start`` without ``sweeps`` and
+        ``sweeps < 1`` are ``ValueError``).  The object keeps what ``nELBO_batch`` keeps.  Where the side-by-side form does
+        not apply (N > ``batch_max_N``, a mask without ``batch_under_mask``, expressions that change shape between
+        vectors) the vectors go one by one with the same meaning: the loop (or n forced sweeps from the same start), then
+        the posterior form of ``gprn_predict`` on what it left; a kernel without a device program raises what
+        ``predict='variational'`` raises for it.  A vector whose factorisation meets a non-positive pivot gets NaN rows.
+        Sharded objects: ``NotImplementedError``.
 
         Returns (mean (B, N*, p), variance (B, N*, p)) and, with `separate`, the latent means (B, G, N*): nodes first,
         then weight (j, i) at q + j p + i.
         """
+        if from_sweeps:
+            return self._predict_batch_from_sweeps(parameter_sets, tstar, states, max_iter, separate, sweeps, start)
+        if sweeps is not None or start is not None:
+            raise ValueError('predict_batch: `sweeps` and `start` go with from_sweeps=True')
         self._refuse_variational_batch('predict_batch')
         assert self._components_set, _NOT_SET
         sets = [np.array(x, dtype=float) for x in parameter_sets]
@@ -1531,21 +1551,126 @@ class inference:
         mean, var = np.array(means_), np.array(vars_)
         return (mean, var, np.array(lats)) if separate else (mean, var)
 
+    def _predict_batch_from_sweeps(self, parameter_sets, tstar, states, max_iter, separate, sweeps, start):
+        """``predict_batch(from_sweeps=True)``: see there."""
+        if self._predict_form != 'variational':
+            raise ValueError("predict_batch: from_sweeps=True predicts from the posterior the sweeps leave; it needs "
+                             "predict='variational' (predict_form)")
+        if states is not None:
+            raise ValueError('predict_batch: from_sweeps=True takes no `states` -- a state carries no X; give `sweeps` and '
+                             '`start` to run forced sweeps from a state of your own')
+        forced = sweeps is not None
+        if start is not None and not forced:
+            raise ValueError('predict_batch: `start` goes with `sweeps`; the loop under the stop rule starts from the state '
+                             'the object holds')
+        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
+        if trips < 1:
+            raise ValueError('predict_batch: from_sweeps=True needs at least one committed sweep')
+        if self._comm is not None:
+            raise NotImplementedError('predict_batch(from_sweeps=True) is not available on a sharded inference object')
+        assert self._components_set, _NOT_SET
+        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        B = len(sets)
+        if B < 1:
+            raise ValueError('predict_batch: no parameter vector')
+        tstar = np.asarray(self.time, dtype=float) if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
+        if tstar.ndim != 1 or tstar.size < 1:
+            raise ValueError('predict_batch: tstar must be a non-empty vector of times')
+        entry = (self._mu, self._var) if start is None else start
+        staged = self._batch_stage(sets, start=start)
+        res = None
+        if staged is not None:
+            ctx, kp, yr, jt, m0, v0 = staged
+            res = ctx.elbocalc_batch_predict(kp, yr, jt, m0, v0, trips, tstar, forced=forced, latent=separate, outputs=True)
+        if res is not None:
+            self._batch_keep(res)
+            lat_mean, out_mean, out_var = res[6], res[8], res[9]
+            mean = np.transpose(out_mean + self._mean_values_batch(sets, tstar), (0, 2, 1))
+            var = np.transpose(out_var, (0, 2, 1))
+            return (mean, var, lat_mean) if separate else (mean, var)
+        # one by one, each vector from the same state
+        means_, vars_, lats = [], [], []
+        keep, first_info = None, 0
+        for x in sets:
+            self.set_parameters(x)
+            nodes, weights, means, jitters = self._get_components()
+            for k in chain(nodes, weights):
+                if not isinstance(k, covfunc.covFunction) or k._device_program() is None:
+                    raise NotImplementedError("predict='variational' needs a device program for every kernel: user-defined "
+                                              'kernels (and sums that hold a two-argument kernel) are not supported')
+            mu0, var0 = entry if entry[0] is not None else self._initMuVar(nodes, weights, jitters)
+            ctx = self._setup_device(nodes, weights, means, jitters)
+            self._swept = None                                 # (the device's committed sweep is no stored state's)
+            self._send_predict_form(ctx)
+            ctx.set_muvar(np.asarray(mu0, dtype=float), np.asarray(var0, dtype=float))
+            if forced:
+                _, _, info = ctx.sweep(trips, commit=True)
+                conv = False
+                mu, var = ctx.get_muvar()
+            else:
+                _, _, conv, info, mu, var = ctx.elbocalc(trips)
+            first_info = first_info or int(info)
+            if info:
+                gmean = gvar = np.full((self.q * (self.p + 1), tstar.size), np.nan)
+            else:
+                gmean, gvar, _ = ctx.predict(tstar)
+            m_, v_, parts = self._combine_prediction(gmean, gvar, means, jitters, tstar, True, once=True)
+            means_.append(m_)
+            vars_.append(v_)
+            lats.append(np.concatenate([np.asarray(parts[0], dtype=float), np.asarray(parts[1], dtype=float)]))
+            if conv and not info:
+                keep = (mu, var)
+        self.last_info = first_info
+        if keep is not None:
+            self._mu, self._var = keep
+        mean, var = np.array(means_), np.array(vars_)
+        return (mean, var, np.array(lats)) if separate else (mean, var)
+
+    def _mean_values_batch(self, sets, tstar):
+        """The mean functions at `tstar` for B vectors, each at its own parameters: ``(B, p, n*)``.  Constant (or no) means
+        are read from the vectors' own columns (nodes, weights, means, jitters: meanfield.py:193-202); anything else is
+        evaluated per vector.  The object's parameters end at the last vector."""
+        B, ns = len(sets), tstar.size
+        n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
+        means = self._get_components()[2]
+        if all(m_ is None or type(m_) is meanfunc.Constant for m_ in means) and all(x.size in (n_free, n_all) for x in sets):
+            free = ~self.frozen_mask
+            full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
+            for b, x in enumerate(sets):
+                full[b, free] = x[free] if x.size == n_all else x     # (a full-length vector: its free entries, as _batch_stage)
+            col = sum(k.pars.size for k in chain(self.nodes, self.weights))
+            out = np.zeros((B, self.p, ns))
+            for i, m_ in enumerate(means):
+                if m_ is not None:
+                    out[:, i, :] = full[:, col:col + 1]
+                    col += 1
+            self.set_parameters(sets[-1])
+            return out
+        out = []
+        for x in sets:
+            self.set_parameters(x)
+            out.append(np.array(np.array_split(self._mean(self._get_components()[2], tstar), self.p)))
+        return np.array(out)
+
     def _refuse_variational_batch(self, what):
         if self._predict_form == 'variational':
             raise NotImplementedError(
-                f"{what} is not available with predict='variational': the side-by-side evaluations keep no committed "
-                "sweep per vector.  The follow-up is a prediction pass at the end of a batch chunk, where the slabs still "
-                "hold each evaluation's X, as the gradient pass runs today; until then set predict_form = 'reference'")
+                f"{what} is not available with predict='variational' unless from_sweeps=True is given: the side-by-side "
+                "evaluations of the reference form keep no committed sweep per vector.  from_sweeps=True runs each "
+                "vector's loop and a prediction pass at the end of a batch chunk, where the slabs still hold each "
+                "evaluation's X; else set predict_form = 'reference'")
 
     def posterior_predictive(self, parameter_sets, tstar=None, weights=None, **kw):
         """
         The first two moments of the mixture of ``predict_batch``'s predictions over `parameter_sets` -- the posterior
         predictive of a chain: ``mean = sum_b w_b mean_b``, ``var = sum_b w_b (var_b + mean_b^2) - mean^2``.  `weights`
-        (B,): default uniform, normalised to sum 1.  Further keywords go to ``predict_batch`` (``states``, ``max_iter``).
+        (B,): default uniform, normalised to sum 1.  Further keywords go to ``predict_batch`` untouched (``states``,
+        ``max_iter``; ``from_sweeps=True`` with ``sweeps`` / ``start``: the variational form, each vector predicted from the
+        posterior its own loop leaves).
         Returns (mean (N*, p), variance (N*, p)).
         """
-        self._refuse_variational_batch('posterior_predictive')
+        if not kw.get('from_sweeps'):
+            self._refuse_variational_batch('posterior_predictive')
         kw.pop('separate', None)
         mean_b, var_b = self.predict_batch(parameter_sets, tstar=tstar, **kw)
         B = mean_b.shape[0]

@@ -403,6 +403,39 @@ int gprn_elbocalc_batch_grad(gprn_ctx* ctx, int n_eval, const double* kernel_par
                              int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
                              double* mu_out, double* var_out, double* grad_out);
 
+/* gprn_elbocalc_batch with, per evaluation, the prediction of the posterior its loop leaves -- the posterior predictive of a
+ * chain on the variational form: the reference's inference._Prediction (meanfield.py:1289-1381), once per hyper-parameter
+ * vector inference.mcmc kept, behind that vector's nELBO (:1095-1111).
+ *   ns, tstar [ns]: the prediction times, the same for every evaluation;
+ *   lat_mean, lat_var [n_eval][G][ns] (or both NULL): row b is what gprn_predict returns in the posterior form
+ *       (GPRN_PREDICT_POSTERIOR) right after gprn_elbocalc has run evaluation b's loop alone on this context from
+ *       (mu_b, var_b): mean* = K* S c, var* = k** - |row of (K* S) X^T|^2, with X = chol(B)^-1, s = sqrt(d) and c = X^T X z of
+ *       that evaluation's LAST COMMITTED sweep.  Always the posterior form, whatever option "predict_form" says (as
+ *       gprn_predict_batch ignores it).  The nugget is the sweeps' own (quirk Q9), not 1.25e-12; it and WhiteNoise are
+ *       delta(t, t'): in K* exactly where t*_m == t_n as doubles, in k** always.  A point of zero precision (a data mask)
+ *       gives a zero column; nothing divides by s.
+ *   out_mean, out_var [n_eval][p][ns] (or both NULL): per output i, sum_j f_j w_ji and
+ *       sum_j [w_ji^2 v_fj + v_wji (v_fj + f_j^2)] + jitter_i^2 -- the jitter ONCE, as the variational form of
+ *       inference.predict has it; the mean functions are the caller's to add.
+ * At least one pair must be given.  flags: as gprn_elbocalc_batch_grad (GPRN_BATCH_FORCED).
+ * elbo, iterations, converged, info and the states are bit-identical to gprn_elbocalc_batch_grad(..., grad_out = NULL) with
+ * the same inputs and flags: the prediction pass runs per chunk behind the chunk's loop and only reads what the loop left
+ * (csrc/midn.hip batch_pred_pass: t* in blocks of at most ld rows; per block the batched posterior fill, one tile product, one
+ * row kernel, the combination, the rows back through a pinned buffer), in buffers the loop has finished with.  An evaluation
+ * with info > 0 gets NaN in all of its prediction rows; the others are untouched.
+ * GPRN_E_ARG: max_iter < 1 (no committed sweep), ns < 1, unknown flag bits, a pair half given, no pair.  Refusals
+ * (GPRN_E_UNSUPPORTED) are gprn_elbocalc_batch's: a communicator, uploaded kernels, a program that is not even in t_i - t_j, a
+ * data mask without option "batch_mask", a one-tile problem with the small path off.  Both sweep orders, the sequential
+ * order under a mask ("order_mask"), the bound form of the ELBO, chunks and halving under "batch_mem_mb" ("batch_chunk"
+ * reports this call's chunk too).  The context's own state, factors and validity flags are not touched: a gprn_sweep right
+ * after the call returns the bits it would have returned before it. */
+int gprn_elbocalc_batch_predict(gprn_ctx* ctx, int n_eval, const double* kernel_params, int n_kernel_params,
+                                const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                int max_iter, int flags, int ns, const double* tstar,
+                                double* elbo, int* iterations, int* converged, int* info,
+                                double* mu_out, double* var_out,
+                                double* lat_mean, double* lat_var, double* out_mean, double* out_var);
+
 /* gprn_predict for n_eval parameter vectors side by side -- the posterior predictive of a chain: the reference's
  * inference._Prediction (meanfield.py:1289-1381) over _gp.GP.prediction (_gp.py:107-138), once per hyper-parameter vector
  * that inference.mcmc kept.
