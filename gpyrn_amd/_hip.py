@@ -88,6 +88,8 @@ SIGNATURES = {
                                             POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp, _dp]),
     'gprn_predict_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
     'gprn_test_predict_fill': (c_int, [c_void_p, c_int, c_int, _dp, c_int, _dp, c_int, c_int, c_int, _dp, _dp, _dp, _dp]),
+    'gprn_test_fill_rect': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, c_double, c_int, c_int, c_int, _dp, _dp, _dp,
+                            _dp]),
     'gprn_elbocalc': (c_int, [c_void_p, c_int, _dp, _dp, _dp, _dp, c_int, _dp, c_int, POINTER(c_int), POINTER(c_int),
                       POINTER(c_int), _dp, _dp]),
     'gprn_expected_loglike': (c_int, [c_void_p, _dp]),
@@ -603,6 +605,22 @@ class Context:
                                                      int(eval_index), int(gp), ts.size, _ptr(ts), _ptr(K), _ptr(Ks), _ptr(kss)),
                     'test_predict_fill')
         return K, Ks, kss
+
+    def test_fill_rect(self, ops, params, nugget, tstar, form=0, batched=0, s=None):
+        """K* and k** of a kernel expression between tstar (rows) and the data times (columns) by one of prediction's four
+        rectangular fills (gprn_test_fill_rect): form 0 the reference form, 1 the posterior form K* diag(s); batched 0 the
+        single launch, 1 / 2 the batched launch with the caller's program in slot 0 / 1 of two.  Returns the WHOLE padded
+        buffers, K* (ns_pad, ld) and k** (ns_pad): NaN wherever the kernel wrote nothing."""
+        flat = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1, 3))
+        par = _f64(np.atleast_1d(params))
+        ts = _f64(np.ravel(tstar))
+        sv = None if s is None else _f64(np.ravel(s), (self.N,))
+        pad = lambda n: -(-n // TILE) * TILE
+        Ks, kss = np.empty((pad(ts.size), pad(self.N))), np.empty(pad(ts.size))
+        self._check(self._lib.gprn_test_fill_rect(self._h, flat.ctypes.data_as(POINTER(c_int32)), flat.shape[0], _ptr(par),
+                                                  par.size, float(nugget), int(form), int(batched), ts.size, _ptr(ts),
+                                                  None if sv is None else _ptr(sv), _ptr(Ks), _ptr(kss)), 'test_fill_rect')
+        return Ks, kss
 
     def option(self, name, value=-1):
         """Read (value < 0) or set a per-context switch of the library; returns the previous value.  Among them

@@ -247,3 +247,6 @@ int check_info(gprn_ctx* c, const int* d_info, const std::vector<int>& gps, int*
 int ensure_gp_storage(gprn_ctx* c, int g);
 // ---- defined in api_more.hip (diagnostics): a scratch "problem" of `batch` ld x ld matrices
 int test_setup(gprn_ctx* c, int ld, int nbuf_needed, int batch);
+// a caller's kernel expression (postfix ops, parameters) as a checked KernelSpec: what gprn_eval_kernel fills from
+int spec_from_args(gprn_ctx* c, KernelSpec& ks, const int32_t* ops, int n_ops, const double* params, int n_params,
+                   int add_nugget);

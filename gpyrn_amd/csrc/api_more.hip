@@ -744,8 +744,8 @@ extern "C" int gprn_predict_upload_kss(gprn_ctx* c, int gp, int ns, const double
 }
 
 // ------------------------------------------------------------------ kernel matrices, prior samples
-static int spec_from_args(gprn_ctx* c, KernelSpec& ks, const int32_t* ops, int n_ops, const double* params,
-                          int n_params, int add_nugget)
+int spec_from_args(gprn_ctx* c, KernelSpec& ks, const int32_t* ops, int n_ops, const double* params,
+                   int n_params, int add_nugget)
 {
     if (!ops || n_ops <= 0 || n_ops > GPRN_MAX_OPS || n_params < 0 || n_params > GPRN_MAX_KPARAMS || (n_params && !params))
         return bad(c, "kernel expression: bad argument");

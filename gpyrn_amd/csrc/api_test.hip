@@ -280,3 +280,71 @@ extern "C" int gprn_test_predict_fill(gprn_ctx* c, int batched, int n_eval, cons
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GPRN_OK;
 }
+
+// The rectangular fills of prediction for ANY program (include/gprn_hip.h): one of fill.hip's four launches on buffers that hold
+// a NaN byte pattern beforehand, every buffer returned in full -- so the zeros of the padding are the kernel's, not the
+// allocator's.  The batched launches fill two matrices, the caller's program beside one with every parameter scaled by 1.25 (and,
+// in the posterior form, another s), staged as mid_predict_stage does: host images by fill_program_with, one copy to the device.
+extern "C" int gprn_test_fill_rect(gprn_ctx* c, const int32_t* ops, int n_ops, const double* params, int n_params,
+                                   double nugget, int form, int batched, int ns, const double* tstar, const double* s,
+                                   double* Ks_out, double* kss_out)
+{
+    DeviceLock lock_(c);
+    if (!c || !c->N) return bad(c, "test_fill_rect: call set_data first");
+    if (form < 0 || form > 1 || batched < 0 || batched > 2 || ns < 1 || ns > 4096 || !tstar || (form == 1 && !s) || !Ks_out ||
+        !kss_out)
+        return bad(c, "test_fill_rect: bad argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    KernelSpec ks;
+    TRY(spec_from_args(c, ks, ops, n_ops, params, n_params, nugget != 0.0));
+    const int N = c->N, ld = c->ld, ns_pad = ((ns + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE, nm = batched ? 2 : 1;
+    const int mine = batched == 2 ? 1 : 0;                   // the caller's slot of a batched launch
+    // every matrix and every k** has a guard behind it (one row, one tile): still NaN bytes after the launch, or the call fails
+    const size_t nk = (size_t)ns_pad * ld, mk = nk + ld, mv = (size_t)ns_pad + GPRN_TILE, pb = fill_program_bytes();
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    CallScratch scr(c);
+    double *d_Ks = nullptr, *d_kss = nullptr, *d_ts = nullptr, *d_s = nullptr;
+    TRY(scr.alloc(&d_Ks, nm * mk));
+    TRY(scr.alloc(&d_kss, nm * mv));
+    TRY(scr.alloc(&d_ts, ns));
+    TRY(scr.alloc(&d_s, (size_t)nm * ld));
+    HIP_TRY(c, hipMemset(d_Ks, 0xFF, nm * mk * sizeof(double)));
+    HIP_TRY(c, hipMemset(d_kss, 0xFF, nm * mv * sizeof(double)));
+    HIP_TRY(c, hipMemset(d_s, 0xFF, (size_t)nm * ld * sizeof(double)));
+    HIP_TRY(c, hipMemcpy(d_ts, tstar, ns * sizeof(double), hipMemcpyHostToDevice));
+    if (form == 1) {
+        std::vector<double> hs((size_t)nm * N);
+        for (int z = 0; z < nm; ++z)
+            for (int n = 0; n < N; ++n) hs[(size_t)z * N + n] = z == mine ? s[n] : s[N - 1 - n] + 1.0;
+        HIP_TRY(c, hipMemcpy2D(d_s, ld * sizeof(double), hs.data(), N * sizeof(double), N * sizeof(double), nm, hipMemcpyHostToDevice));
+    }
+    if (!batched) {
+        if (form == 0) TRY(launch_fill_rect(c, ks, nugget, d_ts, ns, ns_pad, d_Ks, d_kss));
+        else TRY(launch_fill_rect_post(c, ks, nugget, d_ts, ns, ns_pad, d_s, d_Ks, d_kss));
+    } else {
+        std::vector<char> h_programs(2 * pb);
+        std::vector<double> scaled(ks.params, ks.params + ks.n_params);
+        for (double& v : scaled) v *= 1.25;
+        fill_program_with(ks, ks.params, h_programs.data() + mine * pb, nugget);
+        fill_program_with(ks, scaled.data(), h_programs.data() + (1 - mine) * pb, nugget);
+        char* d_programs = nullptr;
+        double** d_p = nullptr;
+        TRY(scr.alloc(&d_programs, 2 * pb));
+        HIP_TRY(c, hipMemcpy(d_programs, h_programs.data(), 2 * pb, hipMemcpyHostToDevice));
+        TRY(scr.table(&d_p, {d_Ks, d_Ks + mk}));
+        if (form == 0) TRY(launch_fill_rect_batch(c, d_programs, d_p, 2, d_ts, ns, ns_pad, d_kss, mv));
+        else TRY(launch_fill_rect_batch_post(c, d_programs, h_programs.data(), d_p, 2, d_ts, ns, ns_pad, d_s, d_kss, mv));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<uint64_t> guard((size_t)nm * (ld + GPRN_TILE));
+    for (int z = 0; z < nm; ++z) {
+        HIP_TRY(c, hipMemcpy(guard.data() + (size_t)z * (ld + GPRN_TILE), d_Ks + z * mk + nk, ld * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(guard.data() + (size_t)z * (ld + GPRN_TILE) + ld, d_kss + z * mv + ns_pad, GPRN_TILE * sizeof(double),
+                             hipMemcpyDeviceToHost));
+    }
+    for (uint64_t w : guard)
+        if (w != ~(uint64_t)0) { c->err = "test_fill_rect: the launch wrote behind a buffer's end"; return GPRN_E_HIP; }
+    HIP_TRY(c, hipMemcpy(Ks_out, d_Ks + mine * mk, nk * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(kss_out, d_kss + mine * mv, ns_pad * sizeof(double), hipMemcpyDeviceToHost));
+    return GPRN_OK;
+}

@@ -615,6 +615,21 @@ int gprn_test_tile_step(gprn_ctx* ctx, int nbatch, double* bufs, int which, int 
 int gprn_test_predict_fill(gprn_ctx* ctx, int batched, int n_eval, const double* kernel_params, int n_kernel_params,
                            const double* var, int eval, int gp, int ns, const double* tstar,
                            double* K_out, double* Ks_out, double* kss_out);
+/* The rectangular fills of prediction for ANY kernel expression, for tests/test_rect_fill_gpu.py: K* and k** of
+ * expr (ops, params as in gprn_eval_kernel; nugget != 0: the program takes that nugget) between `ns` times tstar (rows) and the
+ * data times of gprn_set_data (columns), by ONE of the four launches prediction makes, unchanged.  form 0: the reference form --
+ * K*[i][n] = expr(t*_i, t_n) without nugget or WhiteNoise, k**[i] = expr(t*_i, t*_i) + nugget; form 1: the posterior form --
+ * K* diag(s), s: N values (read for form 1 only), the nugget and WhiteNoise exactly where t*_i == t_n as doubles and in k**.
+ * batched 0: the launch gprn_predict makes (one matrix); 1 / 2: the launch gprn_predict_batch (form 0) or
+ * gprn_elbocalc_batch_predict (form 1) makes, over TWO programs -- the caller's in slot 0 / slot 1, beside it the same
+ * expression with every parameter scaled by 1.25 (form 1: and with s' = reverse(s) + 1) -- of which the caller's matrix is
+ * returned.  Ks_out: the WHOLE padded buffer, (ns_pad, ld) with ns_pad = 128 ceil(ns / 128) and ld = 128 ceil(N / 128); kss_out:
+ * ns_pad values.  Both device buffers hold a NaN byte pattern before the launch: what the kernel does not write comes back NaN.
+ * Behind every buffer lies a guard (a row of ld, a tile of k**) with the same pattern: a launch that writes there is GPRN_E_HIP.
+ * ns <= 4096. */
+int gprn_test_fill_rect(gprn_ctx* ctx, const int32_t* ops, int n_ops, const double* params, int n_params, double nugget,
+                        int form, int batched, int ns, const double* tstar, const double* s, double* Ks_out,
+                        double* kss_out);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,9 @@ gpyrn_amd.covfunc (tests/test_fill_highprec.py) alike:
 
     |K - K_ref| <= (C0 + C1 kappa) 2^-53 |K_ref| + A_DENORM max(1, max |K_ref|),
 
-kappa the element's condition number over r (or t_i, t_j) and the parameters.  Where the reference is NaN, K is NaN."""
+kappa the element's condition number over r (or t_i, t_j) and the parameters.  Where the reference is NaN, K is NaN.
+The rectangular fills of prediction (tests/golden/rect_highprec, oracle/gen_rect_highprec.py; tests/test_rect_fill_gpu.py,
+tests/test_rect_highprec.py) are held to the same bound by the same function: the second half of this file."""
 import json
 import os
 
@@ -35,18 +37,23 @@ def case_arrays(case, d, seq=False):
     return i, j, d['hi'][s], d['lo'][s].astype(float), d['kappa'][s].astype(float)
 
 
-def violations(K, case, d, seq=False):
-    """Elements of the sample where the matrix K breaks the bound: a list of (i, j, K, K_ref, allowed) tuples."""
+def violations(K, case, d, seq=False, c0=C0, ratios=None):
+    """Elements of the sample where the matrix K breaks the bound: a list of (i, j, K, K_ref, allowed) tuples.  c0: C0,
+    raised by the caller for every further rounding its K carries by construction.  ratios: a list that takes the
+    sample's largest error / allowed (finite references only)."""
     i, j, hi, lo, kappa = case_arrays(case, d, seq)
     k = K[i, j]
     nan_ref = np.isnan(hi)
     with np.errstate(invalid='ignore', over='ignore'):
         scale = max(1.0, float(np.nanmax(np.abs(hi))) if not nan_ref.all() else 1.0)
         err = np.abs((k - hi) - lo)
-        allowed = np.where(hi == 0, 0.0, (C0 + C1 * kappa) * EPS * np.abs(hi)) + A_DENORM * scale
+        allowed = np.where(hi == 0, 0.0, (c0 + C1 * kappa) * EPS * np.abs(hi)) + A_DENORM * scale
         bad = np.where(nan_ref, ~np.isnan(k), ~(err <= allowed))
         inf_ref = np.isinf(hi)
         bad = np.where(inf_ref, k != hi, bad)
+        if ratios is not None:
+            r = (err / allowed)[np.isfinite(hi) & np.isfinite(k)]
+            ratios.append(float(r.max()) if r.size else 0.0)
     return [(int(a), int(b), float(x), float(y), float(z)) for a, b, x, y, z in
             zip(i[bad], j[bad], k[bad], hi[bad], allowed[bad])]
 
@@ -59,3 +66,59 @@ def numpy_matrix(case, t):
         if isinstance(k, (covfunc.Polynomial, covfunc.HarmonicPeriodic, covfunc.QuasiHarmonicPeriodic)):
             return np.asarray(k(t[:, None], t[None, :]), dtype=float)
         return np.asarray(k(t[:, None] - t[None, :]), dtype=float)
+
+
+# ------------------------------------------------------------------ the rectangular fills of prediction
+# tests/golden/rect_highprec (oracle/gen_rect_highprec.py): K* and k** of the same cases between t* and t, in the reference
+# form and in the posterior form of prediction, held to the same bound by the same function.
+REF, POST = 0, 1
+
+
+def load_rect():
+    with open(os.path.join(GOLDEN, 'rect_highprec.json')) as f:
+        meta = json.load(f)
+    d = np.load(os.path.join(GOLDEN, 'rect_highprec.npz'))
+    return meta, {k: d[k] for k in d.files}
+
+
+def rect_nugget(meta, case, form):
+    """what the case's program takes as its nugget in `form`: 0 for the kernels that take none"""
+    return (meta['setup_nugget'] if form == POST else meta['tiny_nugget']) if case['nugget'] else 0.0
+
+
+def rect_views(case, d, form, ns):
+    """((case, d) of the K* sample, (case, d) of k** as an (ns, 1) matrix) of one case in `form`, as `violations` and
+    `case_arrays` take them: the posterior form is the reference form but at the coincident pairs."""
+    s = slice(case['off'], case['off'] + case['n'])
+    ks = {k: d[k][s].copy() for k in ('i', 'j', 'hi', 'lo', 'kappa')}
+    if form == POST:
+        c = slice(case['co_off'], case['co_off'] + case['co_n'])
+        for k in ('hi', 'lo', 'kappa'):
+            ks[k][d['co_k'][c]] = d['co_' + k][c]
+    q = slice(case['kss_off'] + form * ns, case['kss_off'] + (form + 1) * ns)
+    kss = {'i': np.arange(ns), 'j': np.zeros(ns, dtype=np.int64), 'hi': d['kss_hi'][q], 'lo': d['kss_lo'][q],
+           'kappa': d['kss_kappa'][q]}
+    return ({'off': 0, 'n': case['n']}, ks), ({'off': 0, 'n': ns}, kss)
+
+
+def scale_columns(view, s):
+    """the view of K* diag(s), s exact powers of two or zeros: the products are exact"""
+    case, ks = view
+    sj = np.asarray(s, dtype=float)[ks['j'].astype(np.int64)]
+    with np.errstate(invalid='ignore'):
+        return case, dict(ks, hi=ks['hi'] * sj, lo=ks['lo'].astype(float) * sj)
+
+
+def numpy_rect(case, ts, t, i, j, delta):
+    """NumPy's own evaluation of the case's kernel (gpyrn_amd.covfunc.__call__) at the pairs (t*_i, t_j), no nugget;
+    `delta`: per pair, whether the element counts as on the diagonal -- read by WhiteNoise alone, which covfunc spells
+    out for square matrices only and which no composite of the fixture contains."""
+    from gpyrn_amd import covfunc
+    k = eval(case['expr'], {'c': covfunc, 'nan': float('nan')})
+    a, b = ts[i], t[j]
+    with np.errstate(all='ignore'):
+        if isinstance(k, covfunc.WhiteNoise):
+            return np.where(delta, k.pars[0]**2, 0.0)
+        if isinstance(k, (covfunc.Polynomial, covfunc.HarmonicPeriodic, covfunc.QuasiHarmonicPeriodic)):
+            return np.asarray(k(a, b), dtype=float)
+        return np.asarray(k(a - b), dtype=float)
