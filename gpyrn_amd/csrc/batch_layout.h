@@ -81,6 +81,38 @@ static inline SmallPinOut small_pin_out(LayoutCursor& c, size_t cap, size_t G, s
 {
     return {c.take<int>(cap * 4), c.take<double>(cap * hist), c.take<int>(cap * 3 * G), c.take<double>(4 * cap * state, 64)};
 }
+// ... and its four device slabs for cap evaluations.  mats: per evaluation nmat matrices of ld x ld -- K, chol(K)^-1, B, X per
+// latent GP, then K_j^-1 per node where quirk Q1 is in force (nmat = 4 G + q; the bound form has none: 4 G).  vecs: per
+// evaluation the seven vectors of a half-sweep over its G slots, in the order SmallPhaseArgs takes them.  states: four copies
+// (mu A, var A, mu B, var B), copy-major.  yv: y - mean | variance of p N each, copy-major.
+struct SmallShape { size_t cap, G, q, p, N, ld, nmat; };
+enum SmallVec { SV_D, SV_S, SV_PRED, SV_Z, SV_U, SV_CS, SV_CT, SV_COUNT };
+struct SmallSlab {
+    SmallShape s;
+    double *mats, *vecs, *states, *yv;
+    size_t nn() const { return s.ld * s.ld; }
+    size_t d() const { return (s.p + 1) * s.q * s.N; }                 // one copy of one evaluation's state
+    size_t pn() const { return s.p * s.N; }
+    size_t vec_pitch() const { return SV_COUNT * s.G * s.ld; }         // doubles from an evaluation's vectors to the next one's
+    size_t mats_count() const { return s.cap * s.nmat * nn(); }        // doubles of each slab ...
+    size_t vecs_count() const { return s.cap * vec_pitch(); }
+    size_t state_count() const { return 4 * s.cap * d(); }
+    size_t yv_count() const { return 2 * s.cap * pn(); }
+    size_t per_eval() const { return s.nmat * nn() + vec_pitch() + 4 * d() + 2 * pn(); }   // ... and of one evaluation in all four
+    double* mat(size_t b, size_t k) const { return mats + (b * s.nmat + k) * nn(); }
+    double* K(size_t b, size_t g) const { return mat(b, g); }
+    double* KLinv(size_t b, size_t g) const { return mat(b, s.G + g); }
+    double* B(size_t b, size_t g) const { return mat(b, 2 * s.G + g); }
+    double* X(size_t b, size_t g) const { return mat(b, 3 * s.G + g); }
+    double* Kinv(size_t b, size_t j) const { return mat(b, 4 * s.G + j); }     // (only where nmat = 4 G + q)
+    double* vec(size_t b, SmallVec which, size_t slot) const { return vecs + b * vec_pitch() + (which * s.G + slot) * s.ld; }
+    size_t state_index(size_t copy, size_t b) const { return copy * s.cap + b; }
+    double* state(size_t copy, size_t b) const { return states + state_index(copy, b) * d(); }
+    double* yres(size_t b) const { return yv + b * pn(); }
+    double* variance(size_t b) const { return yv + (s.cap + b) * pn(); }
+};
+// the copy that holds the mean of an evaluation's last committed sweep (its variance: the next one): odd trips wrote copy B
+static inline size_t small_final_copy(int iters) { return iters >= 1 && (iters & 1) ? 2 : 0; }
 // ---- the pinned input of a chunk (batch_stage; gprn_predict_batch stages its programs, states and, in `variance`, jitters):
 // cap G fill programs of `program` bytes, yv doubles of y - mean and of the variances and `state` of mu and var per evaluation
 struct BatchBufs { char* programs; double *yres, *variance, *mu, *var; };    // (also: where the five go on the device)

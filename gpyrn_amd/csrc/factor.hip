@@ -118,11 +118,10 @@ int launch_diag(gprn_ctx* c, const Phase& ph, int kblk, bool acc, hipStream_t st
     // rows of data in this tile: all 128 but in the last tile of a ragged matrix
     const int rows_here = std::min(GPRN_TILE, ph.N - kblk * GPRN_TILE);
     const int nph = std::max(1, (rows_here + 15) / 16);
-#define GO_D(ARGS, ACC) hipLaunchKernelGGL((k_diag_block<ARGS, ACC>), dim3(nbatch), dim3(256), dyn, stream, (double* const*)ph.ptrs, pa, \
-                           ph.ld, kblk, ph.info, sig.slot, sig.value, aw.flag, aw.value, aw.timed_out, nph)
-    if (tab_rows(c, ph.ptrs, nbatch, &pa)) { if (acc) GO_D(true, true); else GO_D(true, false); }
-    else { if (acc) GO_D(false, true); else GO_D(false, false); }
-#undef GO_D
+    with_flags([&](auto ARGS, auto ACC) {
+        hipLaunchKernelGGL((k_diag_block<ARGS, ACC>), dim3(nbatch), dim3(256), dyn, stream, (double* const*)ph.ptrs, pa,
+                           ph.ld, kblk, ph.info, sig.slot, sig.value, aw.flag, aw.value, aw.timed_out, nph);
+    }, tab_rows(c, ph.ptrs, nbatch, &pa), acc);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

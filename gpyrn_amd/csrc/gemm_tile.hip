@@ -188,11 +188,11 @@ int launch_panel(gprn_ctx* c, const TileTask* d_tasks, size_t n_l, size_t n_x, d
 {
     if (n_l + n_x == 0 || nbatch == 0) return launch_tiles(c, d_tasks, 0, d_ptrs, nbatch, ld, GPRN_T_PANEL, stream, TS_128x64, sig);
     prof_begin(c, GPRN_T_PANEL, stream);
-#define GO_P(ACC) hipLaunchKernelGGL(k_tile_panel<ACC>, dim3((unsigned)(2 * (n_l + n_x)), (unsigned)nbatch), dim3(256), 0, stream, d_tasks, (int)n_l, \
-                       (double* const*)d_ptrs, ld, sig.slot, sig.value, sig.then_wait, sig.then_value, \
-                       aw.timed_out ? aw.timed_out : sig.timed_out, aw.flag, aw.value, raise_at_start, raise_value, raise_at_start2)
-    if (acc) GO_P(true); else GO_P(false);
-#undef GO_P
+    with_flags([&](auto ACC) {
+        hipLaunchKernelGGL(k_tile_panel<ACC>, dim3((unsigned)(2 * (n_l + n_x)), (unsigned)nbatch), dim3(256), 0, stream, d_tasks, (int)n_l,
+                           (double* const*)d_ptrs, ld, sig.slot, sig.value, sig.then_wait, sig.then_value,
+                           aw.timed_out ? aw.timed_out : sig.timed_out, aw.flag, aw.value, raise_at_start, raise_value, raise_at_start2);
+    }, acc);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
@@ -351,14 +351,14 @@ int launch_tile_rows(gprn_ctx* c, int k, double** d_ptrs, int nbatch, int ld, in
     pa.stamps = step_stamp_ptr(c, k, mode == 0 ? 1 : 2);
     const bool args = tab_rows(c, d_ptrs, nbatch, &pa);
     unsigned* const tmo = aw.timed_out ? aw.timed_out : sig.timed_out;
-#define GO_L(A) hipLaunchKernelGGL((k_chain_l<A>), dim3(GPRN_TILE / 16, (unsigned)nbatch), dim3(512), 0, stream, tab, pa, ld, a_off, \
-                                   b_off, sig.slot, sig.value, aw.flag, aw.value, tmo)
-#define GO_U(A) hipLaunchKernelGGL((k_chain_u<A>), dim3(36, (unsigned)nbatch), dim3(64), 0, stream, tab, pa, ld, a_off, c_off, \
-                                   sig.slot, sig.value, aw.flag, aw.value, tmo, raise_at_start, raise_value)
-    if (mode == 0) { if (args) GO_L(true); else GO_L(false); }
-    else { if (args) GO_U(true); else GO_U(false); }
-#undef GO_L
-#undef GO_U
+    with_flags([&](auto A) {
+        if (mode == 0)
+            hipLaunchKernelGGL((k_chain_l<A>), dim3(GPRN_TILE / 16, (unsigned)nbatch), dim3(512), 0, stream, tab, pa, ld, a_off,
+                               b_off, sig.slot, sig.value, aw.flag, aw.value, tmo);
+        else
+            hipLaunchKernelGGL((k_chain_u<A>), dim3(36, (unsigned)nbatch), dim3(64), 0, stream, tab, pa, ld, a_off, c_off,
+                               sig.slot, sig.value, aw.flag, aw.value, tmo, raise_at_start, raise_value);
+    }, args);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -73,6 +74,16 @@ static inline uint8_t tile_modes(int c_mode, int a_mode, int b_mode, int lower_o
             return GPRN_E_HIP;                                                 \
         }                                                                      \
     } while (0)
+
+// Runtime flags to template flags, the one way a launcher selects a kernel variant: f gets a std::true_type or
+// std::false_type per flag, in their order.  with_flags([&](auto W, auto M) { launch k<W, M> }, weights, masked): an
+// integral constant converts to its value where a template argument is asked for.
+template <class F> static inline void with_flags(F&& f) { f(); }
+template <class F, class... Bs> static inline void with_flags(F&& f, bool b, Bs... rest)
+{
+    if (b) with_flags([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else with_flags([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
 
 struct Profiler {
     bool on = false;

@@ -174,24 +174,23 @@ int order_refresh(gprn_ctx* c, const Phase& ph, bool weights)
         const size_t o = (size_t)g.slot0 * g.ld, po = (size_t)g.slot0 * g.T * 2 * g.ld;
         prof_begin(c, GPRN_T_VEC);
         const dim3 grid((g.ld + 255) / 256, gs);
-#define GO_RHS(W, M) hipLaunchKernelGGL((k_order_rhs<W, M>), grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, c->p, c->q, \
-                               (const double*)c->d_mu, (const double*)c->d_mu_old, (const double*)c->d_yres,                   \
-                               (const double*)c->d_variance, (const double*)(c->d_s + o), c->d_pred + o, c->d_z + o, g.ev,     \
-                               (const uint8_t*)c->d_mask)
-        if (weights) { if (c->d_mask) GO_RHS(true, true); else GO_RHS(true, false); }
-        else         { if (c->d_mask) GO_RHS(false, true); else GO_RHS(false, false); }
-#undef GO_RHS
+        with_flags([&](auto W, auto M) {
+            hipLaunchKernelGGL((k_order_rhs<W, M>), grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, c->p, c->q,
+                               (const double*)c->d_mu, (const double*)c->d_mu_old, (const double*)c->d_yres,
+                               (const double*)c->d_variance, (const double*)(c->d_s + o), c->d_pred + o, c->d_z + o, g.ev,
+                               (const uint8_t*)c->d_mask);
+        }, weights, c->d_mask != nullptr);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
         TRY(vec_lower_matvec(c, g, BUF_X, c->d_z + o, g.ld, 0, c->d_u + o));
         prof_begin(c, GPRN_T_VEC);
         hipLaunchKernelGGL(k_order_xtu_partial, dim3(g.ld / 64, g.T, gs), dim3(256), 0, c->stream,
                            (double* const*)g.ptrs, g.ld, g.T, (const double*)(c->d_u + o), c->d_part + po);
-#define GO_MEAN(M) hipLaunchKernelGGL(k_order_mean<M>, grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, g.T, c->p, c->q,   \
-                           (const double*)(c->d_part + po), (const double*)(c->d_s + o), (const double*)(c->d_z + o),        \
-                           c->d_ct + o, c->d_mu, g.ev)
-        if (c->d_mask) GO_MEAN(true); else GO_MEAN(false);
-#undef GO_MEAN
+        with_flags([&](auto M) {
+            hipLaunchKernelGGL(k_order_mean<M>, grid, dim3(256), 0, c->stream, g.slot_gp, g.N, g.ld, g.T, c->p, c->q,
+                               (const double*)(c->d_part + po), (const double*)(c->d_s + o), (const double*)(c->d_z + o),
+                               c->d_ct + o, c->d_mu, g.ev);
+        }, c->d_mask != nullptr);
         prof_end(c);
         HIP_TRY(c, hipGetLastError());
     }
@@ -308,15 +307,9 @@ int order_small(gprn_ctx* c, const Phase& ph, bool weights, const double* mu_in,
                      c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, c->d_u + o, c->d_cs + o, c->d_ct + o,
                      nullptr, nullptr, ph.info, nullptr, c->d_mask};
     const dim3 grid(weights ? c->p : 1);
-#define GO(W, TT, M) hipLaunchKernelGGL((k_order_small<W, TT, M>), grid, dim3(256), 0, c->stream, a)
-    if (c->d_mask) {
-        if (ph.T == 1) { if (weights) GO(true, 1, true); else GO(false, 1, true); }
-        else { if (weights) GO(true, 2, true); else GO(false, 2, true); }
-    } else {
-        if (ph.T == 1) { if (weights) GO(true, 1, false); else GO(false, 1, false); }
-        else { if (weights) GO(true, 2, false); else GO(false, 2, false); }
-    }
-#undef GO
+    with_flags([&](auto W, auto one, auto M) {
+        hipLaunchKernelGGL((k_order_small<W, one ? 1 : 2, M>), grid, dim3(256), 0, c->stream, a);
+    }, weights, ph.T == 1, c->d_mask != nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
@@ -329,10 +322,9 @@ int order_small_batch(gprn_ctx* c, const void* lanes, bool weights, int n_eval, 
     if (!order_on(c) || !n_eval) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
     const dim3 grid(weights ? c->p : 1, n_eval);
-#define GO(W, M) hipLaunchKernelGGL((k_order_small_b<W, M>), grid, dim3(256), 0, c->stream, (const SmallPhaseArgs*)lanes)
-    if (masked) { if (weights) GO(true, true); else GO(false, true); }
-    else { if (weights) GO(true, false); else GO(false, false); }
-#undef GO
+    with_flags([&](auto W, auto M) {
+        hipLaunchKernelGGL((k_order_small_b<W, M>), grid, dim3(256), 0, c->stream, (const SmallPhaseArgs*)lanes);
+    }, weights, masked);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

@@ -89,7 +89,7 @@ struct DiagFromK {
 // MASKED: k_prep_*'s selection inside the workgroup -- a masked entry is left out of d and the right-hand side, a point
 // with d = 0 gets s = z = 0 (row and column of B the identity) and a placeholder state that mask.hip's rows overwrite
 // behind this launch (small_sweep).
-template <bool WEIGHTS, int T, bool MASKED = false>
+template <bool WEIGHTS, int T, bool MASKED>
 __device__ __forceinline__ void small_phase_body(const SmallPhaseArgs& a)
 {
     // (one tile: the diagonal-block kernel's 46.6 KB only -- with the vectors 59 KB, two workgroups per CU when many
@@ -300,7 +300,7 @@ __device__ __forceinline__ void small_loglike(const SmallTailArgs& a, double* sh
 // FORCED (GPRN_BATCH_FORCED): the stop rule is not applied -- max_iter committed trips, converged = 0
 // BOUND (option "elbo_form" = GPRN_ELBO_BOUND): the latent GP's own mean in mu^T K^-1 mu (no quirk Q2), no quirk Q1 -- its
 // product, traces and table reads are compiled out --, the residual in a.yraw (the launchers': no Q3), no division by q
-template <int T, bool MASKED = false, bool FORCED = false, bool BOUND = false>
+template <int T, bool MASKED, bool FORCED, bool BOUND>
 __device__ __forceinline__ void small_tail_body(const SmallTailArgs& a)
 {
     __shared__ __attribute__((aligned(16))) double lds[SMALL_MMA_DOUBLES];
@@ -472,59 +472,29 @@ __device__ __forceinline__ void small_prior_body(const SmallPriorArgs& a)
     }
 }
 
-// ---- the kernels: one problem per launch (grid x = latent GP), or -- gprn_elbocalc_batch -- many independent evaluations
-// of the same problem shape per launch (grid y = evaluation, its arguments in device memory)
-template <bool WEIGHTS, int T>
+// ---- the kernels: ONE __global__ template per body and argument form, flags as template parameters, named by the launchers
+// below and nowhere else (with_flags).  One problem per launch (grid x = latent GP, arguments by value), or -- `_b`,
+// gprn_elbocalc_batch -- many independent evaluations of the same one-tile problem shape per launch (grid y = evaluation, its
+// arguments in device memory).  A flag's instantiations are kernels of their own: the others keep their code and registers.
+template <bool WEIGHTS, int T, bool MASKED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_small_phase(SmallPhaseArgs a) { small_phase_body<WEIGHTS, T>(a); }
-// ... under a data mask (gprn_set_mask): its own kernels, so that the unmasked ones keep their code and registers
-template <bool WEIGHTS, int T>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_small_phase_m(SmallPhaseArgs a) { small_phase_body<WEIGHTS, T, true>(a); }
-// (one tile, many evaluations: up to two workgroups per CU -- 222 registers per lane fit twice)
-template <bool WEIGHTS>
+void k_small_phase(SmallPhaseArgs a) { small_phase_body<WEIGHTS, T, MASKED>(a); }
+// (one tile, many evaluations: up to two workgroups per CU -- 222 registers per lane fit twice; the mask's selection costs
+// no register: 206 / 208 VGPRs + 104 AGPRs either way)
+template <bool WEIGHTS, bool MASKED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
-void k_small_phase_b(const SmallPhaseArgs* __restrict__ lanes) { small_phase_body<WEIGHTS, 1>(lanes[blockIdx.y]); }
-// ... under a data mask (option "batch_mask"): kernels of their own, so that the unmasked ones keep their code and registers;
-// the selection costs no register (206 / 208 VGPRs + 104 AGPRs, as k_small_phase_b: DESIGN.md 7)
-template <bool WEIGHTS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
-void k_small_phase_bm(const SmallPhaseArgs* __restrict__ lanes) { small_phase_body<WEIGHTS, 1, true>(lanes[blockIdx.y]); }
+void k_small_phase_b(const SmallPhaseArgs* __restrict__ lanes) { small_phase_body<WEIGHTS, 1, MASKED>(lanes[blockIdx.y]); }
 
-template <int T>
+template <int T, bool MASKED, bool BOUND>
 __global__ __launch_bounds__(256)
-void k_small_tail(SmallTailArgs a) { small_tail_body<T>(a); }
-template <int T>
-__global__ __launch_bounds__(256)
-void k_small_tail_m(SmallTailArgs a) { small_tail_body<T, true>(a); }
-template <int T, bool FORCED = false>
+void k_small_tail(SmallTailArgs a) { small_tail_body<T, MASKED, false, BOUND>(a); }
+template <int T, bool MASKED, bool FORCED, bool BOUND>
 __global__ __launch_bounds__(256)
 void k_small_tail_b(const SmallTailArgs* __restrict__ lanes, int sweep, int hist_at, int max_iter)
 {
     SmallTailArgs a = lanes[blockIdx.y];
     a.sweep = sweep; a.hist_at = hist_at; a.max_iter = max_iter;
-    small_tail_body<T, false, FORCED>(a);
-}
-template <int T, bool FORCED = false>
-__global__ __launch_bounds__(256)
-void k_small_tail_bm(const SmallTailArgs* __restrict__ lanes, int sweep, int hist_at, int max_iter)
-{
-    SmallTailArgs a = lanes[blockIdx.y];
-    a.sweep = sweep; a.hist_at = hist_at; a.max_iter = max_iter;
-    small_tail_body<T, true, FORCED>(a);
-}
-
-// ... in the bound form of the ELBO (option "elbo_form"): kernels of their own, so that the others keep their code and registers
-template <int T, bool MASKED>
-__global__ __launch_bounds__(256)
-void k_small_tail_bound(SmallTailArgs a) { small_tail_body<T, MASKED, false, true>(a); }
-template <int T, bool MASKED, bool FORCED>
-__global__ __launch_bounds__(256)
-void k_small_tail_bound_b(const SmallTailArgs* __restrict__ lanes, int sweep, int hist_at, int max_iter)
-{
-    SmallTailArgs a = lanes[blockIdx.y];
-    a.sweep = sweep; a.hist_at = hist_at; a.max_iter = max_iter;
-    small_tail_body<T, MASKED, FORCED, true>(a);
+    small_tail_body<T, MASKED, FORCED, BOUND>(a);
 }
 
 template <int T, bool ACC>
@@ -554,15 +524,9 @@ int small_phase(gprn_ctx* c, const Phase& ph, bool weights, double* scal, const 
                      mu_in, var_in, mu_out, var_out, done,
                      c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, c->d_u + o, c->d_cs + o, c->d_ct + o,
                      scal + c->G, scal, ph.info, weights ? nullptr : c->d_small_stamps, c->d_mask};
-#define GO(K, W, TT) hipLaunchKernelGGL((K<W, TT>), dim3(ph.nslots), dim3(256), 0, c->stream, a)
-    if (c->d_mask) {
-        if (ph.T == 1) { if (weights) GO(k_small_phase_m, true, 1); else GO(k_small_phase_m, false, 1); }
-        else { if (weights) GO(k_small_phase_m, true, 2); else GO(k_small_phase_m, false, 2); }
-    } else {
-        if (ph.T == 1) { if (weights) GO(k_small_phase, true, 1); else GO(k_small_phase, false, 1); }
-        else { if (weights) GO(k_small_phase, true, 2); else GO(k_small_phase, false, 2); }
-    }
-#undef GO
+    with_flags([&](auto W, auto one, auto M) {
+        hipLaunchKernelGGL((k_small_phase<W, one ? 1 : 2, M>), dim3(ph.nslots), dim3(256), 0, c->stream, a);
+    }, weights, ph.T == 1, c->d_mask != nullptr);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
@@ -580,18 +544,9 @@ int small_tail(gprn_ctx* c, double* out4, double* scal, const double* mu, const 
                     loop ? loop->ctl : nullptr, loop ? loop->hist : nullptr, loop ? loop->last3 : nullptr,
                     loop ? loop->sweep : 0, loop ? loop->hist_at : 0, loop ? loop->max_iter : 0,
                     c->d_info, 3 * c->nslot, c->d_mask};
-    if (bound) {
-#define GO_TB(TT, M) hipLaunchKernelGGL((k_small_tail_bound<TT, M>), dim3(nn + nw), dim3(256), 0, c->stream, a)
-        if (c->d_mask) { if (c->T == 1) GO_TB(1, true); else GO_TB(2, true); }
-        else { if (c->T == 1) GO_TB(1, false); else GO_TB(2, false); }
-#undef GO_TB
-    } else if (c->d_mask) {
-        if (c->T == 1) hipLaunchKernelGGL(k_small_tail_m<1>, dim3(nn + nw), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL(k_small_tail_m<2>, dim3(nn + nw), dim3(256), 0, c->stream, a);
-    } else {
-        if (c->T == 1) hipLaunchKernelGGL(k_small_tail<1>, dim3(nn + nw), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL(k_small_tail<2>, dim3(nn + nw), dim3(256), 0, c->stream, a);
-    }
+    with_flags([&](auto one, auto M, auto BD) {
+        hipLaunchKernelGGL((k_small_tail<one ? 1 : 2, M, BD>), dim3(nn + nw), dim3(256), 0, c->stream, a);
+    }, c->T == 1, c->d_mask != nullptr, bound);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
@@ -603,11 +558,9 @@ int small_prior(gprn_ctx* c, double** d_tab, const int* d_job_gp, double** d_kin
     prof_begin(c, GPRN_T_DIAG);
     SmallPriorArgs a{(double* const*)d_tab, d_job_gp, (double* const*)d_kinv_out, c->N, c->ld, c->d_logdetK, d_info};
     // (prior matrices: panel steps by substitution unless option "accurate_factor" = 0)
-    const bool acc = c->acc_opt != 0;
-#define GO_SP(TT, ACC) hipLaunchKernelGGL((k_small_prior<TT, ACC>), dim3(njobs), dim3(256), 0, c->stream, a)
-    if (c->T == 1) { if (acc) GO_SP(1, true); else GO_SP(1, false); }
-    else { if (acc) GO_SP(2, true); else GO_SP(2, false); }
-#undef GO_SP
+    with_flags([&](auto one, auto ACC) {
+        hipLaunchKernelGGL((k_small_prior<one ? 1 : 2, ACC>), dim3(njobs), dim3(256), 0, c->stream, a);
+    }, c->T == 1, c->acc_opt != 0);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;
@@ -621,12 +574,8 @@ int small_prior(gprn_ctx* c, double** d_tab, const int* d_job_gp, double** d_kin
 // CUs busy; B of them side by side fill it.
 struct SmallBatchMem {
     int cap = 0;                      // evaluations the buffers hold
-    int G = 0, q = 0, p = 0, N = 0, ld = 0;
     DeviceOwner own;                  // every device and pinned buffer below
-    double *mats = nullptr;           // [cap][4 G + q][ld * ld]: K, KLinv, wsB, wsX per latent GP, K_j^-1 per node
-    double *vecs = nullptr;           // [cap][7][G * ld]
-    double *state = nullptr;          // [4][cap][d]: mu A, var A, mu B, var B
-    double *yv = nullptr;             // [2][cap][p N]: y - mean, variance
+    SmallSlab v{};                    // the problem's shape; matrices, vectors, state copies, y - mean | variance (batch_layout.h)
     double *scal = nullptr, *logdetK = nullptr, *out4 = nullptr, *hist = nullptr;
     int *ctl = nullptr, *info = nullptr, *gp_ids = nullptr;
     unsigned* ticket = nullptr;
@@ -661,6 +610,8 @@ struct SmallBatchMem {
 
 // matrices per evaluation: K, chol(K)^-1, B, X per latent GP -- and K_j^-1 per node where quirk Q1 is in force
 static size_t small_nmat(const gprn_ctx* c) { return 4 * (size_t)c->G + (c->elbo_form == GPRN_ELBO_REFERENCE ? c->q : 0); }
+static SmallShape small_shape(const gprn_ctx* c, size_t cap)
+{ return SmallShape{cap, (size_t)c->G, (size_t)c->q, (size_t)c->p, (size_t)c->N, (size_t)c->ld, small_nmat(c)}; }
 
 void small_batch_free(gprn_ctx* c)
 {
@@ -670,10 +621,11 @@ void small_batch_free(gprn_ctx* c)
 
 static size_t small_bytes_per_eval(const gprn_ctx* c)
 {
-    const size_t nn = (size_t)c->ld * c->ld, d = (size_t)(c->p + 1) * c->q * c->N;
+    const SmallSlab v{small_shape(c, 1), nullptr, nullptr, nullptr, nullptr};
     const size_t ne = batch_mask_entries(c, false).size() + batch_mask_entries(c, true).size();   // (WT and C per entry)
-    return (small_nmat(c) * nn + 7 * (size_t)c->G * c->ld + 6 * d + 4 * (size_t)c->p * c->N + 256 +
-            ne * 2 * GPRN_TILE * c->ld) * sizeof(double) + (size_t)c->G * fill_program_bytes() * 2 + ne * 2 * sizeof(MaskLane);
+    // (the slabs; the pinned images of the state and of y - mean | variance; scalars and control words)
+    return (v.per_eval() + 2 * v.d() + 2 * v.pn() + 256 + ne * 2 * GPRN_TILE * c->ld) * sizeof(double) +
+           (size_t)c->G * fill_program_bytes() * 2 + ne * 2 * sizeof(MaskLane);
 }
 
 // evaluations one chunk may hold: what the memory budget pays for (4 G + q matrices of ld^2 doubles each and small change
@@ -690,23 +642,24 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
 {
     SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
     const int G = c->G, q = c->q, p = c->p, N = c->N, ld = c->ld;
-    if (m && m->cap >= n_eval && m->G == G && m->q == q && m->p == p && m->N == N && m->ld == ld && m->mask == c->d_mask) return GPRN_OK;
+    const SmallShape held = small_shape(c, m ? m->cap : 0);    // (what the buffers must be for, at their capacity)
+    if (m && m->cap >= n_eval && !memcmp(&m->v.s, &held, sizeof held) && m->mask == c->d_mask) return GPRN_OK;
     small_batch_free(c);
     m = new SmallBatchMem();
     c->small_batch = m;
     const int cap = std::max(n_eval, 16);
-    m->G = G; m->q = q; m->p = p; m->N = N; m->ld = ld;
+    SmallSlab& v = m->v;
+    v.s = small_shape(c, cap);
     m->mask = c->d_mask;
     const std::vector<int> ent[2] = {batch_mask_entries(c, false), batch_mask_entries(c, true)};
     const size_t ne0 = ent[0].size(), ne_all = ne0 + ent[1].size(), wc = (size_t)GPRN_TILE * ld;
     m->mask_ne[0] = (int)ne0; m->mask_ne[1] = (int)ent[1].size();
-    const size_t nn = (size_t)ld * ld, d = (size_t)(p + 1) * q * N, pn = (size_t)p * N, nscal = 3 * (size_t)G + (size_t)q * q;
-    const size_t nmat = small_nmat(c), nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
+    const size_t nscal = 3 * (size_t)G + (size_t)q * q, nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
     const bool bound = c->elbo_form == GPRN_ELBO_BOUND;          // (a change of the form frees these buffers: gprn_set_option)
-    TRY(m->own.alloc(c, &m->mats, (size_t)cap * nmat * nn));
-    TRY(m->own.alloc(c, &m->vecs, (size_t)cap * 7 * G * ld));
-    TRY(m->own.alloc(c, &m->state, 4 * (size_t)cap * d));
-    TRY(m->own.alloc(c, &m->yv, 2 * (size_t)cap * pn));
+    TRY(m->own.alloc(c, &v.mats, v.mats_count()));
+    TRY(m->own.alloc(c, &v.vecs, v.vecs_count()));
+    TRY(m->own.alloc(c, &v.states, v.state_count()));
+    TRY(m->own.alloc(c, &v.yv, v.yv_count()));
     TRY(m->own.alloc(c, &m->scal, (size_t)cap * nscal));
     TRY(m->own.alloc(c, &m->logdetK, (size_t)cap * G));
     TRY(m->own.alloc(c, &m->out4, (size_t)cap * 4));
@@ -740,31 +693,22 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     std::vector<MaskLane> ml(2 * (size_t)cap * ne_all);
     std::vector<double*> mt((size_t)cap * ne_all * GPRN_NBUF, nullptr), kd((size_t)cap * G);   // (kd: kptr_dense)
     for (int b = 0; b < cap; ++b) {
-        double* const mb = m->mats + (size_t)b * nmat * nn;
-        auto Kp = [&](int g) { return mb + (size_t)g * nn; };
-        auto KLp = [&](int g) { return mb + ((size_t)G + g) * nn; };
-        auto Bp = [&](int g) { return mb + (2 * (size_t)G + g) * nn; };
-        auto Xp = [&](int g) { return mb + (3 * (size_t)G + g) * nn; };
-        auto Kinvp = [&](int j) { return mb + (4 * (size_t)G + j) * nn; };
         double** const hb = hp.data() + (size_t)b * nptr;           // host image of this evaluation's tables
         double** const db = m->ptrs + (size_t)b * nptr;             // ... and where it lies on the device
         double** const h_setup = hb; double** const h_node = hb + (size_t)G * GPRN_NBUF; double** const h_weight = hb + 2 * (size_t)G * GPRN_NBUF;
         double** const h_kinv_tab = hb + 3 * (size_t)G * GPRN_NBUF; double** const h_kinv_out = h_kinv_tab + q; double** const h_Kptr = h_kinv_out + G;
         for (int g = 0; g < G; ++g) {
-            buf_row(h_setup + (size_t)g * GPRN_NBUF, Bp(g), KLp(g), Kp(g), KLp(g));   // set-up: BUF_B scratch, BUF_X = chol(K)^-1, BUF_K
+            buf_row(h_setup + (size_t)g * GPRN_NBUF, v.B(b, g), v.KLinv(b, g), v.K(b, g), v.KLinv(b, g));   // set-up: BUF_B scratch, BUF_X = chol(K)^-1, BUF_K
             buf_row(g < q ? h_node + (size_t)g * GPRN_NBUF : h_weight + (size_t)(g - q) * GPRN_NBUF,
-                    Bp(g), Xp(g), Kp(g), KLp(g));                                     // sweeps: B, X, K, chol(K)^-1
-            h_kinv_out[g] = (g >= 1 && g < q && !bound) ? Kinvp(g) : nullptr;
-            h_Kptr[g] = kd[(size_t)b * G + g] = Kp(g);
+                    v.B(b, g), v.X(b, g), v.K(b, g), v.KLinv(b, g));                  // sweeps: B, X, K, chol(K)^-1
+            h_kinv_out[g] = (g >= 1 && g < q && !bound) ? v.Kinv(b, g) : nullptr;
+            h_Kptr[g] = kd[(size_t)b * G + g] = v.K(b, g);
         }
-        for (int j = 0; j < q; ++j) h_kinv_tab[j] = (j >= 1 && !bound) ? Kinvp(j) : nullptr;
+        for (int j = 0; j < q; ++j) h_kinv_tab[j] = (j >= 1 && !bound) ? v.Kinv(b, j) : nullptr;
         double** const d_setup = db; double** const d_node = db + (size_t)G * GPRN_NBUF; double** const d_weight = db + 2 * (size_t)G * GPRN_NBUF;
         double** const d_kinv_tab = db + 3 * (size_t)G * GPRN_NBUF; double** const d_kinv_out = d_kinv_tab + q;
-        double* const vb = m->vecs + (size_t)b * 7 * G * ld;
-        auto vec = [&](int which, int slot0) { return vb + ((size_t)which * G + slot0) * ld; };
-        double* const yres = m->yv + (size_t)b * pn; double* const variance = m->yv + ((size_t)cap + b) * pn;
-        double* const st[4] = {m->state + (size_t)b * d, m->state + ((size_t)cap + b) * d, m->state + (2 * (size_t)cap + b) * d,
-                               m->state + (3 * (size_t)cap + b) * d};
+        double* const yres = v.yres(b); double* const variance = v.variance(b);
+        double* const st[4] = {v.state(0, b), v.state(1, b), v.state(2, b), v.state(3, b)};
         double* const scal = m->scal + (size_t)b * nscal;
         int* const ctl = m->ctl + (size_t)b * 4;
         int* const info = m->info + (size_t)b * 3 * G;
@@ -776,7 +720,8 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
                 pa[((size_t)par * 2 + ph) * cap + b] = SmallPhaseArgs{
                     (double* const*)(ph ? d_weight : d_node), m->gp_ids + s0, N, ld, p, q, yres, variance,
                     mu_in, var_in, mu_out, var_out, ctl,
-                    vec(0, s0), vec(1, s0), vec(2, s0), vec(3, s0), vec(4, s0), vec(5, s0), vec(6, s0),
+                    v.vec(b, SV_D, s0), v.vec(b, SV_S, s0), v.vec(b, SV_PRED, s0), v.vec(b, SV_Z, s0), v.vec(b, SV_U, s0),
+                    v.vec(b, SV_CS, s0), v.vec(b, SV_CT, s0),
                     scal + G, scal, info + (size_t)(1 + ph) * G, nullptr, c->d_mask};
                 // the lanes of the rows behind this half-sweep: evaluation-major, so that B evaluations are a prefix
                 const size_t ne = ent[ph].size(), first = ph ? (size_t)cap * ne0 : 0;
@@ -784,13 +729,13 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
                     const int g = ent[ph][e];
                     double* const wt = m->mask_wc + (((size_t)b * ne_all + (ph ? ne0 : 0) + e) * 2) * wc;
                     ml[(size_t)par * cap * ne_all + first + (size_t)b * ne + e] =
-                        MaskLane{Kp(g), vec(1, g), vec(6, g), wt, wt + wc, mu_out, var_out, ctl, g};
-                    buf_row(mt.data() + (first + (size_t)b * ne + e) * GPRN_NBUF, Bp(g), Xp(g), wt, wt + wc);
+                        MaskLane{v.K(b, g), v.vec(b, SV_S, g), v.vec(b, SV_CT, g), wt, wt + wc, mu_out, var_out, ctl, g};
+                    buf_row(mt.data() + (first + (size_t)b * ne + e) * GPRN_NBUF, v.B(b, g), v.X(b, g), wt, wt + wc);
                 }
             }
             ta[(size_t)par * cap + b] = SmallTailArgs{
                 (double* const*)d_node, (double* const*)d_weight, m->gp_ids, m->gp_ids + q, q, G - q, N, ld, p, q, G,
-                mu_out, var_out, bound ? yres : c->d_yraw, variance, vec(1, 0), (double* const*)d_kinv_tab, vec(4, 0), m->logdetK + (size_t)b * G,
+                mu_out, var_out, bound ? yres : c->d_yraw, variance, v.vec(b, SV_S, 0), (double* const*)d_kinv_tab, v.vec(b, SV_U, 0), m->logdetK + (size_t)b * G,
                 scal, m->out4 + (size_t)b * 4, m->ticket + b, ctl, m->hist + (size_t)b * (SB_K + 4),
                 m->hist + (size_t)b * (SB_K + 4) + SB_K, 0, 0, 0, info, 3 * G, c->d_mask};
         }
@@ -806,9 +751,9 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
         HIP_TRY(c, hipMemcpy(m->mask_tab, mt.data(), mt.size() * sizeof(double*), hipMemcpyHostToDevice));
     }
     char* pin_out = nullptr;
-    TRY(m->own.pin(c, &m->pin_in, layout_count<char>(batch_pin_in, cap, G, fill_program_bytes(), pn, d)));
-    TRY(m->own.pin(c, &pin_out, layout_count<char>(small_pin_out, cap, G, d, SB_K + 4)));
-    m->out = layout_at(pin_out, small_pin_out, cap, G, d, SB_K + 4);
+    TRY(m->own.pin(c, &m->pin_in, layout_count<char>(batch_pin_in, cap, G, fill_program_bytes(), v.pn(), v.d())));
+    TRY(m->own.pin(c, &pin_out, layout_count<char>(small_pin_out, cap, G, v.d(), SB_K + 4)));
+    m->out = layout_at(pin_out, small_pin_out, cap, G, v.d(), SB_K + 4);
     m->cap = cap;
     return GPRN_OK;
 }
@@ -823,6 +768,47 @@ int small_batch_reserve(gprn_ctx* c, int want, int* cap)
     return rc;
 }
 
+// One sweep of B evaluations side by side: small_sweep's sequence (api_sweep.hip) with grid y = evaluation -- node half-sweep,
+// weight half-sweep, tail, no host step between them.  par: the state copy the sweep starts from (its argument blocks, which
+// hold each evaluation's own loop words); sweep, hist_at: its number and its place in the group's ELBO history.
+// Under a data mask -- m->mask, which small_batch_ensure keeps the context's -- the masked kernels, and behind each half-sweep
+// the rows U of its entries for all B evaluations.
+static int small_batch_sweep(gprn_ctx* c, SmallBatchMem* m, int B, int par, int sweep, int hist_at, int max_iter, bool forced)
+{
+    const int G = c->G, q = c->q, cap = m->cap;
+    const bool masked = m->mask != nullptr;
+    const size_t ne_all = (size_t)m->mask_ne[0] + m->mask_ne[1];
+    auto lanes = [&](bool weights) { return (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + weights) * cap); };
+    auto phase = [&](bool weights) {
+        prof_begin(c, GPRN_T_DIAG);
+        with_flags([&](auto W, auto M) {
+            hipLaunchKernelGGL((k_small_phase_b<W, M>), dim3(weights ? G - q : q, B), dim3(256), 0, c->stream, lanes(weights));
+        }, weights, masked);
+        prof_end(c);
+    };
+    auto rows_u = [&](int ph) -> int {
+        if (!m->mask_ne[ph]) return GPRN_OK;
+        const size_t first = ph ? (size_t)cap * m->mask_ne[0] : 0;
+        MaskBatch mb = mask_batch_of(c, ph);
+        mb.lanes = m->mask_lanes + (size_t)par * cap * ne_all + first; mb.tab = m->mask_tab + first * GPRN_NBUF;
+        mb.n = B * m->mask_ne[ph];
+        return mask_rows_lanes(c, mb, c->N, c->ld);
+    };
+    phase(false);
+    TRY(order_small_batch(c, lanes(false), false, B, masked));   // (sequential order only)
+    TRY(rows_u(0));
+    phase(true);
+    TRY(order_small_batch(c, lanes(true), true, B, masked));
+    TRY(rows_u(1));
+    prof_begin(c, GPRN_T_VEC);
+    with_flags([&](auto M, auto F, auto BD) {
+        hipLaunchKernelGGL((k_small_tail_b<1, M, F, BD>), dim3(G, B), dim3(256), 0, c->stream,
+                           (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), sweep, hist_at, max_iter);
+    }, masked, forced, c->elbo_form == GPRN_ELBO_BOUND);
+    prof_end(c);
+    return GPRN_OK;
+}
+
 int small_batch_run(gprn_ctx* c, const BatchIo& io)
 {
     SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
@@ -834,15 +820,16 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     const double us_ensure = m->us_reserve;
     m->us_reserve = 0.0;
     hipStream_t st = c->stream;
-    TRY(batch_stage(c, io, m->pin_in, cap, BatchBufs{m->programs, m->yv, m->yv + (size_t)cap * io.yv, m->state, m->state + (size_t)cap * d},
+    TRY(batch_stage(c, io, m->pin_in, cap, BatchBufs{m->programs, m->v.yres(0), m->v.variance(0), m->v.state(0, 0), m->v.state(1, 0)},
                     st, t, &us_stage));
     HIP_TRY(c, hipMemsetAsync(m->ctl, 0, (size_t)B * 4 * sizeof(int), st));
     HIP_TRY(c, hipMemsetAsync(m->info, 0, (size_t)B * 3 * G * sizeof(int), st));    // (the kernels only raise them)
     // ---- set-up: every evaluation's G covariance matrices in one launch, their factors in another
     TRY(launch_fill_batch(c, m->programs, (double* const*)m->kptr_dense, B * G));
     prof_begin(c, GPRN_T_DIAG);
-    if (c->acc_opt != 0) hipLaunchKernelGGL((k_small_prior_b<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallPriorArgs*)m->prior_args);
-    else hipLaunchKernelGGL((k_small_prior_b<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallPriorArgs*)m->prior_args);
+    with_flags([&](auto ACC) {
+        hipLaunchKernelGGL((k_small_prior_b<1, ACC>), dim3(G, B), dim3(256), 0, st, (const SmallPriorArgs*)m->prior_args);
+    }, c->acc_opt != 0);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     // ---- the loop, SB_K sweeps per synchronisation
@@ -853,53 +840,14 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     int s = max_iter >= 1 ? 1 : 0;
     bool all_done = false;
     const int q = c->q;
-    // under a data mask: the masked kernels, and behind each half-sweep the rows U of its entries for all B evaluations
-    const bool masked = m->mask != nullptr;
-    if (masked && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
-    const size_t ne_all = (size_t)m->mask_ne[0] + m->mask_ne[1];
-    auto rows_u = [&](int par, int ph) -> int {
-        if (!m->mask_ne[ph]) return GPRN_OK;
-        const size_t first = ph ? (size_t)cap * m->mask_ne[0] : 0;
-        MaskBatch mb = mask_batch_of(c, ph);
-        mb.lanes = m->mask_lanes + (size_t)par * cap * ne_all + first; mb.tab = m->mask_tab + first * GPRN_NBUF;
-        mb.n = B * m->mask_ne[ph];
-        return mask_rows_lanes(c, mb, c->N, c->ld);
-    };
+    if (m->mask && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
     while (!all_done && s <= max_iter) {
         const int s0 = s;
         int nb = 0;
         const int nb_max = s0 <= 1 ? ELBO_LEAD : SB_K;         // (no verdict before trip 4, and most warm starts stop there)
         for (; nb < nb_max && s <= max_iter; ++nb, ++s) {
             const int par = (s <= 1 || (s & 1)) ? 0 : 1;          // sweep 0 and trip 1 start from copy A, then they alternate
-            prof_begin(c, GPRN_T_DIAG);
-            if (masked) hipLaunchKernelGGL((k_small_phase_bm<false>), dim3(q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 0) * cap));
-            else
-            hipLaunchKernelGGL((k_small_phase_b<false>), dim3(q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 0) * cap));
-            prof_end(c);
-            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 0) * cap, false, B, masked));   // (sequential order only)
-            if (masked) TRY(rows_u(par, 0));
-            prof_begin(c, GPRN_T_DIAG);
-            if (masked) hipLaunchKernelGGL((k_small_phase_bm<true>), dim3(G - q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 1) * cap));
-            else
-            hipLaunchKernelGGL((k_small_phase_b<true>), dim3(G - q, B), dim3(256), 0, st, (const SmallPhaseArgs*)(m->phase_args + ((size_t)par * 2 + 1) * cap));
-            prof_end(c);
-            TRY(order_small_batch(c, m->phase_args + ((size_t)par * 2 + 1) * cap, true, B, masked));
-            if (masked) TRY(rows_u(par, 1));
-            prof_begin(c, GPRN_T_VEC);
-#define GO_TBB(M, F) hipLaunchKernelGGL((k_small_tail_bound_b<1, M, F>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter)
-            if (c->elbo_form == GPRN_ELBO_BOUND) {
-                if (masked) { if (io.flags & GPRN_BATCH_FORCED) GO_TBB(true, true); else GO_TBB(true, false); }
-                else { if (io.flags & GPRN_BATCH_FORCED) GO_TBB(false, true); else GO_TBB(false, false); }
-            } else if (masked && (io.flags & GPRN_BATCH_FORCED))
-                hipLaunchKernelGGL((k_small_tail_bm<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
-            else if (masked)
-                hipLaunchKernelGGL((k_small_tail_bm<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
-            else if (io.flags & GPRN_BATCH_FORCED)
-                hipLaunchKernelGGL((k_small_tail_b<1, true>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
-            else
-                hipLaunchKernelGGL((k_small_tail_b<1, false>), dim3(G, B), dim3(256), 0, st, (const SmallTailArgs*)(m->tail_args + (size_t)par * cap), s, nb, max_iter);
-#undef GO_TBB
-            prof_end(c);
+            TRY(small_batch_sweep(c, m, B, par, s, nb, max_iter, (io.flags & GPRN_BATCH_FORCED) != 0));
         }
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(m->out.ctl, m->ctl, (size_t)B * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -925,13 +873,13 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     }
     if (io.mu_out && io.var_out) {
         for (int k = 0; k < 4; ++k)                            // (B evaluations of each copy, not the buffers' capacity)
-            HIP_TRY(c, hipMemcpyAsync(m->out.state + (size_t)k * cap * d, m->state + (size_t)k * cap * d, (size_t)B * d * sizeof(double),
+            HIP_TRY(c, hipMemcpyAsync(m->out.state + m->v.state_index(k, 0) * d, m->v.state(k, 0), (size_t)B * d * sizeof(double),
                                       hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         for (int b = 0; b < B; ++b) {
-            const bool in_b = iters[b] >= 1 && (iters[b] & 1);     // odd trips wrote copy B
-            memcpy(io.mu_out + (size_t)b * d, m->out.state + ((in_b ? 2 : 0) * (size_t)cap + b) * d, d * sizeof(double));
-            memcpy(io.var_out + (size_t)b * d, m->out.state + ((in_b ? 3 : 1) * (size_t)cap + b) * d, d * sizeof(double));
+            const size_t k = small_final_copy(iters[b]);           // (the pinned image has the slab's layout)
+            memcpy(io.mu_out + (size_t)b * d, m->out.state + m->v.state_index(k, b) * d, d * sizeof(double));
+            memcpy(io.var_out + (size_t)b * d, m->out.state + m->v.state_index(k + 1, b) * d, d * sizeof(double));
         }
     }
     const double us_states = t.lap();
@@ -939,40 +887,37 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
         // ---- the gradient of every evaluation's last committed sweep: grad.hip's batched pass over the B x G one-tile slots
         // (T = 1).  A stopped evaluation's launches were no-ops: X, s and both copies of its state are its last trip's; that
         // trip wrote copy B when odd.
-        const size_t nn = (size_t)c->ld * c->ld, nmat = small_nmat(c);
+        const SmallSlab& v = m->v;
         GradBatchIn in;
         in.N = c->N; in.ld = c->ld; in.T = 1; in.q = q; in.G = G; in.t = c->d_time;
-        in.state = m->state; in.state_stride = d; in.grad_exact = c->grad_exact; in.bound = c->elbo_form == GPRN_ELBO_BOUND; in.p = c->p;
+        in.state = v.states; in.state_stride = d; in.grad_exact = c->grad_exact; in.bound = c->elbo_form == GPRN_ELBO_BOUND; in.p = c->p;
         for (int b = 0; b < B; ++b) {
             if (!grad_batch_enter(io, b, in)) continue;
-            double* const mb = m->mats + (size_t)b * nmat * nn;
             for (int g = 0; g < G; ++g) {
                 in.rows.resize(in.rows.size() + GPRN_NBUF);
-                buf_row(&in.rows[in.rows.size() - GPRN_NBUF], mb + (2 * (size_t)G + g) * nn, mb + (3 * (size_t)G + g) * nn,
-                        mb + (size_t)g * nn, mb + ((size_t)G + g) * nn);
-                in.s.push_back(m->vecs + (size_t)b * 7 * G * c->ld + ((size_t)G + g) * c->ld);
+                buf_row(&in.rows[in.rows.size() - GPRN_NBUF], v.B(b, g), v.X(b, g), v.K(b, g), v.KLinv(b, g));
+                in.s.push_back(v.vec(b, SV_S, g));
             }
-            for (int j = 1; j < q && c->elbo_form == GPRN_ELBO_REFERENCE; ++j) in.kinv.push_back(mb + (4 * (size_t)G + j) * nn);
-            in.state_idx.push_back((iters[b] >= 1 && (iters[b] & 1) ? 2 * cap : 0) + b);
+            for (int j = 1; j < q && c->elbo_form == GPRN_ELBO_REFERENCE; ++j) in.kinv.push_back(v.Kinv(b, j));
+            in.state_idx.push_back((int)v.state_index(small_final_copy(iters[b]), b));
         }
         TRY(grad_batch_pass(c, c->kspec, in, grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c))));
     }
     const double us_grad = t.lap();
     if (io.pred.ns > 0) {
         // ---- the prediction of every evaluation's last committed sweep: midn.hip's pass over the B x G one-tile slots (T = 1),
-        // in the set-up's order.  s and ct are rows G + g and 6 G + g of the evaluation's vectors -- per (evaluation, latent
+        // in the set-up's order.  s and ct are two of the evaluation's seven vectors (batch_layout.h) -- per (evaluation, latent
         // GP) already, a stopped evaluation's are its last trip's: nothing was kept, two pitched copies bring them to the
         // pass's layout.  Its two blocks per slot live in matrices the loop has finished with (B's workspace, the prior's K).
-        const size_t nn = (size_t)c->ld * c->ld, nmat = small_nmat(c), gl = (size_t)G * c->ld, nv = (size_t)cap * gl;
+        const SmallSlab& v = m->v;
+        const size_t gl = (size_t)G * c->ld, nv = (size_t)cap * gl;
         if (!m->pred_tab) {
             std::vector<double*> rows((size_t)cap * G * GPRN_NBUF), kp((size_t)cap * G);
             for (int b = 0; b < cap; ++b)
                 for (int g = 0; g < G; ++g) {
-                    double* const mb = m->mats + (size_t)b * nmat * nn;
                     const size_t sl = (size_t)b * G + g;
-                    buf_row(&rows[sl * GPRN_NBUF], mb + (2 * (size_t)G + g) * nn, mb + (3 * (size_t)G + g) * nn, mb + (2 * (size_t)G + g) * nn,
-                            mb + (size_t)g * nn);
-                    kp[sl] = mb + (2 * (size_t)G + g) * nn;
+                    buf_row(&rows[sl * GPRN_NBUF], v.B(b, g), v.X(b, g), v.B(b, g), v.K(b, g));
+                    kp[sl] = v.B(b, g);
                 }
             TRY(m->own.alloc(c, &m->pred_vecs, 7 * nv));
             TRY(m->own.alloc(c, &m->pred_kptr, kp.size()));
@@ -990,9 +935,9 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
             m->pred_ns = io.pred.ns;
         }
         double* const pv = m->pred_vecs;
-        const size_t rowb = gl * sizeof(double);
-        HIP_TRY(c, hipMemcpy2DAsync(pv, rowb, m->vecs + gl, 7 * rowb, rowb, B, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpy2DAsync(pv + nv, rowb, m->vecs + 6 * gl, 7 * rowb, rowb, B, hipMemcpyDeviceToDevice, st));
+        const size_t rowb = gl * sizeof(double), pitch = v.vec_pitch() * sizeof(double);
+        HIP_TRY(c, hipMemcpy2DAsync(pv, rowb, v.vec(0, SV_S, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpy2DAsync(pv + nv, rowb, v.vec(0, SV_CT, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
         // (a launch's grid z / y is the number of slots: groups of evaluations that stay below its limit)
         const int group = std::max(1, 32768 / G);
         for (int e0 = 0; e0 < B; e0 += group) {

@@ -544,12 +544,12 @@ int vec_prep(gprn_ctx* c, const Phase& ph, bool weights)
     prof_begin(c, GPRN_T_VEC);
     const size_t o = (size_t)ph.slot0 * ph.ld;
     dim3 grid((ph.ld + 255) / 256, ph.nslots);
-#define GO_PREP(KER, M) hipLaunchKernelGGL(KER<M>, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld, \
-                           c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance, \
-                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev, (const uint8_t*)c->d_mask)
-    if (weights) { if (c->d_mask) GO_PREP(k_prep_weights, true); else GO_PREP(k_prep_weights, false); }
-    else         { if (c->d_mask) GO_PREP(k_prep_nodes, true);   else GO_PREP(k_prep_nodes, false); }
-#undef GO_PREP
+    auto go = [&](auto kernel) {                              // (two kernels, one argument list)
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
+                           c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance,
+                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev, (const uint8_t*)c->d_mask);
+    };
+    with_flags([&](auto M) { if (weights) go(k_prep_weights<M>); else go(k_prep_nodes<M>); }, c->d_mask != nullptr);
     LAUNCH_END(c);
 }
 
@@ -631,11 +631,11 @@ int vec_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_logdet)
     if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
     const size_t o = (size_t)ph.slot0 * ph.ld;
-#define GO_FIN(M) hipLaunchKernelGGL(k_finalize<M>, dim3(ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld, \
-                       c->p, c->q, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, c->d_var, \
-                       scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, ph.ev)
-    if (c->d_mask) GO_FIN(true); else GO_FIN(false);
-#undef GO_FIN
+    with_flags([&](auto M) {
+        hipLaunchKernelGGL(k_finalize<M>, dim3(ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
+                           c->p, c->q, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, c->d_var,
+                           scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, ph.ev);
+    }, c->d_mask != nullptr);
     LAUNCH_END(c);
 }
 
@@ -645,13 +645,12 @@ int vec_reduce_finalize(gprn_ctx* c, const Phase& ph, double* scal, bool with_lo
     if (!ph.nslots) return GPRN_OK;
     prof_begin(c, GPRN_T_VEC);
     const size_t o = (size_t)ph.slot0 * ph.ld, po = (size_t)ph.slot0 * ph.T * 2 * ph.ld;
-#define GO_RF(F, M) hipLaunchKernelGGL((k_reduce_finalize<F, M>), dim3((ph.ld + 255) / 256, ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N, \
-                       ph.ld, ph.T, c->p, c->q, c->d_part + po, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu, \
-                       c->d_var, scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal, \
-                       c->d_fin_terms + (size_t)ph.slot0 * 2 * ph.ld, c->d_fin_tickets + ph.slot0, ph.ev)
-    if (c->d_mask) { if (c->fenced_finalize) GO_RF(true, true); else GO_RF(false, true); }
-    else           { if (c->fenced_finalize) GO_RF(true, false); else GO_RF(false, false); }
-#undef GO_RF
+    with_flags([&](auto F, auto M) {
+        hipLaunchKernelGGL((k_reduce_finalize<F, M>), dim3((ph.ld + 255) / 256, ph.nslots), dim3(256), 0, c->stream, ph.slot_gp, ph.N,
+                           ph.ld, ph.T, c->p, c->q, c->d_part + po, c->d_d + o, c->d_s + o, c->d_z + o, c->d_cs + o, c->d_ct + o, c->d_mu,
+                           c->d_var, scal + c->G, with_logdet ? (double* const*)ph.ptrs : (double* const*)nullptr, scal,
+                           c->d_fin_terms + (size_t)ph.slot0 * 2 * ph.ld, c->d_fin_tickets + ph.slot0, ph.ev);
+    }, c->fenced_finalize != 0, c->d_mask != nullptr);
     LAUNCH_END(c);
 }
 
@@ -675,54 +674,29 @@ int vec_dot_self(gprn_ctx* c, const Phase& ph, const double* a, double* out, hip
     LAUNCH_END(c);
 }
 
-// scal: the sweep's per-GP scalars (logdetB | trBinv | muKmu | q1); part: 3 * ELBO_BLOCKS doubles of scratch
-int vec_elbo(gprn_ctx* c, double* out4, const double* scal, double* part, hipStream_t stream)
-{
-    if (!stream) stream = c->stream;
-    prof_begin(c, GPRN_T_VEC, stream);
-    const EvalMap one{nullptr, 0, 0, 0, 0};
-    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;
-#define GO_LL(M, B, Y, MASK) hipLaunchKernelGGL((k_loglike_partial<M, B>), dim3(ELBO_BLOCKS), dim3(256), 0, stream, c->N, c->p, c->q, \
-                           c->d_mu, c->d_var, Y, c->d_variance, part, (const int*)nullptr, one, (const uint8_t*)MASK)
-#define GO_EF(B) hipLaunchKernelGGL(k_elbo_final<B>, dim3(1), dim3(64), 0, stream, c->N, c->p, c->q, part, \
-                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, \
-                       (const int*)nullptr, one)
-    if (bound) {
-        if (c->d_mask) GO_LL(true, true, c->d_yres, c->d_mask); else GO_LL(false, true, c->d_yres, nullptr);
-        GO_EF(true);
-    } else {
-        if (c->d_mask) GO_LL(true, false, c->d_yraw, c->d_mask); else GO_LL(false, false, c->d_yraw, nullptr);
-        GO_EF(false);
-    }
-#undef GO_LL
-#undef GO_EF
-    LAUNCH_END(c);
-}
-
-// the same for the n evaluations listed in d_evals (midn.hip): evaluation b reads its own state, variance and per-GP scalars
-// (strides ev) and writes out4 + 4 b; part: n x 3 * ELBO_BLOCKS doubles of scratch
+// The ELBO of the n evaluations listed in d_evals (midn.hip): evaluation b reads its own state, variance and per-GP scalars
+// (strides ev) and writes out4 + 4 b.  scal: the per-GP scalars (logdetB | trBinv | muKmu | q1); part: n x 3 * ELBO_BLOCKS
+// doubles of scratch
 int vec_elbo_evals(gprn_ctx* c, const EvalMap& ev, const int* d_evals, int n, double* out4, const double* scal, double* part,
                    hipStream_t stream)
 {
     if (!n) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
-    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;
     // (the mask is the data's: one for all evaluations; the bound form's residual is the evaluation's own, stride ev.yv)
-#define GO_LL(M, B, Y, MASK) hipLaunchKernelGGL((k_loglike_partial<M, B>), dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q, \
-                           c->d_mu, c->d_var, Y, c->d_variance, part, d_evals, ev, (const uint8_t*)MASK)
-#define GO_EF(B) hipLaunchKernelGGL(k_elbo_final<B>, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part, \
-                       c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, ev)
-    if (bound) {
-        if (c->d_mask) GO_LL(true, true, c->d_yres, c->d_mask); else GO_LL(false, true, c->d_yres, nullptr);
-        GO_EF(true);
-    } else {
-        if (c->d_mask) GO_LL(true, false, c->d_yraw, c->d_mask); else GO_LL(false, false, c->d_yraw, nullptr);
-        GO_EF(false);
-    }
-#undef GO_LL
-#undef GO_EF
+    with_flags([&](auto M, auto B) {
+        hipLaunchKernelGGL((k_loglike_partial<M, B>), dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
+                           c->d_mu, c->d_var, B ? c->d_yres : c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)c->d_mask);
+        hipLaunchKernelGGL(k_elbo_final<B>, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part,
+                           c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, ev);
+    }, c->d_mask != nullptr, c->elbo_form == GPRN_ELBO_BOUND);
     LAUNCH_END(c);
+}
+
+// ... of the context's one problem: one evaluation, no list, the null map
+int vec_elbo(gprn_ctx* c, double* out4, const double* scal, double* part, hipStream_t stream)
+{
+    return vec_elbo_evals(c, EvalMap{nullptr, 0, 0, 0, 0}, nullptr, 1, out4, scal, part, stream);
 }
 
 // quirk Q1 for the evaluations of a batch (midn.hip; node slots node-major: slot = k * n_eval + a): per (node k, node j > k,

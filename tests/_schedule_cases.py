@@ -87,22 +87,28 @@ def problem(masked):
     return pr
 
 
-def _one_sweep(name, pr):
-    """sweep(mu, var) -> (ELBO, mu, var, parts) of configuration `name`: the `sweep` that the module's `sweeps` loops over."""
-    masked, order, form = CONFIGS[name]
+def compose_sweep(pr, masked, order, form):
+    """sweep(mu, var) -> (ELBO, mu, var, parts) of the combination (data mask?, sweep order, ELBO form) on the problem `pr`
+    (Kf, Kw, Lf, Lw, y_resid, y_raw, yerr2, jitt2, mask): which restatement each combination is held against, stated once
+    (tests/test_small_variants_gpu.py composes its one-tile references through here too)."""
     Kf, Kw, Lf, Lw, y, y_raw, e2, j2, mask = (pr[k] for k in ('Kf', 'Kw', 'Lf', 'Lw', 'y_resid', 'y_raw', 'yerr2', 'jitt2', 'mask'))
+    assert (mask is not None) == masked
     if form == 'bound':                                    # tests/_bound_ref.sweeps, route 'B'
         return lambda mu, var: _bound_ref.sweep(Kf, Kw, Lf, Lw, y, e2, j2, mu, var, mask=mask, order=order, route='B')
-    if name == 'plain':                                    # oracle/cpu_ref
+    if not masked and order == 'reference':                # oracle/cpu_ref
         inv = _order_ref._kf_inv(Lf)
         return lambda mu, var: cpu_ref.sweep_B(Kf, Kw, Lf, Lw, y, y_raw, e2, j2, mu, var, Kf_inv=inv)
-    if name == 'mask':                                     # tests/_mask_ref.sweeps
+    if order == 'reference':                               # tests/_mask_ref.sweeps
         return lambda mu, var: _mask_ref.sweep(Kf, Kw, y, y_raw, e2, j2, mu, var, mask)
-    if name == 'sequential':                               # tests/_order_ref.sweeps
+    if not masked:                                         # tests/_order_ref.sweeps
         inv = _order_ref._kf_inv(Lf)
         return lambda mu, var: _order_ref.sweep(Kf, Kw, Lf, Lw, y, y_raw, e2, j2, mu, var, 'sequential', Kf_inv=inv)
-    assert name == 'order_mask'                            # tests/_order_mask_ref.sweeps
-    return lambda mu, var: _order_mask_ref.sweep(Kf, Kw, y, y_raw, e2, j2, mu, var, mask, 'sequential')
+    return lambda mu, var: _order_mask_ref.sweep(Kf, Kw, y, y_raw, e2, j2, mu, var, mask, 'sequential')   # tests/_order_mask_ref.sweeps
+
+
+def _one_sweep(name, pr):
+    """The `sweep` of configuration `name` that the module's `sweeps` loops over."""
+    return compose_sweep(pr, *CONFIGS[name])
 
 
 def run_sweeps(sweep, mu, var, n=N_SWEEPS):

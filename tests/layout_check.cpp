@@ -2,7 +2,8 @@
 // -- one and three evaluations, q = 1 (no K_j^-1 tables), with and without mask entries, odd int counts, a fill program whose
 // size is no multiple of 8 -- and checks, with the counts restated here: the size of the null-base walk is where the real
 // walk ends, every range is aligned for its type, inside the block, and disjoint from the others; the per-sweep tables are one
-// contiguous tail.  Built and run by tests/test_batch_layout.py.
+// contiguous tail.  The one-tile slabs (walk_small): q = 1 and 3, reference and bound form, 1 and 17 evaluations, every offset
+// against its formula written out.  Built and run by tests/test_batch_layout.py.
 #include "batch_layout.h"
 
 #include <stdio.h>
@@ -124,9 +125,64 @@ static void walk(const MidShape& s, size_t N, size_t program)
     }
 }
 
+// The one-tile slabs (SmallSlab): the four blocks at the sizes small_batch_ensure allocates -- restated here --, every
+// range inside its block and disjoint from the others, and every offset equal to the formula written out.
+static void walk_small(size_t cap, size_t q, size_t p, size_t N, size_t ld, bool bound)
+{
+    const size_t G = q * (p + 1), nmat = bound ? 4 * G : 4 * G + q, nn = ld * ld, d = (p + 1) * q * N, pn = p * N;
+    SmallSlab v{SmallShape{cap, G, q, p, N, ld, nmat}, nullptr, nullptr, nullptr, nullptr};
+    CHECK(v.mats_count() == cap * nmat * nn && v.vecs_count() == cap * 7 * G * ld && v.state_count() == 4 * cap * d &&
+          v.yv_count() == 2 * cap * pn, "small slab: the blocks' sizes");
+    CHECK(v.per_eval() == nmat * nn + 7 * G * ld + 4 * d + 2 * pn && v.vec_pitch() == 7 * G * ld && v.d() == d && v.pn() == pn,
+          "small slab: one evaluation's share");
+    Block bm(v.mats_count() * sizeof(double)), bv(v.vecs_count() * sizeof(double)), bs(v.state_count() * sizeof(double)),
+        by(v.yv_count() * sizeof(double));
+    v.mats = (double*)bm.at; v.vecs = (double*)bv.at; v.states = (double*)bs.at; v.yv = (double*)by.at;
+    std::vector<Range> rm, rv, rs, ry;
+    for (size_t b = 0; b < cap; ++b) {
+        double* const mb = v.mats + b * nmat * nn;
+        for (size_t g = 0; g < G; ++g) {
+            CHECK(v.K(b, g) == mb + g * nn && v.KLinv(b, g) == mb + (G + g) * nn && v.B(b, g) == mb + (2 * G + g) * nn &&
+                  v.X(b, g) == mb + (3 * G + g) * nn, "small slab: the matrices of evaluation %zu, latent GP %zu", b, g);
+            rm.push_back(RANGE(v.K(b, g), nn)); rm.push_back(RANGE(v.KLinv(b, g), nn));
+            rm.push_back(RANGE(v.B(b, g), nn)); rm.push_back(RANGE(v.X(b, g), nn));
+        }
+        for (size_t j = 0; j < q && !bound; ++j) {
+            CHECK(v.Kinv(b, j) == mb + (4 * G + j) * nn, "small slab: K^-1 of evaluation %zu, node %zu", b, j);
+            rm.push_back(RANGE(v.Kinv(b, j), nn));
+        }
+        const SmallVec which[7] = {SV_D, SV_S, SV_PRED, SV_Z, SV_U, SV_CS, SV_CT};
+        for (size_t w = 0; w < 7; ++w)
+            for (size_t g = 0; g < G; ++g) {
+                CHECK(v.vec(b, which[w], g) == v.vecs + b * 7 * G * ld + (w * G + g) * ld, "small slab: vector %zu of slot %zu", w, g);
+                rv.push_back(RANGE(v.vec(b, which[w], g), ld));
+            }
+        for (size_t k = 0; k < 4; ++k) {
+            CHECK(v.state(k, b) == v.states + (k * cap + b) * d && v.state_index(k, b) == k * cap + b, "small slab: state copy %zu", k);
+            rs.push_back(RANGE(v.state(k, b), d));
+        }
+        CHECK(v.yres(b) == v.yv + b * pn && v.variance(b) == v.yv + (cap + b) * pn, "small slab: y - mean | variance");
+        ry.push_back(RANGE(v.yres(b), pn)); ry.push_back(RANGE(v.variance(b), pn));
+    }
+    // (s and ct as the prediction's pitched copies read them: rows G + g and 6 G + g of an evaluation's 7 G)
+    CHECK(v.vec(0, SV_S, 0) == v.vecs + G * ld && v.vec(0, SV_CT, 0) == v.vecs + 6 * G * ld, "small slab: where s and ct start");
+    check("small slab mats", bm.at, bm.bytes, bm.bytes, rm);
+    check("small slab vecs", bv.at, bv.bytes, bv.bytes, rv);
+    check("small slab states", bs.at, bs.bytes, bs.bytes, rs);
+    check("small slab yv", by.at, by.bytes, by.bytes, ry);
+    CHECK(small_final_copy(0) == 0 && small_final_copy(1) == 2 && small_final_copy(2) == 0 && small_final_copy(7) == 2,
+          "the copy of the last committed sweep: B after an odd trip count");
+}
+
 int main()
 {
     int shapes = 0;
+    for (size_t cap : {1, 17})
+        for (size_t q : {1, 3})
+            for (int bound = 0; bound < 2; ++bound) {
+                walk_small(cap, q, 2, 45, 128, bound != 0);
+                ++shapes;
+            }
     for (size_t cap : {1, 3})
         for (size_t q : {1, 2})
             for (size_t p : {1, 2})
