@@ -35,6 +35,23 @@ class BackendError(RuntimeError):
     pass
 
 
+class MeanParams:
+    """What stands in for ``y_resid`` in ``Context.elbocalc_batch`` when y - mean is to be formed on the device
+    (gprn_elbocalc_batch_means): the B rows of mean parameters (B, n_mean_params) -- the programs are the context's
+    (``set_mean``) -- and the raw data (p N).  After the call: ``resid`` (B, p N), the y - mean the call formed, and, where
+    asked for (``want_mean_grad``), ``mean_grad`` (B, n_mean_params), the bound form's mean entries."""
+
+    def __init__(self, params, y_raw, want_mean_grad=False):
+        self.params = np.ascontiguousarray(params, dtype=np.float64)
+        self.y_raw = np.asarray(y_raw, dtype=float).ravel()
+        self.want_mean_grad = bool(want_mean_grad)
+        self.resid = self.mean_grad = None
+
+    def host_resid(self, ctx):
+        """y - mean through gprn_eval_mean, for the entry points that take a host array"""
+        return self.y_raw[None] - ctx.eval_mean(self.params).reshape(self.params.shape[0], -1)
+
+
 # every exported entry point: name -> (restype, argtypes).  tests/test_abi.py
 # checks this table against include/gprn_hip.h and the built library.
 SIGNATURES = {
@@ -57,6 +74,9 @@ SIGNATURES = {
     'gprn_factor_priors': (c_int, [c_void_p]),
     'gprn_set_muvar': (c_int, [c_void_p, _dp, _dp]),
     'gprn_get_muvar': (c_int, [c_void_p, _dp, _dp]),
+    'gprn_set_mean': (c_int, [c_void_p, c_int, POINTER(c_int32), c_int, _dp, c_int]),
+    'gprn_eval_mean': (c_int, [c_void_p, c_int, _dp, c_int, c_int, _dp, _dp]),
+    'gprn_eval_mean_grad': (c_int, [c_void_p, c_int, _dp, c_int, c_int, _dp, _dp]),
     'gprn_sweep': (c_int, [c_void_p, c_int, c_int, _dp, _dp]),
     'gprn_predict': (c_int, [c_void_p, c_int, _dp, _dp, _dp]),
     'gprn_predict_upload': (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp]),
@@ -84,6 +104,8 @@ SIGNATURES = {
                             POINTER(c_int), _dp, _dp]),
     'gprn_elbocalc_batch_grad': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, _dp, POINTER(c_int),
                                  POINTER(c_int), POINTER(c_int), _dp, _dp, _dp]),
+    'gprn_elbocalc_batch_means': (c_int, [c_void_p, c_int, _dp, c_int, _dp, c_int, _dp, _dp, _dp, c_int, c_int, _dp, POINTER(c_int),
+                                  POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp]),
     'gprn_elbocalc_batch_predict': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, _dp,
                                             POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp, _dp]),
     'gprn_predict_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
@@ -250,6 +272,30 @@ class Context:
         self._check(self._lib.gprn_set_kernel(
             self._h, int(gp), flat.ctypes.data_as(POINTER(c_int32)), flat.shape[0],
             _ptr(par), par.size, int(bool(add_nugget))), 'set_kernel')
+
+    def set_mean(self, output, ops, params):
+        """The mean program of `output` (gprn_set_mean; meanfunc's ``_device_program``); ops None or empty: no mean."""
+        flat = np.ascontiguousarray(np.asarray(ops if ops is not None else [], dtype=np.int32).reshape(-1, 3))
+        par = _f64(np.atleast_1d(params)) if flat.shape[0] else np.zeros(0)
+        self._check(self._lib.gprn_set_mean(self._h, int(output), flat.ctypes.data_as(POINTER(c_int32)), flat.shape[0],
+                                            _ptr(par), par.size), 'set_mean')
+
+    def _eval_mean(self, fn, what, mean_params, t, rows):
+        mp = np.atleast_2d(_f64(mean_params))
+        ts = None if t is None else _f64(np.atleast_1d(t))
+        nt = self.N if ts is None else ts.size
+        out = np.empty((mp.shape[0], rows(mp.shape[1]), nt))
+        self._check(fn(self._h, mp.shape[0], _ptr(mp), mp.shape[1], nt, None if ts is None else _ptr(ts), _ptr(out)), what)
+        return out
+
+    def eval_mean(self, mean_params, t=None):
+        """The outputs' means under B parameter rows (B, n_mean_params) at the times t (None: the data's), (B, p, nt):
+        gprn_eval_mean."""
+        return self._eval_mean(self._lib.gprn_eval_mean, 'eval_mean', mean_params, t, lambda n: self.p)
+
+    def eval_mean_grad(self, mean_params, t=None):
+        """d mean / d every mean parameter, (B, n_mean_params, nt): gprn_eval_mean_grad."""
+        return self._eval_mean(self._lib.gprn_eval_mean_grad, 'eval_mean_grad', mean_params, t, lambda n: n)
 
     def upload_K(self, gp, K):
         K = _f64(K, (self.N, self.N))
@@ -475,7 +521,8 @@ class Context:
         kp = _f64(np.atleast_2d(kernel_params))
         B = kp.shape[0]
         d = (self.p + 1) * self.q * self.N
-        yr = _f64(np.reshape(y_resid, (B, self.p * self.N)))
+        means = y_resid if isinstance(y_resid, MeanParams) else None
+        yr = None if means is not None else _f64(np.reshape(y_resid, (B, self.p * self.N)))
         jt = _f64(np.reshape(jitters, (B, self.p)))
         m0, v0 = _f64(np.reshape(mu, (B, d))), _f64(np.reshape(var, (B, d)))
         elbo = np.empty(B)
@@ -484,7 +531,16 @@ class Context:
         vo = np.empty((B, d)) if want_state else None
         ip = lambda a: a.ctypes.data_as(POINTER(c_int))
         grads = np.zeros((B, kp.shape[1])) if want_grad else None
-        if want_grad or forced:
+        if means is not None:
+            means.resid = np.empty((B, self.p * self.N))
+            means.mean_grad = np.zeros((B, means.params.shape[1])) if means.want_mean_grad and want_grad else None
+            rc = self._lib.gprn_elbocalc_batch_means(self._h, B, _ptr(kp), kp.shape[1], _ptr(means.params), means.params.shape[1],
+                                                     _ptr(jt), _ptr(m0), _ptr(v0), int(max_iter),
+                                                     GPRN_BATCH_FORCED if forced else 0, _ptr(elbo), ip(it), ip(cv), ip(info),
+                                                     _ptr(mo) if want_state else None, _ptr(vo) if want_state else None,
+                                                     _ptr(grads) if want_grad else None, _ptr(means.resid),
+                                                     None if means.mean_grad is None else _ptr(means.mean_grad))
+        elif want_grad or forced:
             rc = self._lib.gprn_elbocalc_batch_grad(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
                                                     int(max_iter), GPRN_BATCH_FORCED if forced else 0, _ptr(elbo), ip(it),
                                                     ip(cv), ip(info), _ptr(mo) if want_state else None,
@@ -521,6 +577,8 @@ class Context:
             raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
         B = kp.shape[0]
         d = (self.p + 1) * self.q * self.N
+        if isinstance(y_resid, MeanParams):                 # (this entry point takes a host array: y - mean through gprn_eval_mean)
+            y_resid = y_resid.host_resid(self)
         yr, jt, m0, v0 = _f64(y_resid), _f64(jitters), _f64(mu), _f64(var)
         if yr.size != B * self.p * self.N:
             raise ValueError(f'y_resid must be (B, p, N) = ({B}, {self.p}, {self.N}), got {yr.shape}')

@@ -479,6 +479,7 @@ extern "C" int gprn_set_data(gprn_ctx* c, int N, int p, int q, const double* tim
     c->ld = ((N + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
     c->T = c->ld / GPRN_TILE;
     c->kspec.assign(c->G, KernelSpec());
+    c->mean_spec.assign(p, MeanSpec());
     c->K.assign(c->G, nullptr);
     c->KLinv.assign(c->G, nullptr);
     c->Kinv.assign(q, nullptr);

@@ -775,9 +775,10 @@ size_t batch_budget_bytes(gprn_ctx* c)
 static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
                                const double* y_resid, const double* jitters, const double* mu, const double* var,
                                int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
-                               double* mu_out, double* var_out, double* grad_out, const BatchPred* pred)
+                               double* mu_out, double* var_out, double* grad_out, const BatchPred* pred,
+                               const BatchMeans* means = nullptr)
 {
-    if (!c || !c->N || n_eval < 1 || !kernel_params || !y_resid || !jitters || !mu || !var || max_iter < 0 || !elbo ||
+    if (!c || !c->N || n_eval < 1 || !kernel_params || (!y_resid && !means) || !jitters || !mu || !var || max_iter < 0 || !elbo ||
         !iterations || !converged || !info || (!mu_out != !var_out) || (flags & ~GPRN_BATCH_FORCED))
         return bad(c, "elbocalc_batch: bad argument");
     if (grad_out && max_iter < 1) return bad(c, "elbocalc_batch_grad: a gradient needs a committed sweep (max_iter >= 1)");
@@ -800,7 +801,7 @@ static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_par
     TRY(batch_reserve(c, small ? small_batch_reserve : mid_batch_reserve, n_eval, &cap));
     const BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info,
                      mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N, flags, grad_out,
-                     pred ? *pred : BatchPred{}};
+                     pred ? *pred : BatchPred{}, means ? *means : BatchMeans{}};
     // (with grad_out each chunk ends with the gradient pass of its evaluations, before the next chunk overwrites the slabs;
     // with a prediction, with the prediction pass)
     for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(run(c, io.slice(e0, std::min(cap, n_eval - e0))));
@@ -815,6 +816,32 @@ extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* k
     DeviceLock lock_(c);
     return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
                                iterations, converged, info, mu_out, var_out, grad_out, nullptr);
+}
+
+// gprn_elbocalc_batch_grad with the outputs' mean programs (gprn_set_mean) evaluated on the device in place of a y - mean from the
+// host (include/gprn_hip.h; meanfunc.py:276-293, _utils.py:62-118, meanfield.py:382-411, 623-624): batch_stage launches
+// k_mean_eval_b behind its copies, and a chunk ends with k_mean_grad_b over what its loops left in the slabs (mean.hip)
+extern "C" int gprn_elbocalc_batch_means(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                         const double* mean_params, int n_mean_params, const double* jitters, const double* mu,
+                                         const double* var, int max_iter, int flags, double* elbo, int* iterations, int* converged,
+                                         int* info, double* mu_out, double* var_out, double* grad_out, double* resid_out,
+                                         double* mean_grad_out)
+{
+    DeviceLock lock_(c);
+    if (!c || !c->N || n_eval < 1 || n_mean_params < 0 || (n_mean_params && !mean_params))
+        return bad(c, "elbocalc_batch_means: bad argument");
+    if (mean_grad_out && c->elbo_form != GPRN_ELBO_BOUND) {
+        c->err = "elbocalc_batch_means: mean_grad_out needs the bound form of the ELBO (the reference form reads the raw data, quirk Q3)";
+        return GPRN_E_UNSUPPORTED;
+    }
+    if (mean_grad_out && max_iter < 1) return bad(c, "elbocalc_batch_means: a gradient needs a committed sweep (max_iter >= 1)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    CallScratch scr(c);
+    BatchMeans means;
+    TRY(mean_batch_upload(c, scr, n_eval, mean_params, n_mean_params, &means));
+    means.resid_out = resid_out; means.grad_out = mean_grad_out;
+    return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, nullptr, jitters, mu, var, max_iter, flags, elbo,
+                               iterations, converged, info, mu_out, var_out, grad_out, nullptr, &means);
 }
 
 // gprn_elbocalc_batch_grad(grad_out = NULL) with, per evaluation, gprn_predict's posterior form at the end of its loop (include/
@@ -895,15 +922,17 @@ int batch_stage(gprn_ctx* c, const BatchIo& io, char* pin, int cap, const BatchB
             const double j2 = io.jitters[(size_t)b * p + i] * io.jitters[(size_t)b * p + i];
             for (int n = 0; n < N; ++n) h.variance[b * io.yv + (size_t)i * N + n] = j2 + c->h_yerr2[(size_t)i * N + n];
         }
-    memcpy(h.yres, io.y_resid, B * io.yv * sizeof(double));
+    if (!io.means.programs) memcpy(h.yres, io.y_resid, B * io.yv * sizeof(double));
     memcpy(h.mu, io.mu, B * io.state * sizeof(double));
     memcpy(h.var, io.var, B * io.state * sizeof(double));
     *us_host = t.lap();
     HIP_TRY(c, hipMemcpyAsync(dst.programs, h.programs, (size_t)B * G * fill_program_bytes(), hipMemcpyHostToDevice, stream));
-    HIP_TRY(c, hipMemcpyAsync(dst.yres, h.yres, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (!io.means.programs) HIP_TRY(c, hipMemcpyAsync(dst.yres, h.yres, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
     HIP_TRY(c, hipMemcpyAsync(dst.variance, h.variance, B * io.yv * sizeof(double), hipMemcpyHostToDevice, stream));
     HIP_TRY(c, hipMemcpyAsync(dst.mu, h.mu, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
     HIP_TRY(c, hipMemcpyAsync(dst.var, h.var, B * io.state * sizeof(double), hipMemcpyHostToDevice, stream));
+    // gprn_elbocalc_batch_means: y - mean is formed where it is kept, behind the copies on the staging stream (mean.hip)
+    if (io.means.programs) TRY(mean_stage_resid(c, io.means, B, dst.yres, stream));
     return GPRN_OK;
 }
 

@@ -101,6 +101,12 @@ struct KernelSpec {            // how latent GP g gets its K
     double params[GPRN_MAX_KPARAMS];
 };
 
+struct MeanSpec {              // the mean program of one output (gprn_set_mean, mean.hip); n_ops = 0: no mean
+    int n_ops = 0, n_params = 0;
+    int32_t ops[3 * GPRN_MAX_MEAN_OPS] = {0};
+    double params[GPRN_MAX_KPARAMS] = {0};
+};
+
 // Several evaluations of ONE problem side by side (midn.hip: an optimiser's simplex, emcee's walkers): the slots of a phase
 // then belong to different evaluations, each with its own copy of the per-problem arrays.  slot_eval: slot -> evaluation
 // (null: one evaluation, every stride unused); the strides are doubles between two evaluations' copies.
@@ -177,6 +183,7 @@ struct gprn_ctx {
 
     // ---- per latent GP, persistent across sweeps (only for GPs this rank needs)
     std::vector<KernelSpec> kspec;   // G
+    std::vector<MeanSpec> mean_spec; // p: the outputs' mean programs (mean.hip), cleared by gprn_set_data
     std::vector<double*> K;          // G   (ld x ld), null when not held
     std::vector<double*> KLinv;      // G   chol(K)^-1 lower
     std::vector<double*> Kinv;       // q   K_j^-1 lower, only for nodes j>=1 that feed quirk Q1
@@ -565,6 +572,32 @@ struct BatchPred {
                          out_mean ? out_mean + out : nullptr, out_var ? out_var + out : nullptr, G, p};
     }
 };
+// gprn_elbocalc_batch_means (mean.hip): the outputs' mean programs and every evaluation's mean parameters, on the device for
+// the length of the call; where y - mean and the bound form's mean entries go (host, either may be null)
+struct BatchMeans {
+    const void* programs = nullptr;        // device [p] MeanProgram
+    const double* params = nullptr;        // device [n][n_params]
+    int n_params = 0;
+    double tmean = 0.0;                    // mean of the data times (Linear)
+    double* resid_out = nullptr;           // [n][p N]
+    double* grad_out = nullptr;            // [n][n_params]
+    BatchMeans from(int e0, size_t yv) const
+    {
+        return BatchMeans{programs, params ? params + (size_t)e0 * n_params : nullptr, n_params, tmean,
+                          resid_out ? resid_out + e0 * yv : nullptr, grad_out ? grad_out + (size_t)e0 * n_params : nullptr};
+    }
+};
+// mean.hip: y_raw - mean of io's evaluations into `yres` (device, [n][p N]) on `stream`, behind the copies of batch_stage ...
+int mean_stage_resid(gprn_ctx* c, const BatchMeans& mn, int n, double* yres, hipStream_t stream);
+// ... and the bound form's mean entries of a chunk whose loops have ended, from what they left in the slabs: y - mean and the
+// variances ([n][p N] each), evaluation e's state at state + state_idx[e] * state_stride.  w: the context the launch goes through
+int mean_grad_pass(gprn_ctx* c, gprn_ctx* w, const BatchMeans& mn, int n, const int* info, const double* yres, const double* variance,
+                   const double* state, size_t state_stride, const std::vector<int>& state_idx);
+
+// ... the call's programs and parameters to the device (scr owns them): GPRN_E_ARG where n_params is not the programs' sum
+struct CallScratch;
+int mean_batch_upload(gprn_ctx* c, CallScratch& scr, int n_eval, const double* mean_params, int n_params, BatchMeans* out);
+
 // One call of gprn_elbocalc_batch -- its pointers and counts -- or a run of its evaluations (slice)
 struct BatchIo {
     int n; const double* kparams; int n_kpar; const double *y_resid, *jitters, *mu, *var; int max_iter;
@@ -573,12 +606,13 @@ struct BatchIo {
     int flags;                             // GPRN_BATCH_FORCED: no stop rule, max_iter committed trips each
     double* grad_out;                      // [n][n_kpar]: the gradient of each evaluation's last committed sweep, or null
     BatchPred pred{};                      // gprn_elbocalc_batch_predict: the prediction pass behind the chunk's loop (ns = 0: none)
+    BatchMeans means{};                    // gprn_elbocalc_batch_means: y - mean is formed on the device (programs = null: y_resid is read)
     BatchIo slice(int e0, int ne) const    // evaluations [e0, e0 + ne)
     {
-        return BatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, y_resid + e0 * yv, jitters + (size_t)e0 * p, mu + e0 * state,
+        return BatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, y_resid ? y_resid + e0 * yv : nullptr, jitters + (size_t)e0 * p, mu + e0 * state,
                        var + e0 * state, max_iter, elbo + e0, iters + e0, conv + e0, info + e0,
                        mu_out ? mu_out + e0 * state : nullptr, var_out ? var_out + e0 * state : nullptr, p, state, yv,
-                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0)};
+                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0), means.from(e0, yv)};
     }
 };
 // grad.hip: the steps of gprn_grad_elbo over the evaluations of a batch's chunk whose loops have ended, slots = evaluations x

@@ -498,6 +498,11 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
         }
         TRY(grad_batch_pass(w, c->kspec, in, grad_batch_left(c, (size_t)m->cap * mid_bytes_per_eval(c))));
     }
+    if (io.means.grad_out) {
+        std::vector<int> idx(B);
+        for (int b = 0; b < B; ++b) idx[b] = b;
+        TRY(mean_grad_pass(c, w, io.means, B, io.info, w->d_yres, w->d_variance, w->d_mu, d, idx));
+    }
     const double us_grad = t.lap();
     if (predict) {
         // ---- the prediction of every evaluation's last committed sweep, over the full chunk in the set-up's order

@@ -903,6 +903,11 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
         }
         TRY(grad_batch_pass(c, c->kspec, in, grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c))));
     }
+    if (io.means.grad_out) {
+        std::vector<int> idx(B);
+        for (int b = 0; b < B; ++b) idx[b] = (int)m->v.state_index(small_final_copy(iters[b]), b);
+        TRY(mean_grad_pass(c, c, io.means, B, info, m->v.yres(0), m->v.variance(0), m->v.states, d, idx));
+    }
     const double us_grad = t.lap();
     if (io.pred.ns > 0) {
         // ---- the prediction of every evaluation's last committed sweep: midn.hip's pass over the B x G one-tile slots (T = 1),

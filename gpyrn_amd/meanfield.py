@@ -90,6 +90,18 @@ class inference:
             or QuasiPeriodic keeps its closed form and its bits; kernels without a device program (user subclasses, a Sum
             that holds a two-argument kernel) are contracted on the host as before.  An attribute that may be set later:
             it goes to the device with every set-up.
+        device_means: bool (default False), keyword only
+            Whether the side-by-side forms evaluate the mean functions of all their parameter vectors on the GPU.
+            ``nELBO_batch``, ``mcmc(batch=True)`` and ``nELBO_and_grad_batch`` then hand the library the mean columns of the
+            B full vectors (a third layout of ``_batch_stage``: kernel, mean and jitter columns sliced in one go, no
+            per-vector ``set_parameters``) and ``gprn_elbocalc_batch_means`` forms ``y - mean`` where the batch keeps it;
+            with ``elbo='bound'`` the mean entries of the gradient come back from the same call.  ``predict_batch`` /
+            ``posterior_predictive`` take the means at t* from one ``gprn_eval_mean`` call, and
+            ``predict_batch(from_sweeps=True)`` its ``y - mean`` likewise.  All of it where every mean has a device program
+            (``meanfunc``'s ``_device_program``: Constant, Linear, Parabola, Cubic, Sine, Keplerian and their sums and
+            products).  Off, or where a program is missing (``MultiConstant``, user subclasses), anything but Constant means
+            is evaluated on the host, one vector after the other, as before.  An attribute that may be set later.  Not
+            with ``comm``.
         elbo: 'reference' (default) or 'bound', keyword only
             WHICH function is reported as the ELBO (option ``"elbo_form"`` of the library; not in the reference).
             'reference': the reference's number, quirk for quirk -- node j >= 1 paired with the cumulative covariance
@@ -121,7 +133,7 @@ class inference:
 
     def __init__(self, q: int, time: Array, *args, device=None, comm=None, mask=None, sweep_order='reference',
                  batch_under_mask=False, exact_derivatives=False, sequential_under_mask=False, elbo='reference',
-                 predict='reference'):
+                 predict='reference', device_means=False):
         self.q = q
         self.time = time
         self.N = self.time.size
@@ -147,6 +159,7 @@ class inference:
         self.batch_under_mask = bool(batch_under_mask)
         self.exact_derivatives = bool(exact_derivatives)
         self.sequential_under_mask = bool(sequential_under_mask)
+        self.device_means = bool(device_means)
 
         self._components_set = False
         self._frozen_mask = np.array([])
@@ -1374,7 +1387,23 @@ class inference:
         n_k = sum(k.pars.size for k in kernels)
         plain_kernels = all(sp[2].size == k.pars.size and np.array_equal(sp[2], k.pars) for sp, k in zip(specs, kernels))
         plain_means = all(m_ is None or type(m_) is meanfunc.Constant for m_ in means)
-        if plain_kernels and plain_means and state[0] is not None:
+        programs = None if plain_means else self._mean_programs(means)
+        if plain_kernels and programs is not None and state[0] is not None:
+            # the third layout (``device_means``): as the one below, but every mean has a device program -- the kernel, mean
+            # and jitter columns are slices of the B full vectors, and y - mean of all B vectors is formed on the device inside
+            # the batch call (gprn_elbocalc_batch_means: `yr` carries the mean columns, not an array)
+            full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
+            full[:, ~self.frozen_mask] = np.array(sets)
+            kp = full[:, :n_k]
+            n_m = sum(par.size for _, par in programs)
+            for i, (ops, par) in enumerate(programs):
+                ctx.set_mean(i, ops, par)
+            yr = _hip.MeanParams(full[:, n_k:n_k + n_m], y_raw, want_mean_grad=self._elbo == 'bound')
+            jt = full[:, n_k + n_m:]
+            m0 = np.tile(np.ravel(state[0]), (B, 1))
+            v0 = np.tile(np.ravel(state[1]), (B, 1))
+            self.set_parameters(sets[-1])
+        elif plain_kernels and plain_means and state[0] is not None:
             # every program's parameters ARE its kernel's, the means are constants and the start is the stored state:
             # the B problems are slices of the B full parameter vectors (nodes, weights, means, jitters: meanfield.py:193-202)
             full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
@@ -1410,7 +1439,7 @@ class inference:
                     mu, var = self._initMuVar(nodes, weights, jitters)
                 m0.append(np.ravel(mu))
                 v0.append(np.ravel(var))
-        return ctx, np.array(kp), np.array(yr), np.array(jt), np.array(m0), np.array(v0)
+        return ctx, np.array(kp), yr if isinstance(yr, _hip.MeanParams) else np.array(yr), np.array(jt), np.array(m0), np.array(v0)
 
     # ------------------------------------------------ prediction for many vectors
     def _predict_stage(self, sets, tstar):
@@ -1626,6 +1655,20 @@ class inference:
         mean, var = np.array(means_), np.array(vars_)
         return (mean, var, np.array(lats)) if separate else (mean, var)
 
+    def _mean_programs(self, means):
+        """[(ops, params)] per output -- the empty program for a mean that is None -- where ``device_means`` is on and
+        every mean has a device program; else None: the caller evaluates on the host as it always has."""
+        if not self.device_means or self._comm is not None:
+            return None
+        programs = []
+        for m_ in means:
+            pg = ([], np.zeros(0)) if m_ is None else \
+                m_._device_program() if isinstance(m_, meanfunc.meanFunction) else None
+            if pg is None:
+                return None
+            programs.append(pg)
+        return programs
+
     def _mean_values_batch(self, sets, tstar):
         """The mean functions at `tstar` for B vectors, each at its own parameters: ``(B, p, n*)``.  Constant (or no) means
         are read from the vectors' own columns (nodes, weights, means, jitters: meanfield.py:193-202); anything else is
@@ -1644,6 +1687,21 @@ class inference:
                 if m_ is not None:
                     out[:, i, :] = full[:, col:col + 1]
                     col += 1
+            self.set_parameters(sets[-1])
+            return out
+        programs = self._mean_programs(means)
+        if programs is not None and all(x.size in (n_free, n_all) for x in sets):
+            # every mean has a device program: the mean columns of the B full vectors in one slice, one call
+            free = ~self.frozen_mask
+            full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
+            for b, x in enumerate(sets):
+                full[b, free] = x[free] if x.size == n_all else x
+            col = sum(k.pars.size for k in chain(self.nodes, self.weights))
+            n_mpar = sum(par.size for _, par in programs)
+            ctx = self._backend()
+            for i, (ops, par) in enumerate(programs):
+                ctx.set_mean(i, ops, par)
+            out = ctx.eval_mean(full[:, col:col + n_mpar], tstar)
             self.set_parameters(sets[-1])
             return out
         out = []
@@ -1959,6 +2017,23 @@ class inference:
         w = (np.asarray(resid, dtype=float) - fit) / (jitters[:, :, None]**2 + self.yerr2[None])
         if self.mask is not None:
             w = np.where(self.mask[None], w, 0.0)
+        programs = self._mean_programs(self.means)
+        n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
+        if programs is not None and all(np.ndim(x) == 1 and np.size(x) in (n_free, n_all) for x in sets):
+            # ``device_means``: d mean / d theta of all B vectors in ONE gprn_eval_mean_grad call, contracted here
+            free = ~self.frozen_mask
+            full = np.tile(self.get_parameters(include_frozen=True), (len(sets), 1))
+            for b, x in enumerate(sets):
+                full[b, free] = x[free] if np.size(x) == n_all else x
+            n_k = sum(k.pars.size for k in chain(self.nodes, self.weights))
+            n_m = sum(par.size for _, par in programs)
+            ctx = self._backend()
+            for i, (ops, par) in enumerate(programs):
+                ctx.set_mean(i, ops, par)
+            dm = ctx.eval_mean_grad(full[:, n_k:n_k + n_m])
+            owner = np.repeat(np.arange(self.p), [par.size for _, par in programs])
+            self.set_parameters(sets[-1])
+            return np.einsum('bkn,bkn->bk', dm, w[:, owner])
         rows = []
         for b, x in enumerate(sets):
             self.set_parameters(x)
@@ -2037,8 +2112,10 @@ class inference:
             elbo, _, _, info, mu_f, var_f, g_k = self._batch_keep(res)
             n_m = n_all - n_k - self.p
             if self._elbo == 'bound':
-                resid = np.reshape(yr, (len(sets), self.p, self.N))
-                grads = np.concatenate((g_k, self._mean_grads_batch(sets, jt, mu_f, resid).reshape(len(sets), n_m),
+                on_device = isinstance(yr, _hip.MeanParams)        # (device_means: y - mean and the mean entries came with the call)
+                resid = np.reshape(yr.resid if on_device else yr, (len(sets), self.p, self.N))
+                mean_rows = yr.mean_grad if on_device else self._mean_grads_batch(sets, jt, mu_f, resid)
+                grads = np.concatenate((g_k, mean_rows.reshape(len(sets), n_m),
                                         self._jitter_grads_batch(jt, mu_f, var_f, resid=resid)), axis=1)
             else:
                 grads = np.concatenate((g_k / self.q, np.zeros((len(sets), n_m)), self._jitter_grads_batch(jt, mu_f, var_f)), axis=1)

@@ -73,6 +73,18 @@ enum { GPRN_OP_PUSH = 0, GPRN_OP_ADD = 1, GPRN_OP_MUL = 2 };
 #define GPRN_MAX_OPS 32
 #define GPRN_MAX_KPARAMS 64
 
+/* ---- mean ids of the mean programs (gprn_set_mean; csrc/mean_eval.h; meanfunc.py line numbers) ---- */
+enum {
+    GPRN_M_CONSTANT = 0,            /* :120-135 */
+    GPRN_M_LINEAR = 1,              /* :190-208, slope (t - mean(t)) + intercept */
+    GPRN_M_PARABOLA = 2,            /* :211-229 */
+    GPRN_M_CUBIC = 3,               /* :232-251 */
+    GPRN_M_SINE = 4,                /* :254-273 */
+    GPRN_M_KEPLERIAN = 5,           /* :276-293, a stub in the reference: P, K, e, w, Tp */
+    GPRN_M_COUNT = 6
+};
+#define GPRN_MAX_MEAN_OPS 15        /* eight leaves and the seven operators between them */
+
 /* ---- context ---- */
 int gprn_device_count(void);
 /* Replaces nothing in the reference (it has no device).  One context per model; contexts on one device share the
@@ -136,6 +148,50 @@ int gprn_factor_priors(gprn_ctx* ctx);
  * meanfield.py:473-489 ---- */
 int gprn_set_muvar(gprn_ctx* ctx, const double* mu, const double* var);
 int gprn_get_muvar(gprn_ctx* ctx, double* mu, double* var);
+
+/* ---- mean programs (new): the means of the outputs evaluated on the device for many parameter vectors at once.  The
+ * reference evaluates a mean per call on the host (meanfield.py:382-411, 623-624) and left the Keplerian a stub
+ * (meanfunc.py:276-293 over _utils.keplerian, _utils.py:62-118, whose iteration does not converge for e > 0 and is not
+ * restated).  A program is a kernel program's postfix form -- (GPRN_OP_PUSH, GPRN_M_* id, offset of the leaf's parameters in
+ * `params`), GPRN_OP_ADD, GPRN_OP_MUL (meanfunc.py:49-117) -- of at most GPRN_MAX_MEAN_OPS triples, eight leaves.
+ * gprn_set_mean (meanfunc.py:276-293, _utils.py:62-118, meanfield.py:382-411, 623-624): the program of `output`; n_ops = 0
+ * clears it (the output then has no mean: 0 everywhere).  params: the program's parameters as they stand (n_params of
+ * them; they fix the count, the entry points below take their own).  It touches no set-up and no committed sweep;
+ * gprn_set_data clears every program.  GPRN_E_ARG: a malformed program, a leaf whose parameters run past n_params. */
+int gprn_set_mean(gprn_ctx* ctx, int output, const int32_t* ops, int n_ops, const double* params, int n_params);
+/* gprn_eval_mean (meanfunc.py:276-293, _utils.py:62-118, meanfield.py:382-411, 623-624): out[e][i][n] = mean_i(t_n) under
+ * evaluation e's parameters.  mean_params: (n_eval, n_mean_params), a row the outputs' program parameters in output order
+ * (n_mean_params their sum, else GPRN_E_ARG); t: nt times, NULL: the data times (nt ignored); out: (n_eval, p, nt).
+ * Linear subtracts the mean of the nt times of the call (meanfunc.py:204).  A Keplerian with e < 0, e >= 1, P <= 0 or a
+ * non-finite parameter is NaN at every time, in that evaluation only.  Each value is within
+ * (4 |m| + 2 kappa) 2^-53 of the exact one, kappa = sum_u |u dm/du| over t, the parameters and the rounded intermediates
+ * (tests/golden/mean_highprec, tests/test_mean_gpu.py), BJD times included.  n_eval <= 65535. */
+int gprn_eval_mean(gprn_ctx* ctx, int n_eval, const double* mean_params, int n_mean_params, int nt, const double* t,
+                   double* out);
+/* gprn_eval_mean_grad (meanfunc.py:276-293, _utils.py:62-118, meanfield.py:382-411, 623-624; not in the reference):
+ * out[e][k][n] = d mean_i(t_n) / d mean_params[e][k], i the output parameter k belongs to -- a parameter's row belongs to its
+ * own output; out: (n_eval, n_mean_params, nt).  Closed forms (csrc/mean_eval.h), the same arguments, limits and bound as
+ * gprn_eval_mean. */
+int gprn_eval_mean_grad(gprn_ctx* ctx, int n_eval, const double* mean_params, int n_mean_params, int nt, const double* t,
+                        double* out);
+/* gprn_elbocalc_batch_means (meanfunc.py:276-293, _utils.py:62-118, meanfield.py:382-411, 623-624; not in the reference):
+ * gprn_elbocalc_batch_grad (below) with mean_params (n_eval, n_mean_params; the layout of gprn_eval_mean) in place of y_resid:
+ * y - mean of every evaluation is formed on the device from the data of gprn_set_data and the programs of gprn_set_mean, on
+ * the staging stream behind the chunk's copies, where the batch keeps it -- no host array is read.  Chunks slice mean_params as
+ * they slice everything else.  Two more optional outputs: resid_out (n_eval, p N), the y - mean it formed; mean_grad_out
+ * (n_eval, n_mean_params), the bound form's mean entries sum_n w_n d mean_i(t_n) / d theta_k, w = ((y - mean) - sum_j mu_w_ij
+ * mu_f_j) / v, from each evaluation's final state, y - mean and variances as its loop left them in the chunk's buffers (both
+ * batch paths); masked entries are selected away (NaN y / yerr there reach no arithmetic); the sum runs in a fixed order: two
+ * calls return the same bits; a row of zeros where info > 0.  elbo, iterations, converged, info, the states and grad_out are
+ * bit for bit those of gprn_elbocalc_batch_grad given the resid_out this call returns.  A Keplerian out of range makes that
+ * evaluation's y - mean, ELBO and rows NaN and no other's.  Refusals: those of gprn_elbocalc_batch; GPRN_E_UNSUPPORTED for
+ * mean_grad_out under the reference form of the ELBO (quirk Q3: the reported ELBO does not read the means); GPRN_E_ARG where
+ * n_mean_params is not the sum of the programs' parameters.  An output whose mean has no program cannot be expressed here: the
+ * caller (inference._batch_stage) keeps to gprn_elbocalc_batch_grad then. */
+int gprn_elbocalc_batch_means(gprn_ctx* ctx, int n_eval, const double* kernel_params, int n_kernel_params,
+                              const double* mean_params, int n_mean_params, const double* jitters, const double* mu,
+                              const double* var, int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
+                              double* mu_out, double* var_out, double* grad_out, double* resid_out, double* mean_grad_out);
 
 /* ---- the hot loop: n_sweeps x ELBOaux (meanfield.py:651-710 = _updateSigMu
  * :713-893 + _entropy :1069-1093 + _expectedLogPrior :992-1067 +
