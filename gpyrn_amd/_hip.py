@@ -108,6 +108,8 @@ SIGNATURES = {
                                   POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp]),
     'gprn_elbocalc_batch_predict': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, _dp,
                                             POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp, _dp]),
+    'gprn_elbocalc_batch_draws': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, c_int, _dp, _dp,
+                                          POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
     'gprn_predict_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
     'gprn_test_predict_fill': (c_int, [c_void_p, c_int, c_int, _dp, c_int, _dp, c_int, c_int, c_int, _dp, _dp, _dp, _dp]),
     'gprn_test_fill_rect': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, c_double, c_int, c_int, c_int, _dp, _dp, _dp,
@@ -609,6 +611,63 @@ class Context:
         self._check(rc, 'elbocalc_batch_predict')
         shape = (B, self.p + 1, self.q, self.N)
         return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), lm, lv, om, ov)
+
+    def elbocalc_batch_draws(self, kernel_params, y_resid, jitters, mu, var, max_iter, tstar, z, forced=False, latent=True,
+                             outputs=True):
+        """B independent ELBOcalc loops side by side, each followed by joint draws from the posterior it leaves
+        (gprn_elbocalc_batch_draws): the arrays of ``elbocalc_batch``, tstar (n*), the standard normals z (B, G, n, n*).
+        Returns (elbo, iterations, converged, info, mu_out, var_out, lat_draws, out_draws, nuggets, draw_info): the first six
+        what ``elbocalc_batch(want_state=True)`` returns, to the bit; the latent draws (B, G, n, n*) -- row b what
+        ``predict_draws()`` returns in the posterior form right after ``elbocalc`` ran vector b's loop alone from
+        (mu_b, var_b), with z_b -- or None without `latent`; sum_j w o f per output, (B, p, n, n*), without mean functions
+        and noise, or None without `outputs`; the nugget of every (vector, latent GP), (B, G); draw_info (B,), > 0 where a
+        vector's last rung failed.  Rows of an evaluation with info > 0 or draw_info > 0 are NaN.  forced
+        (GPRN_BATCH_FORCED): no stop rule, exactly max_iter committed sweeps each.  None where the library has no
+        side-by-side form for this problem."""
+        if not (latent or outputs):
+            raise ValueError('elbocalc_batch_draws: ask for the latent draws, the output draws or both')
+        kp = _f64(kernel_params)
+        if kp.ndim != 2 or kp.shape[0] < 1:
+            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        B = kp.shape[0]
+        d = (self.p + 1) * self.q * self.N
+        if isinstance(y_resid, MeanParams):                 # (this entry point takes a host array: y - mean through gprn_eval_mean)
+            y_resid = y_resid.host_resid(self)
+        yr, jt, m0, v0 = _f64(y_resid), _f64(jitters), _f64(mu), _f64(var)
+        if yr.size != B * self.p * self.N:
+            raise ValueError(f'y_resid must be (B, p, N) = ({B}, {self.p}, {self.N}), got {yr.shape}')
+        if jt.size != B * self.p:
+            raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
+        if m0.size != B * d or v0.size != B * d:
+            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
+        ts = _f64(np.ravel(tstar))
+        if ts.size < 1:
+            raise ValueError('tstar is empty')
+        ns = ts.size
+        z = _f64(z)
+        if z.ndim != 4 or z.shape[0] != B or z.shape[1] != self.G or z.shape[2] < 1 or z.shape[3] != ns:
+            raise ValueError(f'z must be (B, G, n, n*) = ({B}, {self.G}, n, {ns}), got {z.shape}')
+        if int(max_iter) < 1:
+            raise ValueError('elbocalc_batch_draws: a draw needs a committed sweep (max_iter >= 1)')
+        nd = z.shape[2]
+        elbo = np.empty(B)
+        it, cv, info, dinfo = (np.zeros(B, dtype=np.int32) for _ in range(4))
+        mo, vo = np.empty((B, d)), np.empty((B, d))
+        lat = np.empty((B, self.G, nd, ns)) if latent else None
+        out = np.empty((B, self.p, nd, ns)) if outputs else None
+        nug = np.zeros((B, self.G))
+        ip = lambda a: a.ctypes.data_as(POINTER(c_int))
+        opt = lambda a: None if a is None else _ptr(a)
+        rc = self._lib.gprn_elbocalc_batch_draws(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
+                                                 int(max_iter), GPRN_BATCH_FORCED if forced else 0, ns, _ptr(ts), nd, _ptr(z),
+                                                 _ptr(elbo), ip(it), ip(cv), ip(info), _ptr(mo), _ptr(vo), opt(lat), opt(out),
+                                                 _ptr(nug), ip(dinfo))
+        if rc == GPRN_E_UNSUPPORTED:
+            return None
+        self._check(rc, 'elbocalc_batch_draws')
+        shape = (B, self.p + 1, self.q, self.N)
+        return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), lat, out, nug,
+                dinfo.astype(int))
 
     def predict_batch(self, kernel_params, mu, var, tstar, jitters=None, latent=True, outputs=True):
         """gprn_predict for B parameter vectors side by side (gprn_predict_batch): kernel_params (B, n_kpar), mu / var (B, d)

@@ -96,6 +96,21 @@ struct CallScratch {
     }
 };
 
+// ---- api_more.hip: the steps of gprn_predict_cov / gprn_predict_draws behind the means, over G matrices -- the latent GPs of
+// one call (every latent GP is local -- one rank -- and slot s = latent GP s) or the slots = evaluations x latent GPs of a
+// batch's draw pass (midn.hip batch_draw_pass).  Geometry and device memory: C (G ns_pad^2); draws: the factor's B and X
+// (2 G ns_pad^2), Z and L Z (2 G nd_pad ns_pad); matrix g of each at g times its size
+struct CovWork {
+    int G, ns, ns_pad, Ts, ld, nd, nd_pad;
+    size_t nn;
+    double *C = nullptr, *F = nullptr, *X = nullptr, *Z = nullptr, *LZ = nullptr, *out = nullptr, *lat = nullptr;
+    double** t_C = nullptr;                           // the matrices of C as a table
+};
+int cov_subtract(gprn_ctx* c, CallScratch& scr, CovWork& w, const std::vector<double*>& WT);
+int cov_ladder(gprn_ctx* c, CallScratch& scr, const CovWork& w, std::vector<int> pending, bool first_ends, std::vector<double>& nu,
+               std::vector<int>& fail);
+int cov_lz(gprn_ctx* c, CallScratch& scr, const CovWork& w, const std::function<int()>& normals);
+
 // the two events of a rate diagnostic
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;

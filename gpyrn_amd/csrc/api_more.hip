@@ -429,20 +429,10 @@ struct CovRequest {
     int info_gp = -1;
 };
 
-// Geometry and device memory of one call, shared by the parts of cov_after (each runs behind predict_impl's means, PredAfter:
-// every latent GP is local -- one rank -- and slot s = latent GP s): C (G ns_pad^2); draws: the factor's B and X
-// (2 G ns_pad^2), Z and L Z (2 G nd_pad ns_pad)
-struct CovWork {
-    int G, ns, ns_pad, Ts, ld, nd, nd_pad;
-    size_t nn;
-    double *C = nullptr, *F = nullptr, *X = nullptr, *Z = nullptr, *LZ = nullptr, *out = nullptr, *lat = nullptr;
-    double** t_C = nullptr;                           // the matrices of C as a table
-};
-
 // C = K** - W W^T, symmetric
 static int cov_conditional(gprn_ctx* c, CallScratch& scr, const PredState& st, CovWork& w)
 {
-    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad, ld = w.ld;
+    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad;
     const size_t nn = w.nn;
     // ---- K** at t* into C (identity padding); the caller's matrix for a host-evaluated kernel
     for (int g = 0; g < G; ++g) {
@@ -464,11 +454,19 @@ static int cov_conditional(gprn_ctx* c, CallScratch& scr, const PredState& st, C
         HIP_TRY(c, hipMemcpyAsync(Cg, pad.data(), nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    // ---- C -= W W^T: lower tiles (bt, at), K = ld (W^T's columns beyond N are zero), diagonal tiles lower blocks only
+    return cov_subtract(c, scr, w, c->predWT);
+}
+
+// ---- C -= W W^T over w.G matrices, WT[g] = W^T of matrix g (ns_pad x ld): lower tiles (bt, at), K = ld (W^T's columns beyond N
+// are zero), diagonal tiles lower blocks only; then the upper triangle from the lower one.  Leaves w.t_C, the matrices as a table
+int cov_subtract(gprn_ctx* c, CallScratch& scr, CovWork& w, const std::vector<double*>& WT)
+{
+    const int G = w.G, ns_pad = w.ns_pad, ld = w.ld;
+    const size_t nn = w.nn;
     std::vector<double*> rows((size_t)G * GPRN_NBUF, nullptr);
     for (int g = 0; g < G; ++g) {
         rows[(size_t)g * GPRN_NBUF + BUF_B] = w.C + (size_t)g * nn;
-        rows[(size_t)g * GPRN_NBUF + BUF_KLINV] = c->predWT[g];
+        rows[(size_t)g * GPRN_NBUF + BUF_KLINV] = WT[g];
     }
     double** t_pred = nullptr;
     TRY(scr.table(&t_pred, rows));
@@ -526,24 +524,27 @@ static int cov_outputs(gprn_ctx* c, CallScratch& scr, const PredState& st, const
     return GPRN_OK;
 }
 
-// ---- the ladder: factor C_g + nu_g I for every latent GP still pending in ONE phase of geometry (ns, ns_pad, Ts)
-// (its task lists replace the context's: every other factorisation rebuilds them for its own T).  L_g is left in F;
-// rq.info > 0: the last rung failed for rq.info_gp
-static int cov_ladder(gprn_ctx* c, CallScratch& scr, const CovWork& w, CovRequest& rq)
+// ---- the ladder: factor C_g + nu_g I for every matrix still pending in ONE phase of geometry (ns, ns_pad, Ts)
+// (its task lists replace the context's: every other factorisation rebuilds them for its own T).  L_g is left in F.
+// pending: the matrices to factor (the others are left alone); nu: every matrix's nugget, 1.25e-12 going in, the rung it
+// ended on coming out; fail[g] > 0: the pivot at which the last rung failed for g.  first_ends: the first such verdict ends the
+// ladder for everybody (one call's latent GPs: the call fails); else the others go on (a batch's slots)
+int cov_ladder(gprn_ctx* c, CallScratch& scr, const CovWork& w, std::vector<int> pending, bool first_ends, std::vector<double>& nu,
+               std::vector<int>& fail)
 {
     const int G = w.G, ns = w.ns, ns_pad = w.ns_pad;
     const size_t nn = w.nn;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream2));
     HIP_TRY(c, hipStreamSynchronize(c->stream3)); if (c->stream4) HIP_TRY(c, hipStreamSynchronize(c->stream4));
-    std::vector<int> pending(G);
-    std::vector<double> nu(G, 1.25e-12);
-    for (int g = 0; g < G; ++g) pending[g] = g;
+    nu.assign(G, 1.25e-12);
+    fail.assign(G, 0);
+    bool ended = false;
     double **t_fac = nullptr, **t_src = nullptr, **t_dst = nullptr, *d_nu = nullptr;
     int* d_inf = nullptr;
     TRY(scr.alloc(&t_fac, (size_t)G * GPRN_NBUF));
     TRY(scr.alloc(&t_src, G)); TRY(scr.alloc(&t_dst, G));
     TRY(scr.alloc(&d_nu, G)); TRY(scr.alloc(&d_inf, G));
-    while (!pending.empty() && !rq.info) {
+    while (!pending.empty() && !ended) {
         const int np = (int)pending.size();
         std::vector<double*> fr((size_t)np * GPRN_NBUF, nullptr), src(np), dst(np);
         std::vector<double> nup(np);
@@ -573,7 +574,8 @@ static int cov_ladder(gprn_ctx* c, CallScratch& scr, const CovWork& w, CovReques
             const int g = pending[b];
             if (inf[b] <= 0) continue;
             if (nu[g] >= 1.25e-6 * 0.5) {            // the last rung failed
-                if (!rq.info) { rq.info = inf[b]; rq.info_gp = g; }
+                if (!ended) fail[g] = inf[b];
+                ended = first_ends;
                 continue;
             }
             nu[g] *= 100.0;
@@ -581,26 +583,23 @@ static int cov_ladder(gprn_ctx* c, CallScratch& scr, const CovWork& w, CovReques
         }
         pending.swap(again);
     }
-    if (rq.nugget_out) memcpy(rq.nugget_out, nu.data(), G * sizeof(double));
     return GPRN_OK;
 }
 
-// ---- L Z for every draw: out tile (dt, nt) = Z[dt, 0:nt+1] L[nt, 0:nt+1]^T, K = (nt + 1) 128 (L is zero beyond); then the
-// draws of the latent GPs and of the outputs, to the host
-static int cov_draw(gprn_ctx* c, CallScratch& scr, const PredState& st, const CovWork& w, const CovRequest& rq)
+// ---- L Z for every draw of w.G matrices: out tile (dt, nt) = Z[dt, 0:nt+1] L[nt, 0:nt+1]^T, K = (nt + 1) 128 (L is zero
+// beyond), into w.LZ.  normals: brings the normals to w.Z (nd_pad x ns_pad per matrix, zero padding), behind the launch that
+// clears L's diagonal tiles above the diagonal
+int cov_lz(gprn_ctx* c, CallScratch& scr, const CovWork& w, const std::function<int()>& normals)
 {
-    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad, nd = w.nd, nd_pad = w.nd_pad;
+    const int G = w.G, ns_pad = w.ns_pad, nd_pad = w.nd_pad;
     const size_t nn = w.nn;
     std::vector<double*> rows(G, nullptr);
     for (int g = 0; g < G; ++g) rows[g] = w.F + (size_t)g * nn;
-    double **t_L = nullptr, **t_mm = nullptr, **t_LZ = nullptr;
+    double **t_L = nullptr, **t_mm = nullptr;
     TRY(scr.table(&t_L, rows));
     hipLaunchKernelGGL(k_zero_diag_upper, dim3(w.Ts, G), dim3(256), 0, c->stream, t_L, ns_pad);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemsetAsync(w.Z, 0, (size_t)G * nd_pad * ns_pad * sizeof(double), c->stream));
-    for (int g = 0; g < G; ++g)
-        HIP_TRY(c, hipMemcpy2DAsync(w.Z + (size_t)g * nd_pad * ns_pad, (size_t)ns_pad * sizeof(double), rq.z + (size_t)g * nd * ns,
-                                    (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), nd, hipMemcpyHostToDevice, c->stream));
+    TRY(normals());
     rows.assign((size_t)G * GPRN_NBUF, nullptr);
     for (int g = 0; g < G; ++g) {
         rows[(size_t)g * GPRN_NBUF + BUF_B] = w.F + (size_t)g * nn;
@@ -616,10 +615,24 @@ static int cov_draw(gprn_ctx* c, CallScratch& scr, const PredState& st, const Co
                                      tile_modes(CM_SET, 0, 0)});
     TileTask* d_t = nullptr;
     TRY(scr.tasks(&d_t, tasks));
-    TRY(launch_tiles(c, d_t, tasks.size(), t_mm, G, ns_pad, GPRN_T_UPDATE, c->stream,
-                     tasks.size() * (size_t)G > GPRN_FEW_TASKS ? TS_128x128 : TS_64x64));
-    rows.assign(G, nullptr);
+    return launch_tiles(c, d_t, tasks.size(), t_mm, G, ns_pad, GPRN_T_UPDATE, c->stream,
+                        tasks.size() * (size_t)G > GPRN_FEW_TASKS ? TS_128x128 : TS_64x64);
+}
+
+// ---- ... then the draws of the latent GPs and of the outputs, to the host
+static int cov_draw(gprn_ctx* c, CallScratch& scr, const PredState& st, const CovWork& w, const CovRequest& rq)
+{
+    const int G = w.G, ns = w.ns, ns_pad = w.ns_pad, nd = w.nd, nd_pad = w.nd_pad;
+    TRY(cov_lz(c, scr, w, [&]() -> int {
+        HIP_TRY(c, hipMemsetAsync(w.Z, 0, (size_t)G * nd_pad * ns_pad * sizeof(double), c->stream));
+        for (int g = 0; g < G; ++g)
+            HIP_TRY(c, hipMemcpy2DAsync(w.Z + (size_t)g * nd_pad * ns_pad, (size_t)ns_pad * sizeof(double), rq.z + (size_t)g * nd * ns,
+                                        (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), nd, hipMemcpyHostToDevice, c->stream));
+        return GPRN_OK;
+    }));
+    std::vector<double*> rows(G, nullptr);
     for (int g = 0; g < G; ++g) rows[g] = w.LZ + (size_t)g * nd_pad * ns_pad;
+    double** t_LZ = nullptr;
     TRY(scr.table(&t_LZ, rows));
     prof_begin(c, GPRN_T_VEC);
     hipLaunchKernelGGL(k_draw_combine, dim3((ns + 255) / 256, nd), dim3(256), 0, c->stream, (const double* const*)t_LZ,
@@ -664,7 +677,13 @@ static int cov_after(gprn_ctx* c, const PredState& st, CovRequest& rq)
     }
     TRY(cov_conditional(c, scr, st, w));
     if (!draws) return cov_outputs(c, scr, st, w, rq);
-    TRY(cov_ladder(c, scr, w, rq));
+    std::vector<int> all(G), fail;
+    std::vector<double> nu;
+    for (int g = 0; g < G; ++g) all[g] = g;
+    TRY(cov_ladder(c, scr, w, all, true, nu, fail));
+    for (int g = 0; g < G && !rq.info; ++g)
+        if (fail[g] > 0) { rq.info = fail[g]; rq.info_gp = g; }
+    if (rq.nugget_out) memcpy(rq.nugget_out, nu.data(), G * sizeof(double));
     if (rq.info) return GPRN_OK;
     return cov_draw(c, scr, st, w, rq);
 }

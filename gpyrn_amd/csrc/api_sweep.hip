@@ -776,7 +776,7 @@ static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_par
                                const double* y_resid, const double* jitters, const double* mu, const double* var,
                                int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
                                double* mu_out, double* var_out, double* grad_out, const BatchPred* pred,
-                               const BatchMeans* means = nullptr)
+                               const BatchMeans* means = nullptr, const BatchDraws* draws = nullptr)
 {
     if (!c || !c->N || n_eval < 1 || !kernel_params || (!y_resid && !means) || !jitters || !mu || !var || max_iter < 0 || !elbo ||
         !iterations || !converged || !info || (!mu_out != !var_out) || (flags & ~GPRN_BATCH_FORCED))
@@ -786,7 +786,7 @@ static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_par
     if (c->d_mask && !c->batch_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     // (a prediction's call reads what the loops left in the batch's own buffers and writes nothing of the context's: a committed
     // sweep of the context stays what it was, as under gprn_predict_batch)
-    if (!pred) c->grad_ready = false;
+    if (!pred && !draws) c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "elbocalc_batch: call set_owners first");
     if (comm_active(c) || c->world != 1) { c->err = "elbocalc_batch: one rank only (a pool of ranks splits the list itself)"; return GPRN_E_UNSUPPORTED; }
@@ -801,9 +801,9 @@ static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_par
     TRY(batch_reserve(c, small ? small_batch_reserve : mid_batch_reserve, n_eval, &cap));
     const BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info,
                      mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N, flags, grad_out,
-                     pred ? *pred : BatchPred{}, means ? *means : BatchMeans{}};
+                     pred ? *pred : BatchPred{}, means ? *means : BatchMeans{}, draws ? *draws : BatchDraws{}};
     // (with grad_out each chunk ends with the gradient pass of its evaluations, before the next chunk overwrites the slabs;
-    // with a prediction, with the prediction pass)
+    // with a prediction, with the prediction pass; with draws, with the draw pass)
     for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(run(c, io.slice(e0, std::min(cap, n_eval - e0))));
     return GPRN_OK;
 }
@@ -864,6 +864,32 @@ extern "C" int gprn_elbocalc_batch_predict(gprn_ctx* c, int n_eval, const double
     const BatchPred pred{ns, tstar, lat_mean, lat_var, out_mean, out_var, c->G, c->p};
     return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
                                iterations, converged, info, mu_out, var_out, nullptr, &pred);
+}
+
+// gprn_elbocalc_batch_predict with joint draws in place of the four prediction rows (include/gprn_hip.h): per evaluation
+// gprn_predict_draws' posterior form at the end of its loop, from the caller's normals -- what inference.sample_posterior does
+// once per kept vector, behind nELBO.  Each chunk ends with midn.hip's batch_draw_pass over what its loops left in the slabs;
+// always the posterior form, whatever option "predict_form" says
+extern "C" int gprn_elbocalc_batch_draws(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                         const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                         int max_iter, int flags, int ns, const double* tstar, int n_draws, const double* z,
+                                         double* elbo, int* iterations, int* converged, int* info, double* mu_out, double* var_out,
+                                         double* lat_draws, double* out_draws, double* nugget_out, int* draw_info)
+{
+    DeviceLock lock_(c);
+    WatchScope watch_(c, "gprn_elbocalc_batch_draws");
+    if (!c || !c->N) return bad(c, "elbocalc_batch_draws: bad argument");
+    if (ns < 1 || !tstar) return bad(c, "elbocalc_batch_draws: ns >= 1 prediction times expected");
+    if (n_draws < 1 || !z) return bad(c, "elbocalc_batch_draws: n_draws >= 1 draws and their normals z expected");
+    if (max_iter < 1) return bad(c, "elbocalc_batch_draws: a draw needs a committed sweep (max_iter >= 1)");
+    if (!lat_draws && !out_draws) return bad(c, "elbocalc_batch_draws: neither the latent nor the output draws were asked for");
+    if (!nugget_out || !draw_info) return bad(c, "elbocalc_batch_draws: nugget_out and draw_info expected");
+    int info_gp = -1;
+    const BatchDraws draws{ns, n_draws, tstar, z, lat_draws, out_draws, nugget_out, draw_info, &info_gp, c->G, c->p};
+    const int rc = elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
+                                       iterations, converged, info, mu_out, var_out, nullptr, nullptr, nullptr, &draws);
+    if (!rc && info_gp >= 0) c->info_gp = info_gp;       // (the latent GP of the first failed last rung: gprn_last_info_gp)
+    return rc;
 }
 
 extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,

@@ -113,6 +113,42 @@ struct SmallSlab {
 };
 // the copy that holds the mean of an evaluation's last committed sweep (its variance: the next one): odd trips wrote copy B
 static inline size_t small_final_copy(int iters) { return iters >= 1 && (iters & 1) ? 2 : 0; }
+// ---- the draw pass behind a chunk's loop (gprn_elbocalc_batch_draws; midn.hip batch_draw_pass): the scratch of one GROUP of
+// evaluations, an allocation class of its own.  Per slot (= evaluation x latent GP) W^T = (K* S) X^T of all ns_pad rows
+// (ns_pad x ld), the covariance C, the rung's matrix / its factor F and the factor's inverse X (ns_pad^2 each), the normals Z
+// and the product L Z (nd_pad x ns_pad each); behind them the rows (k**, mean*, var* at pitch ns_pad), the outputs' draws,
+// t*, and the pointer tables: one row block of W per block of at most ld prediction times (nblk of them: BUF_X = the slot's X, BUF_K = the driver's block of K* S, BUF_KLINV = that block of W), where the fills
+// write, and the matrices of C and L Z as lists.  Two ranges are used twice, one use after the other on the pass's stream:
+// LZ first holds the caller's normals as they came ([slot][nd][ns], unpadded), Z at the end the latent draws in the caller's
+// layout ([slot][nd][ns]).
+struct DrawShape { size_t slots, evals, p, ld, ns, ns_pad, nd, nd_pad, nblk, nb; };
+// ... of `evals` evaluations of G latent GPs and p outputs (matrices of pitch ld) at ns times and nd draws; rows of nb pointers
+static inline DrawShape draw_shape(size_t evals, size_t G, size_t p, size_t ld, size_t ns, size_t nd, size_t nb)
+{
+    return {evals * G, evals, p, ld, ns, (ns + 127) / 128 * 128, nd, (nd + 127) / 128 * 128, (ns + ld - 1) / ld, nb};
+}
+struct DrawScratch {
+    double *W, *C, *F, *X, *Z, *LZ;          // [slots] matrices
+    double *kss, *mean, *pvar;               // [slots][ns_pad]
+    double *out;                             // [evals][p][nd][ns]
+    double *ts;                              // [ns]
+    double **blk, **kblk, **cs, **lz;        // [nblk][slots][nb], [slots] three times
+    size_t w_count() const { return s.ns_pad * s.ld; }
+    size_t nn() const { return s.ns_pad * s.ns_pad; }
+    size_t z_count() const { return s.nd_pad * s.ns_pad; }
+    DrawShape s;
+};
+static inline DrawScratch draw_scratch(LayoutCursor& c, const DrawShape& s)
+{
+    const size_t nn = s.ns_pad * s.ns_pad, nz = s.nd_pad * s.ns_pad, rows = s.slots * s.ns_pad;
+    // (the matrices on 256-byte boundaries: the tile kernel and the fills move them as double2)
+    return {c.take<double>(s.slots * s.ns_pad * s.ld, 256), c.take<double>(s.slots * nn, 256), c.take<double>(s.slots * nn, 256),
+            c.take<double>(s.slots * nn, 256), c.take<double>(s.slots * nz, 256), c.take<double>(s.slots * nz, 256),
+            c.take<double>(rows, 256), c.take<double>(rows), c.take<double>(rows),
+            c.take<double>(s.evals * s.p * s.nd * s.ns, 256), c.take<double>(s.ns),
+            c.take<double*>(s.nblk * s.slots * s.nb, 256), c.take<double*>(s.slots), c.take<double*>(s.slots),
+            c.take<double*>(s.slots), s};
+}
 // ---- the pinned input of a chunk (batch_stage; gprn_predict_batch stages its programs, states and, in `variance`, jitters):
 // cap G fill programs of `program` bytes, yv doubles of y - mean and of the variances and `state` of mu and var per evaluation
 struct BatchBufs { char* programs; double *yres, *variance, *mu, *var; };    // (also: where the five go on the device)

@@ -522,6 +522,21 @@ int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, 
     return GPRN_OK;
 }
 
+// the same kernel over any time vector t (N entries, device) into matrices of pitch ld (a multiple of 128; identity padding):
+// K** of many slots at the prediction times, each with its own program (gprn_elbocalc_batch_draws) -- launch_fill_times' relation
+// to launch_fill
+int launch_fill_batch_times(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* t, int N, int ld)
+{
+    if (n_matrices <= 0) return GPRN_OK;
+    prof_begin(c, GPRN_T_FILL);
+    const int nb = ld / 64;
+    hipLaunchKernelGGL(k_fill_sym_batch<false>, dim3(nb * (nb + 1) / 2, n_matrices), dim3(256), 0, c->stream,
+                       (const FillProgram*)d_programs, t, d_Ks, (double* const*)nullptr, N, ld, (const double* const*)nullptr);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
 // Rectangular cross-covariance K*[i][n] = k(t*_i, t_n), no nugget (_gp.py:50-61, meanfield.py:455-471),
 // rows padded to a multiple of 128 with zeros; and the prior variance at the prediction points,
 // kss[i] = k(t*_i, t*_i) + nugget (the diagonal of _gp.py:40-48 evaluated at tstar).
@@ -639,6 +654,27 @@ int launch_fill_coincide(gprn_ctx* c, double* K, const double* t, int N, int ld)
 {
     prof_begin(c, GPRN_T_FILL);
     hipLaunchKernelGGL(k_fill_coincide, dim3((N + 255) / 256, N), dim3(256), 0, c->stream, K, t, N, ld);
+    prof_end(c);
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
+}
+
+// ... over a table of matrices at the same times (the draw pass of a batch: every slot's K**).  A separate kernel, the table
+// form of the one above: the one-matrix kernel keeps its code.  grid (ld / 256, N, matrices)
+__global__ __launch_bounds__(256)
+void k_fill_coincide_b(double* const* __restrict__ Ks, const double* __restrict__ t, int N, int ld)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (j >= N || i >= N || i == j) return;
+    double* const K = Ks[blockIdx.z];
+    if (t[i] == t[j]) K[(size_t)i * ld + j] = K[(size_t)i * ld + i];
+}
+
+int launch_fill_coincide_batch(gprn_ctx* c, double* const* d_Ks, int n_matrices, const double* t, int N, int ld)
+{
+    if (n_matrices <= 0) return GPRN_OK;
+    prof_begin(c, GPRN_T_FILL);
+    hipLaunchKernelGGL(k_fill_coincide_b, dim3((N + 255) / 256, N, n_matrices), dim3(256), 0, c->stream, d_Ks, t, N, ld);
     prof_end(c);
     HIP_TRY(c, hipGetLastError());
     return GPRN_OK;

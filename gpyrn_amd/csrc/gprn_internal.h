@@ -368,6 +368,10 @@ bool fill_program_with(const KernelSpec& ks, const double* params, void* dst, do
 int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices,
                       double* const* d_K2s = nullptr,       // d_K2s: a second copy of every matrix, or null
                       const double* const* d_diags = nullptr);   // per matrix: N values added to its diagonal, or null
+// ... over a time vector of the caller's (N entries, device) into matrices of pitch ld = 128 k (K** of many slots at the
+// prediction times), and launch_fill_coincide over the same table
+int launch_fill_batch_times(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* t, int N, int ld);
+int launch_fill_coincide_batch(gprn_ctx* c, double* const* d_Ks, int n_matrices, const double* t, int N, int ld);
 // K* (ns rows, zero-padded to ns_pad <= ld) and k** of many matrices at the same prediction times in one launch
 int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* d_tstar,
                            int ns, int ns_pad, double* kss, size_t kss_stride);
@@ -572,6 +576,21 @@ struct BatchPred {
                          out_mean ? out_mean + out : nullptr, out_var ? out_var + out : nullptr, G, p};
     }
 };
+// The draws a chunk of gprn_elbocalc_batch_draws ends with: ns times (0: none asked for) and nd draws per latent GP from the
+// caller's normals z [n][G][nd][ns]; the caller's rows of its evaluations -- lat [n][G][nd][ns] or null, out [n][p][nd][ns] or
+// null, nugget [n][G], info [n] (> 0: the pivot at which the last rung failed); info_gp: where the latent GP of the first such
+// verdict of the call goes (host, -1 going in)
+struct BatchDraws {
+    int ns = 0, nd = 0; const double *tstar = nullptr, *z = nullptr;
+    double *lat = nullptr, *out = nullptr, *nugget = nullptr; int *info = nullptr, *info_gp = nullptr;
+    int G = 0, p = 0;
+    BatchDraws from(int e0) const              // evaluations [e0, ...)
+    {
+        const size_t lt = (size_t)e0 * G * nd * ns, ot = (size_t)e0 * p * nd * ns;
+        return BatchDraws{ns, nd, tstar, z ? z + lt : nullptr, lat ? lat + lt : nullptr, out ? out + ot : nullptr,
+                          nugget ? nugget + (size_t)e0 * G : nullptr, info ? info + e0 : nullptr, info_gp, G, p};
+    }
+};
 // gprn_elbocalc_batch_means (mean.hip): the outputs' mean programs and every evaluation's mean parameters, on the device for
 // the length of the call; where y - mean and the bound form's mean entries go (host, either may be null)
 struct BatchMeans {
@@ -607,12 +626,13 @@ struct BatchIo {
     double* grad_out;                      // [n][n_kpar]: the gradient of each evaluation's last committed sweep, or null
     BatchPred pred{};                      // gprn_elbocalc_batch_predict: the prediction pass behind the chunk's loop (ns = 0: none)
     BatchMeans means{};                    // gprn_elbocalc_batch_means: y - mean is formed on the device (programs = null: y_resid is read)
+    BatchDraws draws{};                    // gprn_elbocalc_batch_draws: the draw pass behind the chunk's loop (ns = 0: none)
     BatchIo slice(int e0, int ne) const    // evaluations [e0, e0 + ne)
     {
         return BatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, y_resid ? y_resid + e0 * yv : nullptr, jitters + (size_t)e0 * p, mu + e0 * state,
                        var + e0 * state, max_iter, elbo + e0, iters + e0, conv + e0, info + e0,
                        mu_out ? mu_out + e0 * state : nullptr, var_out ? var_out + e0 * state : nullptr, p, state, yv,
-                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0), means.from(e0, yv)};
+                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0), means.from(e0, yv), draws.from(e0)};
     }
 };
 // grad.hip: the steps of gprn_grad_elbo over the evaluations of a batch's chunk whose loops have ended, slots = evaluations x
@@ -660,6 +680,23 @@ struct PredPassIn {
     double* pin;                           // pinned host: a block's rows on their way out, 2 (n G + n p) ld doubles
 };
 int batch_pred_pass(gprn_ctx* w, const PredPassIn& in, const BatchPred& out);
+// midn.hip: the draw pass behind a chunk's loop (gprn_elbocalc_batch_draws), for both drivers -- gprn_predict_draws' posterior
+// form (api_more.hip) over slots = evaluations x latent GPs in the set-up's order: W^T = (K* S) X^T of ALL rows of t* and the
+// means as batch_pred_pass forms them, K** of every slot in one launch, C = K** - W W^T, the ladder per slot, L Z, the
+// combination -- in groups of evaluations whose scratch (batch_layout.h draw_scratch) fits `budget` bytes.  The driver says
+// where each slot's X lies and which ld x ld buffer per slot the loop has finished with (a block of K* S); evaluations whose
+// info > 0 are left out of the ladder and get NaN rows, as does one whose last rung failed.
+struct DrawPassIn {
+    int n, G, p, q, N, ld, T;              // evaluations, the problem's geometry
+    std::vector<double*> X, blk;           // host [n G]: the slot's X (read), an ld x ld buffer it may write
+    const void* d_programs;                // device [n G] fill programs (the set-up's: they carry the sweeps' nugget)
+    const char* h_programs;                // ... and their staged host image
+    const double *s, *ct;                  // device [n G][ld]: sqrt(d) and X^T X z of each slot's last committed sweep
+    const int* info;                       // host [n]
+    double* pin; size_t pin_count;         // pinned host, the driver's: the normals on their way in, the draws on their way out
+};
+int batch_draw_pass(gprn_ctx* w, const DrawPassIn& in, const BatchDraws& out, size_t budget);
+#define GPRN_DRAW_PIN_DOUBLES ((size_t)1 << 21)   // the drivers' pinned buffer for it: 16 MiB, pieces of that size travel
 // W^T = (K* S) X^T over T x T tiles, row block by row block: a ragged last block of t* runs a prefix of the list
 std::vector<TileTask> pred_pass_tasks(int T, int ld);
 // What both drivers of gprn_elbocalc_batch ask of the caller's kernels and kernel_params (api_sweep.hip)

@@ -29,6 +29,11 @@
 // kept beside s (keep_ct), and the pass's two ld x ld buffers per slot are slabs the loop has finished with (a block of K* S
 // in the B workspace, of (K* S) X^T in K) through a pointer table of its own -- no new ld x ld allocation.
 //
+// With draws asked for (gprn_elbocalc_batch_draws) a chunk ends with batch_draw_pass instead: the same three inputs, W^T of ALL
+// rows of t* kept, and the predictive covariance of every slot factored -- in a scratch of its own, like the gradient pass's.
+// Its ladder factors in a phase of the PREDICTION's geometry (ns_pad / 128 tiles): the worker's task lists are rebuilt for it,
+// and again for the problem's T by the next factorisation (ensure_tasks keys them by T).
+//
 // PREDICTION for many parameter vectors (gprn_predict_batch: mid_predict_chunk, at the end of this file) walks gprn_predict's
 // steps over the same slot table, in the same slabs, at every T >= 1: B holds K + 1.25e-12 I + diag v and then its factor, X
 // its inverse, K and KL a block of K* and of (X K*^T)^T.
@@ -71,6 +76,7 @@ struct MidBatch {
     TileTask* pass_tasks = nullptr;   // pred_pass_tasks(T)
     int pass_ns = 0;
     double* pass_pin = nullptr;       // pinned: a block's rows on their way to the caller, 2 cap (G + p) ld doubles
+    double* draw_pin = nullptr;       // pinned: the draw pass's normals and draws on their way, GPRN_DRAW_PIN_DOUBLES, from the first call that draws
     char* programs = nullptr;         // [cap][G] fill programs
     // tables and pinned blocks, each laid out by its one function of batch_layout.h
     MidPtrTab dp{};                   // device pointer tables (one allocation)
@@ -374,12 +380,13 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
     std::vector<ElboLoop> loops(B);
     const bool forced = (io.flags & GPRN_BATCH_FORCED) != 0;
     // gradients: s of every (evaluation, latent GP) as its last sweep left it (G ld doubles per evaluation beside the slabs)
-    const bool predict = io.pred.ns > 0;
-    if ((io.grad_out || predict) && !m->keep_s) TRY(m->own.alloc(c, &m->keep_s, (size_t)m->cap * G * m->ld));
-    double* const keep_s = io.grad_out || predict ? m->keep_s : nullptr;
+    const bool predict = io.pred.ns > 0, draws = io.draws.ns > 0;
+    if ((io.grad_out || predict || draws) && !m->keep_s) TRY(m->own.alloc(c, &m->keep_s, (size_t)m->cap * G * m->ld));
+    double* const keep_s = io.grad_out || predict || draws ? m->keep_s : nullptr;
     // a prediction: ct = X^T X z too, and the pass's pointer rows -- X where the sweeps leave it, the two blocks in slabs the
     // loop has finished with when the pass runs (B's workspace and the prior's K; the next chunk's set-up refills both)
-    if (predict && !m->keep_ct) TRY(m->own.alloc(c, &m->keep_ct, (size_t)m->cap * G * m->ld));
+    if ((predict || draws) && !m->keep_ct) TRY(m->own.alloc(c, &m->keep_ct, (size_t)m->cap * G * m->ld));
+    if (draws && !m->draw_pin) TRY(m->own.pin(c, &m->draw_pin, GPRN_DRAW_PIN_DOUBLES * sizeof(double)));
     if (predict && !m->pass_tab) {
         const size_t nslot = (size_t)m->cap * G, nn = (size_t)m->ld * m->ld;
         std::vector<double*> rows(nslot * GPRN_NBUF);
@@ -397,7 +404,7 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
         TRY(m->own.alloc(c, &m->pass_ts, (size_t)io.pred.ns));
         m->pass_ns = io.pred.ns;
     }
-    double* const keep_ct = predict ? m->keep_ct : nullptr;
+    double* const keep_ct = predict || draws ? m->keep_ct : nullptr;
     int trips = 0;                                       // (forced: every running evaluation has made this many)
     bool tables_stale = true, first = true;
     while (!act.empty()) {
@@ -511,10 +518,19 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
                             m->pass_ts, m->pass_jit, m->pass_tasks, m->pass_pin};
         TRY(batch_pred_pass(w, in, io.pred));
     }
+    if (draws) {
+        // ---- joint draws from the posterior every evaluation's last committed sweep left, over the full chunk in the set-up's
+        // order: X where the sweeps leave it, a block of K* S in B's workspace (the next chunk's set-up refills it)
+        const size_t nn = (size_t)m->ld * m->ld;
+        DrawPassIn in{B, G, p, q, N, m->ld, w->T, {}, {}, m->programs, m->in.programs, keep_s, keep_ct, io.info, m->draw_pin,
+                      GPRN_DRAW_PIN_DOUBLES};
+        for (size_t sl = 0; sl < (size_t)B * G; ++sl) { in.X.push_back(m->Xw + sl * nn); in.blk.push_back(m->Bw + sl * nn); }
+        TRY(batch_draw_pass(w, in, io.draws, grad_batch_left(c, (size_t)m->cap * mid_bytes_per_eval(c))));
+    }
     const double us_pred = t.lap();
     if (batch_timers_on())
         fprintf(stderr, "[gprn] elbocalc_batch (N = %d, T = %d), %d evaluations, us: staging %.0f | set-up enqueued %.0f | %d sweeps: enqueue %.0f, "
-                        "waiting for the device %.0f, verdicts %.0f | states back %.0f | gradient pass %.0f | prediction pass %.0f | total %.0f\n", N, w->T, B, us_stage, us_setup, n_sweeps,
+                        "waiting for the device %.0f, verdicts %.0f | states back %.0f | gradient pass %.0f | prediction / draw pass %.0f | total %.0f\n", N, w->T, B, us_stage, us_setup, n_sweeps,
                 us_enqueue, us_wait, us_host, us_states, us_grad, us_pred, t.total());
     return GPRN_OK;
 }
@@ -589,6 +605,172 @@ int batch_pred_pass(gprn_ctx* w, const PredPassIn& in, const BatchPred& out)
             std::fill(out.out_mean + (size_t)b * p * ns, out.out_mean + (size_t)(b + 1) * p * ns, NAN);
             std::fill(out.out_var + (size_t)b * p * ns, out.out_var + (size_t)(b + 1) * p * ns, NAN);
         }
+    }
+    return GPRN_OK;
+}
+
+// ------------------------------------------------------------------ the draw pass of both drivers (gprn_elbocalc_batch_draws)
+// Z[slot][d][t] (nd_pad x ns_pad, zero padding) from the caller's normals as they came, z[slot][d][t] (nd x ns).
+// grid (ns_pad / 256, nd_pad, slots)
+__global__ __launch_bounds__(256)
+void k_draw_pad_z(const double* __restrict__ z, int nd, int ns, int nd_pad, int ns_pad, double* __restrict__ Z)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x, slot = blockIdx.z;
+    if (t >= ns_pad) return;
+    for (int d = blockIdx.y; d < nd_pad; d += gridDim.y)
+        Z[((size_t)slot * nd_pad + d) * ns_pad + t] = (d < nd && t < ns) ? z[((size_t)slot * nd + d) * ns + t] : 0.0;
+}
+
+// The _b form of api_more.hip's k_draw_combine, the evaluation on grid z: lat[e][g][d][t] = mean[e G + g][t] + LZ[e G + g][d][t],
+// out[e][i][d][t] = sum_j lat[e][w_ij][d][t] lat[e][f_j][d][t] (out may be null).  LZ: per slot, rows d of pitch ns_pad; mean:
+// rows of pitch ns_pad.  A kernel of its own (DESIGN.md 5 "Variants": lane forms).  grid ((ns + 255) / 256, draws, evaluations)
+__global__ __launch_bounds__(256)
+void k_draw_combine_b(const double* const* __restrict__ LZ, const double* __restrict__ mean, int q, int p, int ns, int ns_pad,
+                      int nd, double* __restrict__ lat, double* __restrict__ out)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= ns) return;
+    const int G = q * (p + 1);
+    const size_t e = blockIdx.z, s0 = e * G;
+    for (int d = blockIdx.y; d < nd; d += gridDim.y) {
+        auto val = [&](int g) { return mean[(s0 + g) * ns_pad + t] + LZ[s0 + g][(size_t)d * ns_pad + t]; };
+        for (int g = 0; g < G; ++g) lat[((s0 + g) * nd + d) * ns + t] = val(g);
+        if (!out) continue;
+        for (int i = 0; i < p; ++i) {
+            double s = 0.0;
+            for (int j = 0; j < q; ++j) s += val(q + j * p + i) * val(j);
+            out[((e * p + i) * nd + d) * ns + t] = s;
+        }
+    }
+}
+
+// count doubles between a device array and a host array of the caller's through the driver's pinned buffer, piece by piece
+// (batch_pred_pass's comment: never a copy between the device and pageable memory)
+static int draw_through_pin(gprn_ctx* w, const DrawPassIn& in, double* dev, double* host, const double* host_in, size_t count)
+{
+    for (size_t at = 0; at < count; at += in.pin_count) {
+        const size_t n = std::min(in.pin_count, count - at);
+        if (host_in) {
+            memcpy(in.pin, host_in + at, n * sizeof(double));
+            HIP_TRY(w, hipMemcpyAsync(dev + at, in.pin, n * sizeof(double), hipMemcpyHostToDevice, w->stream));
+            HIP_TRY(w, hipStreamSynchronize(w->stream));
+        } else {
+            HIP_TRY(w, hipMemcpyAsync(in.pin, dev + at, n * sizeof(double), hipMemcpyDeviceToHost, w->stream));
+            HIP_TRY(w, hipStreamSynchronize(w->stream));
+            memcpy(host + at, in.pin, n * sizeof(double));
+        }
+    }
+    return GPRN_OK;
+}
+
+// evaluations [e0, e0 + ne) of the pass; the scratch comes before the first launch (GPRN_E_NOMEM: nothing has run)
+static int draw_group(gprn_ctx* w, const DrawPassIn& in, const BatchDraws& out, int e0, int ne)
+{
+    const int G = in.G, p = in.p, ld = in.ld, T = in.T, ns = out.ns, nd = out.nd, nslots = ne * G;
+    const DrawShape shape = draw_shape((size_t)ne, (size_t)G, (size_t)p, (size_t)ld, (size_t)ns, (size_t)nd, GPRN_NBUF);
+    const int ns_pad = (int)shape.ns_pad, nd_pad = (int)shape.nd_pad, nblk = (int)shape.nblk;
+    hipStream_t st = w->stream;
+    CallScratch scr(w);                               // (its destructor waits for the stream: the host vectors below outlive the copies)
+    char* block = nullptr;
+    TRY(scr.alloc(&block, layout_count<char>(draw_scratch, shape)));
+    const DrawScratch d = layout_at(block, draw_scratch, shape);
+    const size_t s0 = (size_t)e0 * G, nn = d.nn(), nz = d.z_count(), nw = d.w_count();
+    // ---- the tables: per block of t* the pass's rows, where the fills write, the matrices of C and of L Z
+    std::vector<double*> hp((size_t)(nblk * GPRN_NBUF + 3) * nslots, nullptr), wt(nslots);
+    for (int sl = 0; sl < nslots; ++sl) {
+        double* const W = d.W + (size_t)sl * nw;
+        for (int b = 0; b < nblk; ++b)
+            buf_row(&hp[((size_t)b * nslots + sl) * GPRN_NBUF], nullptr, in.X[s0 + sl], in.blk[s0 + sl], W + (size_t)b * ld * ld);
+        hp[(size_t)nblk * GPRN_NBUF * nslots + sl] = in.blk[s0 + sl];
+        hp[((size_t)nblk * GPRN_NBUF + 1) * nslots + sl] = d.C + (size_t)sl * nn;
+        hp[((size_t)nblk * GPRN_NBUF + 2) * nslots + sl] = d.LZ + (size_t)sl * nz;
+        wt[sl] = W;
+    }
+    // (blk, kblk, cs and lz follow one another in the layout: one copy)
+    HIP_TRY(w, hipMemcpyAsync(d.blk, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, st));
+    HIP_TRY(w, hipMemcpyAsync(d.ts, out.tstar, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, st));
+    TileTask* d_t = nullptr;
+    TRY(scr.tasks(&d_t, pred_pass_tasks(T, ld)));
+    // ---- (1) W^T = (K* S) X^T and the means, block by block of at most ld rows as batch_pred_pass has them; W stays
+    const char* const pg_d = (const char*)in.d_programs + s0 * fill_program_bytes();
+    const char* const pg_h = in.h_programs + s0 * fill_program_bytes();
+    const double *const s = in.s + s0 * ld, *const ct = in.ct + s0 * ld;
+    for (int b = 0; b < nblk; ++b) {
+        const int t0 = b * ld, nsb = std::min(ld, ns - t0), nsb_pad = ((nsb + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+        const Phase pass{d.blk + (size_t)b * nslots * GPRN_NBUF, nullptr, nslots, 0, nullptr, EvalMap{nullptr, 0, 0, 0, 0}, in.N, ld, T};
+        TRY(launch_fill_rect_batch_post(w, pg_d, pg_h, d.kblk, nslots, d.ts + t0, nsb, nsb_pad, s, d.kss + t0, (size_t)ns_pad));
+        TRY(launch_tiles(w, d_t, (size_t)(nsb_pad / GPRN_TILE) * T, pass.ptrs, nslots, ld, GPRN_T_UPDATE));
+        TRY(vec_pred_rows(w, pass, nsb, ns_pad, ct, d.kss + t0, d.mean + t0, d.pvar + t0));
+    }
+    // ---- (2) K** of every slot in one launch, with the sweeps' nugget; the delta terms between equal times
+    TRY(launch_fill_batch_times(w, pg_d, d.cs, nslots, d.ts, ns, ns_pad));
+    TRY(launch_fill_coincide_batch(w, d.cs, nslots, d.ts, ns, ns_pad));
+    // ---- (3) C -= W W^T, mirrored
+    CovWork cw;
+    cw.G = nslots; cw.ns = ns; cw.ns_pad = ns_pad; cw.Ts = ns_pad / GPRN_TILE; cw.ld = ld; cw.nd = nd; cw.nd_pad = nd_pad; cw.nn = nn;
+    cw.C = d.C; cw.F = d.F; cw.X = d.X; cw.Z = d.Z; cw.LZ = d.LZ; cw.lat = d.Z; cw.out = out.out ? d.out : nullptr;
+    TRY(cov_subtract(w, scr, cw, wt));
+    // ---- (4) the ladder, per slot: the slots of an evaluation whose sweeps failed stay out.  factor_invert sizes its flag words
+    // and task lists by the phase's T alone (factor.hip: d_sig, ensure_tasks -- both regrown or rebuilt on the spot, and again
+    // by the next factorisation of the problem's own T), the verdicts are this call's; the batch is a launch's grid y
+    HIP_TRY(w, hipMemsetAsync(d.X, 0, (size_t)nslots * nn * sizeof(double), st));
+    std::vector<int> pending, fail;
+    std::vector<double> nu;
+    for (int e = 0; e < ne; ++e)
+        for (int g = 0; g < G && in.info[e0 + e] <= 0; ++g) pending.push_back(e * G + g);
+    TRY(cov_ladder(w, scr, cw, pending, false, nu, fail));
+    // ---- (5) L Z and the combination.  The caller's normals travel unpadded into LZ's range and are padded into Z from there
+    TRY(cov_lz(w, scr, cw, [&]() -> int {
+        TRY(draw_through_pin(w, in, d.LZ, nullptr, out.z + s0 * nd * ns, (size_t)nslots * nd * ns));
+        hipLaunchKernelGGL(k_draw_pad_z, dim3((ns_pad + 255) / 256, std::min(nd_pad, 65535), nslots), dim3(256), 0, st,
+                           (const double*)d.LZ, nd, ns, nd_pad, ns_pad, d.Z);
+        HIP_TRY(w, hipGetLastError());
+        return GPRN_OK;
+    }));
+    prof_begin(w, GPRN_T_VEC);
+    hipLaunchKernelGGL(k_draw_combine_b, dim3((ns + 255) / 256, std::min(nd, 65535), ne), dim3(256), 0, st, (const double* const*)d.lz,
+                       (const double*)d.mean, in.q, p, ns, ns_pad, nd, cw.lat, cw.out);
+    prof_end(w);
+    HIP_TRY(w, hipGetLastError());
+    // ---- (6) the rows back through the pinned buffer; NaN where the sweeps or the last rung failed
+    const size_t lat_e = (size_t)G * nd * ns, out_e = (size_t)p * nd * ns;
+    if (out.lat) TRY(draw_through_pin(w, in, cw.lat, out.lat + e0 * lat_e, nullptr, ne * lat_e));
+    if (out.out) TRY(draw_through_pin(w, in, cw.out, out.out + e0 * out_e, nullptr, ne * out_e));
+    for (int e = 0; e < ne; ++e) {
+        const int b = e0 + e;
+        int failed = 0, failed_gp = -1;
+        for (int g = 0; g < G && !failed; ++g)
+            if (fail[(size_t)e * G + g] > 0) { failed = fail[(size_t)e * G + g]; failed_gp = g; }
+        out.info[b] = failed;
+        if (failed && out.info_gp && *out.info_gp < 0) *out.info_gp = failed_gp;
+        const bool lost = in.info[b] > 0;
+        for (int g = 0; g < G; ++g) out.nugget[(size_t)b * G + g] = lost ? NAN : nu[(size_t)e * G + g];
+        if (!failed && !lost) continue;
+        if (out.lat) std::fill(out.lat + b * lat_e, out.lat + (b + 1) * lat_e, NAN);
+        if (out.out) std::fill(out.out + b * out_e, out.out + (b + 1) * out_e, NAN);
+    }
+    return GPRN_OK;
+}
+
+int batch_draw_pass(gprn_ctx* w, const DrawPassIn& in, const BatchDraws& out, size_t budget)
+{
+    auto bytes = [&](int ne) {
+        return layout_count<char>(draw_scratch, draw_shape((size_t)ne, (size_t)in.G, (size_t)in.p, (size_t)in.ld, (size_t)out.ns,
+                                                           (size_t)out.nd, GPRN_NBUF));
+    };
+    // (a launch's grid y or z is the number of slots or evaluations of the group: far below its 65 535 limit)
+    int group = (int)std::max<size_t>(1, std::min<size_t>({budget / bytes(1), (size_t)32768 / in.G, (size_t)in.n}));
+    while (group > 1 && bytes(group) > budget) --group;
+    for (int e0 = 0; e0 < in.n;) {
+        const int ne = std::min(group, in.n - e0);
+        const int rc = draw_group(w, in, out, e0, ne);
+        if (rc == GPRN_E_NOMEM && ne > 1) { group = (ne + 1) / 2; w->err.clear(); continue; }   // (nothing of the group has run)
+        if (rc == GPRN_E_NOMEM)
+            w->err = "elbocalc_batch_draws: out of device memory for the draw pass of one evaluation: " + std::to_string(in.G) +
+                     " covariance matrices of " + std::to_string(out.ns) + " x " + std::to_string(out.ns) + ", their factors and " +
+                     std::to_string(out.nd) + " draws (" + w->err + ")";
+        if (rc) return rc;
+        e0 += ne;
     }
     return GPRN_OK;
 }

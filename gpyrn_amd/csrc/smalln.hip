@@ -602,6 +602,9 @@ struct SmallBatchMem {
     TileTask* pred_tasks = nullptr;   // pred_pass_tasks(1)
     int pred_ns = 0;
     double* pred_pin = nullptr;       // pinned: a block's rows on their way to the caller, 2 cap (G + p) ld doubles
+    // draws behind the loop (gprn_elbocalc_batch_draws), likewise: s and ct gathered per slot, the pass's pinned buffer
+    double* draw_vecs = nullptr;      // [2][cap G ld]
+    double* draw_pin = nullptr;       // GPRN_DRAW_PIN_DOUBLES
     char* pin_in = nullptr;           // pinned: batch_pin_in
     SmallPinOut out{};                // pinned: what a group of sweeps sends back, the four state copies
     double us_reserve = 0.0;          // GPRN_BATCH_TIMERS: what making room took, reported with the next chunk
@@ -955,6 +958,27 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
                                 m->pred_ts, m->pred_jit, m->pred_tasks, m->pred_pin};
             TRY(batch_pred_pass(c, in, io.pred.from(e0)));
         }
+    }
+    if (io.draws.ns > 0) {
+        // ---- joint draws from the posterior every evaluation's last committed sweep left: midn.hip's draw pass over the B x G
+        // one-tile slots, in the set-up's order, from the same s, ct and X as the prediction above; its block of K* S in B's
+        // workspace.  The pass's ladder factors on THIS context at the prediction's geometry (its task lists are rebuilt, and
+        // again by the next factorisation at T = 1); a wait of it that gave up re-runs the pass alone, which only reads the slabs.
+        const SmallSlab& v = m->v;
+        const size_t gl = (size_t)G * c->ld, nv = (size_t)cap * gl;
+        if (!m->draw_vecs) {
+            TRY(m->own.alloc(c, &m->draw_vecs, 2 * nv));
+            TRY(m->own.pin(c, &m->draw_pin, GPRN_DRAW_PIN_DOUBLES * sizeof(double)));
+        }
+        const size_t rowb = gl * sizeof(double), pitch = v.vec_pitch() * sizeof(double);
+        HIP_TRY(c, hipMemcpy2DAsync(m->draw_vecs, rowb, v.vec(0, SV_S, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpy2DAsync(m->draw_vecs + nv, rowb, v.vec(0, SV_CT, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
+        DrawPassIn in{B, G, c->p, q, c->N, c->ld, 1, {}, {}, m->programs, m->pin_in, m->draw_vecs, m->draw_vecs + nv, info,
+                      m->draw_pin, GPRN_DRAW_PIN_DOUBLES};
+        for (int b = 0; b < B; ++b)
+            for (int g = 0; g < G; ++g) { in.X.push_back(v.X(b, g)); in.blk.push_back(v.B(b, g)); }
+        const size_t left = grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c));
+        TRY(with_event_fallback(c, "elbocalc_batch_draws", [&](bool) { return batch_draw_pass(c, in, io.draws, left); }));
     }
     const double us_pred = t.lap();
     if (batch_timers_on())

@@ -1655,6 +1655,115 @@ class inference:
         mean, var = np.array(means_), np.array(vars_)
         return (mean, var, np.array(lats)) if separate else (mean, var)
 
+    def sample_posterior_batch(self, parameter_sets, tstar=None, n=1, noise=False, separate=False, rng=None, max_iter=None,
+                               sweeps=None, start=None):
+        """
+        ``sample_posterior`` for several free-parameter vectors -- one joint curve (or `n`) per vector an ``mcmc`` run kept,
+        smooth in `tstar`: each vector's loop runs and the vector is drawn from the posterior ``q(f_g) = N(mu_g, Sigma_g)``
+        THAT loop leaves, all vectors SIDE BY SIDE (``gprn_elbocalc_batch_draws``: a draw pass at the end of each batch
+        chunk, from the X, s and c every evaluation's last committed sweep left in the chunk's slabs).  Not in the reference.
+
+        It needs ``predict='variational'`` (else ``ValueError``), as ``predict_batch(from_sweeps=True)`` does, and
+        ``max_iter`` / ``sweeps`` / ``start`` mean what they mean there.  The standard normals ``(B, G, n, N*)`` are drawn up
+        front from ``np.random.default_rng(rng)``; where the side-by-side form does not apply (N > ``batch_max_N``, a mask
+        without ``batch_under_mask``, expressions that change shape between vectors) the vectors go one by one with the
+        same numbers and the same meaning: the loop, then ``gprn_predict_draws`` in the posterior form on what it left.
+        Every latent GP of every vector has its own nugget from the ladder 1.25e-12 x 100^k <= 1.25e-6
+        (``self.last_nuggets``, (B, G)).  The mean functions are added per vector (on the device with ``device_means``), and
+        with `noise` also N(0, jitter_i^2) per time, once, from each vector's own jitters, drawn after the normals from the
+        same generator.  A vector whose factorisation meets a non-positive pivot -- in its sweeps or on the ladder's last
+        rung -- gets NaN rows; ``last_info`` holds the first positive verdict.  The object keeps what ``nELBO_batch`` keeps.
+        Sharded objects: ``NotImplementedError``.
+
+        Returns draws (B, n, N*, p); with `separate` also the latent draws (B, G, n, N*): nodes first, then weight (j, i)
+        at q + j p + i.
+        """
+        if self._predict_form != 'variational':
+            raise ValueError("sample_posterior_batch draws from the posterior the sweeps leave; it needs "
+                             "predict='variational' (predict_form)")
+        forced = sweeps is not None
+        if start is not None and not forced:
+            raise ValueError('sample_posterior_batch: `start` goes with `sweeps`; the loop under the stop rule starts from '
+                             'the state the object holds')
+        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
+        if trips < 1:
+            raise ValueError('sample_posterior_batch needs at least one committed sweep')
+        n = int(n)
+        if n < 1:
+            raise ValueError('sample_posterior_batch: n >= 1 draws per vector expected')
+        if self._comm is not None:
+            raise NotImplementedError('sample_posterior_batch is not available on a sharded inference object')
+        assert self._components_set, _NOT_SET
+        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        B = len(sets)
+        if B < 1:
+            raise ValueError('sample_posterior_batch: no parameter vector')
+        tstar = np.asarray(self.time, dtype=float) if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
+        if tstar.ndim != 1 or tstar.size < 1:
+            raise ValueError('sample_posterior_batch: tstar must be a non-empty vector of times')
+        q, p, ns = self.q, self.p, tstar.size
+        G = q * (p + 1)
+        gen = np.random.default_rng(rng)
+        z = gen.standard_normal((B, G, n, ns))
+        entry = (self._mu, self._var) if start is None else start
+        staged = self._batch_stage(sets, start=start)
+        res = None
+        if staged is not None:
+            ctx, kp, yr, jt, m0, v0 = staged
+            res = ctx.elbocalc_batch_draws(kp, yr, jt, m0, v0, trips, tstar, z, forced=forced, latent=separate, outputs=True)
+        if res is not None:
+            self._batch_keep(res)
+            lat, out, nug, dinfo = res[6], res[7], res[8], res[9]
+            if not self.last_info and np.any(dinfo):
+                self.last_info = int(dinfo[np.flatnonzero(dinfo)[0]])
+            jit_b = np.asarray(jt, dtype=float).reshape(B, p)
+        else:
+            # one by one, each vector from the same state and its own slice of the normals
+            lats, outs, nugs, jits = [], [], [], []
+            keep, first_info = None, 0
+            for b, x in enumerate(sets):
+                self.set_parameters(x)
+                nodes, weights, means, jitters = self._get_components()
+                for k in chain(nodes, weights):
+                    if not isinstance(k, covfunc.covFunction) or k._device_program() is None:
+                        raise NotImplementedError("predict='variational' needs a device program for every kernel: "
+                                                  'user-defined kernels (and sums that hold a two-argument kernel) are not '
+                                                  'supported')
+                mu0, var0 = entry if entry[0] is not None else self._initMuVar(nodes, weights, jitters)
+                ctx = self._setup_device(nodes, weights, means, jitters)
+                self._swept = None                             # (the device's committed sweep is no stored state's)
+                self._send_predict_form(ctx)
+                ctx.set_muvar(np.asarray(mu0, dtype=float), np.asarray(var0, dtype=float))
+                if forced:
+                    _, _, info = ctx.sweep(trips, commit=True)
+                    conv = False
+                    mu, var = ctx.get_muvar()
+                else:
+                    _, _, conv, info, mu, var = ctx.elbocalc(trips)
+                lat_b, out_b, nug_b = np.full((G, n, ns), np.nan), np.full((p, n, ns), np.nan), np.full(G, np.nan)
+                if not info:
+                    l_, o_, nug_b, dinfo = ctx.predict_draws(tstar, z[b])
+                    info = dinfo
+                    if not dinfo:
+                        lat_b, out_b = l_, o_
+                first_info = first_info or int(info)
+                lats.append(lat_b)
+                outs.append(out_b)
+                nugs.append(nug_b)
+                jits.append(np.asarray(jitters, dtype=float))
+                if conv and not info:
+                    keep = (mu, var)
+            self.last_info = first_info
+            if keep is not None:
+                self._mu, self._var = keep
+            lat, out, nug, jit_b = np.array(lats), np.array(outs), np.array(nugs), np.array(jits).reshape(B, p)
+        self.last_nuggets = nug
+        meanvals = self._mean_values_batch(sets, tstar)                         # (B, p, N*)
+        draws = np.transpose(out, (0, 2, 3, 1)) + np.transpose(meanvals, (0, 2, 1))[:, None]
+        if noise:
+            draws = draws + gen.standard_normal(draws.shape) * np.abs(jit_b)[:, None, None, :]
+        return (draws, lat) if separate else draws
+
     def _mean_programs(self, means):
         """[(ops, params)] per output -- the empty program for a mean that is None -- where ``device_means`` is on and
         every mean has a device program; else None: the caller evaluates on the host as it always has."""
@@ -1718,18 +1827,34 @@ class inference:
                 "vector's loop and a prediction pass at the end of a batch chunk, where the slabs still hold each "
                 "evaluation's X; else set predict_form = 'reference'")
 
-    def posterior_predictive(self, parameter_sets, tstar=None, weights=None, **kw):
+    def posterior_predictive(self, parameter_sets, tstar=None, weights=None, draws=None, **kw):
         """
         The first two moments of the mixture of ``predict_batch``'s predictions over `parameter_sets` -- the posterior
         predictive of a chain: ``mean = sum_b w_b mean_b``, ``var = sum_b w_b (var_b + mean_b^2) - mean^2``.  `weights`
         (B,): default uniform, normalised to sum 1.  Further keywords go to ``predict_batch`` untouched (``states``,
         ``max_iter``; ``from_sweeps=True`` with ``sweeps`` / ``start``: the variational form, each vector predicted from the
         posterior its own loop leaves).
-        Returns (mean (N*, p), variance (N*, p)).
+        ``draws=k`` (``predict='variational'``; uniform `weights` only, else ``ValueError``: resample the chain first)
+        additionally returns k joint curves per vector from ``sample_posterior_batch`` -- ``max_iter``, ``sweeps`` and ``start``
+        as given here, ``rng`` and ``noise`` its own; every vector's loop starts from the state the call found.
+        Returns (mean (N*, p), variance (N*, p)) and, with `draws`, the curves (B k, N*, p), k per vector.
         """
+        draw_kw = {key: kw.pop(key) for key in ('rng', 'noise') if key in kw}
+        if draws is None and draw_kw:
+            raise ValueError('posterior_predictive: `rng` and `noise` go with `draws`')
+        if draws is not None:
+            if int(draws) < 1:
+                raise ValueError('posterior_predictive: draws >= 1 curves per vector expected')
+            if weights is not None and np.ptp(np.asarray(weights, dtype=float)) > 0:
+                raise ValueError('posterior_predictive: draws come one set per vector -- with non-uniform weights resample '
+                                 'the chain first')
+            if self._predict_form != 'variational':
+                raise ValueError("posterior_predictive: draws need predict='variational' (predict_form)")
+            kw.setdefault('from_sweeps', True)
         if not kw.get('from_sweeps'):
             self._refuse_variational_batch('posterior_predictive')
         kw.pop('separate', None)
+        found = (self._mu, self._var)
         mean_b, var_b = self.predict_batch(parameter_sets, tstar=tstar, **kw)
         B = mean_b.shape[0]
         w = np.full(B, 1.0 / B) if weights is None else np.asarray(weights, dtype=float)
@@ -1738,7 +1863,12 @@ class inference:
         w = (w / np.sum(w))[:, None, None]
         mean = np.sum(w * mean_b, axis=0)
         var = np.sum(w * (var_b + mean_b * mean_b), axis=0) - mean * mean
-        return mean, var
+        if draws is None:
+            return mean, var
+        self._mu, self._var = found
+        curves = self.sample_posterior_batch(parameter_sets, tstar=tstar, n=int(draws), max_iter=kw.get('max_iter'),
+                                             sweeps=kw.get('sweeps'), start=kw.get('start'), **draw_kw)
+        return mean, var, curves.reshape((-1,) + curves.shape[2:])
 
     # ------------------------------------------------------------ gradients
     def grad_ELBO(self, mean_sweeps=8, mean_start=None, total=False, fused=False):

@@ -492,6 +492,42 @@ int gprn_elbocalc_batch_predict(gprn_ctx* ctx, int n_eval, const double* kernel_
                                 double* mu_out, double* var_out,
                                 double* lat_mean, double* lat_var, double* out_mean, double* out_var);
 
+/* gprn_elbocalc_batch_predict with JOINT DRAWS in place of the four prediction rows -- one curve per kept vector of a chain,
+ * smooth in t*: what inference.sample_posterior returns, once per hyper-parameter vector, behind that vector's nELBO.
+ *   ns, tstar [ns]: the prediction times, the same for every evaluation; n_draws >= 1;
+ *   z [n_eval][G][n_draws][ns]: the caller's standard normals (the call is deterministic, as gprn_predict_draws is);
+ *   lat_draws [n_eval][G][n_draws][ns] (or NULL), out_draws [n_eval][p][n_draws][ns] (or NULL), at least one of them: row b is
+ *       what gprn_predict_draws returns in the posterior form (GPRN_PREDICT_POSTERIOR) right after gprn_elbocalc has run
+ *       evaluation b's loop alone on this context from (mu_b, var_b), with z_b:
+ *           mean*_g = K*_g S c,   C*_g = K**_g - W W^T, W^T = (K*_g S) X^T,   C*_g + nu_g I = L L^T,   lat_g = mean*_g + L z_g,
+ *           out_i = sum_j lat[w_ij] o lat[f_j]
+ *       with X, s = sqrt(d) and c = X^T X z of that evaluation's LAST COMMITTED sweep.  K** carries the sweeps' nugget (quirk
+ *       Q9); it and WhiteNoise are delta(t, t'), between equal entries of t* too.  Mean functions and observation noise are
+ *       the caller's to add.  Always the posterior form, whatever option "predict_form" says;
+ *   nugget_out [n_eval][G]: nu of every slot (evaluation, latent GP), from the ladder 1.25e-12 x 100^k <= 1.25e-6 -- PER SLOT:
+ *       only the slots whose factorisation failed are factored again;
+ *   draw_info [n_eval]: 0, or the pivot at which an evaluation's last rung failed (the latent GP of the call's first such
+ *       verdict: gprn_last_info_gp); that evaluation's rows are NaN.  An evaluation with info > 0 (its sweeps) gets NaN rows
+ *       and NaN nuggets too.  The other evaluations are untouched in both cases.
+ * flags: as gprn_elbocalc_batch_grad (GPRN_BATCH_FORCED).  elbo, iterations, converged, info and the states are bit-identical to
+ * gprn_elbocalc_batch_grad(..., grad_out = NULL) with the same inputs and flags: the draw pass runs per chunk behind the
+ * chunk's loop and only reads what the loop left (csrc/midn.hip batch_draw_pass: W^T of all rows of t* by the prediction
+ * pass's launches, K** of every slot in one launch, the lower tiles of C, the ladder in one phase of the prediction's
+ * geometry per rung, L Z, the combination; the rows travel through a pinned buffer).  Its scratch is an allocation of its
+ * own, ns_pad ld + 3 ns_pad^2 + 2 nd_pad ns_pad doubles per slot (ns_pad, nd_pad: ns, n_draws rounded up to 128), which takes
+ * what the chunk's slabs left of "batch_mem_mb"; beyond that a chunk's evaluations go in groups, and GPRN_E_NOMEM comes back
+ * only when one evaluation's scratch does not fit.
+ * GPRN_E_ARG: max_iter < 1 (no committed sweep), ns < 1, n_draws < 1, z NULL, neither output given, nugget_out or draw_info
+ * NULL, unknown flag bits.  Refusals (GPRN_E_UNSUPPORTED) are gprn_elbocalc_batch's.  Both sweep orders, masks under
+ * "batch_mask" and "order_mask", the bound form of the ELBO, chunks and halving under "batch_mem_mb" ("batch_chunk" reports
+ * this call's chunk too).  The context's own state, factors and validity flags are not touched: a gprn_sweep right after
+ * the call returns the bits it would have returned before it. */
+int gprn_elbocalc_batch_draws(gprn_ctx* ctx, int n_eval, const double* kernel_params, int n_kernel_params,
+                              const double* y_resid, const double* jitters, const double* mu, const double* var,
+                              int max_iter, int flags, int ns, const double* tstar, int n_draws, const double* z,
+                              double* elbo, int* iterations, int* converged, int* info, double* mu_out, double* var_out,
+                              double* lat_draws, double* out_draws, double* nugget_out, int* draw_info);
+
 /* gprn_predict for n_eval parameter vectors side by side -- the posterior predictive of a chain: the reference's
  * inference._Prediction (meanfield.py:1289-1381) over _gp.GP.prediction (_gp.py:107-138), once per hyper-parameter vector
  * that inference.mcmc kept.
