@@ -36,7 +36,7 @@ static void dev_free(T*& p) { if (p) hipFree(p); p = nullptr; }
 static inline int bad(gprn_ctx* c, const char* msg) { if (c) c->err = msg; return GPRN_E_ARG; }
 
 // Owns device and pinned allocations: everything it hands out is freed in release() and in its destructor, on every path
-// (CallScratch for one call; SmallBatchMem, MidBatch between side-by-side calls).  A failed alloc / pin leaves a null pointer.
+// (CallScratch for one call; SmallBatchMem, MidBatch and through them batch_tail.hip's TailKept between side-by-side calls).  A failed alloc / pin leaves a null pointer.
 struct DeviceOwner {
     std::vector<void*> dev, pinned;
     DeviceOwner() = default;
@@ -98,7 +98,7 @@ struct CallScratch {
 
 // ---- api_more.hip: the steps of gprn_predict_cov / gprn_predict_draws behind the means, over G matrices -- the latent GPs of
 // one call (every latent GP is local -- one rank -- and slot s = latent GP s) or the slots = evaluations x latent GPs of a
-// batch's draw pass (midn.hip batch_draw_pass).  Geometry and device memory: C (G ns_pad^2); draws: the factor's B and X
+// batch's draw pass (batch_tail.hip batch_draw_pass).  Geometry and device memory: C (G ns_pad^2); draws: the factor's B and X
 // (2 G ns_pad^2), Z and L Z (2 G nd_pad ns_pad); matrix g of each at g times its size
 struct CovWork {
     int G, ns, ns_pad, Ts, ld, nd, nd_pad;

@@ -771,22 +771,18 @@ size_t batch_budget_bytes(gprn_ctx* c)
 // B independent evaluations of the loop above, side by side on the device: see include/gprn_hip.h.  One-tile problems run a
 // half-sweep of ALL evaluations as one launch (smalln.hip); larger ones go through the launch schedule with
 // batch = evaluations x latent GPs (midn.hip).  Either way a list longer than the memory budget holds runs chunk by chunk.
-// pred: the prediction each chunk ends with (gprn_elbocalc_batch_predict), or null
-static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
-                               const double* y_resid, const double* jitters, const double* mu, const double* var,
-                               int max_iter, int flags, double* elbo, int* iterations, int* converged, int* info,
-                               double* mu_out, double* var_out, double* grad_out, const BatchPred* pred,
-                               const BatchMeans* means = nullptr, const BatchDraws* draws = nullptr)
+// io: the call's request as its entry point filled it in (the per-evaluation sizes p, state, yv are entered here)
+static int elbocalc_batch_impl(gprn_ctx* c, BatchIo io)
 {
-    if (!c || !c->N || n_eval < 1 || !kernel_params || (!y_resid && !means) || !jitters || !mu || !var || max_iter < 0 || !elbo ||
-        !iterations || !converged || !info || (!mu_out != !var_out) || (flags & ~GPRN_BATCH_FORCED))
+    if (!c || !c->N || io.n < 1 || !io.kparams || (!io.y_resid && !io.means.programs) || !io.jitters || !io.mu || !io.var || io.max_iter < 0 ||
+        !io.elbo || !io.iters || !io.conv || !io.info || (!io.mu_out != !io.var_out) || (io.flags & ~GPRN_BATCH_FORCED))
         return bad(c, "elbocalc_batch: bad argument");
-    if (grad_out && max_iter < 1) return bad(c, "elbocalc_batch_grad: a gradient needs a committed sweep (max_iter >= 1)");
+    if (io.grad_out && io.max_iter < 1) return bad(c, "elbocalc_batch_grad: a gradient needs a committed sweep (max_iter >= 1)");
     // (side by side every evaluation starts from one shared state: under a mask that is the caller's choice, option "batch_mask")
     if (c->d_mask && !c->batch_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     // (a prediction's call reads what the loops left in the batch's own buffers and writes nothing of the context's: a committed
     // sweep of the context stays what it was, as under gprn_predict_batch)
-    if (!pred && !draws) c->grad_ready = false;
+    if (!io.pred.ns && !io.draws.ns) c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "elbocalc_batch: call set_owners first");
     if (comm_active(c) || c->world != 1) { c->err = "elbocalc_batch: one rank only (a pool of ranks splits the list itself)"; return GPRN_E_UNSUPPORTED; }
@@ -795,16 +791,14 @@ static int elbocalc_batch_impl(gprn_ctx* c, int n_eval, const double* kernel_par
     // (a one-tile problem with the small path switched off -- option "small_path" = 0, or gprn_keep_sigma on: there is no
     // batched form for it, as include/gprn_hip.h promises; inference.nELBO_batch then evaluates one by one -- ADVICE r5)
     if (!small && c->T < 2) { c->err = "elbocalc_batch: one-tile problems run side by side on the small path only"; return GPRN_E_UNSUPPORTED; }
-    TRY(batch_validate(c, n_kernel_params));
+    TRY(batch_validate(c, io.n_kpar));
     const auto run = small ? small_batch_run : mid_batch_run;
     int cap = 0;
-    TRY(batch_reserve(c, small ? small_batch_reserve : mid_batch_reserve, n_eval, &cap));
-    const BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info,
-                     mu_out, var_out, c->p, (size_t)(c->p + 1) * c->q * c->N, (size_t)c->p * c->N, flags, grad_out,
-                     pred ? *pred : BatchPred{}, means ? *means : BatchMeans{}, draws ? *draws : BatchDraws{}};
-    // (with grad_out each chunk ends with the gradient pass of its evaluations, before the next chunk overwrites the slabs;
-    // with a prediction, with the prediction pass; with draws, with the draw pass)
-    for (int e0 = 0; e0 < n_eval; e0 += cap) TRY(run(c, io.slice(e0, std::min(cap, n_eval - e0))));
+    TRY(batch_reserve(c, small ? small_batch_reserve : mid_batch_reserve, io.n, &cap));
+    io.p = c->p; io.state = (size_t)(c->p + 1) * c->q * c->N; io.yv = (size_t)c->p * c->N;
+    // (each chunk ends with batch_tail.hip's tail over its evaluations -- the gradient pass, the mean entries, the prediction
+    // pass, the draw pass, as asked for -- before the next chunk overwrites the slabs)
+    for (int e0 = 0; e0 < io.n; e0 += cap) TRY(run(c, io.slice(e0, std::min(cap, io.n - e0))));
     return GPRN_OK;
 }
 
@@ -814,13 +808,14 @@ extern "C" int gprn_elbocalc_batch_grad(gprn_ctx* c, int n_eval, const double* k
                                         double* mu_out, double* var_out, double* grad_out)
 {
     DeviceLock lock_(c);
-    return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
-                               iterations, converged, info, mu_out, var_out, grad_out, nullptr);
+    BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info, mu_out, var_out};
+    io.flags = flags; io.grad_out = grad_out;
+    return elbocalc_batch_impl(c, io);
 }
 
 // gprn_elbocalc_batch_grad with the outputs' mean programs (gprn_set_mean) evaluated on the device in place of a y - mean from the
 // host (include/gprn_hip.h; meanfunc.py:276-293, _utils.py:62-118, meanfield.py:382-411, 623-624): batch_stage launches
-// k_mean_eval_b behind its copies, and a chunk ends with k_mean_grad_b over what its loops left in the slabs (mean.hip)
+// k_mean_eval_b behind its copies, and a chunk's tail runs k_mean_grad_b over what its loops left in the slabs (mean.hip)
 extern "C" int gprn_elbocalc_batch_means(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
                                          const double* mean_params, int n_mean_params, const double* jitters, const double* mu,
                                          const double* var, int max_iter, int flags, double* elbo, int* iterations, int* converged,
@@ -837,16 +832,16 @@ extern "C" int gprn_elbocalc_batch_means(gprn_ctx* c, int n_eval, const double* 
     if (mean_grad_out && max_iter < 1) return bad(c, "elbocalc_batch_means: a gradient needs a committed sweep (max_iter >= 1)");
     HIP_TRY(c, hipSetDevice(c->device));
     CallScratch scr(c);
-    BatchMeans means;
-    TRY(mean_batch_upload(c, scr, n_eval, mean_params, n_mean_params, &means));
-    means.resid_out = resid_out; means.grad_out = mean_grad_out;
-    return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, nullptr, jitters, mu, var, max_iter, flags, elbo,
-                               iterations, converged, info, mu_out, var_out, grad_out, nullptr, &means);
+    BatchIo io{n_eval, kernel_params, n_kernel_params, nullptr, jitters, mu, var, max_iter, elbo, iterations, converged, info, mu_out, var_out};
+    io.flags = flags; io.grad_out = grad_out;
+    TRY(mean_batch_upload(c, scr, n_eval, mean_params, n_mean_params, &io.means));
+    io.means.resid_out = resid_out; io.means.grad_out = mean_grad_out;
+    return elbocalc_batch_impl(c, io);
 }
 
 // gprn_elbocalc_batch_grad(grad_out = NULL) with, per evaluation, gprn_predict's posterior form at the end of its loop (include/
-// gprn_hip.h): the reference's _Prediction (meanfield.py:1289-1381) once per kept vector, behind nELBO -- each chunk ends with
-// midn.hip's batch_pred_pass over what its loops left in the slabs
+// gprn_hip.h): the reference's _Prediction (meanfield.py:1289-1381) once per kept vector, behind nELBO -- each chunk's tail runs
+// batch_tail.hip's prediction pass over what its loops left in the slabs
 extern "C" int gprn_elbocalc_batch_predict(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
                                            const double* y_resid, const double* jitters, const double* mu, const double* var,
                                            int max_iter, int flags, int ns, const double* tstar,
@@ -861,14 +856,15 @@ extern "C" int gprn_elbocalc_batch_predict(gprn_ctx* c, int n_eval, const double
     if (max_iter < 1) return bad(c, "elbocalc_batch_predict: a prediction needs a committed sweep (max_iter >= 1)");
     if ((!lat_mean != !lat_var) || (!out_mean != !out_var)) return bad(c, "elbocalc_batch_predict: each pair is both or neither NULL");
     if (!lat_mean && !out_mean) return bad(c, "elbocalc_batch_predict: neither the latent nor the output pair was asked for");
-    const BatchPred pred{ns, tstar, lat_mean, lat_var, out_mean, out_var, c->G, c->p};
-    return elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
-                               iterations, converged, info, mu_out, var_out, nullptr, &pred);
+    BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info, mu_out, var_out};
+    io.flags = flags;
+    io.pred = BatchPred{ns, tstar, lat_mean, lat_var, out_mean, out_var, c->G, c->p};
+    return elbocalc_batch_impl(c, io);
 }
 
 // gprn_elbocalc_batch_predict with joint draws in place of the four prediction rows (include/gprn_hip.h): per evaluation
 // gprn_predict_draws' posterior form at the end of its loop, from the caller's normals -- what inference.sample_posterior does
-// once per kept vector, behind nELBO.  Each chunk ends with midn.hip's batch_draw_pass over what its loops left in the slabs;
+// once per kept vector, behind nELBO.  Each chunk's tail runs batch_tail.hip's draw pass over what its loops left in the slabs;
 // always the posterior form, whatever option "predict_form" says
 extern "C" int gprn_elbocalc_batch_draws(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
                                          const double* y_resid, const double* jitters, const double* mu, const double* var,
@@ -885,9 +881,10 @@ extern "C" int gprn_elbocalc_batch_draws(gprn_ctx* c, int n_eval, const double* 
     if (!lat_draws && !out_draws) return bad(c, "elbocalc_batch_draws: neither the latent nor the output draws were asked for");
     if (!nugget_out || !draw_info) return bad(c, "elbocalc_batch_draws: nugget_out and draw_info expected");
     int info_gp = -1;
-    const BatchDraws draws{ns, n_draws, tstar, z, lat_draws, out_draws, nugget_out, draw_info, &info_gp, c->G, c->p};
-    const int rc = elbocalc_batch_impl(c, n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, flags, elbo,
-                                       iterations, converged, info, mu_out, var_out, nullptr, nullptr, nullptr, &draws);
+    BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info, mu_out, var_out};
+    io.flags = flags;
+    io.draws = BatchDraws{ns, n_draws, tstar, z, lat_draws, out_draws, nugget_out, draw_info, &info_gp, c->G, c->p};
+    const int rc = elbocalc_batch_impl(c, io);
     if (!rc && info_gp >= 0) c->info_gp = info_gp;       // (the latent GP of the first failed last rung: gprn_last_info_gp)
     return rc;
 }

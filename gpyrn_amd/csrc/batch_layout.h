@@ -1,4 +1,4 @@
-// The layouts of the blocks a context keeps between side-by-side calls (smalln.hip, midn.hip, api_sweep.hip's staging): ONE
+// The layouts of the blocks a context keeps between side-by-side calls (smalln.hip, midn.hip, batch_tail.hip's draw pass, api_sweep.hip's staging): ONE
 // function per block, walked with a null base for the block's size (layout_count) and with the real base for the pointers
 // into it (layout_at).  A layout's struct lists its ranges in the block's order.  No HIP in here (tests/layout_check.cpp).
 #pragma once
@@ -113,7 +113,7 @@ struct SmallSlab {
 };
 // the copy that holds the mean of an evaluation's last committed sweep (its variance: the next one): odd trips wrote copy B
 static inline size_t small_final_copy(int iters) { return iters >= 1 && (iters & 1) ? 2 : 0; }
-// ---- the draw pass behind a chunk's loop (gprn_elbocalc_batch_draws; midn.hip batch_draw_pass): the scratch of one GROUP of
+// ---- the draw pass behind a chunk's loop (gprn_elbocalc_batch_draws; batch_tail.hip batch_draw_pass): the scratch of one GROUP of
 // evaluations, an allocation class of its own.  Per slot (= evaluation x latent GP) W^T = (K* S) X^T of all ns_pad rows
 // (ns_pad x ld), the covariance C, the rung's matrix / its factor F and the factor's inverse X (ns_pad^2 each), the normals Z
 // and the product L Z (nd_pad x ns_pad each); behind them the rows (k**, mean*, var* at pitch ns_pad), the outputs' draws,

@@ -764,7 +764,7 @@ int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d
     return GPRN_OK;
 }
 
-// ---- ... in the POSTERIOR form (gprn_elbocalc_batch_predict: the prediction pass behind a chunk's loop, midn.hip
+// ---- ... in the POSTERIOR form (gprn_elbocalc_batch_predict: the prediction pass behind a chunk's loop, batch_tail.hip
 // batch_pred_pass): K* diag(s) and k** of many matrices, matrix z with its own program and its own s = sqrt(d) at s + z * ld.
 // The delta handling of k_fill_rect<KID, true>: the nugget and WhiteNoise apply in K* exactly where t*_i == t_n as doubles,
 // in k** always; column ld of a row group (one thread of an extra workgroup) is k**, so the element code has ONE call site

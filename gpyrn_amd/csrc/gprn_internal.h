@@ -608,10 +608,10 @@ struct BatchMeans {
 };
 // mean.hip: y_raw - mean of io's evaluations into `yres` (device, [n][p N]) on `stream`, behind the copies of batch_stage ...
 int mean_stage_resid(gprn_ctx* c, const BatchMeans& mn, int n, double* yres, hipStream_t stream);
-// ... and the bound form's mean entries of a chunk whose loops have ended, from what they left in the slabs: y - mean and the
-// variances ([n][p N] each), evaluation e's state at state + state_idx[e] * state_stride.  w: the context the launch goes through
-int mean_grad_pass(gprn_ctx* c, gprn_ctx* w, const BatchMeans& mn, int n, const int* info, const double* yres, const double* variance,
-                   const double* state, size_t state_stride, const std::vector<int>& state_idx);
+// ... and the bound form's mean entries of a chunk whose loops have ended, from what they left (ChunkLeft, below): y - mean, the
+// variances and every evaluation's final state
+struct ChunkLeft;
+int mean_grad_pass(gprn_ctx* c, const ChunkLeft& left, const BatchMeans& mn);
 
 // ... the call's programs and parameters to the device (scr owns them): GPRN_E_ARG where n_params is not the programs' sum
 struct CallScratch;
@@ -621,9 +621,9 @@ int mean_batch_upload(gprn_ctx* c, CallScratch& scr, int n_eval, const double* m
 struct BatchIo {
     int n; const double* kparams; int n_kpar; const double *y_resid, *jitters, *mu, *var; int max_iter;
     double* elbo; int *iters, *conv, *info; double *mu_out, *var_out;     // (mu_out, var_out: both or neither)
-    int p; size_t state, yv;               // per evaluation: jitters, doubles of mu / var, doubles of y_resid
-    int flags;                             // GPRN_BATCH_FORCED: no stop rule, max_iter committed trips each
-    double* grad_out;                      // [n][n_kpar]: the gradient of each evaluation's last committed sweep, or null
+    int p = 0; size_t state = 0, yv = 0;   // per evaluation: jitters, doubles of mu / var, doubles of y_resid (elbocalc_batch_impl enters them)
+    int flags = 0;                         // GPRN_BATCH_FORCED: no stop rule, max_iter committed trips each
+    double* grad_out = nullptr;            // [n][n_kpar]: the gradient of each evaluation's last committed sweep, or null
     BatchPred pred{};                      // gprn_elbocalc_batch_predict: the prediction pass behind the chunk's loop (ns = 0: none)
     BatchMeans means{};                    // gprn_elbocalc_batch_means: y - mean is formed on the device (programs = null: y_resid is read)
     BatchDraws draws{};                    // gprn_elbocalc_batch_draws: the draw pass behind the chunk's loop (ns = 0: none)
@@ -635,68 +635,67 @@ struct BatchIo {
                        flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0), means.from(e0, yv), draws.from(e0)};
     }
 };
-// grad.hip: the steps of gprn_grad_elbo over the evaluations of a batch's chunk whose loops have ended, slots = evaluations x
-// latent GPs (gprn_elbocalc_batch_grad).  The drivers say where each evaluation's matrices, s = sqrt(d) and state lie; the
-// launches do not grow with n.  Evaluation e's state is state + state_idx[e] * state_stride (the reference's layout).
-struct GradBatchIn {
-    int N, ld, T, q, G;
-    const double* t;                       // the observation times (device)
-    int n = 0;                             // evaluations
-    std::vector<double*> rows;             // [n][G][GPRN_NBUF]: BUF_B (overwritten: lower(B^-1)), BUF_X, BUF_K, BUF_KLINV
-    std::vector<double*> kinv;             // [n][q - 1]: lower(K_j^-1), j >= 1
-    std::vector<double*> s;                // [n][G]: sqrt(d) of the last committed sweep (ld each)
-    const double* state = nullptr;
-    size_t state_stride = 0;
-    std::vector<int> state_idx;            // [n]
-    std::vector<const double*> kparams;    // [n] (host): the evaluation's kernel parameters
-    std::vector<double*> out;              // [n] (host): its row of grad_out
-    int grad_exact = 0;                    // the caller's option "grad_exact"
-    bool bound = false;                    // the caller's option "elbo_form" is GPRN_ELBO_BOUND: a from the latent GP's own mean, no cross
-    int p = 0;                             // terms (kinv is empty); p: outputs, for the own-mean row
-};
-// w: the context the launches go through (its stream, its task lists, its grad_scratch); budget: bytes the pass's scratch may
-// take -- beyond it (or when the device refuses) the evaluations go in groups; GPRN_E_NOMEM when one evaluation's scratch does
-// not fit.  The scratch is an allocation class of its own: the drivers give it what the chunk's slabs left of the budget
-int grad_batch_pass(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const GradBatchIn& in, size_t budget);
-// midn.hip: the prediction pass behind a chunk's loop (gprn_elbocalc_batch_predict), for both drivers -- the posterior form of
-// gprn_predict (api_more.hip) over slots = evaluations x latent GPs in the set-up's order (slot = evaluation * G + latent GP),
-// t* in blocks of at most ld rows: the batched posterior fill, (K* S) X^T by the tile kernel, the row kernel, the jitter-once
-// combination, the block's rows through a pinned buffer into the caller's rows.  The driver says where each slot's X lies and which two ld x ld
-// buffers per slot the loop has finished with; evaluations whose info > 0 get NaN rows.
-struct PredPassIn {
-    int n, G, p, N, ld, T;                 // evaluations of the launches, the problem's geometry
-    double** tab;                          // device [n G][GPRN_NBUF]: BUF_X = X (read), BUF_K = a block of K* S, BUF_KLINV = of W^T
-    double* const* kptr;                   // device [n G]: the BUF_K pointers again (where the fill writes)
+// ---- batch_tail.hip: what runs behind a chunk's loop of gprn_elbocalc_batch*, written once for both drivers.
+// What the loop left, in ONE description: each driver has one function that fills it (smalln.hip small_left, midn.hip mid_left)
+// and the passes read it beside their own request -- io.grad_out with io.kparams, BatchMeans, BatchPred, BatchDraws.  Slots =
+// evaluations x latent GPs in the set-up's order (slot = evaluation * G + latent GP); everything is as the LAST COMMITTED sweep of
+// each evaluation left it.
+struct ChunkLeft {
+    int n, cap;                            // evaluations of the chunk; evaluations the driver's tables are laid out for
+    int G, p, q, N, ld, T;                 // the problem's geometry
+    gprn_ctx* w;                           // the context the launches go through: c itself on one tile, the worker above
+    double* const* rows;                   // host [cap G][GPRN_NBUF]: the sweeps' pointer rows -- B, X, K, chol(K)^-1
+    double* const* kinv;                   // host [cap][q - 1]: lower(K_j^-1), j >= 1; null in the bound form
+    const double *s, *ct;                  // device [n G][ld]: sqrt(d) and X^T X z; null where the call does not need them
+    // the states: copy k of the means at mu + k * state, of the variances at var + k * state; evaluation e's final one is copy
+    // final_copy[e] (host) -- below 0: nothing was committed, the caller's own state is the result.  They come back as `ranges`
+    // ranges of n copies each, range_stride copies apart, into pinned images indexed like the device's
+    const double *mu, *var;
+    size_t state;
+    const int* final_copy;
+    int ranges; size_t range_stride;
+    double *pin_mu, *pin_var;
+    const double *yres, *variance;         // device [n][p N]: y - mean and the variances
     const void* d_programs;                // device [n G] fill programs (the set-up's: they carry the sweeps' nugget)
-    const char* h_programs;                // ... and their staged host image (which instruction streams the fill needs)
-    const double *s, *ct;                  // device [n G][ld]: sqrt(d) and X^T X z of each slot's last committed sweep
-    double *kss, *lmean, *lvar;            // device [n G][ld]: a block's k**, latent means and variances
-    double *omean, *ovar;                  // device [n p][ld]: a block's outputs
-    const double* jitters;                 // host [n][p]
-    const int* info;                       // host [n]
-    // the pass's own small buffers, kept by the driver between calls (a call allocates and frees nothing on the device):
-    double *d_ts, *d_jit;                  // device: ns prediction times, n p jitters
-    const TileTask* d_tasks;               // device: pred_pass_tasks(T), uploaded once
-    double* pin;                           // pinned host: a block's rows on their way out, 2 (n G + n p) ld doubles
+    const char* h_programs;                // ... and their staged host image (which instruction streams a fill needs)
+    const int* info;                       // host [n]: the pivot verdicts (> 0: the evaluation's matrices hold what the failure left)
+    size_t left;                           // bytes the chunk's slabs left of option "batch_mem_mb": the passes' scratch
 };
-int batch_pred_pass(gprn_ctx* w, const PredPassIn& in, const BatchPred& out);
-// midn.hip: the draw pass behind a chunk's loop (gprn_elbocalc_batch_draws), for both drivers -- gprn_predict_draws' posterior
-// form (api_more.hip) over slots = evaluations x latent GPs in the set-up's order: W^T = (K* S) X^T of ALL rows of t* and the
-// means as batch_pred_pass forms them, K** of every slot in one launch, C = K** - W W^T, the ladder per slot, L Z, the
-// combination -- in groups of evaluations whose scratch (batch_layout.h draw_scratch) fits `budget` bytes.  The driver says
-// where each slot's X lies and which ld x ld buffer per slot the loop has finished with (a block of K* S); evaluations whose
-// info > 0 are left out of the ladder and get NaN rows, as does one whose last rung failed.
-struct DrawPassIn {
-    int n, G, p, q, N, ld, T;              // evaluations, the problem's geometry
-    std::vector<double*> X, blk;           // host [n G]: the slot's X (read), an ld x ld buffer it may write
-    const void* d_programs;                // device [n G] fill programs (the set-up's: they carry the sweeps' nugget)
-    const char* h_programs;                // ... and their staged host image
-    const double *s, *ct;                  // device [n G][ld]: sqrt(d) and X^T X z of each slot's last committed sweep
-    const int* info;                       // host [n]
-    double* pin; size_t pin_count;         // pinned host, the driver's: the normals on their way in, the draws on their way out
+// The per-block row vectors of the prediction pass, device [n G][ld] (the outputs: [n p][ld]) -- the driver lends them: above one
+// tile the worker's per-slot vectors, on one tile an allocation of its own
+struct PredRows { double *kss, *lmean, *lvar, *omean, *ovar; };
+// The passes' kept buffers, charged to the driver's DeviceOwner (freed with the batch): there from the first call that asks for
+// a prediction or for draws, so that a call allocates and frees nothing on the device once they exist
+struct DeviceOwner;
+struct TailKept {
+    DeviceOwner* own = nullptr;            // the driver's
+    PredRows rows{};                       // the driver's
+    // the prediction pass's device rows, derived from ChunkLeft::rows: BUF_X = X (read), BUF_K = a block of K* S in B's
+    // workspace, BUF_KLINV = its W^T in K (two ld x ld buffers per slot the loop has finished with; the next chunk's set-up
+    // refills both) -- and behind them the BUF_K pointers again, where the fill writes
+    double** tab = nullptr;                // [cap G][GPRN_NBUF]
+    double** kptr = nullptr;               // [cap G]
+    double *jit = nullptr, *ts = nullptr;  // [cap p] jitters, [ns] prediction times (it only grows)
+    int ns = 0;
+    TileTask* tasks = nullptr;             // pred_pass_tasks(T)
+    double* pin = nullptr;                 // pinned: a block's rows on their way to the caller, 2 cap (G + p) ld doubles
+    double* draw_pin = nullptr;            // pinned: the draw pass's normals and draws on their way, GPRN_DRAW_PIN_DOUBLES
+    int ensure(gprn_ctx* c, const ChunkLeft& left, int pred_ns, bool draws);
 };
-int batch_draw_pass(gprn_ctx* w, const DrawPassIn& in, const BatchDraws& out, size_t budget);
-#define GPRN_DRAW_PIN_DOUBLES ((size_t)1 << 21)   // the drivers' pinned buffer for it: 16 MiB, pieces of that size travel
+#define GPRN_DRAW_PIN_DOUBLES ((size_t)1 << 21)   // 16 MiB, pieces of that size travel
+// GPRN_BATCH_TIMERS: the driver's timer, its own start of the line (head, formatted only when the timers are on), what it
+// calls the last pass, time spent before the timer started, and what follows the total
+struct LapTimer;
+struct TailReport { LapTimer& t; std::string head; const char* pass_label; double before; std::string suffix; };
+// The tail of a chunk: the states back, the gradient pass, the bound form's mean entries, the prediction pass, the draw pass,
+// the timers' line.  retry_draws: a dependency wait of the draw pass's ladder that gave up re-runs the pass alone on the event
+// schedule (one tile; above, mid_run re-runs the whole chunk)
+int batch_tail(gprn_ctx* c, const BatchIo& io, const ChunkLeft& left, TailKept& kept, bool retry_draws, TailReport& rep);
+// grad.hip: the steps of gprn_grad_elbo over the chunk's evaluations (gprn_elbocalc_batch_grad), slots = evaluations x latent
+// GPs; the launches do not grow with n.  An evaluation whose pivot failed gets a row of zeros and is left out.  Writes lower(B^-1)
+// over each slot's B.  The scratch is an allocation class of its own (gprn_ctx::grad_scratch of left.w) within left.left bytes --
+// beyond them (or when the device refuses) the evaluations go in groups; GPRN_E_NOMEM when one evaluation's scratch does not fit
+int grad_batch_pass(gprn_ctx* c, const ChunkLeft& left, const BatchIo& io);
 // W^T = (K* S) X^T over T x T tiles, row block by row block: a ragged last block of t* runs a prefix of the list
 std::vector<TileTask> pred_pass_tasks(int T, int ld);
 // What both drivers of gprn_elbocalc_batch ask of the caller's kernels and kernel_params (api_sweep.hip)
@@ -719,15 +718,7 @@ int batch_stage_programs(gprn_ctx* c, const double* kparams, int n_kpar, int B, 
 // piece than it reports free the chunk is halved until it fits (nothing has run yet: the buffers come before any launch)
 int batch_reserve(gprn_ctx* c, int (*reserve)(gprn_ctx*, int, int*), int n_eval, int* cap);
 size_t batch_budget_bytes(gprn_ctx* c);        // device memory a chunk of evaluations may take (option "batch_mem_mb")
-// Evaluation b of a chunk enters the gradient pass (the driver appends its rows, s, kinv, state_idx) -- unless its pivot
-// failed: a row of zeros, left out (false).  grad_batch_left: the scratch gets what the chunk's `held` bytes left of the budget
-static inline bool grad_batch_enter(const BatchIo& io, int b, GradBatchIn& in)
-{
-    double* const row = io.grad_out + (size_t)b * io.n_kpar;
-    if (io.info[b] > 0) { std::fill(row, row + io.n_kpar, 0.0); return false; }
-    in.kparams.push_back(io.kparams + (size_t)b * io.n_kpar); in.out.push_back(row); in.n += 1;
-    return true;
-}
+// the passes' scratch gets what the chunk's `held` bytes left of the budget
 static inline size_t grad_batch_left(gprn_ctx* c, size_t held) { const size_t b = batch_budget_bytes(c); return b > held ? b - held : 0; }
 // one row of a pointer table; the first positive pivot verdict among n (LAPACK style: the failing latent GP's), or 0
 static inline void buf_row(double** r, double* B, double* X, double* K, double* KLinv) { r[BUF_B] = B; r[BUF_X] = X; r[BUF_K] = K; r[BUF_KLINV] = KLinv; }

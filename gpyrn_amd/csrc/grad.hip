@@ -581,21 +581,23 @@ static void grad_batch_counts(const std::vector<KernelSpec>& kspec, int exact, i
 
 // device bytes of the pass's scratch per evaluation: a, u, the residual, the column partial sums, the blocks' partial sums,
 // three ld x ld matrices per node j >= 1, the slots and the tables
-static size_t grad_batch_bytes(const GradBatchIn& in, int total, int pmax)
+static size_t grad_batch_bytes(const ChunkLeft& in, bool bound, int total, int pmax)
 {
     const size_t ld = in.ld, nn = ld * ld, G = in.G, nb = ld / 64, nblk = nb * (nb + 1) / 2;
-    const size_t nq1 = in.bound ? 0 : (size_t)(in.q - 1);          // (nodes with a cross term: none in the bound form)
+    const size_t nq1 = bound ? 0 : (size_t)(in.q - 1);          // (nodes with a cross term: none in the bound form)
     return (G * ld * (3 + (size_t)in.T) + G * pmax * nblk + total + 3 * nq1 * nn) * sizeof(double) +
            G * (sizeof(GradSlot) + (GPRN_NBUF + 3) * sizeof(double*) + 2 * sizeof(int)) + nq1 * GPRN_NBUF * sizeof(double*) +
            256 * 11;                                         // (each piece is rounded up to 256 bytes; the task list is per group)
 }
 
-// evaluations [e0, e0 + ne) of the pass; the scratch grows before the first launch (GPRN_E_NOMEM: nothing has run)
-static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const GradBatchIn& in, int e0, int ne, int total,
-                            int pmax)
+// the ne evaluations evs[0 .. ne) of the chunk; the scratch grows before the first launch (GPRN_E_NOMEM: nothing has run)
+static int grad_batch_group(gprn_ctx* c, const ChunkLeft& in, const BatchIo& io, const int* evs, int ne, int total, int pmax)
 {
+    gprn_ctx* const w = in.w;
+    const std::vector<KernelSpec>& kspec = c->kspec;
+    const bool bound = c->elbo_form == GPRN_ELBO_BOUND;   // (a from the latent GP's own mean, no cross terms: kinv is empty)
     const int N = in.N, ld = in.ld, T = in.T, q = in.q, G = in.G;
-    const size_t nn = (size_t)ld * ld, nslots = (size_t)ne * G, nj = in.bound ? 0 : (size_t)ne * (q - 1);
+    const size_t nn = (size_t)ld * ld, nslots = (size_t)ne * G, nj = bound ? 0 : (size_t)ne * (q - 1);
     const int nb = ld / 64, nblk = nb * (nb + 1) / 2;
     hipStream_t st = w->stream;
     std::vector<double> h((size_t)ne * total);
@@ -647,20 +649,21 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
     std::vector<int> hi(2 * nslots);
     std::vector<GradSlot> slots(nslots);
     for (int e = 0; e < ne; ++e) {
-        const int ev = e0 + e;
-        const double* kp = in.kparams[ev];
+        const int ev = evs[e];
+        const double* kp = io.kparams + (size_t)ev * io.n_kpar;
         int off = 0;
         for (int g = 0; g < G; ++g) {
             const size_t sl = (size_t)e * G + g;
-            double* const* row = in.rows.data() + ((size_t)ev * G + g) * GPRN_NBUF;
+            double* const* row = in.rows + ((size_t)ev * G + g) * GPRN_NBUF;
+            double* const s_ev = const_cast<double*>(in.s) + ((size_t)ev * G + g) * ld;
             for (int b = 0; b < GPRN_NBUF; ++b) hp[sl * GPRN_NBUF + b] = row[b];
             hp[o_kl + sl] = row[BUF_KLINV];
             hp[o_k + sl] = row[BUF_K];
-            hp[o_s + sl] = in.s[(size_t)ev * G + g];
+            hp[o_s + sl] = s_ev;
             hi[sl] = g;
-            hi[nslots + sl] = in.state_idx[ev];
+            hi[nslots + sl] = in.final_copy[ev];
             double* cr = nullptr;
-            if (g >= 1 && g < q && !in.bound) {
+            if (g >= 1 && g < q && !bound) {
                 const size_t z = (size_t)e * (q - 1) + (g - 1);
                 double** cp = hp.data() + o_cp + z * GPRN_NBUF;
                 cp[0] = cross + (3 * z) * nn; cp[1] = in.kinv[(size_t)ev * (q - 1) + (g - 1)];
@@ -669,8 +672,8 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
             }
             GradSlot& s = slots[sl];
             memset(&s, 0, sizeof(s));
-            grad_slot_kernel(kspec[g], kp + off, e * total + off, &s, in.grad_exact);
-            s.Binv = row[BUF_B]; s.s = in.s[(size_t)ev * G + g]; s.a = a + sl * ld; s.cross = cr;
+            grad_slot_kernel(kspec[g], kp + off, e * total + off, &s, c->grad_exact);
+            s.Binv = row[BUF_B]; s.s = s_ev; s.a = a + sl * ld; s.cross = cr;
             off += kspec[g].n_params;
         }
     }
@@ -680,7 +683,7 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
     HIP_TRY(w, hipMemcpyAsync(d_int, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(w, hipMemcpyAsync(d_slots, slots.data(), nslots * sizeof(GradSlot), hipMemcpyHostToDevice, st));
     if (nj) HIP_TRY(w, hipMemcpyAsync(d_t, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice, st));
-    const Phase ph{d_ptr, d_int, (int)nslots, 0, nullptr, EvalMap{d_int + nslots, in.state_stride, 0, 0, 0}, N, ld, T};
+    const Phase ph{d_ptr, d_int, (int)nslots, 0, nullptr, EvalMap{d_int + nslots, in.state, 0, 0, 0}, N, ld, T};
     // (1) lower(B^-1) = lower(X^T X) of every slot into its B workspace
     TRY(lauum_lower(w, ph));
     // (2) the cross terms of every (evaluation, node j >= 1): grad_prelude's pair of task lists, batch = nj
@@ -697,12 +700,12 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
     // (3) a = L_K^-T L_K^-1 m and one refinement step, per slot
     HIP_TRY(w, hipMemsetAsync(resid, 0, nslots * ld * sizeof(double), st));
     for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 0) TRY(vec_lower_matvec(w, ph, BUF_KLINV, in.state, N, in.bound ? 2 : 1, u));
+        if (pass == 0) TRY(vec_lower_matvec(w, ph, BUF_KLINV, in.mu, N, bound ? 2 : 1, u));
         else {
             prof_begin(w, GPRN_T_VEC);
             hipLaunchKernelGGL(k_grad_residual<true>, dim3((N + 3) / 4, (unsigned)nslots), dim3(256), 0, st,
-                               (double* const*)(d_ptr + o_k), in.state, (const double*)a, N, ld, resid, (const int*)d_int, ph.ev,
-                               in.p, in.bound ? q : 0);
+                               (double* const*)(d_ptr + o_k), in.mu, (const double*)a, N, ld, resid, (const int*)d_int, ph.ev,
+                               in.p, bound ? q : 0);
             prof_end(w);
             HIP_TRY(w, hipGetLastError());
             TRY(vec_lower_matvec(w, ph, BUF_KLINV, resid, ld, 0, u));
@@ -722,13 +725,13 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
     }
     prof_begin(w, GPRN_T_VEC);
     if (any_closed)
-        hipLaunchKernelGGL(k_grad_contract_b<0>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+        hipLaunchKernelGGL(k_grad_contract_b<0>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, (const double*)w->d_time,
                            N, ld, nblk, pmax, part);
     if (any_fd)
-        hipLaunchKernelGGL(k_grad_contract_b<1>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+        hipLaunchKernelGGL(k_grad_contract_b<1>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, (const double*)w->d_time,
                            N, ld, nblk, pmax, part);
     if (any_exact)
-        hipLaunchKernelGGL(k_grad_contract_b<2>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, in.t,
+        hipLaunchKernelGGL(k_grad_contract_b<2>, dim3(nblk, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, (const double*)w->d_time,
                            N, ld, nblk, pmax, part);
     hipLaunchKernelGGL(k_grad_final, dim3(pmax, (unsigned)nslots), dim3(256), 0, st, (const GradSlot*)d_slots, (const double*)part,
                        nblk, pmax, d_out);
@@ -736,22 +739,30 @@ static int grad_batch_group(gprn_ctx* w, const std::vector<KernelSpec>& kspec, c
     HIP_TRY(w, hipGetLastError());
     HIP_TRY(w, hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(w, hipStreamSynchronize(st));
-    for (int e = 0; e < ne; ++e) memcpy(in.out[e0 + e], h.data() + (size_t)e * total, (size_t)total * sizeof(double));
+    for (int e = 0; e < ne; ++e) memcpy(io.grad_out + (size_t)evs[e] * io.n_kpar, h.data() + (size_t)e * total, (size_t)total * sizeof(double));
     return GPRN_OK;
 }
 
-int grad_batch_pass(gprn_ctx* w, const std::vector<KernelSpec>& kspec, const GradBatchIn& in, size_t budget)
+int grad_batch_pass(gprn_ctx* c, const ChunkLeft& left, const BatchIo& io)
 {
-    if (!in.n) return GPRN_OK;
+    // an evaluation whose pivot failed: a row of zeros, left out of the launches
+    std::vector<int> evs;
+    for (int b = 0; b < left.n; ++b) {
+        if (left.info[b] > 0) std::fill(io.grad_out + (size_t)b * io.n_kpar, io.grad_out + (size_t)(b + 1) * io.n_kpar, 0.0);
+        else evs.push_back(b);
+    }
+    const int n = (int)evs.size();
+    if (!n) return GPRN_OK;
+    gprn_ctx* const w = left.w;
     int total = 0, pmax = 1;
-    grad_batch_counts(kspec, in.grad_exact, &total, &pmax);
+    grad_batch_counts(c->kspec, c->grad_exact, &total, &pmax);
     if (!total) return GPRN_OK;
-    const size_t per = grad_batch_bytes(in, total, pmax);
+    const size_t per = grad_batch_bytes(left, c->elbo_form == GPRN_ELBO_BOUND, total, pmax);
     // (a launch's grid y or z is the number of slots of the group: far below its 65 535 limit)
-    int group = (int)std::max<size_t>(1, std::min<size_t>(budget / per, (size_t)32768 / in.G));
-    for (int e0 = 0; e0 < in.n;) {
-        const int ne = std::min(group, in.n - e0);
-        const int rc = grad_batch_group(w, kspec, in, e0, ne, total, pmax);
+    int group = (int)std::max<size_t>(1, std::min<size_t>(left.left / per, (size_t)32768 / left.G));
+    for (int e0 = 0; e0 < n;) {
+        const int ne = std::min(group, n - e0);
+        const int rc = grad_batch_group(c, left, io, evs.data() + e0, ne, total, pmax);
         if (rc == GPRN_E_NOMEM && ne > 1) { group = (ne + 1) / 2; w->err.clear(); continue; }   // (nothing of the group has run)
         if (rc == GPRN_E_NOMEM)
             w->err = "elbocalc_batch_grad: out of device memory for the gradient pass of one evaluation (" + w->err + ")";

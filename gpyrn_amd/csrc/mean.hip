@@ -300,24 +300,25 @@ int mean_stage_resid(gprn_ctx* c, const BatchMeans& mn, int n, double* yres, hip
     return GPRN_OK;
 }
 
-int mean_grad_pass(gprn_ctx* c, gprn_ctx* w, const BatchMeans& mn, int n, const int* info, const double* yres, const double* variance,
-                   const double* state, size_t state_stride, const std::vector<int>& state_idx)
+int mean_grad_pass(gprn_ctx* c, const ChunkLeft& left, const BatchMeans& mn)
 {
     if (!mn.n_params) return GPRN_OK;
+    gprn_ctx* const w = left.w;
+    const int n = left.n;
     DeviceOwner own;
     int* d_idx = nullptr;
     double* d_out = nullptr;
     TRY(own.alloc(c, &d_idx, (size_t)n));
     TRY(own.alloc(c, &d_out, (size_t)n * mn.n_params));
-    HIP_TRY(c, hipMemcpyAsync(d_idx, state_idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_idx, left.final_copy, (size_t)n * sizeof(int), hipMemcpyHostToDevice, w->stream));
     HIP_TRY(c, hipMemsetAsync(d_out, 0, (size_t)n * mn.n_params * sizeof(double), w->stream));
     hipLaunchKernelGGL(k_mean_grad_b, dim3(1, c->p, n), dim3(MEAN_GRAD_THREADS), 0, w->stream, (const MeanProgram*)mn.programs, mn.params,
-                       mn.n_params, (const double*)c->d_time, c->N, mn.tmean, yres, variance, state, state_stride, (const int*)d_idx,
+                       mn.n_params, (const double*)c->d_time, c->N, mn.tmean, left.yres, left.variance, left.mu, left.state, (const int*)d_idx,
                        (const uint8_t*)c->d_mask, c->q, d_out);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(w->stream));
     HIP_TRY(c, hipMemcpy(mn.grad_out, d_out, (size_t)n * mn.n_params * sizeof(double), hipMemcpyDeviceToHost));
     for (int b = 0; b < n; ++b)                          // (a failed pivot: a row of zeros, as the kernels' rows of grad_out)
-        if (info[b] > 0) std::fill(mn.grad_out + (size_t)b * mn.n_params, mn.grad_out + (size_t)(b + 1) * mn.n_params, 0.0);
+        if (left.info[b] > 0) std::fill(mn.grad_out + (size_t)b * mn.n_params, mn.grad_out + (size_t)(b + 1) * mn.n_params, 0.0);
     return GPRN_OK;
 }

@@ -1,4 +1,5 @@
-// Many independent evaluations of ONE problem of more than one tile, side by side (gprn_elbocalc_batch for N > 128).
+// Many independent evaluations of ONE problem side by side through a worker context and slabs: the driver of
+// gprn_elbocalc_batch* above one tile (N > 128: mid_batch_reserve, mid_sweep, mid_chunk) and gprn_predict_batch at every N.
 //
 // The reference's realistic callers -- scipy's simplex under inference.optimize, emcee's walkers under inference.mcmc
 // (meanfield.py:1095-1152, 1222-1260) -- ask for nELBO at one parameter vector after the other, on problems of a few
@@ -18,21 +19,12 @@
 // next sweep (its slots are compacted away: the launches shrink with the number of evaluations still running).
 // Lists longer than the memory budget (option "batch_mem_mb") run chunk by chunk.
 //
-// With gradients asked for (gprn_elbocalc_batch_grad) a chunk ends with grad.hip's batched pass over its evaluations: X, the
-// state and the prior's factors of an evaluation stay where its last sweep left them, but the per-slot vectors are indexed by
-// the slot of the ACTIVE tables, which later sweeps of the others reuse -- so s = sqrt(d) of every running evaluation is kept
-// per (evaluation, latent GP) behind each group of sweeps (k_mid_keep_s: reads only, the values' bits do not change).  The pass's
-// scratch is an allocation of its own (gprn_ctx::grad_scratch of the worker) that takes what the slabs left of the budget.
-//
-// With a prediction asked for (gprn_elbocalc_batch_predict) a chunk ends with batch_pred_pass over its evaluations -- the
-// posterior form of gprn_predict, from the X, s = sqrt(d) and ct = X^T X z each evaluation's last committed sweep left: ct is
-// kept beside s (keep_ct), and the pass's two ld x ld buffers per slot are slabs the loop has finished with (a block of K* S
-// in the B workspace, of (K* S) X^T in K) through a pointer table of its own -- no new ld x ld allocation.
-//
-// With draws asked for (gprn_elbocalc_batch_draws) a chunk ends with batch_draw_pass instead: the same three inputs, W^T of ALL
-// rows of t* kept, and the predictive covariance of every slot factored -- in a scratch of its own, like the gradient pass's.
-// Its ladder factors in a phase of the PREDICTION's geometry (ns_pad / 128 tiles): the worker's task lists are rebuilt for it,
-// and again for the problem's T by the next factorisation (ensure_tasks keys them by T).
+// What runs behind a chunk's loop -- the states back, the gradient pass, the mean entries, the prediction pass, the draw pass
+// -- is batch_tail.hip's, for this driver and the one-tile one alike: mid_chunk ends by describing what its loop left (mid_left)
+// and calling batch_tail.  X, the state and the prior's factors of an evaluation stay where its last sweep left them, but the
+// per-slot vectors are indexed by the slot of the ACTIVE tables, which later sweeps of the others reuse -- so for the passes
+// that read them s = sqrt(d) and ct = X^T X z of every running evaluation are kept per (evaluation, latent GP) behind each
+// group of sweeps (k_mid_keep_s into keep_s, keep_ct: reads only, the values' bits do not change).
 //
 // PREDICTION for many parameter vectors (gprn_predict_batch: mid_predict_chunk, at the end of this file) walks gprn_predict's
 // steps over the same slot table, in the same slabs, at every T >= 1: B holds K + 1.25e-12 I + diag v and then its factor, X
@@ -71,12 +63,9 @@ struct MidBatch {
     double *q1_scratch = nullptr;     // [cap q (q - 1) / 2][ld]
     double *keep_s = nullptr;         // [cap][G][ld]: s of each evaluation's last sweep, there from the first call that asks for gradients
     double *keep_ct = nullptr;        // [cap][G][ld]: ct = X^T X z likewise, from the first call that asks for a prediction
-    double **pass_tab = nullptr;      // [cap G][GPRN_NBUF], device: the prediction pass's rows (X; K* S in Bw, its W^T in K), likewise
-    double *pass_jit = nullptr, *pass_ts = nullptr;   // [cap p] jitters, [pass_ns] prediction times (it only grows)
-    TileTask* pass_tasks = nullptr;   // pred_pass_tasks(T)
-    int pass_ns = 0;
-    double* pass_pin = nullptr;       // pinned: a block's rows on their way to the caller, 2 cap (G + p) ld doubles
-    double* draw_pin = nullptr;       // pinned: the draw pass's normals and draws on their way, GPRN_DRAW_PIN_DOUBLES, from the first call that draws
+    TailKept kept;                    // batch_tail.hip's kept buffers (charged to own)
+    std::vector<double*> kinv;        // host [cap][q - 1]: the K_j^-1 above, as the tail reads them
+    std::vector<int> final_copy;      // host [chunk]: the state copy a chunk's evaluations ended in (mid_left)
     char* programs = nullptr;         // [cap][G] fill programs
     // tables and pinned blocks, each laid out by its one function of batch_layout.h
     MidPtrTab dp{};                   // device pointer tables (one allocation)
@@ -203,6 +192,7 @@ static int mid_make(gprn_ctx* c, MidBatch* m, int cap)
         for (int j = 1; j < q && q1; ++j) {                    // lower(K_j^-1) = lower(X^T X), X = chol(K_j)^-1
             const size_t s = (size_t)b * (q - 1) + (j - 1);
             buf_row(hp.kinv + s * GPRN_NBUF, m->Kinv + s * nn, m->KL + ((size_t)b * G + j) * nn, nullptr, nullptr);
+            m->kinv.push_back(m->Kinv + s * nn);
         }
     HIP_TRY(c, hipMemcpy(d_ptr, hp.kptr, (hp.node - hp.kptr) * sizeof(double*), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_int, hi.gp_setup, (hi.gp_node - hi.gp_setup) * sizeof(int), hipMemcpyHostToDevice));
@@ -347,12 +337,29 @@ static int mid_sweep(gprn_ctx* w, MidBatch* m, int nA, double* out4)
     return vec_elbo_evals(w, mid_ev(m, nullptr), m->di.evals, nA, out4, scal, w->d_elbo_part);
 }
 
+// What a chunk's loop left (gprn_internal.h ChunkLeft).  Everything lies in the set-up's order already: the rows are the
+// prediction's (slot = evaluation * G + latent GP), s and ct the kept ones (null: the call did not keep them), evaluation b's
+// final state is copy b of the worker's -- unless nothing was committed (max_iter = 0: the one sweep's update is the discarded
+// one, and the caller's state is what comes back).  The prediction pass's rows per block are the worker's per-slot vectors
+static ChunkLeft mid_left(gprn_ctx* c, MidBatch* m, const BatchIo& io, const double* keep_s, const double* keep_ct)
+{
+    gprn_ctx* w = m->w;
+    m->final_copy.resize(io.n);
+    for (int b = 0; b < io.n; ++b) m->final_copy[b] = io.max_iter == 0 ? -1 : b;
+    m->kept.own = &m->own;
+    m->kept.rows = PredRows{w->d_d, w->d_pred, w->d_s, w->d_z, w->d_cs};
+    const bool scratch = io.grad_out || io.draws.ns > 0;   // (the passes with a scratch of their own)
+    return ChunkLeft{io.n, m->cap, m->G, m->p, m->q, m->N, m->ld, w->T, w, m->host.ptr.pred, m->Kinv ? m->kinv.data() : nullptr,
+                     keep_s, keep_ct, w->d_mu, w->d_var, io.state, m->final_copy.data(), 1, 0, m->out.mu, m->out.var,
+                     w->d_yres, w->d_variance, m->programs, m->in.programs, io.info,
+                     scratch ? grad_batch_left(c, (size_t)m->cap * mid_bytes_per_eval(c)) : 0};
+}
+
 // One chunk of evaluations (n <= cap) from staging to results; restartable (everything it reads is the caller's).
 static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
 {
     gprn_ctx* w = m->w;
     const int B = io.n, G = m->G, p = m->p, q = m->q, N = m->N;
-    const size_t d = io.state;
     hipStream_t st = w->stream;
     LapTimer t;
     double us_stage = 0.0, us_setup = 0.0, us_enqueue = 0.0, us_wait = 0.0, us_host = 0.0;
@@ -383,27 +390,8 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
     const bool predict = io.pred.ns > 0, draws = io.draws.ns > 0;
     if ((io.grad_out || predict || draws) && !m->keep_s) TRY(m->own.alloc(c, &m->keep_s, (size_t)m->cap * G * m->ld));
     double* const keep_s = io.grad_out || predict || draws ? m->keep_s : nullptr;
-    // a prediction: ct = X^T X z too, and the pass's pointer rows -- X where the sweeps leave it, the two blocks in slabs the
-    // loop has finished with when the pass runs (B's workspace and the prior's K; the next chunk's set-up refills both)
+    // a prediction or draws: ct = X^T X z too
     if ((predict || draws) && !m->keep_ct) TRY(m->own.alloc(c, &m->keep_ct, (size_t)m->cap * G * m->ld));
-    if (draws && !m->draw_pin) TRY(m->own.pin(c, &m->draw_pin, GPRN_DRAW_PIN_DOUBLES * sizeof(double)));
-    if (predict && !m->pass_tab) {
-        const size_t nslot = (size_t)m->cap * G, nn = (size_t)m->ld * m->ld;
-        std::vector<double*> rows(nslot * GPRN_NBUF);
-        for (size_t sl = 0; sl < nslot; ++sl)
-            buf_row(&rows[sl * GPRN_NBUF], m->Bw + sl * nn, m->Xw + sl * nn, m->Bw + sl * nn, m->K + sl * nn);
-        TRY(m->own.alloc(c, &m->pass_tab, rows.size()));
-        HIP_TRY(c, hipMemcpy(m->pass_tab, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice));
-        const std::vector<TileTask> tasks = pred_pass_tasks(w->T, m->ld);
-        TRY(m->own.alloc(c, &m->pass_tasks, tasks.size()));
-        HIP_TRY(c, hipMemcpy(m->pass_tasks, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice));
-        TRY(m->own.alloc(c, &m->pass_jit, (size_t)m->cap * p));
-        TRY(m->own.pin(c, &m->pass_pin, 2 * (size_t)m->cap * (G + p) * m->ld * sizeof(double)));
-    }
-    if (predict && io.pred.ns > m->pass_ns) {           // (a longer t* than any before: a new array; the old one goes with the batch)
-        TRY(m->own.alloc(c, &m->pass_ts, (size_t)io.pred.ns));
-        m->pass_ns = io.pred.ns;
-    }
     double* const keep_ct = predict || draws ? m->keep_ct : nullptr;
     int trips = 0;                                       // (forced: every running evaluation has made this many)
     bool tables_stale = true, first = true;
@@ -475,304 +463,16 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
         first = false;
         us_host += t.lap();
     }
-    if (io.mu_out && io.var_out) {
-        HIP_TRY(c, hipMemcpyAsync(m->out.mu, w->d_mu, (size_t)B * d * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipMemcpyAsync(m->out.var, w->d_var, (size_t)B * d * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        memcpy(io.mu_out, m->out.mu, (size_t)B * d * sizeof(double));
-        memcpy(io.var_out, m->out.var, (size_t)B * d * sizeof(double));
-        if (io.max_iter == 0) {                          // (the one sweep's update is the discarded one)
-            memcpy(io.mu_out, io.mu, (size_t)B * d * sizeof(double));
-            memcpy(io.var_out, io.var, (size_t)B * d * sizeof(double));
-        }
+    // ---- what the loop left, and the tail over the full chunk in the set-up's order (batch_tail.hip)
+    TailReport rep{t, std::string(), "prediction / draw pass", 0.0, std::string()};
+    if (batch_timers_on()) {
+        char head[400];
+        snprintf(head, sizeof head, "(N = %d, T = %d), %d evaluations, us: staging %.0f | set-up enqueued %.0f | %d sweeps: enqueue %.0f, "
+                 "waiting for the device %.0f, verdicts %.0f", N, w->T, B, us_stage, us_setup, n_sweeps, us_enqueue, us_wait, us_host);
+        rep.head = head;
     }
-    const double us_states = t.lap();
-    if (io.grad_out) {
-        // ---- the gradient of every evaluation's last committed sweep (grad.hip), over the full chunk in the set-up's order
-        const size_t nn = (size_t)m->ld * m->ld;
-        GradBatchIn in;
-        in.N = N; in.ld = m->ld; in.T = w->T; in.q = q; in.G = G; in.t = w->d_time;
-        in.state = w->d_mu; in.state_stride = d; in.grad_exact = c->grad_exact; in.bound = c->elbo_form == GPRN_ELBO_BOUND; in.p = p;
-        for (int b = 0; b < B; ++b) {
-            if (!grad_batch_enter(io, b, in)) continue;
-            for (int g = 0; g < G; ++g) {
-                in.rows.resize(in.rows.size() + GPRN_NBUF);
-                m->row(&in.rows[in.rows.size() - GPRN_NBUF], (size_t)b * G + g);
-                in.s.push_back(keep_s + ((size_t)b * G + g) * m->ld);
-            }
-            for (int j = 1; j < q && m->Kinv; ++j) in.kinv.push_back(m->Kinv + ((size_t)b * (q - 1) + (j - 1)) * nn);
-            in.state_idx.push_back(b);
-        }
-        TRY(grad_batch_pass(w, c->kspec, in, grad_batch_left(c, (size_t)m->cap * mid_bytes_per_eval(c))));
-    }
-    if (io.means.grad_out) {
-        std::vector<int> idx(B);
-        for (int b = 0; b < B; ++b) idx[b] = b;
-        TRY(mean_grad_pass(c, w, io.means, B, io.info, w->d_yres, w->d_variance, w->d_mu, d, idx));
-    }
-    const double us_grad = t.lap();
-    if (predict) {
-        // ---- the prediction of every evaluation's last committed sweep, over the full chunk in the set-up's order
-        const PredPassIn in{B, G, p, N, m->ld, w->T, m->pass_tab, (double* const*)m->dp.kptr2, m->programs, m->in.programs,
-                            keep_s, keep_ct, w->d_d, w->d_pred, w->d_s, w->d_z, w->d_cs, io.jitters, io.info,
-                            m->pass_ts, m->pass_jit, m->pass_tasks, m->pass_pin};
-        TRY(batch_pred_pass(w, in, io.pred));
-    }
-    if (draws) {
-        // ---- joint draws from the posterior every evaluation's last committed sweep left, over the full chunk in the set-up's
-        // order: X where the sweeps leave it, a block of K* S in B's workspace (the next chunk's set-up refills it)
-        const size_t nn = (size_t)m->ld * m->ld;
-        DrawPassIn in{B, G, p, q, N, m->ld, w->T, {}, {}, m->programs, m->in.programs, keep_s, keep_ct, io.info, m->draw_pin,
-                      GPRN_DRAW_PIN_DOUBLES};
-        for (size_t sl = 0; sl < (size_t)B * G; ++sl) { in.X.push_back(m->Xw + sl * nn); in.blk.push_back(m->Bw + sl * nn); }
-        TRY(batch_draw_pass(w, in, io.draws, grad_batch_left(c, (size_t)m->cap * mid_bytes_per_eval(c))));
-    }
-    const double us_pred = t.lap();
-    if (batch_timers_on())
-        fprintf(stderr, "[gprn] elbocalc_batch (N = %d, T = %d), %d evaluations, us: staging %.0f | set-up enqueued %.0f | %d sweeps: enqueue %.0f, "
-                        "waiting for the device %.0f, verdicts %.0f | states back %.0f | gradient pass %.0f | prediction / draw pass %.0f | total %.0f\n", N, w->T, B, us_stage, us_setup, n_sweeps,
-                us_enqueue, us_wait, us_host, us_states, us_grad, us_pred, t.total());
-    return GPRN_OK;
-}
-
-// The prediction pass of both drivers (gprn_internal.h PredPassIn): gprn_predict's posterior form (api_more.hip predict_impl)
-// with batch = evaluations x latent GPs.  Launches per block of at most ld prediction times: the posterior fill (one per
-// instruction stream its programs need: one or two), one tile product, one row kernel and, for the out_* pair, the
-// combination, then the block's rows back.  The rows go through a PINNED buffer of the driver's and from there, row by
-// row, into the caller's arrays -- not straight into them: a pitched device-to-host copy into pageable memory makes the
-// runtime register the caller's pages, and when the caller frees such an array (a NumPy result dropped) the process's
-// queues are evicted and restored, which stalled the sweeps of the NEXT batch call by 10-25 ms.  Per call one copy of t* and of the jitters.  Nothing is filled at the data times, nothing is factored, and
-// nothing is allocated or freed on the device: t*, the jitters and the task list live in buffers the driver keeps.  Reads X,
-// s, ct and the programs; writes the two blocks and the per-slot rows it was given.
-std::vector<TileTask> pred_pass_tasks(int T, int ld)
-{
-    std::vector<TileTask> tasks;
-    for (int bt = 0; bt < T; ++bt)
-        for (int at = 0; at < T; ++at)
-            tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE, (int64_t)bt * GPRN_TILE * ld,
-                                     (int64_t)at * GPRN_TILE * ld, (at + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_X,
-                                     tile_modes(CM_SET, 0, 0)});
-    return tasks;
-}
-
-int batch_pred_pass(gprn_ctx* w, const PredPassIn& in, const BatchPred& out)
-{
-    const int B = in.n, G = in.G, p = in.p, ld = in.ld, T = in.T, ns = out.ns, nslots = B * G;
-    hipStream_t st = w->stream;
-    double *const d_ts = in.d_ts, *const d_jit = in.d_jit;
-    const TileTask* const d_t = in.d_tasks;
-    HIP_TRY(w, hipMemcpyAsync(d_ts, out.tstar, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, st));
-    if (out.out_mean)
-        HIP_TRY(w, hipMemcpyAsync(d_jit, in.jitters, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, st));
-    const Phase pass{in.tab, nullptr, nslots, 0, nullptr, EvalMap{nullptr, 0, 0, 0, 0}, in.N, ld, T};
-    const size_t row = sizeof(double), n_lat = (size_t)nslots * ld, n_out = (size_t)B * p * ld;
-    double *const pin_lm = in.pin, *const pin_lv = pin_lm + n_lat, *const pin_om = pin_lv + n_lat, *const pin_ov = pin_om + n_out;
-    for (int t0 = 0; t0 < ns; t0 += ld) {
-        const int nsb = std::min(ld, ns - t0), nsb_pad = ((nsb + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
-        TRY(launch_fill_rect_batch_post(w, in.d_programs, in.h_programs, in.kptr, nslots, d_ts + t0, nsb, nsb_pad, in.s, in.kss, ld));
-        TRY(launch_tiles(w, d_t, (size_t)(nsb_pad / GPRN_TILE) * T, pass.ptrs, nslots, ld, GPRN_T_UPDATE));
-        TRY(vec_pred_rows(w, pass, nsb, ld, in.ct, in.kss, in.lmean, in.lvar));
-        if (out.lat_mean) {
-            HIP_TRY(w, hipMemcpyAsync(pin_lm, in.lmean, n_lat * row, hipMemcpyDeviceToHost, st));
-            HIP_TRY(w, hipMemcpyAsync(pin_lv, in.lvar, n_lat * row, hipMemcpyDeviceToHost, st));
-        }
-        if (out.out_mean) {
-            TRY(vec_predict_outputs(w, B, nsb, ld, in.lmean, in.lvar, d_jit, in.omean, in.ovar, true));
-            HIP_TRY(w, hipMemcpyAsync(pin_om, in.omean, n_out * row, hipMemcpyDeviceToHost, st));
-            HIP_TRY(w, hipMemcpyAsync(pin_ov, in.ovar, n_out * row, hipMemcpyDeviceToHost, st));
-        }
-        // (the next block rewrites the rows these copies read)
-        HIP_TRY(w, hipStreamSynchronize(st));
-        if (out.lat_mean)
-            for (int r = 0; r < nslots; ++r) {
-                memcpy(out.lat_mean + (size_t)r * ns + t0, pin_lm + (size_t)r * ld, nsb * row);
-                memcpy(out.lat_var + (size_t)r * ns + t0, pin_lv + (size_t)r * ld, nsb * row);
-            }
-        if (out.out_mean)
-            for (int r = 0; r < B * p; ++r) {
-                memcpy(out.out_mean + (size_t)r * ns + t0, pin_om + (size_t)r * ld, nsb * row);
-                memcpy(out.out_var + (size_t)r * ns + t0, pin_ov + (size_t)r * ld, nsb * row);
-            }
-    }
-    // an evaluation whose pivot failed: NaN in all of its rows (its X holds whatever the failed factorisation left)
-    for (int b = 0; b < B; ++b) {
-        if (in.info[b] <= 0) continue;
-        if (out.lat_mean) {
-            std::fill(out.lat_mean + (size_t)b * G * ns, out.lat_mean + (size_t)(b + 1) * G * ns, NAN);
-            std::fill(out.lat_var + (size_t)b * G * ns, out.lat_var + (size_t)(b + 1) * G * ns, NAN);
-        }
-        if (out.out_mean) {
-            std::fill(out.out_mean + (size_t)b * p * ns, out.out_mean + (size_t)(b + 1) * p * ns, NAN);
-            std::fill(out.out_var + (size_t)b * p * ns, out.out_var + (size_t)(b + 1) * p * ns, NAN);
-        }
-    }
-    return GPRN_OK;
-}
-
-// ------------------------------------------------------------------ the draw pass of both drivers (gprn_elbocalc_batch_draws)
-// Z[slot][d][t] (nd_pad x ns_pad, zero padding) from the caller's normals as they came, z[slot][d][t] (nd x ns).
-// grid (ns_pad / 256, nd_pad, slots)
-__global__ __launch_bounds__(256)
-void k_draw_pad_z(const double* __restrict__ z, int nd, int ns, int nd_pad, int ns_pad, double* __restrict__ Z)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x, slot = blockIdx.z;
-    if (t >= ns_pad) return;
-    for (int d = blockIdx.y; d < nd_pad; d += gridDim.y)
-        Z[((size_t)slot * nd_pad + d) * ns_pad + t] = (d < nd && t < ns) ? z[((size_t)slot * nd + d) * ns + t] : 0.0;
-}
-
-// The _b form of api_more.hip's k_draw_combine, the evaluation on grid z: lat[e][g][d][t] = mean[e G + g][t] + LZ[e G + g][d][t],
-// out[e][i][d][t] = sum_j lat[e][w_ij][d][t] lat[e][f_j][d][t] (out may be null).  LZ: per slot, rows d of pitch ns_pad; mean:
-// rows of pitch ns_pad.  A kernel of its own (DESIGN.md 5 "Variants": lane forms).  grid ((ns + 255) / 256, draws, evaluations)
-__global__ __launch_bounds__(256)
-void k_draw_combine_b(const double* const* __restrict__ LZ, const double* __restrict__ mean, int q, int p, int ns, int ns_pad,
-                      int nd, double* __restrict__ lat, double* __restrict__ out)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= ns) return;
-    const int G = q * (p + 1);
-    const size_t e = blockIdx.z, s0 = e * G;
-    for (int d = blockIdx.y; d < nd; d += gridDim.y) {
-        auto val = [&](int g) { return mean[(s0 + g) * ns_pad + t] + LZ[s0 + g][(size_t)d * ns_pad + t]; };
-        for (int g = 0; g < G; ++g) lat[((s0 + g) * nd + d) * ns + t] = val(g);
-        if (!out) continue;
-        for (int i = 0; i < p; ++i) {
-            double s = 0.0;
-            for (int j = 0; j < q; ++j) s += val(q + j * p + i) * val(j);
-            out[((e * p + i) * nd + d) * ns + t] = s;
-        }
-    }
-}
-
-// count doubles between a device array and a host array of the caller's through the driver's pinned buffer, piece by piece
-// (batch_pred_pass's comment: never a copy between the device and pageable memory)
-static int draw_through_pin(gprn_ctx* w, const DrawPassIn& in, double* dev, double* host, const double* host_in, size_t count)
-{
-    for (size_t at = 0; at < count; at += in.pin_count) {
-        const size_t n = std::min(in.pin_count, count - at);
-        if (host_in) {
-            memcpy(in.pin, host_in + at, n * sizeof(double));
-            HIP_TRY(w, hipMemcpyAsync(dev + at, in.pin, n * sizeof(double), hipMemcpyHostToDevice, w->stream));
-            HIP_TRY(w, hipStreamSynchronize(w->stream));
-        } else {
-            HIP_TRY(w, hipMemcpyAsync(in.pin, dev + at, n * sizeof(double), hipMemcpyDeviceToHost, w->stream));
-            HIP_TRY(w, hipStreamSynchronize(w->stream));
-            memcpy(host + at, in.pin, n * sizeof(double));
-        }
-    }
-    return GPRN_OK;
-}
-
-// evaluations [e0, e0 + ne) of the pass; the scratch comes before the first launch (GPRN_E_NOMEM: nothing has run)
-static int draw_group(gprn_ctx* w, const DrawPassIn& in, const BatchDraws& out, int e0, int ne)
-{
-    const int G = in.G, p = in.p, ld = in.ld, T = in.T, ns = out.ns, nd = out.nd, nslots = ne * G;
-    const DrawShape shape = draw_shape((size_t)ne, (size_t)G, (size_t)p, (size_t)ld, (size_t)ns, (size_t)nd, GPRN_NBUF);
-    const int ns_pad = (int)shape.ns_pad, nd_pad = (int)shape.nd_pad, nblk = (int)shape.nblk;
-    hipStream_t st = w->stream;
-    CallScratch scr(w);                               // (its destructor waits for the stream: the host vectors below outlive the copies)
-    char* block = nullptr;
-    TRY(scr.alloc(&block, layout_count<char>(draw_scratch, shape)));
-    const DrawScratch d = layout_at(block, draw_scratch, shape);
-    const size_t s0 = (size_t)e0 * G, nn = d.nn(), nz = d.z_count(), nw = d.w_count();
-    // ---- the tables: per block of t* the pass's rows, where the fills write, the matrices of C and of L Z
-    std::vector<double*> hp((size_t)(nblk * GPRN_NBUF + 3) * nslots, nullptr), wt(nslots);
-    for (int sl = 0; sl < nslots; ++sl) {
-        double* const W = d.W + (size_t)sl * nw;
-        for (int b = 0; b < nblk; ++b)
-            buf_row(&hp[((size_t)b * nslots + sl) * GPRN_NBUF], nullptr, in.X[s0 + sl], in.blk[s0 + sl], W + (size_t)b * ld * ld);
-        hp[(size_t)nblk * GPRN_NBUF * nslots + sl] = in.blk[s0 + sl];
-        hp[((size_t)nblk * GPRN_NBUF + 1) * nslots + sl] = d.C + (size_t)sl * nn;
-        hp[((size_t)nblk * GPRN_NBUF + 2) * nslots + sl] = d.LZ + (size_t)sl * nz;
-        wt[sl] = W;
-    }
-    // (blk, kblk, cs and lz follow one another in the layout: one copy)
-    HIP_TRY(w, hipMemcpyAsync(d.blk, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, st));
-    HIP_TRY(w, hipMemcpyAsync(d.ts, out.tstar, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, st));
-    TileTask* d_t = nullptr;
-    TRY(scr.tasks(&d_t, pred_pass_tasks(T, ld)));
-    // ---- (1) W^T = (K* S) X^T and the means, block by block of at most ld rows as batch_pred_pass has them; W stays
-    const char* const pg_d = (const char*)in.d_programs + s0 * fill_program_bytes();
-    const char* const pg_h = in.h_programs + s0 * fill_program_bytes();
-    const double *const s = in.s + s0 * ld, *const ct = in.ct + s0 * ld;
-    for (int b = 0; b < nblk; ++b) {
-        const int t0 = b * ld, nsb = std::min(ld, ns - t0), nsb_pad = ((nsb + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
-        const Phase pass{d.blk + (size_t)b * nslots * GPRN_NBUF, nullptr, nslots, 0, nullptr, EvalMap{nullptr, 0, 0, 0, 0}, in.N, ld, T};
-        TRY(launch_fill_rect_batch_post(w, pg_d, pg_h, d.kblk, nslots, d.ts + t0, nsb, nsb_pad, s, d.kss + t0, (size_t)ns_pad));
-        TRY(launch_tiles(w, d_t, (size_t)(nsb_pad / GPRN_TILE) * T, pass.ptrs, nslots, ld, GPRN_T_UPDATE));
-        TRY(vec_pred_rows(w, pass, nsb, ns_pad, ct, d.kss + t0, d.mean + t0, d.pvar + t0));
-    }
-    // ---- (2) K** of every slot in one launch, with the sweeps' nugget; the delta terms between equal times
-    TRY(launch_fill_batch_times(w, pg_d, d.cs, nslots, d.ts, ns, ns_pad));
-    TRY(launch_fill_coincide_batch(w, d.cs, nslots, d.ts, ns, ns_pad));
-    // ---- (3) C -= W W^T, mirrored
-    CovWork cw;
-    cw.G = nslots; cw.ns = ns; cw.ns_pad = ns_pad; cw.Ts = ns_pad / GPRN_TILE; cw.ld = ld; cw.nd = nd; cw.nd_pad = nd_pad; cw.nn = nn;
-    cw.C = d.C; cw.F = d.F; cw.X = d.X; cw.Z = d.Z; cw.LZ = d.LZ; cw.lat = d.Z; cw.out = out.out ? d.out : nullptr;
-    TRY(cov_subtract(w, scr, cw, wt));
-    // ---- (4) the ladder, per slot: the slots of an evaluation whose sweeps failed stay out.  factor_invert sizes its flag words
-    // and task lists by the phase's T alone (factor.hip: d_sig, ensure_tasks -- both regrown or rebuilt on the spot, and again
-    // by the next factorisation of the problem's own T), the verdicts are this call's; the batch is a launch's grid y
-    HIP_TRY(w, hipMemsetAsync(d.X, 0, (size_t)nslots * nn * sizeof(double), st));
-    std::vector<int> pending, fail;
-    std::vector<double> nu;
-    for (int e = 0; e < ne; ++e)
-        for (int g = 0; g < G && in.info[e0 + e] <= 0; ++g) pending.push_back(e * G + g);
-    TRY(cov_ladder(w, scr, cw, pending, false, nu, fail));
-    // ---- (5) L Z and the combination.  The caller's normals travel unpadded into LZ's range and are padded into Z from there
-    TRY(cov_lz(w, scr, cw, [&]() -> int {
-        TRY(draw_through_pin(w, in, d.LZ, nullptr, out.z + s0 * nd * ns, (size_t)nslots * nd * ns));
-        hipLaunchKernelGGL(k_draw_pad_z, dim3((ns_pad + 255) / 256, std::min(nd_pad, 65535), nslots), dim3(256), 0, st,
-                           (const double*)d.LZ, nd, ns, nd_pad, ns_pad, d.Z);
-        HIP_TRY(w, hipGetLastError());
-        return GPRN_OK;
-    }));
-    prof_begin(w, GPRN_T_VEC);
-    hipLaunchKernelGGL(k_draw_combine_b, dim3((ns + 255) / 256, std::min(nd, 65535), ne), dim3(256), 0, st, (const double* const*)d.lz,
-                       (const double*)d.mean, in.q, p, ns, ns_pad, nd, cw.lat, cw.out);
-    prof_end(w);
-    HIP_TRY(w, hipGetLastError());
-    // ---- (6) the rows back through the pinned buffer; NaN where the sweeps or the last rung failed
-    const size_t lat_e = (size_t)G * nd * ns, out_e = (size_t)p * nd * ns;
-    if (out.lat) TRY(draw_through_pin(w, in, cw.lat, out.lat + e0 * lat_e, nullptr, ne * lat_e));
-    if (out.out) TRY(draw_through_pin(w, in, cw.out, out.out + e0 * out_e, nullptr, ne * out_e));
-    for (int e = 0; e < ne; ++e) {
-        const int b = e0 + e;
-        int failed = 0, failed_gp = -1;
-        for (int g = 0; g < G && !failed; ++g)
-            if (fail[(size_t)e * G + g] > 0) { failed = fail[(size_t)e * G + g]; failed_gp = g; }
-        out.info[b] = failed;
-        if (failed && out.info_gp && *out.info_gp < 0) *out.info_gp = failed_gp;
-        const bool lost = in.info[b] > 0;
-        for (int g = 0; g < G; ++g) out.nugget[(size_t)b * G + g] = lost ? NAN : nu[(size_t)e * G + g];
-        if (!failed && !lost) continue;
-        if (out.lat) std::fill(out.lat + b * lat_e, out.lat + (b + 1) * lat_e, NAN);
-        if (out.out) std::fill(out.out + b * out_e, out.out + (b + 1) * out_e, NAN);
-    }
-    return GPRN_OK;
-}
-
-int batch_draw_pass(gprn_ctx* w, const DrawPassIn& in, const BatchDraws& out, size_t budget)
-{
-    auto bytes = [&](int ne) {
-        return layout_count<char>(draw_scratch, draw_shape((size_t)ne, (size_t)in.G, (size_t)in.p, (size_t)in.ld, (size_t)out.ns,
-                                                           (size_t)out.nd, GPRN_NBUF));
-    };
-    // (a launch's grid y or z is the number of slots or evaluations of the group: far below its 65 535 limit)
-    int group = (int)std::max<size_t>(1, std::min<size_t>({budget / bytes(1), (size_t)32768 / in.G, (size_t)in.n}));
-    while (group > 1 && bytes(group) > budget) --group;
-    for (int e0 = 0; e0 < in.n;) {
-        const int ne = std::min(group, in.n - e0);
-        const int rc = draw_group(w, in, out, e0, ne);
-        if (rc == GPRN_E_NOMEM && ne > 1) { group = (ne + 1) / 2; w->err.clear(); continue; }   // (nothing of the group has run)
-        if (rc == GPRN_E_NOMEM)
-            w->err = "elbocalc_batch_draws: out of device memory for the draw pass of one evaluation: " + std::to_string(in.G) +
-                     " covariance matrices of " + std::to_string(out.ns) + " x " + std::to_string(out.ns) + ", their factors and " +
-                     std::to_string(out.nd) + " draws (" + w->err + ")";
-        if (rc) return rc;
-        e0 += ne;
-    }
-    return GPRN_OK;
+    // (a dependency wait of the draw pass that gave up: mid_run runs the whole chunk again)
+    return batch_tail(c, io, mid_left(c, m, io, keep_s, keep_ct), m->kept, false, rep);
 }
 
 // the worker follows the parent's switches

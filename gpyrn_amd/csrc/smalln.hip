@@ -14,6 +14,13 @@
 // Every reduction follows the order of the kernels it replaces (vecops.hip: k_lower_matvec, k_colops_partial / _reduce,
 // k_reduce_finalize, k_dot_self, k_q1_rows / k_sum_to, k_loglike_partial / k_elbo_final), so the two paths agree to
 // rounding of the compiler's contraction choices (tests/test_parity_gpu.py::test_small_path_matches_launch_schedule).
+//
+// The file holds, in this order: the three kernels and their `_b` forms (grid y = evaluation); their launchers for one
+// evaluation (small_phase, small_tail, small_prior: gprn_elbocalc's one-tile loop in api_sweep.hip calls them); and the
+// one-tile DRIVER of the side-by-side batches gprn_elbocalc_batch* -- SmallBatchMem (its buffers, one owner, batch_layout.h's
+// SmallSlab), small_batch_reserve, small_batch_sweep and small_batch_run: staging, set-up, the loop of SB_K sweeps per
+// synchronisation, then small_left (what the loop left: gprn_internal.h ChunkLeft) and batch_tail.hip's tail, which is where
+// the states come back and the gradient, mean, prediction and draw passes run.
 #include "api_internal.h"
 #include "tile_mma.h"
 #include "diag_tile.h"
@@ -593,18 +600,15 @@ struct SmallBatchMem {
     double* mask_wc = nullptr;        // [cap][ne node + ne weight][2][128 * ld]
     MaskLane* mask_lanes = nullptr;   // [2 parity][cap ne node | cap ne weight], evaluation-major
     double** mask_tab = nullptr;      // [cap ne node | cap ne weight][GPRN_NBUF]
-    // a prediction behind the loop (gprn_elbocalc_batch_predict), there from the first call that asks for one: the pass's
-    // pointer rows (X; a block of K* S in the B workspace, of its W^T in K), where its fill writes, and its vectors
-    double** pred_tab = nullptr;      // [cap G][GPRN_NBUF]
-    double** pred_kptr = nullptr;     // [cap G]
-    double* pred_vecs = nullptr;      // [7][cap G ld]: s, ct (gathered from vecs), k**, latent means and variances, outputs (twice cap p ld)
-    double *pred_jit = nullptr, *pred_ts = nullptr;   // [cap p] jitters, [pred_ns] prediction times (it only grows)
-    TileTask* pred_tasks = nullptr;   // pred_pass_tasks(1)
-    int pred_ns = 0;
-    double* pred_pin = nullptr;       // pinned: a block's rows on their way to the caller, 2 cap (G + p) ld doubles
-    // draws behind the loop (gprn_elbocalc_batch_draws), likewise: s and ct gathered per slot, the pass's pinned buffer
-    double* draw_vecs = nullptr;      // [2][cap G ld]
-    double* draw_pin = nullptr;       // GPRN_DRAW_PIN_DOUBLES
+    // what the tail behind a chunk's loop reads (batch_tail.hip; small_left): its kept buffers, the host image of the sweeps'
+    // rows [cap G][GPRN_NBUF] and of K_j^-1 [cap][q - 1], each evaluation's final state copy, s and ct gathered to slot order
+    // (from the first call that asks for a gradient, a prediction or draws) and the prediction pass's rows per block (from the
+    // first call that asks for a prediction: k**, latent means and variances, outputs -- the last two [cap p ld] of their plane)
+    TailKept kept;
+    std::vector<double*> rows, kinv;
+    std::vector<int> final_copy;
+    double* left_vecs = nullptr;      // [2][cap G ld]
+    double* block_rows = nullptr;     // [5][cap G ld]
     char* pin_in = nullptr;           // pinned: batch_pin_in
     SmallPinOut out{};                // pinned: what a group of sweeps sends back, the four state copies
     double us_reserve = 0.0;          // GPRN_BATCH_TIMERS: what making room took, reported with the next chunk
@@ -708,6 +712,11 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
             h_Kptr[g] = kd[(size_t)b * G + g] = v.K(b, g);
         }
         for (int j = 0; j < q; ++j) h_kinv_tab[j] = (j >= 1 && !bound) ? v.Kinv(b, j) : nullptr;
+        for (int g = 0; g < G; ++g) {
+            m->rows.resize(m->rows.size() + GPRN_NBUF);
+            buf_row(&m->rows[m->rows.size() - GPRN_NBUF], v.B(b, g), v.X(b, g), v.K(b, g), v.KLinv(b, g));
+        }
+        for (int j = 1; j < q && !bound; ++j) m->kinv.push_back(v.Kinv(b, j));
         double** const d_setup = db; double** const d_node = db + (size_t)G * GPRN_NBUF; double** const d_weight = db + 2 * (size_t)G * GPRN_NBUF;
         double** const d_kinv_tab = db + 3 * (size_t)G * GPRN_NBUF; double** const d_kinv_out = d_kinv_tab + q;
         double* const yres = v.yres(b); double* const variance = v.variance(b);
@@ -812,11 +821,41 @@ static int small_batch_sweep(gprn_ctx* c, SmallBatchMem* m, int B, int par, int 
     return GPRN_OK;
 }
 
+// What a chunk's loop left (gprn_internal.h ChunkLeft).  A stopped evaluation's launches were no-ops: X, s, ct and both copies of
+// its state are its last trip's, and that trip wrote copy B when odd (small_final_copy).  s and ct are two of the evaluation's
+// seven vectors (batch_layout.h) -- per (evaluation, latent GP) already, nothing was kept: two pitched copies bring them to
+// slot order, once for every pass of the call.  The prediction pass's rows per block are an allocation of this driver's.
+static int small_left(gprn_ctx* c, SmallBatchMem* m, const BatchIo& io, ChunkLeft* out)
+{
+    const SmallSlab& v = m->v;
+    const int G = c->G, B = io.n, cap = m->cap;
+    const size_t nv = (size_t)cap * G * c->ld;
+    const bool predict = io.pred.ns > 0, draws = io.draws.ns > 0;
+    m->final_copy.resize(B);
+    for (int b = 0; b < B; ++b) m->final_copy[b] = (int)v.state_index(small_final_copy(io.iters[b]), b);
+    const bool need_s = io.grad_out || predict || draws, need_ct = predict || draws;
+    if (need_s) {
+        if (!m->left_vecs) TRY(m->own.alloc(c, &m->left_vecs, 2 * nv));
+        const size_t rowb = (size_t)G * c->ld * sizeof(double), pitch = v.vec_pitch() * sizeof(double);
+        HIP_TRY(c, hipMemcpy2DAsync(m->left_vecs, rowb, v.vec(0, SV_S, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, c->stream));
+        if (need_ct)
+            HIP_TRY(c, hipMemcpy2DAsync(m->left_vecs + nv, rowb, v.vec(0, SV_CT, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (predict && !m->block_rows) TRY(m->own.alloc(c, &m->block_rows, 5 * nv));
+    m->kept.own = &m->own;
+    if (double* const br = m->block_rows) m->kept.rows = PredRows{br, br + nv, br + 2 * nv, br + 3 * nv, br + 4 * nv};
+    *out = ChunkLeft{B, cap, G, c->p, c->q, c->N, c->ld, 1, c, m->rows.data(), m->kinv.empty() ? nullptr : m->kinv.data(),
+                     need_s ? m->left_vecs : nullptr, need_ct ? m->left_vecs + nv : nullptr, v.states, v.states + (size_t)cap * v.d(), v.d(),
+                     m->final_copy.data(), 2, 2 * (size_t)cap, m->out.state, m->out.state + (size_t)cap * v.d(),
+                     v.yres(0), v.variance(0), m->programs, m->pin_in, io.info,
+                     io.grad_out || draws ? grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c)) : 0};
+    return GPRN_OK;
+}
+
 int small_batch_run(gprn_ctx* c, const BatchIo& io)
 {
     SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
     const int G = c->G, B = io.n, cap = m->cap, max_iter = io.max_iter;
-    const size_t d = io.state;
     double* const elbo = io.elbo; int* const iters = io.iters; int* const conv = io.conv; int* const info = io.info;
     LapTimer t;
     double us_stage = 0.0, us_enqueue = 0.0, us_wait = 0.0, us_host = 0.0;
@@ -842,7 +881,6 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     // same input; it runs once, as trip 1.  Only max_iter = 0 enqueues sweep 0.)
     int s = max_iter >= 1 ? 1 : 0;
     bool all_done = false;
-    const int q = c->q;
     if (m->mask && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
     while (!all_done && s <= max_iter) {
         const int s0 = s;
@@ -874,116 +912,18 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
         }
         us_host += t.lap();
     }
-    if (io.mu_out && io.var_out) {
-        for (int k = 0; k < 4; ++k)                            // (B evaluations of each copy, not the buffers' capacity)
-            HIP_TRY(c, hipMemcpyAsync(m->out.state + m->v.state_index(k, 0) * d, m->v.state(k, 0), (size_t)B * d * sizeof(double),
-                                      hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        for (int b = 0; b < B; ++b) {
-            const size_t k = small_final_copy(iters[b]);           // (the pinned image has the slab's layout)
-            memcpy(io.mu_out + (size_t)b * d, m->out.state + m->v.state_index(k, b) * d, d * sizeof(double));
-            memcpy(io.var_out + (size_t)b * d, m->out.state + m->v.state_index(k + 1, b) * d, d * sizeof(double));
-        }
+    // ---- what the loop left, and the tail over the B x G one-tile slots in the set-up's order (batch_tail.hip)
+    ChunkLeft left;
+    TRY(small_left(c, m, io, &left));
+    TailReport rep{t, std::string(), "prediction pass", us_ensure, std::string()};
+    if (batch_timers_on()) {
+        char head[400];
+        snprintf(head, sizeof head, "(one tile), %d evaluations, us: buffers %.0f | staging %.0f | enqueue %.0f | waiting for the device "
+                 "%.0f | verdicts %.0f", B, us_ensure, us_stage, us_enqueue, us_wait, us_host);
+        rep.head = head;
+        rep.suffix = " (" + std::to_string(s - (max_iter >= 1 ? 1 : 0)) + " launches of sweeps)";
     }
-    const double us_states = t.lap();
-    if (io.grad_out) {
-        // ---- the gradient of every evaluation's last committed sweep: grad.hip's batched pass over the B x G one-tile slots
-        // (T = 1).  A stopped evaluation's launches were no-ops: X, s and both copies of its state are its last trip's; that
-        // trip wrote copy B when odd.
-        const SmallSlab& v = m->v;
-        GradBatchIn in;
-        in.N = c->N; in.ld = c->ld; in.T = 1; in.q = q; in.G = G; in.t = c->d_time;
-        in.state = v.states; in.state_stride = d; in.grad_exact = c->grad_exact; in.bound = c->elbo_form == GPRN_ELBO_BOUND; in.p = c->p;
-        for (int b = 0; b < B; ++b) {
-            if (!grad_batch_enter(io, b, in)) continue;
-            for (int g = 0; g < G; ++g) {
-                in.rows.resize(in.rows.size() + GPRN_NBUF);
-                buf_row(&in.rows[in.rows.size() - GPRN_NBUF], v.B(b, g), v.X(b, g), v.K(b, g), v.KLinv(b, g));
-                in.s.push_back(v.vec(b, SV_S, g));
-            }
-            for (int j = 1; j < q && c->elbo_form == GPRN_ELBO_REFERENCE; ++j) in.kinv.push_back(v.Kinv(b, j));
-            in.state_idx.push_back((int)v.state_index(small_final_copy(iters[b]), b));
-        }
-        TRY(grad_batch_pass(c, c->kspec, in, grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c))));
-    }
-    if (io.means.grad_out) {
-        std::vector<int> idx(B);
-        for (int b = 0; b < B; ++b) idx[b] = (int)m->v.state_index(small_final_copy(iters[b]), b);
-        TRY(mean_grad_pass(c, c, io.means, B, info, m->v.yres(0), m->v.variance(0), m->v.states, d, idx));
-    }
-    const double us_grad = t.lap();
-    if (io.pred.ns > 0) {
-        // ---- the prediction of every evaluation's last committed sweep: midn.hip's pass over the B x G one-tile slots (T = 1),
-        // in the set-up's order.  s and ct are two of the evaluation's seven vectors (batch_layout.h) -- per (evaluation, latent
-        // GP) already, a stopped evaluation's are its last trip's: nothing was kept, two pitched copies bring them to the
-        // pass's layout.  Its two blocks per slot live in matrices the loop has finished with (B's workspace, the prior's K).
-        const SmallSlab& v = m->v;
-        const size_t gl = (size_t)G * c->ld, nv = (size_t)cap * gl;
-        if (!m->pred_tab) {
-            std::vector<double*> rows((size_t)cap * G * GPRN_NBUF), kp((size_t)cap * G);
-            for (int b = 0; b < cap; ++b)
-                for (int g = 0; g < G; ++g) {
-                    const size_t sl = (size_t)b * G + g;
-                    buf_row(&rows[sl * GPRN_NBUF], v.B(b, g), v.X(b, g), v.B(b, g), v.K(b, g));
-                    kp[sl] = v.B(b, g);
-                }
-            TRY(m->own.alloc(c, &m->pred_vecs, 7 * nv));
-            TRY(m->own.alloc(c, &m->pred_kptr, kp.size()));
-            TRY(m->own.alloc(c, &m->pred_tab, rows.size()));
-            HIP_TRY(c, hipMemcpy(m->pred_kptr, kp.data(), kp.size() * sizeof(double*), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(m->pred_tab, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice));
-            const std::vector<TileTask> tasks = pred_pass_tasks(1, c->ld);
-            TRY(m->own.alloc(c, &m->pred_tasks, tasks.size()));
-            HIP_TRY(c, hipMemcpy(m->pred_tasks, tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice));
-            TRY(m->own.alloc(c, &m->pred_jit, (size_t)cap * c->p));
-            TRY(m->own.pin(c, &m->pred_pin, 2 * (size_t)cap * (G + c->p) * c->ld * sizeof(double)));
-        }
-        if (io.pred.ns > m->pred_ns) {                  // (a longer t* than any before: a new array; the old one goes with the buffers)
-            TRY(m->own.alloc(c, &m->pred_ts, (size_t)io.pred.ns));
-            m->pred_ns = io.pred.ns;
-        }
-        double* const pv = m->pred_vecs;
-        const size_t rowb = gl * sizeof(double), pitch = v.vec_pitch() * sizeof(double);
-        HIP_TRY(c, hipMemcpy2DAsync(pv, rowb, v.vec(0, SV_S, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpy2DAsync(pv + nv, rowb, v.vec(0, SV_CT, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
-        // (a launch's grid z / y is the number of slots: groups of evaluations that stay below its limit)
-        const int group = std::max(1, 32768 / G);
-        for (int e0 = 0; e0 < B; e0 += group) {
-            const int nb = std::min(group, B - e0);
-            const size_t s0 = (size_t)e0 * G, o0 = (size_t)e0 * c->p * c->ld;
-            const PredPassIn in{nb, G, c->p, c->N, c->ld, 1, m->pred_tab + s0 * GPRN_NBUF, m->pred_kptr + s0,
-                                m->programs + s0 * fill_program_bytes(), m->pin_in + s0 * fill_program_bytes(),
-                                pv + s0 * c->ld, pv + nv + s0 * c->ld, pv + 2 * nv + s0 * c->ld, pv + 3 * nv + s0 * c->ld,
-                                pv + 4 * nv + s0 * c->ld, pv + 5 * nv + o0, pv + 6 * nv + o0, io.jitters + (size_t)e0 * c->p, info + e0,
-                                m->pred_ts, m->pred_jit, m->pred_tasks, m->pred_pin};
-            TRY(batch_pred_pass(c, in, io.pred.from(e0)));
-        }
-    }
-    if (io.draws.ns > 0) {
-        // ---- joint draws from the posterior every evaluation's last committed sweep left: midn.hip's draw pass over the B x G
-        // one-tile slots, in the set-up's order, from the same s, ct and X as the prediction above; its block of K* S in B's
-        // workspace.  The pass's ladder factors on THIS context at the prediction's geometry (its task lists are rebuilt, and
-        // again by the next factorisation at T = 1); a wait of it that gave up re-runs the pass alone, which only reads the slabs.
-        const SmallSlab& v = m->v;
-        const size_t gl = (size_t)G * c->ld, nv = (size_t)cap * gl;
-        if (!m->draw_vecs) {
-            TRY(m->own.alloc(c, &m->draw_vecs, 2 * nv));
-            TRY(m->own.pin(c, &m->draw_pin, GPRN_DRAW_PIN_DOUBLES * sizeof(double)));
-        }
-        const size_t rowb = gl * sizeof(double), pitch = v.vec_pitch() * sizeof(double);
-        HIP_TRY(c, hipMemcpy2DAsync(m->draw_vecs, rowb, v.vec(0, SV_S, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpy2DAsync(m->draw_vecs + nv, rowb, v.vec(0, SV_CT, 0), pitch, rowb, B, hipMemcpyDeviceToDevice, st));
-        DrawPassIn in{B, G, c->p, q, c->N, c->ld, 1, {}, {}, m->programs, m->pin_in, m->draw_vecs, m->draw_vecs + nv, info,
-                      m->draw_pin, GPRN_DRAW_PIN_DOUBLES};
-        for (int b = 0; b < B; ++b)
-            for (int g = 0; g < G; ++g) { in.X.push_back(v.X(b, g)); in.blk.push_back(v.B(b, g)); }
-        const size_t left = grad_batch_left(c, (size_t)cap * small_bytes_per_eval(c));
-        TRY(with_event_fallback(c, "elbocalc_batch_draws", [&](bool) { return batch_draw_pass(c, in, io.draws, left); }));
-    }
-    const double us_pred = t.lap();
-    if (batch_timers_on())
-        fprintf(stderr, "[gprn] elbocalc_batch (one tile), %d evaluations, us: buffers %.0f | staging %.0f | enqueue %.0f | waiting for the device "
-                        "%.0f | verdicts %.0f | states back %.0f | gradient pass %.0f | prediction pass %.0f | total %.0f (%d launches of sweeps)\n", B, us_ensure, us_stage,
-                us_enqueue, us_wait, us_host, us_states, us_grad, us_pred, us_ensure + t.total(), s - (max_iter >= 1 ? 1 : 0));
-    return GPRN_OK;
+    // (the draw pass's ladder factors on THIS context at the prediction's geometry; a wait of it that gave up re-runs the pass
+    // alone, which only reads the slabs)
+    return batch_tail(c, io, left, m->kept, true, rep);
 }

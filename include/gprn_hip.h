@@ -476,7 +476,7 @@ int gprn_elbocalc_batch_grad(gprn_ctx* ctx, int n_eval, const double* kernel_par
  * At least one pair must be given.  flags: as gprn_elbocalc_batch_grad (GPRN_BATCH_FORCED).
  * elbo, iterations, converged, info and the states are bit-identical to gprn_elbocalc_batch_grad(..., grad_out = NULL) with
  * the same inputs and flags: the prediction pass runs per chunk behind the chunk's loop and only reads what the loop left
- * (csrc/midn.hip batch_pred_pass: t* in blocks of at most ld rows; per block the batched posterior fill, one tile product, one
+ * (csrc/batch_tail.hip batch_pred_pass: t* in blocks of at most ld rows; per block the batched posterior fill, one tile product, one
  * row kernel, the combination, the rows back through a pinned buffer), in buffers the loop has finished with.  An evaluation
  * with info > 0 gets NaN in all of its prediction rows; the others are untouched.
  * GPRN_E_ARG: max_iter < 1 (no committed sweep), ns < 1, unknown flag bits, a pair half given, no pair.  Refusals
@@ -511,7 +511,7 @@ int gprn_elbocalc_batch_predict(gprn_ctx* ctx, int n_eval, const double* kernel_
  *       and NaN nuggets too.  The other evaluations are untouched in both cases.
  * flags: as gprn_elbocalc_batch_grad (GPRN_BATCH_FORCED).  elbo, iterations, converged, info and the states are bit-identical to
  * gprn_elbocalc_batch_grad(..., grad_out = NULL) with the same inputs and flags: the draw pass runs per chunk behind the
- * chunk's loop and only reads what the loop left (csrc/midn.hip batch_draw_pass: W^T of all rows of t* by the prediction
+ * chunk's loop and only reads what the loop left (csrc/batch_tail.hip batch_draw_pass: W^T of all rows of t* by the prediction
  * pass's launches, K** of every slot in one launch, the lower tiles of C, the ladder in one phase of the prediction's
  * geometry per rung, L Z, the combination; the rows travel through a pinned buffer).  Its scratch is an allocation of its
  * own, ns_pad ld + 3 ns_pad^2 + 2 nd_pad ns_pad doubles per slot (ns_pad, nd_pad: ns, n_draws rounded up to 128), which takes
