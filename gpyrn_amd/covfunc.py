@@ -36,6 +36,7 @@ __all__ = [
     'Matern52', 'Linear', 'GammaExp', 'Polynomial', 'Piecewise', 'Paciorek',
     'NewPeriodic', 'QuasiNewPeriodic', 'NewRQP', 'HarmonicPeriodic',
     'QuasiHarmonicPeriodic', 'CosPeriodic', 'QuasiCosPeriodic',
+    'SHO', 'Rotation', 'CeleriteTerm',
 ]
 
 # Kernel ids understood by csrc/fill.hip -- keep in step with include/gprn_hip.h.
@@ -45,6 +46,7 @@ KID = dict(
     PACIOREK=13, NEWPERIODIC=14, QUASINEWPERIODIC=15, COSPERIODIC=16,
     QUASICOSPERIODIC=17, POLYNOMIAL=18, HARMONICPERIODIC=19,
     QUASIHARMONICPERIODIC=20, DSE=21, DPERIODIC=22, DQP=23,
+    SHO=24, ROTATION=25, CELERITE=26,
 )
 OP_PUSH, OP_ADD, OP_MUL = 0, 1, 2
 # kernels that _KMatrix calls as kernel(t_i, t_j) and leaves without nugget
@@ -669,3 +671,144 @@ class QuasiCosPeriodic(covFunction):
 
     def _device_pars(self):
         return [self.amplitude, self.ell_e, self.P, self.ell_p]
+
+
+# ------------------------------------------------------------------ the celerite family (not in the reference)
+_D_SERIES = [(-1.0)**n * 2 * n / float(np.prod(np.arange(1.0, 2 * n + 2))) for n in range(1, 11)]
+
+
+def _sho_D(a, x, eC, eS):
+    """e^-a D(x), D = (C - S) / x: its series (-1)^n 2n / (2n + 1)! x^(n-1) for |x| < 1, where the difference cancels"""
+    D = np.zeros_like(a)
+    for c in _D_SERIES[::-1]:
+        D = D * x + c
+    return np.where(np.abs(x) < 1, np.exp(-a) * D, (eC - eS) / np.where(x == 0, 1.0, x))
+
+
+def _sho_under(a, s, sn, cs):
+    """``e^-a`` times C(x), S(x) and D(x) = (C - S) / x at x = s^2 >= 0, C = cos s and S = sin s / s from the sine and
+    cosine of the phase; S(0) = 1, D(0) = -1/3 (csrc/dk_eval.h, dk_sho_under)."""
+    e = np.exp(-a)
+    eC = e * cs
+    eS = e * np.where(s == 0, 1.0, sn / np.where(s == 0, 1.0, s))
+    return eC, eS, _sho_D(a, s * s, eC, eS)
+
+
+def _sho_over(a, w, Q):
+    """the same below the critical point, w = (2Q - 1)(2Q + 1) < 0: C = cosh, S = sinh / of y = sqrt(-w) a, the exponents
+    combined before e^-a cosh(y) becomes 0 x inf -- e^-a(1-h) (1 + E) / 2 and e^-a(1-h) (1 - E) / (2 y), E = e^-2y,
+    a (1 - h) = a 4 Q^2 / (1 + h).  A NaN parameter comes here and stays NaN."""
+    h = np.sqrt(-w)
+    y = h * a
+    E = np.exp(-2 * y)
+    e = np.exp(-(a * (4 * (Q * Q) / (1 + h))))
+    eC = e * (0.5 * (1 + E))
+    eS = e * np.where(y == 0, 1.0, -np.expm1(-2 * y) / np.where(y == 0, 1.0, 2 * y))
+    return eC, eS, _sho_D(a, w * a * a, eC, eS)
+
+
+class SHO(covFunction):
+    r"""Stochastically driven damped harmonic oscillator (celerite's SHOTerm with omega_0 = 2 pi / P0 and
+    S_0 omega_0 Q = theta^2):  K_ij = theta^2 e^-a [C(x) + a S(x)],  a = pi |r| / (P0 Q),  x = (2Q - 1)(2Q + 1) a^2,
+    C = cos sqrt(x) and S = sin sqrt(x) / sqrt(x) (cosh, sinh of sqrt(-x) for Q < 1/2).  At Q = 1/2 it is
+    ``Matern32(theta, sqrt(3) P0 / (2 pi))``."""
+    _param_names = 'theta', 'P0', 'Q'
+    _tag = 'SHO'
+    _device_id = KID['SHO']
+
+    def __init__(self, theta: float, P0: float, Q: float):
+        super().__init__(theta, P0, Q)
+
+    def __call__(self, r):
+        theta, P0, Q = self.pars
+        w = (2 * Q - 1) * (2 * Q + 1)
+        with np.errstate(all='ignore'):
+            a = np.pi * np.abs(r) / (P0 * Q)
+            if w >= 0:
+                s = np.sqrt(w) * a
+                eC, eS, _ = _sho_under(a, s, np.sin(s), np.cos(s))
+            else:
+                eC, eS, _ = _sho_over(a, w, Q)
+            return theta**2 * (eC + a * eS)
+
+    def _dk_dpars(self, r):
+        theta, P0, Q = self.pars
+        w = (2 * Q - 1) * (2 * Q + 1)
+        with np.errstate(all='ignore'):
+            b = np.pi * np.abs(r) / P0
+            a = b / Q
+            if w >= 0:
+                s = np.sqrt(w) * a
+                eC, eS, eD = _sho_under(a, s, np.sin(s), np.cos(s))
+            else:
+                eC, eS, eD = _sho_over(a, w, Q)
+            return [2 * theta * (eC + a * eS), theta**2 * 4 * b**2 * eS / P0, theta**2 * 4 * Q * a**3 * eD]
+
+
+class Rotation(covFunction):
+    r"""celerite2's RotationTerm: two oscillators, at the period P with Q = 1/2 + Q0 + dQ and at P / 2 with Q = 1/2 + Q0,
+    in the amplitude ratio 1 : f.  With g1 = 2 sqrt((Q0 + dQ)(Q0 + dQ + 1)), g2 = 2 sqrt(Q0 (Q0 + 1)):
+    K_ij = theta^2 / (1 + f) {T(2 pi |r| / P, g1) + f T(4 pi |r| / P, g2)},  T(phi, g) = e^(-phi / g) [cos phi + sin phi / g].
+    Domain: Q0 > 0, dQ >= 0, f >= 0."""
+    _param_names = 'theta', 'P', 'Q0', 'dQ', 'f'
+    _tag = 'ROT'
+    _device_id = KID['ROTATION']
+
+    def __init__(self, theta: float, P: float, Q0: float, dQ: float, f: float):
+        super().__init__(theta, P, Q0, dQ, f)
+
+    def __call__(self, r):
+        theta, P, Q0, dQ, f = self.pars
+        Q1 = Q0 + dQ
+        with np.errstate(all='ignore'):
+            g1, g2 = 2 * np.sqrt(Q1 * (Q1 + 1)), 2 * np.sqrt(Q0 * (Q0 + 1))
+            p1, p2 = 2 * np.pi * np.abs(r) / P, 4 * np.pi * np.abs(r) / P
+            k1 = np.exp(-(p1 / g1)) * (np.cos(p1) + np.sin(p1) / g1)
+            k2 = np.exp(-(p2 / g2)) * (np.cos(p2) + np.sin(p2) / g2)
+            return theta**2 / (1 + f) * (k1 + f * k2)
+
+    def _dk_dpars(self, r):
+        theta, P, Q0, dQ, f = self.pars
+        Q1 = Q0 + dQ
+        with np.errstate(all='ignore'):
+            w1, w2 = 4 * Q1 * (Q1 + 1), 4 * Q0 * (Q0 + 1)
+            g1, g2 = np.sqrt(w1), np.sqrt(w2)
+            p1 = 2 * np.pi * np.abs(r) / P
+            p2 = 2 * p1
+            a1, a2 = p1 / g1, p2 / g2
+            C1, S1, D1 = _sho_under(a1, p1, np.sin(p1), np.cos(p1))
+            C2, S2, D2 = _sho_under(a2, p2, np.sin(p2), np.cos(p2))
+            T1, T2 = C1 + a1 * S1, C2 + a2 * S2
+            # dT / dQ of each oscillator: phi (x e^-a D + a e^-a S) / w, times dg / dQ = 2 (2Q + 1) / g
+            T1g = p1 * (p1**2 * D1 + a1 * S1) / w1 * (2 * (2 * Q1 + 1) / g1)
+            T2g = p2 * (p2**2 * D2 + a2 * S2) / w2 * (2 * (2 * Q0 + 1) / g2)
+            A = theta**2 / (1 + f)
+            return [2 * theta / (1 + f) * (T1 + f * T2),
+                    A * (p1**2 * S1 * (1 + 1 / w1) + f * (p2**2 * S2 * (1 + 1 / w2))) / P,
+                    A * (T1g + f * T2g), A * T1g, theta**2 * (T2 - T1) / (1 + f)**2]
+
+
+class CeleriteTerm(covFunction):
+    r"""The general celerite term  K_ij = e^(-c |r|) [a cos(d |r|) + b sin(d |r|)].  Whether it is positive definite
+    is the caller's business (b = d = 0: ``Exponential(sqrt(a), 1 / c)``)."""
+    _param_names = 'a', 'b', 'c', 'd'
+    _tag = 'CEL'
+    _device_id = KID['CELERITE']
+
+    def __init__(self, a: float, b: float, c: float, d: float):
+        super().__init__(a, b, c, d)
+
+    def __call__(self, r):
+        a, b, c, d = self.pars
+        tau = np.abs(r)
+        with np.errstate(all='ignore'):
+            return np.exp(-(c * tau)) * (a * np.cos(d * tau) + b * np.sin(d * tau))
+
+    def _dk_dpars(self, r):
+        a, b, c, d = self.pars
+        tau = np.abs(r)
+        with np.errstate(all='ignore'):
+            e = np.exp(-(c * tau))
+            sn, cs = np.sin(d * tau), np.cos(d * tau)
+            k = e * (a * cs + b * sn)
+            return [e * cs, e * sn, -tau * k, tau * e * (b * cs - a * sn)]

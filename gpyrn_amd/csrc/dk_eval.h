@@ -17,8 +17,12 @@
 
 #include "../../include/gprn_hip.h"
 
+// DK_NI: a function every caller CALLS (the celerite kernels: see dk_celerite); on the host whatever DK_HD is
 #ifndef DK_HD
 #define DK_HD __host__ __device__ __forceinline__
+#define DK_NI static __host__ __device__ __noinline__
+#else
+#define DK_NI DK_HD
 #endif
 
 #define DK_MAX_LEAF_PARAMS 5
@@ -31,9 +35,10 @@ DK_HD int dk_nparams(int kid)
     case GPRN_K_CONSTANT: case GPRN_K_WHITENOISE: case GPRN_K_PIECEWISE: return 1;
     case GPRN_K_SE: case GPRN_K_COSINE: case GPRN_K_EXPONENTIAL: case GPRN_K_MATERN32: case GPRN_K_MATERN52: case GPRN_K_DSE: return 2;
     case GPRN_K_PERIODIC: case GPRN_K_RQ: case GPRN_K_GAMMAEXP: case GPRN_K_PACIOREK: case GPRN_K_COSPERIODIC:
-    case GPRN_K_POLYNOMIAL: case GPRN_K_DPERIODIC: return 3;
+    case GPRN_K_POLYNOMIAL: case GPRN_K_DPERIODIC: case GPRN_K_SHO: return 3;
+    case GPRN_K_CELERITE:
     case GPRN_K_QP: case GPRN_K_NEWPERIODIC: case GPRN_K_QUASICOSPERIODIC: case GPRN_K_HARMONICPERIODIC: case GPRN_K_DQP: return 4;
-    case GPRN_K_RQP: case GPRN_K_QUASINEWPERIODIC: case GPRN_K_QUASIHARMONICPERIODIC: return 5;
+    case GPRN_K_RQP: case GPRN_K_QUASINEWPERIODIC: case GPRN_K_QUASIHARMONICPERIODIC: case GPRN_K_ROTATION: return 5;
     default: return 0;
     }
 }
@@ -68,6 +73,116 @@ DK_HD DkHarmonic dk_harmonic(double Nh, double P, double t)
     h.half = DK_PI * t / P;
     h.phase = (Nh + 0.5) * h.w;
     return h;
+}
+
+// The oscillator's shape (fill_eval.h, sho_shape) in the pieces its derivatives are products of: e^-a times C(x), S(x) and
+// D(x) = (C - S) / x at x = w a^2, w = (2Q - 1)(2Q + 1) -- C = cos sqrt(x), S = sin sqrt(x) / sqrt(x), cosh and sinh below 0;
+// C' = -S / 2 and S' = D / 2.  D is entire (-1/3 + x/30 - ...: coefficients (-1)^n 2n / (2n + 1)!) and takes that series for
+// |x| < 1, where C - S cancels; beyond, the difference keeps a quarter of its digits at worst.  Over-damped, the exponents are
+// combined before anything overflows: e^-a cosh(y) = e^-a(1-h) (1 + E) / 2, e^-a sinh(y) / y = e^-a(1-h) (1 - E) / (2 y),
+// y = h a, E = e^-2y, a (1 - h) = a 4 Q^2 / (1 + h).  With F = e^-a (C + a S), b = a Q:
+//   a dF/da + 2 x dF/dx = -4 b^2 e^-a S,     Q dF/dQ = 4 b^2 a e^-a D      (one product each: nothing cancels)
+struct DkSho { double eC, eS, eD; };
+
+// e^-a D(x) beside e^-a C and e^-a S
+DK_HD double dk_sho_D(double a, double x, double eC, double eS)
+{
+    if (fabs(x) < 1.0) {
+        double D = 1.0 / 2554547108585472000.0;
+        D = fma(D, x, -1.0 / 6758061133824000.0);
+        D = fma(D, x, 1.0 / 22230464256000.0);
+        D = fma(D, x, -1.0 / 93405312000.0);
+        D = fma(D, x, 1.0 / 518918400.0);
+        D = fma(D, x, -1.0 / 3991680.0);
+        D = fma(D, x, 1.0 / 45360.0);
+        D = fma(D, x, -1.0 / 840.0);
+        D = fma(D, x, 1.0 / 30.0);
+        D = fma(D, x, -1.0 / 3.0);
+        return exp(-a) * D;
+    }
+    return (eC - eS) / x;                       // (a NaN x comes here)
+}
+
+// under-damped or critical (x = s^2 >= 0), from the sine and cosine of the phase s
+DK_HD DkSho dk_sho_under(double a, double s, double sn, double cs)
+{
+    DkSho p;
+    const double e = exp(-a);
+    p.eC = e * cs;
+    p.eS = e * (s == 0.0 ? 1.0 : sn / s);
+    p.eD = dk_sho_D(a, s * s, p.eC, p.eS);
+    return p;
+}
+
+// over-damped (w < 0; a NaN w comes here too), x = w a^2
+DK_HD DkSho dk_sho_over(double a, double w, double Q)
+{
+    DkSho p;
+    const double h = sqrt(-w), y = h * a, E = exp(-2 * y), e = exp(-(a * (4 * (Q * Q) / (1 + h))));
+    p.eC = e * (0.5 * (1 + E));
+    p.eS = e * (y == 0.0 ? 1.0 : -expm1(-2 * y) / (2 * y));
+    p.eD = dk_sho_D(a, w * a * a, p.eC, p.eS);
+    return p;
+}
+
+// The celerite kernels (not in the reference) behind ONE call that is not inlined: inlined into dk_kernel they took the
+// generic consumers (k_grad_exact_rows, k_fill_grad, k_grad_contract_b<2>) across an occupancy step for every program of the
+// kernels that were there before (profiles/celerite_isa_resources.txt).  (k, dk/dq[0 .. 4]) by value; a = |r|.
+struct DkCelerite { double k, d0, d1, d2, d3, d4; };
+DK_NI DkCelerite dk_celerite(int kid, double q0, double q1, double q2, double q3, double q4, double a)
+{
+    DkCelerite c;
+    c.d0 = c.d1 = c.d2 = c.d3 = c.d4 = 0.0;
+    if (kid == GPRN_K_SHO) {                // theta, P0, Q:  theta^2 F, F = e^-al (C + al S), al = pi |r| / (P0 Q)
+        const double Q = q2, b = DK_PI * a / q1, al = b / Q, w = (2 * Q - 1) * (2 * Q + 1);
+        DkSho p;
+        if (w >= 0.0) {
+            const double s = sqrt(w) * al;
+            double sn, cs;
+            sincos(s, &sn, &cs);
+            p = dk_sho_under(al, s, sn, cs);
+        } else {
+            p = dk_sho_over(al, w, Q);
+        }
+        const double F = p.eC + al * p.eS;
+        c.d0 = 2 * q0 * F;
+        c.d1 = q0 * q0 * 4 * (b * b) * p.eS / q1;
+        c.d2 = q0 * q0 * 4 * Q * (al * al * al) * p.eD;
+        c.k = q0 * q0 * F;
+        return c;
+    }
+    if (kid == GPRN_K_ROTATION) {           // theta, P, Q0, dQ, f:  theta^2 / (1 + f) (T_1 + f T_2), T = e^-(phi/g) (cos phi + sin phi / g)
+        // an oscillator with w = g^2 at al = phi / g:  dT/dphi = -phi e^-al S (1 + 1/w),  dT/dg = phi (x e^-al D + al e^-al S) / w
+        const double Q1 = q2 + q3, f = q4, A = q0 * q0 / (1 + f);
+        const double w1 = 4 * Q1 * (Q1 + 1), w2 = 4 * q2 * (q2 + 1), g1 = sqrt(w1), g2 = sqrt(w2);
+        const double p1 = 2 * DK_PI * a / q1, p2 = 2 * p1;
+        double sn1, cs1, sn2, cs2;
+        sincos(p1, &sn1, &cs1);
+        sincos(p2, &sn2, &cs2);
+        const DkSho s1 = dk_sho_under(p1 / g1, p1, sn1, cs1), s2 = dk_sho_under(p2 / g2, p2, sn2, cs2);
+        const double T1 = s1.eC + p1 / g1 * s1.eS, T2 = s2.eC + p2 / g2 * s2.eS;
+        const double T1g = p1 * ((p1 * p1) * s1.eD + p1 / g1 * s1.eS) / w1 * (2 * (2 * Q1 + 1) / g1);    // dT_1 / dQ_1
+        const double T2g = p2 * ((p2 * p2) * s2.eD + p2 / g2 * s2.eS) / w2 * (2 * (2 * q2 + 1) / g2);
+        c.d0 = 2 * q0 / (1 + f) * (T1 + f * T2);
+        c.d1 = A * ((p1 * p1) * s1.eS * (1 + 1 / w1) + f * ((p2 * p2) * s2.eS * (1 + 1 / w2))) / q1;
+        c.d2 = A * (T1g + f * T2g);
+        c.d3 = A * T1g;
+        c.d4 = q0 * q0 * (T2 - T1) / ((1 + f) * (1 + f));
+        c.k = A * (T1 + f * T2);
+        return c;
+    }
+    {                                       // CeleriteTerm a, b, c, d:  e^-c|r| (a cos d|r| + b sin d|r|)
+        double sn, cs;
+        sincos(q3 * a, &sn, &cs);
+        const double e = exp(-(q2 * a));
+        const double k = e * (q0 * cs + q1 * sn);
+        c.d0 = e * cs;
+        c.d1 = e * sn;
+        c.d2 = -a * k;
+        c.d3 = a * e * (q1 * cs - q0 * sn);
+        c.k = k;
+        return c;
+    }
 }
 
 // k(t_i, t_j) of built-in `kid` with the parameters q; d0 .. d4 <- dk/dq[0 .. 4] (those past the kernel's own count: 0)
@@ -287,6 +402,12 @@ DK_HD double dk_kernel(int kid, const double* __restrict__ q, double ti, double 
         d2 = th * th * se * (p_P + poly * (-2 / P + 2 * x * S / (P * lp2)));
         d3 = th * th * se * (p_lp + poly * (-4 / lp + 4 * (sx * sx) / (lp2 * lp)));
         return th * th * se * poly;
+    }
+    case GPRN_K_SHO: case GPRN_K_ROTATION: case GPRN_K_CELERITE: {
+        // (by value, each kernel its own count: SHO has three parameters, CeleriteTerm four)
+        const DkCelerite c = dk_celerite(kid, q[0], q[1], q[2], kid == GPRN_K_SHO ? 0.0 : q[3], kid == GPRN_K_ROTATION ? q[4] : 0.0, a);
+        d0 = c.d0; d1 = c.d1; d2 = c.d2; d3 = c.d3; d4 = c.d4;
+        return c.k;
     }
     default: return 0.0;
     }

@@ -128,8 +128,8 @@ static bool program_is_even(const FillProgram& pg)
 // host-side choice of the instantiation: the id of a one-kernel program, else the generic one
 #define GPRN_FOR_EACH_KID(X) \
     X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) \
-    X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23)
-static_assert(GPRN_K_COUNT == 24, "add the new kernel id to GPRN_FOR_EACH_KID");
+    X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26)
+static_assert(GPRN_K_COUNT == 27, "add the new kernel id to GPRN_FOR_EACH_KID");
 
 static int program_kid(const FillProgram& pg)
 {

@@ -109,6 +109,56 @@ __device__ __forceinline__ void harmonic_terms(double Nh, double P, double t, do
     u = 0.5 / tan(half) - cos(phase) / 2 * sin(half);
 }
 
+// The oscillator's shape e^-a [C(x) + a S(x)], x = w a^2, w = (2Q - 1)(2Q + 1) (not in the reference): C = cos sqrt(x),
+// S = sin sqrt(x) / sqrt(x) for x >= 0, cosh and sinh of sqrt(-x) below.  Both are entire in x and the critical point w = 0
+// is no special case: sqrt(|w|) a is small there and S(0) = 1.  Over-damped, e^-a cosh(h a) is 0 x inf in the far tail, so
+// the exponents are combined first -- with y = h a, E = e^-2y:
+//   e^-a(1-h) [(1 + E) / 2 + a (1 - E) / (2 y)],   a (1 - h) = a 4 Q^2 / (1 + h)   (1 - h itself cancels for small Q)
+// E - 1 and (1 - E) / (2 y) from ONE expm1, which does not cancel near y = 0.  A NaN parameter fails `w >= 0` and leaves the second
+// branch as NaN; a deep tail is 0 times a finite bracket.
+__device__ __forceinline__ double sho_shape(double a, double w, double Q)
+{
+#pragma clang fp contract(off)
+    if (w >= 0.0) {
+        const double s = sqrt(w) * a;
+        double sn, cs;
+        sincos(s, &sn, &cs);
+        const double S = s == 0.0 ? 1.0 : sn / s;
+        return exp(-a) * (cs + a * S);
+    }
+    const double h = sqrt(-w), y = h * a;
+    const double m = expm1(-2 * y);                           // E - 1
+    const double T = y == 0.0 ? 1.0 : -m / (2 * y);
+    return exp(-(a * (4 * (Q * Q) / (1 + h)))) * (0.5 * (2 + m) + a * T);
+}
+
+// The three kernels behind ONE call that is not inlined: inlined, their sincos / exp / expm1 chains took the generic-program
+// kernels (k_fill_sym<-1>, k_grad_fd_rows, k_grad_contract_b<2>, ...) from 241 to 256 VGPRs, one wave per SIMD instead of two,
+// for every composite of the kernels that were there before (profiles/celerite_isa_resources.txt).  Behind the call those
+// kernels keep their registers, and the kernels' own instantiations run the same code, hence the same bits.
+static __device__ __noinline__ double celerite_value(int kid, double q0, double q1, double q2, double q3, double q4, double tau)
+{
+#pragma clang fp contract(off)
+    if (kid == GPRN_K_SHO) {
+        const double Q = q2, a = PI_D * tau / (q1 * Q);
+        return q0 * q0 * sho_shape(a, (2 * Q - 1) * (2 * Q + 1), Q);
+    }
+    if (kid == GPRN_K_ROTATION) {
+        const double Q1 = q2 + q3, f = q4;
+        const double g1 = 2 * sqrt(Q1 * (Q1 + 1)), g2 = 2 * sqrt(q2 * (q2 + 1));
+        const double p1 = 2 * PI_D * tau / q1, p2 = 4 * PI_D * tau / q1;
+        double s1, c1, s2, c2;
+        sincos(p1, &s1, &c1);
+        sincos(p2, &s2, &c2);
+        const double k1 = exp(-(p1 / g1)) * (c1 + s1 / g1);
+        const double k2 = exp(-(p2 / g2)) * (c2 + s2 / g2);
+        return q0 * q0 / (1 + f) * (k1 + f * k2);
+    }
+    double sn, cs;
+    sincos(q3 * tau, &sn, &cs);
+    return exp(-(q2 * tau)) * (q0 * cs + q1 * sn);
+}
+
 __device__ __forceinline__ double eval_kernel(int kid, const double* __restrict__ q,
                                               double ti, double tj, bool diag, const double* __restrict__ aux = nullptr)
 {
@@ -234,6 +284,10 @@ __device__ __forceinline__ double eval_kernel(int kid, const double* __restrict_
         const double env = exp(-(lp2 * (r * r) + 2 * le2 * (sx * sx)) / (lp2 * le2));
         return scale * poly * env;
     }
+    // The celerite family (not in the reference; gpyrn_amd/covfunc.py SHO, Rotation, CeleriteTerm): functions of |r| alone
+    // (by value, each kernel its own count: SHO has three parameters, CeleriteTerm four)
+    case GPRN_K_SHO: case GPRN_K_ROTATION: case GPRN_K_CELERITE:
+        return celerite_value(kid, q[0], q[1], q[2], kid == GPRN_K_SHO ? 0.0 : q[3], kid == GPRN_K_ROTATION ? q[4] : 0.0, fabs(r));
     default: return 0.0;
     }
 }

@@ -66,7 +66,10 @@ enum {
     GPRN_K_DSE = 21,                /* :182-185 */
     GPRN_K_DPERIODIC = 22,          /* :215-221 */
     GPRN_K_DQP = 23,                /* :257-266 */
-    GPRN_K_COUNT = 24
+    GPRN_K_SHO = 24,                /* not in the reference: damped harmonic oscillator (theta, P0, Q) */
+    GPRN_K_ROTATION = 25,           /* not in the reference: two tied oscillators (theta, P, Q0, dQ, f) */
+    GPRN_K_CELERITE = 26,           /* not in the reference: exp(-c r) (a cos(d r) + b sin(d r)) (a, b, c, d) */
+    GPRN_K_COUNT = 27
 };
 /* postfix opcodes of a kernel expression (covfunc.py:65-77 Sum/Multiplication) */
 enum { GPRN_OP_PUSH = 0, GPRN_OP_ADD = 1, GPRN_OP_MUL = 2 };
