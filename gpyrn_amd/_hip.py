@@ -110,6 +110,9 @@ SIGNATURES = {
                                             POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp, _dp]),
     'gprn_elbocalc_batch_draws': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, c_int, _dp, c_int, _dp, _dp,
                                           POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
+    'gprn_elbocalc_batch_heldout': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, _dp, c_int, c_int, c_void_p, _dp,
+                                            POINTER(c_int), POINTER(c_int), POINTER(c_int), _dp, _dp, _dp, _dp, _dp,
+                                            POINTER(c_int)]),
     'gprn_predict_batch': (c_int, [c_void_p, c_int, _dp, c_int, _dp, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, POINTER(c_int)]),
     'gprn_test_predict_fill': (c_int, [c_void_p, c_int, c_int, _dp, c_int, _dp, c_int, c_int, c_int, _dp, _dp, _dp, _dp]),
     'gprn_test_fill_rect': (c_int, [c_void_p, POINTER(c_int32), c_int, _dp, c_int, c_double, c_int, c_int, c_int, _dp, _dp, _dp,
@@ -611,6 +614,55 @@ class Context:
         self._check(rc, 'elbocalc_batch_predict')
         shape = (B, self.p + 1, self.q, self.N)
         return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), lm, lv, om, ov)
+
+    def elbocalc_batch_heldout(self, kernel_params, y_resid, jitters, mu, var, max_iter, fit_masks, forced=False, rows=True):
+        """B independent ELBOcalc loops side by side, evaluation b fitted under its OWN mask fit_masks[b] (p, N; True = fitted),
+        each followed by the score of what it held out (gprn_elbocalc_batch_heldout): the arrays of ``elbocalc_batch``.
+        Returns (elbo, iterations, converged, info, mu_out, var_out, held_mean, held_var, lpd, n_held): the first six what
+        ``elbocalc`` returns on a context masked with fit_masks[b]; the predictive mean (without the mean functions) and
+        variance of every held-out entry, (B, p, N), zero elsewhere -- or None without `rows`; the log predictive density
+        summed over the held-out entries of each output, (B, p), and their number.  Rows of an evaluation with info > 0 are
+        NaN.  forced (GPRN_BATCH_FORCED): no stop rule, exactly max_iter committed sweeps each.  None where the library has
+        no side-by-side form for this problem."""
+        kp = _f64(kernel_params)
+        if kp.ndim != 2 or kp.shape[0] < 1:
+            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        B = kp.shape[0]
+        d = (self.p + 1) * self.q * self.N
+        if isinstance(y_resid, MeanParams):
+            y_resid = y_resid.host_resid(self)
+        yr, jt, m0, v0 = _f64(y_resid), _f64(jitters), _f64(mu), _f64(var)
+        if yr.size != B * self.p * self.N:
+            raise ValueError(f'y_resid must be (B, p, N) = ({B}, {self.p}, {self.N}), got {yr.shape}')
+        if jt.size != B * self.p:
+            raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
+        if m0.size != B * d or v0.size != B * d:
+            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
+        fm = np.asarray(fit_masks)
+        if fm.shape != (B, self.p, self.N):
+            raise ValueError(f'fit_masks must be (B, p, N) = ({B}, {self.p}, {self.N}), got {fm.shape}')
+        fm = np.ascontiguousarray(fm != 0, dtype=np.uint8)
+        if int(max_iter) < 1:
+            raise ValueError('elbocalc_batch_heldout: a held-out score needs a committed sweep (max_iter >= 1)')
+        elbo = np.empty(B)
+        it, cv, info = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        mo, vo = np.empty((B, d)), np.empty((B, d))
+        hm = np.empty((B, self.p, self.N)) if rows else None
+        hv = np.empty((B, self.p, self.N)) if rows else None
+        lpd = np.empty((B, self.p))
+        nh = np.zeros((B, self.p), dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(POINTER(c_int))
+        opt = lambda a: None if a is None else _ptr(a)
+        rc = self._lib.gprn_elbocalc_batch_heldout(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
+                                                   int(max_iter), GPRN_BATCH_FORCED if forced else 0, fm.ctypes.data,
+                                                   _ptr(elbo), ip(it), ip(cv), ip(info), _ptr(mo), _ptr(vo), opt(hm), opt(hv),
+                                                   _ptr(lpd), ip(nh))
+        if rc == GPRN_E_UNSUPPORTED:
+            return None
+        self._check(rc, 'elbocalc_batch_heldout')
+        shape = (B, self.p + 1, self.q, self.N)
+        return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), hm, hv, lpd,
+                nh.astype(int))
 
     def elbocalc_batch_draws(self, kernel_params, y_resid, jitters, mu, var, max_iter, tstar, z, forced=False, latent=True,
                              outputs=True):

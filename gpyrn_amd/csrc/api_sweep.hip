@@ -779,10 +779,11 @@ static int elbocalc_batch_impl(gprn_ctx* c, BatchIo io)
         return bad(c, "elbocalc_batch: bad argument");
     if (io.grad_out && io.max_iter < 1) return bad(c, "elbocalc_batch_grad: a gradient needs a committed sweep (max_iter >= 1)");
     // (side by side every evaluation starts from one shared state: under a mask that is the caller's choice, option "batch_mask")
-    if (c->d_mask && !c->batch_mask) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
+    // (gprn_elbocalc_batch_heldout brings a fit mask per evaluation and needs no option: it is a new entry point)
+    if (c->d_mask && !c->batch_mask && !io.held.fit) { c->err = "elbocalc_batch: not supported under a data mask (gprn_set_mask)"; return GPRN_E_UNSUPPORTED; }
     // (a prediction's call reads what the loops left in the batch's own buffers and writes nothing of the context's: a committed
-    // sweep of the context stays what it was, as under gprn_predict_batch)
-    if (!io.pred.ns && !io.draws.ns) c->grad_ready = false;
+    // sweep of the context stays what it was, as under gprn_predict_batch; so does a held-out call)
+    if (!io.pred.ns && !io.draws.ns && !io.held.fit) c->grad_ready = false;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->owner.empty()) return bad(c, "elbocalc_batch: call set_owners first");
     if (comm_active(c) || c->world != 1) { c->err = "elbocalc_batch: one rank only (a pool of ranks splits the list itself)"; return GPRN_E_UNSUPPORTED; }
@@ -887,6 +888,66 @@ extern "C" int gprn_elbocalc_batch_draws(gprn_ctx* c, int n_eval, const double* 
     const int rc = elbocalc_batch_impl(c, io);
     if (!rc && info_gp >= 0) c->info_gp = info_gp;       // (the latent GP of the first failed last rung: gprn_last_info_gp)
     return rc;
+}
+
+// gprn_elbocalc_batch_grad(grad_out = NULL) with a fit mask per evaluation and, behind each chunk's loop, the held-out pass of
+// batch_tail.hip (include/gprn_hip.h): k folds x S vectors of a cross-validation in one call.  The masks are checked here, on the
+// host, before anything is launched; the call's plan -- which latent GPs have a U in some evaluation, the largest |U| -- sizes the
+// drivers' lanes and slabs through gprn_ctx::held for the length of the call
+extern "C" int gprn_elbocalc_batch_heldout(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,
+                                           const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                           int max_iter, int flags, const uint8_t* fit_mask,
+                                           double* elbo, int* iterations, int* converged, int* info, double* mu_out, double* var_out,
+                                           double* held_mean, double* held_var, double* lpd, int* n_held)
+{
+    DeviceLock lock_(c);
+    WatchScope watch_(c, "gprn_elbocalc_batch_heldout");
+    if (!c || !c->N || n_eval < 1 || !fit_mask || !lpd || !n_held || (!held_mean != !held_var))
+        return bad(c, "elbocalc_batch_heldout: bad argument");
+    if (max_iter < 1) return bad(c, "elbocalc_batch_heldout: a held-out score needs a committed sweep (max_iter >= 1)");
+    if (c->sweep_order != GPRN_ORDER_REFERENCE) {
+        c->err = "elbocalc_batch_heldout: not supported under the sequential sweep order (gprn_set_sweep_order)";
+        return GPRN_E_UNSUPPORTED;
+    }
+    const int N = c->N, p = c->p, q = c->q, G = c->G;
+    const size_t pn = (size_t)p * N;
+    std::vector<uint8_t> fit((size_t)n_eval * pn);
+    HeldPlan plan;
+    std::vector<char> has_u(G, 0);
+    size_t umax = 0;
+    for (int b = 0; b < n_eval; ++b) {
+        uint8_t* const f = fit.data() + b * pn;
+        const std::string who = "elbocalc_batch_heldout: the fit mask of evaluation " + std::to_string(b);
+        for (size_t k = 0; k < pn; ++k) {
+            f[k] = fit_mask[b * pn + k] ? 1 : 0;
+            if (f[k] && !c->h_mask.empty() && !c->h_mask[k]) {
+                c->err = who + " fits an entry the data mask does not hold (gprn_set_mask)"; return GPRN_E_ARG;
+            }
+        }
+        for (int i = 0; i < p; ++i) {
+            bool any = false;
+            for (int n = 0; n < N && !any; ++n) any = f[(size_t)i * N + n] != 0;
+            if (!any) { c->err = who + " leaves an output without a fitted entry"; return GPRN_E_ARG; }
+        }
+        for (int n = 0; n < N && q > 1; ++n) {
+            bool any = false;
+            for (int i = 0; i < p; ++i) any = any || f[(size_t)i * N + n] != 0;
+            if (!any) { c->err = who + " leaves a time without a fitted output (q >= 2 needs one at every time)"; return GPRN_E_ARG; }
+        }
+        for (int g = 0; g < G; ++g) {
+            const size_t nu = held_rows_of(f, p, q, N, g).size();
+            if (nu) has_u[g] = 1;
+            umax = std::max(umax, nu);
+        }
+    }
+    for (int g = 0; g < G; ++g) if (has_u[g]) plan.ent[g < q ? 0 : 1].push_back(g);
+    plan.upad = (int)((umax + GPRN_TILE - 1) / GPRN_TILE) * GPRN_TILE;
+    BatchIo io{n_eval, kernel_params, n_kernel_params, y_resid, jitters, mu, var, max_iter, elbo, iterations, converged, info, mu_out, var_out};
+    io.flags = flags;
+    io.held = BatchHeld{fit.data(), held_mean, held_var, lpd, n_held, p, pn};
+    struct Plan { gprn_ctx* c; ~Plan() { c->held = nullptr; } } plan_{c};
+    c->held = &plan;
+    return elbocalc_batch_impl(c, io);
 }
 
 extern "C" int gprn_elbocalc_batch(gprn_ctx* c, int n_eval, const double* kernel_params, int n_kernel_params,

@@ -30,7 +30,9 @@ struct MaskLane {
     double *mu, *var;          // the evaluation's state copy the half-sweep writes, (p + 1, q, N)
     const int* done;           // the evaluation's stop word (one tile: its workgroups are no-ops once it is set), or null
     int gp;
+    int row;                   // its row of the tables U / nU: gp under the data's one mask, evaluation * G + gp under per-evaluation masks
 };
+static_assert(sizeof(MaskLane) == 72, "the lane's row number lives in what was padding behind gp");
 
 // ---- above one tile (midn.hip): the device tables and their pinned image, for cap evaluations of G = q (p + 1) latent GPs,
 // ne0 / ne1 of the node / weight phase with a non-empty U, rows of nb pointers.  Two constraints on the order, stated here

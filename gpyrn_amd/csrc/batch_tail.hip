@@ -1,7 +1,8 @@
 // The tail of a chunk of side-by-side evaluations (gprn_elbocalc_batch*): everything that runs behind the chunk's loop, once
 // for both drivers (one tile: smalln.hip; above: midn.hip).  A driver ends with two steps: it describes what its loop left
 // (gprn_internal.h ChunkLeft) and calls batch_tail, which runs, in this order, the states back, the gradient pass (grad.hip
-// grad_batch_pass), the bound form's mean entries (mean.hip mean_grad_pass), the prediction pass and the draw pass (both in
+// grad_batch_pass), the bound form's mean entries (mean.hip mean_grad_pass), the held-out pass (gprn_elbocalc_batch_heldout: one
+// kernel, k_heldout_tail, and the chunk's fit masks HeldDev), the prediction pass and the draw pass (all three in
 // this file, with their kept buffers TailKept and the two kernels of the draw pass) and the GPRN_BATCH_TIMERS line.
 // The two passes are the posterior forms of gprn_predict and gprn_predict_draws (api_more.hip) with batch = evaluations x latent
 // GPs, from the X, s = sqrt(d) and ct = X^T X z each evaluation's last committed sweep left; they share pred_block, one block
@@ -306,6 +307,158 @@ static int batch_draw_pass(const ChunkLeft& left, double* pin, const BatchDraws&
     return GPRN_OK;
 }
 
+// ------------------------------------------------------------------ the held-out pass (gprn_elbocalc_batch_heldout)
+// Each evaluation fitted under its own mask; H_b = D and not fit_b is what it held out (D: the context's data mask, null: all
+// ones).  On H_b the state of the evaluation's last committed sweep holds the imputed rows mask.hip wrote, so the predictive of
+// output i at t_n is read off the state alone -- no fill, no factorisation, no tile product:
+//     m = sum_j mu_f_j mu_w_ij,   v = sum_j [mu_w_ij^2 var_f_j + var_w_ij (var_f_j + mu_f_j^2)] + (jitter_i^2 + yerr_in^2)
+// (the last term is the sweeps' own `variance`, jitter once), lpd_bi = sum_{n in H_b} -1/2 [log(2 pi v) + (y_resid - m)^2 / v].
+// One workgroup per (output, evaluation); thread t adds its n = t, t + 256, ... in turn, then the waves' shuffle tree and the
+// four wave sums in a fixed order: two calls return the same bits.  Entries outside H_b are never read beyond the two masks
+// (NaN / inf in a never-observed y_resid or yerr reach no arithmetic) and get 0 in both rows.  grid (p, evaluations)
+__global__ __launch_bounds__(256)
+void k_heldout_tail(const double* __restrict__ mu, const double* __restrict__ var, size_t state, const int* __restrict__ fcopy,
+                    const uint8_t* __restrict__ fit, const uint8_t* __restrict__ D, const double* __restrict__ yres,
+                    const double* __restrict__ variance, int N, int p, int q, size_t cap_pn, double* __restrict__ rows,
+                    double* __restrict__ lpd, int* __restrict__ count)
+{
+    __shared__ double sh[4];
+    __shared__ int shc[4];
+    const double TWO_PI = 6.283185307179586;
+    const int i = blockIdx.x, b = blockIdx.y;
+    const size_t pn = (size_t)p * N, eb = (size_t)b * pn + (size_t)i * N;
+    mu += (size_t)fcopy[b] * state; var += (size_t)fcopy[b] * state;
+    const size_t wrow = (size_t)(1 + i) * q;
+    double acc = 0.0;
+    int cnt = 0;
+    for (int n = threadIdx.x; n < N; n += 256) {
+        const bool held = (!D || D[(size_t)i * N + n]) && !fit[eb + n];
+        double m = 0.0, v = 0.0;
+        if (held) {
+            for (int j = 0; j < q; ++j) {
+                const double mf = mu[(size_t)j * N + n], vf = var[(size_t)j * N + n];
+                const double mw = mu[(wrow + j) * N + n], vw = var[(wrow + j) * N + n];
+                m += mf * mw;
+                v += mw * mw * vf + vw * (vf + mf * mf);
+            }
+            v += variance[eb + n];
+            const double r = yres[eb + n] - m;
+            acc += -0.5 * (log(TWO_PI * v) + r * r / v);
+            cnt += 1;
+        }
+        rows[eb + n] = m;
+        rows[cap_pn + eb + n] = v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc += __shfl_down(acc, o, 64);
+        cnt += __shfl_down(cnt, o, 64);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { sh[w] = acc; shc[w] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        lpd[(size_t)b * p + i] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+        count[(size_t)b * p + i] = (shc[0] + shc[1]) + (shc[2] + shc[3]);
+    }
+}
+
+// the pinned block of HeldDev: what goes in per chunk, then what comes out
+struct HeldPin { uint8_t* fit; int *U, *nU, *fcopy; double* rows; int* count; };
+static HeldPin held_pin(LayoutCursor& c, size_t cap, size_t G, size_t p, size_t pn, size_t upad_all)
+{
+    return {c.take<uint8_t>(cap * pn), c.take<int>(cap * G * upad_all), c.take<int>(cap * G), c.take<int>(cap),
+            c.take<double>(2 * cap * pn + cap * p), c.take<int>(cap * p)};
+}
+
+int HeldDev::make(gprn_ctx* c, DeviceOwner& own, int cap_, int T, int ld)
+{
+    const size_t n = (size_t)cap_, G = c->G, p = c->p, pn = p * (size_t)c->N;
+    upad = c->held->upad; upad_all = std::max(upad, 1); cap = cap_;
+    TRY(own.alloc(c, &fit, n * pn));
+    TRY(own.alloc(c, &U, n * G * upad_all));
+    TRY(own.alloc(c, &nU, n * G));
+    TRY(own.alloc(c, &fcopy, n));
+    TRY(own.alloc(c, &rows, 2 * n * pn + n * p));
+    TRY(own.alloc(c, &count, n * p));
+    TRY(own.pin(c, &pin, layout_count<char>(held_pin, n, G, p, pn, (size_t)upad_all)));
+    // C = WT X^T by 128 x 128 tiles for the call's upad (mask_prepare's list is the context's mask's, which may not exist)
+    std::vector<TileTask> t;
+    for (int bt = 0; bt < upad / GPRN_TILE; ++bt)
+        for (int at = 0; at < T; ++at)
+            t.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE, (int64_t)bt * GPRN_TILE * ld,
+                                 (int64_t)at * GPRN_TILE * ld, (at + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_X, tile_modes(CM_SET, 0, 0)});
+    ntasks = t.size();
+    TRY(own.alloc(c, &tasks, ntasks));
+    if (ntasks) HIP_TRY(c, hipMemcpy(tasks, t.data(), ntasks * sizeof(TileTask), hipMemcpyHostToDevice));
+    return GPRN_OK;
+}
+
+// the masks of the chunk's n evaluations and their rows U (gprn_set_mask's rule per evaluation), behind whatever `st` still runs
+int HeldDev::upload(gprn_ctx* c, const BatchHeld& h, int n, hipStream_t st)
+{
+    const int G = c->G, p = c->p, q = c->q, N = c->N;
+    const size_t pn = (size_t)p * N;
+    const HeldPin hp = layout_at(pin, held_pin, (size_t)cap, (size_t)G, (size_t)p, pn, (size_t)upad_all);
+    HIP_TRY(c, hipStreamSynchronize(st));            // (the pinned image may still be on its way out of the last chunk)
+    memcpy(hp.fit, h.fit, (size_t)n * pn);
+    h_nU.assign((size_t)n * G, 0);
+    for (int b = 0; b < n; ++b)
+        for (int g = 0; g < G; ++g) {
+            const std::vector<int> u = held_rows_of(h.fit + b * pn, p, q, N, g);
+            if ((int)u.size() > upad) return bad(c, "elbocalc_batch_heldout: a fit mask has more rows U than the call was planned for");
+            const size_t row = (size_t)b * G + g;
+            h_nU[row] = hp.nU[row] = (int)u.size();
+            std::fill(hp.U + row * upad_all, hp.U + (row + 1) * upad_all, -1);
+            std::copy(u.begin(), u.end(), hp.U + row * upad_all);
+        }
+    HIP_TRY(c, hipMemcpyAsync(fit, hp.fit, (size_t)n * pn, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(U, hp.U, (size_t)n * G * upad_all * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(nU, hp.nU, (size_t)n * G * sizeof(int), hipMemcpyHostToDevice, st));
+    return GPRN_OK;
+}
+
+// One launch over the chunk, the rows and sums back through the pinned block; an evaluation whose pivot failed gets NaN
+static int batch_held_pass(gprn_ctx* c, const ChunkLeft& left, HeldDev& hd, const BatchHeld& out)
+{
+    gprn_ctx* const w = left.w;
+    const int n = left.n, p = left.p, G = left.G;
+    const size_t pn = (size_t)p * left.N, cap_pn = (size_t)hd.cap * pn;
+    hipStream_t st = w->stream;
+    const HeldPin hp = layout_at(hd.pin, held_pin, (size_t)hd.cap, (size_t)G, (size_t)p, pn, (size_t)hd.upad_all);
+    for (int b = 0; b < n; ++b) {
+        if (left.final_copy[b] < 0) return bad(c, "elbocalc_batch_heldout: no sweep was committed");
+        hp.fcopy[b] = left.final_copy[b];
+    }
+    HIP_TRY(c, hipMemcpyAsync(hd.fcopy, hp.fcopy, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    prof_begin(w, GPRN_T_VEC);
+    hipLaunchKernelGGL(k_heldout_tail, dim3(p, n), dim3(256), 0, st, left.mu, left.var, left.state, (const int*)hd.fcopy,
+                       (const uint8_t*)hd.fit, (const uint8_t*)c->d_mask, left.yres, left.variance, left.N, p, left.q, cap_pn, hd.rows,
+                       hd.rows + 2 * cap_pn, hd.count);
+    prof_end(w);
+    HIP_TRY(c, hipGetLastError());
+    double* const pin_lpd = hp.rows + 2 * cap_pn;
+    if (out.mean) {
+        HIP_TRY(c, hipMemcpyAsync(hp.rows, hd.rows, (size_t)n * pn * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(hp.rows + cap_pn, hd.rows + cap_pn, (size_t)n * pn * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(c, hipMemcpyAsync(pin_lpd, hd.rows + 2 * cap_pn, (size_t)n * p * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(hp.count, hd.count, (size_t)n * p * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (out.mean) {
+        memcpy(out.mean, hp.rows, (size_t)n * pn * sizeof(double));
+        memcpy(out.var, hp.rows + cap_pn, (size_t)n * pn * sizeof(double));
+    }
+    memcpy(out.lpd, pin_lpd, (size_t)n * p * sizeof(double));
+    memcpy(out.n_held, hp.count, (size_t)n * p * sizeof(int));
+    for (int b = 0; b < n; ++b) {
+        if (left.info[b] <= 0) continue;
+        std::fill(out.lpd + (size_t)b * p, out.lpd + (size_t)(b + 1) * p, NAN);
+        if (out.mean) { std::fill(out.mean + b * pn, out.mean + (b + 1) * pn, NAN); std::fill(out.var + b * pn, out.var + (b + 1) * pn, NAN); }
+    }
+    return GPRN_OK;
+}
+
 // ------------------------------------------------------------------ the tail
 // every evaluation's final state through the pinned images into the caller's arrays
 static int states_back(gprn_ctx* c, const BatchIo& io, const ChunkLeft& left)
@@ -335,6 +488,7 @@ int batch_tail(gprn_ctx* c, const BatchIo& io, const ChunkLeft& left, TailKept& 
     const double us_states = rep.t.lap();
     if (io.grad_out) TRY(grad_batch_pass(c, left, io));
     if (io.means.grad_out) TRY(mean_grad_pass(c, left, io.means));
+    if (io.held.fit) TRY(batch_held_pass(c, left, kept.held, io.held));
     const double us_grad = rep.t.lap();
     if (predict || draws) TRY(kept.ensure(c, left, io.pred.ns, draws));
     if (predict) TRY(batch_pred_pass(left, kept, io.jitters, io.pred));

@@ -119,8 +119,10 @@ struct EvalMap {
 };
 
 // The rows U of many evaluations side by side (mask.hip's _b kernels; gprn_elbocalc_batch under option "batch_mask"): one
-// lane per (evaluation, latent GP of the phase with a non-empty U).  The mask, and with it every U, is the data's: the same
-// for all evaluations.
+// lane per (evaluation, latent GP of the phase with a non-empty U).  Under option "batch_mask" the mask, and with it every U, is
+// the data's: U / nU are the context's tables and a lane's row is its latent GP.  Under gprn_elbocalc_batch_heldout every
+// evaluation has its own: U / nU are the chunk's tables (HeldDev), a lane's row is evaluation x G + latent GP.
+struct HeldPlan;
 struct MaskBatch {
     const MaskLane* lanes = nullptr;   // [n] (device)
     double** tab = nullptr;            // [n][GPRN_NBUF]: BUF_X = the slot's X, BUF_K = WT, BUF_KLINV = C
@@ -290,6 +292,11 @@ struct gprn_ctx {
     int batch_mask = 0;                  // gprn_set_option "batch_mask": gprn_elbocalc_batch* run under a data mask (default: refused)
     int grad_exact = 0;                  // gprn_set_option "grad_exact": the gradient entry points take dK/dtheta from dk_eval.h, not from differences
     MaskBatch mask_batch[2];             // a batch's worker context (midn.hip): the lanes of its node / weight phase
+    // gprn_elbocalc_batch_heldout: set for the length of the call on the caller's context -- the drivers size their lanes and
+    // slabs by it instead of by the context's own mask; on a batch's worker, bytes between two evaluations' fit masks behind
+    // d_mask (0: the mask is shared; the masked vec_prep / vec_elbo_evals instantiations add slot_eval x this)
+    const HeldPlan* held = nullptr;
+    size_t mask_ev_stride = 0;
 
     // ---- small-N path (smalln.hip): problems of one or two tiles run a half-sweep as ONE launch, one workgroup per latent GP
     int small_opt = -1;              // gprn_set_option "small_path": 0 never, else wherever it applies (small_applies)
@@ -617,6 +624,36 @@ int mean_grad_pass(gprn_ctx* c, const ChunkLeft& left, const BatchMeans& mn);
 struct CallScratch;
 int mean_batch_upload(gprn_ctx* c, CallScratch& scr, int n_eval, const double* mean_params, int n_params, BatchMeans* out);
 
+// gprn_elbocalc_batch_heldout: every evaluation fits under a mask of its own and the tail scores what it held out.  fit: the
+// caller's masks as 0 / 1 bytes (null: another entry point); the caller's rows of its evaluations -- mean, var [n][p N] (both or
+// neither), lpd [n][p], n_held [n][p]
+struct BatchHeld {
+    const uint8_t* fit = nullptr;
+    double *mean = nullptr, *var = nullptr, *lpd = nullptr; int* n_held = nullptr;
+    int p = 0; size_t pn = 0;
+    BatchHeld from(int e0) const               // evaluations [e0, ...)
+    {
+        return BatchHeld{fit ? fit + e0 * pn : nullptr, mean ? mean + e0 * pn : nullptr, var ? var + e0 * pn : nullptr,
+                         lpd ? lpd + (size_t)e0 * p : nullptr, n_held ? n_held + (size_t)e0 * p : nullptr, p, pn};
+    }
+};
+// ... and what the drivers size their buffers by for the length of such a call (gprn_ctx::held): per phase the latent GPs with a
+// non-empty U in ANY evaluation of the call ("entries": a lane whose own U is empty does nothing), and the call's largest |U|
+// rounded up to 128 (0: nothing is held out at all)
+struct HeldPlan { std::vector<int> ent[2]; int upad = 0; };
+// the rows U of latent GP gp under the fit mask `fit` (p, N; 0 / 1): gprn_set_mask's rule
+static inline std::vector<int> held_rows_of(const uint8_t* fit, int p, int q, int N, int gp)
+{
+    std::vector<int> U;
+    for (int n = 0; n < N; ++n) {
+        bool zero;
+        if (gp >= q) zero = !fit[(size_t)((gp - q) % p) * N + n];
+        else { zero = q == 1; for (int i = 0; i < p && zero; ++i) zero = !fit[(size_t)i * N + n]; }
+        if (zero) U.push_back(n);
+    }
+    return U;
+}
+
 // One call of gprn_elbocalc_batch -- its pointers and counts -- or a run of its evaluations (slice)
 struct BatchIo {
     int n; const double* kparams; int n_kpar; const double *y_resid, *jitters, *mu, *var; int max_iter;
@@ -627,12 +664,14 @@ struct BatchIo {
     BatchPred pred{};                      // gprn_elbocalc_batch_predict: the prediction pass behind the chunk's loop (ns = 0: none)
     BatchMeans means{};                    // gprn_elbocalc_batch_means: y - mean is formed on the device (programs = null: y_resid is read)
     BatchDraws draws{};                    // gprn_elbocalc_batch_draws: the draw pass behind the chunk's loop (ns = 0: none)
+    BatchHeld held{};                      // gprn_elbocalc_batch_heldout: per-evaluation fit masks and the held-out pass (fit = null: none)
     BatchIo slice(int e0, int ne) const    // evaluations [e0, e0 + ne)
     {
         return BatchIo{ne, kparams + (size_t)e0 * n_kpar, n_kpar, y_resid ? y_resid + e0 * yv : nullptr, jitters + (size_t)e0 * p, mu + e0 * state,
                        var + e0 * state, max_iter, elbo + e0, iters + e0, conv + e0, info + e0,
                        mu_out ? mu_out + e0 * state : nullptr, var_out ? var_out + e0 * state : nullptr, p, state, yv,
-                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0), means.from(e0, yv), draws.from(e0)};
+                       flags, grad_out ? grad_out + (size_t)e0 * n_kpar : nullptr, pred.from(e0), means.from(e0, yv), draws.from(e0),
+                       held.from(e0)};
     }
 };
 // ---- batch_tail.hip: what runs behind a chunk's loop of gprn_elbocalc_batch*, written once for both drivers.
@@ -667,9 +706,28 @@ struct PredRows { double *kss, *lmean, *lvar, *omean, *ovar; };
 // The passes' kept buffers, charged to the driver's DeviceOwner (freed with the batch): there from the first call that asks for
 // a prediction or for draws, so that a call allocates and frees nothing on the device once they exist
 struct DeviceOwner;
+// gprn_elbocalc_batch_heldout: a chunk's fit masks and their rows U on the device, the task list of C = WT X^T for the call's
+// upad, and what the held-out pass writes on its way to the caller -- made with the driver's buffers (charged to its owner),
+// filled per chunk by upload() before the chunk's first launch
+struct HeldDev {
+    uint8_t* fit = nullptr;                // [cap][p N], 1 = fitted
+    int *U = nullptr, *nU = nullptr;       // [cap G][upad_all], [cap G]: row = evaluation * G + latent GP
+    int* fcopy = nullptr;                  // [cap]: the state copy each evaluation ended in
+    TileTask* tasks = nullptr;             // (upad / 128) x T tiles
+    size_t ntasks = 0;
+    int upad = 0, upad_all = 1, cap = 0;
+    double* rows = nullptr;                // [2][cap][p N] held means | held variances, then [cap p] lpd
+    int* count = nullptr;                  // [cap p] n_held
+    char* pin = nullptr;                   // pinned: the masks and tables going in, the rows coming out
+    std::vector<int> h_nU;                 // host [chunk G]: which lanes have anything to do (midn.hip)
+    int make(gprn_ctx* c, DeviceOwner& own, int cap, int T, int ld);
+    int upload(gprn_ctx* c, const BatchHeld& h, int n, hipStream_t st);
+    MaskBatch batch() const { return MaskBatch{nullptr, nullptr, 0, upad, tasks, ntasks, U, nU, upad_all}; }
+};
 struct TailKept {
     DeviceOwner* own = nullptr;            // the driver's
     PredRows rows{};                       // the driver's
+    HeldDev held;                          // gprn_elbocalc_batch_heldout (made by the driver with its buffers)
     // the prediction pass's device rows, derived from ChunkLeft::rows: BUF_X = X (read), BUF_K = a block of K* S in B's
     // workspace, BUF_KLINV = its W^T in K (two ld x ld buffers per slot the loop has finished with; the next chunk's set-up
     // refills both) -- and behind them the BUF_K pointers again, where the fill writes
@@ -764,6 +822,17 @@ int mask_rows_lanes(gprn_ctx* c, const MaskBatch& mb, int N, int ld);
 // the latent GPs of a phase with a non-empty U under c's mask, when batches run under it (one rank: slot = latent GP, nodes
 // first), and what a MaskBatch of that phase takes from c's mask (lanes, tab, n: the driver's)
 std::vector<int> batch_mask_entries(const gprn_ctx* c, bool weights);
+// ... what a driver sizes a chunk by: the call's plan under gprn_elbocalc_batch_heldout, else the context's mask -- the entries of
+// a phase, the rows of WT / C per entry, and the bytes per evaluation of HeldDev's tables
+static inline std::vector<int> batch_plan_entries(const gprn_ctx* c, bool weights)
+{ return c->held ? c->held->ent[weights ? 1 : 0] : batch_mask_entries(c, weights); }
+static inline int batch_plan_upad(const gprn_ctx* c) { return c->held ? c->held->upad : c->mask_upad; }
+static inline size_t held_bytes_per_eval(const gprn_ctx* c)
+{
+    if (!c->held) return 0;
+    const size_t pn = (size_t)c->p * c->N, rows = (size_t)c->G * (std::max(c->held->upad, 1) + 1);
+    return 2 * (pn + (rows + 1 + c->p) * sizeof(int) + (2 * pn + c->p) * sizeof(double));   // (device and pinned)
+}
 static inline MaskBatch mask_batch_of(const gprn_ctx* c, int ph)
 { return MaskBatch{nullptr, nullptr, 0, c->mask_upad_ph[ph], c->d_mask_tasks[ph], c->mask_ntasks[ph], c->d_mask_U, c->d_mask_nU, c->mask_upad}; }
 int mask_prepare(gprn_ctx* c);       // buffers, tables and task lists for the current slots (build_tables: the set-up)

@@ -78,7 +78,9 @@ void k_mask_rows(double* const* __restrict__ ptrs, double* const* __restrict__ m
 }
 
 // ---- the same two kernels for many evaluations side by side: lane = (evaluation, latent GP with a U), everything an
-// evaluation owns found through its MaskLane; a lane whose evaluation has stopped does nothing (its state stays its last trip's)
+// evaluation owns found through its MaskLane -- its rows of U / nU included (MaskLane::row: the latent GP under the data's one
+// mask, evaluation * G + latent GP under gprn_elbocalc_batch_heldout's per-evaluation masks); a lane whose evaluation has stopped
+// does nothing (its state stays its last trip's), nor does one whose own U is empty
 // grid (ld / 256, upad, lanes)
 __global__ __launch_bounds__(256)
 void k_mask_gather_b(const MaskLane* __restrict__ lanes, const int* __restrict__ U, const int* __restrict__ nU, int upad_all,
@@ -89,8 +91,8 @@ void k_mask_gather_b(const MaskLane* __restrict__ lanes, const int* __restrict__
     const int u = blockIdx.y, m = blockIdx.x * 256 + threadIdx.x;
     if (m >= ld) return;
     double v = 0.0;
-    if (u < nU[a.gp] && m < N) {
-        const int n = U[(size_t)a.gp * upad_all + u];
+    if (u < nU[a.row] && m < N) {
+        const int n = U[(size_t)a.row * upad_all + u];
         v = a.K[(size_t)n * ld + m] * a.s[m];
     }
     a.WT[(size_t)u * ld + m] = v;
@@ -105,8 +107,8 @@ void k_mask_rows_b(const MaskLane* __restrict__ lanes, const int* __restrict__ U
     if (a.done && *a.done) return;
     const int u = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int gp = a.gp;
-    if (u >= nU[gp]) return;
-    const int n = U[(size_t)gp * upad_all + u];
+    if (u >= nU[a.row]) return;
+    const int n = U[(size_t)a.row * upad_all + u];
     const double* WT = a.WT + (size_t)u * ld;
     const double* C = a.C + (size_t)u * ld;
     double sa = 0.0, sb = 0.0;

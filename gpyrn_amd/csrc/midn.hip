@@ -77,6 +77,9 @@ struct MidBatch {
     // evaluation); WT and C per (evaluation, entry); the lanes of mask.hip's batched rows over the ACTIVE evaluations and the tile
     // product's pointer rows (dp.mask), rebuilt with the node-major tables (mid_upload_active)
     const uint8_t* mask = nullptr;    // the parent's mask the slabs were sized for (null: none)
+    // gprn_elbocalc_batch_heldout: the entries and mask_upad are the call's plan (the slabs are keyed by them), `mask` is the
+    // chunk's own fit masks (kept.held.fit, p N bytes per evaluation) and a lane carries row evaluation * G + latent GP
+    bool held = false;
     std::vector<int> mask_gps[2];
     int mask_upad = 0;
     double* mask_wc = nullptr;        // [cap][entries of both phases][2][mask_upad * ld]
@@ -104,9 +107,10 @@ static size_t mid_bytes_per_eval(const gprn_ctx* c)
                + G * ld * (7 + 2 * (size_t)c->T + 2)           // per-slot vectors, partial column sums, finalising terms
                + n_q1 * c->q / 2 * ld + 2 * d + 2 * (size_t)c->p * c->N + 64;
     // (under a data mask: WT and C of every latent GP with a U, mask_upad x ld each, its lane and pointer row)
-    const size_t ne = batch_mask_entries(c, false).size() + batch_mask_entries(c, true).size();
-    dbl += ne * (2 * (size_t)c->mask_upad * ld + GPRN_NBUF);
-    return dbl * sizeof(double) + ne * sizeof(MaskLane);
+    // (under gprn_elbocalc_batch_heldout: of every entry of the call's plan, upad the call's, and the evaluation's own mask and U tables)
+    const size_t ne = batch_plan_entries(c, false).size() + batch_plan_entries(c, true).size();
+    dbl += ne * (2 * (size_t)batch_plan_upad(c) * ld + GPRN_NBUF);
+    return dbl * sizeof(double) + ne * sizeof(MaskLane) + held_bytes_per_eval(c);
 }
 
 // the worker's arrays, the slabs and the tables for `cap` evaluations of the parent's problem
@@ -114,8 +118,9 @@ static int mid_make(gprn_ctx* c, MidBatch* m, int cap)
 {
     const int N = c->N, p = c->p, q = c->q, G = c->G, ld = c->ld, T = c->T;
     m->N = N; m->p = p; m->q = q; m->G = G; m->ld = ld;
-    m->mask_gps[0] = batch_mask_entries(c, false); m->mask_gps[1] = batch_mask_entries(c, true);
-    m->mask_upad = c->mask_upad;
+    m->mask_gps[0] = batch_plan_entries(c, false); m->mask_gps[1] = batch_plan_entries(c, true);
+    m->mask_upad = batch_plan_upad(c);
+    m->held = c->held != nullptr;
     const MidShape sh{(size_t)cap, (size_t)G, (size_t)q, (size_t)p, m->mask_gps[0].size(), m->mask_gps[1].size(), GPRN_NBUF};
     const size_t ne_all = sh.ne0 + sh.ne1;
     // ---- the worker: the parent's problem, `cap` evaluations' worth of state and per-slot vectors
@@ -158,6 +163,10 @@ static int mid_make(gprn_ctx* c, MidBatch* m, int cap)
     if (ne_all) {
         TRY(m->own.alloc(c, &m->mask_wc, (size_t)cap * ne_all * 2 * m->mask_upad * ld));
         TRY(m->own.alloc(c, &m->d_mask_lanes, (size_t)cap * ne_all));
+    }
+    if (m->held) {                                        // (the masks the worker's kernels read are the chunk's own)
+        TRY(m->kept.held.make(c, m->own, cap, T, ld));
+        m->mask = m->kept.held.fit;
     }
     // ---- tables and pinned blocks
     double** d_ptr = nullptr;
@@ -209,7 +218,11 @@ int mid_batch_reserve(gprn_ctx* c, int want, int* cap_out)
     const int fit = (int)std::max<size_t>(1, std::min<size_t>(batch_budget_bytes(c) / per, (size_t)32768 / c->G));
     want = std::min(want, fit);
     const uint8_t* const mask = c->batch_mask ? c->d_mask : nullptr;
-    const bool same = m && m->N == c->N && m->p == c->p && m->q == c->q && m->ld == c->ld && m->mask == mask;
+    const bool held = c->held != nullptr;
+    const bool same_mask = m && m->held == held &&
+                           (held ? m->mask_gps[0] == c->held->ent[0] && m->mask_gps[1] == c->held->ent[1] && m->mask_upad == c->held->upad
+                                 : m->mask == mask);
+    const bool same = m && m->N == c->N && m->p == c->p && m->q == c->q && m->ld == c->ld && same_mask;
     if (same && m->cap >= want && m->cap <= fit) { *cap_out = m->cap; return GPRN_OK; }
     // new slabs in a new MidBatch (no member of the old one survives); the worker of the same problem moves over
     gprn_ctx* w = nullptr;
@@ -256,20 +269,24 @@ static int mid_upload_active(gprn_ctx* c, MidBatch* m, const std::vector<int>& a
         const size_t d = (size_t)(p + 1) * q * m->N, wc = (size_t)m->mask_upad * m->ld;
         for (int wt = 0; wt < 2; ++wt) {
             const size_t ne = m->mask_gps[wt].size(), first = wt ? (size_t)m->cap * ne0 : 0;
+            size_t ln = 0;
             for (size_t e = 0; e < ne; ++e)
                 for (int a = 0; a < nA; ++a) {
                     const int g = m->mask_gps[wt][e], b = act[a];
                     // (node-major slots: the per-slot vectors of the weight phase lie behind the q nA node slots)
                     const size_t slot = wt ? (size_t)q * nA + (size_t)(g - q) * nA + a : (size_t)g * nA + a;
-                    const size_t sb = (size_t)b * G + g, ln = e * nA + a;
+                    const size_t sb = (size_t)b * G + g;
+                    // (per-evaluation masks: an entry is a latent GP with a U in SOME evaluation; where this one has none, no lane)
+                    if (m->held && !m->kept.held.h_nU[sb]) continue;
                     double* const wtp = m->mask_wc + (((size_t)b * ne_all + (wt ? ne0 : 0) + e) * 2) * wc;
                     hl[first + ln] = MaskLane{m->K + sb * nn, w->d_s + slot * m->ld, w->d_ct + slot * m->ld, wtp, wtp + wc,
-                                              w->d_mu + (size_t)b * d, w->d_var + (size_t)b * d, nullptr, g};
+                                              w->d_mu + (size_t)b * d, w->d_var + (size_t)b * d, nullptr, g, m->held ? (int)sb : g};
                     buf_row(hp.mask[wt] + ln * GPRN_NBUF, m->Bw + sb * nn, m->Xw + sb * nn, wtp, wtp + wc);
+                    ++ln;
                 }
             w->mask_batch[wt].lanes = m->d_mask_lanes + first;
             w->mask_batch[wt].tab = m->dp.mask[wt];
-            w->mask_batch[wt].n = (int)ne * nA;
+            w->mask_batch[wt].n = (int)ln;
         }
         HIP_TRY(c, hipMemcpyAsync(m->d_mask_lanes, hl, (size_t)m->cap * ne_all * sizeof(MaskLane), hipMemcpyHostToDevice, w->stream));
     }
@@ -364,6 +381,7 @@ static int mid_chunk(gprn_ctx* c, MidBatch* m, const BatchIo& io)
     LapTimer t;
     double us_stage = 0.0, us_setup = 0.0, us_enqueue = 0.0, us_wait = 0.0, us_host = 0.0;
     int n_sweeps = 0;
+    if (m->held) TRY(m->kept.held.upload(c, io.held, B, st));   // (this chunk's fit masks and their rows U)
     TRY(batch_stage(c, io, m->in.programs, m->cap, BatchBufs{m->programs, w->d_yres, w->d_variance, w->d_mu, w->d_var}, st, t, &us_stage));
     // ---- set-up (meanfield.py:619-622): every evaluation's G covariance matrices in one launch, chol(K) and its inverse for
     // all of them in one factorisation, log det K, and K_j^-1 = X^T X for the nodes quirk Q1 needs
@@ -498,9 +516,12 @@ struct MidMaskLoan {
     MidMaskLoan(gprn_ctx* c, gprn_ctx* w_, const MidBatch* m) : w(w_)
     {
         w->d_mask = const_cast<uint8_t*>(m->mask);
-        for (int wt = 0; wt < 2; ++wt) w->mask_batch[wt] = m->mask && !m->mask_gps[wt].empty() ? mask_batch_of(c, wt) : MaskBatch{};
+        // (gprn_elbocalc_batch_heldout: the masks are the chunk's, one per evaluation -- the slabs' own, lent the same way)
+        w->mask_ev_stride = m->held ? (size_t)m->p * m->N : 0;
+        for (int wt = 0; wt < 2; ++wt)
+            w->mask_batch[wt] = !m->mask || m->mask_gps[wt].empty() ? MaskBatch{} : m->held ? m->kept.held.batch() : mask_batch_of(c, wt);
     }
-    ~MidMaskLoan() { w->d_mask = nullptr; w->mask_batch[0] = w->mask_batch[1] = MaskBatch{}; }
+    ~MidMaskLoan() { w->d_mask = nullptr; w->mask_ev_stride = 0; w->mask_batch[0] = w->mask_batch[1] = MaskBatch{}; }
 };
 
 // a chunk through the worker; an in-kernel dependency wait that gave up: both contexts go to the event schedule and the chunk
@@ -517,7 +538,7 @@ int mid_batch_run(gprn_ctx* c, const BatchIo& io)
 {
     MidBatch* m = (MidBatch*)c->mid_batch;
     mid_follow(c, m->w);
-    if (m->mask && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
+    if (m->mask && !m->held && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
     const MidMaskLoan loan(c, m->w, m);
     return mid_run(c, m->w, "elbocalc_batch", [&] { return mid_chunk(c, m, io); });
 }

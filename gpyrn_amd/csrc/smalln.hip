@@ -596,6 +596,11 @@ struct SmallBatchMem {
     // evaluation), per (evaluation, entry) WT and C of 128 x ld each, the lanes of mask.hip's batched rows -- one set per
     // parity, because mu_out / var_out alternate -- and the tile product's pointer rows
     const uint8_t* mask = nullptr;    // the mask the argument blocks were made for (null: none)
+    // gprn_elbocalc_batch_heldout: evaluation b's blocks point at ITS fit mask (kept.held.fit + b p N, which is `mask`), its lanes
+    // carry row b G + gp of the chunk's U tables; the entries and upad are the call's plan, which the buffers are keyed by
+    bool held = false;
+    std::vector<int> ent[2];
+    int upad = 0;
     int mask_ne[2] = {0, 0};
     double* mask_wc = nullptr;        // [cap][ne node + ne weight][2][128 * ld]
     MaskLane* mask_lanes = nullptr;   // [2 parity][cap ne node | cap ne weight], evaluation-major
@@ -629,10 +634,10 @@ void small_batch_free(gprn_ctx* c)
 static size_t small_bytes_per_eval(const gprn_ctx* c)
 {
     const SmallSlab v{small_shape(c, 1), nullptr, nullptr, nullptr, nullptr};
-    const size_t ne = batch_mask_entries(c, false).size() + batch_mask_entries(c, true).size();   // (WT and C per entry)
-    // (the slabs; the pinned images of the state and of y - mean | variance; scalars and control words)
+    const size_t ne = batch_plan_entries(c, false).size() + batch_plan_entries(c, true).size();   // (WT and C per entry)
+    // (the slabs; the pinned images of the state and of y - mean | variance; scalars and control words; per-evaluation masks)
     return (v.per_eval() + 2 * v.d() + 2 * v.pn() + 256 + ne * 2 * GPRN_TILE * c->ld) * sizeof(double) +
-           (size_t)c->G * fill_program_bytes() * 2 + ne * 2 * sizeof(MaskLane);
+           (size_t)c->G * fill_program_bytes() * 2 + ne * 2 * sizeof(MaskLane) + held_bytes_per_eval(c);
 }
 
 // evaluations one chunk may hold: what the memory budget pays for (4 G + q matrices of ld^2 doubles each and small change
@@ -641,7 +646,7 @@ static int small_batch_chunk(gprn_ctx* c)
 {
     const size_t per = small_bytes_per_eval(c);
     // (grid y = evaluations; under a mask the rows' launches have evaluations x entries of a phase in grid y / z: below 65 535)
-    const size_t ne = std::max<size_t>(1, std::max(batch_mask_entries(c, false).size(), batch_mask_entries(c, true).size()));
+    const size_t ne = std::max<size_t>(1, std::max(batch_plan_entries(c, false).size(), batch_plan_entries(c, true).size()));
     return (int)std::max<size_t>(16, std::min<size_t>(batch_budget_bytes(c) / per, std::min<size_t>(32768, 65535 / ne)));
 }
 
@@ -650,15 +655,21 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
     SmallBatchMem* m = (SmallBatchMem*)c->small_batch;
     const int G = c->G, q = c->q, p = c->p, N = c->N, ld = c->ld;
     const SmallShape held = small_shape(c, m ? m->cap : 0);    // (what the buffers must be for, at their capacity)
-    if (m && m->cap >= n_eval && !memcmp(&m->v.s, &held, sizeof held) && m->mask == c->d_mask) return GPRN_OK;
+    const bool per_eval = c->held != nullptr;                  // (gprn_elbocalc_batch_heldout: a fit mask per evaluation)
+    const std::vector<int> ent[2] = {batch_plan_entries(c, false), batch_plan_entries(c, true)};
+    const bool same_mask = m && m->held == per_eval &&
+                           (per_eval ? m->ent[0] == ent[0] && m->ent[1] == ent[1] && m->upad == batch_plan_upad(c) : m->mask == c->d_mask);
+    if (m && m->cap >= n_eval && !memcmp(&m->v.s, &held, sizeof held) && same_mask) return GPRN_OK;
     small_batch_free(c);
     m = new SmallBatchMem();
     c->small_batch = m;
     const int cap = std::max(n_eval, 16);
     SmallSlab& v = m->v;
     v.s = small_shape(c, cap);
-    m->mask = c->d_mask;
-    const std::vector<int> ent[2] = {batch_mask_entries(c, false), batch_mask_entries(c, true)};
+    m->held = per_eval; m->ent[0] = ent[0]; m->ent[1] = ent[1]; m->upad = batch_plan_upad(c);
+    if (per_eval) TRY(m->kept.held.make(c, m->own, cap, 1, ld));
+    m->mask = per_eval ? m->kept.held.fit : c->d_mask;
+    const size_t pn_mask = per_eval ? (size_t)p * N : 0;       // bytes from one evaluation's mask to the next one's
     const size_t ne0 = ent[0].size(), ne_all = ne0 + ent[1].size(), wc = (size_t)GPRN_TILE * ld;
     m->mask_ne[0] = (int)ne0; m->mask_ne[1] = (int)ent[1].size();
     const size_t nscal = 3 * (size_t)G + (size_t)q * q, nptr = 3 * (size_t)G * GPRN_NBUF + q + 2 * (size_t)G;
@@ -734,14 +745,15 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
                     mu_in, var_in, mu_out, var_out, ctl,
                     v.vec(b, SV_D, s0), v.vec(b, SV_S, s0), v.vec(b, SV_PRED, s0), v.vec(b, SV_Z, s0), v.vec(b, SV_U, s0),
                     v.vec(b, SV_CS, s0), v.vec(b, SV_CT, s0),
-                    scal + G, scal, info + (size_t)(1 + ph) * G, nullptr, c->d_mask};
+                    scal + G, scal, info + (size_t)(1 + ph) * G, nullptr, m->mask ? m->mask + b * pn_mask : nullptr};
                 // the lanes of the rows behind this half-sweep: evaluation-major, so that B evaluations are a prefix
                 const size_t ne = ent[ph].size(), first = ph ? (size_t)cap * ne0 : 0;
                 for (size_t e = 0; e < ne; ++e) {
                     const int g = ent[ph][e];
                     double* const wt = m->mask_wc + (((size_t)b * ne_all + (ph ? ne0 : 0) + e) * 2) * wc;
                     ml[(size_t)par * cap * ne_all + first + (size_t)b * ne + e] =
-                        MaskLane{v.K(b, g), v.vec(b, SV_S, g), v.vec(b, SV_CT, g), wt, wt + wc, mu_out, var_out, ctl, g};
+                        MaskLane{v.K(b, g), v.vec(b, SV_S, g), v.vec(b, SV_CT, g), wt, wt + wc, mu_out, var_out, ctl, g,
+                                 per_eval ? b * G + g : g};
                     buf_row(mt.data() + (first + (size_t)b * ne + e) * GPRN_NBUF, v.B(b, g), v.X(b, g), wt, wt + wc);
                 }
             }
@@ -749,7 +761,7 @@ static int small_batch_ensure(gprn_ctx* c, int n_eval)
                 (double* const*)d_node, (double* const*)d_weight, m->gp_ids, m->gp_ids + q, q, G - q, N, ld, p, q, G,
                 mu_out, var_out, bound ? yres : c->d_yraw, variance, v.vec(b, SV_S, 0), (double* const*)d_kinv_tab, v.vec(b, SV_U, 0), m->logdetK + (size_t)b * G,
                 scal, m->out4 + (size_t)b * 4, m->ticket + b, ctl, m->hist + (size_t)b * (SB_K + 4),
-                m->hist + (size_t)b * (SB_K + 4) + SB_K, 0, 0, 0, info, 3 * G, c->d_mask};
+                m->hist + (size_t)b * (SB_K + 4) + SB_K, 0, 0, 0, info, 3 * G, m->mask ? m->mask + b * pn_mask : nullptr};
         }
         pr[b] = SmallPriorArgs{(double* const*)d_setup, m->gp_ids, (double* const*)d_kinv_out, N, ld, m->logdetK + (size_t)b * G, info};
     }
@@ -783,8 +795,8 @@ int small_batch_reserve(gprn_ctx* c, int want, int* cap)
 // One sweep of B evaluations side by side: small_sweep's sequence (api_sweep.hip) with grid y = evaluation -- node half-sweep,
 // weight half-sweep, tail, no host step between them.  par: the state copy the sweep starts from (its argument blocks, which
 // hold each evaluation's own loop words); sweep, hist_at: its number and its place in the group's ELBO history.
-// Under a data mask -- m->mask, which small_batch_ensure keeps the context's -- the masked kernels, and behind each half-sweep
-// the rows U of its entries for all B evaluations.
+// Under a data mask -- m->mask, which small_batch_ensure keeps the context's, or under gprn_elbocalc_batch_heldout the chunk's
+// per-evaluation fit masks -- the masked kernels, and behind each half-sweep the rows U of its entries for all B evaluations.
 static int small_batch_sweep(gprn_ctx* c, SmallBatchMem* m, int B, int par, int sweep, int hist_at, int max_iter, bool forced)
 {
     const int G = c->G, q = c->q, cap = m->cap;
@@ -801,7 +813,7 @@ static int small_batch_sweep(gprn_ctx* c, SmallBatchMem* m, int B, int par, int 
     auto rows_u = [&](int ph) -> int {
         if (!m->mask_ne[ph]) return GPRN_OK;
         const size_t first = ph ? (size_t)cap * m->mask_ne[0] : 0;
-        MaskBatch mb = mask_batch_of(c, ph);
+        MaskBatch mb = m->held ? m->kept.held.batch() : mask_batch_of(c, ph);
         mb.lanes = m->mask_lanes + (size_t)par * cap * ne_all + first; mb.tab = m->mask_tab + first * GPRN_NBUF;
         mb.n = B * m->mask_ne[ph];
         return mask_rows_lanes(c, mb, c->N, c->ld);
@@ -862,6 +874,8 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     const double us_ensure = m->us_reserve;
     m->us_reserve = 0.0;
     hipStream_t st = c->stream;
+    if (m->held) TRY(m->kept.held.upload(c, io.held, B, st));   // (this chunk's fit masks and their rows U)
+    else if (m->mask && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
     TRY(batch_stage(c, io, m->pin_in, cap, BatchBufs{m->programs, m->v.yres(0), m->v.variance(0), m->v.state(0, 0), m->v.state(1, 0)},
                     st, t, &us_stage));
     HIP_TRY(c, hipMemsetAsync(m->ctl, 0, (size_t)B * 4 * sizeof(int), st));
@@ -881,7 +895,6 @@ int small_batch_run(gprn_ctx* c, const BatchIo& io)
     // same input; it runs once, as trip 1.  Only max_iter = 0 enqueues sweep 0.)
     int s = max_iter >= 1 ? 1 : 0;
     bool all_done = false;
-    if (m->mask && !c->mask_ready) return bad(c, "elbocalc_batch: the data mask's buffers are not set up");
     while (!all_done && s <= max_iter) {
         const int s0 = s;
         int nb = 0;

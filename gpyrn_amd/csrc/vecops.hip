@@ -50,13 +50,14 @@ void k_prep_nodes(const int* __restrict__ slot_gp, int N, int ld, int p, int q,
                   const double* __restrict__ mu, const double* __restrict__ var,
                   const double* __restrict__ yres, const double* __restrict__ variance,
                   double* __restrict__ d, double* __restrict__ s, double* __restrict__ pred,
-                  double* __restrict__ z, EvalMap ev, const uint8_t* __restrict__ mask)
+                  double* __restrict__ z, EvalMap ev, const uint8_t* __restrict__ mask, size_t mask_stride)
 {
     const int slot = blockIdx.y, j = slot_gp[slot];
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= ld) return;
     const size_t eb = ev_of(ev, slot);               // (several evaluations side by side: this slot's copy of the problem)
     mu += eb * ev.state; var += eb * ev.state; yres += eb * ev.yv; variance += eb * ev.yv;
+    if (MASKED) mask += eb * mask_stride;            // (0: the data's one mask; else the slot's evaluation's own)
     double dsum = 1.0, psum = 0.0;
     if (n < N) {
         dsum = 0.0;
@@ -87,7 +88,7 @@ void k_prep_weights(const int* __restrict__ slot_gp, int N, int ld, int p, int q
                     const double* __restrict__ mu, const double* __restrict__ var,
                     const double* __restrict__ yres, const double* __restrict__ variance,
                     double* __restrict__ d, double* __restrict__ s, double* __restrict__ pred,
-                    double* __restrict__ z, EvalMap ev, const uint8_t* __restrict__ mask)
+                    double* __restrict__ z, EvalMap ev, const uint8_t* __restrict__ mask, size_t mask_stride)
 {
     const int slot = blockIdx.y, kk = slot_gp[slot] - q;
     const int j = kk / p, i = kk % p;
@@ -95,6 +96,7 @@ void k_prep_weights(const int* __restrict__ slot_gp, int N, int ld, int p, int q
     if (n >= ld) return;
     const size_t eb = ev_of(ev, slot);
     mu += eb * ev.state; var += eb * ev.state; yres += eb * ev.yv; variance += eb * ev.yv;
+    if (MASKED) mask += eb * mask_stride;
     double dv = 1.0, pv = 0.0;
     if (MASKED && n < N && !mask[(size_t)i * N + n]) {
         const size_t o = (size_t)slot * ld + n;
@@ -462,7 +464,7 @@ __global__ __launch_bounds__(256)
 void k_loglike_partial(int N, int p, int q, const double* __restrict__ mu, const double* __restrict__ var,
                        const double* __restrict__ yraw, const double* __restrict__ variance,
                        double* __restrict__ part /* [ELBO_BLOCKS][3] */, const int* __restrict__ evals, EvalMap ev,
-                       const uint8_t* __restrict__ mask)
+                       const uint8_t* __restrict__ mask, size_t mask_stride)
 {
     __shared__ double sh[4];
     const double TWO_PI = 6.283185307179586;
@@ -470,6 +472,7 @@ void k_loglike_partial(int N, int p, int q, const double* __restrict__ mu, const
     const size_t eb = evals ? (size_t)evals[blockIdx.y] : 0;
     mu += eb * ev.state; var += eb * ev.state; variance += eb * ev.yv;
     if (BOUND) yraw += eb * ev.yv;
+    if (MASKED) mask += eb * mask_stride;            // (0: the data's one mask; else the evaluation's own)
     part += (size_t)blockIdx.y * 3 * ELBO_BLOCKS;
     double t1 = 0.0, t2 = 0.0, t3 = 0.0;
     for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += 256 * ELBO_BLOCKS) {
@@ -547,7 +550,7 @@ int vec_prep(gprn_ctx* c, const Phase& ph, bool weights)
     auto go = [&](auto kernel) {                              // (two kernels, one argument list)
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, ph.slot_gp, ph.N, ph.ld,
                            c->p, c->q, c->d_mu, c->d_var, c->d_yres, c->d_variance,
-                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev, (const uint8_t*)c->d_mask);
+                           c->d_d + o, c->d_s + o, c->d_pred + o, c->d_z + o, ph.ev, (const uint8_t*)c->d_mask, c->mask_ev_stride);
     };
     with_flags([&](auto M) { if (weights) go(k_prep_weights<M>); else go(k_prep_nodes<M>); }, c->d_mask != nullptr);
     LAUNCH_END(c);
@@ -683,10 +686,12 @@ int vec_elbo_evals(gprn_ctx* c, const EvalMap& ev, const int* d_evals, int n, do
     if (!n) return GPRN_OK;
     if (!stream) stream = c->stream;
     prof_begin(c, GPRN_T_VEC, stream);
-    // (the mask is the data's: one for all evaluations; the bound form's residual is the evaluation's own, stride ev.yv)
+    // (the mask is the data's, one for all evaluations -- or, under gprn_elbocalc_batch_heldout, the evaluation's own,
+    // mask_ev_stride bytes apart; the bound form's residual is the evaluation's own, stride ev.yv)
     with_flags([&](auto M, auto B) {
         hipLaunchKernelGGL((k_loglike_partial<M, B>), dim3(ELBO_BLOCKS, n), dim3(256), 0, stream, c->N, c->p, c->q,
-                           c->d_mu, c->d_var, B ? c->d_yres : c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)c->d_mask);
+                           c->d_mu, c->d_var, B ? c->d_yres : c->d_yraw, c->d_variance, part, d_evals, ev, (const uint8_t*)c->d_mask,
+                           c->mask_ev_stride);
         hipLaunchKernelGGL(k_elbo_final<B>, dim3(n), dim3(64), 0, stream, c->N, c->p, c->q, part,
                            c->d_logdetK, scal, scal + c->G, scal + 2 * (size_t)c->G, scal + 3 * (size_t)c->G, out4, d_evals, ev);
     }, c->d_mask != nullptr, c->elbo_form == GPRN_ELBO_BOUND);

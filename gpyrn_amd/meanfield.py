@@ -22,6 +22,7 @@ emits the weight block node-major; ELBO = (LogL + LogP + Ent) / q.
 """
 import os
 import time as time_module
+from collections import namedtuple
 from itertools import chain
 
 import numpy as np
@@ -36,6 +37,18 @@ _TINY_NUGGET = 1.25e-12 # meanfield.py:450
 _TWO_ARGUMENT = (covfunc.HarmonicPeriodic, covfunc.QuasiHarmonicPeriodic,
                  covfunc.Polynomial)          # meanfield.py:426-428
 _NOT_SET = 'GPRN components not set, use set_components'
+
+# what inference.heldout_batch and inference.cross_validate return (see there)
+HeldOut = namedtuple('HeldOut', 'lpd n_held mean var elbo iterations converged info state_mu state_var')
+CrossValidation = namedtuple('CrossValidation', 'lpd elpd n_held mean var elbo iterations converged info')
+
+
+class _Folds(np.ndarray):
+    """The (k, p, N) fit masks of ``inference.cv_folds`` with ``n_never_held``: observed entries that no fold holds out."""
+    n_never_held = 0
+
+    def __array_finalize__(self, obj):
+        self.n_never_held = getattr(obj, 'n_never_held', 0)
 
 
 class inference:
@@ -1351,12 +1364,13 @@ class inference:
             self._mu, self._var = mu_f[done[-1]], var_f[done[-1]]
         return res
 
-    def _batch_stage(self, sets, start=None):
+    def _batch_stage(self, sets, start=None, own_masks=False):
         """The B problems of a side-by-side call laid out for ``Context.elbocalc_batch``: ``(ctx, kernel_params (B, n_kpar),
         y_resid (B, p N), jitters (B, p), mu (B, d), var (B, d))``, every evaluation starting from ``start`` = ``(mu, var)``,
         else the stored state, else ``_initMuVar`` of its own parameters -- or None where the side-by-side form does not
-        apply.  The kernel programs go to the device; the object's parameters end at the last vector."""
-        if self._comm is not None or self.N > self.batch_max_N or self._mask_bars_batch():
+        apply.  The kernel programs go to the device; the object's parameters end at the last vector.  ``own_masks``: the
+        call brings a fit mask per evaluation (``heldout_batch``), so a data mask does not bar it."""
+        if self._comm is not None or self.N > self.batch_max_N or (self._mask_bars_batch() and not own_masks):
             return None
         ctx = self._backend()
         ctx.option('batch_mask', 1 if self.batch_under_mask else 0)   # (every call: the attribute may have changed)
@@ -2283,6 +2297,185 @@ class inference:
         if keep is not None:
             self._mu, self._var = keep
         return values, grads
+
+    # ------------------------------------------------ held-out scores: cross-validation side by side
+    def _data_mask(self):
+        """The object's data mask as a (p, N) bool array (all True without one)."""
+        return np.ones((self.p, self.N), dtype=bool) if self.mask is None else np.asarray(self.mask, dtype=bool)
+
+    def _check_fit_masks(self, fit_masks, B, what):
+        """(B, p, N) bool fit masks under the data mask that obey the mask's own rules, or a ``ValueError`` naming the
+        evaluation -- before anything touches a device."""
+        fit = np.asarray(fit_masks)
+        if fit.shape != (B, self.p, self.N):
+            raise ValueError(f'{what}: fit_masks must have shape (B, p, N) = {(B, self.p, self.N)}, got {fit.shape}')
+        fit = fit.astype(bool)
+        D = self._data_mask()
+        for b in range(B):
+            if np.any(fit[b] & ~D):
+                raise ValueError(f'{what}: fit mask {b} fits an entry the data mask does not hold')
+            empty = np.flatnonzero(~fit[b].any(axis=1))
+            if empty.size:
+                raise ValueError(f'{what}: fit mask {b} leaves output(s) {empty.tolist()} without a fitted entry')
+            if self.q >= 2:
+                gaps = np.flatnonzero(~fit[b].any(axis=0))
+                if gaps.size:
+                    raise ValueError(f'{what}: fit mask {b} leaves time index(es) {gaps[:10].tolist()} without a fitted '
+                                     f'output (q >= 2 needs one at every time)')
+        return fit
+
+    def heldout_batch(self, parameter_sets, fit_masks, max_iter=None, sweeps=None, start=None):
+        """
+        Fit vector b of ``parameter_sets`` on the entries ``fit_masks[b]`` (p, N; True = fitted) and score the rest: the
+        held-out log predictive density, all evaluations SIDE BY SIDE on the GPU (``gprn_elbocalc_batch_heldout``) --
+        k folds x S vectors of a cross-validation in one call.  Not in the reference, whose only model score is the ELBO.
+
+        Every fit mask lies under the object's data mask D and obeys its rules (an entry per output; with q >= 2 an output
+        at every time); evaluation b holds out ``D & ~fit_masks[b]``.  ``sweeps=n``: exactly n forced sweeps, no stop rule,
+        as in ``nELBO_and_grad_batch``; else the loop under the stop rule, ``max_iter`` trips at most.  Each evaluation
+        starts from ``_initMuVar`` on y zero-filled under ITS fit mask -- what a fresh object with ``mask=fit_masks[b]``
+        starts from, so that no held-out value leaks into the start -- or, with ``start=(mu, var)``, from that state.
+
+        Returns a ``HeldOut`` record: ``lpd`` (B, p) and ``n_held`` (B, p), the log predictive density summed over the
+        held-out entries of each output and their number; ``mean`` and ``var`` (B, p, N), the predictive mean (mean
+        functions included) and variance (jitter once, yerr^2 included) at the held-out entries, zero elsewhere; ``elbo``,
+        ``iterations``, ``converged``, ``info`` (B,) and ``state_mu``, ``state_var`` -- row b what ``ELBOcalc`` returns on an
+        object with ``mask=fit_masks[b]``.  An evaluation whose factorisation failed has NaN in ``elbo``, ``lpd`` and rows.
+
+        Where the side-by-side form does not apply this raises ``NotImplementedError`` with the reason -- a sharded
+        object, user-defined kernels, ``sweep_order='sequential'``, N above ``batch_max_N``; there is no silent one-by-one
+        fallback.  The object's stored state is left alone; its parameters end at the last vector.
+        """
+        what = 'heldout_batch'
+        assert self._components_set, _NOT_SET
+        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        B = len(sets)
+        if B < 1:
+            raise ValueError(f'{what}: no parameter vector')
+        if any(x.ndim != 1 for x in sets):
+            raise ValueError(f'{what}: one-dimensional parameter vectors expected')
+        fit = self._check_fit_masks(fit_masks, B, what)
+        forced = sweeps is not None
+        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
+        if trips < 1:
+            raise ValueError(f'{what}: a held-out score needs at least one committed sweep')
+        if start is not None and (len(start) != 2 or np.size(start[0]) != self.d or np.size(start[1]) != self.d):
+            raise ValueError(f'{what}: start must be (mu, var) of {self.d} values each')
+        if self._comm is not None:
+            raise NotImplementedError(f'{what} is not available on a sharded inference object')
+        if self._sweep_order != 'reference':
+            raise NotImplementedError(f"{what}: per-evaluation fit masks are not supported under sweep_order='sequential'")
+        if self.N > self.batch_max_N:
+            raise NotImplementedError(f'{what}: N = {self.N} is above batch_max_N = {self.batch_max_N}, the largest problem '
+                                      'the side-by-side form takes')
+        nodes, weights, _, _ = self._get_components()
+        if any(self._kernel_spec(k)[0] != 'device' for k in chain(nodes, weights)):
+            raise NotImplementedError(f'{what} needs a device program for every kernel: user-defined kernels (and sums '
+                                      'that hold a two-argument kernel) are not supported')
+        placeholder = (np.zeros(self.d), np.ones(self.d))
+        staged = self._batch_stage(sets, start=placeholder if start is None else start, own_masks=True)
+        if staged is None:
+            raise NotImplementedError(f'{what}: the vectors cannot be laid out side by side (lengths that differ, or kernel '
+                                      'expressions that change shape between vectors)')
+        ctx, kp, yr, jt, m0, v0 = staged
+        if start is None:
+            y_all = self.y
+            try:
+                for b, x in enumerate(sets):
+                    self.set_parameters(x)
+                    nodes, weights, _, jitters = self._get_components()
+                    self.y = np.where(fit[b], y_all, 0.0)
+                    mu, var = self._initMuVar(nodes, weights, jitters)
+                    m0[b], v0[b] = np.ravel(mu), np.ravel(var)
+            finally:
+                self.y = y_all
+        res = ctx.elbocalc_batch_heldout(kp, yr, jt, m0, v0, trips, fit, forced=forced)
+        if res is None:
+            raise NotImplementedError(f'{what}: the library has no side-by-side form for this problem')
+        elbo, iters, conv, info, mu_f, var_f, hmean, hvar, lpd, n_held = res
+        self.last_info = int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
+        held = self._data_mask()[None] & ~fit
+        hmean = np.where(held, hmean + self._mean_values_batch(sets, np.asarray(self.time, dtype=float)), hmean)
+        return HeldOut(lpd=lpd, n_held=n_held, mean=hmean, var=hvar, elbo=elbo, iterations=iters, converged=conv, info=info,
+                       state_mu=mu_f, state_var=var_f)
+
+    def cv_folds(self, k, scheme='entries', block=None, rng=None):
+        """
+        ``k`` fit masks (k, p, N) under the object's data mask for a k-fold cross-validation: fold f fits everything but
+        the observed entries assigned to it.
+
+        * ``scheme='entries'``: entry (i, n) goes to fold (r_n + i) mod k with a seeded r_n per time, so that (with p <= k)
+          two outputs of one time never share a fold;
+        * ``scheme='blocks'``: per output, contiguous runs of ``block`` times (default: about N / (2 k)) go to one fold, run
+          r of output i to fold (r + i + r_0) mod k -- whole seasons are held out, the runs of the outputs offset.
+
+        Every observed entry is held out in exactly one fold, except those whose removal would break the mask's rules -- the
+        only fitted entry of an output, or with q >= 2 the only observed output of a time: they stay fitted in every fold
+        and are counted in the result's ``n_never_held``.  ``rng``: a seed or a ``numpy.random.RandomState``.
+        ``ValueError`` where no valid split exists: k < 2, or q >= 2 with p = 1.
+        """
+        k = int(k)
+        if k < 2:
+            raise ValueError('cv_folds: k >= 2 folds expected')
+        if self.q >= 2 and self.p == 1:
+            raise ValueError('cv_folds: with q >= 2 every time needs a fitted output, and with p = 1 nothing can be held out')
+        if scheme not in ('entries', 'blocks'):
+            raise ValueError(f"cv_folds: scheme must be 'entries' or 'blocks', got {scheme!r}")
+        rs = rng if isinstance(rng, np.random.RandomState) else np.random.RandomState(rng)
+        D = self._data_mask()
+        i_idx, n_idx = np.arange(self.p)[:, None], np.arange(self.N)[None, :]
+        if scheme == 'entries':
+            fold = (rs.randint(0, k, size=self.N)[None, :] + i_idx) % k
+        else:
+            block = max(1, self.N // (2 * k)) if block is None else int(block)
+            if block < 1:
+                raise ValueError('cv_folds: block >= 1 times expected')
+            fold = (n_idx // block + i_idx + rs.randint(0, k)) % k
+        hold = np.array([D & (fold == f) for f in range(k)])
+        for f in range(k):
+            fitted = D & ~hold[f]
+            if self.q >= 2:                                    # a time whose observed outputs all went to this fold keeps its first
+                for n in np.flatnonzero(D.any(axis=0) & ~fitted.any(axis=0)):
+                    hold[f, np.flatnonzero(D[:, n])[0], n] = False
+            fitted = D & ~hold[f]
+            for i in np.flatnonzero(~fitted.any(axis=1)):       # an output with nothing left keeps its first observed entry
+                hold[f, i, np.flatnonzero(D[i])[0]] = False
+        folds = (D[None] & ~hold).view(_Folds)
+        folds.n_never_held = int((D & ~hold.any(axis=0)).sum())
+        return folds
+
+    def cross_validate(self, folds, parameter_sets=None, **kw):
+        """
+        k-fold cross-validation of S parameter vectors in ONE side-by-side call: the S x k evaluations, set-major, through
+        ``heldout_batch`` (whose keywords ``max_iter``, ``sweeps``, ``start`` pass through).  ``folds``: (k, p, N) fit masks,
+        as ``cv_folds`` returns them; ``parameter_sets``: default the object's current vector.
+
+        Returns a ``CrossValidation`` record: ``lpd`` (S, k, p) and ``n_held`` (S, k, p); ``elpd`` (S,), the sum of ``lpd``
+        over folds and outputs -- the score to compare models by; ``mean`` and ``var`` (S, p, N), each entry from the fold
+        that held it out, NaN where no fold did; ``elbo``, ``iterations``, ``converged``, ``info`` (S, k).
+        """
+        folds = np.asarray(folds)
+        if folds.ndim != 3 or folds.shape[1:] != (self.p, self.N) or folds.shape[0] < 1:
+            raise ValueError(f'cross_validate: folds must have shape (k, p, N) = (k, {self.p}, {self.N}), got {folds.shape}')
+        folds = folds.astype(bool)
+        k = folds.shape[0]
+        sets = [np.array(self.get_parameters(), dtype=float)] if parameter_sets is None else \
+            [np.array(x, dtype=float) for x in parameter_sets]
+        S = len(sets)
+        if S < 1:
+            raise ValueError('cross_validate: no parameter vector')
+        res = self.heldout_batch([x for x in sets for _ in range(k)], np.tile(folds, (S, 1, 1)), **kw)
+        held = self._data_mask()[None] & ~folds                  # (k, p, N)
+        mean = np.full((S, self.p, self.N), np.nan)
+        var = np.full((S, self.p, self.N), np.nan)
+        rm, rv = res.mean.reshape(S, k, self.p, self.N), res.var.reshape(S, k, self.p, self.N)
+        for f in range(k):
+            mean[:, held[f]] = rm[:, f][:, held[f]]
+            var[:, held[f]] = rv[:, f][:, held[f]]
+        lpd = res.lpd.reshape(S, k, self.p)
+        return CrossValidation(lpd=lpd, elpd=lpd.sum(axis=(1, 2)), n_held=res.n_held.reshape(S, k, self.p), mean=mean, var=var,
+                               elbo=res.elbo.reshape(S, k), iterations=res.iterations.reshape(S, k),
+                               converged=res.converged.reshape(S, k), info=res.info.reshape(S, k))
 
     def mcmc(self, priors, p0=None, vars=None, niter=500, **kwargs):
         """

@@ -531,6 +531,44 @@ int gprn_elbocalc_batch_draws(gprn_ctx* ctx, int n_eval, const double* kernel_pa
                               double* elbo, int* iterations, int* converged, int* info, double* mu_out, double* var_out,
                               double* lat_draws, double* out_draws, double* nugget_out, int* draw_info);
 
+/* gprn_elbocalc_batch_grad(grad_out = NULL) with a FIT MASK PER EVALUATION and, per evaluation, the log predictive density of
+ * what it held out -- k folds x S parameter vectors of a cross-validation in one call, where one by one each fold costs a
+ * gprn_set_mask, a re-factorisation, gprn_elbocalc and a prediction.
+ *   fit_mask [n_eval][p][N], bytes, non-zero = fitted.  With D the context's data mask (gprn_set_mask; all ones without one)
+ *       every fit_mask[b] must be <= D and obey gprn_set_mask's own rules (a fitted entry in every output; with q >= 2 a
+ *       fitted output at every time): else GPRN_E_ARG, the message names the evaluation, and nothing has been launched.
+ *       H_b = D and not fit_mask[b] is what evaluation b holds out.
+ *   elbo, iterations, converged, info, mu_out, var_out: row b is what gprn_elbocalc returns on this context after
+ *       gprn_set_mask(fit_mask[b]) for vector b from (mu_b, var_b).  flags: as gprn_elbocalc_batch_grad (GPRN_BATCH_FORCED).
+ *   held_mean, held_var [n_eval][p][N] (or both NULL), lpd [n_eval][p], n_held [n_eval][p]: from the state of evaluation b's
+ *       last committed sweep, whose rows at held-out entries are the imputed ones csrc/mask.hip wrote.  On H_b
+ *           m_in = sum_j mu_f_j(n) mu_w_ij(n),
+ *           v_in = sum_j [mu_w_ij^2 var_f_j + var_w_ij (var_f_j + mu_f_j^2)] + jitter_bi^2 + yerr_in^2
+ *       (the jitter once, as in the variational prediction; yerr^2 the context's, from gprn_set_data; the mean functions are the
+ *       caller's to add to m), lpd[b][i] = sum_{n in H_b} -1/2 [log(2 pi v_in) + (y_resid[b][i][n] - m_in)^2 / v_in], n_held
+ *       [b][i] = |H_b| in output i, and the two rows are m and v on H_b, 0 elsewhere.  Every sum runs in a fixed order: two
+ *       calls return the same bits.  No fill, no factorisation and no tile product: the pass reads the state alone
+ *       (csrc/batch_tail.hip k_heldout_tail, one workgroup per (evaluation, output), behind each chunk's loop).
+ * An evaluation with info > 0 gets a NaN ELBO, NaN lpd and NaN in both of its rows; the others are untouched.  An entry outside
+ * D may hold NaN or inf in y_resid or yerr: it reaches no arithmetic.
+ * On the device every evaluation's kernels read ITS mask (one tile: its argument blocks; above: the masked instantiations of
+ * k_prep_nodes / k_prep_weights and k_loglike_partial add slot_eval x p N to the mask's address) and the rows U behind each
+ * half-sweep come from a table with one row per (evaluation, latent GP); the lanes of a phase cover the latent GPs with a U in
+ * any evaluation of the call, a lane whose own U is empty does nothing, and upad is the call's largest |U| rounded up to 128.
+ * Works with or without a data mask of the context's own and does not need option "batch_mask"; both forms of the ELBO; chunks
+ * and halving under "batch_mem_mb" with the per-evaluation WT / C slabs, masks and U tables counted ("batch_chunk" reports the
+ * chunk).  The buffers kept between side-by-side calls are keyed by the call's plan: a call with other entries or another upad,
+ * or a gprn_elbocalc_batch* call in between, builds them again.  The context's own state, factors, mask and validity flags are
+ * not touched: a gprn_sweep right after the call returns the bits it would have returned before it.
+ * GPRN_E_ARG: max_iter < 1 (no committed sweep), fit_mask, lpd or n_held NULL, the row pair half given, unknown flag bits, a
+ * fit mask that breaks the rules above.  Refusals (GPRN_E_UNSUPPORTED) are gprn_elbocalc_batch's (a communicator, uploaded
+ * kernels, a program that is not even in t_i - t_j, a one-tile problem with the small path off) and the sequential sweep order. */
+int gprn_elbocalc_batch_heldout(gprn_ctx* ctx, int n_eval, const double* kernel_params, int n_kernel_params,
+                                const double* y_resid, const double* jitters, const double* mu, const double* var,
+                                int max_iter, int flags, const uint8_t* fit_mask,
+                                double* elbo, int* iterations, int* converged, int* info, double* mu_out, double* var_out,
+                                double* held_mean, double* held_var, double* lpd, int* n_held);
+
 /* gprn_predict for n_eval parameter vectors side by side -- the posterior predictive of a chain: the reference's
  * inference._Prediction (meanfield.py:1289-1381) over _gp.GP.prediction (_gp.py:107-138), once per hyper-parameter vector
  * that inference.mcmc kept.
