@@ -169,6 +169,62 @@ def _ptr(a):
     return a.ctypes.data_as(_dp)
 
 
+def _ip(a):
+    return a.ctypes.data_as(POINTER(c_int))
+
+
+def _opt(a):
+    return None if a is None else _ptr(a)
+
+
+# what the side-by-side wrappers (Context.elbocalc_batch*, predict_batch) share.  Plain functions of anything that has
+# p, q and N: the wrappers are also called unbound, on an object that holds the sizes and no handle.
+def _batch_inputs(ctx, kernel_params, mu, var, y_resid=None, jitters=None):
+    """kernel_params (B, n_kpar), mu / var (B, d) and, where given, y_resid (B, p, N) and jitters (B, p), checked and made
+    contiguous: ``(kp, yr, jt, m0, v0)``.  A ``MeanParams`` becomes y - mean through gprn_eval_mean: the entry points that
+    come here take a host array."""
+    kp = _f64(kernel_params)
+    if kp.ndim != 2 or kp.shape[0] < 1:
+        raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+    B = kp.shape[0]
+    d = (ctx.p + 1) * ctx.q * ctx.N
+    if isinstance(y_resid, MeanParams):
+        y_resid = y_resid.host_resid(ctx)
+    yr, jt = (None if a is None else _f64(a) for a in (y_resid, jitters))
+    m0, v0 = _f64(mu), _f64(var)
+    if yr is not None and yr.size != B * ctx.p * ctx.N:
+        raise ValueError(f'y_resid must be (B, p, N) = ({B}, {ctx.p}, {ctx.N}), got {yr.shape}')
+    if jt is not None and jt.size != B * ctx.p:
+        raise ValueError(f'jitters must be (B, p) = ({B}, {ctx.p}), got {jt.shape}')
+    if m0.size != B * d or v0.size != B * d:
+        raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
+    return kp, yr, jt, m0, v0
+
+
+def _batch_outputs(ctx, B, want_state=True):
+    """The six outputs every gprn_elbocalc_batch* entry fills: ``(elbo, iterations, converged, info, mu_out, var_out)``."""
+    d = (ctx.p + 1) * ctx.q * ctx.N
+    elbo = np.empty(B)
+    it, cv, info = (np.zeros(B, dtype=np.int32) for _ in range(3))
+    mo = np.empty((B, d)) if want_state else None
+    vo = np.empty((B, d)) if want_state else None
+    return elbo, it, cv, info, mo, vo
+
+
+def _batch_result(ctx, rc, what, outs, *tail):
+    """What a gprn_elbocalc_batch* wrapper returns: None where the library has no side-by-side form, else ``outs`` (as
+    ``_batch_outputs`` made them) as (elbo, iterations, converged, info[, states (B, p+1, q, N) twice]), then ``tail``."""
+    if rc == GPRN_E_UNSUPPORTED:
+        return None
+    ctx._check(rc, what)
+    elbo, it, cv, info, mo, vo = outs
+    head = (elbo, it.astype(int), cv.astype(bool), info.astype(int))
+    if mo is not None:
+        shape = (elbo.size, ctx.p + 1, ctx.q, ctx.N)
+        head += (mo.reshape(shape), vo.reshape(shape))
+    return head + tail
+
+
 def comm_unique_id():
     buf = ctypes.create_string_buffer(128)
     rc = load_library().gprn_comm_unique_id(buf)
@@ -502,7 +558,6 @@ class Context:
         d = (self.p + 1) * self.q * self.N
         mu_out, var_out = np.empty(d), np.empty(d)
         n, it, conv = c_int(0), c_int(0), c_int(0)
-        opt = lambda a, size: None if a is None else _ptr(_f64(np.ravel(a), (size,)))
         keep = [None if a is None else _f64(np.ravel(a)) for a in (y_resid, jitters, mu, var)]
         ptrs = [None if a is None else _ptr(a) for a in keep]
         if (keep[0] is not None and keep[0].size != self.p * self.N) or (keep[1] is not None and keep[1].size != self.p) or \
@@ -530,40 +585,24 @@ class Context:
         yr = None if means is not None else _f64(np.reshape(y_resid, (B, self.p * self.N)))
         jt = _f64(np.reshape(jitters, (B, self.p)))
         m0, v0 = _f64(np.reshape(mu, (B, d))), _f64(np.reshape(var, (B, d)))
-        elbo = np.empty(B)
-        it, cv, info = (np.zeros(B, dtype=np.int32) for _ in range(3))
-        mo = np.empty((B, d)) if want_state else None
-        vo = np.empty((B, d)) if want_state else None
-        ip = lambda a: a.ctypes.data_as(POINTER(c_int))
+        outs = elbo, it, cv, info, mo, vo = _batch_outputs(self, B, want_state)
         grads = np.zeros((B, kp.shape[1])) if want_grad else None
         if means is not None:
             means.resid = np.empty((B, self.p * self.N))
             means.mean_grad = np.zeros((B, means.params.shape[1])) if means.want_mean_grad and want_grad else None
             rc = self._lib.gprn_elbocalc_batch_means(self._h, B, _ptr(kp), kp.shape[1], _ptr(means.params), means.params.shape[1],
                                                      _ptr(jt), _ptr(m0), _ptr(v0), int(max_iter),
-                                                     GPRN_BATCH_FORCED if forced else 0, _ptr(elbo), ip(it), ip(cv), ip(info),
-                                                     _ptr(mo) if want_state else None, _ptr(vo) if want_state else None,
-                                                     _ptr(grads) if want_grad else None, _ptr(means.resid),
-                                                     None if means.mean_grad is None else _ptr(means.mean_grad))
+                                                     GPRN_BATCH_FORCED if forced else 0, _ptr(elbo), _ip(it), _ip(cv),
+                                                     _ip(info), _opt(mo), _opt(vo), _opt(grads), _ptr(means.resid),
+                                                     _opt(means.mean_grad))
         elif want_grad or forced:
             rc = self._lib.gprn_elbocalc_batch_grad(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
-                                                    int(max_iter), GPRN_BATCH_FORCED if forced else 0, _ptr(elbo), ip(it),
-                                                    ip(cv), ip(info), _ptr(mo) if want_state else None,
-                                                    _ptr(vo) if want_state else None, _ptr(grads) if want_grad else None)
+                                                    int(max_iter), GPRN_BATCH_FORCED if forced else 0, _ptr(elbo), _ip(it),
+                                                    _ip(cv), _ip(info), _opt(mo), _opt(vo), _opt(grads))
         else:
             rc = self._lib.gprn_elbocalc_batch(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
-                                               int(max_iter), _ptr(elbo), ip(it), ip(cv), ip(info),
-                                               _ptr(mo) if want_state else None, _ptr(vo) if want_state else None)
-        if rc == GPRN_E_UNSUPPORTED:
-            return None
-        self._check(rc, 'elbocalc_batch')
-        out = (elbo, it.astype(int), cv.astype(bool), info.astype(int))
-        if want_state:
-            shape = (B, self.p + 1, self.q, self.N)
-            out += (mo.reshape(shape), vo.reshape(shape))
-        if want_grad:
-            out += (grads,)
-        return out
+                                               int(max_iter), _ptr(elbo), _ip(it), _ip(cv), _ip(info), _opt(mo), _opt(vo))
+        return _batch_result(self, rc, 'elbocalc_batch', outs, *((grads,) if want_grad else ()))
 
     def elbocalc_batch_predict(self, kernel_params, y_resid, jitters, mu, var, max_iter, tstar, forced=False, latent=True,
                                outputs=True):
@@ -577,43 +616,24 @@ class Context:
         where the library has no side-by-side form for this problem."""
         if not (latent or outputs):
             raise ValueError('elbocalc_batch_predict: ask for the latent pair, the output pair or both')
-        kp = _f64(kernel_params)
-        if kp.ndim != 2 or kp.shape[0] < 1:
-            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        kp, yr, jt, m0, v0 = _batch_inputs(self, kernel_params, mu, var, y_resid, jitters)
         B = kp.shape[0]
-        d = (self.p + 1) * self.q * self.N
-        if isinstance(y_resid, MeanParams):                 # (this entry point takes a host array: y - mean through gprn_eval_mean)
-            y_resid = y_resid.host_resid(self)
-        yr, jt, m0, v0 = _f64(y_resid), _f64(jitters), _f64(mu), _f64(var)
-        if yr.size != B * self.p * self.N:
-            raise ValueError(f'y_resid must be (B, p, N) = ({B}, {self.p}, {self.N}), got {yr.shape}')
-        if jt.size != B * self.p:
-            raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
-        if m0.size != B * d or v0.size != B * d:
-            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
         ts = _f64(np.ravel(tstar))
         if ts.size < 1:
             raise ValueError('tstar is empty')
         if int(max_iter) < 1:
             raise ValueError('elbocalc_batch_predict: a prediction needs a committed sweep (max_iter >= 1)')
         ns = ts.size
-        elbo = np.empty(B)
-        it, cv, info = (np.zeros(B, dtype=np.int32) for _ in range(3))
-        mo, vo = np.empty((B, d)), np.empty((B, d))
+        outs = elbo, it, cv, info, mo, vo = _batch_outputs(self, B)
         lm = np.empty((B, self.G, ns)) if latent else None
         lv = np.empty((B, self.G, ns)) if latent else None
         om = np.empty((B, self.p, ns)) if outputs else None
         ov = np.empty((B, self.p, ns)) if outputs else None
-        ip = lambda a: a.ctypes.data_as(POINTER(c_int))
-        opt = lambda a: None if a is None else _ptr(a)
         rc = self._lib.gprn_elbocalc_batch_predict(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
                                                    int(max_iter), GPRN_BATCH_FORCED if forced else 0, ns, _ptr(ts), _ptr(elbo),
-                                                   ip(it), ip(cv), ip(info), _ptr(mo), _ptr(vo), opt(lm), opt(lv), opt(om), opt(ov))
-        if rc == GPRN_E_UNSUPPORTED:
-            return None
-        self._check(rc, 'elbocalc_batch_predict')
-        shape = (B, self.p + 1, self.q, self.N)
-        return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), lm, lv, om, ov)
+                                                   _ip(it), _ip(cv), _ip(info), _ptr(mo), _ptr(vo), _opt(lm), _opt(lv),
+                                                   _opt(om), _opt(ov))
+        return _batch_result(self, rc, 'elbocalc_batch_predict', outs, lm, lv, om, ov)
 
     def elbocalc_batch_heldout(self, kernel_params, y_resid, jitters, mu, var, max_iter, fit_masks, forced=False, rows=True):
         """B independent ELBOcalc loops side by side, evaluation b fitted under its OWN mask fit_masks[b] (p, N; True = fitted),
@@ -624,45 +644,24 @@ class Context:
         summed over the held-out entries of each output, (B, p), and their number.  Rows of an evaluation with info > 0 are
         NaN.  forced (GPRN_BATCH_FORCED): no stop rule, exactly max_iter committed sweeps each.  None where the library has
         no side-by-side form for this problem."""
-        kp = _f64(kernel_params)
-        if kp.ndim != 2 or kp.shape[0] < 1:
-            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        kp, yr, jt, m0, v0 = _batch_inputs(self, kernel_params, mu, var, y_resid, jitters)
         B = kp.shape[0]
-        d = (self.p + 1) * self.q * self.N
-        if isinstance(y_resid, MeanParams):
-            y_resid = y_resid.host_resid(self)
-        yr, jt, m0, v0 = _f64(y_resid), _f64(jitters), _f64(mu), _f64(var)
-        if yr.size != B * self.p * self.N:
-            raise ValueError(f'y_resid must be (B, p, N) = ({B}, {self.p}, {self.N}), got {yr.shape}')
-        if jt.size != B * self.p:
-            raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
-        if m0.size != B * d or v0.size != B * d:
-            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
         fm = np.asarray(fit_masks)
         if fm.shape != (B, self.p, self.N):
             raise ValueError(f'fit_masks must be (B, p, N) = ({B}, {self.p}, {self.N}), got {fm.shape}')
         fm = np.ascontiguousarray(fm != 0, dtype=np.uint8)
         if int(max_iter) < 1:
             raise ValueError('elbocalc_batch_heldout: a held-out score needs a committed sweep (max_iter >= 1)')
-        elbo = np.empty(B)
-        it, cv, info = (np.zeros(B, dtype=np.int32) for _ in range(3))
-        mo, vo = np.empty((B, d)), np.empty((B, d))
+        outs = elbo, it, cv, info, mo, vo = _batch_outputs(self, B)
         hm = np.empty((B, self.p, self.N)) if rows else None
         hv = np.empty((B, self.p, self.N)) if rows else None
         lpd = np.empty((B, self.p))
         nh = np.zeros((B, self.p), dtype=np.int32)
-        ip = lambda a: a.ctypes.data_as(POINTER(c_int))
-        opt = lambda a: None if a is None else _ptr(a)
         rc = self._lib.gprn_elbocalc_batch_heldout(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
                                                    int(max_iter), GPRN_BATCH_FORCED if forced else 0, fm.ctypes.data,
-                                                   _ptr(elbo), ip(it), ip(cv), ip(info), _ptr(mo), _ptr(vo), opt(hm), opt(hv),
-                                                   _ptr(lpd), ip(nh))
-        if rc == GPRN_E_UNSUPPORTED:
-            return None
-        self._check(rc, 'elbocalc_batch_heldout')
-        shape = (B, self.p + 1, self.q, self.N)
-        return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), hm, hv, lpd,
-                nh.astype(int))
+                                                   _ptr(elbo), _ip(it), _ip(cv), _ip(info), _ptr(mo), _ptr(vo), _opt(hm),
+                                                   _opt(hv), _ptr(lpd), _ip(nh))
+        return _batch_result(self, rc, 'elbocalc_batch_heldout', outs, hm, hv, lpd, nh.astype(int))
 
     def elbocalc_batch_draws(self, kernel_params, y_resid, jitters, mu, var, max_iter, tstar, z, forced=False, latent=True,
                              outputs=True):
@@ -678,20 +677,8 @@ class Context:
         side-by-side form for this problem."""
         if not (latent or outputs):
             raise ValueError('elbocalc_batch_draws: ask for the latent draws, the output draws or both')
-        kp = _f64(kernel_params)
-        if kp.ndim != 2 or kp.shape[0] < 1:
-            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        kp, yr, jt, m0, v0 = _batch_inputs(self, kernel_params, mu, var, y_resid, jitters)
         B = kp.shape[0]
-        d = (self.p + 1) * self.q * self.N
-        if isinstance(y_resid, MeanParams):                 # (this entry point takes a host array: y - mean through gprn_eval_mean)
-            y_resid = y_resid.host_resid(self)
-        yr, jt, m0, v0 = _f64(y_resid), _f64(jitters), _f64(mu), _f64(var)
-        if yr.size != B * self.p * self.N:
-            raise ValueError(f'y_resid must be (B, p, N) = ({B}, {self.p}, {self.N}), got {yr.shape}')
-        if jt.size != B * self.p:
-            raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
-        if m0.size != B * d or v0.size != B * d:
-            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
         ts = _f64(np.ravel(tstar))
         if ts.size < 1:
             raise ValueError('tstar is empty')
@@ -702,24 +689,16 @@ class Context:
         if int(max_iter) < 1:
             raise ValueError('elbocalc_batch_draws: a draw needs a committed sweep (max_iter >= 1)')
         nd = z.shape[2]
-        elbo = np.empty(B)
-        it, cv, info, dinfo = (np.zeros(B, dtype=np.int32) for _ in range(4))
-        mo, vo = np.empty((B, d)), np.empty((B, d))
+        outs = elbo, it, cv, info, mo, vo = _batch_outputs(self, B)
+        dinfo = np.zeros(B, dtype=np.int32)
         lat = np.empty((B, self.G, nd, ns)) if latent else None
         out = np.empty((B, self.p, nd, ns)) if outputs else None
         nug = np.zeros((B, self.G))
-        ip = lambda a: a.ctypes.data_as(POINTER(c_int))
-        opt = lambda a: None if a is None else _ptr(a)
         rc = self._lib.gprn_elbocalc_batch_draws(self._h, B, _ptr(kp), kp.shape[1], _ptr(yr), _ptr(jt), _ptr(m0), _ptr(v0),
                                                  int(max_iter), GPRN_BATCH_FORCED if forced else 0, ns, _ptr(ts), nd, _ptr(z),
-                                                 _ptr(elbo), ip(it), ip(cv), ip(info), _ptr(mo), _ptr(vo), opt(lat), opt(out),
-                                                 _ptr(nug), ip(dinfo))
-        if rc == GPRN_E_UNSUPPORTED:
-            return None
-        self._check(rc, 'elbocalc_batch_draws')
-        shape = (B, self.p + 1, self.q, self.N)
-        return (elbo, it.astype(int), cv.astype(bool), info.astype(int), mo.reshape(shape), vo.reshape(shape), lat, out, nug,
-                dinfo.astype(int))
+                                                 _ptr(elbo), _ip(it), _ip(cv), _ip(info), _ptr(mo), _ptr(vo), _opt(lat),
+                                                 _opt(out), _ptr(nug), _ip(dinfo))
+        return _batch_result(self, rc, 'elbocalc_batch_draws', outs, lat, out, nug, dinfo.astype(int))
 
     def predict_batch(self, kernel_params, mu, var, tstar, jitters=None, latent=True, outputs=True):
         """gprn_predict for B parameter vectors side by side (gprn_predict_batch): kernel_params (B, n_kpar), mu / var (B, d)
@@ -730,33 +709,21 @@ class Context:
         this problem (a communicator, a host-evaluated kernel, a kernel that is not even in t_i - t_j)."""
         if not (latent or outputs):
             raise ValueError('predict_batch: ask for the latent pair, the output pair or both')
-        kp = _f64(kernel_params)
-        if kp.ndim != 2 or kp.shape[0] < 1:
-            raise ValueError(f'kernel_params must be (B, n_kpar), got {kp.shape}')
+        if outputs and jitters is None:
+            raise ValueError('predict_batch: the output pair needs the jitters')
+        kp, _, jt, m0, v0 = _batch_inputs(self, kernel_params, mu, var, jitters=jitters if outputs else None)
         B = kp.shape[0]
-        d = (self.p + 1) * self.q * self.N
-        m0, v0 = _f64(mu), _f64(var)
-        if m0.size != B * d or v0.size != B * d:
-            raise ValueError(f'mu and var must hold (B, d) = ({B}, {d}) values each, got {m0.shape} and {v0.shape}')
         ts = _f64(np.ravel(tstar))
         if ts.size < 1:
             raise ValueError('tstar is empty')
-        jt = None
-        if outputs:
-            if jitters is None:
-                raise ValueError('predict_batch: the output pair needs the jitters')
-            jt = _f64(jitters)
-            if jt.size != B * self.p:
-                raise ValueError(f'jitters must be (B, p) = ({B}, {self.p}), got {jt.shape}')
         ns = ts.size
         lm = np.empty((B, self.G, ns)) if latent else None
         lv = np.empty((B, self.G, ns)) if latent else None
         om = np.empty((B, self.p, ns)) if outputs else None
         ov = np.empty((B, self.p, ns)) if outputs else None
         info = np.zeros(B, dtype=np.int32)
-        opt = lambda a: None if a is None else _ptr(a)
-        rc = self._lib.gprn_predict_batch(self._h, B, _ptr(kp), kp.shape[1], _ptr(m0), _ptr(v0), opt(jt), ns, _ptr(ts),
-                                          opt(lm), opt(lv), opt(om), opt(ov), info.ctypes.data_as(POINTER(c_int)))
+        rc = self._lib.gprn_predict_batch(self._h, B, _ptr(kp), kp.shape[1], _ptr(m0), _ptr(v0), _opt(jt), ns, _ptr(ts),
+                                          _opt(lm), _opt(lv), _opt(om), _opt(ov), _ip(info))
         if rc == GPRN_E_UNSUPPORTED:
             return None
         self._check(rc, 'predict_batch')

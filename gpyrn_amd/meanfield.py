@@ -51,6 +51,16 @@ class _Folds(np.ndarray):
         self.n_never_held = getattr(obj, 'n_never_held', 0)
 
 
+def _max_trips(max_iter):
+    """ELBOcalc's cap on the loop's trips, its default included (meanfield.py:615-616)."""
+    return 10000 if max_iter is None else int(max_iter)
+
+
+def _first_verdict(info):
+    """``last_info`` from the verdicts of B evaluations: the first positive one, else 0."""
+    return int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
+
+
 class inference:
     """
     Mean-field variational inference for GPRNs (Nguyen & Bonilla 2013).
@@ -1103,10 +1113,7 @@ class inference:
         * `mu`, `var` given: one sweep from that state; the stored state is left alone (and the marker dropped: the device
           no longer holds the stored state's sweep).
         A non-positive pivot raises ``np.linalg.LinAlgError``; a user-defined kernel ``NotImplementedError``."""
-        for k in chain(nodes, weights):
-            if not isinstance(k, covfunc.covFunction) or k._device_program() is None:
-                raise NotImplementedError("predict='variational' needs a device program for every kernel: user-defined "
-                                          'kernels (and sums that hold a two-argument kernel) are not supported')
+        self._need_programs("predict='variational'", nodes, weights)
         explicit = mu is not None or var is not None
         if explicit and (mu is None or var is None):
             raise ValueError('_Prediction: give both mu and var, or neither')
@@ -1339,30 +1346,74 @@ class inference:
         """``nELBO_batch`` through ``gprn_elbocalc_batch``, or None where that does not apply (larger problems, sharded
         objects, user-defined kernels, kernel expressions that change shape from one vector to the next, a data mask without
         ``batch_under_mask``)."""
-        max_iter = 10000 if max_iter is None else int(max_iter)
         start = time_module.time()
+        res = self._batch_run(sets, max_iter)
+        if res is None:
+            return None
+        took = 1e3 * (time_module.time() - start)
+        print(f'{len(sets)} ELBO evaluations side by side (took {took:5.2f} ms)' + 20 * ' ', end='\r', flush=True)
+        return [float(-e) for e in res[0]]
+
+    def _batch_run(self, sets, max_iter):
+        """Stage, run every vector's loop side by side under the stop rule, keep (``_batch_keep``): what
+        ``Context.elbocalc_batch(want_state=True)`` returned, or None where the side-by-side form does not apply."""
         staged = self._batch_stage(sets)
         if staged is None:
             return None
         ctx, kp, yr, jt, m0, v0 = staged
-        res = ctx.elbocalc_batch(kp, yr, jt, m0, v0, max_iter, want_state=True)
-        if res is None:
-            return None
-        elbo = self._batch_keep(res)[0]
-        took = 1e3 * (time_module.time() - start)
-        print(f'{len(sets)} ELBO evaluations side by side (took {took:5.2f} ms)' + 20 * ' ', end='\r', flush=True)
-        return [float(-e) for e in elbo]
+        res = ctx.elbocalc_batch(kp, yr, jt, m0, v0, _max_trips(max_iter), want_state=True)
+        return None if res is None else self._batch_keep(res)
 
     def _batch_keep(self, res):
         """What a side-by-side call leaves with the object: ``last_info``, and as the warm start of whatever comes next the
         state of the last evaluation whose loop converged (meanfield.py:644-646).  Returns ``res``."""
         info, conv, mu_f, var_f = res[3], res[2], res[4], res[5]
-        self.last_info = int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
+        self.last_info = _first_verdict(info)
         done = np.flatnonzero(conv)
         self._batch_last_done = int(done[-1]) if done.size else -1
         if done.size:
             self._mu, self._var = mu_f[done[-1]], var_f[done[-1]]
         return res
+
+    def _full_vectors(self, sets):
+        """``(full (B, n_all), n_k, n_m)``: every vector of `sets` as a full parameter vector (nodes, weights, means,
+        jitters: meanfield.py:193-202) -- a free-length vector over the object's frozen values, a full-length one
+        contributing its free entries, as ``set_parameters`` reads them (meanfield.py:223-259) -- with the columns where
+        the mean parameters begin and how many they are.  None where a vector is neither length (the one-by-one forms
+        raise the reference's ValueError)."""
+        free = ~self.frozen_mask
+        n_free, n_all = int(free.sum()), int(free.size)
+        if any(x.ndim != 1 or x.size not in (n_free, n_all) for x in sets):
+            return None
+        if n_free != n_all and any(x.size == n_all for x in sets):
+            sets = [x[free] if x.size == n_all else x for x in sets]
+        full = np.tile(self.get_parameters(include_frozen=True), (len(sets), 1))
+        full[:, free] = np.array(sets)
+        n_k = sum(k.pars.size for k in chain(self.nodes, self.weights))
+        return full, n_k, n_all - n_k - self.p
+
+    def _need_programs(self, what, nodes, weights):
+        for k in chain(nodes, weights):
+            if not isinstance(k, covfunc.covFunction) or k._device_program() is None:
+                raise NotImplementedError(f'{what} needs a device program for every kernel: user-defined kernels (and sums '
+                                          'that hold a two-argument kernel) are not supported')
+
+    def _scan_programs(self, ctx, shape_ref=None):
+        """One vector's step of the scan both stagings make: ``(components, specs, shape)`` at the object's current
+        parameters -- or None where a kernel has no device program, or the programs' shape is not `shape_ref`, the first
+        vector's.  The first vector (no `shape_ref`) sends the programs the library substitutes the parameters into."""
+        components = self._get_components()
+        specs = [self._kernel_spec(k) for k in chain(components[0], components[1])]
+        if any(sp[0] != 'device' for sp in specs):
+            return None
+        shape = tuple((sp[1], sp[3]) for sp in specs)
+        if shape_ref is None:
+            for gp, sp in enumerate(specs):
+                self._send_spec(ctx, gp, sp)
+            self._prior_key = None                             # (the object's own factors are stale now)
+        elif shape != shape_ref:
+            return None
+        return components, specs, shape
 
     def _batch_stage(self, sets, start=None, own_masks=False):
         """The B problems of a side-by-side call laid out for ``Context.elbocalc_batch``: ``(ctx, kernel_params (B, n_kpar),
@@ -1380,70 +1431,49 @@ class inference:
         y_raw = np.concatenate(self.y)
         B = len(sets)
         state = (self._mu, self._var) if start is None else (np.asarray(start[0], dtype=float), np.asarray(start[1], dtype=float))
-        # (set_parameters takes full-length vectors too, meanfield.py:223-259: the fast layout below wants them all alike)
-        n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
-        if any(x.ndim != 1 or x.size not in (n_free, n_all) for x in sets):
-            return None                                        # (the one-by-one form raises the reference's ValueError)
-        if n_free != n_all and any(x.size == n_all for x in sets):
-            free_ = ~self.frozen_mask
-            sets = [x[free_] if x.size == n_all else x for x in sets]
-        # the first vector the ordinary way: it tells what the programs are and whether the rest can be laid out in one go
-        self.set_parameters(sets[0])
-        nodes, weights, means, jitters = self._get_components()
-        kernels = list(chain(nodes, weights))
-        specs = [self._kernel_spec(k) for k in kernels]
-        if any(sp[0] != 'device' for sp in specs):
+        laid = self._full_vectors(sets)
+        if laid is None:
             return None
-        shape_ref = tuple((sp[1], sp[3]) for sp in specs)
-        for gp, sp in enumerate(specs):                        # the programs the library substitutes the parameters into
-            self._send_spec(ctx, gp, sp)
-        self._prior_key = None                                 # (the object's own factors are stale now)
-        n_k = sum(k.pars.size for k in kernels)
+        full, n_k, n_m = laid
+        # the first vector the ordinary way: it tells what the programs are and whether the rest can be laid out in one go
+        self.set_parameters(full[0, ~self.frozen_mask])
+        scanned = self._scan_programs(ctx)
+        if scanned is None:
+            return None
+        (nodes, weights, means, jitters), specs, shape_ref = scanned
+        kernels = list(chain(nodes, weights))
         plain_kernels = all(sp[2].size == k.pars.size and np.array_equal(sp[2], k.pars) for sp, k in zip(specs, kernels))
         plain_means = all(m_ is None or type(m_) is meanfunc.Constant for m_ in means)
         programs = None if plain_means else self._mean_programs(means)
-        if plain_kernels and programs is not None and state[0] is not None:
-            # the third layout (``device_means``): as the one below, but every mean has a device program -- the kernel, mean
-            # and jitter columns are slices of the B full vectors, and y - mean of all B vectors is formed on the device inside
-            # the batch call (gprn_elbocalc_batch_means: `yr` carries the mean columns, not an array)
-            full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
-            full[:, ~self.frozen_mask] = np.array(sets)
-            kp = full[:, :n_k]
-            n_m = sum(par.size for _, par in programs)
-            for i, (ops, par) in enumerate(programs):
-                ctx.set_mean(i, ops, par)
-            yr = _hip.MeanParams(full[:, n_k:n_k + n_m], y_raw, want_mean_grad=self._elbo == 'bound')
-            jt = full[:, n_k + n_m:]
+        if plain_kernels and (plain_means or programs is not None) and state[0] is not None:
+            # every program's parameters ARE its kernel's and the start is the stored state: the kernel, mean and jitter
+            # columns of the B problems are slices of the B full parameter vectors
+            kp, jt = full[:, :n_k], full[:, n_k + n_m:]
+            if programs is not None:
+                # (``device_means``: every mean has a device program, and y - mean of all B vectors is formed on the device
+                # inside the batch call -- gprn_elbocalc_batch_means: `yr` carries the mean columns, not an array)
+                for i, (ops, par) in enumerate(programs):
+                    ctx.set_mean(i, ops, par)
+                yr = _hip.MeanParams(full[:, n_k:n_k + n_m], y_raw, want_mean_grad=self._elbo == 'bound')
+            else:                                              # (the means are constants: a column each)
+                yr = np.tile(y_raw, (B, 1))
+                col = n_k
+                for i, m_ in enumerate(means):
+                    if m_ is not None:
+                        yr[:, i * self.N:(i + 1) * self.N] -= full[:, col:col + 1]
+                        col += 1
             m0 = np.tile(np.ravel(state[0]), (B, 1))
             v0 = np.tile(np.ravel(state[1]), (B, 1))
-            self.set_parameters(sets[-1])
-        elif plain_kernels and plain_means and state[0] is not None:
-            # every program's parameters ARE its kernel's, the means are constants and the start is the stored state:
-            # the B problems are slices of the B full parameter vectors (nodes, weights, means, jitters: meanfield.py:193-202)
-            full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
-            free = ~self.frozen_mask
-            full[:, free] = np.array(sets)
-            kp = full[:, :n_k]
-            n_m = sum(0 if m_ is None else 1 for m_ in means)
-            yr = np.tile(y_raw, (B, 1))
-            col = n_k
-            for i, m_ in enumerate(means):
-                if m_ is not None:
-                    yr[:, i * self.N:(i + 1) * self.N] -= full[:, col:col + 1]
-                    col += 1
-            jt = full[:, n_k + n_m:]
-            m0 = np.tile(np.ravel(state[0]), (B, 1))
-            v0 = np.tile(np.ravel(state[1]), (B, 1))
-            self.set_parameters(sets[-1])
+            self.set_parameters(full[-1, ~self.frozen_mask])
         else:
             kp, yr, jt, m0, v0 = [], [], [], [], []
-            for i, x in enumerate(sets):
+            for i in range(B):
                 if i:
-                    self.set_parameters(x)
-                    nodes, weights, means, jitters = self._get_components()
-                    specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
-                    if any(sp[0] != 'device' for sp in specs) or tuple((sp[1], sp[3]) for sp in specs) != shape_ref:
+                    self.set_parameters(full[i, ~self.frozen_mask])
+                    scanned = self._scan_programs(ctx, shape_ref)
+                    if scanned is None:
                         return None
+                    (nodes, weights, means, jitters), specs, _ = scanned
                 kp.append(np.concatenate([sp[2] for sp in specs]))
                 yr.append(y_raw - self._mean(means))
                 jt.append(np.asarray(jitters, dtype=float))
@@ -1472,18 +1502,10 @@ class inference:
         shape_ref = None
         for x in sets:
             self.set_parameters(x)
-            nodes, weights, means, jitters = self._get_components()
-            specs = [self._kernel_spec(k) for k in chain(nodes, weights)]
-            if any(sp[0] != 'device' for sp in specs):
+            scanned = self._scan_programs(ctx, shape_ref)
+            if scanned is None:
                 return None
-            shape = tuple((sp[1], sp[3]) for sp in specs)
-            if shape_ref is None:
-                shape_ref = shape
-                for gp, sp in enumerate(specs):                # the programs the library substitutes the parameters into
-                    self._send_spec(ctx, gp, sp)
-                self._prior_key = None                         # (the object's own factors are stale now)
-            elif shape != shape_ref:
-                return None
+            (_, _, means, jitters), specs, shape_ref = scanned
             kp.append(np.concatenate([sp[2] for sp in specs]))
             jt.append(np.asarray(jitters, dtype=float))
             mv.append(np.array(np.array_split(self._mean(means, tstar), self.p)))
@@ -1493,14 +1515,9 @@ class inference:
         """Each vector's ``ELBOcalc`` loop as ``nELBO_batch`` runs it -- side by side from the state the object holds where
         ``_batchable()`` holds, else one after the other, each warm-started by its predecessor -- and the state each loop
         ended in: ``(mu (B, p+1, q, N), var)``.  The object keeps what ``nELBO_batch`` would keep."""
-        if len(sets) > 1 and self._batchable():
-            staged = self._batch_stage(sets)
-            if staged is not None:
-                ctx, kp, yr, jt, m0, v0 = staged
-                res = ctx.elbocalc_batch(kp, yr, jt, m0, v0, 10000 if max_iter is None else int(max_iter), want_state=True)
-                if res is not None:
-                    self._batch_keep(res)
-                    return res[4], res[5]
+        res = self._batch_run(sets, max_iter) if len(sets) > 1 and self._batchable() else None
+        if res is not None:
+            return res[4], res[5]
         mus, vars_ = [], []
         for x in sets:
             self.set_parameters(x)
@@ -1509,6 +1526,76 @@ class inference:
             mus.append(mu)
             vars_.append(var)
         return np.array(mus), np.array(vars_)
+
+    def _times(self, what, tstar):
+        """`tstar` as a non-empty vector of times, the data's by default."""
+        tstar = np.asarray(self.time, dtype=float) if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
+        if tstar.ndim != 1 or tstar.size < 1:
+            raise ValueError(f'{what}: tstar must be a non-empty vector of times')
+        return tstar
+
+    def _batch_request(self, what, parameter_sets, max_iter, sweeps, start, no_trips, tstar=False, start_needs_sweeps=True,
+                       empty_ok=False):
+        """The arguments the side-by-side methods share, read before anything touches a device: ``(sets, forced, trips,
+        tstar)`` -- the vectors as float arrays; whether ``sweeps`` forces the number of sweeps, and the trips either way
+        (``sweeps``, else ``max_iter`` with ELBOcalc's default); `tstar` through ``_times`` (``False``: the method takes no
+        times).  `what` names the method in the messages; `no_trips` is its message for fewer than one trip."""
+        assert self._components_set, _NOT_SET
+        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        if not sets and not empty_ok:
+            raise ValueError(f'{what}: no parameter vector')
+        forced = sweeps is not None
+        if start_needs_sweeps and start is not None and not forced:
+            raise ValueError(f'{what}: `start` goes with `sweeps`; the loop under the stop rule starts from the state the '
+                             'object holds')
+        trips = int(sweeps) if forced else _max_trips(max_iter)
+        if trips < 1:
+            raise ValueError(no_trips)
+        return sets, forced, trips, tstar if tstar is False else self._times(what, tstar)
+
+    def _one_by_one(self, sets, entry, forced, trips, each, variational, chain_info):
+        """The one-by-one form of a side-by-side call.  Every vector starts from `entry` = ``(mu, var)`` -- ``(None, None)``:
+        from ``_initMuVar`` of its own parameters -- and runs the set-up, then `trips` forced committed sweeps or the loop
+        under the stop rule, `trips` at most; then ``each(b, ctx, components, info, history, mu, var)`` makes the vector's
+        payload from what that left and returns ``(payload, failed)``, `failed` the verdict that bars keeping the state
+        (the loop's `info`, or what the payload's own factorisation found).  Returns the payloads.  The object keeps the
+        state of the last vector whose loop converged and did not fail.
+
+        `variational`: the payload predicts from the posterior the sweeps leave -- a kernel without a device program is
+        refused as ``predict='variational'`` refuses it, the marker of the stored state's sweep is dropped (the set-up
+        drops it only where it sends kernels) and the predict form is sent.
+        `chain_info`: ``last_info`` is carried from vector to vector, ``info or last_info`` with what the object held on entry
+        and what each set-up left, and `each` is handed that; else ``last_info`` is this call's first positive `failed`."""
+        payloads, keep, first = [], None, 0
+        for b, x in enumerate(sets):
+            self.set_parameters(x)
+            components = nodes, weights, means, jitters = self._get_components()
+            if variational:
+                self._need_programs("predict='variational'", nodes, weights)
+            mu0, var0 = entry if entry[0] is not None else self._initMuVar(nodes, weights, jitters)
+            ctx = self._setup_device(nodes, weights, means, jitters)
+            if variational:
+                self._swept = None                             # (the device's committed sweep is no stored state's)
+                self._send_predict_form(ctx)
+            ctx.set_muvar(np.asarray(mu0, dtype=float), np.asarray(var0, dtype=float))
+            if forced:
+                history, _, info = ctx.sweep(trips, commit=True)
+                conv = False
+                mu, var = ctx.get_muvar()
+            else:
+                history, _, conv, info, mu, var = ctx.elbocalc(trips)
+            if chain_info:
+                info = self.last_info = info or self.last_info
+            payload, failed = each(b, ctx, components, info, history, mu, var)
+            payloads.append(payload)
+            first = first or int(failed)
+            if conv and not failed:
+                keep = (mu, var)
+        if not chain_info:
+            self.last_info = first
+        if keep is not None:
+            self._mu, self._var = keep
+        return payloads
 
     def predict_batch(self, parameter_sets, tstar=None, states=None, max_iter=None, separate=False, from_sweeps=False,
                       sweeps=None, start=None):
@@ -1557,9 +1644,7 @@ class inference:
         B = len(sets)
         if B < 1:
             raise ValueError('predict_batch: no parameter vector')
-        tstar = np.asarray(self.time, dtype=float) if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
-        if tstar.ndim != 1 or tstar.size < 1:
-            raise ValueError('predict_batch: tstar must be a non-empty vector of times')
+        tstar = self._times('predict_batch', tstar)
         d = (self.p + 1) * self.q * self.N
         if states is None:
             states = self._final_states(sets, max_iter)
@@ -1578,7 +1663,7 @@ class inference:
             res = ctx.predict_batch(kp, mu_b, var_b, tstar, jitters=jt, latent=separate, outputs=True)
         if res is not None:
             lat_mean, _, out_mean, out_var, info = res
-            self.last_info = int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
+            self.last_info = _first_verdict(info)
             mean = np.transpose(out_mean + meanvals, (0, 2, 1))
             var = np.transpose(out_var, (0, 2, 1))
             return (mean, var, lat_mean) if separate else (mean, var)
@@ -1602,24 +1687,11 @@ class inference:
         if states is not None:
             raise ValueError('predict_batch: from_sweeps=True takes no `states` -- a state carries no X; give `sweeps` and '
                              '`start` to run forced sweeps from a state of your own')
-        forced = sweeps is not None
-        if start is not None and not forced:
-            raise ValueError('predict_batch: `start` goes with `sweeps`; the loop under the stop rule starts from the state '
-                             'the object holds')
-        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
-        if trips < 1:
-            raise ValueError('predict_batch: from_sweeps=True needs at least one committed sweep')
         if self._comm is not None:
             raise NotImplementedError('predict_batch(from_sweeps=True) is not available on a sharded inference object')
-        assert self._components_set, _NOT_SET
-        sets = [np.array(x, dtype=float) for x in parameter_sets]
-        B = len(sets)
-        if B < 1:
-            raise ValueError('predict_batch: no parameter vector')
-        tstar = np.asarray(self.time, dtype=float) if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
-        if tstar.ndim != 1 or tstar.size < 1:
-            raise ValueError('predict_batch: tstar must be a non-empty vector of times')
-        entry = (self._mu, self._var) if start is None else start
+        sets, forced, trips, tstar = self._batch_request(
+            'predict_batch', parameter_sets, max_iter, sweeps, start, tstar=tstar,
+            no_trips='predict_batch: from_sweeps=True needs at least one committed sweep')
         staged = self._batch_stage(sets, start=start)
         res = None
         if staged is not None:
@@ -1631,41 +1703,18 @@ class inference:
             mean = np.transpose(out_mean + self._mean_values_batch(sets, tstar), (0, 2, 1))
             var = np.transpose(out_var, (0, 2, 1))
             return (mean, var, lat_mean) if separate else (mean, var)
-        # one by one, each vector from the same state
-        means_, vars_, lats = [], [], []
-        keep, first_info = None, 0
-        for x in sets:
-            self.set_parameters(x)
-            nodes, weights, means, jitters = self._get_components()
-            for k in chain(nodes, weights):
-                if not isinstance(k, covfunc.covFunction) or k._device_program() is None:
-                    raise NotImplementedError("predict='variational' needs a device program for every kernel: user-defined "
-                                              'kernels (and sums that hold a two-argument kernel) are not supported')
-            mu0, var0 = entry if entry[0] is not None else self._initMuVar(nodes, weights, jitters)
-            ctx = self._setup_device(nodes, weights, means, jitters)
-            self._swept = None                                 # (the device's committed sweep is no stored state's)
-            self._send_predict_form(ctx)
-            ctx.set_muvar(np.asarray(mu0, dtype=float), np.asarray(var0, dtype=float))
-            if forced:
-                _, _, info = ctx.sweep(trips, commit=True)
-                conv = False
-                mu, var = ctx.get_muvar()
-            else:
-                _, _, conv, info, mu, var = ctx.elbocalc(trips)
-            first_info = first_info or int(info)
+
+        def predict(b, ctx, components, info, history, mu, var):
+            _, _, means, jitters = components
             if info:
                 gmean = gvar = np.full((self.q * (self.p + 1), tstar.size), np.nan)
             else:
                 gmean, gvar, _ = ctx.predict(tstar)
             m_, v_, parts = self._combine_prediction(gmean, gvar, means, jitters, tstar, True, once=True)
-            means_.append(m_)
-            vars_.append(v_)
-            lats.append(np.concatenate([np.asarray(parts[0], dtype=float), np.asarray(parts[1], dtype=float)]))
-            if conv and not info:
-                keep = (mu, var)
-        self.last_info = first_info
-        if keep is not None:
-            self._mu, self._var = keep
+            return (m_, v_, np.concatenate([np.asarray(parts[0], dtype=float), np.asarray(parts[1], dtype=float)])), info
+
+        entry = (self._mu, self._var) if start is None else start
+        means_, vars_, lats = zip(*self._one_by_one(sets, entry, forced, trips, predict, variational=True, chain_info=False))
         mean, var = np.array(means_), np.array(vars_)
         return (mean, var, np.array(lats)) if separate else (mean, var)
 
@@ -1695,31 +1744,19 @@ class inference:
         if self._predict_form != 'variational':
             raise ValueError("sample_posterior_batch draws from the posterior the sweeps leave; it needs "
                              "predict='variational' (predict_form)")
-        forced = sweeps is not None
-        if start is not None and not forced:
-            raise ValueError('sample_posterior_batch: `start` goes with `sweeps`; the loop under the stop rule starts from '
-                             'the state the object holds')
-        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
-        if trips < 1:
-            raise ValueError('sample_posterior_batch needs at least one committed sweep')
         n = int(n)
         if n < 1:
             raise ValueError('sample_posterior_batch: n >= 1 draws per vector expected')
         if self._comm is not None:
             raise NotImplementedError('sample_posterior_batch is not available on a sharded inference object')
-        assert self._components_set, _NOT_SET
-        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        sets, forced, trips, tstar = self._batch_request(
+            'sample_posterior_batch', parameter_sets, max_iter, sweeps, start, tstar=tstar,
+            no_trips='sample_posterior_batch needs at least one committed sweep')
         B = len(sets)
-        if B < 1:
-            raise ValueError('sample_posterior_batch: no parameter vector')
-        tstar = np.asarray(self.time, dtype=float) if tstar is None else np.atleast_1d(np.asarray(tstar, dtype=float))
-        if tstar.ndim != 1 or tstar.size < 1:
-            raise ValueError('sample_posterior_batch: tstar must be a non-empty vector of times')
         q, p, ns = self.q, self.p, tstar.size
         G = q * (p + 1)
         gen = np.random.default_rng(rng)
         z = gen.standard_normal((B, G, n, ns))
-        entry = (self._mu, self._var) if start is None else start
         staged = self._batch_stage(sets, start=start)
         res = None
         if staged is not None:
@@ -1729,47 +1766,20 @@ class inference:
             self._batch_keep(res)
             lat, out, nug, dinfo = res[6], res[7], res[8], res[9]
             if not self.last_info and np.any(dinfo):
-                self.last_info = int(dinfo[np.flatnonzero(dinfo)[0]])
+                self.last_info = _first_verdict(dinfo)
             jit_b = np.asarray(jt, dtype=float).reshape(B, p)
         else:
             # one by one, each vector from the same state and its own slice of the normals
-            lats, outs, nugs, jits = [], [], [], []
-            keep, first_info = None, 0
-            for b, x in enumerate(sets):
-                self.set_parameters(x)
-                nodes, weights, means, jitters = self._get_components()
-                for k in chain(nodes, weights):
-                    if not isinstance(k, covfunc.covFunction) or k._device_program() is None:
-                        raise NotImplementedError("predict='variational' needs a device program for every kernel: "
-                                                  'user-defined kernels (and sums that hold a two-argument kernel) are not '
-                                                  'supported')
-                mu0, var0 = entry if entry[0] is not None else self._initMuVar(nodes, weights, jitters)
-                ctx = self._setup_device(nodes, weights, means, jitters)
-                self._swept = None                             # (the device's committed sweep is no stored state's)
-                self._send_predict_form(ctx)
-                ctx.set_muvar(np.asarray(mu0, dtype=float), np.asarray(var0, dtype=float))
-                if forced:
-                    _, _, info = ctx.sweep(trips, commit=True)
-                    conv = False
-                    mu, var = ctx.get_muvar()
-                else:
-                    _, _, conv, info, mu, var = ctx.elbocalc(trips)
+            def draw(b, ctx, components, info, history, mu, var):
                 lat_b, out_b, nug_b = np.full((G, n, ns), np.nan), np.full((p, n, ns), np.nan), np.full(G, np.nan)
                 if not info:
-                    l_, o_, nug_b, dinfo = ctx.predict_draws(tstar, z[b])
-                    info = dinfo
-                    if not dinfo:
+                    l_, o_, nug_b, info = ctx.predict_draws(tstar, z[b])
+                    if not info:
                         lat_b, out_b = l_, o_
-                first_info = first_info or int(info)
-                lats.append(lat_b)
-                outs.append(out_b)
-                nugs.append(nug_b)
-                jits.append(np.asarray(jitters, dtype=float))
-                if conv and not info:
-                    keep = (mu, var)
-            self.last_info = first_info
-            if keep is not None:
-                self._mu, self._var = keep
+                return (lat_b, out_b, nug_b, np.asarray(components[3], dtype=float)), info
+
+            entry = (self._mu, self._var) if start is None else start
+            lats, outs, nugs, jits = zip(*self._one_by_one(sets, entry, forced, trips, draw, variational=True, chain_info=False))
             lat, out, nug, jit_b = np.array(lats), np.array(outs), np.array(nugs), np.array(jits).reshape(B, p)
         self.last_nuggets = nug
         meanvals = self._mean_values_batch(sets, tstar)                         # (B, p, N*)
@@ -1796,16 +1806,11 @@ class inference:
         """The mean functions at `tstar` for B vectors, each at its own parameters: ``(B, p, n*)``.  Constant (or no) means
         are read from the vectors' own columns (nodes, weights, means, jitters: meanfield.py:193-202); anything else is
         evaluated per vector.  The object's parameters end at the last vector."""
-        B, ns = len(sets), tstar.size
-        n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
         means = self._get_components()[2]
-        if all(m_ is None or type(m_) is meanfunc.Constant for m_ in means) and all(x.size in (n_free, n_all) for x in sets):
-            free = ~self.frozen_mask
-            full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
-            for b, x in enumerate(sets):
-                full[b, free] = x[free] if x.size == n_all else x     # (a full-length vector: its free entries, as _batch_stage)
-            col = sum(k.pars.size for k in chain(self.nodes, self.weights))
-            out = np.zeros((B, self.p, ns))
+        laid = self._full_vectors(sets)
+        if laid is not None and all(m_ is None or type(m_) is meanfunc.Constant for m_ in means):
+            full, col, _ = laid
+            out = np.zeros((len(sets), self.p, tstar.size))
             for i, m_ in enumerate(means):
                 if m_ is not None:
                     out[:, i, :] = full[:, col:col + 1]
@@ -1813,18 +1818,13 @@ class inference:
             self.set_parameters(sets[-1])
             return out
         programs = self._mean_programs(means)
-        if programs is not None and all(x.size in (n_free, n_all) for x in sets):
+        if laid is not None and programs is not None:
             # every mean has a device program: the mean columns of the B full vectors in one slice, one call
-            free = ~self.frozen_mask
-            full = np.tile(self.get_parameters(include_frozen=True), (B, 1))
-            for b, x in enumerate(sets):
-                full[b, free] = x[free] if x.size == n_all else x
-            col = sum(k.pars.size for k in chain(self.nodes, self.weights))
-            n_mpar = sum(par.size for _, par in programs)
+            full, n_k, n_m = laid
             ctx = self._backend()
             for i, (ops, par) in enumerate(programs):
                 ctx.set_mean(i, ops, par)
-            out = ctx.eval_mean(full[:, col:col + n_mpar], tstar)
+            out = ctx.eval_mean(full[:, n_k:n_k + n_m], tstar)
             self.set_parameters(sets[-1])
             return out
         out = []
@@ -2162,15 +2162,10 @@ class inference:
         if self.mask is not None:
             w = np.where(self.mask[None], w, 0.0)
         programs = self._mean_programs(self.means)
-        n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
-        if programs is not None and all(np.ndim(x) == 1 and np.size(x) in (n_free, n_all) for x in sets):
+        laid = None if programs is None else self._full_vectors([np.asarray(x) for x in sets])
+        if laid is not None:
             # ``device_means``: d mean / d theta of all B vectors in ONE gprn_eval_mean_grad call, contracted here
-            free = ~self.frozen_mask
-            full = np.tile(self.get_parameters(include_frozen=True), (len(sets), 1))
-            for b, x in enumerate(sets):
-                full[b, free] = x[free] if np.size(x) == n_all else x
-            n_k = sum(k.pars.size for k in chain(self.nodes, self.weights))
-            n_m = sum(par.size for _, par in programs)
+            full, n_k, n_m = laid
             ctx = self._backend()
             for i, (ops, par) in enumerate(programs):
                 ctx.set_mean(i, ops, par)
@@ -2226,21 +2221,14 @@ class inference:
         """
         if self._comm is not None:
             raise NotImplementedError('nELBO_and_grad_batch is not available on a sharded inference object')
-        assert self._components_set, _NOT_SET
-        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        sets, forced, trips, _ = self._batch_request('nELBO_and_grad_batch', parameter_sets, max_iter, sweeps, start, empty_ok=True,
+                                                     no_trips='nELBO_and_grad_batch: a gradient needs at least one sweep')
         n_free, n_all = int((~self.frozen_mask).sum()), int(self.frozen_mask.size)
         for x in sets:
             if x.ndim != 1:                                    # (before anything of the object changes)
                 raise ValueError('nELBO_and_grad_batch: one-dimensional parameter vectors expected')
             if x.size not in (n_free, n_all):
                 self.set_parameters(x)                         # (raises the reference's ValueError, meanfield.py:223-259)
-        forced = sweeps is not None
-        if start is not None and not forced:
-            raise ValueError('nELBO_and_grad_batch: `start` goes with `sweeps`; the loop under the stop rule starts from '
-                             'the state the object holds')
-        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
-        if trips < 1:
-            raise ValueError('nELBO_and_grad_batch: a gradient needs at least one sweep')
         free = ~self.frozen_mask
         if not sets:
             return [], np.zeros((0, n_free))
@@ -2268,34 +2256,17 @@ class inference:
             values = [float('inf') if b else float(-e) for e, b in zip(elbo, bad)]
             return values, -grads[:, free]
         # one by one, each vector from the same state
-        values, grads = [], np.zeros((len(sets), n_free))
-        keep = None
-        for b, x in enumerate(sets):
-            self.set_parameters(x)
-            nodes, weights, means, jitters = self._get_components()
-            mu0, var0 = entry if entry[0] is not None else self._initMuVar(nodes, weights, jitters)
-            ctx = self._setup_device(nodes, weights, means, jitters)
-            ctx.set_muvar(np.asarray(mu0, dtype=float), np.asarray(var0, dtype=float))
-            if forced:
-                e, _, info = ctx.sweep(trips, commit=True)
-                e, conv = e[-1], False
-                mu, var = ctx.get_muvar()
-            else:
-                hist, _, conv, info, mu, var = ctx.elbocalc(trips)
-                e = hist[-1]
-            info = info or self.last_info
-            self.last_info = info
+        grads = np.zeros((len(sets), n_free))
+
+        def value_and_grad(b, ctx, components, info, history, mu, var):
+            e = history[-1]
             if info or not np.isfinite(e):
-                values.append(float('inf'))
-                continue
-            g = np.array(self._grad_from_state(nodes, weights, means, jitters, mu, var, None, fused=ctx,
-                                               bound=self._elbo == 'bound'))
-            values.append(float(-e))
+                return float('inf'), True
+            g = np.array(self._grad_from_state(*components, mu, var, None, fused=ctx, bound=self._elbo == 'bound'))
             grads[b] = -g[free]
-            if conv:
-                keep = (mu, var)
-        if keep is not None:
-            self._mu, self._var = keep
+            return float(-e), False
+
+        values = self._one_by_one(sets, entry, forced, trips, value_and_grad, variational=False, chain_info=True)
         return values, grads
 
     # ------------------------------------------------ held-out scores: cross-validation side by side
@@ -2347,18 +2318,12 @@ class inference:
         fallback.  The object's stored state is left alone; its parameters end at the last vector.
         """
         what = 'heldout_batch'
-        assert self._components_set, _NOT_SET
-        sets = [np.array(x, dtype=float) for x in parameter_sets]
+        sets, forced, trips, _ = self._batch_request(what, parameter_sets, max_iter, sweeps, start, start_needs_sweeps=False,
+                                                     no_trips=f'{what}: a held-out score needs at least one committed sweep')
         B = len(sets)
-        if B < 1:
-            raise ValueError(f'{what}: no parameter vector')
         if any(x.ndim != 1 for x in sets):
             raise ValueError(f'{what}: one-dimensional parameter vectors expected')
         fit = self._check_fit_masks(fit_masks, B, what)
-        forced = sweeps is not None
-        trips = int(sweeps) if forced else (10000 if max_iter is None else int(max_iter))
-        if trips < 1:
-            raise ValueError(f'{what}: a held-out score needs at least one committed sweep')
         if start is not None and (len(start) != 2 or np.size(start[0]) != self.d or np.size(start[1]) != self.d):
             raise ValueError(f'{what}: start must be (mu, var) of {self.d} values each')
         if self._comm is not None:
@@ -2368,10 +2333,7 @@ class inference:
         if self.N > self.batch_max_N:
             raise NotImplementedError(f'{what}: N = {self.N} is above batch_max_N = {self.batch_max_N}, the largest problem '
                                       'the side-by-side form takes')
-        nodes, weights, _, _ = self._get_components()
-        if any(self._kernel_spec(k)[0] != 'device' for k in chain(nodes, weights)):
-            raise NotImplementedError(f'{what} needs a device program for every kernel: user-defined kernels (and sums '
-                                      'that hold a two-argument kernel) are not supported')
+        self._need_programs(what, *self._get_components()[:2])
         placeholder = (np.zeros(self.d), np.ones(self.d))
         staged = self._batch_stage(sets, start=placeholder if start is None else start, own_masks=True)
         if staged is None:
@@ -2393,7 +2355,7 @@ class inference:
         if res is None:
             raise NotImplementedError(f'{what}: the library has no side-by-side form for this problem')
         elbo, iters, conv, info, mu_f, var_f, hmean, hvar, lpd, n_held = res
-        self.last_info = int(info[np.flatnonzero(info)[0]]) if np.any(info) else 0
+        self.last_info = _first_verdict(info)
         held = self._data_mask()[None] & ~fit
         hmean = np.where(held, hmean + self._mean_values_batch(sets, np.asarray(self.time, dtype=float)), hmean)
         return HeldOut(lpd=lpd, n_held=n_held, mean=hmean, var=hvar, elbo=elbo, iterations=iters, converged=conv, info=info,
