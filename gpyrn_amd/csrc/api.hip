@@ -186,6 +186,8 @@ static void watch_unregister(gprn_ctx* c)
 //   "fenced_finalize" test hook: 1 = k_reduce_finalize hands its terms over with release / acquire fences (vecops.hip)
 //   "fallbacks"      read-only: calls re-run on the event schedule after a time-out
 //   "batch_chunk"    read-only: evaluations per chunk in the last gprn_elbocalc_batch call
+//   "live_allocs" / "allocs_made"  read-only, process-wide (any context reads them): device and pinned allocations the library
+//                    holds now / has made since it was loaded (device_mem.h)
 extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* old)
 {
     DeviceLock lock_(c);
@@ -210,6 +212,8 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     else if (!strcmp(name, "fenced_finalize")) field = &c->fenced_finalize;
     else if (!strcmp(name, "fallbacks")) { if (old) *old = c->fallbacks; return GPRN_OK; }
     else if (!strcmp(name, "batch_chunk")) { if (old) *old = c->last_batch_chunk; return GPRN_OK; }
+    else if (!strcmp(name, "live_allocs")) { if (old) *old = (int)g_mem_live.load(); return GPRN_OK; }
+    else if (!strcmp(name, "allocs_made")) { if (old) *old = (int)g_mem_made.load(); return GPRN_OK; }
     else return bad(c, "set_option: unknown option");
     if (old) *old = *field;
     const bool is_pad = field == &c->pad_kb_opt || field == &c->pad_small_kb_opt;
@@ -269,70 +273,113 @@ extern "C" int gprn_set_option(gprn_ctx* c, const char* name, int value, int* ol
     return GPRN_OK;
 }
 
-void free_slot_arrays(gprn_ctx* c)
+// ------------------------------------------------------------------ memory
+// The allocator (device_mem.h): the four HIP calls and their two counters, here and nowhere else
+std::atomic<long long> g_mem_live{0}, g_mem_made{0};
+static int mem_made(void** p, hipError_t e, const char* what, int code, std::string* err)
 {
-    dev_free(c->d_d); dev_free(c->d_s); dev_free(c->d_pred); dev_free(c->d_z); dev_free(c->d_u);
-    dev_free(c->d_cs); dev_free(c->d_ct); dev_free(c->d_part); dev_free(c->d_fin_terms); dev_free(c->d_fin_tickets);
-    dev_free(c->d_info);
-    c->nslot = 0;
+    if (e == hipSuccess) { g_mem_live += 1; g_mem_made += 1; return GPRN_OK; }
+    *p = nullptr;
+    if (err) *err = std::string(what) + hipGetErrorString(e);
+    return code;
+}
+int mem_dev_alloc(void** p, size_t bytes, std::string* err)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) (void)hipGetLastError();     // (not sticky: a batch call allocates again, in halves -- gprn_elbocalc_batch)
+    return mem_made(p, e, "hipMalloc: ", GPRN_E_NOMEM, err);
+}
+int mem_pin_alloc(void** p, size_t bytes, std::string* err)
+{
+    return mem_made(p, hipHostMalloc(p, bytes, hipHostMallocDefault), "hipHostMalloc: ", GPRN_E_HIP, err);
+}
+void mem_dev_free(void* p) { if (p) { hipFree(p); g_mem_live -= 1; } }
+void mem_pin_free(void* p) { if (p) { hipHostFree(p); g_mem_live -= 1; } }
+
+// The releases of gprn_ctx::Mem's groups: noted tables forgotten BEFORE their memory goes back, then views null, sizes reset
+void release_slots(gprn_ctx* c)
+{
+    tab_forget(c, c->tab_node); tab_forget(c, c->tab_weight); tab_forget(c, c->tab_setup);
+    c->mem.slots.release();
+    c->wsB.clear(); c->wsX.clear();
+    c->tab_node = c->tab_weight = c->tab_setup = nullptr;
+    c->d_slotgp_node = c->d_slotgp_weight = c->d_slotgp_setup = nullptr;
+    c->d_d = c->d_s = c->d_pred = c->d_z = c->d_u = c->d_cs = c->d_ct = c->d_part = c->d_fin_terms = nullptr;
+    c->d_fin_tickets = nullptr; c->d_info = nullptr;
+    c->nslot = 0; c->tables_ready = false;
 }
 
-int alloc_slot_arrays(gprn_ctx* c, int nslot)
+void release_mask_data(gprn_ctx* c)
 {
-    const size_t vec = (size_t)nslot * c->ld;
-    TRY(dev_alloc(c, &c->d_d, vec)); TRY(dev_alloc(c, &c->d_s, vec)); TRY(dev_alloc(c, &c->d_pred, vec));
-    TRY(dev_alloc(c, &c->d_z, vec)); TRY(dev_alloc(c, &c->d_u, vec)); TRY(dev_alloc(c, &c->d_cs, vec));
-    TRY(dev_alloc(c, &c->d_ct, vec));
-    TRY(dev_alloc(c, &c->d_part, vec * c->T * 2));
-    TRY(dev_alloc(c, &c->d_fin_terms, vec * 2));         // (vec_reduce_finalize, vecops.hip: tickets zero between launches)
-    TRY(dev_alloc(c, &c->d_fin_tickets, (size_t)nslot));
-    TRY(dev_alloc(c, &c->d_info, 3 * (size_t)nslot));
-    HIP_TRY(c, hipMemset(c->d_fin_tickets, 0, (size_t)nslot * sizeof(unsigned)));
-    HIP_TRY(c, hipMemset(c->d_info, 0, 3 * (size_t)nslot * sizeof(int)));
-    c->nslot = nslot;
-    return GPRN_OK;
+    c->mem.mask_data.release();
+    c->d_mask = nullptr; c->d_mask_U = c->d_mask_nU = nullptr;
+    c->h_mask.clear(); c->mask_U.clear(); c->mask_upad = 0;
+}
+
+void mask_free(gprn_ctx* c)
+{
+    for (int w = 0; w < 2; ++w) {
+        tab_forget(c, c->tab_mask[w]);
+        c->tab_mask[w] = nullptr; c->d_mask_slot[w] = c->d_mask_gp[w] = nullptr; c->d_mask_tasks[w] = nullptr;
+        c->mask_n[w] = 0; c->mask_ntasks[w] = 0; c->mask_upad_ph[w] = 0;
+    }
+    c->mem.mask_bufs.release();
+    c->mask_WT.clear(); c->mask_C.clear();
+    c->mask_ready = false;
+}
+
+void release_pred(gprn_ctx* c)
+{
+    tab_forget(c, c->tab_pred);
+    c->mem.pred.release();
+    c->predKs.clear(); c->predWT.clear(); c->pred_cap = 0;
+    c->tab_pred = nullptr; c->d_slotgp_all = nullptr;
 }
 
 void free_problem(gprn_ctx* c)
 {
-    dev_free(c->d_time); dev_free(c->d_yraw); dev_free(c->d_yerr2); dev_free(c->d_yres);
-    dev_free(c->d_variance); dev_free(c->d_mu); dev_free(c->d_var);
-    dev_free(c->d_mu_save); dev_free(c->d_var_save);
-    dev_free(c->d_mu_alt); dev_free(c->d_var_alt);
-    dev_free(c->d_mu_old); c->mu_old_cap = 0;
-    if (c->d_loop_ctl) { hipFree(c->d_loop_ctl); c->d_loop_ctl = nullptr; }
-    small_batch_free(c);
-    mid_batch_free(c);
-    if (c->grad_scratch) { hipFree(c->grad_scratch); c->grad_scratch = nullptr; c->grad_scratch_bytes = 0; }
-    if (c->h_pin_in) { hipHostFree(c->h_pin_in); c->h_pin_in = nullptr; c->pin_in_cap = 0; }
-    if (c->h_pin_out) { hipHostFree(c->h_pin_out); c->h_pin_out = nullptr; c->pin_out_cap = 0; }
-    dev_free(c->d_loop_hist);
-    for (auto& p : c->K) dev_free(p);
-    for (auto& p : c->KLinv) dev_free(p);
-    for (auto& p : c->Kinv) dev_free(p);
-    for (auto& p : c->Sig) dev_free(p);
-    for (auto& p : c->wsB) dev_free(p);
-    for (auto& p : c->wsX) dev_free(p);
-    c->K.clear(); c->KLinv.clear(); c->Kinv.clear(); c->Sig.clear(); c->wsB.clear(); c->wsX.clear();
-    dev_free(c->d_logdetK);
-    dev_free(c->d_kinv_tab); dev_free(c->d_kinv_out); dev_free(c->d_small_ticket); dev_free(c->d_small_stamps);
-    for (auto& p : c->predKs) dev_free(p);
-    for (auto& p : c->predWT) dev_free(p);
-    c->predKs.clear(); c->predWT.clear(); c->pred_cap = 0;
-    tab_forget(c, nullptr);
-    dev_free(c->tab_pred); dev_free(c->d_slotgp_all);
-    mask_free(c);
-    dev_free(c->d_mask); dev_free(c->d_mask_U); dev_free(c->d_mask_nU);
-    c->h_mask.clear(); c->mask_U.clear(); c->mask_upad = 0;
-    dev_free(c->tab_node); dev_free(c->tab_weight); dev_free(c->tab_setup);
-    dev_free(c->d_slotgp_node); dev_free(c->d_slotgp_weight); dev_free(c->d_slotgp_setup);
-    free_slot_arrays(c);
-    dev_free(c->d_scal_base); c->d_scal = nullptr; dev_free(c->d_elbo_part); dev_free(c->d_out);
-    c->out_cap = 0;
+    small_batch_free(c); mid_batch_free(c);
+    release_pred(c); mask_free(c); release_mask_data(c); release_slots(c);
+    c->tab_host.clear();
+    gprn_ctx::Mem& m = c->mem;
+    m.problem.release();
+    m.kinv_tab.release(); m.kinv_out.release(); m.tab_kinv1.release();
+    m.out.release(); m.mu_old.release(); m.pin_in.release(); m.pin_out.release(); m.grad_scratch.release();
+    c->d_time = c->d_yraw = c->d_yerr2 = c->d_yres = c->d_variance = nullptr;
+    c->d_mu = c->d_var = c->d_mu_save = c->d_var_save = c->d_mu_alt = c->d_var_alt = c->d_mu_old = nullptr;
+    c->d_logdetK = c->d_scal_base = c->d_scal = c->d_elbo_part = c->d_out = c->d_loop_hist = nullptr;
+    c->K.clear(); c->KLinv.clear(); c->Kinv.clear(); c->Sig.clear();
+    c->d_kinv_tab = c->d_kinv_out = c->tab_kinv1 = nullptr;
+    c->d_small_ticket = nullptr; c->d_small_stamps = nullptr; c->d_loop_ctl = nullptr;
+    c->h_pin_in = c->h_pin_out = nullptr; c->grad_scratch = nullptr;
     c->factored = c->have_yres = c->have_jit = c->have_muvar = false;
-    c->tables_ready = false;
     c->small_tabs_ready = c->small_sweep_ready = c->setup1_ready = false;
-    dev_free(c->tab_kinv1);
+}
+
+void release_context(gprn_ctx* c)
+{
+    gprn_ctx::Mem& m = c->mem;
+    m.ctx.release();
+    m.tasks.release(); m.sig.release(); m.step_stamps.release(); m.side_stamps.release();
+    for (int b = 0; b < 3; ++b) { m.test[b].release(); c->d_test[b] = nullptr; }
+    c->d_agree = nullptr; c->d_tasks = nullptr; c->d_sig = nullptr;
+    c->d_step_stamps = c->d_side_stamps = c->side_stamps = nullptr;
+    c->tasks_T = c->sig_T = c->step_stamps_T = 0;
+}
+
+int alloc_slot_arrays(gprn_ctx* c, int nslot)
+{
+    DeviceOwner& own = c->mem.slots;
+    const size_t vec = (size_t)nslot * c->ld;
+    for (double** v : {&c->d_d, &c->d_s, &c->d_pred, &c->d_z, &c->d_u, &c->d_cs, &c->d_ct}) TRY(own.alloc(c, v, vec));
+    TRY(own.alloc(c, &c->d_part, vec * c->T * 2));
+    TRY(own.alloc(c, &c->d_fin_terms, vec * 2));         // (vec_reduce_finalize, vecops.hip: tickets zero between launches)
+    TRY(own.alloc(c, &c->d_fin_tickets, (size_t)nslot));
+    TRY(own.alloc(c, &c->d_info, 3 * (size_t)nslot));
+    HIP_TRY(c, hipMemset(c->d_fin_tickets, 0, (size_t)nslot * sizeof(unsigned)));
+    HIP_TRY(c, hipMemset(c->d_info, 0, 3 * (size_t)nslot * sizeof(int)));
+    c->nslot = nslot;
+    return GPRN_OK;
 }
 
 // ------------------------------------------------------------------ context
@@ -439,13 +486,8 @@ extern "C" void gprn_destroy(gprn_ctx* c)
         prof_collect(c);
         for (auto e : c->prof.pool) hipEventDestroy(e);
         comm_teardown(c);
-        free_problem(c);
-        dev_free(c->d_tasks);
-        if (c->d_sig) hipFree(c->d_sig);
-        if (c->d_step_stamps) hipFree(c->d_step_stamps);
-        if (c->d_side_stamps) hipFree(c->d_side_stamps);
-        dev_free(c->d_agree);
-        dev_free(c->d_test[0]); dev_free(c->d_test[1]); dev_free(c->d_test[2]);
+        free_problem(c);                           // (explicitly, here: with the device set, the streams idle and the lock
+        release_context(c);                        // held -- the owners' destructors behind `delete c` find nothing left)
         hipEventDestroy(c->ev_diag);
         hipEventDestroy(c->ev_first);
         hipEventDestroy(c->ev_minil);
@@ -487,21 +529,14 @@ extern "C" int gprn_set_data(gprn_ctx* c, int N, int p, int q, const double* tim
     if (c->world == 1) c->owner.assign(c->G, 0);
     else c->owner.clear();                      // gprn_set_owners must follow
     const size_t pn = (size_t)p * N, dn = (size_t)(p + 1) * q * N;
-    TRY(dev_alloc(c, &c->d_time, N));
-    TRY(dev_alloc(c, &c->d_yraw, pn));
-    TRY(dev_alloc(c, &c->d_yerr2, pn));
-    TRY(dev_alloc(c, &c->d_yres, pn));
-    TRY(dev_alloc(c, &c->d_variance, pn));
-    TRY(dev_alloc(c, &c->d_mu, dn));
-    TRY(dev_alloc(c, &c->d_var, dn));
-    TRY(dev_alloc(c, &c->d_mu_save, dn));
-    TRY(dev_alloc(c, &c->d_var_save, dn));
-    TRY(dev_alloc(c, &c->d_mu_alt, dn));
-    TRY(dev_alloc(c, &c->d_var_alt, dn));
-    TRY(dev_alloc(c, &c->d_logdetK, c->G));
-    TRY(dev_alloc(c, &c->d_scal_base, 2 * (size_t)(3 * c->G + q * q)));
+    DeviceOwner& own = c->mem.problem;
+    TRY(own.alloc(c, &c->d_time, N));
+    for (double** a : {&c->d_yraw, &c->d_yerr2, &c->d_yres, &c->d_variance}) TRY(own.alloc(c, a, pn));
+    for (double** a : {&c->d_mu, &c->d_var, &c->d_mu_save, &c->d_var_save, &c->d_mu_alt, &c->d_var_alt}) TRY(own.alloc(c, a, dn));
+    TRY(own.alloc(c, &c->d_logdetK, c->G));
+    TRY(own.alloc(c, &c->d_scal_base, 2 * (size_t)(3 * c->G + q * q)));
     HIP_TRY(c, hipMemset(c->d_scal_base, 0, 2 * (size_t)(3 * c->G + q * q) * sizeof(double)));
-    TRY(dev_alloc(c, &c->d_elbo_part, 2 * (size_t)GPRN_ELBO_PART_DOUBLES));
+    TRY(own.alloc(c, &c->d_elbo_part, 2 * (size_t)GPRN_ELBO_PART_DOUBLES));
     c->d_scal = c->d_scal_base;
     std::vector<double> e2(pn);
     for (size_t i = 0; i < pn; ++i) e2[i] = yerr[i] * yerr[i];
@@ -548,8 +583,8 @@ extern "C" int gprn_set_kernel(gprn_ctx* c, int gp, const int32_t* ops, int n_op
 int ensure_gp_storage(gprn_ctx* c, int g)
 {
     const size_t nn = (size_t)c->ld * c->ld;
-    if (!c->K[g]) TRY(dev_alloc(c, &c->K[g], nn));
-    if (!c->KLinv[g]) TRY(dev_alloc(c, &c->KLinv[g], nn));
+    if (!c->K[g]) TRY(c->mem.problem.alloc(c, &c->K[g], nn));
+    if (!c->KLinv[g]) TRY(c->mem.problem.alloc(c, &c->KLinv[g], nn));
     return GPRN_OK;
 }
 
@@ -973,22 +1008,16 @@ int build_tables(gprn_ctx* c)
     const int want = std::max<size_t>(1, c->loc_nodes.size() + c->loc_weights.size());
     const size_t nn = (size_t)c->ld * c->ld;
     if (want != c->nslot) {
-        for (auto& p : c->wsB) dev_free(p);
-        for (auto& p : c->wsX) dev_free(p);
+        release_slots(c);
+        DeviceOwner& own = c->mem.slots;
         c->wsB.assign(want, nullptr); c->wsX.assign(want, nullptr);
         for (int s = 0; s < want; ++s) {
-            TRY(dev_alloc(c, &c->wsB[s], nn));
-            TRY(dev_alloc(c, &c->wsX[s], nn));
+            TRY(own.alloc(c, &c->wsB[s], nn));
+            TRY(own.alloc(c, &c->wsX[s], nn));
         }
-        tab_forget(c, c->tab_node); tab_forget(c, c->tab_weight); tab_forget(c, c->tab_setup);
-        dev_free(c->tab_node); dev_free(c->tab_weight); dev_free(c->tab_setup);
-        dev_free(c->d_slotgp_node); dev_free(c->d_slotgp_weight); dev_free(c->d_slotgp_setup);
-        free_slot_arrays(c);
         const size_t tab = (size_t)want * GPRN_NBUF;
-        TRY(dev_alloc(c, &c->tab_node, tab)); TRY(dev_alloc(c, &c->tab_weight, tab));
-        TRY(dev_alloc(c, &c->tab_setup, tab));
-        TRY(dev_alloc(c, &c->d_slotgp_node, want)); TRY(dev_alloc(c, &c->d_slotgp_weight, want));
-        TRY(dev_alloc(c, &c->d_slotgp_setup, want));
+        for (double*** t : {&c->tab_node, &c->tab_weight, &c->tab_setup}) TRY(own.alloc(c, t, tab));
+        for (int** g : {&c->d_slotgp_node, &c->d_slotgp_weight, &c->d_slotgp_setup}) TRY(own.alloc(c, g, want));
         TRY(alloc_slot_arrays(c, want));
     }
     for (int g : c->loc_nodes) TRY(ensure_gp_storage(c, g));

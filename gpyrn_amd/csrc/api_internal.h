@@ -1,7 +1,8 @@
 // Shared by the translation units of the C ABI (api.hip: context, problem, options, watchdog, communicator, tables, read-back;
 // api_sweep.hip: the set-up, the sweep, the ELBOcalc loop; api_more.hip: prediction, kernel matrices and prior draws, gradients,
 // the ELBO's terms on their own, diagnostics).  Round 6 split of a 2 700-line api.hip along its section banners; the 42
-// exported symbols are unchanged (tests/test_abi.py).
+// exported symbols are unchanged (tests/test_abi.py).  Memory: device_mem.h (the allocator, DeviceOwner, DevBuf); what the context
+// keeps hangs off gprn_ctx::Mem (gprn_internal.h), one owner per lifetime; ONE call's temporaries have CallScratch, below.
 #pragma once
 #include "gprn_internal.h"
 #include "vecops.h"
@@ -15,45 +16,15 @@
 #include <algorithm>
 
 // ------------------------------------------------------------------ helpers
-template <typename T>
-static int dev_alloc(gprn_ctx* c, T** p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();          // (not sticky: a batch call allocates again, in halves -- gprn_elbocalc_batch)
-        c->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return GPRN_E_NOMEM;
-    }
-    return GPRN_OK;
-}
 #define TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
-
-template <typename T>
-static void dev_free(T*& p) { if (p) hipFree(p); p = nullptr; }
 
 static inline int bad(gprn_ctx* c, const char* msg) { if (c) c->err = msg; return GPRN_E_ARG; }
 
-// Owns device and pinned allocations: everything it hands out is freed in release() and in its destructor, on every path
-// (CallScratch for one call; SmallBatchMem, MidBatch and through them batch_tail.hip's TailKept between side-by-side calls).  A failed alloc / pin leaves a null pointer.
-struct DeviceOwner {
-    std::vector<void*> dev, pinned;
-    DeviceOwner() = default;
-    DeviceOwner(const DeviceOwner&) = delete; DeviceOwner& operator=(const DeviceOwner&) = delete;
-    ~DeviceOwner() { release(); }
-    template <typename T>
-    int alloc(gprn_ctx* c, T** p, size_t count) { TRY(dev_alloc(c, p, count)); dev.push_back(*p); return GPRN_OK; }
-    template <typename T>
-    int pin(gprn_ctx* c, T** p, size_t bytes) { *p = nullptr; HIP_TRY(c, hipHostMalloc((void**)p, bytes, hipHostMallocDefault)); pinned.push_back(*p); return GPRN_OK; }
-    void release() { for (void* p : dev) hipFree(p); for (void* p : pinned) hipHostFree(p); dev.clear(); pinned.clear(); }
-};
-
-// The device temporaries of ONE call (nothing is kept across calls; what the context owns -- workspaces, prediction
-// buffers, d_test, slot arrays, masks, batch slabs -- stays with the context).  Whatever it hands out lives until it goes out of
+// The device temporaries of ONE call (nothing is kept across calls; what the context keeps belongs to the lifetime groups of
+// gprn_ctx::Mem, what a batch keeps to its driver's DeviceOwner -- device_mem.h).  Whatever it hands out lives until it goes out of
 // scope, on every return path: the destructor waits for c->stream, forgets the tables it noted and frees everything.
 // (tab_host, which tab_rows reads, is keyed by a table's device address: a table freed while still noted would hand its old
-// rows to whichever table hipMalloc puts at that address next.)  Declare it AFTER the host buffers that copies queued on
+// rows to whichever table the allocator puts at that address next.)  Declare it AFTER the host buffers that copies queued on
 // c->stream write into: locals go in reverse order, so its wait then comes before they do.
 struct CallScratch {
     gprn_ctx* const c;
@@ -146,7 +117,7 @@ static inline int agree_on_timeout(gprn_ctx* c, int rc, bool* any)
     *any = rc == GPRN_E_WAIT_TIMEOUT;
     if (!comm_active(c)) return GPRN_OK;
     if (rc == GPRN_E_COMM) return GPRN_OK;             // the transport itself is down: nothing to agree through
-    if (!c->d_agree && hipMalloc(&c->d_agree, sizeof(double)) != hipSuccess) { c->err = "hipMalloc: timeout word"; return GPRN_E_NOMEM; }
+    if (!c->d_agree && c->mem.ctx.alloc(c, &c->d_agree, 1)) { c->err = "hipMalloc: timeout word"; return GPRN_E_NOMEM; }
     const double mine = *any ? 1.0 : 0.0;
     double all = 0.0;
     HIP_TRY(c, hipMemcpyAsync(c->d_agree, &mine, sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -165,7 +136,7 @@ static inline int agree_on_timeout(gprn_ctx* c, int rc, bool* any)
 static inline int agree_to_start(gprn_ctx* c, int local_rc, const char* what)
 {
     if (!comm_active(c)) return local_rc;
-    if (!c->d_agree && hipMalloc(&c->d_agree, sizeof(double)) != hipSuccess) { c->err = "hipMalloc: agreement word"; return GPRN_E_NOMEM; }
+    if (!c->d_agree && c->mem.ctx.alloc(c, &c->d_agree, 1)) { c->err = "hipMalloc: agreement word"; return GPRN_E_NOMEM; }
     const double mine = local_rc ? 1.0 : 0.0;
     double all = 0.0;
     HIP_TRY(c, hipMemcpyAsync(c->d_agree, &mine, sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -253,10 +224,8 @@ int exchange_rows(gprn_ctx* c, bool weights);
 int reduce_scalars(gprn_ctx* c, double* scal);     // all-reduce of a sweep's scalars (one copy of d_scal_base)
 int upload_table(gprn_ctx* c, double** d_tab, const std::vector<double*>& rows);
 int build_tables(gprn_ctx* c);
-void free_problem(gprn_ctx* c);                   // every device and pinned array of the context's problem
-// the per-slot arrays (d, s, pred, z, u, colsq, colt, partial column sums, finalising terms and tickets, pivot verdicts):
-// freed, and allocated for c->nslot = nslot slots of the context's ld and T
-void free_slot_arrays(gprn_ctx* c);
+// the per-slot arrays (d, s, pred, z, u, colsq, colt, partial column sums, finalising terms and tickets, pivot verdicts) for
+// c->nslot = nslot slots of the context's ld and T, charged to the context's slot group
 int alloc_slot_arrays(gprn_ctx* c, int nslot);
 int check_info(gprn_ctx* c, const int* d_info, const std::vector<int>& gps, int* first);
 int ensure_gp_storage(gprn_ctx* c, int g);

@@ -146,18 +146,16 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
     const size_t need = (size_t)ns_pad * ld;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     if (nloc && (c->predKs.size() != (size_t)c->nslot || c->pred_cap < need)) {
-        for (auto& p : c->predKs) dev_free(p);
-        for (auto& p : c->predWT) dev_free(p);
+        release_pred(c);
+        DeviceOwner& own = c->mem.pred;
         c->predKs.assign(c->nslot, nullptr); c->predWT.assign(c->nslot, nullptr);
         for (int s = 0; s < c->nslot; ++s) {
-            TRY(dev_alloc(c, &c->predKs[s], need));
-            TRY(dev_alloc(c, &c->predWT[s], need));
+            TRY(own.alloc(c, &c->predKs[s], need));
+            TRY(own.alloc(c, &c->predWT[s], need));
         }
         c->pred_cap = need;
-        if (c->tab_pred) tab_forget(c, c->tab_pred);       // (a null argument forgets EVERY table's host copy)
-        dev_free(c->tab_pred); dev_free(c->d_slotgp_all);
-        TRY(dev_alloc(c, &c->tab_pred, (size_t)c->nslot * GPRN_NBUF));
-        TRY(dev_alloc(c, &c->d_slotgp_all, c->nslot));
+        TRY(own.alloc(c, &c->tab_pred, (size_t)c->nslot * GPRN_NBUF));
+        TRY(own.alloc(c, &c->d_slotgp_all, c->nslot));
     }
     std::vector<double*> rows((size_t)c->nslot * GPRN_NBUF, nullptr);
     std::vector<int> staterow(nloc);
@@ -1017,7 +1015,7 @@ extern "C" int gprn_expected_loglike(gprn_ctx* c, double* logl_out)
     HIP_TRY(c, hipSetDevice(c->device));
     // (scal is not read by the launch we keep: a throw-away ELBO assembly over whatever the scalars hold)
     double* part = c->d_elbo_part;
-    if (c->out_cap < 1) { dev_free(c->d_out); TRY(dev_alloc(c, &c->d_out, 4)); c->out_cap = 1; }
+    TRY(dev_ensure(c, c->mem.out, c->d_out, 4));
     TRY(vec_elbo(c, c->d_out, c->d_scal_base, part));
     double h[GPRN_ELBO_PART_DOUBLES];
     HIP_TRY(c, hipMemcpyAsync(h, part, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -1114,13 +1112,7 @@ int test_setup(gprn_ctx* c, int ld, int nbuf_needed, int batch)
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); watch_progress(c);
     const size_t nn = (size_t)ld * ld * batch;
-    for (int b = 0; b < 3; ++b) {
-        if (b < nbuf_needed && c->test_cap[b] < nn) {
-            dev_free(c->d_test[b]);
-            TRY(dev_alloc(c, &c->d_test[b], nn));
-            c->test_cap[b] = nn;
-        }
-    }
+    for (int b = 0; b < nbuf_needed && b < 3; ++b) TRY(dev_ensure(c, c->mem.test[b], c->d_test[b], nn));
     return GPRN_OK;
 }
 

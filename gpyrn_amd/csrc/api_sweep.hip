@@ -35,11 +35,11 @@ static int ensure_small_sweep_tabs(gprn_ctx* c)
         if (!c->Kinv[j]) return bad(c, "small path: K_j^-1 of a node is missing (no set-up yet?)");
         ktab[j] = c->Kinv[j];
     }
-    dev_free(c->d_kinv_tab);
-    TRY(dev_alloc(c, &c->d_kinv_tab, (size_t)c->q));
+    c->mem.kinv_tab.release();                         // (a table of its own every time, as its contents change)
+    TRY(dev_ensure(c, c->mem.kinv_tab, c->d_kinv_tab, (size_t)c->q));
     HIP_TRY(c, hipMemcpy(c->d_kinv_tab, ktab.data(), ktab.size() * sizeof(double*), hipMemcpyHostToDevice));
     if (!c->d_small_ticket) {
-        TRY(dev_alloc(c, &c->d_small_ticket, 1));
+        TRY(c->mem.problem.alloc(c, &c->d_small_ticket, 1));
         HIP_TRY(c, hipMemset(c->d_small_ticket, 0, sizeof(unsigned)));
     }
     c->small_sweep_ready = true;
@@ -65,15 +65,15 @@ static int factor_priors_small(gprn_ctx* c, bool sync = true)
             rows[s * GPRN_NBUF + BUF_K] = c->K[g];
             rows[s * GPRN_NBUF + BUF_KLINV] = c->KLinv[g];
             if (g >= 1 && g < c->q && c->elbo_form == GPRN_ELBO_REFERENCE) {   // quirk Q1: node k < j needs K_j^-1
-                if (!c->Kinv[g]) { TRY(dev_alloc(c, &c->Kinv[g], nn)); c->small_sweep_ready = false; }
+                if (!c->Kinv[g]) { TRY(c->mem.problem.alloc(c, &c->Kinv[g], nn)); c->small_sweep_ready = false; }
                 kout[s] = c->Kinv[g];
             }
         }
         TRY(upload_table(c, c->tab_setup, rows));
         c->setup1_ready = false;                       // (the launch-path set-up's rows are gone)
         HIP_TRY(c, hipMemcpy(c->d_slotgp_setup, gps.data(), nj * sizeof(int), hipMemcpyHostToDevice));
-        dev_free(c->d_kinv_out);
-        TRY(dev_alloc(c, &c->d_kinv_out, (size_t)c->nslot));
+        c->mem.kinv_out.release();
+        TRY(dev_ensure(c, c->mem.kinv_out, c->d_kinv_out, (size_t)c->nslot));
         HIP_TRY(c, hipMemcpy(c->d_kinv_out, kout.data(), kout.size() * sizeof(double*), hipMemcpyHostToDevice));
         c->small_tabs_ready = true;
     }
@@ -107,7 +107,7 @@ static int factor_priors_single(gprn_ctx* c)
     gps.insert(gps.end(), c->loc_weights.begin(), c->loc_weights.end());
     const int nb = (int)gps.size(), n_inv = c->elbo_form == GPRN_ELBO_REFERENCE ? c->q - 1 : 0;   // (bound form: no quirk Q1)
     for (int j = 1; j <= n_inv; ++j)
-        if (!c->Kinv[j]) { TRY(dev_alloc(c, &c->Kinv[j], nn)); c->setup1_ready = false; }
+        if (!c->Kinv[j]) { TRY(c->mem.problem.alloc(c, &c->Kinv[j], nn)); c->setup1_ready = false; }
     if (!c->setup1_ready) {
         std::vector<double*> rows((size_t)c->nslot * GPRN_NBUF, nullptr);
         for (int s = 0; s < nb; ++s) {
@@ -119,8 +119,8 @@ static int factor_priors_single(gprn_ctx* c)
         TRY(upload_table(c, c->tab_setup, rows));
         HIP_TRY(c, hipMemcpy(c->d_slotgp_setup, gps.data(), nb * sizeof(int), hipMemcpyHostToDevice));
         if (n_inv > 0) {                                   // lower(K_j^-1) = lower(X^T X), X = chol(K_j)^-1: nodes 1 .. q - 1
-            dev_free(c->tab_kinv1);
-            TRY(dev_alloc(c, &c->tab_kinv1, (size_t)n_inv * GPRN_NBUF));
+            c->mem.tab_kinv1.release();
+            TRY(dev_ensure(c, c->mem.tab_kinv1, c->tab_kinv1, (size_t)n_inv * GPRN_NBUF));
             std::vector<double*> kr((size_t)n_inv * GPRN_NBUF, nullptr);
             for (int j = 1; j < c->q; ++j) {
                 kr[(size_t)(j - 1) * GPRN_NBUF + BUF_B] = c->Kinv[j];
@@ -210,7 +210,7 @@ static int factor_priors_impl(gprn_ctx* c)
         for (int s = 0; s < nb; ++s) {
             const int g = gps[s];
             if (g >= c->q || !need_inv[g]) continue;
-            if (!c->Kinv[g]) TRY(dev_alloc(c, &c->Kinv[g], nn));
+            if (!c->Kinv[g]) TRY(c->mem.problem.alloc(c, &c->Kinv[g], nn));
             std::vector<double*> one((size_t)c->nslot * GPRN_NBUF, nullptr);
             one[BUF_B] = c->Kinv[g];
             one[BUF_X] = rows[s * GPRN_NBUF + BUF_X];
@@ -349,7 +349,7 @@ static int run_phase(gprn_ctx* c, bool weights, double* scal, std::function<int(
             TRY(lauum_lower(c, ph));
             for (int s = 0; s < ns; ++s) {
                 if (!c->Sig[gps[s]]) {
-                    TRY(dev_alloc(c, &c->Sig[gps[s]], nn));
+                    TRY(c->mem.problem.alloc(c, &c->Sig[gps[s]], nn));
                     HIP_TRY(c, hipMemsetAsync(c->Sig[gps[s]], 0, nn * sizeof(double), c->stream));   // padding stays zero
                 }
                 TRY(vec_sigma(c, c->wsB[ph.slot0 + s], c->d_s + o + (size_t)s * c->ld, c->Sig[gps[s]]));
@@ -416,11 +416,7 @@ extern "C" int gprn_sweep(gprn_ctx* c, int n_sweeps, int commit, double* elbo_ou
 static int sweep_impl(gprn_ctx* c, int n_sweeps, int commit, double* elbo_out, double* parts_out, bool retry)
 {
     c->grad_ready = false;                           // set again below: by a committed call whose pivots all passed
-    if (n_sweeps > c->out_cap) {
-        dev_free(c->d_out);
-        TRY(dev_alloc(c, &c->d_out, 4 * (size_t)n_sweeps));
-        c->out_cap = n_sweeps;
-    }
+    TRY(dev_ensure(c, c->mem.out, c->d_out, 4 * (size_t)n_sweeps));
     const size_t dn = (size_t)(c->p + 1) * c->q * c->N * sizeof(double);
     const bool small = small_applies(c);
     // the state the call started from: what commit = 0 returns to, and what a re-run starts over from (the small path
@@ -550,7 +546,7 @@ static int elbocalc_small(gprn_ctx* c, const ElboIo& io, int max_iter, std::vect
     static int stamps_env = -1;                                // GPRN_SMALL_STAMPS=1 (probes): where a half-sweep's time goes
     if (stamps_env < 0) { const char* e = getenv("GPRN_SMALL_STAMPS"); stamps_env = e ? atoi(e) : 0; }
     if (stamps_env && !c->d_small_stamps) {
-        HIP_TRY(c, hipMalloc(&c->d_small_stamps, 8 * sizeof(unsigned long long)));
+        TRY(c->mem.problem.alloc(c, &c->d_small_stamps, 8));
         HIP_TRY(c, hipMemset(c->d_small_stamps, 0, 8 * sizeof(unsigned long long)));
     }
     TRY(build_tables(c));
@@ -558,21 +554,11 @@ static int elbocalc_small(gprn_ctx* c, const ElboIo& io, int max_iter, std::vect
     const size_t n_info = 3 * (size_t)c->nslot;
     // pinned staging: in = y_resid | variance | mu | var;  out = A | Av | B | Bv | batch history | ctl (4 ints) | info
     const size_t in_doubles = 2 * pn + 2 * d, out_doubles = 4 * d + K + 4 + (n_info + 1) / 2 + 2;
-    if (c->pin_in_cap < in_doubles) {
-        if (c->h_pin_in) hipHostFree(c->h_pin_in);
-        c->h_pin_in = nullptr; c->pin_in_cap = 0;
-        HIP_TRY(c, hipHostMalloc((void**)&c->h_pin_in, in_doubles * sizeof(double), hipHostMallocDefault));
-        c->pin_in_cap = in_doubles;
-    }
-    if (c->pin_out_cap < out_doubles) {
-        if (c->h_pin_out) hipHostFree(c->h_pin_out);
-        c->h_pin_out = nullptr; c->pin_out_cap = 0;
-        HIP_TRY(c, hipHostMalloc((void**)&c->h_pin_out, out_doubles * sizeof(double), hipHostMallocDefault));
-        c->pin_out_cap = out_doubles;
-    }
+    TRY(dev_ensure(c, c->mem.pin_in, c->h_pin_in, in_doubles));
+    TRY(dev_ensure(c, c->mem.pin_out, c->h_pin_out, out_doubles));
     if (!c->d_loop_ctl) {
-        HIP_TRY(c, hipMalloc(&c->d_loop_ctl, 4 * sizeof(int)));
-        TRY(dev_alloc(c, &c->d_loop_hist, (size_t)K + 4));
+        TRY(c->mem.problem.alloc(c, &c->d_loop_ctl, 4));
+        TRY(c->mem.problem.alloc(c, &c->d_loop_hist, (size_t)K + 4));
     }
     // ---- inputs
     double* const pin = c->h_pin_in;
@@ -606,7 +592,7 @@ static int elbocalc_small(gprn_ctx* c, const ElboIo& io, int max_iter, std::vect
     double* const A = c->d_mu; double* const Av = c->d_var;
     double* const B = c->d_mu_alt; double* const Bv = c->d_var_alt;
     double* const scal = c->d_scal_base;
-    if (c->out_cap < 1) { dev_free(c->d_out); TRY(dev_alloc(c, &c->d_out, 4)); c->out_cap = 1; }
+    TRY(dev_ensure(c, c->mem.out, c->d_out, 4));
     double* const po = c->h_pin_out;
     double* const hb = po + 4 * d;
     int* const ctl = reinterpret_cast<int*>(hb + K);

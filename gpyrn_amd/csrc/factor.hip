@@ -66,7 +66,6 @@ void tab_note(gprn_ctx* c, double** d_tab, double* const* rows, size_t count)
 
 void tab_forget(gprn_ctx* c, double** d_tab)
 {
-    if (!d_tab) { c->tab_host.clear(); return; }
     for (size_t i = 0; i < c->tab_host.size(); ++i)
         if (c->tab_host[i].first == d_tab) { c->tab_host.erase(c->tab_host.begin() + i); return; }
 }
@@ -272,12 +271,7 @@ int ensure_tasks(gprn_ctx* c, int T)
                                  BUF_B, BUF_X, BUF_X, tile_modes(CM_SET, 1, 1)});
     c->nlauum = v.size() - c->lauum0;
 
-    if (v.size() > c->tasks_cap) {
-        if (c->d_tasks) hipFree(c->d_tasks);
-        c->d_tasks = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_tasks, v.size() * sizeof(TileTask)));
-        c->tasks_cap = v.size();
-    }
+    if (const int rc = dev_ensure(c, c->mem.tasks, c->d_tasks, v.size())) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream2));
     HIP_TRY(c, hipMemcpyAsync(c->d_tasks, v.data(), v.size() * sizeof(TileTask),
                               hipMemcpyHostToDevice, c->stream));
@@ -321,8 +315,9 @@ __global__ void k_flag_multi(FlagOps ops, unsigned value, unsigned* timed_out)
 // `producer` raise it -- i.e. the two streams sit on different hardware queues
 static bool streams_overlap(hipStream_t waiter, hipStream_t producer)
 {
+    DeviceOwner own;
     unsigned* w = nullptr;                         // [0] flag, [2] time-out word, [3] budget in 100 MHz ticks, [4] which flag
-    if (hipMalloc(&w, 8 * sizeof(unsigned)) != hipSuccess) return false;
+    if (own.alloc(&w, 8, nullptr)) return false;
     const unsigned init[8] = {0u, 0u, 0u, 2000000u, 0u, 0u, 0u, 0u};
     bool ok = hipMemcpy(w, init, sizeof(init), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
@@ -332,7 +327,6 @@ static bool streams_overlap(hipStream_t waiter, hipStream_t producer)
     }
     unsigned out[8] = {0, 0, 1, 0, 0, 0, 0, 0};
     if (ok) ok = hipMemcpy(out, w, sizeof(out), hipMemcpyDeviceToHost) == hipSuccess;
-    hipFree(w);
     return ok && out[0] == 1u && out[2] == 0u;
 }
 
@@ -395,10 +389,8 @@ static int factor_invert_launches(gprn_ctx* c, const Phase& ph, FactorHooks& h, 
     enum { F_DIAG = 0, F_MINIL, F_INNER, F_PANEL, F_NEXT, F_REST, F_FIRST, F_XW, F_RESTA, F_TAIL, F_KINDS };
     static_assert(F_KINDS == GPRN_FLAG_KINDS, "factor_check_waits decodes the flag table by GPRN_FLAG_KINDS");
     if (use_flags && c->sig_T < T) {
-        if (c->d_sig) hipFree(c->d_sig);
-        c->d_sig = nullptr;
         // [T][F_KINDS] pairs {counter, flag}, then: sticky time-out word, budget of one wait, which flag timed out
-        HIP_TRY(c, hipMalloc(&c->d_sig, ((size_t)T * F_KINDS * 2 + 4) * sizeof(unsigned)));
+        if (const int rc = dev_ensure(c, c->mem.sig, c->d_sig, (size_t)T * F_KINDS * 2 + 4)) return rc;
         HIP_TRY(c, hipMemset(c->d_sig, 0, ((size_t)T * F_KINDS * 2 + 4) * sizeof(unsigned)));
         c->sig_T = T;
         c->epoch = 0;
@@ -816,11 +808,8 @@ int factor_invert(gprn_ctx* c, const Phase& ph, bool prior, FactorHooks* hooks)
     c->side_stamps = nullptr;
     if (step_stamps_env) {
         if (c->step_stamps_T < T) {
-            if (c->d_step_stamps) hipFree(c->d_step_stamps);
-            if (c->d_side_stamps) hipFree(c->d_side_stamps);
-            c->d_side_stamps = nullptr;
-            HIP_TRY(c, hipMalloc(&c->d_side_stamps, (size_t)T * 8 * sizeof(unsigned long long)));
-            HIP_TRY(c, hipMalloc(&c->d_step_stamps, (size_t)8 * T * 9 * sizeof(unsigned long long)));
+            if ((rc = dev_ensure(c, c->mem.side_stamps, c->d_side_stamps, (size_t)T * 8))) return rc;
+            if ((rc = dev_ensure(c, c->mem.step_stamps, c->d_step_stamps, (size_t)8 * T * 9))) return rc;
             c->step_stamps_T = T;
             c->step_stamps_n = 0;
         }

@@ -497,8 +497,9 @@ extern "C" int gprn_test_mfma_peak(gprn_ctx* c, int wg_per_cu, int iters, double
     hipDeviceProp_t prop;
     HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
     const int nwg = prop.multiProcessorCount * wg_per_cu;
+    DeviceOwner own;
     double* d = nullptr;
-    HIP_TRY(c, hipMalloc(&d, (size_t)nwg * 256 * sizeof(double)));
+    if (const int rc = own.alloc(c, &d, (size_t)nwg * 256)) return rc;
     hipEvent_t e0, e1;
     HIP_TRY(c, hipEventCreate(&e0));
     HIP_TRY(c, hipEventCreate(&e1));
@@ -510,6 +511,6 @@ extern "C" int gprn_test_mfma_peak(gprn_ctx* c, int wg_per_cu, int iters, double
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
     *tflops = (double)nwg * 4 * iters * 16 * 2048.0 / (ms * 1e-3) / 1e12;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return GPRN_OK;
 }

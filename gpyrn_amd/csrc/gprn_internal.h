@@ -14,6 +14,7 @@
 
 #include "../../include/gprn_hip.h"
 #include "batch_layout.h"
+#include "device_mem.h"
 
 #define GPRN_TILE 128          // tile edge of the blocked factorisation (nb)
 #define GPRN_KC 16             // K chunk staged through LDS per pipeline stage
@@ -202,8 +203,8 @@ struct gprn_ctx {
     double **tab_node = nullptr, **tab_weight = nullptr, **tab_setup = nullptr;  // [nslot][GPRN_NBUF]
     int *d_slotgp_node = nullptr, *d_slotgp_weight = nullptr, *d_slotgp_setup = nullptr;
     bool tables_ready = false;
-    // per-slot vectors (ld each): d, s, pred, w(=K pred), z, u, colsq, colt
-    double *d_d = nullptr, *d_s = nullptr, *d_pred = nullptr, *d_w = nullptr,
+    // per-slot vectors (ld each): d, s, pred, z, u, colsq, colt
+    double *d_d = nullptr, *d_s = nullptr, *d_pred = nullptr,
            *d_z = nullptr, *d_u = nullptr, *d_cs = nullptr, *d_ct = nullptr;
     double* d_part = nullptr;        // partial column sums scratch [nslot][T][2][ld]
     double* d_fin_terms = nullptr;   // k_reduce_finalize: per-element terms of tr B^-1 and log det B [nslot][2][ld]
@@ -213,8 +214,7 @@ struct gprn_ctx {
     double* d_scal_base = nullptr;   // two copies: a sweep's ELBO assembly may run beside the next sweep (sweep_impl)
     double* d_scal = nullptr;        // the copy the last sweep wrote (gprn_get_scalars)
     double* d_elbo_part = nullptr;   // scratch of the ELBO assembly, two copies
-    double* d_out = nullptr;         // per sweep: elbo, logl, logp, ent
-    int out_cap = 0;
+    double* d_out = nullptr;         // per sweep: elbo, logl, logp, ent (mem.out)
     int* d_info = nullptr;           // [3][nslot] first failing pivot per slot: setup, node phase, weight phase
     // prediction scratch (gprn_predict): K* and (X K*^T)^T per local GP, [ns_pad x ld] each
     std::vector<double*> predKs, predWT;
@@ -226,8 +226,7 @@ struct gprn_ctx {
     double **tab_pred = nullptr;
     int* d_slotgp_all = nullptr;
     // scratch of the diagnostic entry points
-    double* d_test[3] = {nullptr, nullptr, nullptr};
-    size_t test_cap[3] = {0, 0, 0};
+    double* d_test[3] = {nullptr, nullptr, nullptr};   // (mem.test)
     // tile-task lists for the factorisation at the current T (device)
     TileTask* d_tasks = nullptr;
     unsigned* d_sig = nullptr;       // completion signals of the chain: (tile step, kind) -> {counter, flag}
@@ -256,7 +255,6 @@ struct gprn_ctx {
     int step_stamps_batch[8] = {0};
     unsigned long long *d_side_stamps = nullptr, *side_stamps = nullptr;   // GPRN_STEP_STAMPS=2: stream3's clock, [T][8]
     int side_stamps_ph = -1;
-    size_t tasks_cap = 0;
     std::vector<TileTask> h_tasks;
     struct StepRange { size_t panel0, npanel_l, npanel, upd0, nupd, ncol1; };   // per tile step: panel (L part first, then X part), in-panel update (the first ncol1 tasks: the chain's own tile and the two its next step touches)
     // two sets: [0] throughput schedule (outer panel = GPRN_OUTER tiles), [1] latency schedule for
@@ -309,7 +307,6 @@ struct gprn_ctx {
     double* d_loop_hist = nullptr;   // ... the batch's ELBO values, then the loop's last three
     double *h_pin_in = nullptr, *h_pin_out = nullptr;    // pinned staging of gprn_elbocalc's inputs / read-backs
     void* small_batch = nullptr;     // SmallBatchMem (smalln.hip): buffers of gprn_elbocalc_batch
-    size_t pin_in_cap = 0, pin_out_cap = 0;
     bool small_tabs_ready = false;   // the set-up's tables for this problem are on the device (factor_priors_small)
     bool small_sweep_ready = false;  // ... and what a sweep of the small path reads beside the phase tables (ensure_small_sweep_tabs)
     bool setup1_ready = false;       // tab_setup / d_slotgp_setup / tab_kinv1 hold the unsharded launch-path set-up's rows (factor_priors_single)
@@ -320,8 +317,7 @@ struct gprn_ctx {
     int batch_mem_mb = -1;           // gprn_set_option "batch_mem_mb": device memory one chunk of evaluations may take; -1: a share of what is free
     // scratch of the batched gradient pass (grad.hip grad_batch_pass), on the context its launches go through: one piece that
     // only grows and stays until the problem is freed
-    void* grad_scratch = nullptr;
-    size_t grad_scratch_bytes = 0;
+    void* grad_scratch = nullptr;    // (mem.grad_scratch)
     int last_batch_chunk = 0;        // read-only option "batch_chunk": evaluations per chunk in the last gprn_elbocalc_batch call
     // ---- sweep order (gprn_set_sweep_order, order.hip)
     int sweep_order = 0;             // GPRN_ORDER_REFERENCE (Jacobi, quirk Q6) or GPRN_ORDER_SEQUENTIAL
@@ -329,9 +325,36 @@ struct gprn_ctx {
     int elbo_form = 0;               // gprn_set_option "elbo_form": GPRN_ELBO_REFERENCE (quirks Q1-Q3, Q5) or GPRN_ELBO_BOUND
     int predict_form = 0;            // gprn_set_option "predict_form": GPRN_PREDICT_REFERENCE (_gp.GP.prediction) or GPRN_PREDICT_POSTERIOR
     double* d_mu_old = nullptr;      // sequential order on the launch path: the means a phase started from (order_snapshot)
-    size_t mu_old_cap = 0;
     int n_states = 1;                // copies of the state behind d_mu (a batch's worker context: its evaluations)
+
+    // ---- device and pinned memory: every pointer field above is a VIEW of what ONE of these owners holds, an owner per
+    // lifetime (or of what is lent: a batch worker's d_mask, MidMaskLoan).  A group goes in one call, below the struct
+    struct Mem {
+        DeviceOwner ctx;                // until gprn_destroy: d_agree ...
+        DevBuf<TileTask> tasks;         // ... and what grows with T or with a diagnostic's size
+        DevBuf<unsigned> sig;
+        DevBuf<unsigned long long> step_stamps, side_stamps;
+        DevBuf<double> test[3];
+        DeviceOwner problem;            // until the next gprn_set_data: its arrays, K / KLinv / Kinv / Sig as they are made, the
+        DevBuf<double*> kinv_tab, kinv_out, tab_kinv1;   // small path's ticket, stamps and loop words; the regrowable ones
+        DevBuf<double> out, mu_old, pin_in{true}, pin_out{true};
+        DevBuf<char> grad_scratch;
+        DeviceOwner slots;              // what build_tables replaces with the slot count: wsB / wsX, phase tables, per-slot arrays
+        DeviceOwner mask_data;          // gprn_set_mask: d_mask, d_mask_U, d_mask_nU (a batch's worker: empty, its d_mask is lent)
+        DeviceOwner mask_bufs;          // mask_prepare: mask_WT, mask_C, tab_mask, d_mask_slot, d_mask_gp, d_mask_tasks
+        DeviceOwner pred;               // gprn_predict: predKs, predWT, tab_pred, d_slotgp_all
+    } mem;
 };
+// the groups' releases (api.hip), each: tab_forget of the group's tables, free, views null, sizes / ready flags reset
+void release_slots(gprn_ctx* c);
+void release_mask_data(gprn_ctx* c);
+void mask_free(gprn_ctx* c);            // (the mask buffers)
+void release_pred(gprn_ctx* c);
+void free_problem(gprn_ctx* c);         // the problem group and the four above, the batches, the host-side state
+void release_context(gprn_ctx* c);      // the context-lifetime group (gprn_destroy, behind free_problem)
+template <typename T, typename V>       // grow one of the context's DevBufs and point its view at it (null after a failed grow)
+static inline int dev_ensure(gprn_ctx* c, DevBuf<T>& buf, V*& view, size_t count)
+{ const int rc = buf.ensure(count, &c->err); view = (V*)buf.p; return rc; }
 
 // The matrices a call works on -- a half-sweep, a set-up, a prediction, a diagnostic -- passed by const reference to
 // everything that launches against them
@@ -453,7 +476,7 @@ int launch_panel(gprn_ctx* c, const TileTask* d_tasks, size_t n_l, size_t n_x, d
 struct PtrArgs { double* p[GPRN_ARG_SLOTS][2];
                  unsigned long long* stamps; };   // GPRN_STEP_STAMPS: 100 MHz clock stamps of this launch (3 words), or null
 void tab_note(gprn_ctx* c, double** d_tab, double* const* rows, size_t count);
-void tab_forget(gprn_ctx* c, double** d_tab);                    // d_tab null: all of them
+void tab_forget(gprn_ctx* c, double** d_tab);                    // (a table nobody noted, or null: nothing happens)
 // rows of `nbatch` matrices starting at d_ptrs if a host copy is known (and nbatch fits), else false
 bool tab_rows(gprn_ctx* c, double** d_ptrs, int nbatch, PtrArgs* out);
 unsigned long long* step_stamp_ptr(gprn_ctx* c, int k, int which);   // GPRN_STEP_STAMPS (factor.hip)
@@ -705,7 +728,6 @@ struct ChunkLeft {
 struct PredRows { double *kss, *lmean, *lvar, *omean, *ovar; };
 // The passes' kept buffers, charged to the driver's DeviceOwner (freed with the batch): there from the first call that asks for
 // a prediction or for draws, so that a call allocates and frees nothing on the device once they exist
-struct DeviceOwner;
 // gprn_elbocalc_batch_heldout: a chunk's fit masks and their rows U on the device, the task list of C = WT X^T for the call's
 // upad, and what the held-out pass writes on its way to the caller -- made with the driver's buffers (charged to its owner),
 // filled per chunk by upload() before the chunk's first launch
@@ -836,7 +858,6 @@ static inline size_t held_bytes_per_eval(const gprn_ctx* c)
 static inline MaskBatch mask_batch_of(const gprn_ctx* c, int ph)
 { return MaskBatch{nullptr, nullptr, 0, c->mask_upad_ph[ph], c->d_mask_tasks[ph], c->mask_ntasks[ph], c->d_mask_U, c->d_mask_nU, c->mask_upad}; }
 int mask_prepare(gprn_ctx* c);       // buffers, tables and task lists for the current slots (build_tables: the set-up)
-void mask_free(gprn_ctx* c);
 void mask_invalidate(gprn_ctx* c);   // the slots changed (build_tables rebuilds them)
 
 // order.hip: the sequential sweep order (no-ops under the reference's order and for q = 1).  order_snapshot before a

@@ -627,13 +627,9 @@ static int grad_batch_group(gprn_ctx* c, const ChunkLeft& in, const BatchIo& io,
                  at_cross = carve(3 * nj * nn * sizeof(double)), at_ptr = carve(n_ptr * sizeof(double*)),
                  at_int = carve(2 * nslots * sizeof(int)), at_slots = carve(nslots * sizeof(GradSlot)),
                  at_tasks = carve(tasks.size() * sizeof(TileTask));
-    if (w->grad_scratch_bytes < need) {
+    if (w->mem.grad_scratch.cap < need) {
         HIP_TRY(w, hipStreamSynchronize(st));
-        if (w->grad_scratch) hipFree(w->grad_scratch);
-        w->grad_scratch = nullptr; w->grad_scratch_bytes = 0;
-        char* fresh = nullptr;
-        TRY(dev_alloc(w, &fresh, need));
-        w->grad_scratch = fresh; w->grad_scratch_bytes = need;
+        TRY(dev_ensure(w, w->mem.grad_scratch, w->grad_scratch, need));
     }
     char* const base = (char*)w->grad_scratch;
     double* const u = (double*)(base + at_u); double* const a = (double*)(base + at_a);

@@ -165,25 +165,13 @@ void mask_invalidate(gprn_ctx* c)
     c->mask_ready = false;
 }
 
-void mask_free(gprn_ctx* c)
-{
-    for (auto& p : c->mask_WT) dev_free(p);
-    for (auto& p : c->mask_C) dev_free(p);
-    c->mask_WT.clear(); c->mask_C.clear();
-    for (int w = 0; w < 2; ++w) {
-        if (c->tab_mask[w]) tab_forget(c, c->tab_mask[w]);   // (a null argument forgets every table's host copy)
-        dev_free(c->tab_mask[w]); dev_free(c->d_mask_slot[w]); dev_free(c->d_mask_gp[w]); dev_free(c->d_mask_tasks[w]);
-        c->mask_n[w] = 0; c->mask_ntasks[w] = 0; c->mask_upad_ph[w] = 0;
-    }
-    c->mask_ready = false;
-}
-
 // Per phase: its entries (latent GPs with a U), their WT and C buffers (upad x ld each), pointer table, entry -> slot / GP
 // lists and the task list.  Part of the set-up (build_tables): nothing is allocated or copied inside a sweep.
 int mask_prepare(gprn_ctx* c)
 {
     if (!c->d_mask || c->mask_ready) return GPRN_OK;
     mask_free(c);
+    DeviceOwner& own = c->mem.mask_bufs;
     const int ld = c->ld, T = c->T;
     for (int w = 0; w < 2; ++w) {
         const std::vector<int>& gps = w ? c->loc_weights : c->loc_nodes;
@@ -202,19 +190,19 @@ int mask_prepare(gprn_ctx* c)
         std::vector<double*> rows((size_t)ne * GPRN_NBUF, nullptr);
         for (int e = 0; e < ne; ++e) {
             double *wt = nullptr, *cc = nullptr;
-            TRY(dev_alloc(c, &wt, need));
+            TRY(own.alloc(c, &wt, need));
             c->mask_WT.push_back(wt);
-            TRY(dev_alloc(c, &cc, need));
+            TRY(own.alloc(c, &cc, need));
             c->mask_C.push_back(cc);
             rows[(size_t)e * GPRN_NBUF + BUF_B] = c->wsB[first + es[e]];
             rows[(size_t)e * GPRN_NBUF + BUF_X] = c->wsX[first + es[e]];
             rows[(size_t)e * GPRN_NBUF + BUF_K] = wt;
             rows[(size_t)e * GPRN_NBUF + BUF_KLINV] = cc;
         }
-        TRY(dev_alloc(c, &c->tab_mask[w], rows.size()));
+        TRY(own.alloc(c, &c->tab_mask[w], rows.size()));
         TRY(upload_table(c, c->tab_mask[w], rows));
-        TRY(dev_alloc(c, &c->d_mask_slot[w], (size_t)ne));
-        TRY(dev_alloc(c, &c->d_mask_gp[w], (size_t)ne));
+        TRY(own.alloc(c, &c->d_mask_slot[w], (size_t)ne));
+        TRY(own.alloc(c, &c->d_mask_gp[w], (size_t)ne));
         HIP_TRY(c, hipMemcpy(c->d_mask_slot[w], es.data(), ne * sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(c->d_mask_gp[w], eg.data(), ne * sizeof(int), hipMemcpyHostToDevice));
         // C = WT X^T by 128 x 128 tiles: row tile bt of U, column tile at of X (lower: K runs to the end of that tile)
@@ -224,7 +212,7 @@ int mask_prepare(gprn_ctx* c)
                 tasks.push_back(TileTask{(int64_t)bt * GPRN_TILE * ld + (int64_t)at * GPRN_TILE,
                                          (int64_t)bt * GPRN_TILE * ld, (int64_t)at * GPRN_TILE * ld,
                                          (at + 1) * GPRN_TILE, BUF_KLINV, BUF_K, BUF_X, tile_modes(CM_SET, 0, 0)});
-        TRY(dev_alloc(c, &c->d_mask_tasks[w], tasks.size()));
+        TRY(own.alloc(c, &c->d_mask_tasks[w], tasks.size()));
         HIP_TRY(c, hipMemcpy(c->d_mask_tasks[w], tasks.data(), tasks.size() * sizeof(TileTask), hipMemcpyHostToDevice));
         c->mask_ntasks[w] = tasks.size();
         c->mask_n[w] = ne;
@@ -300,8 +288,7 @@ extern "C" int gprn_set_mask(gprn_ctx* c, const uint8_t* mask)
     // (the batches' cached argument blocks, lanes and slabs are the old mask's: gprn_elbocalc_batch under "batch_mask")
     small_batch_free(c);
     mid_batch_free(c);
-    dev_free(c->d_mask); dev_free(c->d_mask_U); dev_free(c->d_mask_nU);
-    c->h_mask.clear(); c->mask_U.clear(); c->mask_upad = 0;
+    release_mask_data(c);
     c->factored = false;                 // the set-up runs on the path the sweeps will take (small_applies)
     c->grad_ready = false;
     c->small_tabs_ready = false; c->small_sweep_ready = false; c->setup1_ready = false;
@@ -316,12 +303,10 @@ extern "C" int gprn_set_mask(gprn_ctx* c, const uint8_t* mask)
     }
     c->h_mask.assign(mask, mask + (size_t)p * N);
     for (auto& b : c->h_mask) b = b ? 1 : 0;
-    uint8_t* dm = nullptr;
-    HIP_TRY(c, hipMalloc(&dm, c->h_mask.size()));
-    c->d_mask = dm;
+    TRY(c->mem.mask_data.alloc(c, &c->d_mask, c->h_mask.size()));
     HIP_TRY(c, hipMemcpy(c->d_mask, c->h_mask.data(), c->h_mask.size(), hipMemcpyHostToDevice));
-    TRY(dev_alloc(c, &c->d_mask_U, hU.size()));
-    TRY(dev_alloc(c, &c->d_mask_nU, (size_t)G));
+    TRY(c->mem.mask_data.alloc(c, &c->d_mask_U, hU.size()));
+    TRY(c->mem.mask_data.alloc(c, &c->d_mask_nU, (size_t)G));
     HIP_TRY(c, hipMemcpy(c->d_mask_U, hU.data(), hU.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_mask_nU, hn.data(), hn.size() * sizeof(int), hipMemcpyHostToDevice));
     c->mask_U = U;

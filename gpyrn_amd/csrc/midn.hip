@@ -132,18 +132,16 @@ static int mid_make(gprn_ctx* c, MidBatch* m, int cap)
     w->h_yerr2 = c->h_yerr2;
     w->world = 1; w->rank = 0;
     w->owner.assign(G, 0);
-    w->out_cap = cap;
     w->n_states = cap;
-    TRY(dev_alloc(c, &w->d_time, (size_t)N));
-    TRY(dev_alloc(c, &w->d_yraw, pn));
-    TRY(dev_alloc(c, &w->d_mu, (size_t)cap * d));
-    TRY(dev_alloc(c, &w->d_var, (size_t)cap * d));
-    TRY(dev_alloc(c, &w->d_yres, (size_t)cap * pn));
-    TRY(dev_alloc(c, &w->d_variance, (size_t)cap * pn));
-    TRY(dev_alloc(c, &w->d_logdetK, (size_t)cap * G));
-    TRY(dev_alloc(c, &w->d_scal_base, (size_t)cap * nscal));
-    TRY(dev_alloc(c, &w->d_elbo_part, (size_t)cap * GPRN_ELBO_PART_DOUBLES));
-    TRY(dev_alloc(c, &w->d_out, (size_t)ELBO_LEAD * cap * 4));      // (one block of results per sweep enqueued ahead)
+    DeviceOwner& own = w->mem.problem;                    // (the worker's arrays are the worker's: its problem and slot groups)
+    TRY(own.alloc(c, &w->d_time, (size_t)N));
+    TRY(own.alloc(c, &w->d_yraw, pn));
+    for (double** a : {&w->d_mu, &w->d_var}) TRY(own.alloc(c, a, (size_t)cap * d));
+    for (double** a : {&w->d_yres, &w->d_variance}) TRY(own.alloc(c, a, (size_t)cap * pn));
+    TRY(own.alloc(c, &w->d_logdetK, (size_t)cap * G));
+    TRY(own.alloc(c, &w->d_scal_base, (size_t)cap * nscal));
+    TRY(own.alloc(c, &w->d_elbo_part, (size_t)cap * GPRN_ELBO_PART_DOUBLES));
+    TRY(dev_ensure(c, w->mem.out, w->d_out, (size_t)ELBO_LEAD * cap * 4));   // (one block of results per sweep enqueued ahead)
     if (const int rc = alloc_slot_arrays(w, (int)nslot)) { c->err = w->err; return rc; }
     HIP_TRY(c, hipMemcpy(w->d_time, c->d_time, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice));
     HIP_TRY(c, hipMemcpy(w->d_yraw, c->d_yraw, pn * sizeof(double), hipMemcpyDeviceToDevice));
@@ -509,7 +507,8 @@ static void mid_follow(const gprn_ctx* c, gprn_ctx* w)
 }
 
 // The worker BORROWS the parent's data mask for the length of a run (the mask is the data's: one for all evaluations) and
-// hands it back before anything could free it: free_problem(w) / gprn_destroy(w) never see the parent's device arrays.
+// hands it back at its end.  The field is a view: the worker's own mask-data group (gprn_ctx::Mem) is empty, so free_problem(w) /
+// gprn_destroy(w) can free nothing of the parent's through it, whether or not this destructor ran.
 // With it phase_core takes the masked vec_prep / finalize instantiations and ends in mask_rows over the batch's lanes.
 struct MidMaskLoan {
     gprn_ctx* w;

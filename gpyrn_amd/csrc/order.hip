@@ -146,12 +146,7 @@ int order_snapshot(gprn_ctx* c, const Phase& ph)
 {
     if (!order_on(c) || !ph.nslots) return GPRN_OK;
     const size_t n = (size_t)c->n_states * (size_t)(c->p + 1) * c->q * c->N;
-    if (c->mu_old_cap < n) {
-        dev_free(c->d_mu_old);
-        c->mu_old_cap = 0;
-        TRY(dev_alloc(c, &c->d_mu_old, n));
-        c->mu_old_cap = n;
-    }
+    TRY(dev_ensure(c, c->mem.mu_old, c->d_mu_old, n));
     HIP_TRY(c, hipMemcpyAsync(c->d_mu_old, c->d_mu, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return GPRN_OK;
 }

@@ -610,7 +610,8 @@ int gprn_predict_batch(gprn_ctx* ctx, int n_eval, const double* kernel_params, i
  * of two tiles too; 0: the launch schedule at every size; same results to rounding); "batch_mem_mb" (device memory, MiB, that
  * one chunk of gprn_elbocalc_batch's evaluations may take: longer lists run chunk by chunk; default: half of what is free, 48 GiB
  * at most; when the device cannot give that much in one piece the chunk is halved until it can); "batch_chunk" (read-only:
- * evaluations per chunk in the last gprn_elbocalc_batch call); "batch_mask" (0, the default: gprn_elbocalc_batch and
+ * evaluations per chunk in the last gprn_elbocalc_batch call); "live_allocs" / "allocs_made" (read-only, process-wide: device and
+ * pinned allocations the library holds now / has made since it was loaded); "batch_mask" (0, the default: gprn_elbocalc_batch and
  * gprn_elbocalc_batch_grad refuse a context with a data mask; 1: they run under it -- side by side every evaluation starts from
  * one shared state, which moves rule-stopped values within the stop rule's 1e-3 against one evaluation after the other);
  * "order_mask" (0, the default: gprn_set_mask refuses a context in the sequential sweep order and gprn_set_sweep_order refuses
