@@ -2,6 +2,7 @@
 // posterior draws, kernel matrices and prior draws (:413-434,
 // 517-539), the gradient's pieces, the ELBO's terms on their own (:895-1093), diagnostics.
 #include "api_internal.h"
+#include "fill_shared.h"
 
 // ------------------------------------------------------------------ prediction
 // Conditional mean / variance of every latent GP at new times, from the current variational
@@ -288,15 +289,7 @@ static int predict_impl(gprn_ctx* c, int ns, const double* tstar, double* mean_o
 // Draws: C_g + nu_g I = L_g L_g^T by the blocked factorisation, nu_g = 1.25e-12 x 100^k up to 1.25e-6 (the ladder of
 // inference._sample_from_gp), latent draw = mean + L z, output draw sum_j w_ij o f_j (mean functions and noise: host).
 
-#define GPRN_COV_BLK 32
-// the lower 32 x 32 blocks of an n x n grid, block L -> (bi, bj), bi >= bj
-__device__ __forceinline__ void lower_block(int L, int& bi, int& bj)
-{
-    bi = (int)((sqrt(8.0 * L + 1.0) - 1.0) * 0.5);
-    while ((bi + 1) * (bi + 2) / 2 <= L) ++bi;
-    while (bi * (bi + 1) / 2 > L) --bi;
-    bj = L - bi * (bi + 1) / 2;
-}
+#define GPRN_COV_BLK 32      // the lower 32 x 32 blocks of an n x n grid (fill_shared.h, lower_block)
 
 // upper triangle := lower triangle, every matrix of the table (pitch n_pad, all n_pad rows); block (bi, bj) of the
 // lower triangle goes through LDS to (bj, bi).  grid (lower blocks, matrices)

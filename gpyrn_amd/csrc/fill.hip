@@ -1,21 +1,25 @@
-// Fused pairwise-difference + covariance fill:  K[m][n] = k(t_m, t_n) (+ nugget).
+// Fused pairwise-difference + covariance fill:  K[m][n] = k(t_m, t_n) (+ nugget), each element from two reads of the time
+// vector and written once (inference._KMatrix, meanfield.py:413-434, over covFunction.__call__).  The element arithmetic is
+// fill_eval.h's; this file holds ONE body per shape, and every kernel of a shape is a caller of a few lines that says where
+// the program comes from (a kernel argument, or device memory through LDS: one matrix per grid y / z) and which element
+// functor the body makes of it -- so single and batched launches have the same bits by construction.
 //
-// Replaces inference._KMatrix (meanfield.py:413-434) over covFunction.__call__
-// (covfunc.py, line numbers per kernel in include/gprn_hip.h): the reference
-// materialises r = t[:,None]-t[None,:] and 5-8 more N x N temporaries per
-// kernel; here each element is produced from two reads of the time vector
-// (L2 resident) and written once -- 8 N^2 bytes of HBM traffic per matrix.
+//   shape                              body                   kernels
+//   full matrix (Polynomial)           k_fill                 k_fill<KID>
+//   symmetric, lower 64 x 64 blocks    fill_sym_block         k_fill_sym<KID>, k_fill_sym_batch<DIAG>
+//   K* and k**, reference form         fill_rect_rows         k_fill_rect<KID, false>, k_fill_rect_batch
+//   K* diag(s) and k**, posterior form fill_rect_rows_post    k_fill_rect<KID, true>, k_fill_rect_batch_post<PROGRAM>
+//   equal prediction times in K**      fill_coincide_row      k_fill_coincide, k_fill_coincide_b
+//   dK/dtheta, lower 64 x 64 blocks    k_fill_grad            (and the ELBO's gradient rows: k_grad_fd_rows, k_grad_exact_rows)
 //
-// A kernel expression (Sum / Multiplication trees of built-ins, covfunc.py:65-77)
-// arrives as a postfix program evaluated per element on a tiny register stack.
-// Formulas follow the reference's operation order so host and device agree to
-// rounding (device libm vs NumPy: <= 2 ulp).
+// Host side: with_kid turns a program's kernel id into an instantiation, launched wraps every launch in the profiler's
+// family and the launch error, fill_shared.h decides what a one-kernel program is and which block a workgroup owns.
 #include "gprn_internal.h"
 
 #include <math.h>
 #include <string.h>
 
-#include "fill_eval.h"
+#include "fill_shared.h"
 #include "dk_eval.h"
 
 // One instantiation per built-in kernel id (KID >= 0: the switch in eval_kernel folds away, each
@@ -28,6 +32,35 @@ __device__ __forceinline__ double eval_any(const FillProgram& pg, double ti, dou
     else if constexpr (KID >= 0) return eval_kernel(KID, pg.par, ti, tj, diag);
     else return eval_program(pg, ti, tj, diag);
 }
+
+// The element of a fill as a functor that a shared body makes of the program it is given, a local VALUE of the body.
+// ArgElem: a single launch, the kernel's own instantiation on the program it got as an argument.  FillElem: a batched
+// launch, whose program lies in LDS -- the three kernels that carry host-computed reciprocals (SE, Periodic, QP) take their
+// handful of parameters into registers and run their own instruction stream, everything else goes through the postfix
+// program where it lies.  Either way the arithmetic is eval_kernel's on the same values.
+// (Why the body and not its caller makes it: registers of k_fill_rect_batch_post<false>, profiles/fill_bodies_isa_resources.txt.)
+template <int KID>
+struct ArgElem {
+    const FillProgram& pg;
+    __device__ __forceinline__ explicit ArgElem(const FillProgram& p) : pg(p) {}
+    __device__ __forceinline__ double operator()(double ti, double tj, bool diag) const { return eval_any<KID>(pg, ti, tj, diag); }
+};
+template <int KID>
+struct FillElem {
+    double par[4], aux[3];
+    __device__ __forceinline__ explicit FillElem(const FillProgram& pg)
+    {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) par[i] = pg.par[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) aux[i] = pg.aux[i];
+    }
+    __device__ __forceinline__ double operator()(double ti, double tj, bool diag) const { return eval_kernel(KID, par, ti, tj, diag, aux); }
+};
+template <>
+struct FillElem<-1> : ArgElem<-1> {
+    using ArgElem<-1>::ArgElem;
+};
 
 // one block = 8 rows x 256 columns; each thread 8 rows x 1 column -> per row the
 // 256 threads write 2 KiB contiguous.  Padded region (>= N) becomes identity so
@@ -70,40 +103,43 @@ void k_fill(FillProgram pg, const double* __restrict__ t, double* __restrict__ K
 // 4.9 TB/s, a kernel that stores a constant in the same pattern 23.6 us = 5.7 TB/s (32-row strips, 256-byte segments in
 // the mirror image: 5 % slower); one column per thread with the device library's exp / sinpi, as in rounds 1-2: 29.6 /
 // 40.8 us in the same bench.  (Into ONE matrix over and over the same kernels take 20.5 / 23.6 us: the 256 MB cache.)
-template <int KID>
-__global__ __launch_bounds__(256)
-void k_fill_sym(FillProgram pg, const double* __restrict__ t, double* __restrict__ K, int N, int ld,
-                const double* __restrict__ diag_add)
+//
+// The body of both symmetric kernels: block blockIdx.x of the lower triangle of K (and of its second copy K2, or null: the
+// set-up factors a copy in place) from the program pg through the functor Elem; diag (or null): N values that the diagonal
+// gets on top, behind the nugget.  A null that the caller passes as a constant folds away.
+template <class Elem>
+__device__ __forceinline__ void fill_sym_block(const FillProgram& pg, const double* __restrict__ t,
+                                               double* __restrict__ K, double* __restrict__ K2, int N, int ld,
+                                               double (*tile)[65], const double* __restrict__ diag)
 {
+    const Elem eval(pg);
+    const int nugget = pg.nugget;
+    const double nugget_val = pg.nugget_val;
     constexpr int TR = 64;
-    __shared__ double tile[TR][65];
-    // lower-triangular block index -> (bi, bj), bi >= bj
-    const int L = blockIdx.x, sub = 0;
-    int bi = (int)((sqrt(8.0 * L + 1.0) - 1.0) * 0.5);
-    while ((bi + 1) * (bi + 2) / 2 <= L) ++bi;
-    while (bi * (bi + 1) / 2 > L) --bi;
-    const int bj = L - bi * (bi + 1) / 2;
+    int bi, bj;
+    lower_block(blockIdx.x, bi, bj);
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int n = bj * 64 + 2 * tx;                // ld is a multiple of 128: n + 1 < ld
     const double tn0 = (n < N) ? t[n] : 0.0, tn1 = (n + 1 < N) ? t[n + 1] : 0.0;
-    const int row0 = bi * 64 + sub * TR;
+    const int row0 = bi * 64;
 #pragma unroll 2
     for (int i = 0; i < TR / 8; ++i) {
         const int r = ty + 8 * i, m = row0 + r;
         const double tm = (m < N) ? t[m] : 0.0;
         // (both evaluated unconditionally, on zeros in the padding: one straight-line instruction stream for the pair)
-        double v0 = eval_any<KID>(pg, tm, tn0, m == n);
-        double v1 = eval_any<KID>(pg, tm, tn1, m == n + 1);
+        double v0 = eval(tm, tn0, m == n);
+        double v1 = eval(tm, tn1, m == n + 1);
         if (m == n || m == n + 1) {
             double d = (m == n) ? v0 : v1;
-            if (pg.nugget) d += pg.nugget_val;
-            if (diag_add && m < N) d += diag_add[m];
+            if (nugget) d += nugget_val;
+            if (diag && m < N) d += diag[m];
             if (m == n) v0 = d; else v1 = d;
         }
         // the padded region (>= N) becomes identity so that the blocked factorisation can run on whole tiles
         if (m >= N || n >= N) v0 = (m == n) ? 1.0 : 0.0;
         if (m >= N || n + 1 >= N) v1 = (m == n + 1) ? 1.0 : 0.0;
         *(double2*)(K + (size_t)m * ld + n) = make_double2(v0, v1);
+        if (K2) *(double2*)(K2 + (size_t)m * ld + n) = make_double2(v0, v1);
         tile[r][2 * tx] = v0;
         tile[r][2 * tx + 1] = v1;
     }
@@ -114,8 +150,19 @@ void k_fill_sym(FillProgram pg, const double* __restrict__ t, double* __restrict
 #pragma unroll
     for (int idx = threadIdx.x; idx < 64 * CP; idx += 256) {
         const int c = idx / CP, rp = idx % CP;
-        *(double2*)(K + (size_t)(bj * 64 + c) * ld + row0 + 2 * rp) = make_double2(tile[2 * rp][c], tile[2 * rp + 1][c]);
+        const double2 v = make_double2(tile[2 * rp][c], tile[2 * rp + 1][c]);
+        *(double2*)(K + (size_t)(bj * 64 + c) * ld + row0 + 2 * rp) = v;
+        if (K2) *(double2*)(K2 + (size_t)(bj * 64 + c) * ld + row0 + 2 * rp) = v;
     }
+}
+
+template <int KID>
+__global__ __launch_bounds__(256)
+void k_fill_sym(FillProgram pg, const double* __restrict__ t, double* __restrict__ K, int N, int ld,
+                const double* __restrict__ diag_add)
+{
+    __shared__ double tile[64][65];
+    fill_sym_block<ArgElem<KID>>(pg, t, K, nullptr, N, ld, tile, diag_add);
 }
 
 static bool program_is_even(const FillProgram& pg)
@@ -125,15 +172,34 @@ static bool program_is_even(const FillProgram& pg)
     return true;
 }
 
-// host-side choice of the instantiation: the id of a one-kernel program, else the generic one
+// host-side choice of the instantiation: f gets the id of a one-kernel program (program_kid), else -1 for the generic one, as
+// a std::integral_constant -- which converts to its value where a template argument is asked for (as with_flags' do)
 #define GPRN_FOR_EACH_KID(X) \
     X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) \
     X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26)
 static_assert(GPRN_K_COUNT == 27, "add the new kernel id to GPRN_FOR_EACH_KID");
-
-static int program_kid(const FillProgram& pg)
+template <class F> static void with_kid(int kid, F&& f)
 {
-    return (pg.n_ops == 1 && pg.ops[1] >= 0 && pg.ops[1] < GPRN_K_COUNT && pg.ops[2] == 0) ? pg.ops[1] : -1;
+    switch (kid) {
+#define X(id) case id: f(std::integral_constant<int, id>{}); break;
+    GPRN_FOR_EACH_KID(X)
+#undef X
+    default: f(std::integral_constant<int, -1>{});
+    }
+}
+
+// what every launcher here does around its launches: the profiler's family, then the launch error.  A body may return a
+// status of its own (nothing was launched: no launch error is asked for)
+template <class F> static int launched(gprn_ctx* c, int family, F&& body)
+{
+    prof_begin(c, family);
+    int rc = GPRN_OK;
+    if constexpr (std::is_void<decltype(body())>::value) body();
+    else rc = body();
+    prof_end(c);
+    if (rc != GPRN_OK) return rc;
+    HIP_TRY(c, hipGetLastError());
+    return GPRN_OK;
 }
 
 static void make_program(const KernelSpec& ks, double nugget_val, FillProgram& pg)
@@ -204,26 +270,24 @@ void k_sum_fixed(const double* __restrict__ part, int n, double* __restrict__ ou
 int launch_grad_fd(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, const double* P, const double* a,
                    double* part, double* out)
 {
-    prof_begin(c, GPRN_T_VEC);
-    for (int l = 0; l < ks.n_params; ++l) {
-        FillProgram pp, pm;
-        make_program(ks, 0.0, pp);
-        make_program(ks, 0.0, pm);
-        const double v = ks.params[l], h = 1e-6 * fmax(1.0, fabs(v));
-        // -D(h) / 3, then + 4 D(h/2) / 3 (the same steps and weights as covfunc._richardson)
-        for (int k = 0; k < 2; ++k) {
-            const double s = k ? 0.5 * h : h;
-            pp.par[l] = v + s;
-            pm.par[l] = v - s;
-            const double coef = (k ? 4.0 : -1.0) / (3.0 * (2 * s));
-            hipLaunchKernelGGL(k_grad_fd_rows, dim3((c->N + 3) / 4), dim3(256), 0, c->stream, pp, pm, coef, k, c->d_time,
-                               Kinv, P, a, c->N, c->ld, part);
+    return launched(c, GPRN_T_VEC, [&] {
+        for (int l = 0; l < ks.n_params; ++l) {
+            FillProgram pp, pm;
+            make_program(ks, 0.0, pp);
+            make_program(ks, 0.0, pm);
+            const double v = ks.params[l], h = 1e-6 * fmax(1.0, fabs(v));
+            // -D(h) / 3, then + 4 D(h/2) / 3 (the same steps and weights as covfunc._richardson)
+            for (int k = 0; k < 2; ++k) {
+                const double s = k ? 0.5 * h : h;
+                pp.par[l] = v + s;
+                pm.par[l] = v - s;
+                const double coef = (k ? 4.0 : -1.0) / (3.0 * (2 * s));
+                hipLaunchKernelGGL(k_grad_fd_rows, dim3((c->N + 3) / 4), dim3(256), 0, c->stream, pp, pm, coef, k, c->d_time,
+                                   Kinv, P, a, c->N, c->ld, part);
+            }
+            hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(256), 0, c->stream, (const double*)part, c->N, out + l);
         }
-        hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(256), 0, c->stream, (const double*)part, c->N, out + l);
-    }
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
+    });
 }
 
 // ---- the same gradient with the EXACT parameter derivatives of the program (dk_eval.h; option "grad_exact"): one launch in
@@ -288,13 +352,11 @@ int launch_grad_exact(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, con
     FillProgram pg;
     make_program(ks, 0.0, pg);
     HIP_TRY(c, hipMemsetAsync(part, 0, (size_t)ks.n_params * c->N * sizeof(double), c->stream));
-    prof_begin(c, GPRN_T_VEC);
-    hipLaunchKernelGGL(k_grad_exact_rows, dim3((c->N + 3) / 4), dim3(256), 0, c->stream, pg, c->d_time, Kinv, P, a, c->N,
-                       c->ld, part);
-    hipLaunchKernelGGL(k_sum_fixed, dim3(ks.n_params), dim3(256), 0, c->stream, (const double*)part, c->N, out);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
+    return launched(c, GPRN_T_VEC, [&] {
+        hipLaunchKernelGGL(k_grad_exact_rows, dim3((c->N + 3) / 4), dim3(256), 0, c->stream, pg, c->d_time, Kinv, P, a, c->N,
+                           c->ld, part);
+        hipLaunchKernelGGL(k_sum_fixed, dim3(ks.n_params), dim3(256), 0, c->stream, (const double*)part, c->N, out);
+    });
 }
 
 // ---- dK/dtheta_l itself (gprn_eval_kernel_grad): dK[(l * N + m) * N + n] for every parameter l of the program, by the exact
@@ -305,11 +367,8 @@ int launch_grad_exact(gprn_ctx* c, const KernelSpec& ks, const double* Kinv, con
 __global__ __launch_bounds__(256)
 void k_fill_grad(FillProgram pg, const double* __restrict__ t, double* __restrict__ dK, int N)
 {
-    const int L = blockIdx.x;
-    int bi = (int)((sqrt(8.0 * L + 1.0) - 1.0) * 0.5);
-    while ((bi + 1) * (bi + 2) / 2 <= L) ++bi;
-    while (bi * (bi + 1) / 2 > L) --bi;
-    const int bj = L - bi * (bi + 1) / 2;
+    int bi, bj;
+    lower_block(blockIdx.x, bi, bj);
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const size_t nn = (size_t)N * N;
 #pragma unroll 1
@@ -346,11 +405,9 @@ int launch_fill_grad(gprn_ctx* c, const KernelSpec& ks, double* dK)
     make_program(ks, 0.0, pg);
     const int nb = (c->N + 63) / 64;
     HIP_TRY(c, hipMemsetAsync(dK, 0, (size_t)ks.n_params * c->N * c->N * sizeof(double), c->stream));
-    prof_begin(c, GPRN_T_FILL);
-    hipLaunchKernelGGL(k_fill_grad, dim3(nb * (nb + 1) / 2), dim3(256), 0, c->stream, pg, c->d_time, dK, c->N);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
+    return launched(c, GPRN_T_FILL, [&] {
+        hipLaunchKernelGGL(k_fill_grad, dim3(nb * (nb + 1) / 2), dim3(256), 0, c->stream, pg, c->d_time, dK, c->N);
+    });
 }
 
 int launch_fill(gprn_ctx* c, const KernelSpec& ks, double* K, double nugget_val, const double* diag_add)
@@ -365,100 +422,26 @@ int launch_fill_times(gprn_ctx* c, const KernelSpec& ks, double* K, double nugge
 {
     FillProgram pg;
     make_program(ks, nugget_val, pg);
-    prof_begin(c, GPRN_T_FILL);
     static int use_sym = -1;                       // GPRN_FILL_SYM=0: always the full-matrix kernel
     if (use_sym < 0) { const char* e = getenv("GPRN_FILL_SYM"); use_sym = e ? atoi(e) : 1; }
-    if (use_sym && program_is_even(pg)) {          // ld is a multiple of 128
-        const int nb = ld / 64;
-        dim3 tri(nb * (nb + 1) / 2);
-        switch (program_kid(pg)) {
-#define X(id) case id: hipLaunchKernelGGL(k_fill_sym<id>, tri, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add); break;
-        GPRN_FOR_EACH_KID(X)
-#undef X
-        default: hipLaunchKernelGGL(k_fill_sym<-1>, tri, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add);
-        }
-        prof_end(c);
-        HIP_TRY(c, hipGetLastError());
-        return GPRN_OK;
-    }
-    dim3 grid((ld + 255) / 256, (ld + 7) / 8);
-    switch (program_kid(pg)) {
-#define X(id) case id: hipLaunchKernelGGL(k_fill<id>, grid, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add); break;
-    GPRN_FOR_EACH_KID(X)
-#undef X
-    default: hipLaunchKernelGGL(k_fill<-1>, grid, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add);
-    }
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
+    const bool sym = use_sym && program_is_even(pg);
+    const int nb = ld / 64;                        // ld is a multiple of 128
+    const dim3 tri(nb * (nb + 1) / 2), full((ld + 255) / 256, (ld + 7) / 8);
+    return launched(c, GPRN_T_FILL, [&] {
+        with_kid(program_kid(pg), [&](auto kid) {
+            if (sym) hipLaunchKernelGGL(k_fill_sym<kid>, tri, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add);
+            else hipLaunchKernelGGL(k_fill<kid>, full, dim3(256), 0, c->stream, pg, t, K, N, ld, diag_add);
+        });
+    });
 }
 
 // ---- many matrices in one launch (gprn_elbocalc_batch: smalln.hip, midn.hip): matrix b of the launch has its own program
-// (device memory) and its own destination(s); one workgroup per lower 64 x 64 block as in k_fill_sym, the same two columns x
-// 8 rows per thread.  The program comes into LDS once per workgroup; the three kernels that carry host-computed reciprocals
-// (SE, Periodic, QP) take their handful of parameters into registers and run their own instruction stream, so that a
-// matrix filled here has the bits of one filled by launch_fill; everything else goes through the postfix program.
+// (device memory) and its own destination(s); fill_sym_block on a program that comes into LDS once per workgroup, with
+// FillElem's instruction stream per kind of program, so that a matrix filled here has the bits of one filled by launch_fill.
 // (The first version read the program from global memory inside the element loop: 1.04 ms for 256 matrices of 512^2,
-// 0.5 TB/s -- profiles/r05_batch512_first_kernel_stats.txt.)  K2: a second copy of every matrix (the set-up factors a
-// copy of K in place), or null.  DIAG (gprn_predict_batch): matrix b also gets diags[b][m] on its diagonal, m < N, behind the
-// nugget -- the bits of launch_fill with diag_add; the instantiation without it is the kernel the ELBO batches always had.
-template <int KID, bool DIAG>
-__device__ __forceinline__ void fill_sym_batch_block(const FillProgram& pg, const double* __restrict__ t, double* __restrict__ K,
-                                                     double* __restrict__ K2, int N, int ld, double (*tile)[65],
-                                                     const double* __restrict__ diag)
-{
-    constexpr int TR = 64;
-    double par[4] = {0.0, 0.0, 0.0, 0.0}, aux[3] = {0.0, 0.0, 0.0};
-    if (KID >= 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) par[i] = pg.par[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) aux[i] = pg.aux[i];
-    }
-    const int nugget = pg.nugget;
-    const double nugget_val = pg.nugget_val;
-    const int L = blockIdx.x;
-    int bi = 0;
-    while ((bi + 1) * (bi + 2) / 2 <= L) ++bi;
-    const int bj = L - bi * (bi + 1) / 2;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int n = bj * 64 + 2 * tx;
-    const double tn0 = (n < N) ? t[n] : 0.0, tn1 = (n + 1 < N) ? t[n + 1] : 0.0;
-    const int row0 = bi * 64;
-    auto eval = [&](double ti, double tj, bool diag) {
-        if constexpr (KID >= 0) return eval_kernel(KID, par, ti, tj, diag, aux);
-        else return eval_program(pg, ti, tj, diag);
-    };
-#pragma unroll 2
-    for (int i = 0; i < TR / 8; ++i) {
-        const int r = ty + 8 * i, m = row0 + r;
-        const double tm = (m < N) ? t[m] : 0.0;
-        double v0 = eval(tm, tn0, m == n);
-        double v1 = eval(tm, tn1, m == n + 1);
-        if (m == n || m == n + 1) {
-            double d = (m == n) ? v0 : v1;
-            if (nugget) d += nugget_val;
-            if constexpr (DIAG) { if (m < N) d += diag[m]; }
-            if (m == n) v0 = d; else v1 = d;
-        }
-        if (m >= N || n >= N) v0 = (m == n) ? 1.0 : 0.0;
-        if (m >= N || n + 1 >= N) v1 = (m == n + 1) ? 1.0 : 0.0;
-        *(double2*)(K + (size_t)m * ld + n) = make_double2(v0, v1);
-        if (K2) *(double2*)(K2 + (size_t)m * ld + n) = make_double2(v0, v1);
-        tile[r][2 * tx] = v0;
-        tile[r][2 * tx + 1] = v1;
-    }
-    if (bi == bj) return;
-    __syncthreads();
-    constexpr int CP = TR / 2;
-    for (int idx = threadIdx.x; idx < 64 * CP; idx += 256) {
-        const int c = idx / CP, rp = idx % CP;
-        const double2 v = make_double2(tile[2 * rp][c], tile[2 * rp + 1][c]);
-        *(double2*)(K + (size_t)(bj * 64 + c) * ld + row0 + 2 * rp) = v;
-        if (K2) *(double2*)(K2 + (size_t)(bj * 64 + c) * ld + row0 + 2 * rp) = v;
-    }
-}
-
+// 0.5 TB/s -- profiles/r05_batch512_first_kernel_stats.txt.)  K2s: a second copy of every matrix, or null.  DIAG
+// (gprn_predict_batch): matrix b also gets diags[b][m] on its diagonal, m < N, behind the nugget -- launch_fill's diag_add;
+// the instantiation without it is the kernel the ELBO batches always had.
 template <bool DIAG>
 __global__ __launch_bounds__(256)
 void k_fill_sym_batch(const FillProgram* __restrict__ pgs, const double* __restrict__ t, double* const* __restrict__ Ks,
@@ -466,23 +449,15 @@ void k_fill_sym_batch(const FillProgram* __restrict__ pgs, const double* __restr
 {
     __shared__ double tile[64][65];
     __shared__ FillProgram spg;
-    {
-        const int* src = reinterpret_cast<const int*>(pgs + blockIdx.y);
-        int* dst = reinterpret_cast<int*>(&spg);
-        for (int i = threadIdx.x; i < (int)(sizeof(FillProgram) / sizeof(int)); i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
+    program_to_lds(&spg, pgs + blockIdx.y);
     double* const K = Ks[blockIdx.y];
     double* const K2 = K2s ? K2s[blockIdx.y] : nullptr;
-    // (uniform per workgroup: a scalar branch)
-    const double* diag = nullptr;
-    if constexpr (DIAG) diag = diags[blockIdx.y];
-    const int kid = (spg.n_ops == 1 && spg.ops[0] == GPRN_OP_PUSH && spg.ops[2] == 0) ? spg.ops[1] : -1;
-    switch (kid) {
-    case GPRN_K_SE: fill_sym_batch_block<GPRN_K_SE, DIAG>(spg, t, K, K2, N, ld, tile, diag); break;
-    case GPRN_K_PERIODIC: fill_sym_batch_block<GPRN_K_PERIODIC, DIAG>(spg, t, K, K2, N, ld, tile, diag); break;
-    case GPRN_K_QP: fill_sym_batch_block<GPRN_K_QP, DIAG>(spg, t, K, K2, N, ld, tile, diag); break;
-    default: fill_sym_batch_block<-1, DIAG>(spg, t, K, K2, N, ld, tile, diag);
+    const double* const diag = DIAG ? diags[blockIdx.y] : nullptr;
+    switch (program_kid(spg)) {                  // (uniform per workgroup: a scalar branch)
+    case GPRN_K_SE: fill_sym_block<FillElem<GPRN_K_SE>>(spg, t, K, K2, N, ld, tile, diag); break;
+    case GPRN_K_PERIODIC: fill_sym_block<FillElem<GPRN_K_PERIODIC>>(spg, t, K, K2, N, ld, tile, diag); break;
+    case GPRN_K_QP: fill_sym_block<FillElem<GPRN_K_QP>>(spg, t, K, K2, N, ld, tile, diag); break;
+    default: fill_sym_block<FillElem<-1>>(spg, t, K, K2, N, ld, tile, diag);
     }
 }
 
@@ -507,34 +482,23 @@ bool fill_program_with(const KernelSpec& ks, const double* params, void* dst, do
 int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, double* const* d_K2s,
                       const double* const* d_diags)
 {
-    if (n_matrices <= 0) return GPRN_OK;
-    prof_begin(c, GPRN_T_FILL);
-    const int nb = c->ld / 64;
-    const dim3 grid(nb * (nb + 1) / 2, n_matrices);
-    if (d_diags)
-        hipLaunchKernelGGL(k_fill_sym_batch<true>, grid, dim3(256), 0, c->stream,
-                           (const FillProgram*)d_programs, c->d_time, d_Ks, d_K2s, c->N, c->ld, d_diags);
-    else
-        hipLaunchKernelGGL(k_fill_sym_batch<false>, grid, dim3(256), 0, c->stream,
-                           (const FillProgram*)d_programs, c->d_time, d_Ks, d_K2s, c->N, c->ld, d_diags);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
+    return launch_fill_batch_times(c, d_programs, d_Ks, n_matrices, c->d_time, c->N, c->ld, d_K2s, d_diags);
 }
 
-// the same kernel over any time vector t (N entries, device) into matrices of pitch ld (a multiple of 128; identity padding):
+// the same over any time vector t (N entries, device) into matrices of pitch ld (a multiple of 128; identity padding):
 // K** of many slots at the prediction times, each with its own program (gprn_elbocalc_batch_draws) -- launch_fill_times' relation
 // to launch_fill
-int launch_fill_batch_times(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* t, int N, int ld)
+int launch_fill_batch_times(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* t, int N, int ld,
+                            double* const* d_K2s, const double* const* d_diags)
 {
     if (n_matrices <= 0) return GPRN_OK;
-    prof_begin(c, GPRN_T_FILL);
     const int nb = ld / 64;
-    hipLaunchKernelGGL(k_fill_sym_batch<false>, dim3(nb * (nb + 1) / 2, n_matrices), dim3(256), 0, c->stream,
-                       (const FillProgram*)d_programs, t, d_Ks, (double* const*)nullptr, N, ld, (const double* const*)nullptr);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
+    return launched(c, GPRN_T_FILL, [&] {
+        with_flags([&](auto diag) {
+            hipLaunchKernelGGL(k_fill_sym_batch<diag>, dim3(nb * (nb + 1) / 2, n_matrices), dim3(256), 0, c->stream,
+                               (const FillProgram*)d_programs, t, d_Ks, d_K2s, N, ld, d_diags);
+        }, d_diags != nullptr);
+    });
 }
 
 // Rectangular cross-covariance K*[i][n] = k(t*_i, t_n), no nugget (_gp.py:50-61, meanfield.py:455-471),
@@ -544,174 +508,24 @@ int launch_fill_batch_times(gprn_ctx* c, const void* d_programs, double* const* 
 // sweep left it (zero on the rows of zero precision: zero columns, nothing is divided), and the nugget and WhiteNoise are
 // delta(t, t') -- in K* exactly where t*_i == t_n, so that at a data time the row is the row of the set-up's K.  The other
 // instantiation is the kernel prediction always had.
-template <int KID, bool POST = false>
-__global__ __launch_bounds__(256)
-void k_fill_rect(FillProgram pg, const double* __restrict__ ts, int ns, int ns_pad,
-                 const double* __restrict__ t, int N, int ld, double* __restrict__ Ks,
-                 double* __restrict__ kss, const double* __restrict__ s)
+//
+// The bodies of the single and the batched kernels of either form, from the program pg through the functor Elem: ROWS rows
+// of one column per thread, consecutive threads consecutive columns, so that a row goes out as 2 KiB contiguous.
+// grid (columns / 256, ceil(ns_pad / ROWS)[, matrices]).  Rows [ns, ns_pad) and columns [N, ld) are zeros.
+template <int ROWS, class Elem>
+__device__ __forceinline__ void fill_rect_rows(const FillProgram& pg, const double* __restrict__ ts, int ns,
+                                               int ns_pad, const double* __restrict__ t, int N, int ld,
+                                               double* __restrict__ Ks, double* __restrict__ kss)
 {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    constexpr int ROWS = (POST && KID < 0) ? 1 : 8;
-    const int i0 = blockIdx.y * ROWS;
-    if constexpr (POST) {
-        // ROWS rows per thread: 8 as in the other form, 1 for the postfix program (no scratch that way);
-        // column ld (one thread of an extra workgroup per row group) is k**: ONE call site of the element code for both, the
-        // delta terms wherever the two times are equal -- k** always
-        if (n > ld) return;
-        const bool is_kss = n == ld;
-        const double tn = (n < N) ? t[n] : 0.0;
-        const double sn = (n < N) ? s[n] : 0.0;
-#pragma unroll 1
-        for (int r = 0; r < ROWS; ++r) {
-            const int i = i0 + r;
-            if (i >= ns_pad) break;
-            double v = 0.0;
-            if (i < ns && (n < N || is_kss)) {
-                const double ti = ts[i], tj = is_kss ? ti : tn;
-                const bool same = ti == tj;
-                v = eval_any<KID>(pg, ti, tj, same);
-                if (same && pg.nugget) v += pg.nugget_val;
-            }
-            if (!is_kss) Ks[(size_t)i * ld + n] = v * sn;
-            else if (i < ns) kss[i] = v;
-        }
-    } else {
-        if (n >= ld) return;
-        const double tn = (n < N) ? t[n] : 0.0;
-#pragma unroll 1
-        for (int r = 0; r < 8; ++r) {
-            const int i = i0 + r;
-            if (i >= ns_pad) break;
-            double v = 0.0;
-            if (i < ns && n < N)
-                v = eval_any<KID>(pg, ts[i], tn, false);
-            Ks[(size_t)i * ld + n] = v;
-            if (n == 0 && i < ns) {
-                double d = eval_any<KID>(pg, ts[i], ts[i], true);
-                if (pg.nugget) d += pg.nugget_val;
-                kss[i] = d;
-            }
-        }
-    }
-}
-
-int launch_fill_rect(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
-                     int ns, int ns_pad, double* Ks, double* kss)
-{
-    FillProgram pg;
-    make_program(ks, nugget_val, pg);
-    prof_begin(c, GPRN_T_FILL);
-    dim3 grid((c->ld + 255) / 256, (ns_pad + 7) / 8);
-    switch (program_kid(pg)) {
-#define X(id) case id: hipLaunchKernelGGL(k_fill_rect<id>, grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, (const double*)nullptr); break;
-    GPRN_FOR_EACH_KID(X)
-#undef X
-    default: hipLaunchKernelGGL(k_fill_rect<-1>, grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, (const double*)nullptr);
-    }
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
-}
-
-int launch_fill_rect_post(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
-                          int ns, int ns_pad, const double* s, double* Ks, double* kss)
-{
-    FillProgram pg;
-    make_program(ks, nugget_val, pg);
-    prof_begin(c, GPRN_T_FILL);
-    dim3 grid((c->ld + 1 + 255) / 256, (ns_pad + 7) / 8);     // (column ld: k**)
-    switch (program_kid(pg)) {
-#define X(id) case id: hipLaunchKernelGGL((k_fill_rect<id, true>), grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, s); break;
-    GPRN_FOR_EACH_KID(X)
-#undef X
-    // (the program form: one row per thread -- with the row loop around the whole switch the compiler reserves scratch)
-    default:
-        if (ns_pad > 65535) {
-            prof_end(c);
-            c->err = "predict: the posterior form takes at most 65535 times per call for a composite kernel";
-            return GPRN_E_ARG;
-        }
-        grid.y = ns_pad; hipLaunchKernelGGL((k_fill_rect<-1, true>), grid, dim3(256), 0, c->stream, pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, s);
-    }
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
-}
-
-// The delta terms of K** between EQUAL prediction times (the posterior form): with t_i == t_j bit for bit, k(t_i, t_j) with its
-// delta terms IS the diagonal entry k(t_i, t_i) + nugget the fill has written, so entry (i, j) takes K[i][i] -- no kernel is
-// evaluated again, and the matrix stays symmetric (K[i][i] and K[j][j] are the same evaluation of the same arguments).
-// Reads the diagonal only, writes off-diagonal entries only.  grid (ld / 256, N)
-__global__ __launch_bounds__(256)
-void k_fill_coincide(double* __restrict__ K, const double* __restrict__ t, int N, int ld)
-{
-    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
-    if (j >= N || i >= N || i == j) return;
-    if (t[i] == t[j]) K[(size_t)i * ld + j] = K[(size_t)i * ld + i];
-}
-
-int launch_fill_coincide(gprn_ctx* c, double* K, const double* t, int N, int ld)
-{
-    prof_begin(c, GPRN_T_FILL);
-    hipLaunchKernelGGL(k_fill_coincide, dim3((N + 255) / 256, N), dim3(256), 0, c->stream, K, t, N, ld);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
-}
-
-// ... over a table of matrices at the same times (the draw pass of a batch: every slot's K**).  A separate kernel, the table
-// form of the one above: the one-matrix kernel keeps its code.  grid (ld / 256, N, matrices)
-__global__ __launch_bounds__(256)
-void k_fill_coincide_b(double* const* __restrict__ Ks, const double* __restrict__ t, int N, int ld)
-{
-    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
-    if (j >= N || i >= N || i == j) return;
-    double* const K = Ks[blockIdx.z];
-    if (t[i] == t[j]) K[(size_t)i * ld + j] = K[(size_t)i * ld + i];
-}
-
-int launch_fill_coincide_batch(gprn_ctx* c, double* const* d_Ks, int n_matrices, const double* t, int N, int ld)
-{
-    if (n_matrices <= 0) return GPRN_OK;
-    prof_begin(c, GPRN_T_FILL);
-    hipLaunchKernelGGL(k_fill_coincide_b, dim3((N + 255) / 256, N, n_matrices), dim3(256), 0, c->stream, d_Ks, t, N, ld);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
-}
-
-// ---- K* and k** of many matrices in one launch (gprn_predict_batch, midn.hip): matrix b of the launch has its own program
-// (device memory) and destinations Ks[b] (rows of pitch ld) and kss + b * kss_stride; the prediction times are the same for
-// all.  One workgroup = 32 rows x 256 columns of one matrix, a thread one column of them: a row goes out as 2 KiB
-// contiguous, as in k_fill_rect.  The program comes into LDS once per workgroup; SE, Periodic and QP take their parameters and
-// host-computed reciprocals into registers and run their own instruction stream, everything else goes through the postfix
-// program (fill_eval.h: the element code of k_fill_rect, so a matrix filled here has launch_fill_rect's bits).  Rows
-// [ns, ns_pad) and columns [N, ld) are zeros.
-#define GPRN_RECT_ROWS 32
-template <int KID>
-__device__ __forceinline__ void fill_rect_batch_rows(const FillProgram& pg, const double* __restrict__ ts, int ns, int ns_pad,
-                                                     const double* __restrict__ t, int N, int ld, double* __restrict__ Ks,
-                                                     double* __restrict__ kss)
-{
-    double par[4] = {0.0, 0.0, 0.0, 0.0}, aux[3] = {0.0, 0.0, 0.0};
-    if (KID >= 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) par[i] = pg.par[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) aux[i] = pg.aux[i];
-    }
+    const Elem eval(pg);
     const int nugget = pg.nugget;
     const double nugget_val = pg.nugget_val;
-    auto eval = [&](double ti, double tj, bool diag) {
-        if constexpr (KID >= 0) return eval_kernel(KID, par, ti, tj, diag, aux);
-        else return eval_program(pg, ti, tj, diag);
-    };
     const int n = blockIdx.x * 256 + threadIdx.x;
-    const int i0 = blockIdx.y * GPRN_RECT_ROWS;
+    const int i0 = blockIdx.y * ROWS;
     if (n >= ld) return;
     const double tn = (n < N) ? t[n] : 0.0;
 #pragma unroll 1
-    for (int r = 0; r < GPRN_RECT_ROWS; ++r) {
+    for (int r = 0; r < ROWS; ++r) {
         const int i = i0 + r;
         if (i >= ns_pad) break;
         double v = 0.0;
@@ -725,77 +539,17 @@ __device__ __forceinline__ void fill_rect_batch_rows(const FillProgram& pg, cons
     }
 }
 
-// grid (ceil(ld / 256), ceil(ns_pad / 32), matrices)
-__global__ __launch_bounds__(256)
-void k_fill_rect_batch(const FillProgram* __restrict__ pgs, const double* __restrict__ ts, int ns, int ns_pad,
-                       const double* __restrict__ t, int N, int ld, double* const* __restrict__ Kss,
-                       double* __restrict__ kss, size_t kss_stride)
+// column ld (one thread of an extra workgroup per row group) is k**: ONE call site of the element code for both, the delta
+// terms wherever the two times are equal -- k** always.  s: the matrix's own sqrt(d), ld entries
+template <int ROWS, class Elem>
+__device__ __forceinline__ void fill_rect_rows_post(const FillProgram& pg, const double* __restrict__ ts,
+                                                    int ns, int ns_pad, const double* __restrict__ t, int N, int ld,
+                                                    const double* __restrict__ s, double* __restrict__ Ks,
+                                                    double* __restrict__ kss)
 {
-    __shared__ FillProgram spg;
-    {
-        const int* src = reinterpret_cast<const int*>(pgs + blockIdx.z);
-        int* dst = reinterpret_cast<int*>(&spg);
-        for (int i = threadIdx.x; i < (int)(sizeof(FillProgram) / sizeof(int)); i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    double* const Ks = Kss[blockIdx.z];
-    double* const kd = kss + (size_t)blockIdx.z * kss_stride;
-    // (uniform per workgroup: a scalar branch)
-    const int kid = (spg.n_ops == 1 && spg.ops[0] == GPRN_OP_PUSH && spg.ops[2] == 0) ? spg.ops[1] : -1;
-    switch (kid) {
-    case GPRN_K_SE: fill_rect_batch_rows<GPRN_K_SE>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
-    case GPRN_K_PERIODIC: fill_rect_batch_rows<GPRN_K_PERIODIC>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
-    case GPRN_K_QP: fill_rect_batch_rows<GPRN_K_QP>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
-    default: fill_rect_batch_rows<-1>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd);
-    }
-}
-
-// ns <= ns_pad <= ld rows (ns_pad a multiple of 128) of n_matrices matrices: K* into d_Ks[i], k** into kss + i * kss_stride
-int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* d_tstar,
-                           int ns, int ns_pad, double* kss, size_t kss_stride)
-{
-    if (n_matrices <= 0) return GPRN_OK;
-    prof_begin(c, GPRN_T_FILL);
-    hipLaunchKernelGGL(k_fill_rect_batch, dim3((c->ld + 255) / 256, (ns_pad + GPRN_RECT_ROWS - 1) / GPRN_RECT_ROWS, n_matrices),
-                       dim3(256), 0, c->stream, (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time,
-                       c->N, c->ld, d_Ks, kss, kss_stride);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
-}
-
-// ---- ... in the POSTERIOR form (gprn_elbocalc_batch_predict: the prediction pass behind a chunk's loop, batch_tail.hip
-// batch_pred_pass): K* diag(s) and k** of many matrices, matrix z with its own program and its own s = sqrt(d) at s + z * ld.
-// The delta handling of k_fill_rect<KID, true>: the nugget and WhiteNoise apply in K* exactly where t*_i == t_n as doubles,
-// in k** always; column ld of a row group (one thread of an extra workgroup) is k**, so the element code has ONE call site
-// for both.  A point of zero precision has s = 0: a zero column, nothing is divided.  Rows [ns, ns_pad) and columns [N, ld)
-// are zeros.  A thread one column, consecutive threads consecutive columns: a row goes out as 2 KiB contiguous.
-// Two instruction streams in two kernels, so that neither carries the other's registers (k_fill_rect_batch, which holds all
-// four behind one switch, spills): PROGRAM = false -- the one-kernel SE / Periodic / QP programs, parameters and host-computed
-// reciprocals in registers behind the uniform branch, GPRN_RECT_ROWS rows per thread; PROGRAM = true -- everything else
-// through the postfix program, ONE row per thread as k_fill_rect<-1, true> takes it (with a row loop around the program's
-// stack the compiler reserves scratch).  A workgroup whose matrix belongs to the other kernel returns at once (uniform: it
-// reads the program's head through scalar loads); the host launches only the kernels its programs need.  The program comes
-// into LDS once per workgroup.
-template <int KID, int ROWS>
-__device__ __forceinline__ void fill_rect_batch_rows_post(const FillProgram& pg, const double* __restrict__ ts, int ns, int ns_pad,
-                                                          const double* __restrict__ t, int N, int ld,
-                                                          const double* __restrict__ s, double* __restrict__ Ks,
-                                                          double* __restrict__ kss)
-{
-    double par[4] = {0.0, 0.0, 0.0, 0.0}, aux[3] = {0.0, 0.0, 0.0};
-    if (KID >= 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) par[i] = pg.par[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) aux[i] = pg.aux[i];
-    }
+    const Elem eval(pg);
     const int nugget = pg.nugget;
     const double nugget_val = pg.nugget_val;
-    auto eval = [&](double ti, double tj, bool diag) {
-        if constexpr (KID >= 0) return eval_kernel(KID, par, ti, tj, diag, aux);
-        else return eval_program(pg, ti, tj, diag);
-    };
     const int n = blockIdx.x * 256 + threadIdx.x;
     const int i0 = blockIdx.y * ROWS;
     if (n > ld) return;
@@ -818,13 +572,143 @@ __device__ __forceinline__ void fill_rect_batch_rows_post(const FillProgram& pg,
     }
 }
 
-// does this program run on the register form (a single SE, Periodic or QP kernel)?
-static __host__ __device__ __forceinline__ bool program_in_registers(const FillProgram& pg)
+// rows per thread of a single launch: 8, but 1 for the postfix program in the posterior form (with the row loop around the
+// program's stack the compiler reserves scratch)
+constexpr int rect_rows(int kid, bool post) { return (post && kid < 0) ? 1 : 8; }
+
+template <int KID, bool POST = false>
+__global__ __launch_bounds__(256)
+void k_fill_rect(FillProgram pg, const double* __restrict__ ts, int ns, int ns_pad,
+                 const double* __restrict__ t, int N, int ld, double* __restrict__ Ks,
+                 double* __restrict__ kss, const double* __restrict__ s)
 {
-    if (!(pg.n_ops == 1 && pg.ops[0] == GPRN_OP_PUSH && pg.ops[2] == 0)) return false;
-    return pg.ops[1] == GPRN_K_SE || pg.ops[1] == GPRN_K_PERIODIC || pg.ops[1] == GPRN_K_QP;
+    constexpr int ROWS = rect_rows(KID, POST);
+    if constexpr (POST) fill_rect_rows_post<ROWS, ArgElem<KID>>(pg, ts, ns, ns_pad, t, N, ld, s, Ks, kss);
+    else fill_rect_rows<ROWS, ArgElem<KID>>(pg, ts, ns, ns_pad, t, N, ld, Ks, kss);
 }
 
+// both forms of the single launch; s: the posterior form's sqrt(d), not read by the reference form
+static int fill_rect_form(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar, int ns, int ns_pad,
+                          bool posterior, const double* s, double* Ks, double* kss)
+{
+    FillProgram pg;
+    make_program(ks, nugget_val, pg);
+    return launched(c, GPRN_T_FILL, [&] {
+        int rc = GPRN_OK;
+        with_kid(program_kid(pg), [&](auto kid) {
+            with_flags([&](auto post) {
+                constexpr int KID = decltype(kid)::value, ROWS = rect_rows(KID, decltype(post)::value);
+                const int columns = c->ld + (post ? 1 : 0);            // (column ld: k**)
+                const dim3 grid((columns + 255) / 256, (ns_pad + ROWS - 1) / ROWS);
+                if (ROWS == 1 && ns_pad > 65535) {
+                    c->err = "predict: the posterior form takes at most 65535 times per call for a composite kernel";
+                    rc = GPRN_E_ARG;
+                    return;
+                }
+                hipLaunchKernelGGL((k_fill_rect<KID, post>), grid, dim3(256), 0, c->stream,
+                                   pg, d_tstar, ns, ns_pad, c->d_time, c->N, c->ld, Ks, kss, s);
+            }, posterior);
+        });
+        return rc;
+    });
+}
+
+int launch_fill_rect(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
+                     int ns, int ns_pad, double* Ks, double* kss)
+{
+    return fill_rect_form(c, ks, nugget_val, d_tstar, ns, ns_pad, false, nullptr, Ks, kss);
+}
+
+int launch_fill_rect_post(gprn_ctx* c, const KernelSpec& ks, double nugget_val, const double* d_tstar,
+                          int ns, int ns_pad, const double* s, double* Ks, double* kss)
+{
+    return fill_rect_form(c, ks, nugget_val, d_tstar, ns, ns_pad, true, s, Ks, kss);
+}
+
+// The delta terms of K** between EQUAL prediction times (the posterior form): with t_i == t_j bit for bit, k(t_i, t_j) with its
+// delta terms IS the diagonal entry k(t_i, t_i) + nugget the fill has written, so entry (i, j) takes K[i][i] -- no kernel is
+// evaluated again, and the matrix stays symmetric (K[i][i] and K[j][j] are the same evaluation of the same arguments).
+// Reads the diagonal only, writes off-diagonal entries only.  grid (ld / 256, N[, matrices])
+__device__ __forceinline__ void fill_coincide_row(double* __restrict__ K, const double* __restrict__ t, int N, int ld)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (j >= N || i >= N || i == j) return;
+    if (t[i] == t[j]) K[(size_t)i * ld + j] = K[(size_t)i * ld + i];
+}
+
+__global__ __launch_bounds__(256)
+void k_fill_coincide(double* __restrict__ K, const double* __restrict__ t, int N, int ld)
+{
+    fill_coincide_row(K, t, N, ld);
+}
+
+// ... over a table of matrices at the same times (the draw pass of a batch: every slot's K**)
+__global__ __launch_bounds__(256)
+void k_fill_coincide_b(double* const* __restrict__ Ks, const double* __restrict__ t, int N, int ld)
+{
+    fill_coincide_row(Ks[blockIdx.z], t, N, ld);
+}
+
+int launch_fill_coincide(gprn_ctx* c, double* K, const double* t, int N, int ld)
+{
+    return launched(c, GPRN_T_FILL, [&] {
+        hipLaunchKernelGGL(k_fill_coincide, dim3((N + 255) / 256, N), dim3(256), 0, c->stream, K, t, N, ld);
+    });
+}
+
+int launch_fill_coincide_batch(gprn_ctx* c, double* const* d_Ks, int n_matrices, const double* t, int N, int ld)
+{
+    if (n_matrices <= 0) return GPRN_OK;
+    return launched(c, GPRN_T_FILL, [&] {
+        hipLaunchKernelGGL(k_fill_coincide_b, dim3((N + 255) / 256, N, n_matrices), dim3(256), 0, c->stream, d_Ks, t, N, ld);
+    });
+}
+
+// ---- K* and k** of many matrices in one launch (gprn_predict_batch, midn.hip): matrix b of the launch has its own program
+// (device memory) and destinations Ks[b] (rows of pitch ld) and kss + b * kss_stride; the prediction times are the same for
+// all.  One workgroup = 32 rows x 256 columns of one matrix: fill_rect_rows on a program that comes into LDS once per
+// workgroup, with FillElem's instruction stream per kind of program, so that a matrix filled here has launch_fill_rect's bits.
+// grid (ceil(ld / 256), ceil(ns_pad / 32), matrices)
+#define GPRN_RECT_ROWS 32
+__global__ __launch_bounds__(256)
+void k_fill_rect_batch(const FillProgram* __restrict__ pgs, const double* __restrict__ ts, int ns, int ns_pad,
+                       const double* __restrict__ t, int N, int ld, double* const* __restrict__ Kss,
+                       double* __restrict__ kss, size_t kss_stride)
+{
+    __shared__ FillProgram spg;
+    program_to_lds(&spg, pgs + blockIdx.z);
+    double* const Ks = Kss[blockIdx.z];
+    double* const kd = kss + (size_t)blockIdx.z * kss_stride;
+    switch (program_kid(spg)) {                  // (uniform per workgroup: a scalar branch)
+    case GPRN_K_SE: fill_rect_rows<GPRN_RECT_ROWS, FillElem<GPRN_K_SE>>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
+    case GPRN_K_PERIODIC: fill_rect_rows<GPRN_RECT_ROWS, FillElem<GPRN_K_PERIODIC>>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
+    case GPRN_K_QP: fill_rect_rows<GPRN_RECT_ROWS, FillElem<GPRN_K_QP>>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd); break;
+    default: fill_rect_rows<GPRN_RECT_ROWS, FillElem<-1>>(spg, ts, ns, ns_pad, t, N, ld, Ks, kd);
+    }
+}
+
+// ns <= ns_pad <= ld rows (ns_pad a multiple of 128) of n_matrices matrices: K* into d_Ks[i], k** into kss + i * kss_stride
+int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* d_tstar,
+                           int ns, int ns_pad, double* kss, size_t kss_stride)
+{
+    if (n_matrices <= 0) return GPRN_OK;
+    return launched(c, GPRN_T_FILL, [&] {
+        hipLaunchKernelGGL(k_fill_rect_batch, dim3((c->ld + 255) / 256, (ns_pad + GPRN_RECT_ROWS - 1) / GPRN_RECT_ROWS, n_matrices),
+                           dim3(256), 0, c->stream, (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time,
+                           c->N, c->ld, d_Ks, kss, kss_stride);
+    });
+}
+
+// ---- ... in the POSTERIOR form (gprn_elbocalc_batch_predict: the prediction pass behind a chunk's loop, batch_tail.hip
+// batch_pred_pass): K* diag(s) and k** of many matrices, matrix z with its own program and its own s = sqrt(d) at s + z * ld.
+// fill_rect_rows_post, the body of k_fill_rect<KID, true>: the nugget and WhiteNoise apply in K* exactly where t*_i == t_n as
+// doubles, in k** always.  A point of zero precision has s = 0: a zero column, nothing is divided.
+// Two instruction streams in two kernels, so that neither carries the other's registers: PROGRAM = false -- the one-kernel
+// SE / Periodic / QP programs, parameters and host-computed reciprocals in registers behind the uniform branch,
+// GPRN_RECT_ROWS rows per thread; PROGRAM = true -- everything else through the postfix program, ONE row per thread as
+// k_fill_rect<-1, true> takes it (with a row loop around the program's stack the compiler reserves scratch).  A workgroup
+// whose matrix belongs to the other kernel returns at once (uniform: it reads the program's head through scalar loads); the
+// host launches only the kernels its programs need.  The program comes into LDS once per workgroup.
 // grid (ceil((ld + 1) / 256), ceil(ns_pad / rows per thread), matrices)
 template <bool PROGRAM>
 __global__ __launch_bounds__(256)
@@ -834,21 +718,16 @@ void k_fill_rect_batch_post(const FillProgram* __restrict__ pgs, const double* _
 {
     if (program_in_registers(pgs[blockIdx.z]) == PROGRAM) return;     // (the other kernel's matrix: uniform)
     __shared__ FillProgram spg;
-    {
-        const int* src = reinterpret_cast<const int*>(pgs + blockIdx.z);
-        int* dst = reinterpret_cast<int*>(&spg);
-        for (int i = threadIdx.x; i < (int)(sizeof(FillProgram) / sizeof(int)); i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
+    program_to_lds(&spg, pgs + blockIdx.z);
     double* const Ks = Kss[blockIdx.z];
     double* const kd = kss + (size_t)blockIdx.z * kss_stride;
     const double* const sz = s + (size_t)blockIdx.z * ld;
-    if constexpr (PROGRAM) fill_rect_batch_rows_post<-1, 1>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd);
+    if constexpr (PROGRAM) fill_rect_rows_post<1, FillElem<-1>>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd);
     else
         switch (spg.ops[1]) {                    // (uniform per workgroup: a scalar branch)
-        case GPRN_K_SE: fill_rect_batch_rows_post<GPRN_K_SE, GPRN_RECT_ROWS>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd); break;
-        case GPRN_K_PERIODIC: fill_rect_batch_rows_post<GPRN_K_PERIODIC, GPRN_RECT_ROWS>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd); break;
-        default: fill_rect_batch_rows_post<GPRN_K_QP, GPRN_RECT_ROWS>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd);
+        case GPRN_K_SE: fill_rect_rows_post<GPRN_RECT_ROWS, FillElem<GPRN_K_SE>>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd); break;
+        case GPRN_K_PERIODIC: fill_rect_rows_post<GPRN_RECT_ROWS, FillElem<GPRN_K_PERIODIC>>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd); break;
+        default: fill_rect_rows_post<GPRN_RECT_ROWS, FillElem<GPRN_K_QP>>(spg, ts, ns, ns_pad, t, N, ld, sz, Ks, kd);
         }
 }
 
@@ -864,17 +743,15 @@ int launch_fill_rect_batch_post(gprn_ctx* c, const void* d_programs, const char*
         memcpy(&pg, h_programs + (size_t)i * sizeof(FillProgram), sizeof(pg));
         any[program_in_registers(pg) ? 0 : 1] = true;
     }
-    prof_begin(c, GPRN_T_FILL);
     const unsigned gx = (c->ld + 1 + 255) / 256;             // (column ld: k**)
-    if (any[0])
-        hipLaunchKernelGGL(k_fill_rect_batch_post<false>, dim3(gx, (ns_pad + GPRN_RECT_ROWS - 1) / GPRN_RECT_ROWS, n_matrices),
-                           dim3(256), 0, c->stream, (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time,
-                           c->N, c->ld, s, d_Ks, kss, kss_stride);
-    if (any[1])
-        hipLaunchKernelGGL(k_fill_rect_batch_post<true>, dim3(gx, ns_pad, n_matrices), dim3(256), 0, c->stream,
-                           (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time, c->N, c->ld, s, d_Ks,
-                           kss, kss_stride);
-    prof_end(c);
-    HIP_TRY(c, hipGetLastError());
-    return GPRN_OK;
+    return launched(c, GPRN_T_FILL, [&] {
+        if (any[0])
+            hipLaunchKernelGGL(k_fill_rect_batch_post<false>, dim3(gx, (ns_pad + GPRN_RECT_ROWS - 1) / GPRN_RECT_ROWS, n_matrices),
+                               dim3(256), 0, c->stream, (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time,
+                               c->N, c->ld, s, d_Ks, kss, kss_stride);
+        if (any[1])
+            hipLaunchKernelGGL(k_fill_rect_batch_post<true>, dim3(gx, ns_pad, n_matrices), dim3(256), 0, c->stream,
+                               (const FillProgram*)d_programs, d_tstar, ns, ns_pad, (const double*)c->d_time, c->N, c->ld, s, d_Ks,
+                               kss, kss_stride);
+    });
 }

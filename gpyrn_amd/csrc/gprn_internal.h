@@ -400,7 +400,8 @@ int launch_fill_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, 
                       const double* const* d_diags = nullptr);   // per matrix: N values added to its diagonal, or null
 // ... over a time vector of the caller's (N entries, device) into matrices of pitch ld = 128 k (K** of many slots at the
 // prediction times), and launch_fill_coincide over the same table
-int launch_fill_batch_times(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* t, int N, int ld);
+int launch_fill_batch_times(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* t, int N, int ld,
+                            double* const* d_K2s = nullptr, const double* const* d_diags = nullptr);
 int launch_fill_coincide_batch(gprn_ctx* c, double* const* d_Ks, int n_matrices, const double* t, int N, int ld);
 // K* (ns rows, zero-padded to ns_pad <= ld) and k** of many matrices at the same prediction times in one launch
 int launch_fill_rect_batch(gprn_ctx* c, const void* d_programs, double* const* d_Ks, int n_matrices, const double* d_tstar,

@@ -21,7 +21,7 @@
 // grad_batch_pass runs the same steps over the evaluations of a batch's chunk (gprn_elbocalc_batch_grad): slots = evaluations
 // x latent GPs in every launch's batch dimension, so the number of launches does not depend on the number of evaluations.
 #include "api_internal.h"
-#include "fill_eval.h"
+#include "fill_shared.h"
 #include "grad_elem.h"
 #include "dk_eval.h"
 
@@ -171,11 +171,8 @@ void k_grad_contract_b(const GradSlot* __restrict__ slots, const double* __restr
     }
     __syncthreads();
     if (sl.mode != MODE) return;                       // (uniform: another instantiation's slot, or no entry at all)
-    // lower-triangular block index -> (bi, bj), bi >= bj
-    int bi = (int)((sqrt(8.0 * blk + 1.0) - 1.0) * 0.5);
-    while ((bi + 1) * (bi + 2) / 2 <= blk) ++bi;
-    while (bi * (bi + 1) / 2 > blk) --bi;
-    const int bj = blk - bi * (bi + 1) / 2;
+    int bi, bj;
+    lower_block(blk, bi, bj);
     if (tid < 128) {
         const int side = tid >> 6, k = tid & 63, idx = (side ? bj : bi) * 64 + k;
         const bool in = idx < N;
@@ -183,14 +180,9 @@ void k_grad_contract_b(const GradSlot* __restrict__ slots, const double* __restr
         ss[side][k] = in ? sl.s[idx] : 0.0;
         sa[side][k] = in ? sl.a[idx] : 0.0;
     }
-    if (MODE == 1) {
-        const int* src = reinterpret_cast<const int*>(&slots[g].pg);
-        for (int k = 0; k < 4; ++k) {
-            int* dst = reinterpret_cast<int*>(&spg[k]);
-            for (int i = tid; i < (int)(sizeof(FillProgram) / sizeof(int)); i += 256) dst[i] = src[i];
-        }
-    }
-    __syncthreads();
+    // ONE barrier on either branch (program_to_lds ends with its own), which also publishes st, ss and sa written above
+    if (MODE == 1) program_to_lds(spg, &slots[g].pg, 4);
+    else __syncthreads();
     const int tx = tid & 31, ty = tid >> 5;
     const int n = bj * 64 + 2 * tx;
     const double tn0 = st[1][2 * tx], tn1 = st[1][2 * tx + 1];
